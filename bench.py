@@ -8,7 +8,10 @@ GPU and step.  N > 1: one process per GPU (RCCL), clips are independent (no data
 `python bench.py --gpus N` without WORLD_SIZE in the environment starts the N ranks itself (torch.distributed.run,
 from a parent that never touches the GPU) and relays rank 0's line; `n_gpus` is what torch.distributed saw.
 
-One JSON line (rank 0) with the contract fields plus
+A plain run sets up, warms up, times exactly --steps steps and prints one JSON line (rank 0) with the contract fields
+(metric, value, unit, higher_is_better, dtype, ms_per_step, ...).  `--dump-outputs DIR` then also writes what the timed
+path returned in its last step as DIR/<name>.npy (float32; inputs are seeded, so two builds compare output for output).
+Everything else is measured only with `--full`, which adds to the line
   max_abs_err_vs_oracle  the headline dtype's output against the CPU restatement of the reference on ALL clips of the
                          batch (the reference's tolerance is 1e-4: bf16 does not meet it, it is the throughput mode);
   parity_mode            the modes that DO meet 1e-4, each timed the same way: "f16x2" (contractions on fp16 split
@@ -22,7 +25,8 @@ One JSON line (rank 0) with the contract fields plus
   cpu_baseline           oracle/torch_cpu.py (torch-CPU restatement of the reference's fp32 path, pinned to the same
                          reference goldens as the numpy oracle) on this host's cores: median of 5 after 2 warm-ups.
 `--mode train` times the configs[2] step instead (local batch 32 x 2 windows: fwd + bwd + bucketed gradient all-reduce +
-fused Adam) and adds allreduce_ms / overlap_frac.
+fused Adam); with `--full` it adds allreduce_ms / overlap_frac (N > 1), roofline, cpu_baseline and the one-GPU exchange
+rehearsal.
 """
 from __future__ import annotations
 
@@ -44,6 +48,7 @@ import torch  # noqa: E402  (importing torch does not initialise the GPU)
 PEAK_MFMA_TFLOPS = 2500.0   # dense bf16 / f16 MFMA, MI355X_MICROARCH.md "Chip-level parameters"
 PEAK_F32_TFLOPS = 157.3     # v_mfma_f32_16x16x4_f32 (same table)
 PEAK_HBM_GBS = 8000.0
+DUMP_LIMIT_BYTES = 60_000_000  # --dump-outputs: under 64 MB in all, .npy headers included
 FLOP_PER_FRAME = 0.6512e9   # MSMD.forward from raw audio = 65.12 GFLOP per 100-frame clip
 DENOISER_FLOP = 7.886e9     # per call and sequence
 TRAIN_FLOP_PER_SAMPLE = 317e9
@@ -82,6 +87,21 @@ def graphed_step(model, b):
     run(motion_feat=b["motion"], audio=b["audio"], shape_feat=b["shape"], style_feat=b["style"], time_step=ts,
         indicator=b["indicator"], eps=b["eps"])
     return lambda: run()
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: write every array as directory/<name>.npy in float32.  Above DUMP_LIMIT_BYTES in all, every
+    batch-major array keeps the same fixed, seeded sample of batch rows (sorted), so dumps of two builds still line up."""
+    arrays = {k: v.detach().float().contiguous().cpu().numpy() for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        B = max(v.shape[0] for v in arrays.values() if v.ndim)
+        rows = np.sort(np.random.default_rng(0).choice(B, max(1, B * DUMP_LIMIT_BYTES // total), replace=False))
+        arrays = {k: v[rows] if v.ndim and v.shape[0] == B else v for k, v in arrays.items()}
+        print(f"[bench] --dump-outputs: {total} bytes in all, kept {len(rows)} of {B} batch rows (seed 0)", file=sys.stderr)
+    os.makedirs(directory, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(directory, k + ".npy"), v)
 
 
 # ----------------------------------------------------------------------------------------------- roofline
@@ -787,14 +807,15 @@ def run_forward(a, rank, world, device):
                     if os.environ.get("BENCH_DEBUG"):
                         print(f"[bench] mode {mode}: streams {S}, concurrent == serial: {ok}", file=sys.stderr)
                     if ok:
-                        single_ms = dp.timed_steps(runs[0], a.steps, a.warmup, sync=torch.cuda.synchronize, device=device) / a.steps * 1e3
+                        if a.full:
+                            single_ms = dp.timed_steps(runs[0], a.steps, a.warmup, sync=torch.cuda.synchronize, device=device) / a.steps * 1e3
                         state = {"i": 0}
 
                         def run():
                             i = state["i"]
                             state["i"] = (i + 1) % S
                             with torch.cuda.stream(streams[i]):
-                                runs[i]()
+                                return runs[i]()
                         launch = (f"{S} steps in flight: hipGraph replays issued round-robin on {S} HIP streams, one captured graph + "
                                   f"input buffers + batch per stream (each batch written once into its captured buffers; concurrent replays verified "
                                   f"bit-equal to one-at-a-time replays before timing)")
@@ -803,8 +824,15 @@ def run_forward(a, rank, world, device):
             except Exception as e:
                 print(f"[bench] hipGraph capture unavailable ({type(e).__name__}: {e}); timing eager launches", file=sys.stderr)
                 torch.cuda.synchronize()
-        elapsed = dp.timed_steps(run, a.steps, a.warmup, sync=torch.cuda.synchronize, device=device)
-        if launch != "eager" and max(1, a.streams) == 1:
+        last = {}
+
+        def kept():
+            last["out"] = run()
+        elapsed = dp.timed_steps(kept, a.steps, a.warmup, sync=torch.cuda.synchronize, device=device)
+        if a.dump_outputs and mode == a.dtype and rank == 0:
+            # MSMD.forward's four returns; written before any further replay overwrites the graph's output buffers
+            dump_outputs(a.dump_outputs, dict(zip(("eps", "target", "motion_feat", "audio_feat"), last["out"])))
+        if a.full and launch != "eager" and max(1, a.streams) == 1:
             # the object that was TIMED (the hipGraph replay), not only the eager step before it, goes to the checker
             o = run()
             torch.cuda.synchronize()
@@ -832,6 +860,8 @@ def run_forward(a, rank, world, device):
     }
     if single_ms is not None:
         out["single_stream_ms_per_step"] = round(single_ms, 3)   # one step at a time (latency of a step)
+    if not a.full:
+        return out
     if n > 1:
         if not a.no_roofline:     # rank 0's dominant kernel (no collective inside: the other ranks wait at the closing barrier)
             out["roofline"] = roofline_leg(model, b, a.dtype)
@@ -926,9 +956,15 @@ def run_train(a, rank, world, device):
         tr.capture_all(batch)
     run = lambda: tr.step(batch, it=1)
     warm = max(a.warmup, 2)
-    elapsed = dp.timed_steps(run, a.steps, warm, sync=torch.cuda.synchronize, device=device)
+    last = {}
+
+    def kept():
+        last["out"] = run()
+    elapsed = dp.timed_steps(kept, a.steps, warm, sync=torch.cuda.synchronize, device=device)
+    if a.dump_outputs and rank == 0:     # the step's detached loss tensors
+        dump_outputs(a.dump_outputs, {k: torch.as_tensor(v) for k, v in last["out"].items()})
     extra = {}
-    if world > 1:
+    if world > 1 and a.full:
         # the exchange alone (all buckets, nothing to overlap with) and the step without any exchange
         ar = dp.timed_steps(tr.reducer.exchange_only, 5, 2, sync=torch.cuda.synchronize, device=device) / 5
         tr.reducer.mute = True
@@ -939,7 +975,7 @@ def run_train(a, rank, world, device):
                      overlap_frac=round(max(0.0, min(1.0, 1.0 - exposed / ar)), 3) if ar > 0 else None,
                      gradient_bytes=int(tr.reducer.arena.numel() * 4), buckets=len(tr.reducer.buckets))
     roof = None
-    if not a.no_roofline:
+    if a.full and not a.no_roofline:
         # dominant kernel of the iteration (the 128 x 128 forward / data-gradient GEMM: ~27 % of the step's GPU time),
         # per-launch HIP events on an EAGER iteration of the same trainer (the timed one replays hipGraphs)
         was = (tr.use_graph, tr.direct_grad)
@@ -967,6 +1003,8 @@ def run_train(a, rank, world, device):
         roof["note"] = ("dominant kernel of the training iteration = the forward / data-gradient GEMM (msmd_gemm; the weight-gradient "
                         "product is msmd_gemm_tn); launches traced on one eager iteration. " + roof["note"])
         out["roofline"] = roof
+    if not a.full:
+        return out
     if world == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_train_baseline()
     if world == 1 and not a.no_exchange_rehearsal:
@@ -1057,17 +1095,23 @@ def main():
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16", "fp32", "f16x2"])
     ap.add_argument("--mode", default="forward", choices=["forward", "train"])
-    ap.add_argument("--legs", default="all", help="all | none | comma-separated subset of sampler,lbs,train,hubert")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the f16x2 / fp32 parity-mode timings")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure and check everything else: CPU baseline and the error against the "
+                         "oracle, roofline, parity modes, two-streams leg, the other BASELINE legs (the options below select "
+                         "among them); without it a run times the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step as DIR/<name>.npy (float32, at most 64 MB)")
+    ap.add_argument("--legs", default="all", help="--full: all | none | comma-separated subset of sampler,lbs,train,hubert")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the oracle comparison")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: skip the roofline legs")
+    ap.add_argument("--no-parity", action="store_true", help="--full: skip the f16x2 / fp32 parity-mode timings")
     ap.add_argument("--bucket-dtype", default="fp32", choices=["fp32", "bf16", "fp16"],
                     help="train mode: dtype the gradient buckets are summed in over RCCL (16-bit = staged copy, half the bytes)")
     ap.add_argument("--no-exchange-rehearsal", action="store_true",
-                    help="train mode, one GPU: skip the leg that runs the step with a one-rank RCCL communicator on every bucket")
+                    help="--full, train mode, one GPU: skip the leg that runs the step with a one-rank RCCL communicator on every bucket")
     ap.add_argument("--eager", action="store_true", help="launch every kernel from the host instead of hipGraph replays")
     ap.add_argument("--no-two-streams-leg", dest="two_streams_leg", action="store_false",
-                    help="skip the extra leg that times two steps in flight (verified per step)")
+                    help="--full: skip the extra leg that times two steps in flight (verified per step)")
     ap.add_argument("--tune", default="", help="developer (experimental library only): comma-separated key=value pairs for msmd_exp_set_tuning")
     ap.add_argument("--streams", type=int, default=1,
                     help="forward mode: steps in flight (one hipGraph + batch per HIP stream; every concurrent replay is checked "
@@ -1076,6 +1120,8 @@ def main():
                          "under a second stream were packed-fp32 VALU results, not stream ordering: DESIGN.md 5c; the library is built "
                          "without packed fp32 since)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         sys.exit(spawn(a, sys.argv[1:]))

@@ -739,7 +739,7 @@ def test_bench_two_ranks_rehearsal_on_one_gpu():
     for mode, port in (("forward", "29531"), ("train", "29532")):
         r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                             "--master-addr", "127.0.0.1", "--master-port", port, os.path.join(root, "bench.py"), "--gpus", "2",
-                            "--steps", "2", "--warmup", "1", "--mode", mode, "--no-cpu-baseline"],
+                            "--steps", "2", "--warmup", "1", "--mode", mode, "--full", "--no-cpu-baseline"],
                            capture_output=True, text=True, env=env, timeout=900, cwd=root)
         assert r.returncode == 0, (mode, r.stderr[-3000:])
         lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
@@ -762,7 +762,7 @@ def test_bench_eight_ranks_rehearsal_on_one_gpu():
     env = dict(os.environ, MSMD_DIST_BACKEND="gloo", MSMD_ONE_DEVICE="1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8",
                         "--master-addr", "127.0.0.1", "--master-port", "29533", os.path.join(root, "bench.py"), "--gpus", "8",
-                        "--steps", "2", "--warmup", "1", "--mode", "train", "--batch", "8", "--no-cpu-baseline"],
+                        "--steps", "2", "--warmup", "1", "--mode", "train", "--batch", "8", "--full", "--no-cpu-baseline"],
                        capture_output=True, text=True, env=env, timeout=1500, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]

@@ -4,7 +4,7 @@ cd ${GRAFT_REPO_ROOT:-/root/repo}
 A=$1; B=$2
 for rep in 1 2; do
   for lib in $A $B; do
-    MSMD_LIB=$lib MSMD_LIB_ALLOW_MISSING=1 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-parity --no-two-streams-leg --no-roofline --legs lbs,rot 2>/dev/null |
+    MSMD_LIB=$lib MSMD_LIB_ALLOW_MISSING=1 python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-parity --no-two-streams-leg --no-roofline --legs lbs,rot 2>/dev/null |
       python -c "
 import json,sys
 d=json.loads(sys.stdin.read())['legs']

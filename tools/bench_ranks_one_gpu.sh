@@ -11,7 +11,7 @@ export MSMD_DIST_BACKEND=gloo MSMD_ONE_DEVICE=1
 for mode in $MODES; do
   SECONDS=0
   timeout 3000 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port 29541 \
-    bench.py --gpus $N --steps 2 --warmup 1 --mode $mode --batch ${BATCH:-8} --no-cpu-baseline > /tmp/ranks_$mode.log 2>&1
+    bench.py --gpus $N --steps 2 --warmup 1 --mode $mode --full --batch ${BATCH:-8} --no-cpu-baseline > /tmp/ranks_$mode.log 2>&1
   echo "mode $mode: exit $? after $SECONDS s"
   grep '"metric"' /tmp/ranks_$mode.log | cut -c1-600
   grep -iE "error|traceback" /tmp/ranks_$mode.log | head -5

@@ -7,7 +7,7 @@ cd $ROOT
 export MSMD_DIST_BACKEND=gloo MSMD_ONE_DEVICE=1
 for mode in forward train; do
   timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 \
-    bench.py --gpus 2 --steps 3 --warmup 1 --mode $mode --no-cpu-baseline > /tmp/two_$mode.log 2>&1
+    bench.py --gpus 2 --steps 3 --warmup 1 --mode $mode --full --no-cpu-baseline > /tmp/two_$mode.log 2>&1
   echo "mode $mode: exit $?"
   grep '"metric"' /tmp/two_$mode.log | cut -c1-420
   grep -iE "error|traceback" /tmp/two_$mode.log | head -5

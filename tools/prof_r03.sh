@@ -7,7 +7,7 @@ WHAT=${1:-all}
 O=$ROOT/gpurun_out/r03
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-C="--steps 20 --warmup 3 --no-cpu-baseline --no-parity --no-two-streams-leg"
+C="--full --steps 20 --warmup 3 --no-cpu-baseline --no-parity --no-two-streams-leg"
 stats() {   # stats <tag> <program args...>: kernel-trace + stats of one command -> $O/<tag>_kernel_stats.csv
   local tag=$1; shift
   rm -rf /tmp/pr_$tag

@@ -7,7 +7,7 @@ WHAT=${1:-all}
 O=$ROOT/gpurun_out/r04
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-C="--steps 20 --warmup 3 --no-cpu-baseline --no-parity --no-two-streams-leg"
+C="--full --steps 20 --warmup 3 --no-cpu-baseline --no-parity --no-two-streams-leg"
 stats() {   # stats <tag> <program args...>: kernel-trace + stats of one command -> $O/<tag>_kernel_stats.csv
   local tag=$1; shift
   rm -rf /tmp/pr_$tag
@@ -28,7 +28,7 @@ if [ "$WHAT" != "pmc" ]; then
   stats hubert_large_10s_b32 $ROOT/bench.py $C --legs hubert --steps 2 --warmup 1 --no-roofline
   stats rotations_landmarks $ROOT/tools/rot_lmk_once.py
   # configs[2] as bench.py --mode train times it, with the one-rank RCCL rehearsal leg (librccl executes on every bucket)
-  timeout 900 python3 $ROOT/bench.py --mode train --steps 10 --warmup 3 --no-cpu-baseline > /tmp/train_line.log 2>&1; grep '"metric"' /tmp/train_line.log | tail -1 > $O/r04_bench_train_full.json
+  timeout 900 python3 $ROOT/bench.py --mode train --full --steps 10 --warmup 3 --no-cpu-baseline > /tmp/train_line.log 2>&1; grep '"metric"' /tmp/train_line.log | tail -1 > $O/r04_bench_train_full.json
   # one replay of the training step, per-kernel totals
   DELIM=adam_kernel TOP=30 bash $ROOT/tools/step_timeline.sh --mode train --no-exchange-rehearsal > $O/r04_train_step_timeline.txt 2>&1
 fi

@@ -7,7 +7,7 @@ WHAT=${1:-all}
 O=$ROOT/gpurun_out/r06
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-C="--steps 20 --warmup 3 --no-cpu-baseline --no-parity --no-two-streams-leg"
+C="--full --steps 20 --warmup 3 --no-cpu-baseline --no-parity --no-two-streams-leg"
 stats() {   # stats <tag> <program args...>: kernel-trace + stats of one command -> $O/r06_<tag>_kernel_stats.csv
   local tag=$1; shift
   rm -rf /tmp/pr_$tag
@@ -53,7 +53,7 @@ if [ "$WHAT" = "stats" ] || [ "$WHAT" = "all" ]; then
   stats train_step_b32 $ROOT/bench.py $C --legs train --steps 2 --warmup 1 --no-roofline
   stats hubert_large_10s_b32 $ROOT/bench.py $C --legs hubert --steps 2 --warmup 1 --no-roofline
   stats rotations_landmarks_attention $ROOT/bench.py $C --legs rot,att --steps 2 --warmup 1 --no-roofline
-  timeout 900 python3 $ROOT/bench.py --mode train --steps 10 --warmup 3 --no-cpu-baseline > /tmp/train_line.log 2>&1; grep '"metric"' /tmp/train_line.log | tail -1 > $O/r06_bench_train_full.json
+  timeout 900 python3 $ROOT/bench.py --mode train --full --steps 10 --warmup 3 --no-cpu-baseline > /tmp/train_line.log 2>&1; grep '"metric"' /tmp/train_line.log | tail -1 > $O/r06_bench_train_full.json
 fi
 if [ "$WHAT" = "timelines" ] || [ "$WHAT" = "all" ]; then
   TOP=30 bash $ROOT/tools/step_timeline.sh > $O/r06_forward_step_timeline.txt 2>&1
