@@ -387,7 +387,10 @@ int msmd_lbs_prepare(const float* betas, const float* pose, const float* JS, con
  * One subject, many frames: with shape_varies (1 int) and v_template_folded (3, Vp) given (plus dirs (3, 192, Vp) and
  * v_template (3, Vp) to build it from), the call also writes  v_template_folded = v_template + sum_{k < 96} shape[0][k]
  * dirs[k]  and sets *shape_varies to whether any frame's first 96 shape coefficients differ from frame 0's -- on the
- * device, nothing reads back.  msmd_lbs_skin_v2 handed both skips those K groups when *shape_varies == 0. */
+ * device, nothing reads back.  msmd_lbs_skin_v2 handed both skips those K groups when *shape_varies == 0.
+ * The fold runs only when NS >= 96 and all four of shape_varies, v_template_folded, dirs and v_template are given; whenever
+ * shape_varies is given and the fold does not run, *shape_varies is set nonzero ("varies", v_template_folded untouched), so
+ * the pair can always be handed on to the skinning call.  Every write is stream ordered (kernels only: graph-capture safe). */
 int msmd_flame_prepare(const float* shape, const float* expr, const float* pose6, const float* eye, const float* JS,
                        const int* parents, float* coef, float* A, float* joints, void* skin_tiles, int B, int NS, int NE,
                        int ignore_global_rot, int* shape_varies, float* v_template_folded, const float* dirs,

@@ -344,8 +344,10 @@ extern "C" int msmd_flame_prepare(const float* shape, const float* expr, const f
   if (B <= 0 || NS <= 0 || NE <= 0 || NB > 256 || Kp < NB + (J - 1) * 9 || !shape || !expr || !pose6 || !skin_tiles) return 1;
   hipStream_t st = (hipStream_t)stream;
   const bool fold = shape_varies && v_template_folded && dirs && v_template && NS >= LBS_KFOLD;
-  if (fold) {
-    hipError_t e = msmd_zero_async(shape_varies, sizeof(int), st);
+  if (shape_varies) {
+    // the fold needs the first LBS_KFOLD coefficients to be shape ones: below that (or without the planes to fold) the flag
+    // says "varies", so a skinning call handed it takes the general path instead of reading an unwritten folded template
+    hipError_t e = msmd_fill_async(shape_varies, sizeof(int), fold ? 0u : 1u, st);
     if (e != hipSuccess) return (int)e;
   }
   hipLaunchKernelGGL(lbs_prepare_kernel, dim3((B + LBS_FPB - 1) / LBS_FPB), dim3(256), lbs_prepare_lds(NB, J), st, shape, pose6,
@@ -536,9 +538,9 @@ extern "C" int msmd_lbs_skin_bf16x3(const void* coef_hl, const float* A, const f
 // Stores: 12 bytes (x, y, z of the lane's vertex) per lane and frame, 16 lanes = 192 contiguous bytes.  (Turning each
 // wave's 16 x 48 floats through an LDS patch into plain dword stores of whole row slices was built and measured: the
 // 28 extra LDS instructions per lane and tile cost more than the narrower stores saved, 765 vs 695 us at 25 600 frames.)
-// No lane is ever masked: padding vertices (v >= V) and padding frames (f >= B) recompute and re-store vertex V - 1 /
-// frame B - 1 (identical bytes), so every wave issues exactly 4 store instructions per tile and the vmcnt arithmetic
-// is uniform.
+// No lane is ever masked: padding vertices (v >= V) and padding frames (f >= B) recompute and re-store vertex V - 1 (OUT16:
+// the last vertex pair) / frame B - 1 (identical bytes), so every wave issues exactly 4 store instructions per tile and the
+// vmcnt arithmetic is uniform.
 template <int N> __device__ __forceinline__ void vm_wait() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 __device__ __forceinline__ void vm_wait_n(int n) {   // n = (pieces per load group) a + (stores per tile) b, see the kernel
 #define VMW(k) case k: vm_wait<k>(); break;
@@ -608,7 +610,11 @@ void lbs_skin_v2_kernel(const unsigned char* __restrict__ tiles,
   if (f_begin >= B) return;
   const int f_end = min(B, f_begin + frames_per_block);
   const int ntiles = (f_end - f_begin + 15) >> 4;
-  const int ve = min(v_tile * VPB + wid * 16 + i, V - 1);
+  // padding lanes (v >= V) recompute vertex V - 1.  OUT16 stores a vertex PAIR at (ve & ~1): clamp the pair, not the lane, so a
+  // pair made only of padding lanes holds [v(base), v(base + 1)] at the last valid pair's base and stores exactly that pair's
+  // bytes.  (Clamping each lane to V - 1 put [v(V-1), v(V-1)] at slot V - 2 when V is even, racing the valid pair's store.)
+  const int vu = v_tile * VPB + wid * 16 + i;
+  const int ve = OUT16 ? min(min(vu & ~1, (V - 1) & ~1) + (vu & 1), V - 1) : min(vu, V - 1);
 
   u32x4 dh[3][KG], dl[3][F16P ? 1 : KG];     // F16P: dirs_hl points at the ONE fp16 plane (3, Kp / 8, Vp, 8)
 #pragma unroll

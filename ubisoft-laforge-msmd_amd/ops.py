@@ -784,7 +784,9 @@ def lbs_prepare(betas, pose, JS, parents, Kp=192, pose_is_matrix=False, want_joi
 def flame_prepare(shape, expr, pose6, eye, JS, parents, ignore_global_rot=False, dirs=None, v_template_planes=None):
     """FLAME.forward's (B, NS) shape, (B, NE) expression, (B, 6) [global | jaw] pose (+ optional (B, 6) eye pose) ->
     msmd_lbs_skin_v2's tile records, without the concatenated betas / full_pose tensors.  With `dirs` (3, 192, Vp) and the
-    template planes also -> (shape_varies flag, folded template) for the one-subject fast path of lbs_skin_v2."""
+    template planes also -> (shape_varies flag, folded template) for the one-subject fast path of lbs_skin_v2.  The fold
+    needs NS >= 96 shape coefficients: with fewer the kernel sets the flag to "varies" (nonzero) and leaves the folded
+    template unwritten, so the pair may always be passed on to lbs_skin_v2."""
     lib = _lib.load()
     _need_cuda(shape, expr, pose6)
     B = shape.shape[0]
