@@ -544,6 +544,8 @@ int msmd_allreduce_bucket(void* comm, void* buf, long n, int dtype, msmd_stream_
 /* ------------------------------------------------------------------------------------------------
  * Backward-pass building blocks (training; reference training_script.py:195).  dgrad / wgrad are msmd_gemm calls on
  * transposed operands: dX = dZ . W (W^T as the (K, N) operand), dW = dZ^T . X (both operands transposed).
+ * The entries below with a dtype argument take MSMD_F32 or MSMD_BF16 (and msmd_dropout the same) and return 1 for any
+ * other code; msmd_transpose and msmd_unfold_t, which only move bits, also take MSMD_F16.
  */
 /* y[z][c][r] = x[z][r][c] for batch * batch_inner matrices; matrix z = zo * batch_inner + zi starts at
  * base + zo * stride + zi * stride_i (elements). */
@@ -563,6 +565,8 @@ int msmd_act_bwd_dropout(const void* dy, const void* z, void* dz, long n, int ac
                          const unsigned long* rng_state, unsigned int site, int dtype, msmd_stream_t stream);
 /* LayerNorm backward for y = LN(x)*gamma + beta (x = the LN input, residual already added):
  * dx (rows, cols); dgamma / dbeta (cols) fp32 are ACCUMULATED into (zero them for a fresh gradient).
+ * The row statistics are recomputed in two passes (mean, then the sum of squared deviations), as msmd_layernorm forms
+ * them: no cancellation on rows whose mean is large against their spread.  cols <= 1024; dtype MSMD_F32 or MSMD_BF16.
  * ws: optional msmd_layernorm_bwd_workspace() bytes for per-workgroup partial sums (NULL: fp32 atomics). */
 int msmd_layernorm_bwd(const void* dy, const void* x, const float* gamma, void* dx, float* dgamma, float* dbeta,
                        int rows, int cols, float eps, int dtype, void* ws, long ws_bytes, msmd_stream_t stream);

@@ -33,6 +33,7 @@ extern "C" int msmd_transpose(const void* x, void* y, int rows, int cols, long l
                               long stride_y, int batch_inner, long stride_x_i, long stride_y_i, int dtype,
                               msmd_stream_t stream) {
   if (rows <= 0 || cols <= 0 || batch <= 0 || batch_inner <= 0) return 1;
+  if (dtype != MSMD_F32 && dtype != MSMD_BF16 && dtype != MSMD_F16) return 1;   // moves bits: any 2- or 4-byte type
   dim3 grid((cols + 63) / 64, (rows + 63) / 64, batch * batch_inner), block(256);
   if (dtype == MSMD_F32)
     hipLaunchKernelGGL(transpose_kernel<float>, grid, block, 0, (hipStream_t)stream, (const float*)x, (float*)y, rows,
@@ -96,6 +97,7 @@ extern "C" long msmd_colsum_workspace(long rows, int cols) { return ((rows + 127
 extern "C" int msmd_colsum(const void* x, float* out, long rows, int cols, long ld, int accumulate, int dtype,
                            void* ws, long ws_bytes, msmd_stream_t stream) {
   if (rows <= 0 || cols <= 0) return 1;
+  if (dtype != MSMD_F32 && dtype != MSMD_BF16) return 1;   // fp32 or bf16 only (no fp16 training path)
   hipStream_t st = (hipStream_t)stream;
   const int rpb = 128;
   const int nblocks = (int)((rows + rpb - 1) / rpb);
@@ -138,6 +140,7 @@ __global__ void act_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ z
 
 extern "C" int msmd_act_fwd(const void* z, void* y, long n, int act, int dtype, msmd_stream_t stream) {
   if (n <= 0) return 1;
+  if (dtype != MSMD_F32 && dtype != MSMD_BF16) return 1;   // fp32 or bf16 only (no fp16 training path)
   dim3 grid((unsigned)min((n + 255) / 256, (long)8192)), block(256);
   if (dtype == MSMD_F32)
     hipLaunchKernelGGL(act_fwd_kernel<float>, grid, block, 0, (hipStream_t)stream, (const float*)z, (float*)y, n, act);
@@ -147,6 +150,7 @@ extern "C" int msmd_act_fwd(const void* z, void* y, long n, int act, int dtype, 
 }
 extern "C" int msmd_act_bwd(const void* dy, const void* z, void* dz, long n, int act, int dtype, msmd_stream_t stream) {
   if (n <= 0) return 1;
+  if (dtype != MSMD_F32 && dtype != MSMD_BF16) return 1;   // fp32 or bf16 only (no fp16 training path)
   dim3 grid((unsigned)min((n + 255) / 256, (long)8192)), block(256);
   if (dtype == MSMD_F32)
     hipLaunchKernelGGL(act_bwd_kernel<float>, grid, block, 0, (hipStream_t)stream, (const float*)dy, (const float*)z,
@@ -267,7 +271,10 @@ __global__ __launch_bounds__(256) void ln_partial_reduce_kernel(const float* __r
 }
 
 // 4-wide variant: lane owns columns (i * 64 + lane) * 4 + {0..3}: 8-byte (bf16) / 16-byte (fp32) accesses, and two
-// rounds of two independent wave reductions (sum x, sum x^2 | sum g, sum g xhat) instead of four dependent ones.
+// rounds of wave reductions (sum x | sum (x - mean)^2, sum g, sum g (x - mean), three independent ones) instead of four
+// dependent ones.  The variance is the two-pass sum of squared deviations, as in msmd_layernorm and the scalar kernel:
+// the one-pass sum x^2 / n - mean^2 cancels in fp32 on rows whose mean is large against their spread (rstd off by 1.5e-2
+// at mean / std = 100, 768 columns).  sum g xhat = rstd sum g (x - mean) keeps the second round independent of rstd.
 template <typename T> struct Vec4;
 template <> struct Vec4<float> { typedef f32x4 type; };
 template <> struct Vec4<bf16_t> { typedef __bf16 type __attribute__((ext_vector_type(4))); };
@@ -299,7 +306,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd4_kernel(const T* __restrict
   const int r_begin = blockIdx.x * rows_per_block, r_end = min(rows, r_begin + rows_per_block);
   for (int row = r_begin + wid; row < r_end; row += 4) {
     float xv[NCH][4], dyv[NCH][4];
-    float s = 0.f, ss = 0.f;
+    float s = 0.f;
 #pragma unroll
     for (int i = 0; i < NCH; ++i) {
       const int c = (i * 64 + lane) * 4;
@@ -311,39 +318,40 @@ __global__ __launch_bounds__(256) void layernorm_bwd4_kernel(const T* __restrict
           xv[i][j] = (float)a[j];
           dyv[i][j] = (float)d[j];
           s += xv[i][j];
-          ss += xv[i][j] * xv[i][j];
         }
       } else {
 #pragma unroll
         for (int j = 0; j < 4; ++j) xv[i][j] = dyv[i][j] = 0.f;
       }
     }
-    // two independent butterfly reductions interleave in the pipeline
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      s += __shfl_xor(s, o, 64);
-      ss += __shfl_xor(ss, o, 64);
-    }
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
     const float mean = s * inv_n;
-    const float var = fmaxf(ss * inv_n - mean * mean, 0.f);
-    const float rstd = 1.0f / sqrtf(var + eps);
-    float g1 = 0.f, g2 = 0.f;
+    float q = 0.f, g1 = 0.f, g2 = 0.f;
 #pragma unroll
     for (int i = 0; i < NCH; ++i)
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const bool ok = (i * 64 + lane) * 4 + j < cols;
-        xv[i][j] = ok ? (xv[i][j] - mean) * rstd : 0.f;  // xhat
+        xv[i][j] = ok ? xv[i][j] - mean : 0.f;  // x - mean (padding lanes 0)
         const float gv = dyv[i][j] * gam[i][j];
+        q += xv[i][j] * xv[i][j];
         g1 += gv;
         g2 += gv * xv[i][j];
       }
+    // three independent butterfly reductions interleave in the pipeline
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
+      q += __shfl_xor(q, o, 64);
       g1 += __shfl_xor(g1, o, 64);
       g2 += __shfl_xor(g2, o, 64);
     }
-    const float m1 = g1 * inv_n, m2 = g2 * inv_n;
+    const float rstd = 1.0f / sqrtf(q * inv_n + eps);
+#pragma unroll
+    for (int i = 0; i < NCH; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) xv[i][j] *= rstd;  // xhat
+    const float m1 = g1 * inv_n, m2 = g2 * rstd * inv_n;
 #pragma unroll
     for (int i = 0; i < NCH; ++i) {
       const int c = (i * 64 + lane) * 4;
@@ -402,6 +410,7 @@ static int layernorm_bwd_impl(const void* dy, const void* x, const float* gamma,
                               msmd_stream_t stream, void* dx_drop, float p_drop, const unsigned long* rng_state,
                               unsigned site) {
   if (rows <= 0 || cols <= 0 || cols > 1024) return 1;
+  if (dtype != MSMD_F32 && dtype != MSMD_BF16) return 1;   // fp32 or bf16 only (no fp16 training path)
   if (dx_drop && (!(p_drop > 0.f && p_drop < 1.f) || !rng_state || (cols & 3) || ((uintptr_t)dx_drop & 15) ||
                   ((uintptr_t)dy & 15) || ((uintptr_t)x & 15) || ((uintptr_t)dx & 15)))
     return 1;   // the dropped copy exists in the 4-wide kernels only
@@ -512,6 +521,7 @@ __global__ __launch_bounds__(256) void softmax_bwd_rows_kernel(const T* __restri
 extern "C" int msmd_softmax_rows(void* s, const uint8_t* mask, long rows, int cols, int ld, int Tq, float scale,
                                  int dtype, msmd_stream_t stream) {
   if (rows <= 0 || cols <= 0 || Tq <= 0 || ld < cols) return 1;
+  if (dtype != MSMD_F32 && dtype != MSMD_BF16) return 1;   // fp32 or bf16 only (no fp16 training path)
   dim3 grid((unsigned)((rows + 3) / 4)), block(256);
   if (dtype == MSMD_F32)
     hipLaunchKernelGGL(softmax_rows_kernel<float>, grid, block, 0, (hipStream_t)stream, (float*)s, mask, rows, cols, ld,
@@ -524,6 +534,7 @@ extern "C" int msmd_softmax_rows(void* s, const uint8_t* mask, long rows, int co
 extern "C" int msmd_softmax_bwd_rows(const void* P, void* dP, long rows, int cols, int ld, float scale, int dtype,
                                      msmd_stream_t stream) {
   if (rows <= 0 || cols <= 0 || ld < cols) return 1;
+  if (dtype != MSMD_F32 && dtype != MSMD_BF16) return 1;   // fp32 or bf16 only (no fp16 training path)
   dim3 grid((unsigned)((rows + 3) / 4)), block(256);
   if (dtype == MSMD_F32)
     hipLaunchKernelGGL(softmax_bwd_rows_kernel<float>, grid, block, 0, (hipStream_t)stream, (const float*)P,
@@ -558,6 +569,7 @@ __global__ __launch_bounds__(256) void unfold_t_kernel(const T* __restrict__ xp,
 extern "C" int msmd_unfold_t(const void* xp, void* out, int B, int T, int Tp, int G, int Cg, int Kk, long ld_out,
                              int dtype, msmd_stream_t stream) {
   if (B <= 0 || T <= 0 || Tp < T + Kk - 1 || G <= 0 || Cg <= 0 || Kk <= 0 || ld_out < (long)B * T) return 1;
+  if (dtype != MSMD_F32 && dtype != MSMD_BF16 && dtype != MSMD_F16) return 1;   // moves bits: any 2- or 4-byte type
   dim3 grid((unsigned)min((ld_out + 255) / 256, (long)64), Kk * Cg, G), block(256);
   if (dtype == MSMD_F32)
     hipLaunchKernelGGL(unfold_t_kernel<float>, grid, block, 0, (hipStream_t)stream, (const float*)xp, (float*)out, B, T,
@@ -596,6 +608,7 @@ __global__ __launch_bounds__(256) void dropout_kernel(const T* __restrict__ x, c
 extern "C" int msmd_dropout(const void* x, const void* residual, void* y, long n, float p,
                             const unsigned long* rng_state, unsigned int site, int dtype, msmd_stream_t stream) {
   if (n <= 0 || !(p >= 0.f && p < 1.f) || !rng_state) return 1;
+  if (dtype != MSMD_F32 && dtype != MSMD_BF16) return 1;   // fp32 or bf16 only (no fp16 training path)
   dim3 grid((unsigned)min(((n + 3) / 4 + 255) / 256, (long)8192)), block(256);
   if (dtype == MSMD_F32)
     hipLaunchKernelGGL(dropout_kernel<float>, grid, block, 0, (hipStream_t)stream, (const float*)x,
@@ -629,6 +642,7 @@ __global__ __launch_bounds__(256) void act_bwd_dropout_kernel(const T* __restric
 extern "C" int msmd_act_bwd_dropout(const void* dy, const void* z, void* dz, long n, int act, float p,
                                     const unsigned long* rng_state, unsigned int site, int dtype, msmd_stream_t stream) {
   if (n <= 0 || !(p > 0.f && p < 1.f) || !rng_state) return 1;
+  if (dtype != MSMD_F32 && dtype != MSMD_BF16) return 1;   // fp32 or bf16 only (no fp16 training path)
   dim3 grid((unsigned)min(((n + 3) / 4 + 255) / 256, (long)8192)), block(256);
   if (dtype == MSMD_F32)
     hipLaunchKernelGGL(act_bwd_dropout_kernel<float>, grid, block, 0, (hipStream_t)stream, (const float*)dy,
