@@ -359,6 +359,22 @@ int msmd_sampler_step_select(const void* emb_all, const float* coef_table, int* 
 int msmd_cfg_ddpm_step_dev(float* x, const float* res, const float* z, const float* scales, const float* coefs,
                            int n_entries, int B, int L, int Lp, int dm, int mode, int target, msmd_stream_t stream);
 
+/* Few-step solver update (DDIM(eta), DPM-Solver++(2M); sampler.solver_table), in place on x (B, L, dm) fp32.
+ * The CFG combine of res / scales / mode is msmd_cfg_ddpm_step's, same arithmetic in the same order; then
+ *   D = p0 x + p1 theta,  x <- ax x + ath theta + b1 d_prev + sigma z,  d_prev <- D
+ * d_prev (B, L, dm) fp32: the previous step's data prediction, in and out.  z (B, L, dm) or NULL (sigma unused).
+ * msmd_cfg_solver_step_dev: the same with (p0, p1, ax, ath, b1, sigma) read from `coefs` (6) on the device.
+ * msmd_sampler_solver_select: emb_row (d) = emb_tab[i], coefs (6) = coef_tab[i], then i -= 1 (the graph form:
+ * emb_tab (S+1, d) holds the step embeddings gathered at the solver's timesteps, coef_tab (S+1, 6) its rows). */
+int msmd_cfg_solver_step(float* x, const float* res, const float* z, const float* scales, float* d_prev,
+                         int n_entries, int B, int L, int Lp, int dm, int mode, float p0, float p1, float ax,
+                         float ath, float b1, float sigma, msmd_stream_t stream);
+int msmd_cfg_solver_step_dev(float* x, const float* res, const float* z, const float* scales, float* d_prev,
+                             const float* coefs, int n_entries, int B, int L, int Lp, int dm, int mode,
+                             msmd_stream_t stream);
+int msmd_sampler_solver_select(const void* emb_tab, const float* coef_tab, int* i_dev, void* emb_row,
+                               float* coefs, int d, int dtype, msmd_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * FLAME: blendshapes + pose correctives + joint regression + Rodrigues + kinematic chain + skinning
  * (reference utils/lbs.py:141-223, utils/flame.py:180-217) in two launches.

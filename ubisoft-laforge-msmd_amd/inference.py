@@ -43,18 +43,20 @@ def window_plan(n_samples: int, fps, n_motions: int, audio_unit: float):
 @torch.no_grad()
 def infer_coeffs(model, args, audio, shape_coef, audio_unit, style_feats=None, n_repetitions: int = 1, cfg_mode=None,
                  cfg_cond=None, cfg_scale: float = 1.15, include_shape: bool = False, dynamic_threshold=(0, 1, 4),
-                 noise=None):
+                 noise=None, sample_steps=None, solver="ddpm", eta=0.0):
     """Coefficients for one clip of any length (reference inference.py:34-75; same signature, window arithmetic and hand-off
     rules).  The clip is zero-padded to a whole number of n_motions-frame windows and encoded ONCE; each window is one
     `model.sample` call conditioned on the previous window's last n_prev_motions motion / audio-feature frames, every
     window after the first starts from window 0's x_T, and the frames that only cover the padding are cut from the result.
-    ``noise`` (optional, replay): {'xT': tensor, 'z': [per-window dict of per-step draws]}."""
+    ``noise`` (optional, replay): {'xT': tensor, 'z': [per-window dict of per-step draws]}.
+    ``sample_steps`` / ``solver`` / ``eta``: the sampler of every window (MSMD.sample); the default is the reference's."""
     L, keep = args.n_motions, args.n_prev_motions
     _, _, n_windows, pad_samples, pad_frames = window_plan(len(audio), args.fps, L, audio_unit)
     tail = max(pad_frames, 0)                       # frames of the last window that lie entirely in the zero padding
     wave = F.pad(audio, (0, pad_samples), value=0) if pad_samples > 0 else audio
     per_window = model.extract_audio_feature(wave.unsqueeze(0), L * n_windows).split(L, dim=1)
-    guidance = dict(cfg_mode=cfg_mode, cfg_cond=cfg_cond, cfg_scale=cfg_scale, dynamic_threshold=dynamic_threshold)
+    guidance = dict(cfg_mode=cfg_mode, cfg_cond=cfg_cond, cfg_scale=cfg_scale, dynamic_threshold=dynamic_threshold,
+                    sample_steps=sample_steps, solver=solver, eta=eta)
     history = (None, None, None if noise is None else noise["xT"])      # (prev motion, prev audio features, x_T)
     pieces = []
     for w, feat in enumerate(per_window):
@@ -144,10 +146,12 @@ def denormalize_coeffs(overall_coef, coef_stats):
 # ----------------------------------------------------------------------------- many clips per denoise step
 @torch.no_grad()
 def infer_coeffs_batch(model, args, audios, shape_coefs, audio_unit, style_feats, cfg_mode=None, cfg_cond=None,
-                       cfg_scale: float = 1.15, dynamic_threshold=(0, 1, 4), noise=None):
+                       cfg_scale: float = 1.15, dynamic_threshold=(0, 1, 4), noise=None, sample_steps=None, solver="ddpm",
+                       eta=0.0):
     """`infer_coeffs` for a list of clips (1-D audio tensors of any lengths), one repetition each, with window i of
     all clips batched into one `model.sample` call.  shape_coefs: (n_clips, 100); style_feats: (n_clips, d_style).
-    `noise` (optional): list of per-clip {'xT', 'z'} dicts as `infer_coeffs` takes.  Returns a list of (1, clip_len, C)
+    `noise` (optional): list of per-clip {'xT', 'z'} dicts as `infer_coeffs` takes; `sample_steps` / `solver` / `eta`
+    as `infer_coeffs` takes them.  Returns a list of (1, clip_len, C)
     tensors, clip c equal to infer_coeffs(model, args, audios[c], shape_coefs[c:c+1], audio_unit, style_feats[c:c+1])."""
     n = len(audios)
     L, Lp = args.n_motions, args.n_prev_motions
@@ -175,7 +179,7 @@ def infer_coeffs_batch(model, args, audios, shape_coefs, audio_unit, style_feats
                 ind[j, -plans[c][4]:] = 0
         audio_in = torch.cat([feats[c][:, i * L:(i + 1) * L] for c in act], dim=0)
         kw = dict(indicator=ind, cfg_mode=cfg_mode, cfg_cond=cfg_cond, cfg_scale=cfg_scale,
-                  dynamic_threshold=dynamic_threshold)
+                  dynamic_threshold=dynamic_threshold, sample_steps=sample_steps, solver=solver, eta=eta)
         if noise is not None:
             kw["noise"] = {t: torch.cat([noise[c]["z"][i][t] for c in act], dim=0) for t in noise[act[0]]["z"][i]}
         idx = torch.as_tensor(act, device=model.device)
@@ -213,6 +217,10 @@ def build_parser():
     ap.add_argument("--cfg_level", type=float, default=1.4)
     ap.add_argument("--output_dir", type=str, default="/experiments/refactor")
     ap.add_argument("--versions_of_render", type=int, default=1)
+    # sampler choice (not in the reference; the defaults are its DDPM chain over all n_diff_steps)
+    ap.add_argument("--sample_steps", type=int, default=None, help="steps of a few-step solver (default: all)")
+    ap.add_argument("--solver", type=str, default="ddpm", choices=["ddpm", "ddim", "dpmpp_2m"])
+    ap.add_argument("--eta", type=float, default=0.0, help="DDIM noise scale: 0 deterministic, 1 ancestral")
     return ap
 
 
@@ -255,7 +263,7 @@ def main(argv=None):
         np.random.seed(seed)
         torch.manual_seed(seed)
         coef = infer_coeffs(model, model_args, audio_tensor, shape_coef, 640.0, style_coeff, cfg_scale=args.cfg_level,
-                            dynamic_threshold=None)
+                            dynamic_threshold=None, sample_steps=args.sample_steps, solver=args.solver, eta=args.eta)
         exp_code, head_rot = denormalize_coeffs(coef, coef_stats)
         for tag, val in (("exp_code", exp_code), ("head_rot", head_rot)):
             out = os.path.join(temp, f"overall_{tag}_{clip}_seed_{seed}.pkl")

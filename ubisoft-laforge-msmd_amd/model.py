@@ -824,12 +824,15 @@ class MSMD(nn.Module):
     @torch.no_grad()
     def sample(self, audio_or_feat, shape_feat, style_feat=None, prev_motion_feat=None, prev_audio_feat=None,
                motion_at_T=None, indicator=None, cfg_mode=None, cfg_cond=None, cfg_scale=1.15, flexibility=0,
-               dynamic_threshold=None, ret_traj=False, noise=None):
+               dynamic_threshold=None, ret_traj=False, noise=None, sample_steps=None, solver="ddpm", eta=0.0):
         """reference model.py:283-440: DDPM ancestral sampling with 1-3-way classifier-free guidance.
-        ``noise``: optional dict {t: z_t} of injected draws (deterministic replay); default torch.randn_like."""
+        ``noise``: optional dict {t: z_t} of injected draws (deterministic replay); default torch.randn_like.
+        ``solver``: "ddpm" (default: the reference's chain over all T steps), "ddim" (``eta`` in [0, 1]: 0 deterministic,
+        1 ancestral) or "dpmpp_2m" (DPM-Solver++(2M)) over ``sample_steps`` timesteps (sampler.solver_table)."""
         from .sampler import sample as _sample
         return _sample(self, audio_or_feat, shape_feat, style_feat, prev_motion_feat, prev_audio_feat, motion_at_T,
-                       indicator, cfg_mode, cfg_cond, cfg_scale, flexibility, dynamic_threshold, ret_traj, noise)
+                       indicator, cfg_mode, cfg_cond, cfg_scale, flexibility, dynamic_threshold, ret_traj, noise,
+                       sample_steps=sample_steps, solver=solver, eta=eta)
 
     @torch.no_grad()
     def sample_separate(self, audio_or_feat, shape_feat, style_feat=None, prev_motion_feat=None, prev_audio_feat=None,

@@ -737,6 +737,30 @@ def cfg_ddpm_step_dev(x, res, z, scales, coefs, n_entries, Lp, mode, target):
     return x
 
 
+
+def cfg_solver_step(x, res, z, scales, d_prev, n_entries, Lp, mode, p0, p1, ax, ath, b1, sigma):
+    """Few-step solver update (DDIM / DPM-Solver++(2M) row of sampler.solver_table), in place on x and d_prev."""
+    lib = _lib.load()
+    B, L, dm = x.shape
+    _lib.check(lib.msmd_cfg_solver_step(_p(x), _p(res), _p(z), _p(scales), _p(d_prev), n_entries, B, L, Lp, dm, mode,
+                                        float(p0), float(p1), float(ax), float(ath), float(b1), float(sigma), _stream()),
+               "msmd_cfg_solver_step")
+    return x
+
+
+def sampler_solver_select(emb_tab, coef_tab, i_dev, emb_row, coefs):
+    lib = _lib.load()
+    _lib.check(lib.msmd_sampler_solver_select(_p(emb_tab), _p(coef_tab), _p(i_dev), _p(emb_row), _p(coefs),
+                                              emb_tab.shape[-1], _dt(emb_tab), _stream()), "msmd_sampler_solver_select")
+
+
+def cfg_solver_step_dev(x, res, z, scales, d_prev, coefs, n_entries, Lp, mode):
+    lib = _lib.load()
+    B, L, dm = x.shape
+    _lib.check(lib.msmd_cfg_solver_step_dev(_p(x), _p(res), _p(z), _p(scales), _p(d_prev), _p(coefs), n_entries, B, L, Lp,
+                                            dm, mode, _stream()), "msmd_cfg_solver_step_dev")
+    return x
+
 def pad_cols(x, cols_out, out_dtype=None):
     lib = _lib.load()
     cols_in = x.shape[-1]

@@ -9,11 +9,86 @@ traj[t] to the CPU every step, model.py:433); per-step scalars come from host co
 """
 from __future__ import annotations
 
+import math
 import os
 
 import torch
 
 from . import ops
+
+SOLVERS = ("ddpm", "ddim", "dpmpp_2m")
+
+
+def check_solver(T, sample_steps=None, solver="ddpm", eta=0.0, flexibility=0):
+    """Validate the sampler's solver arguments; returns the step count S."""
+    if solver not in SOLVERS:
+        raise ValueError(f"Unknown solver {solver!r}; expected one of {SOLVERS}")
+    if solver == "ddpm":
+        if sample_steps not in (None, T):
+            raise ValueError(f"solver='ddpm' runs all T = {T} steps (got sample_steps={sample_steps}); for fewer "
+                             f"ancestral steps use solver='ddim', eta=1")
+        return T
+    if flexibility != 0:
+        raise ValueError(f"flexibility applies to solver='ddpm' only; solver={solver!r} takes eta instead")
+    if solver == "ddim" and not 0.0 <= eta <= 1.0:
+        raise ValueError(f"eta must lie in [0, 1], got {eta}")
+    if solver == "dpmpp_2m" and eta != 0:
+        raise ValueError("solver='dpmpp_2m' is deterministic: eta must be 0")
+    S = T if sample_steps is None else sample_steps
+    if isinstance(S, bool) or int(S) != S or not 1 <= S <= T:
+        raise ValueError(f"sample_steps must be an integer in [1, {T}], got {sample_steps}")
+    return int(S)
+
+
+def solver_table(sched, steps, solver, eta=0.0, target="sample"):
+    """Timesteps and per-step coefficients of a few-step solver in data-prediction (x0) form, in float64.
+
+    taus[i] = round(i T / S) (half up), i = 0..S ("trailing" spacing: taus[S] = T, taus[0] = 0).  Step i = S..1 goes
+    from s = taus[i] to t = taus[i-1]; rows[i] = (p0, p1, ax, ath, b1, sigma) is what msmd_cfg_solver_step applies:
+    D = p0 x + p1 theta, x <- ax x + ath theta + b1 D_prev + sigma z.  With alpha_u = sqrt(abar_u), sigma_u =
+    sqrt(1 - abar_u), lambda_u = ln(alpha_u / sigma_u), each solver is x <- a x + b0 D + b1 D_prev + sig z:
+      ddim(eta):  sig = eta sqrt((1 - abar_t) / (1 - abar_s)) sqrt(1 - abar_s / abar_t),
+                  a = sqrt(1 - abar_t - sig^2) / sigma_s, b0 = alpha_t - a alpha_s, b1 = 0;
+      dpmpp_2m:   the ddim(0) row for the first step (i = S) and the last (t = 0); otherwise, with h = lambda_t - lambda_s
+                  and r = h_prev / h: a = sigma_t / sigma_s, b0 = -alpha_t (e^-h - 1)(1 + 1/(2r)),
+                  b1 = alpha_t (e^-h - 1) / (2r), sig = 0.
+    ax = a + b0 p0 and ath = b0 p1 are folded here (for target 'noise', p0 = 1/alpha_s reaches ~1e4 at s = T and would
+    cancel in fp32 on the device).  Row 0 is unused (zeros)."""
+    T = int(sched.num_steps)
+    S = check_solver(T, steps, solver, eta)
+    if solver == "ddpm":
+        raise ValueError("solver='ddpm' has no solver table: its per-step coefficients are the reference's")
+    if target not in ("sample", "noise"):
+        raise ValueError("Unknown target type: {}".format(target))
+    ab = sched.alpha_bars.detach().cpu().double()
+    taus = [(2 * i * T + S) // (2 * S) for i in range(S + 1)]
+    al = lambda u: float(torch.sqrt(ab[u]))
+    sg = lambda u: float(torch.sqrt(1 - ab[u]))
+    lam = lambda u: math.log(al(u) / sg(u))
+    rows = torch.zeros(S + 1, 6, dtype=torch.float64)
+    h_prev = None
+    for i in range(S, 0, -1):
+        s, t = taus[i], taus[i - 1]
+        abs_, abt = float(ab[s]), float(ab[t])
+        if solver == "dpmpp_2m" and i != S and t != 0:
+            h = lam(t) - lam(s)
+            r = h_prev / h
+            em1 = math.expm1(-h)
+            a = sg(t) / sg(s)
+            b0 = -al(t) * em1 * (1 + 1 / (2 * r))
+            b1 = al(t) * em1 / (2 * r)
+            sig = 0.0
+        else:
+            e = eta if solver == "ddim" else 0.0
+            sig = e * math.sqrt((1 - abt) / (1 - abs_)) * math.sqrt(max(1 - abs_ / abt, 0.0))
+            a = math.sqrt(max(1 - abt - sig * sig, 0.0)) / sg(s)
+            b0 = al(t) - a * al(s)
+            b1 = 0.0
+        if solver == "dpmpp_2m" and t != 0:
+            h_prev = lam(t) - lam(s)
+        p0, p1 = (0.0, 1.0) if target == "sample" else (1 / al(s), -sg(s) / al(s))
+        rows[i] = torch.tensor([p0, p1, a + b0 * p0, b0 * p1, b1, sig], dtype=torch.float64)
+    return taus, rows
 
 
 def _entries(cfg_cond, cfg_mode):
@@ -34,10 +109,17 @@ def _entries(cfg_cond, cfg_mode):
 
 def sample(model, audio_or_feat, shape_feat, style_feat=None, prev_motion_feat=None, prev_audio_feat=None,
            motion_at_T=None, indicator=None, cfg_mode=None, cfg_cond=None, cfg_scale=1.15, flexibility=0,
-           dynamic_threshold=None, ret_traj=False, noise=None, guidance=None, separate=None):
+           dynamic_threshold=None, ret_traj=False, noise=None, guidance=None, separate=None, sample_steps=None,
+           solver="ddpm", eta=0.0):
     """guidance = (indices, values): naive in-painting of the denoiser INPUT (reference model.py:762-767).
     separate = dict(alpha_mod=callable|None, return_all_alpha=bool): also track the dynamic / static / alpha
-    streams (reference sample_separate, model.py:442-651)."""
+    streams (reference sample_separate, model.py:442-651).
+    solver: "ddpm" (the reference's ancestral chain over all T steps), or "ddim" (eta in [0, 1]) / "dpmpp_2m" over
+    sample_steps timesteps (solver_table); noise is then keyed by the source timestep of each step."""
+    S = check_solver(model.diffusion_sched.num_steps, sample_steps, solver, eta, flexibility)
+    few = solver != "ddpm"
+    if few and (guidance is not None or separate is not None):
+        raise ValueError(f"solver={solver!r} is available in sample() only (not with guidance or stream separation)")
     net = model.denoising_net
     dtype = model.compute_dtype
     dev = model.device
@@ -115,8 +197,13 @@ def sample(model, audio_or_feat, shape_feat, style_feat=None, prev_motion_feat=N
     stat = net.static_bases(style_feat, dtype).float().contiguous()  # real style for every entry (model.py:374)
     pf = ops.pad_cols(person_in.reshape(N, -1).float().contiguous(), P.kp_person, dtype)
     tok_person = ops.gemm(pf, *P.pp)                                   # (N, d) without the step embedding
-    te_all = ops.cast(P.te[: T + 1].contiguous(), dtype)
-    emb_all = ops.gemm(ops.gemm(te_all, *P.ds0, act=ops.ACT_GELU), *P.ds2)  # (T+1, d)
+    if few:
+        # only the rows the solver visits: emb_all[i] is the step embedding of timestep taus[i]
+        taus, rows = solver_table(model.diffusion_sched, S, solver, eta, model.target)
+        te_all = ops.cast(P.te[torch.as_tensor(taus, device=P.te.device)].contiguous(), dtype)
+    else:
+        te_all = ops.cast(P.te[: T + 1].contiguous(), dtype)
+    emb_all = ops.gemm(ops.gemm(te_all, *P.ds0, act=ops.ACT_GELU), *P.ds2)  # (T+1, d); (S+1, d) for a few-step solver
     scales = torch.tensor(list(cfg_scale), device=dev, dtype=torch.float32) if n_entries > 1 else None
     mode = 1 if cfg_mode == "independent" else 0
     target = 0 if model.target == "sample" else 1
@@ -139,8 +226,13 @@ def sample(model, audio_or_feat, shape_feat, style_feat=None, prev_motion_feat=N
     if use_graph:
         x = _graph_loop(model, net, dtype, dev, T, N, n_entries, Lp, L, dm, nb, mode, target, P, motion_at_T, prev_m,
                         ind_in, mem, kv_list, stat, tok_person, emb_all, scales, coefficients,
-                        tuple(dynamic_threshold) if dynamic_threshold else None, cross_list)
+                        tuple(dynamic_threshold) if dynamic_threshold else None, cross_list,
+                        solver=(solver, S, rows) if few else None)
         return x, motion_at_T, audio_feat
+    if few:
+        return _solver_eager_loop(net, dtype, dev, N, n_entries, Lp, L, dm, nb, mode, P, motion_at_T, prev_m, ind_in, mem,
+                                  kv_list, cross_list, stat, tok_person, emb_all, scales, dynamic_threshold, ret_traj, noise,
+                                  taus, rows), motion_at_T, audio_feat
 
     x = motion_at_T.float().clone().contiguous()
     traj = {T: motion_at_T} if ret_traj else None
@@ -206,6 +298,32 @@ def sample(model, audio_or_feat, shape_feat, style_feat=None, prev_motion_feat=N
     return x, motion_at_T, audio_feat
 
 
+def _solver_eager_loop(net, dtype, dev, N, n_entries, Lp, L, dm, nb, mode, P, motion_at_T, prev_m, ind_in, mem, kv_list,
+                       cross_list, stat, tok_person, emb_all, scales, dynamic_threshold, ret_traj, noise, taus, rows):
+    """The few-step solvers' host-driven loop: the DDPM loop's pack -> trunk -> heads -> threshold sequence, then the
+    fused solver update.  Step i reads the draw noise[taus[i]] (or a fresh one) only where its sigma is not 0."""
+    S = len(taus) - 1
+    x = motion_at_T.float().clone().contiguous()
+    d_prev = torch.zeros_like(x)
+    traj = {taus[S]: motion_at_T} if ret_traj else None
+    feats = torch.empty(N, 1 + Lp + L, P.kp_feat, device=dev, dtype=dtype)
+    for i in range(S, 0, -1):
+        p0, p1, ax, ath, b1, sigma = rows[i].tolist()
+        z = None
+        if sigma != 0:
+            z = noise[taus[i]].float().contiguous() if noise is not None else torch.randn_like(x)
+        ops.denoiser_pack_input(x, prev_m, ind_in, feats)
+        dec = net.trunk(feats, tok_person, mem, dtype, kv_list=kv_list, row0_add=emb_all[i], cross_list=cross_list)
+        res = ops.heads_static_mix(dec, stat, Lp + L, dm, nb, net.use_head_alpha, net.regularize_alpha == "sigmoid")
+        if dynamic_threshold:
+            dt_ratio, dt_min, dt_max = dynamic_threshold
+            res = ops.dynamic_threshold_(res.float().contiguous(), L, dt_ratio, dt_min, dt_max)
+        ops.cfg_solver_step(x, res, z, scales, d_prev, n_entries, Lp, mode, p0, p1, ax, ath, b1, sigma)
+        if ret_traj:
+            traj[taus[i - 1]] = x.clone()
+    return traj if ret_traj else x
+
+
 # clamped to [1, 50]: k bodies in one graph keep k steps of intermediates alive in the graph's private pool (about 0.2 GB per
 # step at B = 64, fp16: 2 GB at the default 10 of the 288 GB)
 STEPS_PER_GRAPH = min(50, max(1, int(os.environ.get("MSMD_SAMPLER_STEPS_PER_GRAPH", "10"))))
@@ -226,9 +344,11 @@ def _step_noise(B, L, dm, dev):
 
 
 class _Lane:
-    """Static operand buffers + the step body of one lane (Bl clips x n_entries CFG entries, entry-major rows)."""
+    """Static operand buffers + the step body of one lane (Bl clips x n_entries CFG entries, entry-major rows).
+    few: a few-step solver's body (6-wide coefficient rows, the previous data prediction d_prev) instead of DDPM's."""
 
-    def __init__(self, net, dtype, dev, T, Bl, n_entries, Lp, L, dm, nb, mode, target, P, like, shared, rows, clips, dyn):
+    def __init__(self, net, dtype, dev, T, Bl, n_entries, Lp, L, dm, nb, mode, target, P, like, shared, rows, clips, dyn,
+                 few=False):
         Nl = Bl * n_entries
         take = lambda t: torch.zeros((len(rows),) + tuple(t.shape[1:]), device=dev, dtype=t.dtype)
         self.rows, self.clips = rows, clips          # index tensors into the N-row / B-row operands of the whole batch
@@ -244,11 +364,13 @@ class _Lane:
         self.tok = take(like["tok_person"])
         self.t_dev = torch.zeros(1, device=dev, dtype=torch.int32)
         self.emb_row = torch.zeros(shared["emb_all"].shape[-1], device=dev, dtype=shared["emb_all"].dtype)
-        self.coefs = torch.zeros(3, device=dev, dtype=torch.float32)
+        self.coefs = torch.zeros(6 if few else 3, device=dev, dtype=torch.float32)
+        self.d_prev = torch.zeros(Bl, L, dm, device=dev, dtype=torch.float32) if few else None
         self.feats = torch.zeros(Nl, 1 + Lp + L, P.kp_feat, device=dev, dtype=dtype)
 
         def body(z):
-            ops.sampler_step_select(shared["emb_all"], shared["coef_table"], self.t_dev, self.emb_row, self.coefs)
+            select = ops.sampler_solver_select if few else ops.sampler_step_select
+            select(shared["emb_all"], shared["coef_table"], self.t_dev, self.emb_row, self.coefs)
             ops.denoiser_pack_input(self.x, self.prev_m, self.ind, self.feats)
             dec = net.trunk(self.feats, self.tok, self.mem, dtype, kv_list=self.kv, row0_add=self.emb_row,
                             cross_list=self.cross)
@@ -258,11 +380,16 @@ class _Lane:
                 res = ops.dynamic_threshold_(res.float().contiguous(), L, *dyn)
             # z: this lane's clips of the step's noise, drawn for the WHOLE batch on the forking stream (_StepGraph.bodies): what a
             # clip receives under a given seed does not depend on the lane count; sigma_1 = 0 reproduces z = 0 at t = 1
-            ops.cfg_ddpm_step_dev(self.x, res, z, shared["scales"], self.coefs, n_entries, Lp, mode, target)
+            if few:
+                ops.cfg_solver_step_dev(self.x, res, z, shared["scales"], self.d_prev, self.coefs, n_entries, Lp, mode)
+            else:
+                ops.cfg_ddpm_step_dev(self.x, res, z, shared["scales"], self.coefs, n_entries, Lp, mode, target)
         self.body = body
 
     def load(self, motion_at_T, ops_in):
         self.x.copy_(motion_at_T[self.clips])
+        if self.d_prev is not None:
+            self.d_prev.zero_()
         for name in ("prev_m", "mem"):
             getattr(self, name).copy_(ops_in[name][self.rows])
         if self.stat_per_clip:
@@ -278,28 +405,31 @@ class _Lane:
 
 
 class _StepGraph:
-    """k captured denoise steps per lane (one hipGraph): device-side step counters, static operand buffers."""
+    """k captured denoise steps per lane (one hipGraph): device-side step counters, static operand buffers.
+    T is the number of steps the loop takes: the schedule's for DDPM, S for a few-step solver (few=True: (S+1, 6)
+    coefficient rows, emb_all holds the S+1 embeddings at the solver's timesteps; draw=False: no noise is drawn)."""
 
-    def __init__(self, model, net, dtype, dev, T, N, n_entries, Lp, L, dm, nb, mode, target, P, like, dyn=None, lanes=1):
+    def __init__(self, model, net, dtype, dev, T, N, n_entries, Lp, L, dm, nb, mode, target, P, like, dyn=None, lanes=1,
+                 few=False, draw=True):
         B = N // n_entries
         self.lanes = lanes
         self.shared = dict(lanes=lanes, emb_all=torch.zeros_like(like["emb_all"]), stat=torch.zeros_like(like["stat"]),
                            scales=torch.zeros_like(like["scales"]) if like["scales"] is not None else None,
-                           coef_table=torch.zeros(T + 1, 3, device=dev, dtype=torch.float32))
+                           coef_table=torch.zeros(T + 1, 6 if few else 3, device=dev, dtype=torch.float32))
         Bl = B // lanes
         self.lane = []
         for l in range(lanes):
             clips = torch.arange(l * Bl, (l + 1) * Bl, device=dev)
             rows = torch.cat([clips + e * B for e in range(n_entries)])
             self.lane.append(_Lane(net, dtype, dev, T, Bl, n_entries, Lp, L, dm, nb, mode, target, P, like, self.shared,
-                                   rows, clips, dyn))
+                                   rows, clips, dyn, few))
         self.T = T
         self.streams = [torch.cuda.Stream() for _ in range(lanes)] if lanes > 1 else [None]
 
         def bodies(k):
             # one (B, L, dm) draw per step from the graph-safe philox stream, on the forking stream, sliced per lane: the same
             # generator calls whatever the lane count (each lane drawing its own made seeded output depend on MSMD_SAMPLER_LANES)
-            zs = [_step_noise(B, L, dm, dev) for _ in range(k)]
+            zs = [_step_noise(B, L, dm, dev) if draw else None for _ in range(k)]
             if lanes == 1:
                 for s_ in range(k):
                     self.lane[0].body(zs[s_])
@@ -309,7 +439,7 @@ class _StepGraph:
                 st.wait_stream(cur)
                 with torch.cuda.stream(st):
                     for s_ in range(k):
-                        ln.body(zs[s_][li * Bl:(li + 1) * Bl])
+                        ln.body(zs[s_][li * Bl:(li + 1) * Bl] if draw else None)
             for st in self.streams:                         # ... join
                 cur.wait_stream(st)
         # With more than one lane the LayerNorm-epilogue GEMMs (QKV, out-projection, FFN-2 of a lane: M = 10 656 rows at B = 64) take
@@ -338,17 +468,20 @@ class _StepGraph:
         finally:
             ops.GEMM_LN_TILE = tile_keep
 
-    def run(self, T, motion_at_T, ops_in, coefficients):
+    def run(self, T, motion_at_T, ops_in, coefficients, table=None):
         for ln in self.lane:
             ln.load(motion_at_T, ops_in)
         self.shared["emb_all"].copy_(ops_in["emb_all"])
         self.shared["stat"].copy_(ops_in["stat"])
         if self.shared["scales"] is not None:
             self.shared["scales"].copy_(ops_in["scales"])
-        tab = torch.zeros(T + 1, 3)
-        for t in range(1, T + 1):
-            c0, c1, sg = coefficients(t)
-            tab[t, 0], tab[t, 1], tab[t, 2] = c0, c1, (sg if t > 1 else 0.0)
+        if table is not None:
+            tab = table.float()          # a few-step solver's rows, rounded to fp32 as the eager loop's scalars are
+        else:
+            tab = torch.zeros(T + 1, 3)
+            for t in range(1, T + 1):
+                c0, c1, sg = coefficients(t)
+                tab[t, 0], tab[t, 1], tab[t, 2] = c0, c1, (sg if t > 1 else 0.0)
         self.shared["coef_table"].copy_(tab)
         for ln in self.lane:
             ln.t_dev.fill_(T)
@@ -358,18 +491,26 @@ class _StepGraph:
 
 
 def _graph_loop(model, net, dtype, dev, T, N, n_entries, Lp, L, dm, nb, mode, target, P, motion_at_T, prev_m, ind_in,
-                mem, kv_list, stat, tok_person, emb_all, scales, coefficients, dyn=None, cross_list=None):
+                mem, kv_list, stat, tok_person, emb_all, scales, coefficients, dyn=None, cross_list=None, solver=None):
+    """solver: None (DDPM over all T steps) or (name, S, rows) of a few-step solver (solver_table)."""
     B = N // n_entries
+    table = None
+    few = solver is not None
+    draw = True
+    if few:
+        name, T, table = solver          # the loop runs S steps
+        draw = bool((table[1:, 5] != 0).any())
     like = dict(prev_m=prev_m, ind_in=ind_in, mem=mem, kv_list=kv_list, cross_list=cross_list, stat=stat, tok_person=tok_person,
                 emb_all=emb_all, scales=scales, stat_per_clip=(stat.shape[0] == B and B > 1))
     lanes = getattr(model, "sampler_lanes", LANES)
     while lanes > 1 and (B % lanes or N // lanes < MIN_LANE_SEQS):
         lanes -= 1
     key = (T, N, n_entries, Lp, L, mode, target, dtype, ind_in is not None, getattr(net, "_pack_gen", 0), dyn, cross_list is not None,
-           STEPS_PER_GRAPH, lanes)
+           STEPS_PER_GRAPH, lanes, solver[0] if few else "ddpm", draw)
     cache = model.__dict__.setdefault("_step_graphs", {})
     g = cache.get(key)
     if g is None:
         cache.clear()  # one resident graph (its private memory pool holds all step intermediates)
-        g = cache[key] = _StepGraph(model, net, dtype, dev, T, N, n_entries, Lp, L, dm, nb, mode, target, P, like, dyn, lanes)
-    return g.run(T, motion_at_T.float(), like, coefficients)
+        g = cache[key] = _StepGraph(model, net, dtype, dev, T, N, n_entries, Lp, L, dm, nb, mode, target, P, like, dyn, lanes,
+                                    few, draw)
+    return g.run(T, motion_at_T.float(), like, coefficients, table)
