@@ -44,8 +44,8 @@ typedef void* msmd_stream_t; /* hipStream_t */
 int msmd_abi_version(void);
 /* The library keeps NO process-global state: every entry point is re-entrant per stream.  What used to be developer
  * knobs travels per call -- the GEMM kernel variant and epilogue flags in `act` (msmd_gemm below), the contraction
- * split count of msmd_gemm_tn in its `accumulate` argument.  The experimental kernel families of DESIGN.md section 5 /
- * 5b and their A/B switch exist only in the developer build (`make -C csrc EXP=1` -> libmsmd_hip_exp.so). */
+ * split count of msmd_gemm_tn in its `accumulate` argument.  The kernel families of DESIGN.md section 5 / 5b that
+ * lost their measurements are not in the sources any more. */
 #define MSMD_GEMM_VARIANT(v) ((v) << 8)   /* bits 8-15 of `act`: 0 = shape heuristic, 9 / 12 / 13 / 14 / 15 / 17 / 80 (bf16, fp16), 1 / 5 / 14 / 80 (f16x2) */
 #define MSMD_GEMM_WRITE_THROUGH (1 << 16) /* output stores carry `sc1`: the bytes leave the XCD's L2 as they are stored */
 #define MSMD_GEMM_PAIRED_STORES (1 << 17) /* 16-bit outputs: lane pairs swap a fragment row, one 16-byte store each */

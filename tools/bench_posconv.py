@@ -1,6 +1,6 @@
 """The encoder's positional conv (k = 128, 16 groups of 48 channels) as the batched windowed GEMM the encoder launches:
 M = B x T = 6400 rows per group, N = 48, K = 128 x 48 = 6144, batch = 16 -- 60 GFLOP, 10 % of the forward step's FLOPs.
-  python tools/bench_posconv.py 9,12[,...]      variants per call (experimental ones need MSMD_LIB=.../libmsmd_hip_exp.so)"""
+  python tools/bench_posconv.py 9,12[,...]      variants per call"""
 import os
 import sys
 

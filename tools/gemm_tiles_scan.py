@@ -2,10 +2,8 @@
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from msmd_amd import ops, _lib
-lib = _lib.load()
+from msmd_amd import ops
 V = int(os.environ.get("VARIANT", "17"))
-lib.msmd_exp_set_tuning(0, V)
 for K in (768, 3072):
     for N in (768,):
         for mt in [int(x) for x in os.environ.get("MT", "21,32,43,50,64,85,86,100,128,171,200").split(",")]:
@@ -15,13 +13,13 @@ for K in (768, 3072):
             bias = torch.randn(N, device="cuda")
             out = torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
             for _ in range(3):
-                ops.gemm(a, w, bias, None, 1, out=out)
+                ops.gemm(a, w, bias, None, 1, out=out, variant=V)
             torch.cuda.synchronize()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             R = 30
             e0.record()
             for _ in range(R):
-                ops.gemm(a, w, bias, None, 1, out=out)
+                ops.gemm(a, w, bias, None, 1, out=out, variant=V)
             e1.record()
             torch.cuda.synchronize()
             us = e0.elapsed_time(e1) / R * 1e3

@@ -1,7 +1,7 @@
 #!/bin/bash
 # HBM traffic per kernel of the forward bench step: FETCH_SIZE and WRITE_SIZE in SEPARATE --pmc passes (rocprofv3
 # guide), each with --kernel-trace only; per-kernel averages merged into gpurun_out/<tag>_pmc_hbm_fetch_write_per_kernel.json.
-# Usage: [MSMD_TUNE=7=1] bash tools/pmc_hbm.sh <tag> [bench dtype ...]      (tuning keys, if any, come from the environment)
+# Usage: bash tools/pmc_hbm.sh <tag> [bench dtype ...]
 ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp && export TMPDIR=/tmp
 TAG=${1:-cur}; shift

@@ -14,7 +14,7 @@ import re
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 HEADER = os.path.join(_ROOT, "include", "msmd_hip.h")
-# MSMD_LIB selects another build of the SAME C ABI (developers: the experimental library, make -C csrc EXP=1)
+# MSMD_LIB selects another build of the SAME C ABI (same-box A/B of two library builds: tools/ab_lib.sh)
 LIB_PATH = os.environ.get("MSMD_LIB") or os.path.join(_HERE, "csrc", "libmsmd_hip.so")
 
 _CTYPE = {

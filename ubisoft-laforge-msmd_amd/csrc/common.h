@@ -54,14 +54,6 @@ __device__ __forceinline__ unsigned dropout_value16(const Philox4& r, int e, int
   return odd ? w >> 16 : w & 0xffffu;
 }
 
-// Developer knobs: only the experimental build (make EXP=1, -DMSMD_EXPERIMENTAL) has them; in the product library every
-// MSMD_TUNE(k) is the constant 0 and the code it guards folds away (no process-global state: re-entrant per stream).
-#ifdef MSMD_EXPERIMENTAL
-extern int g_tuning[16];
-#define MSMD_TUNE(k) (g_tuning[k])
-#else
-#define MSMD_TUNE(k) 0
-#endif
 #define MSMD_RETURN_LAST() return (int)hipGetLastError()
 
 // Zero a small device workspace with a kernel launch instead of hipMemsetAsync: every node of a captured hipGraph is then

@@ -553,9 +553,7 @@ __device__ __forceinline__ void vm_wait_n(int n) {   // n = (pieces per load gro
 #undef VMW
 }
 
-// NWV waves per workgroup (16 vertices each).  ABL (developer ablations, tuning key 8; 0 in the product): 1 = no vertex
-// stores, 2 = no blend MFMAs, 4 = no blendshape MFMAs, 8 = no LDS-DMA after the prologue (stale tiles) -- outputs are
-// then wrong by construction.
+// NWV waves per workgroup (16 vertices each).
 // WP: also store the un-skinned vertices p = template + coef . dirs (B, V, 3) -- what the backward of the skinning needs
 // (training through the vertex-space loss); 8 instead of 4 store instructions per tile and wave.
 // (Whole-row stores through an LDS image of the tile -- every wave puts its 16 x 16 x 3 results into [16 frames][128 vertices
@@ -573,7 +571,7 @@ __device__ __forceinline__ void vm_wait_n(int n) {   // n = (pieces per load gro
 // product runs on ONE fp16 plane of `dirs` (72 registers instead of 144) and ONE fp16 coefficient plane (12 KB tile records
 // [coef fp16 6 KB | blend rows 6 KB] written by msmd_lbs_tiles_f16): 1 MFMA per K group and coordinate instead of 3.  The
 // operands' own rounding (2^-12 relative on offsets of <= ~0.03) stays under the fp16 step of the stored vertex.
-template <int KG, int NS, int NWV, int ABL = 0, bool WP = false, int RB = 0, bool OUT16 = false, bool F16P = false>
+template <int KG, int NS, int NWV, bool WP = false, int RB = 0, bool OUT16 = false, bool F16P = false>
 __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void lbs_skin_v2_kernel(const unsigned char* __restrict__ tiles,
                         const float* __restrict__ tmpl, const bf16_t* __restrict__ dirs_hl,
@@ -604,6 +602,8 @@ void lbs_skin_v2_kernel(const unsigned char* __restrict__ tiles,
   // workgroups go to the XCDs round-robin (L & 7).  Every frame split of a vertex slice runs on ONE XCD (its dirs stay
   // in that L2); each XCD owns vt8 ADJACENT slices and walks them fastest, so the 128-byte lines two neighbouring slices
   // share in a frame row meet in one L2 (554 vs 588 us at 25 600 frames against dealing the slices one by one).
+  // xcd_adj = 0 is that one-by-one dealing; every launch passes 1.  (The argument stays: without it two instantiations
+  // came out with another scalar register count and a shuffled tail, which nothing here set out to change.)
   const int v_tile = xcd_adj ? (L & 7) * vt8 + ((L >> 3) % vt8) : (L & 7) + 8 * ((L >> 3) % vt8);
   if (v_tile >= vtn) return;
   const int f_begin = ((L >> 3) / vt8) * frames_per_block;
@@ -682,14 +682,9 @@ void lbs_skin_v2_kernel(const unsigned char* __restrict__ tiles,
       const bf16x8 al = __builtin_bit_cast(bf16x8, *(const u32x4*)(sc + (((F16P ? 0 : Kp / 8) + 4 * g + q) * 16 + i) * 16));
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
-        if constexpr (ABL & 4) {
-          if (g == 0) accp[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, __builtin_bit_cast(bf16x8, dh[c][g]), accp[c], 0, 0, 0);
-          asm volatile("" :: "v"(dh[c][g]), "v"(dl[c][F16P ? 0 : g]), "v"(ah), "v"(al));
-        } else {
-          accp[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, __builtin_bit_cast(bf16x8, dh[c][g]), accp[c], 0, 0, 0);
-          accp[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, __builtin_bit_cast(bf16x8, dl[c][F16P ? 0 : g]), accp[c], 0, 0, 0);
-          accp[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, __builtin_bit_cast(bf16x8, dh[c][g]), accp[c], 0, 0, 0);
-        }
+        accp[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, __builtin_bit_cast(bf16x8, dh[c][g]), accp[c], 0, 0, 0);
+        accp[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, __builtin_bit_cast(bf16x8, dl[c][F16P ? 0 : g]), accp[c], 0, 0, 0);
+        accp[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, __builtin_bit_cast(bf16x8, dh[c][g]), accp[c], 0, 0, 0);
       }
     }
     float px[4], py[4], pz[4];
@@ -705,13 +700,8 @@ void lbs_skin_v2_kernel(const unsigned char* __restrict__ tiles,
         // K slots 16 .. 31 are zero on the vertex side (wB), so lanes q >= 2 may feed any finite values: they re-read
         // octet q & 1 (no divergent branch, no select)
         const u32x4 fa = *(const u32x4*)(sat + ((m * 2 + (q & 1)) * 16 + i) * 16);
-        if constexpr (ABL & 2) {
-          T[k] = __builtin_bit_cast(f32x4, fa);
-          asm volatile("" :: "v"(wB));
-        } else {
-          T[k] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, fa), __builtin_bit_cast(f16x8, wB),
-                                                        f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-        }
+        T[k] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, fa), __builtin_bit_cast(f16x8, wB),
+                                                      f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
       }
 #pragma unroll
       for (int e = 0; e < 4; ++e) out[c][e] = fmaf(T[0][e], px[e], fmaf(T[1][e], py[e], fmaf(T[2][e], pz[e], T[3][e])));
@@ -736,8 +726,7 @@ void lbs_skin_v2_kernel(const unsigned char* __restrict__ tiles,
         asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(o.b) : "v"(lo2), "v"(up0));
         asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(o.c) : "v"(up1), "v"(up2));
         const int f = min(f0 + 4 * q + (oddl ? 2 : 0) + s2, B - 1);
-        if constexpr (ABL & 1) asm volatile("" :: "v"(o.a), "v"(o.b), "v"(o.c), "v"(f));
-        else *(U3*)((f16_t*)verts + ((long)f * V_ld + (ve & ~1)) * 3) = o;   // 8 lanes = 96 contiguous bytes per frame
+        *(U3*)((f16_t*)verts + ((long)f * V_ld + (ve & ~1)) * 3) = o;   // 8 lanes = 96 contiguous bytes per frame
       }
       return;
     }
@@ -747,8 +736,7 @@ void lbs_skin_v2_kernel(const unsigned char* __restrict__ tiles,
       const int f = min(f0 + 4 * q + e, B - 1);
       F3 o;
       o.x = out[0][e]; o.y = out[1][e]; o.z = out[2][e];
-      if constexpr (ABL & 1) asm volatile("" :: "v"(o.x), "v"(o.y), "v"(o.z), "v"(f));
-      else *(F3*)(verts + ((long)f * V + ve) * 3) = o;   // 16 lanes = 192 contiguous bytes per frame
+      *(F3*)(verts + ((long)f * V + ve) * 3) = o;   // 16 lanes = 192 contiguous bytes per frame
       if constexpr (WP) {
         F3 pp;
         pp.x = px[e]; pp.y = py[e]; pp.z = pz[e];
@@ -764,9 +752,9 @@ void lbs_skin_v2_kernel(const unsigned char* __restrict__ tiles,
     for (int t = 0; t < ntiles; ++t) {
       // ops younger than tile t's loads, in issue order: min(NS-2, ntiles-1-t) load groups (my_np each) and
       // min(NS-1, t) store groups (SPT each)
-      vm_wait_n((ABL & 9) ? 0 : my_np * min(NS - 2, ntiles - 1 - t) + SPT * min(NS - 1, t));
+      vm_wait_n(my_np * min(NS - 2, ntiles - 1 - t) + SPT * min(NS - 1, t));
       __builtin_amdgcn_s_barrier();
-      if (t + NS - 1 < ntiles && !(ABL & 8)) issue(t + NS - 1);
+      if (t + NS - 1 < ntiles) issue(t + NS - 1);
       do_tile(t);
     }
   } else {
@@ -804,66 +792,35 @@ static int lbs_skin_v2_impl(const void* skin_tiles, const float* v_template, con
                             int V_ld16 = 0, bool single_plane = false) {
   if (B <= 0 || V <= 0 || Vp < V || J != 5 || Kp != 192 || !skin_tiles) return 1;
   if (V_ld16 && (V_ld16 < V || (V_ld16 & 1) || vposed || ((uintptr_t)verts & 3))) return 1;
-  // tuning key 9: 1 = two 4-wave workgroups per CU (64 vertices each, 3-stage rings) instead of one 8-wave workgroup
-  // (128 vertices, 4-stage ring).  Measured at 25 600 frames: 783 vs 732 us -- the smaller workgroups double the
-  // staged bytes per vertex and their phase drift buys less than that costs.
-  const bool big = MSMD_TUNE(9) != 1;
-  const int vpb = big ? 128 : 64;
-  const int vt = (V + vpb - 1) / vpb;
-  int splits = max(1, min((B + 63) / 64, ((big ? 1024 : 2048) + vt - 1) / vt));   // >= 64 frames per workgroup amortise the dirs load
+  // One 8-wave workgroup per CU (128 vertices, 4-stage ring).  Two 4-wave workgroups per CU (64 vertices each, 3-stage
+  // rings) measured 783 vs 732 us at 25 600 frames: the smaller workgroups double the staged bytes per vertex and their
+  // phase drift buys less than that costs.
+  const int vt = (V + 127) / 128;
+  int splits = max(1, min((B + 63) / 64, (1024 + vt - 1) / vt));   // >= 64 frames per workgroup amortise the dirs load
   int fpb = (((B + splits - 1) / splits) + 15) / 16 * 16;
   splits = (B + fpb - 1) / fpb;
   dim3 grid(((vt + 7) / 8) * 8 * splits);
-  const int xcd_adj = MSMD_TUNE(10) != 1;   // key 10 = 1: the round-1 dealing
-#define LBS_V2_LAUNCH(NS, NWV, ABL, ...)                                                                                    \
+  // every form: 8 waves, 4-stage ring of PIECES-KiB tile records; the template arguments after NWV are (WP, RB, OUT16, F16P)
+#define LBS_V2_LAUNCH(PIECES, ...)                                                                                     \
   do {                                                                                                                 \
-    constexpr int lds = NS * 18 * 1024;                                                                                \
-    auto kfn = lbs_skin_v2_kernel<6, NS, NWV, ABL, false, ##__VA_ARGS__>;                                                                 \
-    (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);                       \
-    hipLaunchKernelGGL(kfn, grid, dim3(64 * NWV), lds, (hipStream_t)stream, (const unsigned char*)skin_tiles,           \
-                       v_template, (const bf16_t*)dirs_hl, lbs_weights, verts, B, V, Vp, fpb, vt, \
-                       (float*)nullptr, xcd_adj, shape_varies, tmpl_folded, 0);                                                                           \
+    constexpr int lds = 4 * PIECES * 1024;                                                                             \
+    auto kfn = lbs_skin_v2_kernel<6, 4, 8, __VA_ARGS__>;                                                               \
+    (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);                      \
+    hipLaunchKernelGGL(kfn, grid, dim3(512), lds, (hipStream_t)stream, (const unsigned char*)skin_tiles, v_template,   \
+                       (const bf16_t*)dirs_hl, lbs_weights, verts, B, V, Vp, fpb, vt, vposed, /* xcd_adj */ 1, shape_varies, \
+                       tmpl_folded, V_ld16);                                                                           \
   } while (0)
   if (vposed) {
-    constexpr int lds = 4 * 18 * 1024;
-    auto kfn = lbs_skin_v2_kernel<6, 4, 8, 0, true>;
-    (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    const int vt8w = (V + 127) / 128;
-    hipLaunchKernelGGL(kfn, grid, dim3(512), lds, (hipStream_t)stream, (const unsigned char*)skin_tiles,
-                       v_template, (const bf16_t*)dirs_hl, lbs_weights, verts, B, V, Vp, fpb, vt8w, vposed, xcd_adj, (const int*)nullptr, (const float*)nullptr, 0);
-#ifdef MSMD_EXPERIMENTAL
-  } else if (!big) {
-    LBS_V2_LAUNCH(3, 4, 0);
-  } else if (MSMD_TUNE(8)) {
-    switch (MSMD_TUNE(8)) {   // ablation builds (tools/lbs_ablate.py)
-      case 1: LBS_V2_LAUNCH(4, 8, 1); break;
-      case 2: LBS_V2_LAUNCH(4, 8, 2); break;
-      case 4: LBS_V2_LAUNCH(4, 8, 4); break;
-      case 8: LBS_V2_LAUNCH(4, 8, 8); break;
-      case 7: LBS_V2_LAUNCH(4, 8, 7); break;
-      case 15: LBS_V2_LAUNCH(4, 8, 15); break;
-      default: LBS_V2_LAUNCH(4, 8, 0); break;         // 100: one barrier per tile (the round-2a schedule)
-    }
-#endif
+    LBS_V2_LAUNCH(18, true);
   } else if (V_ld16 && single_plane) {
     // (143 registers.  Twelve-wave workgroups of 192 vertices at three waves per SIMD measured the same as these eight-wave ones:
     // 0.387-0.392 against 0.388-0.394 ms at 25 600 frames; two 8-wave workgroups per CU need 128 registers and spilled 24 bytes
     // into the counted-vmcnt loop.)
-    constexpr int lds = 4 * 12 * 1024;
-    auto kfn = lbs_skin_v2_kernel<6, 4, 8, 0, false, 2, true, true>;
-    (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    hipLaunchKernelGGL(kfn, grid, dim3(512), lds, (hipStream_t)stream, (const unsigned char*)skin_tiles, v_template,
-                       (const bf16_t*)dirs_hl, lbs_weights, verts, B, V, Vp, fpb, vt, (float*)nullptr, xcd_adj, shape_varies,
-                       tmpl_folded, V_ld16);
+    LBS_V2_LAUNCH(12, false, 2, true, true);
   } else if (V_ld16) {
-    constexpr int lds = 4 * 18 * 1024;
-    auto kfn = lbs_skin_v2_kernel<6, 4, 8, 0, false, 2, true>;
-    (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    hipLaunchKernelGGL(kfn, grid, dim3(512), lds, (hipStream_t)stream, (const unsigned char*)skin_tiles, v_template,
-                       (const bf16_t*)dirs_hl, lbs_weights, verts, B, V, Vp, fpb, vt, (float*)nullptr, xcd_adj, shape_varies,
-                       tmpl_folded, V_ld16);
+    LBS_V2_LAUNCH(18, false, 2, true);
   } else {
-    LBS_V2_LAUNCH(4, 8, 0, 2);                        // one barrier per two tiles + wave priorities
+    LBS_V2_LAUNCH(18, false, 2);                      // one barrier per two tiles + wave priorities
   }
 #undef LBS_V2_LAUNCH
   MSMD_RETURN_LAST();
@@ -911,7 +868,7 @@ extern "C" int msmd_lbs_tiles_f16(const void* skin_tiles, void* tiles16, int B, 
 extern "C" int msmd_lbs_skin_v2_train(const void* skin_tiles, const float* v_template,
                                       const void* dirs_hl, const float* lbs_weights, float* verts, float* v_posed, int B,
                                       int J, int V, int Vp, int Kp, msmd_stream_t stream) {
-  if (!v_posed || MSMD_TUNE(9) == 1) return 1;
+  if (!v_posed) return 1;
   return lbs_skin_v2_impl(skin_tiles, v_template, dirs_hl, lbs_weights, verts, v_posed, B, J, V, Vp, Kp, stream);
 }
 

@@ -40,8 +40,6 @@ struct GemmArgs {
   float* stats_out = nullptr; float ln_eps = 1e-5f;
   // flags bit 2 (MSMD_GEMM_STAGGER): the workgroups dispatched second onto their CU start `stagger_ticks` (100 MHz) late
   int stagger_ticks = 0;
-  // developer build only (msmd_exp_set_stamps): per-workgroup time stamps of the plain-epilogue path, 8 longs per workgroup
-  long* stamps = nullptr;
 };
 
 template <typename T> struct Mfma;
@@ -581,16 +579,16 @@ typedef __attribute__((address_space(1))) const void gbl_void_t;
 // EPI: which epilogues this instantiation carries.  0 = all of them behind run-time tests (training: pre-activation copy,
 // dropout, activation backward, both LayerNorm forms); 1 = the plain inference epilogue only (bias, activation, residual);
 // 2 / 3 = the LayerNorm-operand / LayerNorm-residual form only.  One instantiation with everything is 127 KB of code of which a
-// launch executes a few KB scattered among the branches it does not take: per-workgroup stamps (tools/gemm_stamps.py) put the
+// launch executes a few KB scattered among the branches it does not take: per-workgroup time stamps put the
 // epilogue of a 128 x 128 tile at 3.0 us for 32 outputs per lane (bias only), most of it instruction fetch.
 // EPIA = EPI + 10 * (1 + activation) when the activation is compiled in as well (11 / 21 plain with none / GELU, 12 / 22
 // LayerNorm-operand with none / GELU, 13 LayerNorm-residual with none): see act_out_c.
-template <typename TO, int BM, int BN, int WM, int WN, int NSTAGE, bool PIPE = false, typename TI = bf16_t, bool STAG = false, int EPIA = 0>
+template <typename TO, int BM, int BN, int WM, int WN, int NSTAGE, bool PIPE = false, typename TI = bf16_t, int EPIA = 0>
 // 8-wave workgroups whose ring fits twice into a CU's LDS are MEANT to run two per CU: 4 waves per SIMD = 128 registers
 // (the 192-row tile's LayerNorm epilogues drifted to 145 once, i.e. to one workgroup per CU: HuBERT-large 18.7 -> 21.4 ms).
 // Its everything-epilogue instantiation (EPI 0: dropout / pre-activation copies on a tall grid, no caller on the path) does not
 // fit 128 without spilling and keeps the register count the compiler picks.
-__global__ __launch_bounds__(WM * WN * 64, (STAG || (WM * WN == 8 && NSTAGE * (BM + BN) * 128 <= 80 * 1024 && (EPIA % 10 != 0 || BM * BN <= 128 * 128))) ? 4 : 1) void gemm2_kernel(const GemmArgs p) {
+__global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8 && NSTAGE * (BM + BN) * 128 <= 80 * 1024 && (EPIA % 10 != 0 || BM * BN <= 128 * 128)) ? 4 : 1) void gemm2_kernel(const GemmArgs p) {
   constexpr int EPI = EPIA % 10, ACTK = EPIA / 10 - 1;
   constexpr int NW = WM * WN, NT = NW * 64;
   constexpr int STAGE = (BM + BN) * 128;
@@ -611,10 +609,6 @@ __global__ __launch_bounds__(WM * WN * 64, (STAG || (WM * WN == 8 && NSTAGE * (B
   const bf16_t* __restrict__ W = (const bf16_t*)p.W + zo * p.strideW + zi * p.strideW2;
   const int m0 = m_tile * BM, n0 = n_tile * BN;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-#ifdef MSMD_EXPERIMENTAL
-  long stamp[5] = {0, 0, 0, 0, 0};
-  if (p.stamps) stamp[0] = (long)__builtin_amdgcn_s_memrealtime();
-#endif
 
   const bf16_t* src[LPT];
 #pragma unroll
@@ -658,7 +652,7 @@ __global__ __launch_bounds__(WM * WN * 64, (STAG || (WM * WN == 8 && NSTAGE * (B
     while ((long)(__builtin_amdgcn_s_memrealtime() - t0) < p.stagger_ticks) __builtin_amdgcn_s_sleep(16);
   }
   // LayerNorm-folding mode (msmd_gemm_ln; the 4 x 2-wave 128 x 128 tile only): the row statistics' loads go out now, consumed in the epilogue
-  constexpr bool LNK = (BN == 128 || BN == 64) && WN == 2 && (FM == 2 || FM == 3) && !STAG && sizeof(TO) == 2;   // slab = BN / 2
+  constexpr bool LNK = (BN == 128 || BN == 64) && WN == 2 && (FM == 2 || FM == 3) && sizeof(TO) == 2;   // slab = BN / 2
   // the 192-row tile has no registers to spare during the K loop (124 of 128): its statistics are loaded in the epilogue instead
   // (one batched round trip; with two workgroups per CU and grids of many rounds it hides under the neighbour's K loop)
   constexpr bool LN_LATE = FM == 3;
@@ -668,63 +662,10 @@ __global__ __launch_bounds__(WM * WN * 64, (STAG || (WM * WN == 8 && NSTAGE * (B
     else if (p.r_stats) ln_issue<FM>(p.r_stats, p.r_nt, p.M, m0 + wm, fr, fq, lnraw);
   }
   int stage = 0;
-  if constexpr (STAG) {
-    // Staggered halves (MI355X_MICROARCH.md, "Two waves per SIMD", item 9): the eight waves run the same program with one
-    // barrier per K tile, so SIMD partners reach their fragment reads, their MFMAs and the barrier together.  Waves 4-7
-    // (the younger wave of every SIMD) multiply tile k AFTER the barrier of tile k + 1, from fragments they read one
-    // iteration earlier: while waves 0-3 read the new tile, waves 4-7 keep the matrix pipe busy, and vice versa.  Same
-    // products in the same order per output element: results are bit-identical to the unstaggered kernel.
-    // MEASURED (round 3): 25-30 % SLOWER on every shape and 4.76 -> 5.64 ms on the forward step -- with two workgroups per CU
-    // the co-resident workgroup already fills the other's read phase, and the late half lengthens every tile's critical
-    // path.  Experimental build only (variant 41).
-    static_assert(NSTAGE == 2 && NW == 8, "stagger is written for the 2-stage, 8-wave kernel");
-    const bool late = __builtin_amdgcn_readfirstlane(wid) >= 4;
-    u32x4 fx[2][FM], fw[2][FN];
-    auto read_frags = [&](int st) {
-      const unsigned char* sa = smem + st * STAGE;
-      const unsigned char* sw = sa + BM * 128;
-#pragma unroll
-      for (int g = 0; g < 2; ++g) {
-#pragma unroll
-        for (int j = 0; j < FM; ++j) fx[g][j] = *(const u32x4*)(sa + lds_off(wm + j * 16 + fr, g * 4 + fq));
-#pragma unroll
-        for (int i = 0; i < FN; ++i) fw[g][i] = *(const u32x4*)(sw + lds_off(wn + i * 16 + fr, g * 4 + fq));
-      }
-    };
-    auto multiply = [&]() {
-#pragma unroll
-      for (int g = 0; g < 2; ++g)
-#pragma unroll
-        for (int i = 0; i < FN; ++i)
-#pragma unroll
-          for (int j = 0; j < FM; ++j) Mfma<TI>::run(fw[g][i], fx[g][j], acc[i][j]);
-    };
-    for (int kt = 0; kt < nk; ++kt) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      if (kt + 1 < nk) issue(kt + 1, stage ^ 1);
-      if (late && kt > 0) multiply();           // waves 4-7: tile kt - 1, from the fragments read before this barrier
-      __builtin_amdgcn_sched_barrier(0);
-      read_frags(stage);
-      __builtin_amdgcn_sched_barrier(0);
-      if (!late) multiply();                     // waves 0-3: this tile
-      // waves 4-7: the reads must have RETURNED before the wave arrives at the next barrier (after it any wave may re-stage
-      // this buffer); waves 0-3 have consumed theirs in the MFMAs above
-      else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_sched_barrier(0);
-      stage ^= 1;
-    }
-    if (late) multiply();
-    gemm_epilogue<TO, FM, FN, sizeof(TO) == 2>(p, acc, z, m0 + wm, n0 + wn, fr, fq);
-    return;
-  }
   for (int kt = 0; kt < nk; ++kt) {
     if (kt + NSTAGE - 2 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NSTAGE - 2) * LPT) : "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-#ifdef MSMD_EXPERIMENTAL
-    if (p.stamps && kt == 0) stamp[1] = (long)__builtin_amdgcn_s_memrealtime();
-#endif
     if (kt + NSTAGE - 1 < nk) issue(kt + NSTAGE - 1, (stage + NSTAGE - 1) % NSTAGE);
     const unsigned char* sa = smem + stage * STAGE;
     const unsigned char* sw = sa + BM * 128;
@@ -765,9 +706,6 @@ __global__ __launch_bounds__(WM * WN * 64, (STAG || (WM * WN == 8 && NSTAGE * (B
     }
     stage = (stage + 1 == NSTAGE) ? 0 : stage + 1;
   }
-#ifdef MSMD_EXPERIMENTAL
-  if (p.stamps) stamp[2] = (long)__builtin_amdgcn_s_memrealtime();
-#endif
   // the 192-row tile has no register to spare: the lane's fragment coordinates are derived again here instead of living
   // through the K loop (one of them went to scratch otherwise)
   int tid_e = tid;
@@ -802,20 +740,6 @@ __global__ __launch_bounds__(WM * WN * 64, (STAG || (WM * WN == 8 && NSTAGE * (B
     gemm_epilogue<TO, FM, FN, sizeof(TO) == 2, false, ACTK>(p, acc, z, m0 + wm_e, n0 + wn_e, fr_e, fq_e);
   };
   run_epilogue();
-#ifdef MSMD_EXPERIMENTAL
-  if (p.stamps) {      // per-workgroup stamps (tools/gemm_stamps.py): entry, first tile landed, K loop done, stores issued, stores drained
-    stamp[3] = (long)__builtin_amdgcn_s_memrealtime();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    stamp[4] = (long)__builtin_amdgcn_s_memrealtime();
-    if (tid == 0) {
-      long* o = p.stamps + (long)pid * 8;
-      unsigned hw = 0, xcc = 0;
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-      o[0] = stamp[0]; o[1] = stamp[1]; o[2] = stamp[2]; o[3] = stamp[3]; o[4] = stamp[4]; o[5] = hw; o[6] = xcc; o[7] = m_tile * 1000 + n_tile;
-    }
-  }
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1331,8 +1255,8 @@ void gemm4_kernel(const GemmArgs p) {
 // gemm8_kernel: 256 x 256 x 64 tiles, ONE 8-wave workgroup per CU, the 8-phase schedule of cdna_hip_programming.md section 5
 // ("The 256^2 8-phase template") on this library's operand layout.  tools/gemm8_probe.hip is the bare schedule: 1 305 TFLOP/s at
 // 4096^3 and 1 303 at 16384 x 4096 x 3072 on random operands (the guide quotes 1 320-1 340 / 1 470 at 4096^3 / 8192^3) against
-// 1 012-1 105 for the 128 x 128 / 192 x 128 kernels above -- round 3's first attempt at this schedule (exp/gemm_variants.inc,
-// gemm8p: 902) lost a third of that to a branch around every staging step, per-fragment epilogues that fell into 528 bytes of
+// 1 012-1 105 for the 128 x 128 / 192 x 128 kernels above -- round 3's first attempt at this schedule (gemm8p, removed:
+// 902) lost a third of that to a branch around every staging step, per-fragment epilogues that fell into 528 bytes of
 // scratch and 8-byte stores in 32-byte runs.  What is different here:
 //   * the steady-state K tile is branch-free (the last two K tiles are separate copies without staging);
 //   * the epilogue goes through LDS: accumulators are written as fp32 into a 64-row x 256-column block (two blocks of 64 KB =
@@ -1828,37 +1752,21 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #undef G8_EBAR
 }
 
-#ifdef MSMD_EXPERIMENTAL
-// Developer knobs exist ONLY in the experimental build (make EXP=1 -> libmsmd_hip_exp.so): the product library has no
-// process-global state -- kernel variant and epilogue flags travel per call in `act` (include/msmd_hip.h).
-int g_tuning[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-long* g_gemm_stamps = nullptr;
-extern "C" int msmd_exp_set_stamps(long* p) { g_gemm_stamps = p; return 0; }
-extern "C" int msmd_exp_set_tuning(int key, int value) {
-  if (key < 0 || key >= 16) return 1;
-  g_tuning[key] = value;
-  return 0;
-}
-#include "exp/gemm_variants.inc"
-#endif
 
 // XCD grid over (M, N) tiles (p.mt, p.nt set).  With all 8 XCDs striped along M every L2 streams its own copy of the whole weight
 // matrix from HBM, while the activation rows (the previous kernel's output) are still warm: an XCD of an
 // (8 / xn) x xn grid reads 1 / xn of W and xn / 8 of A, so xn is picked per problem from  0.7 xn |A| + (8 / xn) |W|
 // (the 0.7 fitted on the qkv shape, where 2 x 4 ties with 8 x 1 and both trail 4 x 2).  Forward step, same-graph A/B
-// in both orders: 8 x 1 4.96 ms, 4 x 2 everywhere 4.89, this rule 4.88.  tuning key 7 forces xn = 1 / 2 / 4.
-template <int BM, int BN>
-static void gemm2_xcd_grid(GemmArgs& p) {
+// in both orders: 8 x 1 4.96 ms, 4 x 2 everywhere 4.89, this rule 4.88.
+// `lda` is A's row stride in LOGICAL elements, like p.K (the split-pair kernels pass p.lda / 2).  Bytes are counted at 2 per
+// element for every kernel: the split pairs' 4 scale both terms by the same power of two, which no comparison below sees.
+static void gemm2_xcd_grid(GemmArgs& p, long lda) {
+  const double a_bytes = 2.0 * p.M * (double)(p.rows_per_batch < p.M ? lda : p.K), w_bytes = 2.0 * p.N * (double)p.K;
+  double best = 1e30;
   int want_xn = 1;
-  if (MSMD_TUNE(7) == 1 || MSMD_TUNE(7) == 2 || MSMD_TUNE(7) == 4) {
-    want_xn = MSMD_TUNE(7);
-  } else {
-    const double a_bytes = 2.0 * p.M * (double)(p.rows_per_batch < p.M ? p.lda : p.K), w_bytes = 2.0 * p.N * (double)p.K;
-    double best = 1e30;
-    for (int xn = 1; xn <= 4; xn *= 2) {
-      const double c = 0.7 * xn * a_bytes + (8.0 / xn) * w_bytes;
-      if (c < best && p.nt >= xn) { best = c; want_xn = xn; }
-    }
+  for (int xn = 1; xn <= 4; xn *= 2) {
+    const double c = 0.7 * xn * a_bytes + (8.0 / xn) * w_bytes;
+    if (c < best && p.nt >= xn) { best = c; want_xn = xn; }
   }
   p.xn = p.nt >= want_xn ? want_xn : 1;
 }
@@ -1874,32 +1782,26 @@ static int launch_gemm2p(GemmArgs& p, hipStream_t st) {
     attr_done = true;
   }
   p.stagger_ticks = 0;
-#ifdef MSMD_EXPERIMENTAL
-  p.stamps = nullptr;
-#endif
   hipLaunchKernelGGL(kfn, dim3(512, 1, 1), dim3(WM * WN * 64), lds, st, p);
   MSMD_RETURN_LAST();
 }
 
-template <typename TO, int BM, int BN, int WM, int WN, int NSTAGE, bool PIPE = false, typename TI = bf16_t, bool STAG = false, int EPI = 0>
+template <typename TO, int BM, int BN, int WM, int WN, int NSTAGE, bool PIPE = false, typename TI = bf16_t, int EPI = 0>
 static int launch_gemm2(GemmArgs& p, int batch, hipStream_t st) {
   constexpr int lds = NSTAGE * (BM + BN) * 128;
   static bool attr_done = false;
-  auto kfn = gemm2_kernel<TO, BM, BN, WM, WN, NSTAGE, PIPE, TI, STAG, EPI>;
+  auto kfn = gemm2_kernel<TO, BM, BN, WM, WN, NSTAGE, PIPE, TI, EPI>;
   if (!attr_done) {
     (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     attr_done = true;
   }
   p.mt = (p.M + BM - 1) / BM; p.nt = (p.N + BN - 1) / BN;
-  gemm2_xcd_grid<BM, BN>(p);
+  gemm2_xcd_grid(p, p.lda);
   const int xm_n = 8 / p.xn;
   dim3 grid(((p.mt + xm_n - 1) / xm_n) * ((p.nt + p.xn - 1) / p.xn) * 8, 1, batch);
   // stagger (flags bit 2): only where the launch runs more than one round of two workgroups per CU
   p.stagger_ticks = ((p.flags & 4) && batch == 1 && NSTAGE * (BM + BN) * 128 <= 80 * 1024 && (long)p.mt * p.nt > 640)
                         ? (int)(100.0 * 0.5 * ((p.K / 64) * 0.5 + 3.0)) : 0;
-#ifdef MSMD_EXPERIMENTAL
-  p.stamps = g_gemm_stamps;
-#endif
   hipLaunchKernelGGL(kfn, grid, dim3(WM * WN * 64), lds, st, p);
   MSMD_RETURN_LAST();
 }
@@ -1922,7 +1824,7 @@ static int launch_gemm2_epi(GemmArgs& p, int batch, hipStream_t st) {
     // single-round) and the 192-row tile do not fit 128 registers in this form (20-128 bytes of scratch).
     if (batch == 1 && epi >= 1 && a && !(p.flags & 16)) {
       p.mt = (p.M + BM - 1) / BM; p.nt = (p.N + BN - 1) / BN;
-      gemm2_xcd_grid<BM, BN>(p);
+      gemm2_xcd_grid(p, p.lda);
       const int xm_n = 8 / p.xn;
       if (((p.mt + xm_n - 1) / xm_n) * ((p.nt + p.xn - 1) / p.xn) * 8 > 512) {
 #define MSMD_EPI_CASE(E) case E: return launch_gemm2p<TO, BM, BN, WM, WN, TI, E>(p, st)
@@ -1931,7 +1833,7 @@ static int launch_gemm2_epi(GemmArgs& p, int batch, hipStream_t st) {
       }
     }
   }
-#define MSMD_EPI_CASE(E) case E: return launch_gemm2<TO, BM, BN, WM, WN, NSTAGE, PIPE, TI, false, E>(p, batch, st)
+#define MSMD_EPI_CASE(E) case E: return launch_gemm2<TO, BM, BN, WM, WN, NSTAGE, PIPE, TI, E>(p, batch, st)
   if constexpr (LNK) {
     switch (epi + a) { MSMD_EPI_CASE(2); MSMD_EPI_CASE(12); MSMD_EPI_CASE(22); MSMD_EPI_CASE(3); MSMD_EPI_CASE(13); default: break; }
   }
@@ -1940,7 +1842,7 @@ static int launch_gemm2_epi(GemmArgs& p, int batch, hipStream_t st) {
     switch (epi + a) { MSMD_EPI_CASE(10); MSMD_EPI_CASE(20); default: break; }
   }
 #undef MSMD_EPI_CASE
-  return launch_gemm2<TO, BM, BN, WM, WN, NSTAGE, PIPE, TI, false, 0>(p, batch, st);
+  return launch_gemm2<TO, BM, BN, WM, WN, NSTAGE, PIPE, TI, 0>(p, batch, st);
 }
 
 template <typename TO, int BM, int BN, int WM, int WN, int NSTAGE, typename TI = bf16_t, bool ILV = false>
@@ -1954,18 +1856,7 @@ static int launch_gemm4(GemmArgs& p, int batch, hipStream_t st) {
   }
   if ((BM / WM / 16) * (BN / WN / 16) > 8 && (p.Z || p.p_drop > 0.f || (p.flags & 8))) return -1;   // lean epilogue: not a training call
   p.mt = (p.M + BM - 1) / BM; p.nt = (p.N + BN - 1) / BN;
-  int want_xn = 1;     // XCD grid over (M, N) tiles: the cost model of launch_gemm2
-  if (MSMD_TUNE(7) == 1 || MSMD_TUNE(7) == 2 || MSMD_TUNE(7) == 4) {
-    want_xn = MSMD_TUNE(7);
-  } else {
-    const double a_bytes = 2.0 * p.M * (double)(p.rows_per_batch < p.M ? p.lda : p.K), w_bytes = 2.0 * p.N * (double)p.K;
-    double best = 1e30;
-    for (int xn = 1; xn <= 4; xn *= 2) {
-      const double c = 0.7 * xn * a_bytes + (8.0 / xn) * w_bytes;
-      if (c < best && p.nt >= xn) { best = c; want_xn = xn; }
-    }
-  }
-  p.xn = p.nt >= want_xn ? want_xn : 1;
+  gemm2_xcd_grid(p, p.lda);
   const int xm_n = 8 / p.xn;
   dim3 grid(((p.mt + xm_n - 1) / xm_n) * ((p.nt + p.xn - 1) / p.xn) * 8, 1, batch);
   hipLaunchKernelGGL(kfn, grid, dim3(WM * WN * 64), lds, st, p);
@@ -2112,18 +2003,7 @@ static int launch_gemm2s(GemmArgs& p, int batch, hipStream_t st) {
     attr_done = true;
   }
   p.mt = (p.M + BM - 1) / BM; p.nt = (p.N + BN - 1) / BN;
-  int want_xn = 1;
-  if (MSMD_TUNE(7) == 1 || MSMD_TUNE(7) == 2 || MSMD_TUNE(7) == 4) {
-    want_xn = MSMD_TUNE(7);
-  } else {   // same cost model as launch_gemm2 (bytes are 4 per logical element here; the ratio is what matters)
-    const double a_bytes = 4.0 * p.M * (double)(p.rows_per_batch < p.M ? p.lda / 2 : p.K), w_bytes = 4.0 * p.N * (double)p.K;
-    double best = 1e30;
-    for (int xn = 1; xn <= 4; xn *= 2) {
-      const double c = 0.7 * xn * a_bytes + (8.0 / xn) * w_bytes;
-      if (c < best && p.nt >= xn) { best = c; want_xn = xn; }
-    }
-  }
-  p.xn = p.nt >= want_xn ? want_xn : 1;
+  gemm2_xcd_grid(p, p.lda / 2);      // p.lda is the fp16 stride (doubled by gemm_impl)
   const int xm_n = 8 / p.xn;
   dim3 grid(((p.mt + xm_n - 1) / xm_n) * ((p.nt + p.xn - 1) / p.xn) * 8, 1, batch);
   hipLaunchKernelGGL(kfn, grid, dim3(WM * WN * 64), lds, st, p);
@@ -2141,20 +2021,6 @@ static int dispatch_gemm2s(GemmArgs& p, int batch, hipStream_t st, int variant) 
       if (!gemm8s_takes(p, batch, sizeof(TO) == 2)) return -1;
       if (p.flags & 64) return p.act == MSMD_ACT_GELU ? launch_gemm8s<TO, 1, 1>(p, st) : launch_gemm8s<TO, 0, 1>(p, st);   // MSMD_GEMM_W_BELOW_32
       return p.act == MSMD_ACT_GELU ? launch_gemm8s<TO, 1, 0>(p, st) : launch_gemm8s<TO, 0, 0>(p, st);
-#ifdef MSMD_EXPERIMENTAL
-    case 2: return launch_gemm2s<TO, 128, 128, 4, 2, 4>(p, batch, st);   // 128 KB, deep ring
-    case 3: return launch_gemm2s<TO, 128, 128, 2, 2, 2>(p, batch, st);   // 4 waves of 64 x 64
-    case 4: return launch_gemm2s<TO, 256, 128, 4, 2, 3>(p, batch, st);   // 144 KB, 64 x 64 wave tiles
-    case 6: return launch_gemm2s<TO, 128, 64, 2, 2, 3>(p, batch, st);
-    case 7: return launch_gemm2s<TO, 64, 128, 2, 2, 3>(p, batch, st);
-    case 8: return launch_gemm2s<TO, 128, 128, 2, 2, 4>(p, batch, st);
-    case 9: return launch_gemm2s<TO, 128, 128, 4, 2, 3>(p, batch, st);   // 96 KB
-    case 10: return launch_gemm2s<TO, 128, 256, 2, 4, 3>(p, batch, st);  // 144 KB
-    case 11: return launch_gemm3<TO, f16_t, 2, 128, 128, 4, 2, 4>(p, batch, st);   // 1 workgroup / CU, pipelined reads
-    case 12: return launch_gemm3<TO, f16_t, 2, 128, 128, 4, 2, 3>(p, batch, st);
-    case 13: return launch_gemm3<TO, f16_t, 2, 128, 128, 2, 4, 4>(p, batch, st);
-    case 15: return launch_gemm3<TO, f16_t, 2, 128, 128, 4, 2, 4, 4>(p, batch, st);   // + 4 loader waves
-#endif
     default: return -1;
   }
 }
@@ -2162,7 +2028,7 @@ static int dispatch_gemm2s(GemmArgs& p, int batch, hipStream_t st, int variant) 
 // Product variants: 14 = 256 x 64 for narrow outputs; 17 = 128 x 128, 8 waves (4 x 2), 2-stage ring, fragment reads of both k-steps issued first (default
 // once the grid fills the chip); 13 = the same tile with the compiler's own read / multiply interleave; 9 / 12 = 64 x 64
 // tiles with a 4- / 2-stage ring for grids that would not fill the chip.  Every other family that was built and measured
-//  lives in exp/gemm_variants.inc and is compiled only with -DMSMD_EXPERIMENTAL.
+// lost and was removed: its numbers are in DESIGN.md section 5 / 5b.
 template <typename TO>
 static int dispatch_gemm2(GemmArgs& p, int batch, hipStream_t st, int variant) {
   switch (variant) {
@@ -2180,53 +2046,6 @@ static int dispatch_gemm2(GemmArgs& p, int batch, hipStream_t st, int variant) {
     case 62: return launch_gemm4<TO, 128, 128, 4, 2, 2>(p, batch, st);                   // 64 KB, 2 workgroups / CU: variant 17's tile
     case 63: return launch_gemm4<TO, 256, 128, 4, 2, 3, bf16_t, true>(p, batch, st);     // 60 with the refill's DMA between the MFMAs
     case 64: return launch_gemm4<TO, 256, 128, 4, 2, 2, bf16_t, true>(p, batch, st);     // 63 with a 2-stage ring (96 KB)
-#ifdef MSMD_EXPERIMENTAL
-    case 41: return launch_gemm2<TO, 128, 128, 4, 2, 2, true, bf16_t, true>(p, batch, st);   // 17 with waves 4-7 staggered: -25 % (5c)
-    case 40: return launch_gemm8p<TO>(p, batch, st);   // 256 x 256, 8-phase schedule, one workgroup per CU (round 3: slower, see exp/)
-    case 1: return launch_gemm2<TO, 128, 128, 2, 2, 2>(p, batch, st);
-    case 2: return launch_gemm2<TO, 128, 128, 2, 2, 3>(p, batch, st);
-    case 3: return launch_gemm2<TO, 128, 128, 2, 2, 4>(p, batch, st);
-    case 4: return launch_gemm2<TO, 256, 128, 4, 2, 3>(p, batch, st);
-    case 5: return launch_gemm2<TO, 256, 256, 2, 4, 2>(p, batch, st);
-    case 6: return launch_gemm2<TO, 128, 256, 2, 4, 3>(p, batch, st);
-    case 7: return launch_gemm2<TO, 64, 128, 1, 4, 4>(p, batch, st);
-    // more, smaller tiles with a deeper ring for the M = 6400 encoder shapes (round 3: see DESIGN 5c for the numbers)
-    case 48: return launch_gemm2<TO, 128, 64, 4, 2, 3, true>(p, batch, st);   // 72 KB: 2 workgroups / CU, 2 stages in flight each
-    case 49: return launch_gemm2<TO, 128, 64, 4, 2, 2, true>(p, batch, st);   // 48 KB: 3 workgroups / CU
-    case 50: return launch_gemm2<TO, 64, 128, 2, 4, 3, true>(p, batch, st);
-    case 51: return launch_gemm2<TO, 128, 64, 4, 2, 4, true>(p, batch, st);   // 96 KB: 1 workgroup / CU, 3 stages in flight
-    // positional-conv candidates (N = 48 per group, 6400 x 48 x 6144 x 16 groups; variant 9: 140 us, 12: 120 us):
-    case 42: return launch_gemm2<TO, 256, 64, 4, 1, 2>(p, batch, st);         // 94 us
-    case 43: return launch_gemm2<TO, 256, 64, 4, 1, 2, true>(p, batch, st);   // 86 us   (product variant 14, 8 waves: 85 us)
-    case 44: return launch_gemm2<TO, 128, 64, 4, 1, 2, true>(p, batch, st);   // 124 us
-    case 46: return launch_gemm2<TO, 256, 64, 4, 1, 3, true>(p, batch, st);   // 148 us (one workgroup per CU)
-    case 8: return launch_gemm2<TO, 128, 64, 4, 1, 4>(p, batch, st);          // 190 us
-    case 10: return launch_gemm2<TO, 128, 64, 2, 2, 3>(p, batch, st);
-    case 11: return launch_gemm2<TO, 64, 128, 2, 2, 3>(p, batch, st);
-    case 47: return launch_gemm2<TO, 128, 64, 2, 2, 2>(p, batch, st);
-    case 56: return launch_gemm2<TO, 64, 128, 2, 2, 2>(p, batch, st);
-    case 16: return launch_gemm2<TO, 128, 128, 2, 4, 2>(p, batch, st);
-    case 18: return launch_gemm2<TO, 128, 128, 2, 4, 2, true>(p, batch, st);
-    case 19: return launch_gemm2<TO, 64, 64, 2, 2, 2, true>(p, batch, st);
-    case 20: return launch_gemm2<TO, 64, 64, 2, 2, 4, true>(p, batch, st);
-    case 21: return launch_gemm2<TO, 128, 128, 2, 2, 2, true>(p, batch, st);
-    case 22: return launch_gemm2<TO, 256, 128, 4, 2, 3, true>(p, batch, st);
-    case 23: return launch_gemm2<TO, 128, 128, 4, 2, 3, true>(p, batch, st);
-    case 24: return launch_gemm2<TO, 256, 256, 2, 4, 2, true>(p, batch, st);
-    case 25: return launch_gemm2<TO, 256, 256, 4, 2, 2, true>(p, batch, st);
-    case 26: return launch_gemm2<TO, 128, 256, 2, 4, 3, true>(p, batch, st);
-    case 27: return launch_gemm2<TO, 256, 128, 4, 2, 2, true>(p, batch, st);
-    case 28: return launch_gemm2k<TO>(p, batch, st);
-    case 37: return launch_gemm2<TO, 128, 96, 2, 2, 2, true>(p, batch, st);
-    case 38: return launch_gemm2<TO, 128, 96, 2, 2, 3, true>(p, batch, st);
-    case 30: return launch_gemm3<TO, bf16_t, 1, 256, 128, 4, 2, 3>(p, batch, st);
-    case 31: return launch_gemm3<TO, bf16_t, 1, 256, 256, 2, 4, 2>(p, batch, st);
-    case 32: return launch_gemm3<TO, bf16_t, 1, 128, 128, 4, 2, 4>(p, batch, st);
-    case 33: return launch_gemm3<TO, bf16_t, 1, 128, 256, 2, 4, 3>(p, batch, st);
-    case 34: return launch_gemm3<TO, bf16_t, 1, 256, 128, 4, 2, 3, 4>(p, batch, st);   // + 4 loader waves
-    case 35: return launch_gemm3<TO, bf16_t, 1, 128, 128, 4, 2, 4, 4>(p, batch, st);
-    case 36: return launch_gemm3<TO, bf16_t, 1, 128, 256, 2, 4, 3, 4>(p, batch, st);
-#endif
     default: return -1;
   }
 }
@@ -2309,7 +2128,7 @@ static int gemm_impl(const void* A, const void* W, const float* bias, const void
     }
     hipStream_t st = (hipStream_t)stream;
     const int nz = batch * batch_inner;
-    int variant = MSMD_TUNE(3) > 0 ? MSMD_TUNE(3) : hint;
+    int variant = hint;
     if (variant == 80 && !gemm8s_takes(p, nz, out_dtype == MSMD_F16X2)) variant = 0;   // a hint the call cannot follow
     if (variant == 0) {
       const long tiles128 = (long)((M + 127) / 128) * ((N + 127) / 128) * nz;
@@ -2347,10 +2166,10 @@ static int gemm_impl(const void* A, const void* W, const float* bias, const void
     p.flags &= ~2;   // paired stores need 16-byte aligned row pairs
   hipStream_t st = (hipStream_t)stream;
   const int nz = batch * batch_inner;
-  if (in_dtype == MSMD_BF16 && (K % 64) == 0 && MSMD_TUNE(0) >= 0) {
-    // Measured on MI355X (tools/bench_gemm.py): the 128x128 LDS-DMA kernel wins once the grid fills the
+  if (in_dtype == MSMD_BF16 && (K % 64) == 0) {
+    // Measured on MI355X: the 128x128 LDS-DMA kernel wins once the grid fills the
     // chip at 2 workgroups per CU; below that, 64x64 tiles (deep ring for long K) keep more CUs busy.
-    int variant = MSMD_TUNE(0) ? MSMD_TUNE(0) : hint;
+    int variant = hint;
     if (variant == 80 && !gemm8_takes(p, nz, osz)) variant = 0;     // a hint the call cannot follow: the library's own choice
     if (variant == 0) {
       const long tiles128 = (long)((M + 127) / 128) * ((N + 127) / 128) * nz;
@@ -2365,19 +2184,15 @@ static int gemm_impl(const void* A, const void* W, const float* bias, const void
       } else if (N > 64 && tall_rounds_favour_192(M, tiles128, tiles192) && !z_out && !(p_drop > 0.f) && !(flags & 8) && out_dtype == MSMD_BF16) {
         variant = 15;      // inference epilogues only: the 192-row tile's everything-epilogue runs one workgroup per CU
       } else if (N > 64 && tiles128 >= 192) {
-        variant = MSMD_TUNE(4) ? 13 : 17;  // 128x128, 8 waves (4x2), 2-stage ring, 2 workgroups/CU, fragment reads pipelined
-        // experiment knobs (tools/ab_graph.py): 5 = variant for M >= 20000 (conv stack), 6 = variant for the rest
-        if (M >= 20000 && MSMD_TUNE(5) > 0) variant = MSMD_TUNE(5);
-        if (M < 20000 && MSMD_TUNE(6) > 0) variant = MSMD_TUNE(6);
-      }
-      else if (N <= 64 && (long)((M + 255) / 256) * nz >= 256) variant = 14;   // the positional conv: 256 x 64 tiles, 140 -> 85 us
+        variant = 17;  // 128x128, 8 waves (4x2), 2-stage ring, 2 workgroups/CU, fragment reads pipelined
+      } else if (N <= 64 && (long)((M + 255) / 256) * nz >= 256) variant = 14;   // the positional conv: 256 x 64 tiles, 140 -> 85 us
       else variant = (K >= 1024) ? 9 : 12;
     }
     const int r = out_dtype == MSMD_BF16 ? dispatch_gemm2<bf16_t>(p, nz, st, variant)
                                          : dispatch_gemm2<float>(p, nz, st, variant);
     if (r >= 0) return r;
   }
-  if (in_dtype == MSMD_F16 && (out_dtype == MSMD_F16 || out_dtype == MSMD_F32) && (K % 64) == 0 && MSMD_TUNE(0) >= 0) {
+  if (in_dtype == MSMD_F16 && (out_dtype == MSMD_F16 || out_dtype == MSMD_F32) && (K % 64) == 0) {
     // fp16 storage: same LDS-DMA kernels with v_mfma_f32_16x16x32_f16 (the heuristic's variants only)
     const long tiles128 = (long)((M + 127) / 128) * ((N + 127) / 128) * nz;
     const bool no_hint = !hint || (hint == 80 && !gemm8_takes(p, nz, osz));

@@ -40,7 +40,6 @@ struct TnArgs {
   long b_wstride;
   float inv_rpw;
   int accumulate;  // C += product, colsum += sums (gradient accumulation straight into .grad)
-  int plain_order; // tuning key 1 = 1: items in (tile, split) launch order instead of XCD-contiguous eighths
 };
 
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
@@ -99,8 +98,8 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(const TnArgs p) {
   {
     const int items = p.nt_n * p.nt_k * p.splits;
     const int per_xcd = (items + 7) >> 3;
-    const int lin = p.plain_order ? (int)blockIdx.x : (int)(blockIdx.x & 7) * per_xcd + (int)(blockIdx.x >> 3);
-    if (lin >= items || (!p.plain_order && (int)(blockIdx.x >> 3) >= per_xcd)) return;
+    const int lin = (int)(blockIdx.x & 7) * per_xcd + (int)(blockIdx.x >> 3);
+    if (lin >= items || (int)(blockIdx.x >> 3) >= per_xcd) return;
     split = lin % p.splits;
     const int t = lin / p.splits;
     if (p.nt_n >= p.nt_k) { n_tile = t / p.nt_k; k_tile = t % p.nt_k; }
@@ -329,7 +328,6 @@ extern "C" int msmd_gemm_tn(const void* A, const void* B, float* C, float* colsu
   const int forced = (accumulate >> 8) & 0xff;   // per-call override of the contraction split count (tests, tuning)
   accumulate &= 1;
   if (forced > 0) splits = forced;
-  if (MSMD_TUNE(2) > 0) splits = MSMD_TUNE(2);
   splits = max(1L, min(splits, (long)max(1, nk / 4)));
   const long slab = (long)batch * N * K;
   if (!ws) splits = 1;
@@ -342,7 +340,6 @@ extern "C" int msmd_gemm_tn(const void* A, const void* B, float* C, float* colsu
   p.b_wstride = b_window_stride; p.inv_rpw = p.b_rpw ? 1.0f / (float)p.b_rpw : 0.f;
   if (p.b_rpw && ((b_window_stride & 7) || M >= (1 << 24))) return 1;
   p.accumulate = accumulate ? 1 : 0;
-  p.plain_order = MSMD_TUNE(1) == 1;
   if (p.splits > 1 && colsum && !accumulate) {
     hipError_t e = msmd_zero_async(colsum, sizeof(float) * N, st);
     if (e != hipSuccess) return (int)e;

@@ -426,13 +426,9 @@ def gemm_act_bwd(dy, wt, z, act, p_drop=0.0, rng_state=None, site=0):
 
 
 def exp_set_tuning(key, value):
-    """Developer builds only (make -C csrc EXP=1; MSMD_LIB=.../libmsmd_hip_exp.so): msmd_exp_set_tuning(key, value).
-    The product library has no such switch -- use the per-call `variant` / `flags` / `splits` arguments."""
-    lib = _lib.load()
-    fn = getattr(lib, "msmd_exp_set_tuning", None)
-    if fn is None:
-        raise _lib.MsmdLibraryError("msmd_exp_set_tuning needs the experimental library (make -C csrc EXP=1, MSMD_LIB=...)")
-    _lib.check(fn(int(key), int(value)), "msmd_exp_set_tuning")
+    """Kept as a name for callers of the removed experimental library: the library has no process-global switch."""
+    raise _lib.MsmdLibraryError("msmd_exp_set_tuning: the experimental library and its tuning keys were removed; "
+                                "use the per-call `variant` / `flags` / `splits` arguments")
 
 
 g_tn_split = True
