@@ -477,6 +477,15 @@ int msmd_lbs_skin_bwd(const float* grad_verts, const float* v_posed, const float
 int msmd_landmarks(const float* verts, const int* faces, const int* lmk_faces_idx, long idx_bstride,
                    const float* bary, long bary_bstride, float* out, int B, int V, int L, msmd_stream_t stream);
 
+/* Backward of msmd_landmarks: grad_lmk (B, L, 3) scattered to grad_verts (B, V, 3); faces / lmk_faces_idx / bary and their
+ * batch strides exactly as the forward takes them.  Landmarks that share a vertex are summed without atomics, in
+ * (landmark, corner) order: the result is bit-identical from run to run.  accumulate == 0: every vertex of grad_verts is
+ * written (untouched ones with 0, in the same launch); accumulate != 0: the sums are added into grad_verts.  L <= 1024.
+ * No gradient goes to the tables. */
+int msmd_landmarks_bwd(const float* grad_lmk, const int* faces, const int* lmk_faces_idx, long idx_bstride,
+                       const float* bary, long bary_bstride, float* grad_verts, int B, int V, int L, int accumulate,
+                       msmd_stream_t stream);
+
 /* Dynamic-contour LUT row (utils/flame.py:126-172): row (B) int32 from the neck-chain yaw; full_pose is (B, J*3)
  * axis-angle (pose2rot=True) or (B, J*9) rotation matrices (pose_is_matrix, pose2rot=False). */
 int msmd_dynamic_lmk_row(const float* full_pose, const int* neck_chain, int n_chain, int* row, int B, int J,
@@ -484,6 +493,8 @@ int msmd_dynamic_lmk_row(const float* full_pose, const int* neck_chain, int n_ch
 
 /* batch_rodrigues (utils/lbs.py:270-301): R (N, 3, 3) from rot_vecs (N, 3). */
 int msmd_batch_rodrigues(const float* rot_vecs, float* R, int N, msmd_stream_t stream);
+/* Its vector-Jacobian product: grad_rot_vecs (N, 3) from grad_R (N, 3, 3) and the forward's input. */
+int msmd_batch_rodrigues_bwd(const float* rot_vecs, const float* grad_R, float* grad_rot_vecs, int N, msmd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Rotation conversions (reference utils/rotation_conversions.py:38-569), elementwise over n items.
@@ -507,6 +518,13 @@ int msmd_batch_rodrigues(const float* rot_vecs, float* R, int N, msmd_stream_t s
 #define MSMD_ROT_QUAT_APPLY 15 /* in2 = points (n,3) */
 int msmd_rotation_convert(int op, const float* in, const float* in2, float* out, long n, int conv,
                           msmd_stream_t stream);
+/* The vector-Jacobian product of msmd_rotation_convert(op, ...): grad_in (n, in width) -- and grad_in2 (n, in2 width) for
+ * the two-operand ops, NULL otherwise -- from grad_out (n, out width) and the forward's INPUTS (intermediates are
+ * recomputed; the forward saves nothing).  The derivative is that of the branch the forward took, as the reference's
+ * autograd gives it: the Taylor branch below |angle| = 1e-6, zero through a _sqrt_positive_part argument <= 0, +-1
+ * through _copysign / standardize_quaternion, zero through a norm at 0. */
+int msmd_rotation_convert_bwd(int op, const float* in, const float* in2, const float* grad_out, float* grad_in,
+                              float* grad_in2, long n, int conv, msmd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Losses / training-step pieces (reference utils/common.py:198-620, 443-454, 769-832; training_script.py:548-551).

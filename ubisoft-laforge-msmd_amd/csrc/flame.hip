@@ -47,6 +47,59 @@ extern "C" int msmd_batch_rodrigues(const float* rot_vecs, float* R, int N, msmd
   MSMD_RETURN_LAST();
 }
 
+// Backward of rodrigues(): g_r from g_R (reference: autograd through utils/lbs.py:285-300).  With x = r + 1e-8,
+// angle = |x|, d = r / angle, R = I + sin K(d) + (1 - cos) K(d)^2:
+//   g_K = sin g + (1 - cos) (g K^T + K^T g),  g_angle = cos sum(g K) + sin sum(g K^2) - (g_d . r) / angle^2,
+//   g_r = g_d / angle + x g_angle / angle   (the epsilon sits in the norm only)
+__device__ __forceinline__ void rodrigues_bwd(const float* r, const float* g, float* gr) {
+  const float x = r[0] + 1e-8f, y = r[1] + 1e-8f, z = r[2] + 1e-8f;
+  const float angle = sqrtf(x * x + y * y + z * z);
+  const float rx = r[0] / angle, ry = r[1] / angle, rz = r[2] / angle;
+  const float s = sinf(angle), c = cosf(angle), sh = sinf(0.5f * angle);
+  const float c1 = 2.0f * sh * sh;      // 1 - cos without the cancellation: it scales g_d / angle, where u / angle^2 would show
+  const float K[9] = {0.f, -rz, ry, rz, 0.f, -rx, -ry, rx, 0.f};
+  float gK[9];
+  float gs = 0.f, gc1 = 0.f;
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      float kk = 0.f, t = 0.f;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        kk += K[i * 3 + k] * K[k * 3 + j];
+        t += g[i * 3 + k] * K[j * 3 + k] + K[k * 3 + i] * g[k * 3 + j];   // (g K^T + K^T g)[i][j]
+      }
+      gs += g[i * 3 + j] * K[i * 3 + j];
+      gc1 += g[i * 3 + j] * kk;
+      gK[i * 3 + j] = s * g[i * 3 + j] + c1 * t;
+    }
+  const float gd[3] = {gK[7] - gK[5], gK[2] - gK[6], gK[3] - gK[1]};
+  const float g_angle = c * gs + s * gc1 - (gd[0] * r[0] + gd[1] * r[1] + gd[2] * r[2]) / (angle * angle);
+  const float sc = angle > 0.f ? g_angle / angle : 0.f;
+  gr[0] = gd[0] / angle + x * sc; gr[1] = gd[1] / angle + y * sc; gr[2] = gd[2] / angle + z * sc;
+}
+
+__global__ void rodrigues_bwd_kernel(const float* __restrict__ rv, const float* __restrict__ gR, float* __restrict__ grv, int N) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  const float r[3] = {rv[i * 3], rv[i * 3 + 1], rv[i * 3 + 2]};
+  float g[9], o[3];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) g[k] = gR[(long)i * 9 + k];
+  rodrigues_bwd(r, g, o);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) grv[(long)i * 3 + k] = o[k];
+}
+
+extern "C" int msmd_batch_rodrigues_bwd(const float* rot_vecs, const float* grad_R, float* grad_rot_vecs, int N,
+                                        msmd_stream_t stream) {
+  if (N <= 0 || !rot_vecs || !grad_R || !grad_rot_vecs) return 1;
+  hipLaunchKernelGGL(rodrigues_bwd_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, rot_vecs, grad_R,
+                     grad_rot_vecs, N);
+  MSMD_RETURN_LAST();
+}
+
 // ---------------------------------------------------------------------------------------------------
 // Per-frame kinematics: 16 frames per 256-thread workgroup, 16 lanes per frame.  (The first version ran one 64-thread
 // workgroup per frame with the joint chain serial in lane 0: latency bound, 110 us for 25 600 frames -- a sixth of the
@@ -1015,6 +1068,65 @@ extern "C" int msmd_landmarks(const float* verts, const int* faces, const int* l
   if (B <= 0 || V <= 0 || L <= 0) return 1;
   hipLaunchKernelGGL(landmarks_kernel, dim3((B * L + 255) / 256), dim3(256), 0, (hipStream_t)stream, verts, faces,
                      lmk_faces_idx, idx_bstride, bary, bary_bstride, out, B, V, L);
+  MSMD_RETURN_LAST();
+}
+
+// Backward of landmarks_kernel: the (B, L, 3) landmark gradients scattered to the (B, V, 3) vertex gradients.  Several
+// landmarks may share a vertex and the sum must be the same from run to run, so there are no atomics: one workgroup per frame
+// lists the frame's 3 L contributions (vertex id, barycentric weight x landmark gradient) in LDS in (landmark, corner) order;
+// the FIRST contribution of each vertex id owns that vertex and adds up all contributions of the same id in list order,
+// then stores (accumulate = 0) or adds into (accumulate != 0) the vertex gradient.  With accumulate = 0 the same launch
+// zero-fills the frame's other vertices first (a barrier orders the fill before the owners' stores).
+#define LMK_BWD_MAXL 1024
+__global__ __launch_bounds__(256) void landmarks_bwd_kernel(const float* __restrict__ glmk, const int* __restrict__ faces,
+                                                            const int* __restrict__ idx, long idx_bs,
+                                                            const float* __restrict__ bary, long bary_bs,
+                                                            float* __restrict__ gverts, int V, int L, int accumulate) {
+  extern __shared__ __attribute__((aligned(16))) float s_lmk[];
+  const int C = 3 * L;
+  float* s_val = s_lmk;                 // (C, 3)
+  int* s_vid = (int*)(s_lmk + 3 * C);   // (C)
+  const int b = blockIdx.x;
+  float* gv = gverts + (long)b * V * 3;
+  for (int c = threadIdx.x; c < C; c += 256) {
+    const int l = c / 3, k = c - l * 3;
+    const int face = __ldg(idx + b * idx_bs + l);
+    const float w = bary[b * bary_bs + (long)l * 3 + k];
+    const float* gp = glmk + ((long)b * L + l) * 3;
+    s_vid[c] = __ldg(faces + (long)face * 3 + k);
+    s_val[c * 3] = gp[0] * w; s_val[c * 3 + 1] = gp[1] * w; s_val[c * 3 + 2] = gp[2] * w;
+  }
+  if (!accumulate) {
+    const int nw = V * 3;
+    if ((((uintptr_t)gv) & 15) == 0) {
+      const int nv = nw >> 2;
+      for (int i = threadIdx.x; i < nv; i += 256) ((float4*)gv)[i] = float4{0.f, 0.f, 0.f, 0.f};
+      for (int i = (nv << 2) + threadIdx.x; i < nw; i += 256) gv[i] = 0.f;
+    } else {
+      for (int i = threadIdx.x; i < nw; i += 256) gv[i] = 0.f;
+    }
+  }
+  __syncthreads();
+  for (int c = threadIdx.x; c < C; c += 256) {
+    const int vid = s_vid[c];
+    bool owner = (unsigned)vid < (unsigned)V;      // an id outside the mesh owns nothing
+    for (int p = 0; p < c && owner; ++p) owner = s_vid[p] != vid;
+    if (!owner) continue;
+    float sx = s_val[c * 3], sy = s_val[c * 3 + 1], sz = s_val[c * 3 + 2];
+    for (int p = c + 1; p < C; ++p)
+      if (s_vid[p] == vid) { sx += s_val[p * 3]; sy += s_val[p * 3 + 1]; sz += s_val[p * 3 + 2]; }
+    float* o = gv + (long)vid * 3;
+    if (accumulate) { sx += o[0]; sy += o[1]; sz += o[2]; }
+    o[0] = sx; o[1] = sy; o[2] = sz;
+  }
+}
+
+extern "C" int msmd_landmarks_bwd(const float* grad_lmk, const int* faces, const int* lmk_faces_idx, long idx_bstride,
+                                  const float* bary, long bary_bstride, float* grad_verts, int B, int V, int L, int accumulate,
+                                  msmd_stream_t stream) {
+  if (B <= 0 || V <= 0 || L <= 0 || L > LMK_BWD_MAXL || !grad_lmk || !faces || !lmk_faces_idx || !bary || !grad_verts) return 1;
+  hipLaunchKernelGGL(landmarks_bwd_kernel, dim3(B), dim3(256), (size_t)L * 3 * 4 * sizeof(float), (hipStream_t)stream, grad_lmk,
+                     faces, lmk_faces_idx, idx_bstride, bary, bary_bstride, grad_verts, V, L, accumulate);
   MSMD_RETURN_LAST();
 }
 

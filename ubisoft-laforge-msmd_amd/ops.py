@@ -12,6 +12,7 @@ import ctypes
 import os
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 
@@ -912,17 +913,62 @@ def lbs_skin_bwd(grad_verts, vposed, A, weight_planes):
     return dp, dA
 
 
-def landmarks(verts, faces_i32, lmk_faces_idx_i32, bary):
-    """lmk_faces_idx: (L,) / (1, L) shared or (B, L) per frame; bary likewise (.., L, 3)."""
+def _landmarks_launch(verts, faces_i32, idx, bc):
     lib = _lib.load()
     B, V, _ = verts.shape
-    idx = lmk_faces_idx_i32.reshape(-1, lmk_faces_idx_i32.shape[-1])
-    bc = bary.reshape(-1, bary.shape[-2], 3)
     L = idx.shape[1]
     out = torch.empty(B, L, 3, device=verts.device, dtype=torch.float32)
     _lib.check(lib.msmd_landmarks(_p(verts), _p(faces_i32), _p(idx), L if idx.shape[0] > 1 else 0, _p(bc),
                                   L * 3 if bc.shape[0] > 1 else 0, _p(out), B, V, L, _stream()), "msmd_landmarks")
     return out
+
+
+def landmarks_bwd(grad_lmk, faces_i32, idx, bc, V, out=None):
+    """-> grad_verts (B, V, 3): msmd_landmarks_bwd's deterministic scatter (no atomics; see include/msmd_hip.h).  With `out`
+    the sums are added into it."""
+    lib = _lib.load()
+    B, L, _ = grad_lmk.shape
+    gv = out if out is not None else torch.empty(B, V, 3, device=grad_lmk.device, dtype=torch.float32)
+    _lib.check(lib.msmd_landmarks_bwd(_p(grad_lmk), _p(faces_i32), _p(idx), L if idx.shape[0] > 1 else 0, _p(bc),
+                                      L * 3 if bc.shape[0] > 1 else 0, _p(gv), B, V, L, int(out is not None), _stream()),
+               "msmd_landmarks_bwd")
+    return gv
+
+
+def _wants_grad(*ts):
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts)
+
+
+class _LandmarksFn(torch.autograd.Function):
+    """msmd_landmarks with msmd_landmarks_bwd: the gradient goes to the vertices only (index tables are integers, the
+    barycentric tables are buffers)."""
+
+    @staticmethod
+    def forward(ctx, verts, faces_i32, idx, bc):
+        ctx.save_for_backward(faces_i32, idx, bc)      # saved, so that an in-place change of a table before backward raises
+        ctx.V = verts.shape[1]
+        return _landmarks_launch(verts, faces_i32, idx, bc)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        return landmarks_bwd(g.float().contiguous(), *ctx.saved_tensors, ctx.V), None, None, None
+
+
+LANDMARKS_BWD_MAX_L = 1024   # msmd_landmarks_bwd keeps a frame's 3 L contributions in LDS (include/msmd_hip.h)
+
+
+def landmarks(verts, faces_i32, lmk_faces_idx_i32, bary):
+    """lmk_faces_idx: (L,) / (1, L) shared or (B, L) per frame; bary likewise (.., L, 3).  Differentiable (first order) with
+    respect to verts: fp32-contiguous is then made by autograd ops, so the gradient returns in verts' dtype and layout."""
+    idx = lmk_faces_idx_i32.reshape(-1, lmk_faces_idx_i32.shape[-1])
+    bc = bary.reshape(-1, bary.shape[-2], 3)
+    if _wants_grad(verts):
+        if idx.shape[1] > LANDMARKS_BWD_MAX_L:
+            raise ValueError(f"landmarks: the differentiable pass takes at most {LANDMARKS_BWD_MAX_L} landmarks per frame, "
+                             f"got {idx.shape[1]}")
+        return _LandmarksFn.apply(verts.float().contiguous(), faces_i32, idx, bc.detach())
+    return _landmarks_launch(verts, faces_i32, idx, bc)
 
 
 def dynamic_lmk_row(full_pose, neck_chain_i32, pose_is_matrix=False):
@@ -935,7 +981,7 @@ def dynamic_lmk_row(full_pose, neck_chain_i32, pose_is_matrix=False):
     return row
 
 
-def batch_rodrigues(rot_vecs):
+def _batch_rodrigues_launch(rot_vecs):
     lib = _lib.load()
     N = rot_vecs.shape[0]
     R = torch.empty(N, 3, 3, device=rot_vecs.device, dtype=torch.float32)
@@ -943,17 +989,76 @@ def batch_rodrigues(rot_vecs):
     return R
 
 
-def rotation_convert(op, x, in_width, out_shape_tail, x2=None, conv=0):
-    """Generic elementwise rotation conversion: x (..., in_width[, in_width2]) -> (..., *out_shape_tail)."""
+class _RodriguesFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, rot_vecs):
+        ctx.save_for_backward(rot_vecs)
+        return _batch_rodrigues_launch(rot_vecs)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        (r,) = ctx.saved_tensors
+        lib = _lib.load()
+        gr = torch.empty_like(r)
+        _lib.check(lib.msmd_batch_rodrigues_bwd(_p(r), _p(g.float().contiguous()), _p(gr), r.shape[0], _stream()),
+                   "msmd_batch_rodrigues_bwd")
+        return gr
+
+
+def batch_rodrigues(rot_vecs):
+    """rot_vecs: (N, 3) fp32 contiguous.  Differentiable (first order: msmd_batch_rodrigues_bwd)."""
+    if _wants_grad(rot_vecs):
+        return _RodriguesFn.apply(rot_vecs)
+    return _batch_rodrigues_launch(rot_vecs)
+
+
+def _rotation_launch(op, x, x2, out_shape, conv):
     lib = _lib.load()
+    out = torch.empty(out_shape, device=x.device, dtype=torch.float32)
+    _lib.check(lib.msmd_rotation_convert(op, _p(x), _p(x2), _p(out), x.numel() // _ROT_IN_WIDTH[op], conv, _stream()),
+               "msmd_rotation_convert")
+    return out
+
+
+class _RotationFn(torch.autograd.Function):
+    """msmd_rotation_convert with msmd_rotation_convert_bwd.  The forward's inputs are all the backward needs."""
+
+    @staticmethod
+    def forward(ctx, x, x2, op, out_shape, conv):
+        ctx.save_for_backward(x, x2)
+        ctx.op, ctx.conv = op, conv
+        return _rotation_launch(op, x, x2, out_shape, conv)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        x, x2 = ctx.saved_tensors
+        lib = _lib.load()
+        g = g.float().contiguous()
+        gx = torch.empty_like(x)
+        gx2 = torch.empty_like(x2) if x2 is not None else None
+        n = x.numel() // _ROT_IN_WIDTH[ctx.op]
+        _lib.check(lib.msmd_rotation_convert_bwd(ctx.op, _p(x), _p(x2), _p(g), _p(gx), _p(gx2), n, ctx.conv, _stream()),
+                   "msmd_rotation_convert_bwd")
+        return gx, gx2, None, None, None
+
+
+_ROT_IN_WIDTH = (4, 9, 3, 4, 3, 9, 6, 9, 3, 3, 9, 4, 4, 4, 4, 4)   # floats per item of the first operand, by MSMD_ROT_* op
+
+
+def rotation_convert(op, x, in_width, out_shape_tail, x2=None, conv=0):
+    """Generic elementwise rotation conversion: x (..., in_width[, in_width2]) -> (..., *out_shape_tail).  With grad mode on
+    and an input that requires grad the call is differentiable (first order): the casts to contiguous fp32 below are then
+    autograd ops, so gradients return in the inputs' dtype and layout (and reduce over broadcast dimensions)."""
     x = x.contiguous().float()
-    n = x.numel() // in_width
     lead = x.shape[:-1] if in_width in (3, 4, 6) else x.shape[:-2]
-    out = torch.empty(*lead, *out_shape_tail, device=x.device, dtype=torch.float32)
+    out_shape = (*lead, *out_shape_tail)
     if x2 is not None:
         x2 = x2.contiguous().float()
-    _lib.check(lib.msmd_rotation_convert(op, _p(x), _p(x2), _p(out), n, conv, _stream()), "msmd_rotation_convert")
-    return out
+    if _wants_grad(x, x2):
+        return _RotationFn.apply(x, x2, op, out_shape, conv)
+    return _rotation_launch(op, x, x2, out_shape, conv)
 
 
 # ----------------------------------------------------------------------------- losses / training pieces

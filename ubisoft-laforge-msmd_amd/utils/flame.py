@@ -168,9 +168,7 @@ class FLAME(nn.Module):
         if torch.is_grad_enabled() and (betas.requires_grad or full_pose.requires_grad):
             # training through the vertex-space loss (reference training_script.py:167-176): differentiable pass --
             # per-frame kinematics by autograd on tiny tensors, per-vertex skinning forward / backward in HIP
-            if not pose2rot:
-                raise NotImplementedError("the differentiable FLAME pass takes axis-angle poses (pose2rot=True)")
-            vertices = _lbs.lbs_train(betas, full_pose, p["lbs"])
+            vertices = _lbs.lbs_train(betas, full_pose, p["lbs"], pose2rot=pose2rot)
         else:
             vertices, _ = _lbs.lbs(betas, full_pose, self.v_template, self.shapedirs, self.posedirs, self.J_regressor,
                                    self.parents, self.lbs_weights, pose2rot, self.dtype, constants=p["lbs"],

@@ -83,16 +83,27 @@ DEFAULT_PRECISION = "bf16x3"
 
 def lbs(betas, pose, v_template, shapedirs, posedirs, J_regressor, parents, lbs_weights, pose2rot=True,
         dtype=torch.float32, constants: LbsConstants = None, precision: str = None):
-    """reference utils/lbs.py:141-223.  Returns (verts (B, V, 3), posed joints (B, J, 3))."""
+    """reference utils/lbs.py:141-223.  Returns (verts (B, V, 3), posed joints (B, J, 3)).  With grad mode on and betas or
+    pose requiring grad: the differentiable pass (lbs_train), which has a single arithmetic -- precision "bf16x3", 5 joints;
+    anything else raises -- and agrees with the inference path to about 1e-5."""
     if dtype != torch.float32:
         raise TypeError("lbs runs in fp32")
     c = constants or _constants(v_template, shapedirs, posedirs, J_regressor, parents, lbs_weights)
     B = max(betas.shape[0], pose.shape[0])
-    betas = betas.float().expand(B, -1).contiguous()
-    pose = pose.float().reshape(pose.shape[0], -1).expand(B, -1).contiguous()
     precision = precision or DEFAULT_PRECISION
     if precision not in ("bf16x3", "bf16x3_valu", "fp32"):
         raise ValueError(f"Unknown LBS precision {precision}!")
+    if torch.is_grad_enabled() and (betas.requires_grad or pose.requires_grad):
+        # the reference's lbs() is differentiable: the differentiable pass (autograd kinematics + HIP skinning fwd / bwd).
+        # It has ONE arithmetic (msmd_lbs_skin_v2_train: split-bf16 products, fp32 accumulation; 5 joints, KP = 192), so
+        # another requested precision or joint count is an error here, not a silent substitution.
+        if precision != "bf16x3" or c.J != 5:
+            raise NotImplementedError(f"lbs: the differentiable pass runs precision='bf16x3' with 5 joints only "
+                                      f"(got precision={precision!r}, {c.J} joints)")
+        return lbs_train(betas.float().expand(B, -1), pose.float().reshape(pose.shape[0], -1).expand(B, -1), c,
+                         pose2rot=pose2rot, return_joints=True)
+    betas = betas.float().expand(B, -1).contiguous()
+    pose = pose.float().reshape(pose.shape[0], -1).expand(B, -1).contiguous()
     v2 = precision == "bf16x3" and c.J == 5
     split = precision != "fp32" and not v2
     res = ops.lbs_prepare(betas, pose, c.JS, c.parents, KP, pose_is_matrix=not pose2rot, want_split=split,
@@ -119,13 +130,15 @@ def _rodrigues_torch(r):
     return torch.eye(3, device=r.device, dtype=r.dtype)[None] + sin * K + (1 - cos) * torch.bmm(K, K)
 
 
-def kinematics_torch(c: LbsConstants, betas, pose):
+def kinematics_torch(c: LbsConstants, betas, pose, pose2rot=True, return_joints=False):
     """What msmd_lbs_prepare computes -- coef (B, KP) = [betas | R[1:] - I | 0] and the relative rigid transforms
     A (B, J, 12) -- as autograd ops on (B, J, 3, 3)-sized tensors (utils/lbs.py:141-223, 317-371): the per-frame part
-    of the differentiable FLAME pass.  The per-vertex part is SkinFn (HIP forward and backward)."""
+    of the differentiable FLAME pass.  The per-vertex part is SkinFn (HIP forward and backward).  pose is (B, J * 3)
+    axis-angle, or with pose2rot=False (B, J * 9) rotation matrices (Rodrigues skipped).  return_joints adds the posed
+    joints (B, J, 3)."""
     B, J = betas.shape[0], c.J
     joints = c.JS[0].view(1, J, 3) + (betas @ c.JS[1:]).view(B, J, 3)
-    R = _rodrigues_torch(pose.reshape(B * J, 3)).view(B, J, 3, 3)
+    R = _rodrigues_torch(pose.reshape(B * J, 3)).view(B, J, 3, 3) if pose2rot else pose.reshape(B, J, 3, 3)
     eye = torch.eye(3, device=R.device, dtype=R.dtype)
     coef = torch.cat([betas, (R[:, 1:] - eye).reshape(B, (J - 1) * 9),
                       betas.new_zeros(B, KP - betas.shape[1] - (J - 1) * 9)], dim=1)
@@ -139,6 +152,8 @@ def kinematics_torch(c: LbsConstants, betas, pose):
     for i in range(J):
         t = wt[i] - torch.bmm(wR[i], joints[:, i].unsqueeze(-1)).squeeze(-1)
         A.append(torch.cat([wR[i], t.unsqueeze(-1)], dim=-1).reshape(B, 12))
+    if return_joints:
+        return coef, torch.stack(A, dim=1), torch.stack(wt, dim=1)
     return coef, torch.stack(A, dim=1)
 
 
@@ -165,19 +180,23 @@ class SkinFn(torch.autograd.Function):
         return dcoef, dA, None
 
 
-def lbs_train(betas, pose, constants: LbsConstants):
-    """Differentiable lbs(): (betas (B, NB), axis-angle pose (B, J*3)) -> verts (B, V, 3) with gradients to both."""
-    coef, A = kinematics_torch(constants, betas.float(), pose.float())
+def lbs_train(betas, pose, constants: LbsConstants, pose2rot=True, return_joints=False):
+    """Differentiable lbs(): (betas (B, NB), pose (B, J*3) axis-angle or, with pose2rot=False, (B, J*9) matrices) ->
+    verts (B, V, 3) with gradients to both; return_joints: -> (verts, posed joints (B, J, 3)) as lbs() returns them."""
+    if return_joints:
+        coef, A, joints = kinematics_torch(constants, betas.float(), pose.float(), pose2rot, True)
+        return SkinFn.apply(coef, A, constants), joints
+    coef, A = kinematics_torch(constants, betas.float(), pose.float(), pose2rot)
     return SkinFn.apply(coef, A, constants)
 
 
 def batch_rodrigues(rot_vecs, epsilon=1e-8, dtype=torch.float32):
-    """reference utils/lbs.py:270-301."""
+    """reference utils/lbs.py:270-301.  Differentiable (first order); the gradient returns in rot_vecs' dtype."""
     return ops.batch_rodrigues(rot_vecs.float().contiguous())
 
 
 def vertices2landmarks(vertices, faces, lmk_faces_idx, lmk_bary_coords):
-    """reference utils/lbs.py:102-138."""
+    """reference utils/lbs.py:102-138.  Differentiable (first order) with respect to the vertices."""
     return ops.landmarks(vertices.float().contiguous(), faces.to(torch.int32).contiguous(),
                          lmk_faces_idx.to(torch.int32).contiguous(), lmk_bary_coords.float().contiguous())
 

@@ -1,7 +1,9 @@
 """Rotation conversions on the MI355X (public names of reference utils/rotation_conversions.py:38-569).
 
 Every function is one launch of csrc/rotations.hip's elementwise kernel; semantics follow the
-reference (PyTorch3D): real-first quaternions, small-angle Taylor branch under 1e-6.
+reference (PyTorch3D): real-first quaternions, small-angle Taylor branch under 1e-6.  With grad mode on and
+an input that requires grad every function is differentiable (first order): one launch of the kernel's
+vector-Jacobian product (msmd_rotation_convert_bwd), the derivative of the branch the forward took.
 """
 from __future__ import annotations
 
