@@ -88,15 +88,6 @@ int msmd_gemm(const void* A, const void* W, const float* bias, const void* resid
               int batch, long strideA, long strideW, long strideC, long strideBias, long strideR,
               msmd_stream_t stream);
 
-/* The shape rule of msmd_gemm / msmd_gemm_ln for their 256 x 256-tile kernel (variant 80: 16-bit operands and output of one
- * problem, N % 256 == 0, K % 64 == 0, K >= 128, inference epilogues): 1 when a call of this shape that the kernel can take
- * is routed to it, 0 otherwise.  Pure function of (M, N, K); lets a caller that times launches (bench.py's roofline leg) file
- * each one under the kernel that ran it.  No counterpart in the reference. */
-int msmd_gemm_256_tile_rule(int M, int N, int K);
-/* The same for MSMD_F16X2 operands (variant 80 of the split GEMM: one problem, N % 256 == 0, K % 32 == 0, K >= 64, fp32 or split
- * output); w_below_32 = the call carries MSMD_GEMM_W_BELOW_32 (the fold-free form of the kernel wins on more shapes). */
-int msmd_gemm_256_tile_rule_f16x2(int M, int N, int K, int w_below_32);
-
 /* msmd_gemm with the training epilogue:  C = dropout_p(act(A . W^T + bias)) + residual, and optionally
  * z_out = A . W^T + bias (the pre-activation the backward needs; layout and dtype of C).  The keep mask is
  * Philox4x32-10(rng_state[seed, step], site, (m * N + n) / 4) -- exactly msmd_dropout's mask on a contiguous (M, N)
@@ -129,6 +120,22 @@ int msmd_gemm_ex(const void* A, const void* W, const float* bias, const void* re
                  int in_dtype, int out_dtype, long lda, int rows_per_batch, long a_batch_stride, long ldw, long ldc,
                  long ldr, int act, int batch, long strideA, long strideW, long strideC, long strideBias, long strideR,
                  void* z_out, float p_drop, const unsigned long* rng_state, unsigned int site, msmd_stream_t stream);
+
+/* Which kernel a call would run: each query takes exactly the arguments of the call it mirrors (msmd_gemm_route those of
+ * msmd_gemm_ex; a msmd_gemm call is the same with z_out = NULL, p_drop = 0) and returns the MSMD_GEMM_VARIANT number the library
+ * would launch for them -- its own choice or the hint, 80 = the 256 x 256-tile kernel --, 0 for the generic kernel (operands
+ * the tiled kernels do not take, or a hint that names no variant of the operand type), -1 for a call the library rejects
+ * (where the call itself returns 1).  Pure host functions of their arguments: nothing is launched or dereferenced, no HIP call
+ * is made (they run without a GPU) and no state is kept.  They run the plan code of the calls themselves, so a caller that
+ * times launches (bench.py's roofline leg) files each one under the kernel that ran it.  No counterpart in the reference. */
+int msmd_gemm_route(const void* A, const void* W, const float* bias, const void* residual, void* C, int M, int N, int K,
+                    int in_dtype, int out_dtype, long lda, int rows_per_batch, long a_batch_stride, long ldw, long ldc,
+                    long ldr, int act, int batch, long strideA, long strideW, long strideC, long strideBias, long strideR,
+                    void* z_out, float p_drop, const unsigned long* rng_state, unsigned int site, msmd_stream_t stream);
+int msmd_gemm_ln_route(const void* A, const void* W, const float* bias, const void* residual, void* C, int M, int N, int K,
+                       int in_dtype, int out_dtype, long lda, long ldw, long ldc, long ldr, int act, const float* a_stats,
+                       const float* w_colsum, const float* r_stats, const float* r_gamma, const float* r_beta,
+                       float* stats_out, int slab_in, int slab_out, float eps, msmd_stream_t stream);
 
 /* Two-level batched GEMM C[zo][zi] = A[zo][zi] . W[zo][zi]^T (no bias / residual / activation): operand z =
  * zo * batch_inner + zi starts at base + zo * stride_o + zi * stride_i.  Used by the explicit (materialised-P)

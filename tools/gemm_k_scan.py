@@ -8,7 +8,7 @@ import torch
 
 from msmd_amd import ops
 
-variants = [int(v) for v in (sys.argv[1] if len(sys.argv) > 1 else "17,63").split(",")]
+variants = [int(v) for v in (sys.argv[1] if len(sys.argv) > 1 else "17,80").split(",")]
 M = int(sys.argv[2]) if len(sys.argv) > 2 else 6400
 N = int(sys.argv[3]) if len(sys.argv) > 3 else 2304
 g = torch.Generator(device="cuda").manual_seed(0)

@@ -123,8 +123,7 @@ template <typename TO> __device__ __forceinline__ void store4_out(TO* p, const f
 // AB: the kernel also serves msmd_gemm_actbwd (flags bit 3).  Only the LDS-DMA 16-bit kernels carry that code: in the v1 /
 // fp32 kernels it cost 272 bytes of scratch (fp32 mode 23.8 -> 34 ms).
 // LEAN: the inference epilogue only (no pre-activation copy, no dropout, no activation backward): the launcher sends calls that
-// carry those to the kernels that compile them in.  On the 16-fragment wave tiles of gemm4_kernel the full epilogue is
-// tens of thousands of instructions and pushed the accumulators into scratch.
+// carry those to the kernels that compile them in.
 template <typename TO, int FM, int FN, bool AB, bool LEAN, int ACT>
 __device__ __forceinline__ void gemm_epilogue_interior_a(const GemmArgs& p, const f32x4 (&acc)[FN][FM], int z, int m_base,
                                                          int n_base, int fr, int fq) {
@@ -1073,185 +1072,6 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm2s_kernel(const GemmArgs p) 
 }
 
 // ---------------------------------------------------------------------------------------------------
-// bf16 / f16 kernel v4 (round 4): the same LDS image, LDS-DMA ring and epilogues as gemm2_kernel, with the fragment reads
-// software-pipelined INSIDE each wave and one workgroup barrier per K tile placed between its two 32-deep k-steps.
-//
-// Why (tools/lds_share_probe.hip, tools/intake_probe.hip): with LDS-DMA writes, fragment reads and MFMAs
-// running free in the 128 x 128 tile's per-K-tile ratio one CU sustains 0.37 us per K tile (1 460 TFLOP/s chip-wide);
-// gemm2_kernel takes 0.52 us hot and 0.68 us in the step.  Its waves run  wait / barrier / 4 DMA / 12 reads / lgkmcnt(0) /
-// 16 MFMA  back to back: nothing inside a wave overlaps, and a 128 x 128 K tile needs all of the CU's 64 B/clk vector-memory
-// path for as long as its MFMAs take (32 KB staged per 512 MFMA cycles), so every bubble is lost.  Here:
-//   * a wave holds TWO fragment sets; while the 16-32 MFMAs of one k-step issue, the reads of the next k-step are in flight
-//     (also across the K-tile boundary), so the matrix pipe never waits for LDS latency;
-//   * the barrier sits between the k-steps: before it  reads(g1) + MFMA(g0),  after it  DMA(tile + NSTAGE) + reads(next g0) +
-//     MFMA(g1) -- the stage a wave refills is the one whose last reads the barrier has just retired, and the DMA has
-//     NSTAGE - 1 whole K tiles to land;
-//   * bigger tiles at ONE workgroup per CU (256 x 128: 48 KB per 1024 MFMA cycles = 3/4 of the bytes per FLOP; 256 VGPRs):
-//     8 waves of 64 x 64.  Same products in the same order per output element as gemm2_kernel: bit-identical results.
-constexpr int waitcnt_lgkm0() { return 0xC07F; }                                              // lgkmcnt(0), vmcnt / expcnt untouched
-constexpr int waitcnt_vm(int n) { return (n & 0xF) | 0x70 | 0xF00 | ((n >> 4) << 14); }        // vmcnt(n), lgkmcnt / expcnt untouched
-
-template <typename TO, int BM, int BN, int WM, int WN, int NSTAGE, typename TI = bf16_t, bool ILV = false>
-__global__ __launch_bounds__(WM * WN * 64)
-__attribute__((amdgpu_waves_per_eu(NSTAGE * (BM + BN) * 128 > 80 * 1024 ? WM * WN / 4 : WM * WN / 2, NSTAGE * (BM + BN) * 128 > 80 * 1024 ? WM * WN / 4 : WM * WN / 2)))
-void gemm4_kernel(const GemmArgs p) {
-  constexpr int NW = WM * WN, NT = NW * 64;
-  constexpr int STAGE = (BM + BN) * 128;
-  constexpr int LPT = (BM + BN) * 8 / NT;  // LDS-DMA instructions per thread per K tile
-  constexpr int FM = BM / WM / 16, FN = BN / WN / 16;
-  static_assert((BM + BN) * 8 % NT == 0, "tile chunks must divide over the threads");
-  static_assert(NSTAGE == 2 || NSTAGE == 3, "ring of 2 or 3 stages");
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-
-  const int pid = blockIdx.x;
-  const int xcd = pid & 7, slot = pid >> 3;
-  const int xm_n = 8 / p.xn, ntx = (p.nt + p.xn - 1) / p.xn;
-  const int m_tile = (slot / ntx) * xm_n + (xcd % xm_n), n_tile = (slot % ntx) * p.xn + xcd / xm_n;
-  if (m_tile >= p.mt || n_tile >= p.nt) return;
-  const int z = blockIdx.z;
-  const int zo = z / p.batch_inner, zi = z % p.batch_inner;
-  const bf16_t* __restrict__ A = (const bf16_t*)p.A + zo * p.strideA + zi * p.strideA2;
-  const bf16_t* __restrict__ W = (const bf16_t*)p.W + zo * p.strideW + zi * p.strideW2;
-  const int m0 = m_tile * BM, n0 = n_tile * BN;
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-
-  const bf16_t* src[LPT];
-#pragma unroll
-  for (int i = 0; i < LPT; ++i) {
-    const int id = (i * NW + wid) * 64 + lane;  // 16-B slot of the tile image
-    const int row = id >> 3, phys = id & 7;
-    const int c = phys ^ ((row >> 1) & 7);      // logical chunk stored at this physical slot
-    if (row < BM) src[i] = A + a_row_offset(p, min(m0 + row, p.M - 1)) + c * 8;
-    else src[i] = W + (long)min(n0 + row - BM, p.N - 1) * p.ldw + c * 8;
-  }
-  auto issue_piece = [&](int i, int kt, int stage) {
-    __builtin_amdgcn_global_load_lds((gbl_void_t*)(src[i] + kt * 64), (lds_void_t*)(smem + stage * STAGE + (i * NW + wid) * 1024), 16, 0, 0);
-  };
-  auto issue = [&](int kt, int stage) {
-#pragma unroll
-    for (int i = 0; i < LPT; ++i) issue_piece(i, kt, stage);
-  };
-
-  const int wm = (wid / WN) * (BM / WM), wn = (wid % WN) * (BN / WN);
-  const int fr = lane & 15, fq = lane >> 4;
-  // fragment addresses inside a stage: rows wm + 16 j + fr (A) / BM + wn + 16 i + fr (W); the swizzle (row >> 1) & 7 only
-  // depends on fr because the row bases are multiples of 16
-  const int sw = (fr >> 1) & 7;
-  const unsigned offA = (wm + fr) * 128, offW = (BM + wn + fr) * 128;
-  const unsigned ch[2] = {(unsigned)((fq ^ sw) << 4), (unsigned)(((4 + fq) ^ sw) << 4)};
-  f32x4 acc[FN][FM];
-#pragma unroll
-  for (int i = 0; i < FN; ++i)
-#pragma unroll
-    for (int j = 0; j < FM; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  u32x4 fx[2][FM], fw[2][FN];     // two fragment sets: k-step g of the tile being multiplied lives in set g
-  auto read0 = [&](unsigned sbase) {
-#pragma unroll
-    for (int j = 0; j < FM; ++j) fx[0][j] = *(const u32x4*)(smem + sbase + offA + ch[0] + j * 2048);
-#pragma unroll
-    for (int i = 0; i < FN; ++i) fw[0][i] = *(const u32x4*)(smem + sbase + offW + ch[0] + i * 2048);
-  };
-  auto read1 = [&](unsigned sbase) {
-#pragma unroll
-    for (int j = 0; j < FM; ++j) fx[1][j] = *(const u32x4*)(smem + sbase + offA + ch[1] + j * 2048);
-#pragma unroll
-    for (int i = 0; i < FN; ++i) fw[1][i] = *(const u32x4*)(smem + sbase + offW + ch[1] + i * 2048);
-  };
-
-  const int nk = p.K / 64;
-  // LayerNorm-folding mode: the row statistics' loads go out before the K loop, consumed in the epilogue (as gemm2_kernel)
-  constexpr bool LNK = (BN / WN == 64 || BN / WN == 32) && (FM >= 2 && FM <= 4) && sizeof(TO) == 2;
-  f32x2 lnraw[LNK ? FM : 1][4];
-  if constexpr (LNK) {
-    if (p.a_stats) ln_issue<FM>(p.a_stats, p.a_nt, p.M, m0 + wm, fr, fq, lnraw);
-    else if (p.r_stats) ln_issue<FM>(p.r_stats, p.r_nt, p.M, m0 + wm, fr, fq, lnraw);
-  }
-  // prologue: NSTAGE - 1 tiles in flight, tile 0 landed, the last stage filled, fragment set 0 of tile 0 read
-#pragma unroll
-  for (int s = 0; s < NSTAGE - 1; ++s)
-    if (s < nk) issue(s, s);
-  if (NSTAGE - 1 <= nk) __builtin_amdgcn_s_waitcnt(waitcnt_vm((NSTAGE - 2) * LPT));
-  else __builtin_amdgcn_s_waitcnt(waitcnt_vm(0));
-  __builtin_amdgcn_s_barrier();
-  if (NSTAGE - 1 < nk) issue(NSTAGE - 1, NSTAGE - 1);
-  read0(0);
-  __builtin_amdgcn_s_waitcnt(waitcnt_lgkm0());
-  int st = 0;
-  if constexpr (ILV) {
-    // Branch-free body, instruction stream interleaved by hand: every fragment read and every DMA piece sits BETWEEN two
-    // MFMAs (pinned with sched_barrier: sched_group_barrier left the DMA pieces -- chained through M0 -- in one burst).  With one workgroup per CU the
-    // eight waves move in lockstep from barrier to barrier; bursts (48 DMA pieces, then 64 fragment reads, then the MFMAs)
-    // serialise the vector-memory queue, the LDS and the matrix pipe one after the other -- measured 2.1 x the free-running
-    // time per K tile.  Past the last K tile the reads and the refill are repeated on clamped indices (the stage they
-    // touch is never read again) instead of being branched around: one basic block per half.
-    static_assert(FM * FN >= FM + FN + LPT, "one MFMA slot per fragment read and DMA piece");
-    for (int kt = 0; kt < nk; ++kt) {
-      const unsigned char* sa = smem + st * STAGE;
-      // half 1: MFMAs of k-step 0; the 8 fragment reads of k-step 1 go out one per MFMA slot
-#pragma unroll
-      for (int q = 0; q < FM * FN; ++q) {
-        Mfma<TI>::run(fw[0][q / FM], fx[0][q % FM], acc[q / FM][q % FM]);
-        if (q < FM) fx[1][q] = *(const u32x4*)(sa + offA + ch[1] + q * 2048);
-        else if (q < FM + FN) fw[1][q - FM] = *(const u32x4*)(sa + offW + ch[1] + (q - FM) * 2048);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      __builtin_amdgcn_s_waitcnt(waitcnt_vm((NSTAGE - 2) * LPT));
-      __builtin_amdgcn_s_waitcnt(waitcnt_lgkm0());
-      __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_sched_barrier(0);
-      const int sn = st + 1 == NSTAGE ? 0 : st + 1;
-      const unsigned char* sna = smem + sn * STAGE;
-      const int kr = min(kt + NSTAGE, nk - 1);
-      // half 2: MFMAs of k-step 1; the next tile's k-step-0 reads first (they are needed first), then the refill's DMA pieces
-#pragma unroll
-      for (int q = 0; q < FM * FN; ++q) {
-        Mfma<TI>::run(fw[1][q / FM], fx[1][q % FM], acc[q / FM][q % FM]);
-        if (q < FM) fx[0][q] = *(const u32x4*)(sna + offA + ch[0] + q * 2048);
-        else if (q < FM + FN) fw[0][q - FM] = *(const u32x4*)(sna + offW + ch[0] + (q - FM) * 2048);
-        else if (q - FM - FN < LPT) issue_piece(q - FM - FN, kr, st);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      __builtin_amdgcn_s_waitcnt(waitcnt_lgkm0());
-      st = sn;
-    }
-    __builtin_amdgcn_s_waitcnt(waitcnt_vm(0));     // the clamped refills of the last iterations must not outlive the workgroup's LDS
-  } else {
-  for (int kt = 0; kt < nk; ++kt) {
-    const unsigned sb = st * STAGE;
-    read1(sb);                                   // k-step 1 of this tile: in flight under the MFMAs of k-step 0
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int i = 0; i < FN; ++i)
-#pragma unroll
-      for (int j = 0; j < FM; ++j) Mfma<TI>::run(fw[0][i], fx[0][j], acc[i][j]);
-    __builtin_amdgcn_sched_barrier(0);
-    // tile kt + 1 has landed (this wave's share; the barrier makes it everyone's); the newer tile may stay in flight
-    if (kt + NSTAGE - 1 < nk) __builtin_amdgcn_s_waitcnt(waitcnt_vm((NSTAGE - 2) * LPT));
-    else __builtin_amdgcn_s_waitcnt(waitcnt_vm(0));
-    __builtin_amdgcn_s_waitcnt(waitcnt_lgkm0());  // set 1 is in registers: this wave has finished reading stage st
-    __builtin_amdgcn_s_barrier();
-    const int sn = st + 1 == NSTAGE ? 0 : st + 1;
-    if (kt + NSTAGE < nk) issue(kt + NSTAGE, st);   // stage st is free: every wave has its fragments of tile kt in registers
-    if (kt + 1 < nk) read0(sn * STAGE);          // k-step 0 of the next tile: in flight under the MFMAs of k-step 1
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int i = 0; i < FN; ++i)
-#pragma unroll
-      for (int j = 0; j < FM; ++j) Mfma<TI>::run(fw[1][i], fx[1][j], acc[i][j]);
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_waitcnt(waitcnt_lgkm0());
-    st = sn;
-  }
-  }
-  if constexpr (LNK) {
-    if (p.a_stats) { gemm_epilogue_ln<TO, FM, FN, 1>(p, acc, m0 + wm, n0 + wn, fr, fq, lnraw); return; }
-    if (p.r_stats || p.stats_out) { gemm_epilogue_ln<TO, FM, FN, 2>(p, acc, m0 + wm, n0 + wn, fr, fq, lnraw); return; }
-  }
-  // the 16-fragment wave tiles carry the inference epilogue only (launch_gemm4 refuses Z / dropout / actbwd calls for them)
-  gemm_epilogue<TO, FM, FN, sizeof(TO) == 2 && FM * FN <= 8, (FM * FN > 8)>(p, acc, z, m0 + wm, n0 + wn, fr, fq);
-}
-
-// ---------------------------------------------------------------------------------------------------
 // gemm8_kernel: 256 x 256 x 64 tiles, ONE 8-wave workgroup per CU, the 8-phase schedule of cdna_hip_programming.md section 5
 // ("The 256^2 8-phase template") on this library's operand layout.  tools/gemm8_probe.hip is the bare schedule: 1 305 TFLOP/s at
 // 4096^3 and 1 303 at 16384 x 4096 x 3072 on random operands (the guide quotes 1 320-1 340 / 1 470 at 4096^3 / 8192^3) against
@@ -1845,24 +1665,6 @@ static int launch_gemm2_epi(GemmArgs& p, int batch, hipStream_t st) {
   return launch_gemm2<TO, BM, BN, WM, WN, NSTAGE, PIPE, TI, 0>(p, batch, st);
 }
 
-template <typename TO, int BM, int BN, int WM, int WN, int NSTAGE, typename TI = bf16_t, bool ILV = false>
-static int launch_gemm4(GemmArgs& p, int batch, hipStream_t st) {
-  constexpr int lds = NSTAGE * (BM + BN) * 128;
-  static bool attr_done = false;
-  auto kfn = gemm4_kernel<TO, BM, BN, WM, WN, NSTAGE, TI, ILV>;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_done = true;
-  }
-  if ((BM / WM / 16) * (BN / WN / 16) > 8 && (p.Z || p.p_drop > 0.f || (p.flags & 8))) return -1;   // lean epilogue: not a training call
-  p.mt = (p.M + BM - 1) / BM; p.nt = (p.N + BN - 1) / BN;
-  gemm2_xcd_grid(p, p.lda);
-  const int xm_n = 8 / p.xn;
-  dim3 grid(((p.mt + xm_n - 1) / xm_n) * ((p.nt + p.xn - 1) / p.xn) * 8, 1, batch);
-  hipLaunchKernelGGL(kfn, grid, dim3(WM * WN * 64), lds, st, p);
-  MSMD_RETURN_LAST();
-}
-
 // One persistent workgroup per CU: the grid cap is the device's CU count (256 on MI355X; the tile-run logic of the kernel
 // works for any workgroup count, the shape rules below are fitted on 256).
 static int gemm8_workgroup_cap() {
@@ -1944,7 +1746,7 @@ static int launch_gemm8(GemmArgs& p, int batch, hipStream_t st) {
 }
 
 // gemm8_kernel on split-pair operands (SPLIT): the calls it takes, the rule, the launch.  p carries fp16 strides for A / W
-// (doubled by gemm_impl) and logical ldc / ldr.
+// (doubled by gemm_args) and logical ldc / ldr.
 static bool gemm8s_takes(const GemmArgs& p, int batch, bool split_out) {
   if (batch != 1 || p.batch_inner != 1 || (p.N % 256) || (p.K % 32) || p.K < 64 || !p.vec_ok) return false;
   if (((uintptr_t)p.bias & 15) || ((uintptr_t)p.C & 15) || ((uintptr_t)p.R & 15)) return false;
@@ -2003,7 +1805,7 @@ static int launch_gemm2s(GemmArgs& p, int batch, hipStream_t st) {
     attr_done = true;
   }
   p.mt = (p.M + BM - 1) / BM; p.nt = (p.N + BN - 1) / BN;
-  gemm2_xcd_grid(p, p.lda / 2);      // p.lda is the fp16 stride (doubled by gemm_impl)
+  gemm2_xcd_grid(p, p.lda / 2);      // p.lda is the fp16 stride (doubled by gemm_args)
   const int xm_n = 8 / p.xn;
   dim3 grid(((p.mt + xm_n - 1) / xm_n) * ((p.nt + p.xn - 1) / p.xn) * 8, 1, batch);
   hipLaunchKernelGGL(kfn, grid, dim3(WM * WN * 64), lds, st, p);
@@ -2029,23 +1831,27 @@ static int dispatch_gemm2s(GemmArgs& p, int batch, hipStream_t st, int variant) 
 // once the grid fills the chip); 13 = the same tile with the compiler's own read / multiply interleave; 9 / 12 = 64 x 64
 // tiles with a 4- / 2-stage ring for grids that would not fill the chip.  Every other family that was built and measured
 // lost and was removed: its numbers are in DESIGN.md section 5 / 5b.
-template <typename TO>
+// The variants dispatch_gemm2 has for operand type TI; gemm16_route asks the same question, so a routed variant always launches.
+template <typename TI>
+static constexpr bool gemm2_has(int variant) {
+  if (variant == 13 || variant == 66) return __is_same(TI, bf16_t);   // the A/B forms of 17: bf16 only
+  return variant == 9 || variant == 12 || variant == 14 || variant == 15 || variant == 17 || variant == 80;
+}
+
+template <typename TO, typename TI>
 static int dispatch_gemm2(GemmArgs& p, int batch, hipStream_t st, int variant) {
+  if (!gemm2_has<TI>(variant)) return -1;
+  if constexpr (__is_same(TI, bf16_t)) {
+    if (variant == 13) return launch_gemm2<TO, 128, 128, 4, 2, 2>(p, batch, st);
+    if (variant == 66) return launch_gemm2<TO, 128, 128, 4, 2, 2, true>(p, batch, st);   // 17 as ONE kernel with every epilogue (round 3's form)
+  }
   switch (variant) {
-    case 9: return launch_gemm2_epi<TO, 64, 64, 2, 2, 4>(p, batch, st);
-    case 12: return launch_gemm2_epi<TO, 64, 64, 2, 2, 2>(p, batch, st);
-    case 13: return launch_gemm2<TO, 128, 128, 4, 2, 2>(p, batch, st);
-    case 14: return launch_gemm2_epi<TO, 256, 64, 8, 1, 2, true>(p, batch, st);   // narrow outputs (N <= 64): 8 waves of 32 x 64
-    case 15: return launch_gemm2_epi<TO, 192, 128, 4, 2, 2, true>(p, batch, st);  // tall grids (M >= 16 k): 80 KB, still 2 workgroups / CU
-    case 17: return launch_gemm2_epi<TO, 128, 128, 4, 2, 2, true>(p, batch, st);
-    case 66: return launch_gemm2<TO, 128, 128, 4, 2, 2, true>(p, batch, st);       // 17 as ONE kernel with every epilogue (round 3's form)
-    case 80: return launch_gemm8<TO, bf16_t>(p, batch, st);                        // 256 x 256, 8-phase schedule, one workgroup per CU
-    // v4 kernels (fragment reads pipelined inside the wave, barrier between the k-steps):
-    case 60: return launch_gemm4<TO, 256, 128, 4, 2, 3>(p, batch, st);                   // 144 KB, 1 workgroup / CU, 8 waves of 64 x 64
-    case 61: return launch_gemm4<TO, 256, 128, 4, 2, 2>(p, batch, st);                   // 96 KB
-    case 62: return launch_gemm4<TO, 128, 128, 4, 2, 2>(p, batch, st);                   // 64 KB, 2 workgroups / CU: variant 17's tile
-    case 63: return launch_gemm4<TO, 256, 128, 4, 2, 3, bf16_t, true>(p, batch, st);     // 60 with the refill's DMA between the MFMAs
-    case 64: return launch_gemm4<TO, 256, 128, 4, 2, 2, bf16_t, true>(p, batch, st);     // 63 with a 2-stage ring (96 KB)
+    case 9: return launch_gemm2_epi<TO, 64, 64, 2, 2, 4, false, TI>(p, batch, st);
+    case 12: return launch_gemm2_epi<TO, 64, 64, 2, 2, 2, false, TI>(p, batch, st);
+    case 14: return launch_gemm2_epi<TO, 256, 64, 8, 1, 2, true, TI>(p, batch, st);   // narrow outputs (N <= 64): 8 waves of 32 x 64
+    case 15: return launch_gemm2_epi<TO, 192, 128, 4, 2, 2, true, TI>(p, batch, st);  // tall grids (M >= 16 k): 80 KB, still 2 workgroups / CU
+    case 17: return launch_gemm2_epi<TO, 128, 128, 4, 2, 2, true, TI>(p, batch, st);
+    case 80: return launch_gemm8<TO, TI>(p, batch, st);                               // 256 x 256, 8-phase schedule, one workgroup per CU
     default: return -1;
   }
 }
@@ -2066,19 +1872,6 @@ static int launch_gemm(GemmArgs& p, int batch, hipStream_t st) {
   MSMD_RETURN_LAST();
 }
 
-template <typename TO>
-static int dispatch_gemm2_f16(GemmArgs& p, int batch, hipStream_t st, int variant) {
-  switch (variant) {
-    case 9: return launch_gemm2_epi<TO, 64, 64, 2, 2, 4, false, f16_t>(p, batch, st);
-    case 12: return launch_gemm2_epi<TO, 64, 64, 2, 2, 2, false, f16_t>(p, batch, st);
-    case 14: return launch_gemm2_epi<TO, 256, 64, 8, 1, 2, true, f16_t>(p, batch, st);
-    case 15: return launch_gemm2_epi<TO, 192, 128, 4, 2, 2, true, f16_t>(p, batch, st);
-    case 17: return launch_gemm2_epi<TO, 128, 128, 4, 2, 2, true, f16_t>(p, batch, st);
-    case 80: return launch_gemm8<TO, f16_t>(p, batch, st);
-    default: return -1;
-  }
-}
-
 // Between 9 600 and 16 000 rows (the training step's M = 12 800: both windows in one batch) the tile follows how full the
 // LAST round of 512 workgroups is: 12800 x 768 is 600 tiles of 128 x 128 (one full round + 88 stragglers) but 402 of
 // 192 x 128 (one round).  Measured (tools/bench_gemm_variants.py, SHAPES=train): x 768 x 3072 78.9 -> 68.0 us, x 2304 x 768
@@ -2091,138 +1884,149 @@ static bool tall_rounds_favour_192(int M, long tiles128, long tiles192) {
   return 1.2 * fill192 > 1.03 * fill128;
 }
 
+// The one place a GemmArgs is filled; fields it does not name keep the struct's defaults.  `ab` scales every A / W stride: 2 for
+// split-pair operands (logical sizes in, fp16 strides into the kernel), else 1.  osz = bytes of an output element, 0 for
+// split-pair output (the entry has required whole 32-element blocks: every vector access is aligned).
+static GemmArgs gemm_args(const void* A, const void* W, const float* bias, const void* residual, void* C, int M, int N, int K,
+                          long lda, int rows_per_batch, long a_batch_stride, long ldw, long ldc, long ldr, int act, int flags,
+                          long strideA, long strideW, long strideC, long strideBias, long strideR, int batch_inner,
+                          long strideA2, long strideW2, long strideC2, int osz, int ab = 1) {
+  GemmArgs p{};
+  if (rows_per_batch <= 0) rows_per_batch = M;
+  p.A = A; p.W = W; p.bias = bias; p.R = residual; p.C = C;
+  p.M = M; p.N = N; p.K = K;
+  p.lda = ab * lda; p.rows_per_batch = rows_per_batch; p.a_batch_stride = ab * a_batch_stride;
+  p.ldw = ab * ldw; p.ldc = ldc; p.ldr = ldr; p.act = act;
+  p.inv_rpb = 1.0f / (float)rows_per_batch;
+  p.strideA = ab * strideA; p.strideW = ab * strideW; p.strideC = strideC; p.strideBias = strideBias; p.strideR = strideR;
+  p.batch_inner = batch_inner; p.strideA2 = ab * strideA2; p.strideW2 = ab * strideW2; p.strideC2 = strideC2;
+  p.xn = 1;
+  p.vec_ok = osz == 0 ||
+             ((ldc % 4 == 0) && (strideC % 4 == 0) && (strideC2 % 4 == 0) && (((uintptr_t)C % (4 * osz)) == 0) &&
+              (!residual || ((ldr % 4 == 0) && (strideR % 4 == 0) && (((uintptr_t)residual % (4 * osz)) == 0))));
+  if ((flags & 2) && (osz != 2 || (ldc % 8) || (strideC % 8) || (strideC2 % 8) || ((uintptr_t)C % 16) || !p.vec_ok))
+    flags &= ~2;   // paired stores need 16-byte aligned row pairs
+  p.flags = flags;
+  return p;
+}
+
+// The kernel of a call on split-pair operands: variant 1 / 5 / 14 / 80, -1 for a hint that names none of them.
+static int gemm_split_route(const GemmArgs& p, int nz, bool split_out, int hint, int flags) {
+  const bool takes8 = gemm8s_takes(p, nz, split_out);
+  if (hint == 80 && !takes8) hint = 0;   // a hint the call cannot follow
+  if (hint) return (hint == 1 || hint == 5 || hint == 14 || hint == 80) ? hint : -1;
+  // the library's own choice takes the 256 x 256 kernel only under MSMD_GEMM_W_BELOW_32: there it returns the bits of
+  // gemm2s_kernel's WS form, so the row count of a launch never changes a row's result (its folding form, reachable by the
+  // variant hint, sums the cross terms in another order than gemm2s_kernel's two accumulators)
+  if (!(flags & 32) && (flags & 64) && takes8 && gemm8s_wins(p.M, p.N, p.K, true)) return 80;
+  if (p.N <= 64) return (long)((p.M + 255) / 256) * nz >= 256 ? 14 : 5;
+  return (long)((p.M + 127) / 128) * ((p.N + 127) / 128) * nz >= 192 ? 1 : 5;
+}
+
+// The kernel of a call on 16-bit operands with K % 64 == 0 (msmd_gemm's family and msmd_gemm_ln): the variant dispatch_gemm2
+// launches, or 0 for gemm_kernel (a hint that names no variant of this operand type).  Measured on MI355X.
+// Priority of the library's own choice: 256 x 256, the tall 192 x 128 tile, the last-round fill rule, 128 x 128, 256 x 64, 64 x 64.
+// flags bit 5 (MSMD_GEMM_NO_256_TILE) = the caller opts out of the 256 x 256 kernel (A/B).
+// cols: 0 for a plain call, where every tile is open.  msmd_gemm_ln's statistics slabs name the tile family: 128 = the
+// 128-column tiles (17 / 15; 64-column slabs, which the 256 x 256 kernel writes too), 64 = the 64 x 64 tiles (9 / 12; 32-column
+// slabs, so the 256 x 256 kernel only where the call writes no statistics).  Its hints choose within that family.
+static int gemm16_route(const GemmArgs& p, int nz, int osz, bool bf16, int hint, int flags, int cols = 0) {
+  const bool takes8 = (cols != 64 || !p.stats_out) && gemm8_takes(p, nz, osz);
+  const bool rule8 = hint == 0 && !(flags & 32);
+  // a hint the call cannot follow leaves the library's own choice: 80 on a call the kernel does not take, and for msmd_gemm_ln
+  // anything but 15 / 17 / 66 inside the 128-column family
+  if (!(hint == 80 ? takes8 : !cols || (cols == 128 && (hint == 15 || hint == 17 || hint == 66)))) hint = 0;
+  if (hint) return (bf16 ? gemm2_has<bf16_t>(hint) : gemm2_has<f16_t>(hint)) ? hint : 0;
+  const int M = p.M, N = p.N;
+  const long tiles128 = (long)((M + 127) / 128) * ((N + 127) / 128) * nz;
+  const long tiles192 = (long)((M + 191) / 192) * ((N + 127) / 128) * nz;
+  const bool wide = cols ? cols == 128 : N > 64;
+  if (rule8 && takes8 && gemm8_wins(M, N, p.K)) return 80;      // 256 x 256 tiles, 8-phase schedule
+  // tall grids: 192 x 128 tiles (76.8 FLOP per staged byte instead of 64, still two workgroups per CU).  Measured against
+  // the 128 x 128 tile: conv1 454 -> 379 us, 21312 x 512 x 2048 58.7 -> 49.6, 21312 x 2048 x 512 76.6 -> 64.7; worse
+  // below ~16 k rows (12800 x 512 x 1024: 22 -> 28 us) and mixed at M = 6400
+  if (wide && M >= 16000 && tiles192 >= 400) return 15;
+  // inference epilogues only: the 192-row tile's everything-epilogue runs one workgroup per CU
+  if (wide && osz == 2 && !p.Z && !(p.p_drop > 0.f) && !(p.flags & 8) && tall_rounds_favour_192(M, tiles128, tiles192)) return 15;
+  // the 128 x 128 LDS-DMA kernel (8 waves as 4 x 2, 2-stage ring, fragment reads pipelined) wins once the grid fills the chip at
+  // 2 workgroups per CU; below that, 64 x 64 tiles (deep ring for long K) keep more CUs busy
+  if (cols ? wide : wide && tiles128 >= 192) return 17;
+  if (!cols && N <= 64 && (long)((M + 255) / 256) * nz >= 256) return 14;   // the positional conv: 256 x 64 tiles, 140 -> 85 us
+  return p.K >= 1024 ? 9 : 12;
+}
+
+// The plan of a msmd_gemm / msmd_gemm_ex / msmd_gemm_actbwd / msmd_gemm_batched2 call: checks it, fills p and picks the kernel.
+// Returns the variant gemm_launch will launch, 0 for gemm_kernel, -1 for a call the library rejects.  Host arithmetic only,
+// no HIP call and no state: msmd_gemm_route is this function alone.
+static int gemm_plan(GemmArgs& p, const void* A, const void* W, const float* bias, const void* residual, void* C, int M, int N,
+                     int K, int in_dtype, int out_dtype, long lda, int rows_per_batch, long a_batch_stride, long ldw, long ldc,
+                     long ldr, int act, int batch, long strideA, long strideW, long strideC, long strideBias, long strideR,
+                     int batch_inner, long strideA2, long strideW2, long strideC2, void* z_out, float p_drop,
+                     const unsigned long* rng, unsigned site, int internal_flags) {
+  if (M <= 0 || N <= 0 || K <= 0 || batch <= 0 || batch_inner <= 0 || !A || !W || !C) return -1;
+  const int hint = (act >> 8) & 0xff;  // caller-chosen kernel variant (host-side autotune), 0 = the library's own choice
+  const int flags = ((act >> 16) & 0x7) | (((act >> 19) & 1) << 4) | (((act >> 20) & 1) << 5) | (((act >> 21) & 1) << 6) | internal_flags;  // MSMD_GEMM_WRITE_THROUGH / MSMD_GEMM_PAIRED_STORES (include/msmd_hip.h)
+  act &= 0xff;
+  const int nz = batch * batch_inner;
+  if (in_dtype == MSMD_F16X2) {
+    // split-pair operands: 32-element blocks must stay whole
+    if (out_dtype != MSMD_F32 && out_dtype != MSMD_F16X2) return -1;
+    if (K % 32 || lda % 32 || ldw % 32 || a_batch_stride % 32 || strideA % 32 || strideW % 32 || strideA2 % 32 ||
+        strideW2 % 32 || z_out || p_drop != 0.f)
+      return -1;
+    if (((uintptr_t)A & 15) || ((uintptr_t)W & 15) || ((uintptr_t)C & 15)) return -1;
+    if (out_dtype == MSMD_F16X2) {
+      if ((N & 3) || ldc % 32 || strideC % 32 || strideC2 % 32 || (residual && (ldr % 32 || strideR % 32))) return -1;
+      if (bias && (((uintptr_t)bias & 15) || (strideBias & 3))) return -1;
+    }
+    p = gemm_args(A, W, bias, residual, C, M, N, K, lda, rows_per_batch, a_batch_stride, ldw, ldc, ldr, act, flags & (1 | 64),
+                  strideA, strideW, strideC, strideBias, strideR, batch_inner, strideA2, strideW2, strideC2,
+                  out_dtype == MSMD_F32 ? 4 : 0, 2);
+    return gemm_split_route(p, nz, out_dtype == MSMD_F16X2, hint, flags);
+  }
+  if (in_dtype == MSMD_F32 ? (out_dtype != MSMD_F32 && out_dtype != MSMD_F16 && out_dtype != MSMD_BF16)
+                           : ((in_dtype != MSMD_F16 && in_dtype != MSMD_BF16) || (out_dtype != in_dtype && out_dtype != MSMD_F32)))
+    return -1;
+  const int E = in_dtype == MSMD_F32 ? 4 : 8;
+  if (K % E || lda % E || ldw % E || a_batch_stride % E || strideA % E || strideW % E || strideA2 % E || strideW2 % E)
+    return -1;
+  if (((uintptr_t)A & 15) || ((uintptr_t)W & 15)) return -1;
+  if (p_drop != 0.f && (!(p_drop > 0.f && p_drop < 1.f) || !rng || (N & 3) || ldc != N || batch != 1 || batch_inner != 1))
+    return -1;  // the mask index assumes one contiguous (M, N) output
+  const int osz = out_dtype == MSMD_F32 ? 4 : 2;
+  p = gemm_args(A, W, bias, residual, C, M, N, K, lda, rows_per_batch, a_batch_stride, ldw, ldc, ldr, act, flags, strideA,
+                strideW, strideC, strideBias, strideR, batch_inner, strideA2, strideW2, strideC2, osz);
+  p.Z = z_out; p.p_drop = p_drop; p.rng = rng; p.site = site;     // the training epilogue (msmd_gemm_ex, msmd_gemm_actbwd)
+  if (in_dtype == MSMD_F32 || (K % 64)) return 0;    // the LDS-DMA kernels: 16-bit operands in whole 128-byte K tiles
+  return gemm16_route(p, nz, osz, in_dtype == MSMD_BF16, hint, flags);
+}
+
+static int gemm_launch(GemmArgs& p, int in_dtype, int out_dtype, int nz, int variant, hipStream_t st) {
+  int r = -1;
+  if (in_dtype == MSMD_F16X2) r = out_dtype == MSMD_F32 ? dispatch_gemm2s<float>(p, nz, st, variant) : dispatch_gemm2s<f16_t>(p, nz, st, variant);
+  else if (variant && in_dtype == MSMD_BF16) r = out_dtype == MSMD_BF16 ? dispatch_gemm2<bf16_t, bf16_t>(p, nz, st, variant) : dispatch_gemm2<float, bf16_t>(p, nz, st, variant);
+  else if (variant) r = out_dtype == MSMD_F16 ? dispatch_gemm2<f16_t, f16_t>(p, nz, st, variant) : dispatch_gemm2<float, f16_t>(p, nz, st, variant);
+  else if (in_dtype == MSMD_F16 && out_dtype == MSMD_F16) r = launch_gemm<f16_t, f16_t>(p, nz, st);
+  else if (in_dtype == MSMD_F16 && out_dtype == MSMD_F32) r = launch_gemm<f16_t, float>(p, nz, st);
+  else if (in_dtype == MSMD_F32 && out_dtype == MSMD_F16) r = launch_gemm<float, f16_t>(p, nz, st);
+  else if (in_dtype == MSMD_BF16 && out_dtype == MSMD_BF16) r = launch_gemm<bf16_t, bf16_t>(p, nz, st);
+  else if (in_dtype == MSMD_BF16 && out_dtype == MSMD_F32) r = launch_gemm<bf16_t, float>(p, nz, st);
+  else if (in_dtype == MSMD_F32 && out_dtype == MSMD_F32) r = launch_gemm<float, float>(p, nz, st);
+  else if (in_dtype == MSMD_F32 && out_dtype == MSMD_BF16) r = launch_gemm<float, bf16_t>(p, nz, st);
+  return r >= 0 ? r : 1;     // a variant the plan chose and the dispatch does not have is an error, never another kernel
+}
+
 static int gemm_impl(const void* A, const void* W, const float* bias, const void* residual, void* C, int M, int N, int K,
                      int in_dtype, int out_dtype, long lda, int rows_per_batch, long a_batch_stride, long ldw, long ldc,
                      long ldr, int act, int batch, long strideA, long strideW, long strideC, long strideBias,
                      long strideR, int batch_inner, long strideA2, long strideW2, long strideC2, msmd_stream_t stream,
                      void* z_out = nullptr, float p_drop = 0.f, const unsigned long* rng = nullptr, unsigned site = 0,
                      int internal_flags = 0) {
-  if (M <= 0 || N <= 0 || K <= 0 || batch <= 0 || batch_inner <= 0 || !A || !W || !C) return 1;
-  const int hint = (act >> 8) & 0xff;  // caller-chosen kernel variant (host-side autotune), 0 = heuristic below
-  const int flags = ((act >> 16) & 0x7) | (((act >> 19) & 1) << 4) | (((act >> 20) & 1) << 5) | (((act >> 21) & 1) << 6) | internal_flags;  // MSMD_GEMM_WRITE_THROUGH / MSMD_GEMM_PAIRED_STORES (include/msmd_hip.h)
-  act &= 0xff;
-  if (in_dtype == MSMD_F16X2) {
-    // split-pair operands: logical sizes in, fp16 strides (x 2) into the kernel; 32-element blocks must stay whole
-    if (out_dtype != MSMD_F32 && out_dtype != MSMD_F16X2) return 1;
-    if (K % 32 || lda % 32 || ldw % 32 || a_batch_stride % 32 || strideA % 32 || strideW % 32 || strideA2 % 32 ||
-        strideW2 % 32 || z_out || p_drop != 0.f)
-      return 1;
-    if (((uintptr_t)A & 15) || ((uintptr_t)W & 15) || ((uintptr_t)C & 15)) return 1;
-    if (rows_per_batch <= 0) rows_per_batch = M;
-    GemmArgs p;
-    p.A = A; p.W = W; p.bias = bias; p.R = residual; p.C = C;
-    p.M = M; p.N = N; p.K = K;
-    p.lda = 2 * lda; p.rows_per_batch = rows_per_batch; p.a_batch_stride = 2 * a_batch_stride;
-    p.ldw = 2 * ldw; p.ldc = ldc; p.ldr = ldr; p.act = act;
-    p.inv_rpb = 1.0f / (float)rows_per_batch;
-    p.strideA = 2 * strideA; p.strideW = 2 * strideW; p.strideC = strideC; p.strideBias = strideBias; p.strideR = strideR;
-    p.batch_inner = batch_inner; p.strideA2 = 2 * strideA2; p.strideW2 = 2 * strideW2; p.strideC2 = strideC2;
-    p.Z = nullptr; p.p_drop = 0.f; p.rng = nullptr; p.site = 0; p.xn = 1; p.flags = flags & (1 | 64);
-    if (out_dtype == MSMD_F16X2) {
-      if ((N & 3) || ldc % 32 || strideC % 32 || strideC2 % 32 || (residual && (ldr % 32 || strideR % 32))) return 1;
-      if (bias && (((uintptr_t)bias & 15) || (strideBias & 3))) return 1;
-      p.vec_ok = 1;
-    } else {
-      p.vec_ok = (ldc % 4 == 0) && (strideC % 4 == 0) && (strideC2 % 4 == 0) && (((uintptr_t)C % 16) == 0) &&
-                 (!residual || ((ldr % 4 == 0) && (strideR % 4 == 0) && (((uintptr_t)residual % 16) == 0)));
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const int nz = batch * batch_inner;
-    int variant = hint;
-    if (variant == 80 && !gemm8s_takes(p, nz, out_dtype == MSMD_F16X2)) variant = 0;   // a hint the call cannot follow
-    if (variant == 0) {
-      const long tiles128 = (long)((M + 127) / 128) * ((N + 127) / 128) * nz;
-      variant = (N > 64 && tiles128 >= 192) ? 1 : 5;
-      if (N <= 64 && (long)((M + 255) / 256) * nz >= 256) variant = 14;
-      // the library's own choice takes the 256 x 256 kernel only under MSMD_GEMM_W_BELOW_32: there it returns the bits of
-      // gemm2s_kernel's WS form, so the row count of a launch never changes a row's result (its folding form, reachable by the
-      // variant hint, sums the cross terms in another order than gemm2s_kernel's two accumulators)
-      if (!(flags & 32) && (flags & 64) && gemm8s_takes(p, nz, out_dtype == MSMD_F16X2) && gemm8s_wins(M, N, K, true)) variant = 80;
-    }
-    const int r = out_dtype == MSMD_F32 ? dispatch_gemm2s<float>(p, nz, st, variant)
-                                        : dispatch_gemm2s<f16_t>(p, nz, st, variant);
-    return r >= 0 ? r : 1;
-  }
-  const int E = in_dtype == MSMD_F32 ? 4 : 8;
-  if (K % E || lda % E || ldw % E || a_batch_stride % E || strideA % E || strideW % E || strideA2 % E || strideW2 % E)
-    return 1;
-  if (((uintptr_t)A & 15) || ((uintptr_t)W & 15)) return 1;
-  if (rows_per_batch <= 0) rows_per_batch = M;
   GemmArgs p;
-  p.A = A; p.W = W; p.bias = bias; p.R = residual; p.C = C;
-  p.M = M; p.N = N; p.K = K;
-  p.lda = lda; p.rows_per_batch = rows_per_batch; p.a_batch_stride = a_batch_stride;
-  p.ldw = ldw; p.ldc = ldc; p.ldr = ldr; p.act = act;
-  p.inv_rpb = 1.0f / (float)rows_per_batch;
-  p.strideA = strideA; p.strideW = strideW; p.strideC = strideC; p.strideBias = strideBias; p.strideR = strideR;
-  p.batch_inner = batch_inner; p.strideA2 = strideA2; p.strideW2 = strideW2; p.strideC2 = strideC2;
-  p.Z = z_out; p.p_drop = p_drop; p.rng = rng; p.site = site; p.xn = 1; p.flags = flags;
-  if (p_drop != 0.f && (!(p_drop > 0.f && p_drop < 1.f) || !rng || (N & 3) || ldc != N || batch != 1 || batch_inner != 1))
-    return 1;  // the mask index assumes one contiguous (M, N) output
-  const int osz = out_dtype == MSMD_F32 ? 4 : 2;
-  p.vec_ok = (ldc % 4 == 0) && (strideC % 4 == 0) && (strideC2 % 4 == 0) && (((uintptr_t)C % (4 * osz)) == 0) &&
-             (!residual || ((ldr % 4 == 0) && (strideR % 4 == 0) && (((uintptr_t)residual % (4 * osz)) == 0)));
-  if ((p.flags & 2) && (osz != 2 || (ldc % 8) || (strideC % 8) || (strideC2 % 8) || ((uintptr_t)C % 16) || !p.vec_ok))
-    p.flags &= ~2;   // paired stores need 16-byte aligned row pairs
-  hipStream_t st = (hipStream_t)stream;
-  const int nz = batch * batch_inner;
-  if (in_dtype == MSMD_BF16 && (K % 64) == 0) {
-    // Measured on MI355X: the 128x128 LDS-DMA kernel wins once the grid fills the
-    // chip at 2 workgroups per CU; below that, 64x64 tiles (deep ring for long K) keep more CUs busy.
-    int variant = hint;
-    if (variant == 80 && !gemm8_takes(p, nz, osz)) variant = 0;     // a hint the call cannot follow: the library's own choice
-    if (variant == 0) {
-      const long tiles128 = (long)((M + 127) / 128) * ((N + 127) / 128) * nz;
-      const long tiles192 = (long)((M + 191) / 192) * ((N + 127) / 128) * nz;
-      if (!(flags & 32) && gemm8_takes(p, nz, osz) && gemm8_wins(M, N, K)) {
-        variant = 80;      // 256 x 256 tiles, 8-phase schedule (flags bit 5 = caller opts out: A/B)
-      } else if (N > 64 && M >= 16000 && tiles192 >= 400) {
-        // tall grids: 192 x 128 tiles (76.8 FLOP per staged byte instead of 64, still two workgroups per CU).  Measured against
-        // the 128 x 128 tile: conv1 454 -> 379 us, 21312 x 512 x 2048 58.7 -> 49.6, 21312 x 2048 x 512 76.6 -> 64.7; worse
-        // below ~16 k rows (12800 x 512 x 1024: 22 -> 28 us) and mixed at M = 6400
-        variant = 15;
-      } else if (N > 64 && tall_rounds_favour_192(M, tiles128, tiles192) && !z_out && !(p_drop > 0.f) && !(flags & 8) && out_dtype == MSMD_BF16) {
-        variant = 15;      // inference epilogues only: the 192-row tile's everything-epilogue runs one workgroup per CU
-      } else if (N > 64 && tiles128 >= 192) {
-        variant = 17;  // 128x128, 8 waves (4x2), 2-stage ring, 2 workgroups/CU, fragment reads pipelined
-      } else if (N <= 64 && (long)((M + 255) / 256) * nz >= 256) variant = 14;   // the positional conv: 256 x 64 tiles, 140 -> 85 us
-      else variant = (K >= 1024) ? 9 : 12;
-    }
-    const int r = out_dtype == MSMD_BF16 ? dispatch_gemm2<bf16_t>(p, nz, st, variant)
-                                         : dispatch_gemm2<float>(p, nz, st, variant);
-    if (r >= 0) return r;
-  }
-  if (in_dtype == MSMD_F16 && (out_dtype == MSMD_F16 || out_dtype == MSMD_F32) && (K % 64) == 0) {
-    // fp16 storage: same LDS-DMA kernels with v_mfma_f32_16x16x32_f16 (the heuristic's variants only)
-    const long tiles128 = (long)((M + 127) / 128) * ((N + 127) / 128) * nz;
-    const bool no_hint = !hint || (hint == 80 && !gemm8_takes(p, nz, osz));
-    int variant = !no_hint ? hint : ((N > 64 && tiles128 >= 192) ? 17 : ((K >= 1024) ? 9 : 12));
-    if (no_hint && N <= 64 && (long)((M + 255) / 256) * nz >= 256) variant = 14;
-    if (no_hint && N > 64 && M >= 16000 && (long)((M + 191) / 192) * ((N + 127) / 128) * nz >= 400) variant = 15;
-    if (no_hint && N > 64 && out_dtype == MSMD_F16 && !z_out && !(p_drop > 0.f) && !(flags & 8) &&
-        tall_rounds_favour_192(M, tiles128, (long)((M + 191) / 192) * ((N + 127) / 128) * nz))
-      variant = 15;
-    if (no_hint && !(flags & 32) && gemm8_takes(p, nz, osz) && gemm8_wins(M, N, K)) variant = 80;
-    const int r = out_dtype == MSMD_F16 ? dispatch_gemm2_f16<f16_t>(p, nz, st, variant)
-                                        : dispatch_gemm2_f16<float>(p, nz, st, variant);
-    if (r >= 0) return r;
-  }
-  if (in_dtype == MSMD_F16 && out_dtype == MSMD_F16) return launch_gemm<f16_t, f16_t>(p, nz, st);
-  if (in_dtype == MSMD_F16 && out_dtype == MSMD_F32) return launch_gemm<f16_t, float>(p, nz, st);
-  if (in_dtype == MSMD_F32 && out_dtype == MSMD_F16) return launch_gemm<float, f16_t>(p, nz, st);
-  if (in_dtype == MSMD_BF16 && out_dtype == MSMD_BF16) return launch_gemm<bf16_t, bf16_t>(p, nz, st);
-  if (in_dtype == MSMD_BF16 && out_dtype == MSMD_F32) return launch_gemm<bf16_t, float>(p, nz, st);
-  if (in_dtype == MSMD_F32 && out_dtype == MSMD_F32) return launch_gemm<float, float>(p, nz, st);
-  if (in_dtype == MSMD_F32 && out_dtype == MSMD_BF16) return launch_gemm<float, bf16_t>(p, nz, st);
-  return 1;
-}
-
-extern "C" int msmd_gemm_256_tile_rule(int M, int N, int K) {
-  return (M > 0 && N > 0 && K >= 128 && (N % 256) == 0 && (K % 64) == 0 && gemm8_wins(M, N, K)) ? 1 : 0;
-}
-
-extern "C" int msmd_gemm_256_tile_rule_f16x2(int M, int N, int K, int w_below_32) {
-  return (M > 0 && N > 0 && K >= 64 && (N % 256) == 0 && (K % 32) == 0 && w_below_32 && gemm8s_wins(M, N, K, true)) ? 1 : 0;
+  const int variant = gemm_plan(p, A, W, bias, residual, C, M, N, K, in_dtype, out_dtype, lda, rows_per_batch, a_batch_stride,
+                                ldw, ldc, ldr, act, batch, strideA, strideW, strideC, strideBias, strideR, batch_inner,
+                                strideA2, strideW2, strideC2, z_out, p_drop, rng, site, internal_flags);
+  return variant < 0 ? 1 : gemm_launch(p, in_dtype, out_dtype, batch * batch_inner, variant, (hipStream_t)stream);
 }
 
 extern "C" int msmd_gemm(const void* A, const void* W, const float* bias, const void* residual, void* C, int M,
@@ -2237,52 +2041,58 @@ extern "C" int msmd_gemm(const void* A, const void* W, const float* bias, const 
 // the row statistics of C written for the next consumer: see GemmArgs and include/msmd_hip.h.  Plain row-major operands,
 // no batch, 16-bit operands and output.  The statistics' slab width names the kernel that writes them: 64 = the
 // 128 x 128 tile, 32 = the 64 x 64 tile (grids that would not fill the chip with 128 x 128 tiles).
+static int gemm_ln_plan(GemmArgs& p, const void* A, const void* W, const float* bias, const void* residual, void* C, int M, int N,
+                        int K, int in_dtype, int out_dtype, long lda, long ldw, long ldc, long ldr, int act, const float* a_stats,
+                        const float* w_colsum, const float* r_stats, const float* r_gamma, const float* r_beta, float* stats_out,
+                        int slab_in, int slab_out, float eps) {
+  if (M <= 0 || N <= 0 || K <= 0 || !A || !W || !C || (K % 64) || (N % 64)) return -1;
+  if ((in_dtype != MSMD_BF16 && in_dtype != MSMD_F16) || out_dtype != in_dtype) return -1;   // 16-bit rows in and out
+  if ((lda % 8) || (ldw % 8) || (ldc % 4) || (residual && (ldr % 4))) return -1;
+  if (((uintptr_t)A & 15) || ((uintptr_t)W & 15) || ((uintptr_t)C & 15) || ((uintptr_t)residual & 7) || ((uintptr_t)bias & 15)) return -1;
+  if ((a_stats != nullptr) != (w_colsum != nullptr)) return -1;
+  if (!bias || (a_stats && (residual || stats_out)) || (!a_stats && !residual)) return -1;   // the two epilogue modes
+  if (r_stats && (!residual || !r_gamma || !r_beta || a_stats)) return -1;   // one side per call
+  if (((uintptr_t)w_colsum & 15) || ((uintptr_t)r_gamma & 15) || ((uintptr_t)r_beta & 15) || ((uintptr_t)a_stats & 7) ||
+      ((uintptr_t)r_stats & 7) || ((uintptr_t)stats_out & 7))
+    return -1;
+  if ((a_stats || r_stats) && slab_in != 32 && slab_in != 64) return -1;
+  if (stats_out && slab_out != 32 && slab_out != 64) return -1;
+  if ((a_stats && (K % slab_in)) || (r_stats && (N % slab_in))) return -1;
+  // the tile family (gemm16_route's `cols`): the statistics' slab where the call writes them, else by the grid
+  const long tiles128 = (long)((M + 127) / 128) * ((N + 127) / 128);
+  const int cols = (stats_out ? slab_out == 64 : (tiles128 >= 192 && (N % 128) == 0)) ? 128 : 64;
+  if (cols == 128 && (N % 128)) return -1;
+  // flags: paired 16-byte stores where the rows allow them; MSMD_GEMM_ONE_TILE_PER_WORKGROUP
+  p = gemm_args(A, W, bias, residual, C, M, N, K, lda, M, 0, ldw, ldc, ldr, act & 0xff, 2 | (((act >> 19) & 1) << 4), 0, 0, 0, 0, 0,
+                1, 0, 0, 0, 2);
+  p.a_stats = a_stats; p.a_nt = a_stats ? K / slab_in : 0; p.w_colsum = w_colsum;
+  p.r_stats = r_stats; p.r_nt = r_stats ? N / slab_in : 0; p.r_gamma = r_gamma; p.r_beta = r_beta;
+  p.stats_out = stats_out; p.ln_eps = eps;
+  // the caller's tile hint chooses within the 128-column family (15 = 192 x 128, 17 = 128 x 128, 66 = A/B form of 17) or names
+  // the 256 x 256 kernel (80), which writes the same 64-column statistics slabs and reads either width
+  const int variant = gemm16_route(p, 1, 2, in_dtype == MSMD_BF16, (act >> 8) & 0xff, ((act >> 20) & 1) << 5, cols);
+  return variant ? variant : -1;      // no LayerNorm epilogue in gemm_kernel
+}
+
 extern "C" int msmd_gemm_ln(const void* A, const void* W, const float* bias, const void* residual, void* C, int M, int N,
                             int K, int in_dtype, int out_dtype, long lda, long ldw, long ldc, long ldr, int act,
                             const float* a_stats, const float* w_colsum, const float* r_stats, const float* r_gamma,
                             const float* r_beta, float* stats_out, int slab_in, int slab_out, float eps,
                             msmd_stream_t stream) {
-  if (M <= 0 || N <= 0 || K <= 0 || !A || !W || !C || (K % 64) || (N % 64)) return 1;
-  if ((in_dtype != MSMD_BF16 && in_dtype != MSMD_F16) || out_dtype != in_dtype) return 1;   // 16-bit rows in and out
-  if ((lda % 8) || (ldw % 8) || (ldc % 4) || (residual && (ldr % 4))) return 1;
-  if (((uintptr_t)A & 15) || ((uintptr_t)W & 15) || ((uintptr_t)C & 15) || ((uintptr_t)residual & 7) || ((uintptr_t)bias & 15)) return 1;
-  if ((a_stats != nullptr) != (w_colsum != nullptr)) return 1;
-  if (!bias || (a_stats && (residual || stats_out)) || (!a_stats && !residual)) return 1;   // the two epilogue modes
-  if (r_stats && (!residual || !r_gamma || !r_beta || a_stats)) return 1;   // one side per call
-  if (((uintptr_t)w_colsum & 15) || ((uintptr_t)r_gamma & 15) || ((uintptr_t)r_beta & 15) || ((uintptr_t)a_stats & 7) ||
-      ((uintptr_t)r_stats & 7) || ((uintptr_t)stats_out & 7))
-    return 1;
-  if ((a_stats || r_stats) && slab_in != 32 && slab_in != 64) return 1;
-  if (stats_out && slab_out != 32 && slab_out != 64) return 1;
-  if ((a_stats && (K % slab_in)) || (r_stats && (N % slab_in))) return 1;
-  const long tiles128 = (long)((M + 127) / 128) * ((N + 127) / 128);
-  const bool big = stats_out ? slab_out == 64 : (tiles128 >= 192 && (N % 128) == 0);
-  if (big && (N % 128)) return 1;
   GemmArgs p;
-  p.A = A; p.W = W; p.bias = bias; p.R = residual; p.C = C;
-  p.M = M; p.N = N; p.K = K;
-  p.lda = lda; p.rows_per_batch = M; p.a_batch_stride = 0; p.ldw = ldw; p.ldc = ldc; p.ldr = ldr; p.act = act & 0xff;
-  p.inv_rpb = 1.0f / (float)M; p.vec_ok = 1;
-  p.strideA = p.strideW = p.strideC = p.strideBias = p.strideR = 0;
-  p.batch_inner = 1; p.strideA2 = p.strideW2 = p.strideC2 = 0;
-  p.Z = nullptr; p.p_drop = 0.f; p.rng = nullptr; p.site = 0; p.xn = 1;
-  p.flags = ((ldc % 8) == 0 ? 2 : 0) | (((act >> 19) & 1) << 4);   // paired 16-byte stores; MSMD_GEMM_ONE_TILE_PER_WORKGROUP
-  p.a_stats = a_stats; p.a_nt = a_stats ? K / slab_in : 0; p.w_colsum = w_colsum;
-  p.r_stats = r_stats; p.r_nt = r_stats ? N / slab_in : 0; p.r_gamma = r_gamma; p.r_beta = r_beta;
-  p.stats_out = stats_out; p.ln_eps = eps;
-  hipStream_t st = (hipStream_t)stream;
-  int variant = big ? 17 : (K >= 1024 ? 9 : 12);
-  if (big && M >= 16000 && (long)((M + 191) / 192) * (N / 128) >= 400) variant = 15;    // tall grids: the 192 x 128 tile (same 64-column slabs)
-  if (big && tall_rounds_favour_192(M, tiles128, (long)((M + 191) / 192) * (N / 128))) variant = 15;
-  {   // caller's tile hint for the big-tile family (same 64-column statistics slabs): 15 = 192 x 128, 17 = 128 x 128, 66 = A/B form of 17
-    const int hint = (act >> 8) & 0xff;
-    if (big && (hint == 15 || hint == 17 || hint == 66)) variant = hint;
-    // 80 = the 256 x 256 kernel: writes the same 64-column statistics slabs, reads either width
-    const bool can8 = gemm8_takes(p, 1, 2) && (!stats_out || slab_out == 64);
-    if (can8 && (hint == 80 || (hint == 0 && !(act & MSMD_GEMM_NO_256_TILE) && gemm8_wins(M, N, K)))) variant = 80;
-  }
-  const int r = in_dtype == MSMD_BF16 ? dispatch_gemm2<bf16_t>(p, 1, st, variant) : dispatch_gemm2_f16<f16_t>(p, 1, st, variant);
-  return r >= 0 ? r : 1;
+  const int variant = gemm_ln_plan(p, A, W, bias, residual, C, M, N, K, in_dtype, out_dtype, lda, ldw, ldc, ldr, act, a_stats,
+                                   w_colsum, r_stats, r_gamma, r_beta, stats_out, slab_in, slab_out, eps);
+  return variant < 0 ? 1 : gemm_launch(p, in_dtype, out_dtype, 1, variant, (hipStream_t)stream);
+}
+
+// What msmd_gemm_ln would launch for the same arguments: the variant, or -1 for a call it rejects.  Launches nothing.
+extern "C" int msmd_gemm_ln_route(const void* A, const void* W, const float* bias, const void* residual, void* C, int M, int N,
+                                  int K, int in_dtype, int out_dtype, long lda, long ldw, long ldc, long ldr, int act,
+                                  const float* a_stats, const float* w_colsum, const float* r_stats, const float* r_gamma,
+                                  const float* r_beta, float* stats_out, int slab_in, int slab_out, float eps, msmd_stream_t) {
+  GemmArgs p;
+  return gemm_ln_plan(p, A, W, bias, residual, C, M, N, K, in_dtype, out_dtype, lda, ldw, ldc, ldr, act, a_stats, w_colsum,
+                      r_stats, r_gamma, r_beta, stats_out, slab_in, slab_out, eps);
 }
 
 extern "C" int msmd_gemm_ex(const void* A, const void* W, const float* bias, const void* residual, void* C, int M,
@@ -2293,6 +2103,18 @@ extern "C" int msmd_gemm_ex(const void* A, const void* W, const float* bias, con
   return gemm_impl(A, W, bias, residual, C, M, N, K, in_dtype, out_dtype, lda, rows_per_batch, a_batch_stride, ldw, ldc,
                    ldr, act, batch, strideA, strideW, strideC, strideBias, strideR, 1, 0, 0, 0, stream, z_out, p_drop,
                    rng_state, site);
+}
+
+// What msmd_gemm_ex (and msmd_gemm: z_out = NULL, p_drop = 0) would launch for the same arguments: the variant, 0 for
+// gemm_kernel, -1 for a call it rejects.  Launches nothing.
+extern "C" int msmd_gemm_route(const void* A, const void* W, const float* bias, const void* residual, void* C, int M,
+                               int N, int K, int in_dtype, int out_dtype, long lda, int rows_per_batch,
+                               long a_batch_stride, long ldw, long ldc, long ldr, int act, int batch, long strideA,
+                               long strideW, long strideC, long strideBias, long strideR, void* z_out, float p_drop,
+                               const unsigned long* rng_state, unsigned int site, msmd_stream_t) {
+  GemmArgs p;
+  return gemm_plan(p, A, W, bias, residual, C, M, N, K, in_dtype, out_dtype, lda, rows_per_batch, a_batch_stride, ldw, ldc, ldr,
+                   act, batch, strideA, strideW, strideC, strideBias, strideR, 1, 0, 0, 0, z_out, p_drop, rng_state, site, 0);
 }
 
 // dZ = keep_mask / (1 - p) * act'(Z) * (A . W^T): the data gradient of a Linear whose INPUT was dropout(act(Z)) -- the product

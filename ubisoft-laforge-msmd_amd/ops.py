@@ -321,22 +321,17 @@ def gemm(a, w, bias=None, residual=None, act=ACT_NONE, out=None, out_dtype=None,
         if v is None:
             v = _autotune_gemm(lib, args, key, out, residual)
         args[16] = act | (v << 8)
-    if z_out is not None or p_drop > 0.0:
-        _lib.check(lib.msmd_gemm_ex(*args[:-1], _p(z_out), float(p_drop), _p(rng_state), int(site), args[-1]),
-                   "msmd_gemm_ex")
+    train = z_out is not None or p_drop > 0.0
+    if train or GEMM_TRACE is not None:
+        ex = (*args[:-1], _p(z_out), float(p_drop), _p(rng_state), int(site), args[-1])
+    if train:
+        _lib.check(lib.msmd_gemm_ex(*ex), "msmd_gemm_ex")
     else:
         _lib.check(lib.msmd_gemm(*args), "msmd_gemm")
     if GEMM_TRACE is not None:
         e1.record()
-        # last field: did the library run this launch on its 256 x 256-tile kernel (what the kernel takes + the shape rule)
-        if isinstance(a, Split):
-            t256 = (variant in (0, 80) and not (flags & GEMM_NO_256_TILE) and batch == 1 and N % 256 == 0 and K % 32 == 0 and K >= 64
-                    and (variant == 80 or bool(lib.msmd_gemm_256_tile_rule_f16x2(M, N, K, int(bool(flags & GEMM_W_BELOW_32))))))
-        else:
-            t256 = (variant in (0, 80) and not (flags & GEMM_NO_256_TILE) and batch == 1 and z_out is None and not p_drop > 0.0
-                    and a.dtype in (torch.bfloat16, torch.float16) and out.dtype == a.dtype
-                    and (variant == 80 or bool(lib.msmd_gemm_256_tile_rule(M, N, K))) and N % 256 == 0 and K % 64 == 0 and K >= 128)
-        GEMM_TRACE.append((M, N, K, batch, _dt(a), e0, e1, t256))
+        # last field: did the library run this launch on its 256 x 256-tile kernel
+        GEMM_TRACE.append((M, N, K, batch, _dt(a), e0, e1, lib.msmd_gemm_route(*ex) == 80))
     return out
 
 
@@ -380,15 +375,14 @@ def gemm_ln(a, w, bias=None, residual=None, act=ACT_NONE, out=None, out_dtype=No
     if GEMM_TRACE is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-    _lib.check(lib.msmd_gemm_ln(_p(a), _p(w), _p(bias), _p(residual), _p(out), M, N, K, _dt(a), _dt(out), a.stride(-2) if a.dim() >= 2 else K,
-                                w.stride(0), N, ldr, act | GEMM_LN_FLAGS | (((66 if GEMM_LN_ALL_IN_ONE else (GEMM_LN_ROUTER(M, N, K) or 0) if GEMM_LN_ROUTER is not None else (GEMM_LN_TILE or 0))) << 8), _p(a_stats), _p(w_colsum), _p(r_stats), _p(r_gamma),
-                                _p(r_beta), _p(st), slab_in, slab_out, float(eps), _stream()), "msmd_gemm_ln")
+    hint = 66 if GEMM_LN_ALL_IN_ONE else ((GEMM_LN_ROUTER(M, N, K) or 0) if GEMM_LN_ROUTER is not None else (GEMM_LN_TILE or 0))
+    args = (_p(a), _p(w), _p(bias), _p(residual), _p(out), M, N, K, _dt(a), _dt(out), a.stride(-2) if a.dim() >= 2 else K,
+            w.stride(0), N, ldr, act | GEMM_LN_FLAGS | (hint << 8), _p(a_stats), _p(w_colsum), _p(r_stats), _p(r_gamma),
+            _p(r_beta), _p(st), slab_in, slab_out, float(eps), _stream())
+    _lib.check(lib.msmd_gemm_ln(*args), "msmd_gemm_ln")
     if GEMM_TRACE is not None:
         e1.record()
-        hint = 66 if GEMM_LN_ALL_IN_ONE else ((GEMM_LN_ROUTER(M, N, K) or 0) if GEMM_LN_ROUTER is not None else (GEMM_LN_TILE or 0))
-        t256 = ((hint == 80 or (hint == 0 and not (GEMM_LN_FLAGS & GEMM_NO_256_TILE) and bool(lib.msmd_gemm_256_tile_rule(M, N, K))))
-                and N % 256 == 0 and K >= 128 and (st is None or slab_out == 64) and (sin is None or M % 2 == 0))
-        GEMM_TRACE.append((M, N, K, 1, _dt(a), e0, e1, t256))
+        GEMM_TRACE.append((M, N, K, 1, _dt(a), e0, e1, lib.msmd_gemm_ln_route(*args) == 80))
     return (out, st) if st is not None else out
 
 
