@@ -216,10 +216,24 @@ def test_sampler_target_noise_fp32():
     T = 3
     model.diffusion_sched = DiffusionSchedule(T, "linear").to(DEV)
     z = g["noise_z"]
-    y, _, _ = model.sample(dev(x["audio_feat"]), dev(x["shape"]), dev(x["style"]),
-                           motion_at_T=dev(synth.normalish("sm/xT", (2, 100, 67))), cfg_scale=1.15,
-                           indicator=dev(x["indicator"]), noise={T - i: dev(z[i]) for i in range(T - 1)})
+    inputs = (dev(x["audio_feat"]), dev(x["shape"]), dev(x["style"]))
+    kw = dict(motion_at_T=dev(synth.normalish("sm/xT", (2, 100, 67))), cfg_scale=1.15, indicator=dev(x["indicator"]))
+    y, _, _ = model.sample(*inputs, noise={T - i: dev(z[i]) for i in range(T - 1)}, **kw)
     assert maxabs(y.cpu().numpy(), g["noise_x0"]) < 2e-4
+    # the captured loop takes target 'noise' through msmd_cfg_ddpm_step_dev: the eager loop's bits under the same (zero)
+    # noise, on one lane and on two
+    from msmd_amd import sampler as smp
+    eager, _, _ = model.sample(*inputs, noise={t: torch.zeros(2, 100, 67, device=DEV) for t in range(2, T + 1)}, **kw)
+    try:
+        for lanes in (1, 2):
+            model.__dict__.pop("_step_graphs", None)
+            with mock.patch.object(smp, "MIN_LANE_SEQS", 1), mock.patch.object(smp, "LANES", lanes), \
+                    mock.patch.object(smp, "_step_noise", side_effect=lambda B, L, dm, d: torch.zeros(B, L, dm, device=d)):
+                graph, _, _ = model.sample(*inputs, **kw)
+                assert next(iter(model._step_graphs.values())).lanes == lanes
+            assert torch.equal(eager, graph), lanes
+    finally:
+        model.__dict__.pop("_step_graphs", None)
 
 
 def test_infer_coeffs_fp32():
@@ -418,8 +432,19 @@ def test_sampler_hip_graph_matches_eager():
                 assert next(iter(model._step_graphs.values())).lanes == lanes
             seeded.append(out)
         assert torch.equal(seeded[0], seeded[1]) and not torch.equal(seeded[0], rnd)
+        # the eager loop's own draws (noise=None: one generator call per step t > 1): the same bits under the same seed, and
+        # not the zero-noise ones
+        model.use_hip_graph = False
+        drawn = []
+        for _ in range(2):
+            torch.manual_seed(4242)
+            out, _, _ = model.sample(dev(x["audio_feat"]), dev(x["shape"]), dev(x["style"]), dev(x["prev_motion"]),
+                                     dev(x["prev_audio"]), motion_at_T=xT, indicator=dev(x["indicator"]), **kw)
+            drawn.append(out)
+        assert torch.equal(drawn[0], drawn[1]) and not torch.equal(drawn[0], eager)
     finally:
         model.diffusion_sched = old
+        model.__dict__.pop("use_hip_graph", None)
         model.__dict__.pop("_step_graphs", None)
 
 

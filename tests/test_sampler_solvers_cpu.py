@@ -1,18 +1,19 @@
-"""Few-step solver tables (sampler.solver_table) on the host: timesteps, the DDPM identity of DDIM(eta = 1, S = T), the
-first-order rows of DPM-Solver++(2M), and the argument checks.  No GPU."""
+"""Update-rule tables on the host: the DDPM table (sampler.ddpm_table) against its per-step restatement, and the few-step solver
+tables (sampler.solver_table): timesteps, the DDPM identity of DDIM(eta = 1, S = T), the first-order rows of
+DPM-Solver++(2M), and the argument checks.  No GPU."""
 import math
 
 import pytest
 import torch
 
 from msmd_amd.model import DiffusionSchedule
-from msmd_amd.sampler import check_solver, solver_table
+from msmd_amd.sampler import check_solver, ddpm_table, solver_table
 
 SCHEDS = {T: DiffusionSchedule(T, "cosine") for T in (500, 20)}
 
 
-def ddpm_coefficients(sched, t, target):
-    """The sampler's coefficients(t) at flexibility 0, restated: (c0, c1, sigma) in fp32 as the reference computes them."""
+def ddpm_coefficients(sched, t, target, flexibility=0):
+    """The DDPM step's (c0, c1, sigma) at timestep t, restated one element at a time in fp32 as the reference computes them."""
     alpha, ab, abp = sched.alphas.float()[t], sched.alpha_bars.float()[t], sched.alpha_bars.float()[t - 1]
     if target == "noise":
         c0 = 1 / torch.sqrt(alpha)
@@ -20,7 +21,22 @@ def ddpm_coefficients(sched, t, target):
     else:
         c0 = (1 - abp) * torch.sqrt(alpha) / (1 - ab)
         c1 = (1 - alpha) * torch.sqrt(abp) / (1 - ab)
-    return float(c0), float(c1), float(sched.sigmas_inflex.float()[t])
+    sigma = sched.sigmas_flex.float()[t] * flexibility + sched.sigmas_inflex.float()[t] * (1 - flexibility)
+    return float(c0), float(c1), float(sigma)
+
+
+@pytest.mark.parametrize("T", [500, 20])
+@pytest.mark.parametrize("target", ["sample", "noise"])
+@pytest.mark.parametrize("flexibility", [0, 0.3])
+def test_ddpm_table_is_the_per_step_restatement(T, target, flexibility):
+    """Exact: the table's column operations and the restatement's scalar ones are the same correctly rounded IEEE fp32
+    operations (sub, mul, div, sqrt) in the same order.  Row 1 carries sigma = 0 (no noise on the last step)."""
+    sched = SCHEDS[T]
+    table = ddpm_table(sched, flexibility, target)
+    assert table.dtype == torch.float32 and table.shape == (T + 1, 3)
+    for t in range(2, T + 1):
+        assert tuple(table[t].tolist()) == ddpm_coefficients(sched, t, target, flexibility), t
+    assert tuple(table[1].tolist()) == ddpm_coefficients(sched, 1, target, flexibility)[:2] + (0.0,)
 
 
 @pytest.mark.parametrize("T", [500, 20])

@@ -11,6 +11,8 @@ from __future__ import annotations
 
 import math
 import os
+from collections import namedtuple
+from types import SimpleNamespace
 
 import torch
 
@@ -91,6 +93,129 @@ def solver_table(sched, steps, solver, eta=0.0, target="sample"):
     return taus, rows
 
 
+def ddpm_table(sched, flexibility=0, target="sample"):
+    """Per-step coefficients of the reference's ancestral chain (model.py:383-395) as one fp32 host table of shape (T+1, 3).
+
+    Row t = (c0, c1, sigma) is what msmd_cfg_ddpm_step applies on the step from t to t - 1:
+      target 'sample':  x <- c0 x + c1 theta + sigma z,  c0 = (1 - abar_{t-1}) sqrt(alpha_t) / (1 - abar_t),
+                                                        c1 = (1 - alpha_t) sqrt(abar_{t-1}) / (1 - abar_t);
+      target 'noise':   x <- c0 (x - c1 theta) + sigma z,  c0 = 1 / sqrt(alpha_t),  c1 = (1 - alpha_t) / sqrt(1 - abar_t);
+      sigma = sigmas_flex[t] flexibility + sigmas_inflex[t] (1 - flexibility).
+    Every operation is the reference's fp32 tensor operation in the reference's order, on whole columns of
+    sched.host_tables() instead of one element at a time, so each entry has the bits the reference computes.  Row 1's sigma
+    is 0 (the last step adds no noise: z = 0 at t = 1); row 0 is unused (zeros)."""
+    if target not in ("sample", "noise"):
+        raise ValueError("Unknown target type: {}".format(target))
+    tab = sched.host_tables()
+    alpha, alpha_bar, alpha_bar_prev = tab["alphas"][1:], tab["alpha_bars"][1:], tab["alpha_bars"][:-1]
+    sigma = tab["sigmas_flex"][1:] * flexibility + tab["sigmas_inflex"][1:] * (1 - flexibility)
+    if target == "noise":
+        c0 = 1 / torch.sqrt(alpha)
+        c1 = (1 - alpha) / torch.sqrt(1 - alpha_bar)
+    else:
+        c0 = (1 - alpha_bar_prev) * torch.sqrt(alpha) / (1 - alpha_bar)
+        c1 = (1 - alpha) * torch.sqrt(alpha_bar_prev) / (1 - alpha_bar)
+    table = torch.zeros(int(sched.num_steps) + 1, 3)
+    table[1:] = torch.stack([c0, c1, sigma], dim=1)
+    table[1, 2] = 0.0
+    return table
+
+
+# The update rule of one sample() call, for both loops: they take steps i = steps .. 1, and step i leaves timestep times[i] for
+# times[i - 1].  table: (steps + 1, width) fp32 on the host, row i = the step's coefficients; the eager loop passes the row
+# as scalars and the graph loop copies the table to the device, so both apply the same bits.  noisy[i]: step i takes a draw z
+# (noise[times[i]], or one generator call); the others get z = None.  has_d_prev: the step also reads and writes the previous
+# data prediction.  select(emb_all, coef_table, t_dev, emb_row, coefs): row t_dev of both tables, on the device.
+# step / step_dev(o, x, res, z, d_prev, row): the fused CFG combine + update with the row as host scalars / in device memory.
+_Rule = namedtuple("_Rule", "name target steps times table noisy has_d_prev select step step_dev")
+
+
+def _update_rule(sched, solver, steps, eta, flexibility, target):
+    tgt = 0 if target == "sample" else 1
+    if solver == "ddpm":
+        # the reference's ancestral chain: every timestep T .. 1, a draw for every t > 1
+        T = int(sched.num_steps)
+        return _Rule(
+            solver, tgt, T, list(range(T + 1)), ddpm_table(sched, flexibility, target), [t > 1 for t in range(T + 1)], False,
+            ops.sampler_step_select,
+            lambda o, x, res, z, d_prev, row: ops.cfg_ddpm_step(x, res, z, o.scales, o.n_entries, o.Lp, o.mode, tgt, *row),
+            lambda o, x, res, z, d_prev, row: ops.cfg_ddpm_step_dev(x, res, z, o.scales, row, o.n_entries, o.Lp, o.mode, tgt))
+    # a few-step solver draws only where its row's sigma is not 0; its float64 rows are rounded to fp32 here as the scalar
+    # arguments of msmd_cfg_solver_step are
+    taus, rows = solver_table(sched, steps, solver, eta, target)
+    return _Rule(
+        solver, tgt, steps, taus, rows.float(), (rows[:, 5] != 0).tolist(), True, ops.sampler_solver_select,
+        lambda o, x, res, z, d_prev, row: ops.cfg_solver_step(x, res, z, o.scales, d_prev, o.n_entries, o.Lp, o.mode, *row),
+        lambda o, x, res, z, d_prev, row: ops.cfg_solver_step_dev(x, res, z, o.scales, d_prev, row, o.n_entries, o.Lp, o.mode))
+
+
+class _Operands(namedtuple("_Operands", "net P dtype dev B n_entries N L Lp dm nb mode dyn "
+                                        "prev_m ind mem kv_list cross_list stat tok_person emb_all scales")):
+    """Everything the hoisted section of sample() produces and a denoising step consumes.  N = n_entries * B rows, entry-major;
+    mode: the CFG combine, 0 incremental / 1 independent; dyn: the dynamic threshold's (ratio, min, max) or None; stat has B rows
+    or one; emb_all has one step embedding per row of the rule's table; ind, cross_list and scales may be None.  A lane of the
+    graph loop holds the same record with B, N and the tensors of its own rows (_Lane)."""
+
+    def trunk(self, x, feats, emb_row):
+        """pack x into the denoiser input -> decoder trunk; returns dec (N, Lp + L, dm + nb)."""
+        ops.denoiser_pack_input(x, self.prev_m, self.ind, feats)
+        return self.net.trunk(feats, self.tok_person, self.mem, self.dtype, kv_list=self.kv_list, row0_add=emb_row,
+                              cross_list=self.cross_list)
+
+    def threshold(self, res):
+        if self.dyn:
+            # K15 (off in the reference's inference driver, inference.py:272): quantile + clamp in one launch
+            res = ops.dynamic_threshold_(res.float().contiguous(), self.L, *self.dyn)
+        return res
+
+    def heads(self, dec):
+        """heads / static mix -> optional dynamic threshold; returns res (N, Lp + L, dm)."""
+        return self.threshold(ops.heads_static_mix(dec, self.stat, self.Lp + self.L, self.dm, self.nb, self.net.use_head_alpha,
+                                                   self.net.regularize_alpha == "sigmoid"))
+
+
+class _Streams:
+    """sample_separate's step (reference model.py:442-651): the diagnostic variant that also tracks the dynamic / static /
+    alpha streams, in host-library tensor algebra on (N, 110, 4, 67)-sized data."""
+
+    def __init__(self, o, x, separate, cfg_scale):
+        self.o, self.sep, self.cfg_scale = o, separate, cfg_scale
+        self.cum_static, self.alpha_traj = torch.zeros_like(x), []
+        self.stat_full = o.stat[torch.arange(o.N, device=o.dev) % o.stat.shape[0]]  # (N, nb, dm): real style for every entry
+
+    def step(self, dec, x, z, target, row):
+        o, (c0, c1, sigma) = self.o, row
+        dyn, alpha_t = dec[..., :o.dm], dec[..., o.dm:]
+        if self.sep.get("alpha_mod") is not None:
+            alpha_t = self.sep["alpha_mod"](alpha_t)
+        sf = self.stat_full[:, None]  # (N, 1, nb, dm)
+        if o.net.use_head_alpha:
+            static = (sf * alpha_t.unsqueeze(-1)).sum(dim=2)
+        else:
+            static = torch.cat([(sf[..., :-3] * alpha_t.unsqueeze(-1)).sum(dim=2),
+                                sf[..., -3:].sum(dim=2).expand(-1, o.Lp + o.L, -1)], dim=-1)
+        res = o.threshold(dyn + static)
+        streams = [list(v.contiguous().clone().chunk(o.n_entries)) for v in (res, static, dyn, alpha_t)]
+        heads = [st[0][:, -o.L:] for st in streams]  # views: in-place accumulation as the reference (model.py:590-618)
+        for i in range(o.n_entries - 1):
+            for st, hd in zip(streams, heads):
+                base = st[0] if o.mode == 1 else st[i]
+                hd += self.cfg_scale[i] * (st[i + 1][:, -o.L:] - base[:, -o.L:])
+        theta, theta_static, self.theta_dyn, self.theta_alpha = heads
+        zz = z if z is not None else torch.zeros_like(x)
+        if target == 1:
+            x = c0 * (x - c1 * theta) + sigma * zz
+        else:
+            x = c0 * x + c1 * theta + sigma * zz
+        self.cum_static = self.cum_static + c1 * theta_static
+        self.alpha_traj.append(self.theta_alpha)
+        return x
+
+    def outputs(self):
+        last_alpha = torch.cat(self.alpha_traj, dim=0) if self.sep.get("return_all_alpha") else self.theta_alpha
+        return self.theta_dyn, self.cum_static, last_alpha
+
+
 def _entries(cfg_cond, cfg_mode):
     """(use_audio, use_style) per CFG entry in batch order; entry 0 is the null entry (model.py:340-366)."""
     ent = [("audio" not in cfg_cond, "style" not in cfg_cond)]
@@ -117,8 +242,7 @@ def sample(model, audio_or_feat, shape_feat, style_feat=None, prev_motion_feat=N
     solver: "ddpm" (the reference's ancestral chain over all T steps), or "ddim" (eta in [0, 1]) / "dpmpp_2m" over
     sample_steps timesteps (solver_table); noise is then keyed by the source timestep of each step."""
     S = check_solver(model.diffusion_sched.num_steps, sample_steps, solver, eta, flexibility)
-    few = solver != "ddpm"
-    if few and (guidance is not None or separate is not None):
+    if solver != "ddpm" and (guidance is not None or separate is not None):
         raise ValueError(f"solver={solver!r} is available in sample() only (not with guidance or stream separation)")
     net = model.denoising_net
     dtype = model.compute_dtype
@@ -189,139 +313,53 @@ def sample(model, audio_or_feat, shape_feat, style_feat=None, prev_motion_feat=N
     # ---- step-invariant work, hoisted
     P = net.pack(dtype)
     T = model.diffusion_sched.num_steps
-    tab = model.diffusion_sched.host_tables()
+    rule = _update_rule(model.diffusion_sched, solver, S, eta, flexibility, model.target)
     mem = torch.cat([ops.cast(prev_a.contiguous(), dtype), ops.cast(audio_in.contiguous(), dtype)], dim=1)
     kv_list = net.memory_kv(mem, dtype)
-    cross_list = (net.memory_cross(kv_list, dtype)
-                  if (net.pack(dtype).diag and getattr(net, "diag_fast_path", True)) else None)
+    cross_list = net.memory_cross(kv_list, dtype) if (P.diag and getattr(net, "diag_fast_path", True)) else None
     stat = net.static_bases(style_feat, dtype).float().contiguous()  # real style for every entry (model.py:374)
     pf = ops.pad_cols(person_in.reshape(N, -1).float().contiguous(), P.kp_person, dtype)
     tok_person = ops.gemm(pf, *P.pp)                                   # (N, d) without the step embedding
-    if few:
-        # only the rows the solver visits: emb_all[i] is the step embedding of timestep taus[i]
-        taus, rows = solver_table(model.diffusion_sched, S, solver, eta, model.target)
-        te_all = ops.cast(P.te[torch.as_tensor(taus, device=P.te.device)].contiguous(), dtype)
-    else:
-        te_all = ops.cast(P.te[: T + 1].contiguous(), dtype)
+    # a few-step solver: only the rows it visits (emb_all[i] is the step embedding of timestep taus[i])
+    te = P.te[: T + 1] if solver == "ddpm" else P.te[torch.as_tensor(rule.times, device=P.te.device)]
+    te_all = ops.cast(te.contiguous(), dtype)
     emb_all = ops.gemm(ops.gemm(te_all, *P.ds0, act=ops.ACT_GELU), *P.ds2)  # (T+1, d); (S+1, d) for a few-step solver
     scales = torch.tensor(list(cfg_scale), device=dev, dtype=torch.float32) if n_entries > 1 else None
-    mode = 1 if cfg_mode == "independent" else 0
-    target = 0 if model.target == "sample" else 1
+    o = _Operands(net=net, P=P, dtype=dtype, dev=dev, B=batch_size, n_entries=n_entries, N=N, L=L, Lp=Lp, dm=dm, nb=nb,
+                  mode=1 if cfg_mode == "independent" else 0, dyn=tuple(dynamic_threshold) if dynamic_threshold else None,
+                  prev_m=prev_m, ind=ind_in, mem=mem, kv_list=kv_list, cross_list=cross_list, stat=stat,
+                  tok_person=tok_person, emb_all=emb_all, scales=scales)
 
-    def coefficients(t):
-        alpha = tab["alphas"][t]
-        alpha_bar = tab["alpha_bars"][t]
-        alpha_bar_prev = tab["alpha_bars"][t - 1]
-        sigma = tab["sigmas_flex"][t] * flexibility + tab["sigmas_inflex"][t] * (1 - flexibility)
-        if target == 1:
-            c0 = 1 / torch.sqrt(alpha)
-            c1 = (1 - alpha) / torch.sqrt(1 - alpha_bar)
-        else:
-            c0 = (1 - alpha_bar_prev) * torch.sqrt(alpha) / (1 - alpha_bar)
-            c1 = (1 - alpha) * torch.sqrt(alpha_bar_prev) / (1 - alpha_bar)
-        return float(c0), float(c1), float(sigma)
-
-    use_graph = (noise is None and not ret_traj and getattr(model, "use_hip_graph", True)
-                 and T > 1 and guidance is None and separate is None)
-    if use_graph:
-        x = _graph_loop(model, net, dtype, dev, T, N, n_entries, Lp, L, dm, nb, mode, target, P, motion_at_T, prev_m,
-                        ind_in, mem, kv_list, stat, tok_person, emb_all, scales, coefficients,
-                        tuple(dynamic_threshold) if dynamic_threshold else None, cross_list,
-                        solver=(solver, S, rows) if few else None)
-        return x, motion_at_T, audio_feat
-    if few:
-        return _solver_eager_loop(net, dtype, dev, N, n_entries, Lp, L, dm, nb, mode, P, motion_at_T, prev_m, ind_in, mem,
-                                  kv_list, cross_list, stat, tok_person, emb_all, scales, dynamic_threshold, ret_traj, noise,
-                                  taus, rows), motion_at_T, audio_feat
+    if (noise is None and not ret_traj and getattr(model, "use_hip_graph", True) and T > 1 and guidance is None
+            and separate is None):
+        return _graph_loop(model, o, rule, motion_at_T.float()), motion_at_T, audio_feat
 
     x = motion_at_T.float().clone().contiguous()
-    traj = {T: motion_at_T} if ret_traj else None
+    d_prev = torch.zeros_like(x) if rule.has_d_prev else None
+    traj = {rule.times[-1]: motion_at_T} if ret_traj else None
     feats = torch.empty(N, 1 + Lp + L, P.kp_feat, device=dev, dtype=dtype)
-    if separate is not None:
-        cum_static = torch.zeros_like(x)
-        alpha_traj = []
-        stat_full = stat[torch.arange(N, device=dev) % stat.shape[0]]  # (N, nb, dm): real style for every entry
-    for t in range(T, 0, -1):
-        if t > 1:
-            z = noise[t].float().contiguous() if noise is not None else torch.randn_like(x)
-        else:
-            z = None
-        c0, c1, sigma = coefficients(t)
+    streams = _Streams(o, x, separate, cfg_scale) if separate is not None else None
+    for i in range(rule.steps, 0, -1):
+        z = None
+        if rule.noisy[i]:
+            z = noise[rule.times[i]].float().contiguous() if noise is not None else torch.randn_like(x)
+        row = rule.table[i].tolist()
         x_in = x
         if guidance is not None and guidance[0] is not None:
             x_in = x.clone()
             x_in[:, guidance[0], :] = guidance[1].to(x_in.dtype)
-        ops.denoiser_pack_input(x_in, prev_m, ind_in, feats)
-        dec = net.trunk(feats, tok_person, mem, dtype, kv_list=kv_list, row0_add=emb_all[t], cross_list=cross_list)
-        if separate is None:
-            res = ops.heads_static_mix(dec, stat, Lp + L, dm, nb, net.use_head_alpha, net.regularize_alpha == "sigmoid")
+        dec = o.trunk(x_in, feats, emb_all[i])
+        if streams is None:
+            rule.step(o, x, o.heads(dec), z, d_prev, row)
         else:
-            # diagnostic variant: stream bookkeeping in host-library tensor algebra on (N, 110, 4, 67)-sized data
-            dyn, alpha_t = dec[..., :dm], dec[..., dm:]
-            if separate.get("alpha_mod") is not None:
-                alpha_t = separate["alpha_mod"](alpha_t)
-            sf = stat_full[:, None]  # (N, 1, nb, dm)
-            if net.use_head_alpha:
-                static = (sf * alpha_t.unsqueeze(-1)).sum(dim=2)
-            else:
-                static = torch.cat([(sf[..., :-3] * alpha_t.unsqueeze(-1)).sum(dim=2),
-                                    sf[..., -3:].sum(dim=2).expand(-1, Lp + L, -1)], dim=-1)
-            res = dyn + static
-        if dynamic_threshold:
-            # K15 (off in the reference's inference driver, inference.py:272): quantile + clamp in one launch
-            dt_ratio, dt_min, dt_max = dynamic_threshold
-            res = ops.dynamic_threshold_(res.float().contiguous(), L, dt_ratio, dt_min, dt_max)
-        if separate is None:
-            ops.cfg_ddpm_step(x, res, z, scales, n_entries, Lp, mode, target, c0, c1, sigma)
-        else:
-            streams = [list(v.contiguous().clone().chunk(n_entries)) for v in (res, static, dyn, alpha_t)]
-            heads = [st[0][:, -L:] for st in streams]  # views: in-place accumulation as the reference (model.py:590-618)
-            for i in range(n_entries - 1):
-                for st, hd in zip(streams, heads):
-                    base = st[0] if cfg_mode == "independent" else st[i]
-                    hd += cfg_scale[i] * (st[i + 1][:, -L:] - base[:, -L:])
-            theta, theta_static, theta_dyn, theta_alpha = heads
-            zz = z if z is not None else torch.zeros_like(x)
-            if target == 1:
-                x = c0 * (x - c1 * theta) + sigma * zz
-            else:
-                x = c0 * x + c1 * theta + sigma * zz
-            cum_static = cum_static + c1 * theta_static
-            alpha_traj.append(theta_alpha)
+            x = streams.step(dec, x, z, rule.target, row)
         if ret_traj:
-            traj[t - 1] = x.clone()
+            traj[rule.times[i - 1]] = x.clone()
     if ret_traj:
         return traj, motion_at_T, audio_feat
-    if separate is not None:
-        last_alpha = torch.cat(alpha_traj, dim=0) if separate.get("return_all_alpha") else theta_alpha
-        return x, motion_at_T, audio_feat, theta_dyn, cum_static, last_alpha
+    if streams is not None:
+        return (x, motion_at_T, audio_feat) + streams.outputs()
     return x, motion_at_T, audio_feat
-
-
-def _solver_eager_loop(net, dtype, dev, N, n_entries, Lp, L, dm, nb, mode, P, motion_at_T, prev_m, ind_in, mem, kv_list,
-                       cross_list, stat, tok_person, emb_all, scales, dynamic_threshold, ret_traj, noise, taus, rows):
-    """The few-step solvers' host-driven loop: the DDPM loop's pack -> trunk -> heads -> threshold sequence, then the
-    fused solver update.  Step i reads the draw noise[taus[i]] (or a fresh one) only where its sigma is not 0."""
-    S = len(taus) - 1
-    x = motion_at_T.float().clone().contiguous()
-    d_prev = torch.zeros_like(x)
-    traj = {taus[S]: motion_at_T} if ret_traj else None
-    feats = torch.empty(N, 1 + Lp + L, P.kp_feat, device=dev, dtype=dtype)
-    for i in range(S, 0, -1):
-        p0, p1, ax, ath, b1, sigma = rows[i].tolist()
-        z = None
-        if sigma != 0:
-            z = noise[taus[i]].float().contiguous() if noise is not None else torch.randn_like(x)
-        ops.denoiser_pack_input(x, prev_m, ind_in, feats)
-        dec = net.trunk(feats, tok_person, mem, dtype, kv_list=kv_list, row0_add=emb_all[i], cross_list=cross_list)
-        res = ops.heads_static_mix(dec, stat, Lp + L, dm, nb, net.use_head_alpha, net.regularize_alpha == "sigmoid")
-        if dynamic_threshold:
-            dt_ratio, dt_min, dt_max = dynamic_threshold
-            res = ops.dynamic_threshold_(res.float().contiguous(), L, dt_ratio, dt_min, dt_max)
-        ops.cfg_solver_step(x, res, z, scales, d_prev, n_entries, Lp, mode, p0, p1, ax, ath, b1, sigma)
-        if ret_traj:
-            traj[taus[i - 1]] = x.clone()
-    return traj if ret_traj else x
 
 
 # clamped to [1, 50]: k bodies in one graph keep k steps of intermediates alive in the graph's private pool (about 0.2 GB per
@@ -344,92 +382,78 @@ def _step_noise(B, L, dm, dev):
 
 
 class _Lane:
-    """Static operand buffers + the step body of one lane (Bl clips x n_entries CFG entries, entry-major rows).
-    few: a few-step solver's body (6-wide coefficient rows, the previous data prediction d_prev) instead of DDPM's."""
+    """Static operand buffers + the step body of one lane (Bl clips x n_entries CFG entries, entry-major rows): the operands
+    record of its own rows (self.o), the state x (and d_prev where the rule has one) and the device-side step counter."""
 
-    def __init__(self, net, dtype, dev, T, Bl, n_entries, Lp, L, dm, nb, mode, target, P, like, shared, rows, clips, dyn,
-                 few=False):
-        Nl = Bl * n_entries
-        take = lambda t: torch.zeros((len(rows),) + tuple(t.shape[1:]), device=dev, dtype=t.dtype)
+    def __init__(self, o, rule, shared, rows, clips):
+        dev, Bl = o.dev, len(clips)
+        take = lambda t, idx=rows: torch.zeros((len(idx),) + tuple(t.shape[1:]), device=dev, dtype=t.dtype)
+        self.rule, self.shared = rule, shared
         self.rows, self.clips = rows, clips          # index tensors into the N-row / B-row operands of the whole batch
-        self.x = torch.zeros(Bl, L, dm, device=dev, dtype=torch.float32)
-        self.prev_m = take(like["prev_m"])
-        self.ind = take(like["ind_in"]) if like["ind_in"] is not None else None
-        self.mem = take(like["mem"])
-        self.kv = [take(k) for k in like["kv_list"]]
-        self.cross = [take(r) for r in like["cross_list"]] if like.get("cross_list") is not None else None
-        self.stat_per_clip = bool(like["stat_per_clip"])     # stated by sample(): one row of static bases per clip (not one shared row)
-        self.stat = (torch.zeros((Bl,) + tuple(like["stat"].shape[1:]), device=dev, dtype=like["stat"].dtype)
-                     if self.stat_per_clip else shared["stat"])
-        self.tok = take(like["tok_person"])
+        self.x = torch.zeros(Bl, o.L, o.dm, device=dev, dtype=torch.float32)
+        self.own_stat = o.stat.shape[0] == o.B and o.B > 1      # one row of static bases per clip (not one shared row)
+        self.o = o._replace(
+            B=Bl, N=len(rows), prev_m=take(o.prev_m), ind=take(o.ind) if o.ind is not None else None, mem=take(o.mem),
+            kv_list=[take(k) for k in o.kv_list],
+            cross_list=[take(r) for r in o.cross_list] if o.cross_list is not None else None,
+            stat=take(o.stat, clips) if self.own_stat else shared.stat,
+            tok_person=take(o.tok_person), emb_all=shared.emb_all, scales=shared.scales)
         self.t_dev = torch.zeros(1, device=dev, dtype=torch.int32)
-        self.emb_row = torch.zeros(shared["emb_all"].shape[-1], device=dev, dtype=shared["emb_all"].dtype)
-        self.coefs = torch.zeros(6 if few else 3, device=dev, dtype=torch.float32)
-        self.d_prev = torch.zeros(Bl, L, dm, device=dev, dtype=torch.float32) if few else None
-        self.feats = torch.zeros(Nl, 1 + Lp + L, P.kp_feat, device=dev, dtype=dtype)
+        self.emb_row = torch.zeros(o.emb_all.shape[-1], device=dev, dtype=o.emb_all.dtype)
+        self.coefs = torch.zeros(rule.table.shape[1], device=dev, dtype=torch.float32)
+        self.d_prev = torch.zeros_like(self.x) if rule.has_d_prev else None
+        self.feats = torch.zeros(len(rows), 1 + o.Lp + o.L, o.P.kp_feat, device=dev, dtype=o.dtype)
 
-        def body(z):
-            select = ops.sampler_solver_select if few else ops.sampler_step_select
-            select(shared["emb_all"], shared["coef_table"], self.t_dev, self.emb_row, self.coefs)
-            ops.denoiser_pack_input(self.x, self.prev_m, self.ind, self.feats)
-            dec = net.trunk(self.feats, self.tok, self.mem, dtype, kv_list=self.kv, row0_add=self.emb_row,
-                            cross_list=self.cross)
-            res = ops.heads_static_mix(dec, self.stat, Lp + L, dm, nb, net.use_head_alpha,
-                                       net.regularize_alpha == "sigmoid")
-            if dyn:
-                res = ops.dynamic_threshold_(res.float().contiguous(), L, *dyn)
-            # z: this lane's clips of the step's noise, drawn for the WHOLE batch on the forking stream (_StepGraph.bodies): what a
-            # clip receives under a given seed does not depend on the lane count; sigma_1 = 0 reproduces z = 0 at t = 1
-            if few:
-                ops.cfg_solver_step_dev(self.x, res, z, shared["scales"], self.d_prev, self.coefs, n_entries, Lp, mode)
-            else:
-                ops.cfg_ddpm_step_dev(self.x, res, z, shared["scales"], self.coefs, n_entries, Lp, mode, target)
-        self.body = body
+    def body(self, z):
+        o = self.o
+        self.rule.select(o.emb_all, self.shared.coef_table, self.t_dev, self.emb_row, self.coefs)
+        res = o.heads(o.trunk(self.x, self.feats, self.emb_row))
+        # z: this lane's clips of the step's noise, drawn for the WHOLE batch on the forking stream (_StepGraph.bodies): what a
+        # clip receives under a given seed does not depend on the lane count; sigma_1 = 0 reproduces z = 0 at t = 1
+        self.rule.step_dev(o, self.x, res, z, self.d_prev, self.coefs)
 
-    def load(self, motion_at_T, ops_in):
+    def load(self, motion_at_T, whole):
+        """Copy this lane's rows of the whole batch's operands into its static buffers."""
+        o = self.o
         self.x.copy_(motion_at_T[self.clips])
         if self.d_prev is not None:
             self.d_prev.zero_()
-        for name in ("prev_m", "mem"):
-            getattr(self, name).copy_(ops_in[name][self.rows])
-        if self.stat_per_clip:
-            self.stat.copy_(ops_in["stat"][self.clips])
-        self.tok.copy_(ops_in["tok_person"][self.rows])
-        if self.ind is not None:
-            self.ind.copy_(ops_in["ind_in"][self.rows])
-        for dst, src in zip(self.kv, ops_in["kv_list"]):
+        o.prev_m.copy_(whole.prev_m[self.rows])
+        o.mem.copy_(whole.mem[self.rows])
+        if self.own_stat:
+            o.stat.copy_(whole.stat[self.clips])
+        o.tok_person.copy_(whole.tok_person[self.rows])
+        if o.ind is not None:
+            o.ind.copy_(whole.ind[self.rows])
+        for dst, src in zip(o.kv_list, whole.kv_list):
             dst.copy_(src[self.rows])
-        if self.cross is not None:
-            for dst, src in zip(self.cross, ops_in["cross_list"]):
+        if o.cross_list is not None:
+            for dst, src in zip(o.cross_list, whole.cross_list):
                 dst.copy_(src[self.rows])
 
 
 class _StepGraph:
-    """k captured denoise steps per lane (one hipGraph): device-side step counters, static operand buffers.
-    T is the number of steps the loop takes: the schedule's for DDPM, S for a few-step solver (few=True: (S+1, 6)
-    coefficient rows, emb_all holds the S+1 embeddings at the solver's timesteps; draw=False: no noise is drawn)."""
+    """k captured denoise steps per lane (one hipGraph): device-side step counters, static operand buffers.  The loop takes
+    rule.steps steps (the schedule's T for DDPM, S for a few-step solver); no noise is drawn when no step of the rule is noisy."""
 
-    def __init__(self, model, net, dtype, dev, T, N, n_entries, Lp, L, dm, nb, mode, target, P, like, dyn=None, lanes=1,
-                 few=False, draw=True):
-        B = N // n_entries
+    def __init__(self, o, rule, lanes):
+        B, dev, T, draw = o.B, o.dev, rule.steps, any(rule.noisy)
         self.lanes = lanes
-        self.shared = dict(lanes=lanes, emb_all=torch.zeros_like(like["emb_all"]), stat=torch.zeros_like(like["stat"]),
-                           scales=torch.zeros_like(like["scales"]) if like["scales"] is not None else None,
-                           coef_table=torch.zeros(T + 1, 6 if few else 3, device=dev, dtype=torch.float32))
+        self.shared = SimpleNamespace(emb_all=torch.zeros_like(o.emb_all), stat=torch.zeros_like(o.stat),
+                                      scales=torch.zeros_like(o.scales) if o.scales is not None else None,
+                                      coef_table=torch.zeros_like(rule.table, device=dev))
         Bl = B // lanes
         self.lane = []
         for l in range(lanes):
             clips = torch.arange(l * Bl, (l + 1) * Bl, device=dev)
-            rows = torch.cat([clips + e * B for e in range(n_entries)])
-            self.lane.append(_Lane(net, dtype, dev, T, Bl, n_entries, Lp, L, dm, nb, mode, target, P, like, self.shared,
-                                   rows, clips, dyn, few))
-        self.T = T
+            rows = torch.cat([clips + e * B for e in range(o.n_entries)])
+            self.lane.append(_Lane(o, rule, self.shared, rows, clips))
         self.streams = [torch.cuda.Stream() for _ in range(lanes)] if lanes > 1 else [None]
 
         def bodies(k):
             # one (B, L, dm) draw per step from the graph-safe philox stream, on the forking stream, sliced per lane: the same
             # generator calls whatever the lane count (each lane drawing its own made seeded output depend on MSMD_SAMPLER_LANES)
-            zs = [_step_noise(B, L, dm, dev) if draw else None for _ in range(k)]
+            zs = [_step_noise(B, o.L, o.dm, dev) if draw else None for _ in range(k)]
             if lanes == 1:
                 for s_ in range(k):
                     self.lane[0].body(zs[s_])
@@ -468,49 +492,32 @@ class _StepGraph:
         finally:
             ops.GEMM_LN_TILE = tile_keep
 
-    def run(self, T, motion_at_T, ops_in, coefficients, table=None):
+    def run(self, o, rule, motion_at_T):
         for ln in self.lane:
-            ln.load(motion_at_T, ops_in)
-        self.shared["emb_all"].copy_(ops_in["emb_all"])
-        self.shared["stat"].copy_(ops_in["stat"])
-        if self.shared["scales"] is not None:
-            self.shared["scales"].copy_(ops_in["scales"])
-        if table is not None:
-            tab = table.float()          # a few-step solver's rows, rounded to fp32 as the eager loop's scalars are
-        else:
-            tab = torch.zeros(T + 1, 3)
-            for t in range(1, T + 1):
-                c0, c1, sg = coefficients(t)
-                tab[t, 0], tab[t, 1], tab[t, 2] = c0, c1, (sg if t > 1 else 0.0)
-        self.shared["coef_table"].copy_(tab)
+            ln.load(motion_at_T, o)
+        self.shared.emb_all.copy_(o.emb_all)
+        self.shared.stat.copy_(o.stat)
+        if self.shared.scales is not None:
+            self.shared.scales.copy_(o.scales)
+        self.shared.coef_table.copy_(rule.table)
         for ln in self.lane:
-            ln.t_dev.fill_(T)
-        for _ in range(T // self.k):
+            ln.t_dev.fill_(rule.steps)
+        for _ in range(rule.steps // self.k):
             self.graph.replay()
         return torch.cat([ln.x for ln in self.lane], dim=0) if self.lanes > 1 else self.lane[0].x.clone()
 
 
-def _graph_loop(model, net, dtype, dev, T, N, n_entries, Lp, L, dm, nb, mode, target, P, motion_at_T, prev_m, ind_in,
-                mem, kv_list, stat, tok_person, emb_all, scales, coefficients, dyn=None, cross_list=None, solver=None):
-    """solver: None (DDPM over all T steps) or (name, S, rows) of a few-step solver (solver_table)."""
-    B = N // n_entries
-    table = None
-    few = solver is not None
-    draw = True
-    if few:
-        name, T, table = solver          # the loop runs S steps
-        draw = bool((table[1:, 5] != 0).any())
-    like = dict(prev_m=prev_m, ind_in=ind_in, mem=mem, kv_list=kv_list, cross_list=cross_list, stat=stat, tok_person=tok_person,
-                emb_all=emb_all, scales=scales, stat_per_clip=(stat.shape[0] == B and B > 1))
+def _graph_loop(model, o, rule, motion_at_T):
+    """The hipGraph loop: one resident _StepGraph per model, rebuilt when anything the capture depends on changes."""
     lanes = getattr(model, "sampler_lanes", LANES)
-    while lanes > 1 and (B % lanes or N // lanes < MIN_LANE_SEQS):
+    while lanes > 1 and (o.B % lanes or o.N // lanes < MIN_LANE_SEQS):
         lanes -= 1
-    key = (T, N, n_entries, Lp, L, mode, target, dtype, ind_in is not None, getattr(net, "_pack_gen", 0), dyn, cross_list is not None,
-           STEPS_PER_GRAPH, lanes, solver[0] if few else "ddpm", draw)
+    key = (rule.steps, o.N, o.n_entries, o.Lp, o.L, o.mode, rule.target, o.dtype, o.ind is not None,
+           getattr(o.net, "_pack_gen", 0), o.dyn, o.cross_list is not None, STEPS_PER_GRAPH, lanes, rule.name, any(rule.noisy),
+           o.stat.shape[0])
     cache = model.__dict__.setdefault("_step_graphs", {})
     g = cache.get(key)
     if g is None:
         cache.clear()  # one resident graph (its private memory pool holds all step intermediates)
-        g = cache[key] = _StepGraph(model, net, dtype, dev, T, N, n_entries, Lp, L, dm, nb, mode, target, P, like, dyn, lanes,
-                                    few, draw)
-    return g.run(T, motion_at_T.float(), like, coefficients, table)
+        g = cache[key] = _StepGraph(o, rule, lanes)
+    return g.run(o, rule, motion_at_T)
