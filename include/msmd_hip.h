@@ -327,6 +327,15 @@ int msmd_interp_linear(const void* x, void* y, int B, int T_in, int T_crop, int 
 int msmd_group_pad(const void* x, void* y, int B, int T, int G, int Cg, int Cg_out, int pad, int dtype, int out_dtype,
                    msmd_stream_t stream);
 
+/* The encoders' grouped positional conv in the 16-bit modes, in ONE launch and without the regrouped copy:
+ *   y (B, T, G*Cg) = x + GELU(conv1d_groups=G(x, k = kpos, pad = kpos / 2)[:, :T] + bias)
+ * x channels-last, read in place (y must not alias it); w (G, Cg, kpos*Cg) with K index = tap*Cg + channel (the packed
+ * weight of the windowed-GEMM form); bias (G*Cg) fp32.  dtype MSMD_BF16 / MSMD_F16, Cg 48 or 64, kpos 128; anything else
+ * returns 1 and belongs on msmd_group_pad + msmd_gemm.  Each workgroup keeps its <= 256 frames and their halo in LDS and
+ * streams only w.  Bit-identical to msmd_group_pad + msmd_gemm(act = GELU, residual = x) on the same tensors. */
+int msmd_pos_conv(const void* x, const void* w, const float* bias, void* y, int B, int T, int G, int Cg, int kpos,
+                  int dtype, msmd_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Denoiser glue (reference model.py:931-951, 961-996, 231-236, 404-432).
  */

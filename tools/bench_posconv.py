@@ -53,3 +53,31 @@ for v in variants:
         best = min(best, e0.elapsed_time(e1) / 20)
     print(f"variant {v:3d}: {best * 1e3:7.1f} us  {2.0 * B * T * d * kpos * cg / best / 1e9:6.1f} TFLOP/s  "
           f"{'== first' if torch.equal(y, base) else 'max diff %.3g' % float((y.float() - base.float()).abs().max())}", flush=True)
+
+# the one-launch kernel (16-bit modes), against group_pad + the routed GEMM, alternating
+if DT != "f16x2":
+    y2 = torch.empty_like(h)
+
+    def two():
+        xq = ops.group_pad(h, G, kpos // 2, cg_out=cgp)
+        ops.gemm(xq, w, bias, h, ops.ACT_GELU, out=y2, M=B * T, N=cg, K=kpos * cgp, lda=cgp, rows_per_batch=T,
+                 a_batch_stride=G * Tp * cgp, ldw=kpos * cgp, ldc=d, batch=G, strideA=Tp * cgp, strideW=cg * kpos * cgp,
+                 strideC=cg, strideBias=cg, strideR=cg)
+
+    one = lambda: ops.pos_conv(h, w, bias, G, kpos)
+    two()
+    y1 = one()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t = {"group_pad + gemm": [], "pos_conv": []}
+    for _ in range(5):
+        for name, fn in (("group_pad + gemm", two), ("pos_conv", one)):
+            e0.record()
+            for _ in range(20):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            t[name].append(e0.elapsed_time(e1) / 20 * 1e3)
+    for name, v in t.items():
+        print(f"{name:17s}: median {sorted(v)[len(v) // 2]:7.1f} us  min {min(v):7.1f} us  (5 rounds of 20, alternating)")
+    print("pos_conv == group_pad + gemm:", torch.equal(y1, y2), flush=True)

@@ -676,6 +676,22 @@ def group_pad(x, groups, pad, cg_out=None, split=False):
     return y
 
 
+def pos_conv(x, w, bias, groups, kpos=128):
+    """x + GELU(grouped positional conv(x) + bias) on channels-last 16-bit x (B, T, G*Cg) in one launch; w (G, Cg, kpos*Cg)
+    packed as for the windowed-GEMM form (K = tap*Cg + channel).  Bit-identical to group_pad + gemm(ACT_GELU, residual=x)."""
+    lib = _lib.load()
+    _need_cuda(x)
+    B, T, C = x.shape
+    cg = C // groups
+    if not (x.is_contiguous() and w.is_contiguous() and w.dtype == x.dtype and tuple(w.shape) == (groups, cg, kpos * cg)):
+        raise TypeError("pos_conv takes contiguous x (B, T, G*Cg) and w (G, Cg, kpos*Cg) of one 16-bit dtype")
+    if bias.dtype != torch.float32 or bias.numel() != C:
+        raise TypeError("pos_conv takes an fp32 bias of G*Cg values")
+    y = torch.empty_like(x)
+    _lib.check(lib.msmd_pos_conv(_p(x), _p(w), _p(bias), _p(y), B, T, groups, cg, kpos, _dt(x), _stream()), "msmd_pos_conv")
+    return y
+
+
 def denoiser_pack_input(motion, prev_motion, indicator, feats, eps=None, c0=None, c1=None):
     lib = _lib.load()
     N, Tn, Kpad = feats.shape

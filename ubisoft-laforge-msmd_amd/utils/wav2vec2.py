@@ -394,12 +394,16 @@ class Wav2Vec2Model(nn.Module):
         # positional grouped conv (k=128, pad=64, drop last frame) as G windowed GEMMs + GELU + residual
         G, cg, kpos = c.num_conv_pos_embedding_groups, d // c.num_conv_pos_embedding_groups, c.num_conv_pos_embeddings
         cgp = P.pos_cg
-        xp = ops.group_pad(h, G, kpos // 2, cg_out=cgp, split=P.split)  # (B, G, T + kpos, cgp)
-        Tp = T + kpos
-        y = torch.empty_like(h)
-        ops.gemm(xp, P.pos_w, P.pos_b, h, ops.ACT_GELU, out=y, M=B * T, N=cg, K=kpos * cgp, lda=cgp, rows_per_batch=T,
-                 a_batch_stride=G * Tp * cgp, ldw=kpos * cgp, ldc=d, batch=G, strideA=Tp * cgp, strideW=cg * kpos * cgp,
-                 strideC=cg, strideBias=cg, strideR=cg)
+        if not P.split and h.dtype in (torch.bfloat16, torch.float16) and cg in (48, 64) and kpos == 128:
+            # 16-bit modes: one kernel that keeps each block of frames and its halo in LDS (no regrouped copy), same bits
+            y = ops.pos_conv(h, P.pos_w, P.pos_b, G, kpos)
+        else:
+            xp = ops.group_pad(h, G, kpos // 2, cg_out=cgp, split=P.split)  # (B, G, T + kpos, cgp)
+            Tp = T + kpos
+            y = torch.empty_like(h)
+            ops.gemm(xp, P.pos_w, P.pos_b, h, ops.ACT_GELU, out=y, M=B * T, N=cg, K=kpos * cgp, lda=cgp, rows_per_batch=T,
+                     a_batch_stride=G * Tp * cgp, ldw=kpos * cgp, ldc=d, batch=G, strideA=Tp * cgp,
+                     strideW=cg * kpos * cgp, strideC=cg, strideBias=cg, strideR=cg)
         scale, eps = (d // H) ** -0.5, c.layer_norm_eps
         if P.fold and ops.FOLD_LN and c.do_stable_layer_norm:
             # pre-LN blocks without LayerNorm launches: every residual GEMM also writes the row statistics of what it
