@@ -346,6 +346,16 @@ int msmd_denoiser_pack_input(const float* motion, const float* eps, const float*
                              const float* prev_motion, const float* indicator, void* feats, int N, int L,
                              int Lp, int dm, int Kpad, int motion_batch, int out_dtype, msmd_stream_t stream);
 
+/* msmd_denoiser_pack_input with keyframe in-painting of the denoiser input (model.py:762-767): where guide_mask[nm, t] != 0
+ * (nm = n % motion_batch) the motion columns of frame t are guide_values[nm, t, :] instead of motion[nm, t, :]; everything
+ * else is msmd_denoiser_pack_input's arithmetic.  guide_mask (motion_batch, L) uint8, guide_values (motion_batch, L, dm)
+ * fp32: dense, so a captured launch does not depend on which frames are pinned.  guide_mask == NULL is the plain call;
+ * eps != NULL together with a mask returns 1 (the q-sample form is the training path). */
+int msmd_denoiser_pack_input_guided(const float* motion, const float* eps, const float* c0, const float* c1,
+                                    const float* prev_motion, const float* indicator, const unsigned char* guide_mask,
+                                    const float* guide_values, void* feats, int N, int L, int Lp, int dm, int Kpad,
+                                    int motion_batch, int out_dtype, msmd_stream_t stream);
+
 /* x (N, T, d) += pe (T, d) (learned PE, model.py:949); row 0 is REPLACED by tok0[n] + row0_add + pe[0]
  * (tok0 (N, d) = person projection (+ step embedding); row0_add (d) optional shared step embedding). */
 int msmd_add_pe_token(void* x, const float* pe, const void* tok0, const void* row0_add, int N, int T, int d,
@@ -390,6 +400,28 @@ int msmd_cfg_solver_step_dev(float* x, const float* res, const float* z, const f
                              msmd_stream_t stream);
 int msmd_sampler_solver_select(const void* emb_tab, const float* coef_tab, int* i_dev, void* emb_row,
                                float* coefs, int d, int dtype, msmd_stream_t stream);
+
+/* msmd_cfg_solver_step plus the three streams of sample_separate (model.py:442-651) in one launch.  x, d_prev, res, z,
+ * scales, mode and the six scalars are msmd_cfg_solver_step's and x / d_prev come out with its bits.  dec (n_entries*B,
+ * Lp+L, dm+nb; row stride ld_dec), stat (stat_batch, nb, dm), stat_batch and use_head_alpha are msmd_heads_static_mix's
+ * (res is its output on the same dec, after msmd_dynamic_threshold when that is on); dtype is that of dec and stat.  Per
+ * element of the last L frames: dyn_e = dec[e][k], static_e = msmd_heads_static_mix's sum for entry e, alpha_e = the blend
+ * weight a_{e,k} (k < nb); each is CFG-combined like res.  Then
+ *   cum_static (B, L, dm) += ath * theta_static;   theta_dyn (B, L, dm) = the combined dynamic part (overwritten);
+ *   theta_alpha (n_slots*B, L, nb): rows [slot*B, (slot+1)*B) = the combined blend weights.
+ * slot in [0, n_slots).  msmd_cfg_streams_step_dev reads the six scalars from `coefs` and takes slot = 0 when n_slots == 1,
+ * else n_slots - (*step_dev + 1): the ordinal S - i of step i with n_slots = S and step_dev the counter that
+ * msmd_sampler_solver_select has just decremented to i - 1. */
+int msmd_cfg_streams_step(float* x, const float* res, const void* dec, long ld_dec, const void* stat, const float* z,
+                          const float* scales, float* d_prev, float* cum_static, float* theta_dyn, float* theta_alpha,
+                          int slot, int n_slots, int n_entries, int B, int L, int Lp, int dm, int nb, int stat_batch,
+                          int use_head_alpha, int mode, int dtype, float p0, float p1, float ax, float ath, float b1,
+                          float sigma, msmd_stream_t stream);
+int msmd_cfg_streams_step_dev(float* x, const float* res, const void* dec, long ld_dec, const void* stat, const float* z,
+                              const float* scales, float* d_prev, float* cum_static, float* theta_dyn,
+                              float* theta_alpha, const float* coefs, const int* step_dev, int n_slots, int n_entries,
+                              int B, int L, int Lp, int dm, int nb, int stat_batch, int use_head_alpha, int mode,
+                              int dtype, msmd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * FLAME: blendshapes + pose correctives + joint regression + Rodrigues + kinematic chain + skinning

@@ -47,6 +47,61 @@ extern "C" int msmd_denoiser_pack_input(const float* motion, const float* eps, c
   MSMD_RETURN_LAST();
 }
 
+// msmd_denoiser_pack_input with keyframe in-painting of the denoiser INPUT (reference model.py:762-767: motion_in[:, idx, :] =
+// values before every denoiser call): where guide_mask[nm, t] != 0 the motion columns of frame t come from guide_values
+// instead of motion.  The mask / value pair is dense, (motion_batch, L) uint8 / (motion_batch, L, dm) fp32, so a captured
+// launch does not depend on which frames are pinned or how many; the overwrite is per clip and every CFG entry of a clip
+// reads the same overwritten input.  Prev rows, the indicator column, the zero padding, the person-token row and the
+// conversion are pack_input_kernel's.
+template <typename TO>
+__global__ void pack_input_guided_kernel(const float* __restrict__ motion, const float* __restrict__ prev,
+                                         const float* __restrict__ ind, const unsigned char* __restrict__ guide_mask,
+                                         const float* __restrict__ guide_values, TO* __restrict__ feats, int L, int Lp,
+                                         int dm, int Kpad, int motion_batch) {
+  const int n = blockIdx.y;
+  const int Tn = 1 + Lp + L;
+  const int nm = n % motion_batch;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < Tn * Kpad; i += gridDim.x * blockDim.x) {
+    const int r = i / Kpad - 1, k = i % Kpad;
+    float v = 0.f;
+    if (r >= 0 && r < Lp) {
+      if (k < dm) v = prev[((long)n * Lp + r) * dm + k];
+    } else if (r >= Lp) {
+      const int t = r - Lp;
+      if (k < dm) {
+        const long at = ((long)nm * L + t) * dm + k;
+        v = guide_mask[(long)nm * L + t] ? guide_values[at] : motion[at];
+      } else if (k == dm && ind) {
+        v = ind[(long)n * L + t];
+      }
+    }
+    feats[(long)n * Tn * Kpad + i] = from_f32<TO>(v);
+  }
+}
+
+extern "C" int msmd_denoiser_pack_input_guided(const float* motion, const float* eps, const float* c0, const float* c1,
+                                               const float* prev_motion, const float* indicator,
+                                               const unsigned char* guide_mask, const float* guide_values, void* feats,
+                                               int N, int L, int Lp, int dm, int Kpad, int motion_batch, int out_dtype,
+                                               msmd_stream_t stream) {
+  if (!guide_mask)
+    return msmd_denoiser_pack_input(motion, eps, c0, c1, prev_motion, indicator, feats, N, L, Lp, dm, Kpad, motion_batch,
+                                    out_dtype, stream);
+  if (eps || !guide_values) return 1;  // the q-sample form is the training path: no keyframes there
+  if (N <= 0 || L <= 0 || Lp < 0 || dm <= 0 || Kpad < dm + (indicator ? 1 : 0) || motion_batch <= 0) return 1;
+  dim3 grid(((1 + Lp + L) * Kpad + 255) / 256, N), block(256);
+  if (out_dtype == MSMD_F32)
+    hipLaunchKernelGGL(pack_input_guided_kernel<float>, grid, block, 0, (hipStream_t)stream, motion, prev_motion,
+                       indicator, guide_mask, guide_values, (float*)feats, L, Lp, dm, Kpad, motion_batch);
+  else if (out_dtype == MSMD_F16)
+    hipLaunchKernelGGL(pack_input_guided_kernel<f16_t>, grid, block, 0, (hipStream_t)stream, motion, prev_motion,
+                       indicator, guide_mask, guide_values, (f16_t*)feats, L, Lp, dm, Kpad, motion_batch);
+  else
+    hipLaunchKernelGGL(pack_input_guided_kernel<bf16_t>, grid, block, 0, (hipStream_t)stream, motion, prev_motion,
+                       indicator, guide_mask, guide_values, (bf16_t*)feats, L, Lp, dm, Kpad, motion_batch);
+  MSMD_RETURN_LAST();
+}
+
 // x (N, T, d) += pe (T, d); row 0 = tok0 (N, d) + row0_add (d, optional) + pe[0]  (row 0 of x is overwritten)
 template <typename T>
 __global__ void add_pe_token_kernel(T* __restrict__ x, const float* __restrict__ pe, const T* __restrict__ tok0,
@@ -334,6 +389,150 @@ extern "C" int msmd_cfg_solver_step_dev(float* x, const float* res, const float*
                                         int mode, msmd_stream_t stream) {
   return launch_cfg_solver(true, x, res, z, scales, d_prev, coefs, SolverCoefs{}, n_entries, B, L, Lp, dm, mode,
                            stream);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// sample_separate on a few-step solver: the CFG combine and solver update of cfg_solver_kernel (the same two lines, so x and
+// d_prev have its bits under the same res) plus, in the same launch, the three diagnostic streams of reference
+// model.py:442-651.  Per element of the last L frames and per CFG entry e (row n = e B + b of dec / res):
+//   dyn_e = dec[n][k],  static_e = sum_b a_{e,b} stat_b[k]  (the loop of heads_mix_kernel: same order, plain sum of the bases
+//   for the last 3 columns without use_head_alpha & 1, sigmoid under use_head_alpha & 2),  alpha_e = a_{e,k} for k < nb;
+// each stream is CFG-combined across entries by the in-place rule of cfg_ddpm_kernel.  res is the output of
+// msmd_heads_static_mix (after msmd_dynamic_threshold when that is on), so theta is what the plain solver step sees.
+//   cum_static += ath theta_static   (the step's coefficient on theta stands where the DDPM chain has c1, model.py:590-618)
+//   theta_dyn (B, L, dm) is overwritten;  theta_alpha goes to rows [slot B, (slot + 1) B) of an (n_slots B, L, nb) buffer,
+//   slot = 0 for n_slots = 1, else the step ordinal S - i (kDev: i = *step_dev + 1, the counter msmd_sampler_solver_select
+//   has just decremented).
+// Elementwise and HBM-bound like its neighbours: one grid-stride loop, fp32 throughout, running values instead of
+// per-entry arrays (no scratch).
+template <typename T, bool kDev>
+__global__ void cfg_streams_kernel(float* __restrict__ x, const float* __restrict__ res, const T* __restrict__ dec,
+                                   long ld_dec, const T* __restrict__ stat, const float* __restrict__ z,
+                                   const float* __restrict__ scales, float* __restrict__ d_prev,
+                                   float* __restrict__ cum_static, float* __restrict__ theta_dyn,
+                                   float* __restrict__ theta_alpha, const float* __restrict__ coefs,
+                                   const int* __restrict__ step_dev, SolverCoefs c, int slot, int n_slots,
+                                   int n_entries, int B, int L, int Lp, int dm, int nb, int stat_batch,
+                                   int use_head_alpha, int mode) {
+  if (kDev) {
+    c = SolverCoefs{coefs[0], coefs[1], coefs[2], coefs[3], coefs[4], coefs[5]};
+    slot = n_slots > 1 ? n_slots - (*step_dev + 1) : 0;
+  }
+  if (slot < 0 || slot >= n_slots) slot = n_slots - 1;   // a counter outside the loop's range must not write out of bounds
+  const long total = (long)B * L * dm;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int b = (int)(i / ((long)L * dm));
+    const int rem = (int)(i % ((long)L * dm));
+    const int t = rem / dm, k = rem % dm;
+    const long stride_e = (long)B * (Lp + L) * dm;
+    const long off = ((long)b * (Lp + L) + Lp + t) * dm + k;
+    const bool weighted = (use_head_alpha & 1) || (k < dm - 3);
+    float theta = 0.f, th_static = 0.f, th_dyn = 0.f, th_alpha = 0.f;
+    float lo_static = 0.f, lo_dyn = 0.f, lo_alpha = 0.f;   // entry e's own values while entry e + 1 is combined
+    for (int e = 0; e < n_entries; ++e) {
+      const int n = e * B + b;
+      const int ns = n % stat_batch;
+      const T* row = dec + ((long)n * (Lp + L) + Lp + t) * ld_dec;
+      float st = 0.f, al = 0.f;
+      for (int bb = 0; bb < nb; ++bb) {
+        const float s = to_f32(stat[((long)ns * nb + bb) * dm + k]);
+        float a = to_f32(row[dm + bb]);
+        if (use_head_alpha & 2) a = 1.0f / (1.0f + expf(-a));
+        st += weighted ? s * a : s;
+        if (bb == k) al = a;
+      }
+      const float dy = to_f32(row[k]);
+      if (e == 0) {
+        theta = res[off];
+        th_static = st; th_dyn = dy; th_alpha = al;
+      } else {
+        const float sc = scales[e - 1];
+        const bool running = (mode == 1 || e == 1);        // lo = the running theta (entry 0's slice, updated in place)
+        const float hi = res[e * stride_e + off];
+        const float lo = running ? theta : res[(e - 1) * stride_e + off];
+        theta += sc * (hi - lo);
+        th_static += sc * (st - (running ? th_static : lo_static));
+        th_dyn += sc * (dy - (running ? th_dyn : lo_dyn));
+        th_alpha += sc * (al - (running ? th_alpha : lo_alpha));
+      }
+      lo_static = st; lo_dyn = dy; lo_alpha = al;
+    }
+    const float xt = x[i];
+    const float dp = d_prev[i];
+    const float zz = z ? z[i] : 0.f;
+    const float D = c.p0 * xt + c.p1 * theta;
+    x[i] = c.ax * xt + c.ath * theta + c.b1 * dp + c.sigma * zz;
+    d_prev[i] = D;
+    cum_static[i] += c.ath * th_static;
+    theta_dyn[i] = th_dyn;
+    if (k < nb) theta_alpha[(((long)slot * B + b) * L + t) * nb + k] = th_alpha;
+  }
+}
+
+template <typename T>
+static int launch_cfg_streams_t(bool dev, float* x, const float* res, const void* dec, long ld_dec, const void* stat,
+                                const float* z, const float* scales, float* d_prev, float* cum_static, float* theta_dyn,
+                                float* theta_alpha, const float* coefs, const int* step_dev, SolverCoefs c, int slot,
+                                int n_slots, int n_entries, int B, int L, int Lp, int dm, int nb, int stat_batch,
+                                int use_head_alpha, int mode, msmd_stream_t stream) {
+  const long total = (long)B * L * dm;
+  dim3 grid((unsigned)min((total + 255) / 256, (long)2048)), block(256);
+  if (dev)
+    hipLaunchKernelGGL((cfg_streams_kernel<T, true>), grid, block, 0, (hipStream_t)stream, x, res, (const T*)dec, ld_dec,
+                       (const T*)stat, z, scales, d_prev, cum_static, theta_dyn, theta_alpha, coefs, step_dev, c, slot,
+                       n_slots, n_entries, B, L, Lp, dm, nb, stat_batch, use_head_alpha, mode);
+  else
+    hipLaunchKernelGGL((cfg_streams_kernel<T, false>), grid, block, 0, (hipStream_t)stream, x, res, (const T*)dec, ld_dec,
+                       (const T*)stat, z, scales, d_prev, cum_static, theta_dyn, theta_alpha, coefs, step_dev, c, slot,
+                       n_slots, n_entries, B, L, Lp, dm, nb, stat_batch, use_head_alpha, mode);
+  MSMD_RETURN_LAST();
+}
+
+static int launch_cfg_streams(bool dev, float* x, const float* res, const void* dec, long ld_dec, const void* stat,
+                              const float* z, const float* scales, float* d_prev, float* cum_static, float* theta_dyn,
+                              float* theta_alpha, const float* coefs, const int* step_dev, SolverCoefs c, int slot,
+                              int n_slots, int n_entries, int B, int L, int Lp, int dm, int nb, int stat_batch,
+                              int use_head_alpha, int mode, int dtype, msmd_stream_t stream) {
+  if (B <= 0 || L <= 0 || dm <= 3 || Lp < 0 || nb <= 0 || nb > dm || n_entries < 1 || (n_entries > 1 && !scales) || !x ||
+      !res || !dec || !stat || !d_prev || !cum_static || !theta_dyn || !theta_alpha || ld_dec < dm + nb ||
+      (stat_batch != B && stat_batch != 1 && stat_batch != n_entries * B) || n_slots < 1 ||
+      (dev ? (!coefs || !step_dev) : (slot < 0 || slot >= n_slots)))
+    return 1;
+  if (dtype == MSMD_F32)
+    return launch_cfg_streams_t<float>(dev, x, res, dec, ld_dec, stat, z, scales, d_prev, cum_static, theta_dyn,
+                                       theta_alpha, coefs, step_dev, c, slot, n_slots, n_entries, B, L, Lp, dm, nb,
+                                       stat_batch, use_head_alpha, mode, stream);
+  if (dtype == MSMD_F16)
+    return launch_cfg_streams_t<f16_t>(dev, x, res, dec, ld_dec, stat, z, scales, d_prev, cum_static, theta_dyn,
+                                       theta_alpha, coefs, step_dev, c, slot, n_slots, n_entries, B, L, Lp, dm, nb,
+                                       stat_batch, use_head_alpha, mode, stream);
+  if (dtype == MSMD_BF16)
+    return launch_cfg_streams_t<bf16_t>(dev, x, res, dec, ld_dec, stat, z, scales, d_prev, cum_static, theta_dyn,
+                                        theta_alpha, coefs, step_dev, c, slot, n_slots, n_entries, B, L, Lp, dm, nb,
+                                        stat_batch, use_head_alpha, mode, stream);
+  return 1;
+}
+
+extern "C" int msmd_cfg_streams_step(float* x, const float* res, const void* dec, long ld_dec, const void* stat,
+                                     const float* z, const float* scales, float* d_prev, float* cum_static,
+                                     float* theta_dyn, float* theta_alpha, int slot, int n_slots, int n_entries, int B,
+                                     int L, int Lp, int dm, int nb, int stat_batch, int use_head_alpha, int mode,
+                                     int dtype, float p0, float p1, float ax, float ath, float b1, float sigma,
+                                     msmd_stream_t stream) {
+  return launch_cfg_streams(false, x, res, dec, ld_dec, stat, z, scales, d_prev, cum_static, theta_dyn, theta_alpha,
+                            nullptr, nullptr, SolverCoefs{p0, p1, ax, ath, b1, sigma}, slot, n_slots, n_entries, B, L, Lp,
+                            dm, nb, stat_batch, use_head_alpha, mode, dtype, stream);
+}
+
+extern "C" int msmd_cfg_streams_step_dev(float* x, const float* res, const void* dec, long ld_dec, const void* stat,
+                                         const float* z, const float* scales, float* d_prev, float* cum_static,
+                                         float* theta_dyn, float* theta_alpha, const float* coefs, const int* step_dev,
+                                         int n_slots, int n_entries, int B, int L, int Lp, int dm, int nb,
+                                         int stat_batch, int use_head_alpha, int mode, int dtype,
+                                         msmd_stream_t stream) {
+  return launch_cfg_streams(true, x, res, dec, ld_dec, stat, z, scales, d_prev, cum_static, theta_dyn, theta_alpha, coefs,
+                            step_dev, SolverCoefs{}, 0, n_slots, n_entries, B, L, Lp, dm, nb, stat_batch, use_head_alpha,
+                            mode, dtype, stream);
 }
 
 extern "C" int msmd_sampler_solver_select(const void* emb_tab, const float* coef_tab, int* i_dev, void* emb_row,

@@ -26,6 +26,7 @@ import torch
 import torch.nn.functional as F
 
 from .model import get_diffusion_model
+from .sampler import DenseGuide
 from .style_encoder import get_style_encoder
 from .utils.model_common import load_args
 
@@ -40,18 +41,43 @@ def window_plan(n_samples: int, fps, n_motions: int, audio_unit: float):
     return clip_len, n_audio_samples, n_subdivision, n_padding_audio_samples, n_padding_frames
 
 
+def window_keyframes(keyframes, clip_len: int, n_motions: int, n_windows: int):
+    """Keyframes of a whole clip -> per-window local guidance.  keyframes = (frame_indices, values): indices in [0, clip_len)
+    along the clip (an index >= clip_len or < 0 raises IndexError), values (K, C).  Returns a list of n_windows entries, each
+    (local index list, values (k, C)) for the keyframes that fall into that window, in their given order, or None."""
+    if keyframes is None:
+        return [None] * n_windows
+    frames, values = keyframes
+    frames = [int(f) for f in (frames.tolist() if hasattr(frames, "tolist") else frames)]
+    if len(frames) != len(values):
+        raise ValueError(f"keyframes: {len(frames)} frame indices for {len(values)} rows of values")
+    for f in frames:
+        if not 0 <= f < clip_len:
+            raise IndexError(f"keyframe index {f} is out of range for a clip of {clip_len} frames")
+    out = []
+    for w in range(n_windows):
+        mine = [j for j, f in enumerate(frames) if f // n_motions == w]
+        rows = values[mine] if hasattr(values, "shape") else [values[j] for j in mine]      # tensor / array, or a list of rows
+        out.append(([frames[j] - w * n_motions for j in mine], rows) if mine else None)
+    return out
+
+
 @torch.no_grad()
 def infer_coeffs(model, args, audio, shape_coef, audio_unit, style_feats=None, n_repetitions: int = 1, cfg_mode=None,
                  cfg_cond=None, cfg_scale: float = 1.15, include_shape: bool = False, dynamic_threshold=(0, 1, 4),
-                 noise=None, sample_steps=None, solver="ddpm", eta=0.0):
+                 noise=None, sample_steps=None, solver="ddpm", eta=0.0, *, keyframes=None):
     """Coefficients for one clip of any length (reference inference.py:34-75; same signature, window arithmetic and hand-off
     rules).  The clip is zero-padded to a whole number of n_motions-frame windows and encoded ONCE; each window is one
     `model.sample` call conditioned on the previous window's last n_prev_motions motion / audio-feature frames, every
     window after the first starts from window 0's x_T, and the frames that only cover the padding are cut from the result.
     ``noise`` (optional, replay): {'xT': tensor, 'z': [per-window dict of per-step draws]}.
-    ``sample_steps`` / ``solver`` / ``eta``: the sampler of every window (MSMD.sample); the default is the reference's."""
+    ``sample_steps`` / ``solver`` / ``eta``: the sampler of every window (MSMD.sample); the default is the reference's.
+    ``keyframes`` = (frame_indices, values (K, C)): poses pinned along the whole clip; every window receives its own as local
+    guidance (MSMD.sample_with_guide), a window without any takes the plain call.  On the graph loop the two kinds of window have
+    two captures, and one graph is resident per model: a clip pinned in windows 0 and 2 but not 1 captures three times."""
     L, keep = args.n_motions, args.n_prev_motions
-    _, _, n_windows, pad_samples, pad_frames = window_plan(len(audio), args.fps, L, audio_unit)
+    clip_len, _, n_windows, pad_samples, pad_frames = window_plan(len(audio), args.fps, L, audio_unit)
+    pinned = window_keyframes(keyframes, clip_len, L, n_windows)
     tail = max(pad_frames, 0)                       # frames of the last window that lie entirely in the zero padding
     wave = F.pad(audio, (0, pad_samples), value=0) if pad_samples > 0 else audio
     per_window = model.extract_audio_feature(wave.unsqueeze(0), L * n_windows).split(L, dim=1)
@@ -67,8 +93,11 @@ def infer_coeffs(model, args, audio, shape_coef, audio_unit, style_feats=None, n
             if cut:
                 indicator[:, L - cut:] = 0
         style = style_feats[w] if isinstance(style_feats, list) else style_feats
-        x0, x_T, feat_used = model.sample(feat.expand(n_repetitions, -1, -1), shape_coef, style, *history, indicator=indicator,
-                                          noise=None if noise is None else noise["z"][w], **guidance)
+        call, kf = model.sample, {}
+        if pinned[w] is not None:
+            call, kf = model.sample_with_guide, dict(guidance_indice=pinned[w][0], guidance_values=pinned[w][1])
+        x0, x_T, feat_used = call(feat.expand(n_repetitions, -1, -1), shape_coef, style, *history, indicator=indicator,
+                                  noise=None if noise is None else noise["z"][w], **guidance, **kf)
         history = (x0[:, -keep:].clone(), feat_used[:, -keep:], x_T)
         pieces.append(x0[:, :L - cut] if cut else x0)
     return torch.cat(pieces, dim=1)
@@ -147,15 +176,23 @@ def denormalize_coeffs(overall_coef, coef_stats):
 @torch.no_grad()
 def infer_coeffs_batch(model, args, audios, shape_coefs, audio_unit, style_feats, cfg_mode=None, cfg_cond=None,
                        cfg_scale: float = 1.15, dynamic_threshold=(0, 1, 4), noise=None, sample_steps=None, solver="ddpm",
-                       eta=0.0):
+                       eta=0.0, *, keyframes=None):
     """`infer_coeffs` for a list of clips (1-D audio tensors of any lengths), one repetition each, with window i of
     all clips batched into one `model.sample` call.  shape_coefs: (n_clips, 100); style_feats: (n_clips, d_style).
     `noise` (optional): list of per-clip {'xT', 'z'} dicts as `infer_coeffs` takes; `sample_steps` / `solver` / `eta`
-    as `infer_coeffs` takes them.  Returns a list of (1, clip_len, C)
+    as `infer_coeffs` takes them; `keyframes`: one (frame_indices, values) pair or None per clip, as `infer_coeffs` takes
+    it (a window in which no active clip has a keyframe takes the plain call); clips pin different frames, which needs a
+    few-step solver (solver="ddpm" raises ValueError: loop over `infer_coeffs` there).  Returns a list of (1, clip_len, C)
     tensors, clip c equal to infer_coeffs(model, args, audios[c], shape_coefs[c:c+1], audio_unit, style_feats[c:c+1])."""
     n = len(audios)
     L, Lp = args.n_motions, args.n_prev_motions
     plans = [window_plan(len(a), args.fps, L, audio_unit) for a in audios]
+    if keyframes is not None and solver == "ddpm":
+        raise ValueError("infer_coeffs_batch: per-clip keyframes need solver='ddim' or 'dpmpp_2m' (solver='ddpm': one "
+                         "infer_coeffs call per clip)")
+    if keyframes is not None and len(keyframes) != n:
+        raise ValueError(f"keyframes: one entry per clip expected ({n}), got {len(keyframes)}")
+    pinned = [window_keyframes(keyframes[c] if keyframes is not None else None, plans[c][0], L, plans[c][2]) for c in range(n)]
     # one encoder pass per distinct padded length
     feats = [None] * n
     by_sub = {}
@@ -184,16 +221,19 @@ def infer_coeffs_batch(model, args, audios, shape_coefs, audio_unit, style_feats
             kw["noise"] = {t: torch.cat([noise[c]["z"][i][t] for c in act], dim=0) for t in noise[act[0]]["z"][i]}
         idx = torch.as_tensor(act, device=model.device)
         shape_in, style_in = shape_coefs[idx], style_feats[idx]
+        call = model.sample
+        if any(pinned[c][i] is not None for c in act):
+            call = model.sample_with_guide
+            kw["guidance_indice"] = DenseGuide.stack([pinned[c][i] for c in act], L, model.motion_feat_dim)
         if i == 0:
             xT = torch.cat([noise[c]["xT"] for c in act], dim=0) if noise is not None else None
-            motion, nT, pa = model.sample(audio_in, shape_in, style_in, motion_at_T=xT, **kw)
+            motion, nT, pa = call(audio_in, shape_in, style_in, motion_at_T=xT, **kw)
         else:
             # windows i > 0 re-use their clip's x_T and take the previous window's last frames (inference.py:60-69);
             # model.sample substitutes the learned start tokens only when BOTH prev tensors are None, which cannot
             # happen here because every active clip ran window i - 1
-            motion, nT, pa = model.sample(audio_in, shape_in, style_in, torch.cat([prev_m[c] for c in act], dim=0),
-                                          torch.cat([prev_a[c] for c in act], dim=0),
-                                          torch.cat([x_T[c] for c in act], dim=0), **kw)
+            motion, nT, pa = call(audio_in, shape_in, style_in, torch.cat([prev_m[c] for c in act], dim=0),
+                                  torch.cat([prev_a[c] for c in act], dim=0), torch.cat([x_T[c] for c in act], dim=0), **kw)
         for j, c in enumerate(act):
             prev_m[c] = motion[j:j + 1, -Lp:].clone()
             prev_a[c] = pa[j:j + 1, -Lp:]

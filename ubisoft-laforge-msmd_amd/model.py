@@ -838,23 +838,30 @@ class MSMD(nn.Module):
     def sample_separate(self, audio_or_feat, shape_feat, style_feat=None, prev_motion_feat=None, prev_audio_feat=None,
                         motion_at_T=None, indicator=None, cfg_mode=None, cfg_cond=None, cfg_scale=1.15, flexibility=0,
                         dynamic_threshold=None, ret_traj=False, alpah_t_modification=None, return_all_alpha=False,
-                        noise=None):
+                        noise=None, sample_steps=None, solver="ddpm", eta=0.0):
         """reference model.py:442-651: same loop, additionally returns the CFG-combined dynamic part of the last
-        step, the accumulated static pose and the blend weights (argument spelling kept from the reference)."""
+        step, the accumulated static pose and the blend weights (argument spelling kept from the reference).
+        ``sample_steps`` / ``solver`` / ``eta`` as ``sample`` takes them: with "ddim" / "dpmpp_2m" the streams come from the
+        fused streams step (x0 has the bits of ``sample`` under the same solver) and the call replays the captured graph
+        unless ``alpah_t_modification`` is set."""
         from .sampler import sample as _sample
         return _sample(self, audio_or_feat, shape_feat, style_feat, prev_motion_feat, prev_audio_feat, motion_at_T,
                        indicator, cfg_mode, cfg_cond, cfg_scale, flexibility, dynamic_threshold, ret_traj, noise,
-                       separate=dict(alpha_mod=alpah_t_modification, return_all_alpha=return_all_alpha))
+                       separate=dict(alpha_mod=alpah_t_modification, return_all_alpha=return_all_alpha),
+                       sample_steps=sample_steps, solver=solver, eta=eta)
 
     @torch.no_grad()
     def sample_with_guide(self, audio_or_feat, shape_feat, style_feat=None, prev_motion_feat=None,
                           prev_audio_feat=None, motion_at_T=None, indicator=None, cfg_mode=None, cfg_cond=None,
                           cfg_scale=1.15, flexibility=0, dynamic_threshold=None, ret_traj=False, guidance_indice=None,
-                          guidance_values=None, noise=None):
+                          guidance_values=None, noise=None, sample_steps=None, solver="ddpm", eta=0.0):
         """reference model.py:653-818 (naive in-painting: guided frames overwrite the denoiser INPUT each step).
         The reference's call at model.py:770 omits `static_style_feat` and raises TypeError; here the static
-        branch receives the real style exactly as in `sample` (documented fix)."""
+        branch receives the real style exactly as in `sample` (documented fix).
+        ``sample_steps`` / ``solver`` / ``eta`` as ``sample`` takes them: with "ddim" / "dpmpp_2m" the keyframes are
+        overwritten inside the pack kernel and the call replays the captured graph; other keyframes do not recapture.
+        ``guidance_indice`` may be a ``sampler.DenseGuide`` (per-clip keyframes, ``guidance_values`` None)."""
         from .sampler import sample as _sample
         return _sample(self, audio_or_feat, shape_feat, style_feat, prev_motion_feat, prev_audio_feat, motion_at_T,
                        indicator, cfg_mode, cfg_cond, cfg_scale, flexibility, dynamic_threshold, ret_traj, noise,
-                       guidance=(guidance_indice, guidance_values))
+                       guidance=(guidance_indice, guidance_values), sample_steps=sample_steps, solver=solver, eta=eta)

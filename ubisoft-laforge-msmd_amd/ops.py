@@ -704,6 +704,26 @@ def denoiser_pack_input(motion, prev_motion, indicator, feats, eps=None, c0=None
     return feats
 
 
+def denoiser_pack_input_guided(motion, prev_motion, indicator, feats, guide_mask, guide_values, eps=None, c0=None, c1=None):
+    """denoiser_pack_input with keyframes: where guide_mask (B, L) uint8 is set, frame t of clip b enters the denoiser as
+    guide_values[b, t] (B, L, dm) fp32 instead of motion[b, t]."""
+    lib = _lib.load()
+    N, Tn, Kpad = feats.shape
+    B, L, dm = motion.shape
+    Lp = prev_motion.shape[1]
+    assert Tn == 1 + Lp + L
+    if guide_mask is not None:
+        _need_cuda(guide_mask, guide_values)
+        if not (guide_mask.dtype == torch.uint8 and tuple(guide_mask.shape) == (B, L) and guide_mask.is_contiguous()
+                and guide_values.dtype == torch.float32 and tuple(guide_values.shape) == (B, L, dm)
+                and guide_values.is_contiguous()):
+            raise TypeError("denoiser_pack_input_guided takes a contiguous uint8 mask (B, L) and fp32 values (B, L, dm)")
+    _lib.check(lib.msmd_denoiser_pack_input_guided(_p(motion), _p(eps), _p(c0), _p(c1), _p(prev_motion), _p(indicator),
+                                                   _p(guide_mask), _p(guide_values), _p(feats), N, L, Lp, dm, Kpad, B,
+                                                   _dt(feats), _stream()), "msmd_denoiser_pack_input_guided")
+    return feats
+
+
 def add_pe_token(x, pe, tok0, row0_add=None):
     lib = _lib.load()
     N, T, d = x.shape
@@ -767,6 +787,54 @@ def cfg_solver_step_dev(x, res, z, scales, d_prev, coefs, n_entries, Lp, mode):
     _lib.check(lib.msmd_cfg_solver_step_dev(_p(x), _p(res), _p(z), _p(scales), _p(d_prev), _p(coefs), n_entries, B, L, Lp,
                                             dm, mode, _stream()), "msmd_cfg_solver_step_dev")
     return x
+
+
+def _streams_args(x, res, dec, stat, d_prev, cum_static, theta_dyn, theta_alpha, n_entries, Lp, nb):
+    """Shape / dtype checks of the two streams-step forms (the kernel indexes every buffer from these sizes)."""
+    B, L, dm = x.shape
+    _need_cuda(x, res, dec, stat, d_prev, cum_static, theta_dyn, theta_alpha)
+    N = n_entries * B
+    for t in (x, d_prev, cum_static, theta_dyn):
+        if t.dtype != torch.float32 or tuple(t.shape) != (B, L, dm) or not t.is_contiguous():
+            raise TypeError("cfg_streams_step: x, d_prev, cum_static and theta_dyn are contiguous fp32 (B, L, dm)")
+    if res.dtype != torch.float32 or tuple(res.shape) != (N, Lp + L, dm) or not res.is_contiguous():
+        raise TypeError("cfg_streams_step: res is contiguous fp32 (n_entries * B, Lp + L, dm)")
+    if (dec.dtype != stat.dtype or dec.ndim != 3 or dec.shape[0] != N or dec.shape[1] != Lp + L or dec.shape[2] != dm + nb
+            or dec.stride(2) != 1 or dec.stride(0) != (Lp + L) * dec.stride(1) or dec.stride(1) < dm + nb):
+        raise TypeError("cfg_streams_step: dec is (n_entries * B, Lp + L, dm + nb) rows of one stride, in stat's dtype")
+    if stat.ndim != 3 or stat.shape[0] not in (1, B, N) or tuple(stat.shape[1:]) != (nb, dm) or not stat.is_contiguous():
+        raise TypeError("cfg_streams_step: stat is contiguous (1 | B | n_entries * B, nb, dm)")
+    if (theta_alpha.dtype != torch.float32 or theta_alpha.ndim != 3 or theta_alpha.shape[0] % B
+            or tuple(theta_alpha.shape[1:]) != (L, nb) or not theta_alpha.is_contiguous()):
+        raise TypeError("cfg_streams_step: theta_alpha is contiguous fp32 (n_slots * B, L, nb)")
+    return B, L, dm, theta_alpha.shape[0] // B
+
+
+def cfg_streams_step(x, res, dec, stat, z, scales, d_prev, cum_static, theta_dyn, theta_alpha, slot, n_entries, Lp, nb,
+                     use_head_alpha, mode, p0, p1, ax, ath, b1, sigma):
+    """cfg_solver_step plus sample_separate's streams in one launch: cum_static += ath theta_static, theta_dyn overwritten,
+    theta_alpha's row block `slot` written.  use_head_alpha: the bit pair msmd_heads_static_mix takes."""
+    lib = _lib.load()
+    B, L, dm, n_slots = _streams_args(x, res, dec, stat, d_prev, cum_static, theta_dyn, theta_alpha, n_entries, Lp, nb)
+    _lib.check(lib.msmd_cfg_streams_step(_p(x), _p(res), _p(dec), dec.stride(1), _p(stat), _p(z), _p(scales), _p(d_prev),
+                                         _p(cum_static), _p(theta_dyn), _p(theta_alpha), int(slot), n_slots, n_entries, B,
+                                         L, Lp, dm, nb, stat.shape[0], int(use_head_alpha), mode, _dt(dec), float(p0),
+                                         float(p1), float(ax), float(ath), float(b1), float(sigma), _stream()),
+               "msmd_cfg_streams_step")
+    return x
+
+
+def cfg_streams_step_dev(x, res, dec, stat, z, scales, d_prev, cum_static, theta_dyn, theta_alpha, coefs, step_dev,
+                         n_entries, Lp, nb, use_head_alpha, mode):
+    """cfg_streams_step with the six scalars in `coefs` and the slot taken from the device-side step counter."""
+    lib = _lib.load()
+    B, L, dm, n_slots = _streams_args(x, res, dec, stat, d_prev, cum_static, theta_dyn, theta_alpha, n_entries, Lp, nb)
+    _lib.check(lib.msmd_cfg_streams_step_dev(_p(x), _p(res), _p(dec), dec.stride(1), _p(stat), _p(z), _p(scales),
+                                             _p(d_prev), _p(cum_static), _p(theta_dyn), _p(theta_alpha), _p(coefs),
+                                             _p(step_dev), n_slots, n_entries, B, L, Lp, dm, nb, stat.shape[0],
+                                             int(use_head_alpha), mode, _dt(dec), _stream()), "msmd_cfg_streams_step_dev")
+    return x
+
 
 def pad_cols(x, cols_out, out_dtype=None):
     lib = _lib.load()

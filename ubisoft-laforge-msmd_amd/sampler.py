@@ -14,6 +14,7 @@ import os
 from collections import namedtuple
 from types import SimpleNamespace
 
+import numpy as np
 import torch
 
 from . import ops
@@ -126,11 +127,14 @@ def ddpm_table(sched, flexibility=0, target="sample"):
 # as scalars and the graph loop copies the table to the device, so both apply the same bits.  noisy[i]: step i takes a draw z
 # (noise[times[i]], or one generator call); the others get z = None.  has_d_prev: the step also reads and writes the previous
 # data prediction.  select(emb_all, coef_table, t_dev, emb_row, coefs): row t_dev of both tables, on the device.
-# step / step_dev(o, x, res, z, d_prev, row): the fused CFG combine + update with the row as host scalars / in device memory.
+# step / step_dev(o, x, dec, res, z, d_prev, row, i): the fused CFG combine + update of step i with the row as host scalars and
+# i a host integer / with the row in device memory and i the device-side counter (already decremented to i - 1 by select).  A
+# few-step rule with streams=True takes the pair that also writes sample_separate's streams (o.cum_static, o.theta_dyn,
+# o.theta_alpha) from dec; the others ignore dec and i.
 _Rule = namedtuple("_Rule", "name target steps times table noisy has_d_prev select step step_dev")
 
 
-def _update_rule(sched, solver, steps, eta, flexibility, target):
+def _update_rule(sched, solver, steps, eta, flexibility, target, streams=False):
     tgt = 0 if target == "sample" else 1
     if solver == "ddpm":
         # the reference's ancestral chain: every timestep T .. 1, a draw for every t > 1
@@ -138,27 +142,89 @@ def _update_rule(sched, solver, steps, eta, flexibility, target):
         return _Rule(
             solver, tgt, T, list(range(T + 1)), ddpm_table(sched, flexibility, target), [t > 1 for t in range(T + 1)], False,
             ops.sampler_step_select,
-            lambda o, x, res, z, d_prev, row: ops.cfg_ddpm_step(x, res, z, o.scales, o.n_entries, o.Lp, o.mode, tgt, *row),
-            lambda o, x, res, z, d_prev, row: ops.cfg_ddpm_step_dev(x, res, z, o.scales, row, o.n_entries, o.Lp, o.mode, tgt))
+            lambda o, x, dec, res, z, d_prev, row, i: ops.cfg_ddpm_step(x, res, z, o.scales, o.n_entries, o.Lp, o.mode, tgt, *row),
+            lambda o, x, dec, res, z, d_prev, row, i: ops.cfg_ddpm_step_dev(x, res, z, o.scales, row, o.n_entries, o.Lp, o.mode,
+                                                                        tgt))
     # a few-step solver draws only where its row's sigma is not 0; its float64 rows are rounded to fp32 here as the scalar
     # arguments of msmd_cfg_solver_step are
     taus, rows = solver_table(sched, steps, solver, eta, target)
-    return _Rule(
-        solver, tgt, steps, taus, rows.float(), (rows[:, 5] != 0).tolist(), True, ops.sampler_solver_select,
-        lambda o, x, res, z, d_prev, row: ops.cfg_solver_step(x, res, z, o.scales, d_prev, o.n_entries, o.Lp, o.mode, *row),
-        lambda o, x, res, z, d_prev, row: ops.cfg_solver_step_dev(x, res, z, o.scales, d_prev, row, o.n_entries, o.Lp, o.mode))
+    if streams:
+        # theta_alpha's row block: the step ordinal steps - i when every step's blend weights are kept, else 0
+        step = lambda o, x, dec, res, z, d_prev, row, i: ops.cfg_streams_step(
+            x, res, dec, o.stat, z, o.scales, d_prev, o.cum_static, o.theta_dyn, o.theta_alpha,
+            steps - i if o.theta_alpha.shape[0] > o.B else 0, o.n_entries, o.Lp, o.nb, o.head_alpha_bits, o.mode, *row)
+        step_dev = lambda o, x, dec, res, z, d_prev, row, i: ops.cfg_streams_step_dev(
+            x, res, dec, o.stat, z, o.scales, d_prev, o.cum_static, o.theta_dyn, o.theta_alpha, row, i, o.n_entries, o.Lp,
+            o.nb, o.head_alpha_bits, o.mode)
+    else:
+        step = lambda o, x, dec, res, z, d_prev, row, i: ops.cfg_solver_step(x, res, z, o.scales, d_prev, o.n_entries, o.Lp,
+                                                                             o.mode, *row)
+        step_dev = lambda o, x, dec, res, z, d_prev, row, i: ops.cfg_solver_step_dev(x, res, z, o.scales, d_prev, row,
+                                                                                     o.n_entries, o.Lp, o.mode)
+    return _Rule(solver, tgt, steps, taus, rows.float(), (rows[:, 5] != 0).tolist(), True, ops.sampler_solver_select, step,
+                 step_dev)
+
+
+def dense_guidance(indices, values, B, L, dm):
+    """Keyframes (indices, values) as msmd_denoiser_pack_input_guided takes them: (mask (B, L) uint8, dense (B, L, dm) fp32) on
+    the host, the result of `motion_in[:, indices, :] = values` (reference model.py:762-767) restated as "which frames, and
+    what they hold".  indices: anything that indexes a length-L axis (int, int list / array / tensor, slice, bool mask of
+    length L, negative entries); out of range raises IndexError.  values is broadcast to (B, G, dm), G = the number of frames
+    indexed.  Where an index repeats the last occurrence wins (numpy's assignment rule, which oracle/diffusion.py follows)."""
+    if not isinstance(indices, slice):
+        indices = indices.detach().cpu().numpy() if torch.is_tensor(indices) else np.asarray(indices)
+        if indices.size == 0:
+            indices = indices.astype(np.int64)         # an empty list is an empty float array to numpy
+    pos = np.arange(L)[indices]                        # numpy's own index rules, IndexError included
+    if pos.ndim > 1:
+        raise IndexError(f"keyframe indices must index one axis of length {L}, got an index of shape {pos.shape}")
+    vals = values.detach().float().cpu().numpy() if torch.is_tensor(values) else np.asarray(values, dtype=np.float32)
+    if pos.ndim == 0:
+        pos, vals = pos[None], np.broadcast_to(vals, (B, dm))[:, None, :]
+    vals = np.broadcast_to(vals, (B, len(pos), dm))
+    mask, dense = np.zeros((B, L), np.uint8), np.zeros((B, L, dm), np.float32)
+    for g, t in enumerate(pos.tolist()):               # in order: a repeated frame keeps its last value
+        dense[:, t] = vals[:, g]
+        mask[:, t] = 1
+    return torch.from_numpy(mask), torch.from_numpy(dense)
+
+
+class DenseGuide(namedtuple("DenseGuide", "mask values")):
+    """Keyframes already in the dense form (dense_guidance's pair, any device), for callers whose clips pin different frames:
+    pass it as the `indices` of a guidance pair with values None (inference.infer_coeffs_batch does)."""
+
+    @staticmethod
+    def stack(pairs, L, dm):
+        """One clip per entry of `pairs`: (indices, values) or None (no keyframes in that clip)."""
+        each = [dense_guidance(*p, 1, L, dm) if p is not None else dense_guidance([], np.zeros((0, dm), np.float32), 1, L, dm)
+                for p in pairs]
+        return DenseGuide(torch.cat([m for m, _ in each]), torch.cat([v for _, v in each]))
 
 
 class _Operands(namedtuple("_Operands", "net P dtype dev B n_entries N L Lp dm nb mode dyn "
-                                        "prev_m ind mem kv_list cross_list stat tok_person emb_all scales")):
+                                        "prev_m ind mem kv_list cross_list stat tok_person emb_all scales "
+                                        "guide_mask guide_values alpha_mod cum_static theta_dyn theta_alpha",
+                             defaults=(None,) * 6)):
     """Everything the hoisted section of sample() produces and a denoising step consumes.  N = n_entries * B rows, entry-major;
     mode: the CFG combine, 0 incremental / 1 independent; dyn: the dynamic threshold's (ratio, min, max) or None; stat has B rows
     or one; emb_all has one step embedding per row of the rule's table; ind, cross_list and scales may be None.  A lane of the
-    graph loop holds the same record with B, N and the tensors of its own rows (_Lane)."""
+    graph loop holds the same record with B, N and the tensors of its own rows (_Lane).
+    Few-step solvers only (the DDPM chain keeps these None): guide_mask (B, L) uint8 / guide_values (B, L, dm), the keyframes
+    that overwrite the denoiser input in the pack kernel; alpha_mod, sample_separate's callable on the blend weights; cum_static
+    and theta_dyn (B, L, dm) and theta_alpha (n_slots B, L, nb), the streams the streams step writes."""
+
+    @property
+    def head_alpha_bits(self):
+        """msmd_heads_static_mix's use_head_alpha argument."""
+        return int(bool(self.net.use_head_alpha)) | (2 if self.net.regularize_alpha == "sigmoid" else 0)
 
     def trunk(self, x, feats, emb_row):
-        """pack x into the denoiser input -> decoder trunk; returns dec (N, Lp + L, dm + nb)."""
-        ops.denoiser_pack_input(x, self.prev_m, self.ind, feats)
+        """pack x (keyframes overwritten where a guide is set) into the denoiser input -> decoder trunk; returns dec
+        (N, Lp + L, dm + nb)."""
+        if self.guide_mask is not None:
+            ops.denoiser_pack_input_guided(x, self.prev_m, self.ind, feats, self.guide_mask, self.guide_values)
+        else:
+            ops.denoiser_pack_input(x, self.prev_m, self.ind, feats)
         return self.net.trunk(feats, self.tok_person, self.mem, self.dtype, kv_list=self.kv_list, row0_add=emb_row,
                               cross_list=self.cross_list)
 
@@ -169,7 +235,13 @@ class _Operands(namedtuple("_Operands", "net P dtype dev B n_entries N L Lp dm n
         return res
 
     def heads(self, dec):
-        """heads / static mix -> optional dynamic threshold; returns res (N, Lp + L, dm)."""
+        """heads / static mix -> optional dynamic threshold; returns res (N, Lp + L, dm).  alpha_mod (eager loop only: an
+        arbitrary host callable) rewrites dec's blend-weight columns first, so the mix and the streams step read its result.
+        It sees the decoder's raw columns: with regularize_alpha='sigmoid' those are logits (the kernels apply the sigmoid after it,
+        where the reference's callable sees the weights after the sigmoid, model.py:973 then :560), and its result is stored in
+        dec's dtype."""
+        if self.alpha_mod is not None:
+            dec[..., self.dm:] = self.alpha_mod(dec[..., self.dm:])
         return self.threshold(ops.heads_static_mix(dec, self.stat, self.Lp + self.L, self.dm, self.nb, self.net.use_head_alpha,
                                                    self.net.regularize_alpha == "sigmoid"))
 
@@ -240,10 +312,18 @@ def sample(model, audio_or_feat, shape_feat, style_feat=None, prev_motion_feat=N
     separate = dict(alpha_mod=callable|None, return_all_alpha=bool): also track the dynamic / static / alpha
     streams (reference sample_separate, model.py:442-651).
     solver: "ddpm" (the reference's ancestral chain over all T steps), or "ddim" (eta in [0, 1]) / "dpmpp_2m" over
-    sample_steps timesteps (solver_table); noise is then keyed by the source timestep of each step."""
+    sample_steps timesteps (solver_table); noise is then keyed by the source timestep of each step.
+    With a few-step solver guidance and separation (alone or together) are part of the one step body: the keyframes overwrite the
+    denoiser input inside the pack kernel (dense_guidance; indices may also be a DenseGuide with values None) and the streams are
+    written by the streams step (msmd_cfg_streams_step), cum_static accumulating ath theta_static; x0 has the bits of the plain
+    call.  They take the hipGraph loop under sample()'s own rule unless alpha_mod is set.  solver="ddpm" keeps the reference's
+    tensor algebra (_Streams, index put) in the eager loop."""
     S = check_solver(model.diffusion_sched.num_steps, sample_steps, solver, eta, flexibility)
-    if solver != "ddpm" and (guidance is not None or separate is not None):
-        raise ValueError(f"solver={solver!r} is available in sample() only (not with guidance or stream separation)")
+    few = solver != "ddpm"
+    if few and guidance is not None and guidance[0] is None:
+        guidance = None                      # no keyframes: the plain body (the DDPM chain keeps its own test of the pair below)
+    if not few and guidance is not None and isinstance(guidance[0], DenseGuide):
+        raise ValueError("per-clip keyframes (DenseGuide) need solver='ddim' or 'dpmpp_2m'; solver='ddpm' takes (indices, values)")
     net = model.denoising_net
     dtype = model.compute_dtype
     dev = model.device
@@ -313,7 +393,7 @@ def sample(model, audio_or_feat, shape_feat, style_feat=None, prev_motion_feat=N
     # ---- step-invariant work, hoisted
     P = net.pack(dtype)
     T = model.diffusion_sched.num_steps
-    rule = _update_rule(model.diffusion_sched, solver, S, eta, flexibility, model.target)
+    rule = _update_rule(model.diffusion_sched, solver, S, eta, flexibility, model.target, streams=few and separate is not None)
     mem = torch.cat([ops.cast(prev_a.contiguous(), dtype), ops.cast(audio_in.contiguous(), dtype)], dim=1)
     kv_list = net.memory_kv(mem, dtype)
     cross_list = net.memory_cross(kv_list, dtype) if (P.diag and getattr(net, "diag_fast_path", True)) else None
@@ -329,28 +409,46 @@ def sample(model, audio_or_feat, shape_feat, style_feat=None, prev_motion_feat=N
                   mode=1 if cfg_mode == "independent" else 0, dyn=tuple(dynamic_threshold) if dynamic_threshold else None,
                   prev_m=prev_m, ind=ind_in, mem=mem, kv_list=kv_list, cross_list=cross_list, stat=stat,
                   tok_person=tok_person, emb_all=emb_all, scales=scales)
+    dense = None
+    if few and guidance is not None:
+        dense = guidance[0] if isinstance(guidance[0], DenseGuide) else DenseGuide(
+            *dense_guidance(guidance[0], guidance[1], batch_size, L, dm))
+        if tuple(dense.mask.shape) != (batch_size, L) or tuple(dense.values.shape) != (batch_size, L, dm):
+            raise ValueError(f"dense keyframes must be ({batch_size}, {L}) / ({batch_size}, {L}, {dm}), got "
+                             f"{tuple(dense.mask.shape)} / {tuple(dense.values.shape)}")
+        dense = DenseGuide(dense.mask.to(dev, torch.uint8).contiguous(), dense.values.to(dev, torch.float32).contiguous())
+    if few:
+        if dense is not None:
+            o = o._replace(guide_mask=dense.mask, guide_values=dense.values)
+        if separate is not None:
+            n_slots = S if separate.get("return_all_alpha") else 1
+            o = o._replace(alpha_mod=separate.get("alpha_mod"),
+                           cum_static=torch.zeros(batch_size, L, dm, device=dev), theta_dyn=torch.zeros(batch_size, L, dm, device=dev),
+                           theta_alpha=torch.zeros(n_slots * batch_size, L, nb, device=dev))
+    streams_out = lambda oo: (oo.theta_dyn, oo.cum_static, oo.theta_alpha) if few and separate is not None else ()
 
-    if (noise is None and not ret_traj and getattr(model, "use_hip_graph", True) and T > 1 and guidance is None
-            and separate is None):
-        return _graph_loop(model, o, rule, motion_at_T.float()), motion_at_T, audio_feat
+    if (noise is None and not ret_traj and getattr(model, "use_hip_graph", True) and T > 1
+            and (few and o.alpha_mod is None or (guidance is None and separate is None))):
+        x, outs = _graph_loop(model, o, rule, motion_at_T.float())
+        return (x, motion_at_T, audio_feat) + streams_out(outs)
 
     x = motion_at_T.float().clone().contiguous()
     d_prev = torch.zeros_like(x) if rule.has_d_prev else None
     traj = {rule.times[-1]: motion_at_T} if ret_traj else None
     feats = torch.empty(N, 1 + Lp + L, P.kp_feat, device=dev, dtype=dtype)
-    streams = _Streams(o, x, separate, cfg_scale) if separate is not None else None
+    streams = _Streams(o, x, separate, cfg_scale) if separate is not None and not few else None
     for i in range(rule.steps, 0, -1):
         z = None
         if rule.noisy[i]:
             z = noise[rule.times[i]].float().contiguous() if noise is not None else torch.randn_like(x)
         row = rule.table[i].tolist()
         x_in = x
-        if guidance is not None and guidance[0] is not None:
+        if not few and guidance is not None and guidance[0] is not None:
             x_in = x.clone()
             x_in[:, guidance[0], :] = guidance[1].to(x_in.dtype)
         dec = o.trunk(x_in, feats, emb_all[i])
         if streams is None:
-            rule.step(o, x, o.heads(dec), z, d_prev, row)
+            rule.step(o, x, dec, o.heads(dec), z, d_prev, row, i)
         else:
             x = streams.step(dec, x, z, rule.target, row)
         if ret_traj:
@@ -359,7 +457,7 @@ def sample(model, audio_or_feat, shape_feat, style_feat=None, prev_motion_feat=N
         return traj, motion_at_T, audio_feat
     if streams is not None:
         return (x, motion_at_T, audio_feat) + streams.outputs()
-    return x, motion_at_T, audio_feat
+    return (x, motion_at_T, audio_feat) + streams_out(o)
 
 
 # clamped to [1, 50]: k bodies in one graph keep k steps of intermediates alive in the graph's private pool (about 0.2 GB per
@@ -397,7 +495,14 @@ class _Lane:
             kv_list=[take(k) for k in o.kv_list],
             cross_list=[take(r) for r in o.cross_list] if o.cross_list is not None else None,
             stat=take(o.stat, clips) if self.own_stat else shared.stat,
-            tok_person=take(o.tok_person), emb_all=shared.emb_all, scales=shared.scales)
+            tok_person=take(o.tok_person), emb_all=shared.emb_all, scales=shared.scales,
+            # keyframes and the streams: static buffers of the lane's clips, like x (theta_alpha keeps the whole batch's slots)
+            guide_mask=take(o.guide_mask, clips) if o.guide_mask is not None else None,
+            guide_values=take(o.guide_values, clips) if o.guide_mask is not None else None,
+            cum_static=take(o.cum_static, clips) if o.cum_static is not None else None,
+            theta_dyn=take(o.theta_dyn, clips) if o.cum_static is not None else None,
+            theta_alpha=torch.zeros(o.theta_alpha.shape[0] // o.B * Bl, o.L, o.nb, device=dev) if o.cum_static is not None
+            else None)
         self.t_dev = torch.zeros(1, device=dev, dtype=torch.int32)
         self.emb_row = torch.zeros(o.emb_all.shape[-1], device=dev, dtype=o.emb_all.dtype)
         self.coefs = torch.zeros(rule.table.shape[1], device=dev, dtype=torch.float32)
@@ -407,10 +512,10 @@ class _Lane:
     def body(self, z):
         o = self.o
         self.rule.select(o.emb_all, self.shared.coef_table, self.t_dev, self.emb_row, self.coefs)
-        res = o.heads(o.trunk(self.x, self.feats, self.emb_row))
+        dec = o.trunk(self.x, self.feats, self.emb_row)
         # z: this lane's clips of the step's noise, drawn for the WHOLE batch on the forking stream (_StepGraph.bodies): what a
         # clip receives under a given seed does not depend on the lane count; sigma_1 = 0 reproduces z = 0 at t = 1
-        self.rule.step_dev(o, self.x, res, z, self.d_prev, self.coefs)
+        self.rule.step_dev(o, self.x, dec, o.heads(dec), z, self.d_prev, self.coefs, self.t_dev)
 
     def load(self, motion_at_T, whole):
         """Copy this lane's rows of the whole batch's operands into its static buffers."""
@@ -418,6 +523,11 @@ class _Lane:
         self.x.copy_(motion_at_T[self.clips])
         if self.d_prev is not None:
             self.d_prev.zero_()
+        if o.guide_mask is not None:
+            o.guide_mask.copy_(whole.guide_mask[self.clips])
+            o.guide_values.copy_(whole.guide_values[self.clips])
+        if o.cum_static is not None:
+            o.cum_static.zero_()
         o.prev_m.copy_(whole.prev_m[self.rows])
         o.mem.copy_(whole.mem[self.rows])
         if self.own_stat:
@@ -504,17 +614,26 @@ class _StepGraph:
             ln.t_dev.fill_(rule.steps)
         for _ in range(rule.steps // self.k):
             self.graph.replay()
-        return torch.cat([ln.x for ln in self.lane], dim=0) if self.lanes > 1 else self.lane[0].x.clone()
+        x = torch.cat([ln.x for ln in self.lane], dim=0) if self.lanes > 1 else self.lane[0].x.clone()
+        if o.cum_static is None:
+            return x, o
+        # the streams, concatenated across lanes as x is; a lane's theta_alpha is (n_slots, Bl, L, nb) in step order
+        cat = lambda name: torch.cat([getattr(ln.o, name) for ln in self.lane], dim=0)
+        alpha = torch.cat([ln.o.theta_alpha.view(-1, ln.o.B, o.L, o.nb) for ln in self.lane], dim=1).reshape(-1, o.L, o.nb)
+        return x, o._replace(cum_static=cat("cum_static"), theta_dyn=cat("theta_dyn"), theta_alpha=alpha)
 
 
 def _graph_loop(model, o, rule, motion_at_T):
-    """The hipGraph loop: one resident _StepGraph per model, rebuilt when anything the capture depends on changes."""
+    """The hipGraph loop: one resident _StepGraph per model, rebuilt when anything the capture depends on changes (guided or not,
+    separated or not and the number of alpha slots included; which frames are pinned is an operand, not part of the key).
+    Returns (x0, the operand record holding the streams of the whole batch)."""
     lanes = getattr(model, "sampler_lanes", LANES)
     while lanes > 1 and (o.B % lanes or o.N // lanes < MIN_LANE_SEQS):
         lanes -= 1
     key = (rule.steps, o.N, o.n_entries, o.Lp, o.L, o.mode, rule.target, o.dtype, o.ind is not None,
            getattr(o.net, "_pack_gen", 0), o.dyn, o.cross_list is not None, STEPS_PER_GRAPH, lanes, rule.name, any(rule.noisy),
-           o.stat.shape[0])
+           o.stat.shape[0], o.guide_mask is not None, o.cum_static is not None,
+           o.theta_alpha.shape[0] // o.B if o.cum_static is not None else 0)
     cache = model.__dict__.setdefault("_step_graphs", {})
     g = cache.get(key)
     if g is None:
