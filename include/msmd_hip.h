@@ -711,6 +711,39 @@ int msmd_batch_windows(const float* audio_flat, const float* coef_flat, const lo
                        const float* coef_mean, const float* coef_std, float* out_audio, float* out_motion, int B, int L,
                        int C, int n_audio, double audio_unit, msmd_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Mesh renderer (the reference's utils/renderer.py draws through pyrender / OpenGL; an Instinct card has no graphics
+ * pipe, so this is a compute rasteriser with its own Lambert shading: DESIGN.md 5.11).  Two launches per batch of
+ * frames, no host synchronisation, no global atomics, the same bits on every run.
+ *
+ * msmd_render_vertices, one thread per (frame, vertex): verts (B, V, 3) -> screen (B, V, 3) = (x_s, y_s, eye depth d)
+ *   and normals (B, V, 3), the eye-space unit vertex normal.
+ *   - normal = normalised sum of (v1 - v0) x (v2 - v0) over the vertex's incident faces, gathered through the vertex ->
+ *     face table csr_offsets (V + 1) / csr_faces (3 F) in table order; a zero sum gives (0, 0, 1);
+ *   - rot (B, 3) or NULL: per-frame axis-angle rotation about t_center (3), angle = |r|, identity at 0 (cv2.Rodrigues);
+ *   - view (3, 4) row-major: world -> eye, a rigid transform (the inverse of the camera pose); the camera looks down -z;
+ *   - projection with aspect ratio 1: x_ndc = focal x_e / d, d = -z_e, focal = 1 / tan(yfov / 2); viewport
+ *     x_s = (x_ndc / 2 + 1/2) W, y_s = (1/2 - y_ndc / 2) H: row 0 is the top, pixel (i, j) has its centre at (j + .5, i + .5).
+ * msmd_render_raster, one workgroup per (frame, 64 x 64 tile): rgba (B, H, W, 4) uint8, depth (B, H, W) fp32 eye depth,
+ *   face_id (B, H, W) int32 or NULL.
+ *   - coordinates snap to 8 sub-pixel bits, rint(x_s * 256) half-even; edge functions at the pixel centres are exact
+ *     64-bit integers; top-left fill rule (inside positive: a zero edge counts iff its oriented vector has dy > 0, or
+ *     dy == 0 and dx > 0); no back-face culling;
+ *   - NO CLIPPING: a face with a vertex at d < near, with zero snapped area, with a snapped coordinate of magnitude
+ *     >= 2^30 (or not finite) or with a vertex id outside [0, V) is dropped whole;
+ *   - depth: 1/d interpolated by e_k / (e_0 + e_1 + e_2) in fp32, fragments outside [near, far] discarded, the nearest
+ *     wins and the lower face id wins a tie;
+ *   - colour = base (ambient + (1/pi) sum_k I_k max(0, n . l_k)) clamped to [0, 1], floor(255 c + 0.5), alpha 255, with n
+ *     the perspective-correct interpolated vertex normal, renormalised; shade (6) = base rgb, ambient rgb; lights
+ *     (n_lights, 4) = eye-space unit direction TOWARDS the light, intensity;
+ *   - background pixels: `background` (R | G << 8 | B << 16 | A << 24), depth 0, face id -1. */
+int msmd_render_vertices(const float* verts, const int* faces, const int* csr_offsets, const int* csr_faces,
+                         const float* view, const float* t_center, const float* rot, float* screen, float* normals,
+                         int B, int V, int F, float focal, int H, int W, msmd_stream_t stream);
+int msmd_render_raster(const float* screen, const float* normals, const int* faces, const float* shade,
+                       const float* lights, int n_lights, void* rgba, float* depth, int* face_id, int B, int V, int F,
+                       int H, int W, float near, float far, unsigned background, msmd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

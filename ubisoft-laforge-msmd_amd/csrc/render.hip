@@ -1,0 +1,323 @@
+// Compute mesh renderer: vertex normals + camera, then a z-buffered tile rasteriser with Lambert shading.
+// An Instinct card has no graphics pipe; this turns the (B, V, 3) vertices msmd_lbs_skin_v2 leaves on the device into images
+// there.  Two launches per batch of frames, no host synchronisation, no global atomics, bit-identical from run to run.
+#include "common.h"
+
+namespace {
+
+struct __attribute__((packed, aligned(4))) F3 { float x, y, z; };
+struct __attribute__((packed, aligned(4))) I3 { int a, b, c; };
+
+__device__ __forceinline__ F3 cross3(const F3 a, const F3 b) {
+  return F3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
+}
+__device__ __forceinline__ F3 mat3_mul(const float* R, const F3 v) {
+  return F3{R[0] * v.x + R[1] * v.y + R[2] * v.z, R[3] * v.x + R[4] * v.y + R[5] * v.z, R[6] * v.x + R[7] * v.y + R[8] * v.z};
+}
+__device__ __forceinline__ F3 unit_or_z(const F3 v) {
+  const float n2 = v.x * v.x + v.y * v.y + v.z * v.z;
+  if (!(n2 > 0.f)) return F3{0.f, 0.f, 1.f};
+  const float n = sqrtf(n2);
+  return F3{v.x / n, v.y / n, v.z / n};
+}
+
+// ------------------------------------------------------------------------------------------------ vertex stage
+// One thread per (frame, vertex): area-weighted normal gathered through the vertex -> face CSR table in CSR order (the sum
+// of the incident faces' un-normalised cross products, so no atomics and one fixed order), the optional per-frame rigid
+// motion about t_center (Rodrigues as cv2 defines it: angle = |r|, identity at 0), world -> eye, the perspective
+// projection with aspect ratio 1 and the viewport transform with row 0 at the top.
+__global__ __launch_bounds__(256) void render_vertices_kernel(const float* __restrict__ verts, const int* __restrict__ faces,
+                                                              const int* __restrict__ csr_off, const int* __restrict__ csr_face,
+                                                              const float* __restrict__ view, const float* __restrict__ t_center,
+                                                              const float* __restrict__ rot, float* __restrict__ screen,
+                                                              float* __restrict__ normals, int B, int V, int F, float focal,
+                                                              float Wf, float Hf) {
+  const long t = blockIdx.x * 256L + threadIdx.x;
+  if (t >= (long)B * V) return;
+  const int b = (int)(t / V), v = (int)(t - (long)b * V);
+  const float* vb = verts + (long)b * V * 3;
+  F3 p = *(const F3*)(vb + (long)v * 3);
+  F3 n{0.f, 0.f, 0.f};
+  const int e0 = csr_off[v], e1 = csr_off[v + 1];
+  for (int e = e0; e < e1; ++e) {
+    const int f = csr_face[e];
+    if ((unsigned)f >= (unsigned)F) continue;
+    const I3 vi = *(const I3*)(faces + (long)f * 3);
+    if ((unsigned)vi.a >= (unsigned)V || (unsigned)vi.b >= (unsigned)V || (unsigned)vi.c >= (unsigned)V) continue;
+    const F3 a = *(const F3*)(vb + (long)vi.a * 3), q = *(const F3*)(vb + (long)vi.b * 3), c = *(const F3*)(vb + (long)vi.c * 3);
+    const F3 cr = cross3(F3{q.x - a.x, q.y - a.y, q.z - a.z}, F3{c.x - a.x, c.y - a.y, c.z - a.z});
+    n.x += cr.x; n.y += cr.y; n.z += cr.z;
+  }
+  n = unit_or_z(n);
+  if (rot != nullptr) {
+    const float rx = rot[b * 3], ry = rot[b * 3 + 1], rz = rot[b * 3 + 2];
+    const float th = sqrtf(rx * rx + ry * ry + rz * rz);
+    if (th > 0.f) {
+      const float kx = rx / th, ky = ry / th, kz = rz / th;
+      float s, c;
+      sincosf(th, &s, &c);
+      const float c1 = 1.f - c;
+      const float R[9] = {c + c1 * kx * kx, c1 * kx * ky - s * kz, c1 * kx * kz + s * ky,
+                          c1 * kx * ky + s * kz, c + c1 * ky * ky, c1 * ky * kz - s * kx,
+                          c1 * kx * kz - s * ky, c1 * ky * kz + s * kx, c + c1 * kz * kz};
+      const F3 tc{t_center[0], t_center[1], t_center[2]};
+      const F3 r = mat3_mul(R, F3{p.x - tc.x, p.y - tc.y, p.z - tc.z});
+      p = F3{r.x + tc.x, r.y + tc.y, r.z + tc.z};
+      n = mat3_mul(R, n);
+    }
+  }
+  const float M[9] = {view[0], view[1], view[2], view[4], view[5], view[6], view[8], view[9], view[10]};
+  F3 pe = mat3_mul(M, p);
+  pe.x += view[3]; pe.y += view[7]; pe.z += view[11];
+  const F3 ne = mat3_mul(M, n);
+  const float d = -pe.z;
+  const float xn = focal * pe.x / d, yn = focal * pe.y / d;
+  F3 s;
+  s.x = (xn * 0.5f + 0.5f) * Wf;
+  s.y = (0.5f - yn * 0.5f) * Hf;
+  s.z = d;
+  *(F3*)(screen + t * 3) = s;
+  *(F3*)(normals + t * 3) = ne;
+}
+
+// ------------------------------------------------------------------------------------------------ raster stage
+#define RT_TILE 64                 // pixels per tile side
+#define RT_THREADS 256
+#define RT_CAP 2048                // compacted face ids held in LDS between two coverage passes
+#define RT_WAVE_WALK 256           // an in-tile bounding box of more pixels than this is walked by a whole wave
+#define RT_SNAP_LIMIT 1073741824.f // 2^30: |snapped coordinate| below it, so every edge function fits 64 bits (see below)
+#define RT_EMPTY 0xffffffffffffffffull
+
+// A face as the coverage and the shading passes see it, from ONE routine, so both compute the same bits.
+// Coordinates are snapped to 8 sub-pixel bits (round half even).  With |X|, |Y| < 2^30 a difference is below 2^31, a product
+// below 2^62 and an edge function (a difference of two products) below 2^63: exact in int64 for any image size.
+struct FaceSetup {
+  int x0, y0, x1, y1, x2, y2;   // oriented so that the doubled area is positive (vertices 1 and 2 swapped if it was not)
+  int i0, i1, i2;               // vertex ids in that order
+  float q0, q1, q2;             // 1 / eye depth
+  long area;                    // e0 + e1 + e2 at any point
+  int jmin, jmax, imin, imax;   // pixel box inside the tile and the image (empty if min > max)
+  bool ok;
+};
+
+__device__ __forceinline__ long edge_fn(int ax, int ay, int bx, int by, long px, long py) {
+  return (long)(bx - ax) * (py - ay) - (long)(by - ay) * (px - ax);
+}
+// top-left rule: a zero edge value counts only on an edge whose oriented vector has dy > 0, or dy == 0 and dx > 0
+__device__ __forceinline__ long edge_bias(int ax, int ay, int bx, int by) {
+  const int dx = bx - ax, dy = by - ay;
+  return (dy > 0 || (dy == 0 && dx > 0)) ? 0L : -1L;
+}
+
+__device__ __forceinline__ FaceSetup face_setup(const int* __restrict__ faces, const float* __restrict__ scr, int f, int V,
+                                                float near, int tx0, int ty0, int tx1, int ty1) {
+  FaceSetup s;
+  s.ok = false;
+  const I3 vi = *(const I3*)(faces + (long)f * 3);
+  if ((unsigned)vi.a >= (unsigned)V || (unsigned)vi.b >= (unsigned)V || (unsigned)vi.c >= (unsigned)V) return s;
+  const F3 a = *(const F3*)(scr + (long)vi.a * 3), b = *(const F3*)(scr + (long)vi.b * 3), c = *(const F3*)(scr + (long)vi.c * 3);
+  if (!(a.z >= near && b.z >= near && c.z >= near)) return s;                 // no clipping: a face behind `near` is dropped
+  const float fx0 = rintf(a.x * 256.f), fy0 = rintf(a.y * 256.f), fx1 = rintf(b.x * 256.f), fy1 = rintf(b.y * 256.f),
+              fx2 = rintf(c.x * 256.f), fy2 = rintf(c.y * 256.f);
+  if (!(fabsf(fx0) < RT_SNAP_LIMIT && fabsf(fy0) < RT_SNAP_LIMIT && fabsf(fx1) < RT_SNAP_LIMIT && fabsf(fy1) < RT_SNAP_LIMIT &&
+        fabsf(fx2) < RT_SNAP_LIMIT && fabsf(fy2) < RT_SNAP_LIMIT)) return s;  // also NaN / inf
+  s.x0 = (int)fx0; s.y0 = (int)fy0; s.x1 = (int)fx1; s.y1 = (int)fy1; s.x2 = (int)fx2; s.y2 = (int)fy2;
+  s.i0 = vi.a; s.i1 = vi.b; s.i2 = vi.c;
+  s.q0 = 1.f / a.z; s.q1 = 1.f / b.z; s.q2 = 1.f / c.z;
+  s.area = edge_fn(s.x0, s.y0, s.x1, s.y1, s.x2, s.y2);
+  if (s.area == 0) return s;
+  if (s.area < 0) {
+    int t = s.x1; s.x1 = s.x2; s.x2 = t;
+    t = s.y1; s.y1 = s.y2; s.y2 = t;
+    t = s.i1; s.i1 = s.i2; s.i2 = t;
+    const float q = s.q1; s.q1 = s.q2; s.q2 = q;
+    s.area = -s.area;
+  }
+  // pixels whose centre (256 j + 128) lies inside the snapped bounding box
+  const int xmin = min(s.x0, min(s.x1, s.x2)), xmax = max(s.x0, max(s.x1, s.x2));
+  const int ymin = min(s.y0, min(s.y1, s.y2)), ymax = max(s.y0, max(s.y1, s.y2));
+  s.jmin = max((xmin + 127) >> 8, tx0); s.jmax = min((xmax - 128) >> 8, tx1);
+  s.imin = max((ymin + 127) >> 8, ty0); s.imax = min((ymax - 128) >> 8, ty1);
+  s.ok = s.jmin <= s.jmax && s.imin <= s.imax;
+  return s;
+}
+
+// the three edge functions at pixel centre (j, i): e0 is opposite vertex 0, and so on
+__device__ __forceinline__ void edges_at(const FaceSetup& s, int j, int i, long& e0, long& e1, long& e2) {
+  const long px = 256L * j + 128, py = 256L * i + 128;
+  e0 = edge_fn(s.x1, s.y1, s.x2, s.y2, px, py);
+  e1 = edge_fn(s.x2, s.y2, s.x0, s.y0, px, py);
+  e2 = edge_fn(s.x0, s.y0, s.x1, s.y1, px, py);
+}
+// 1 / depth by the integer barycentrics, one fixed order of operations; w_k are returned for the shading pass
+__device__ __forceinline__ float inv_depth(const FaceSetup& s, long e0, long e1, long e2, float& w0, float& w1, float& w2) {
+  const float A = (float)s.area;
+  w0 = (float)e0 / A; w1 = (float)e1 / A; w2 = (float)e2 / A;
+  return fmaf(w2, s.q2, fmaf(w1, s.q1, __fmul_rn(w0, s.q0)));
+}
+
+__device__ __forceinline__ void fragment(const FaceSetup& s, int f, int j, int i, long e0, long e1, long e2, long b0, long b1,
+                                         long b2, float near, float far, int tx0, int ty0, unsigned long long* s_key) {
+  if ((e0 + b0) < 0 || (e1 + b1) < 0 || (e2 + b2) < 0) return;
+  float w0, w1, w2;
+  const float d = 1.f / inv_depth(s, e0, e1, e2, w0, w1, w2);
+  if (!(d >= near && d <= far)) return;
+  const unsigned long long key = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)f;
+  atomicMin(&s_key[(i - ty0) * RT_TILE + (j - tx0)], key);     // LDS; min of (depth, face id): independent of arrival order
+}
+
+// One workgroup per (frame, 64 x 64 tile).  (A) the frame's faces are streamed 256 at a time and those whose snapped box
+// meets the tile are compacted, in face order, into an LDS list; (B) whenever the list could overflow, and at the end, the
+// listed faces are rasterised into the tile's 64-bit (depth bits, face id) keys with one LDS atomicMin per fragment: a lane
+// owns a face and walks its box, a face with a large box is queued and walked by a whole wave; (C) the tile is resolved
+// and shaded pixel-parallel.
+__global__ __launch_bounds__(RT_THREADS) void render_raster_kernel(const float* __restrict__ screen, const float* __restrict__ normals,
+                                                                   const int* __restrict__ faces, const float* __restrict__ shade,
+                                                                   const float* __restrict__ lights, int n_lights,
+                                                                   unsigned* __restrict__ rgba, float* __restrict__ depth,
+                                                                   int* __restrict__ face_id, int V, int F, int H, int W,
+                                                                   int tiles_x, int tiles_y, float near, float far, unsigned bg) {
+  __shared__ unsigned long long s_key[RT_TILE * RT_TILE];   // 32 KB
+  __shared__ int s_list[RT_CAP];
+  __shared__ int s_big[RT_CAP];
+  __shared__ int s_wcnt[2][RT_THREADS / 64];
+  __shared__ int s_nbig;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int tiles = tiles_x * tiles_y;
+  const int b = blockIdx.x / tiles, tile = blockIdx.x - b * tiles;
+  const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
+  const int tx0 = tx * RT_TILE, ty0 = ty * RT_TILE;
+  const int tx1 = min(tx0 + RT_TILE, W) - 1, ty1 = min(ty0 + RT_TILE, H) - 1;
+  const float* scr = screen + (long)b * V * 3;
+  const float* nrm = normals + (long)b * V * 3;
+
+  for (int p = tid; p < RT_TILE * RT_TILE; p += RT_THREADS) s_key[p] = RT_EMPTY;
+  if (tid == 0) s_nbig = 0;
+  int count = 0;   // uniform: entries of s_list
+  int it = 0;
+  for (int base = 0; base < F; base += RT_THREADS, ++it) {
+    // (A) compaction of faces [base, base + 256) behind the `count` entries already listed
+    const int f = base + tid;
+    bool keep = false;
+    if (f < F) keep = face_setup(faces, scr, f, V, near, tx0, ty0, tx1, ty1).ok;
+    const unsigned long long m = __ballot(keep);
+    if (lane == 0) s_wcnt[it & 1][wid] = __popcll(m);
+    __syncthreads();     // also orders the key initialisation / the previous pass before what follows
+    int off = count, total = 0;
+#pragma unroll
+    for (int w = 0; w < RT_THREADS / 64; ++w) {
+      const int c = s_wcnt[it & 1][w];
+      if (w < wid) off += c;
+      total += c;
+    }
+    if (keep) s_list[off + __popcll(m & ((1ull << lane) - 1ull))] = f;
+    count += total;
+    if (count + RT_THREADS <= RT_CAP && base + RT_THREADS < F) continue;
+    __syncthreads();
+    // (B) coverage, face-parallel
+    for (int e = tid; e < count; e += RT_THREADS) {
+      const int g = s_list[e];
+      const FaceSetup s = face_setup(faces, scr, g, V, near, tx0, ty0, tx1, ty1);
+      const int bw = s.jmax - s.jmin + 1, bh = s.imax - s.imin + 1;
+      if (bw * bh > RT_WAVE_WALK) {
+        s_big[atomicAdd(&s_nbig, 1)] = g;       // the order of this queue does not reach the result (min of keys)
+        continue;
+      }
+      const long b0 = edge_bias(s.x1, s.y1, s.x2, s.y2), b1 = edge_bias(s.x2, s.y2, s.x0, s.y0), b2 = edge_bias(s.x0, s.y0, s.x1, s.y1);
+      long r0, r1, r2;
+      edges_at(s, s.jmin, s.imin, r0, r1, r2);
+      // d e / d j = -256 (by - ay), d e / d i = 256 (bx - ax): exact integer steps
+      const long a0 = -256L * (s.y2 - s.y1), a1 = -256L * (s.y0 - s.y2), a2 = -256L * (s.y1 - s.y0);
+      const long c0 = 256L * (s.x2 - s.x1), c1 = 256L * (s.x0 - s.x2), c2 = 256L * (s.x1 - s.x0);
+      for (int i = s.imin; i <= s.imax; ++i) {
+        long e0 = r0, e1 = r1, e2 = r2;
+        for (int j = s.jmin; j <= s.jmax; ++j) {
+          fragment(s, g, j, i, e0, e1, e2, b0, b1, b2, near, far, tx0, ty0, s_key);
+          e0 += a0; e1 += a1; e2 += a2;
+        }
+        r0 += c0; r1 += c1; r2 += c2;
+      }
+    }
+    __syncthreads();
+    const int nbig = s_nbig;
+    for (int e = wid; e < nbig; e += RT_THREADS / 64) {
+      const int g = s_big[e];
+      const FaceSetup s = face_setup(faces, scr, g, V, near, tx0, ty0, tx1, ty1);
+      const long b0 = edge_bias(s.x1, s.y1, s.x2, s.y2), b1 = edge_bias(s.x2, s.y2, s.x0, s.y0), b2 = edge_bias(s.x0, s.y0, s.x1, s.y1);
+      const int bw = s.jmax - s.jmin + 1, n = bw * (s.imax - s.imin + 1);
+      for (int p = lane; p < n; p += 64) {
+        const int i = s.imin + p / bw, j = s.jmin + p % bw;
+        long e0, e1, e2;
+        edges_at(s, j, i, e0, e1, e2);
+        fragment(s, g, j, i, e0, e1, e2, b0, b1, b2, near, far, tx0, ty0, s_key);
+      }
+    }
+    __syncthreads();     // before the lists are refilled
+    count = 0;
+    if (tid == 0) s_nbig = 0;
+  }
+  __syncthreads();
+
+  // (C) resolve and shade: a wave stores one 64-pixel row segment (256 contiguous bytes of RGBA) per step
+  const float base_r = shade[0], base_g = shade[1], base_b = shade[2], amb_r = shade[3], amb_g = shade[4], amb_b = shade[5];
+  for (int p = tid; p < RT_TILE * RT_TILE; p += RT_THREADS) {
+    const int i = ty0 + p / RT_TILE, j = tx0 + p % RT_TILE;
+    if (i > ty1 || j > tx1) continue;
+    const unsigned long long key = s_key[p];
+    const long o = ((long)b * H + i) * W + j;
+    if (key == RT_EMPTY) {
+      rgba[o] = bg;
+      depth[o] = 0.f;
+      if (face_id != nullptr) face_id[o] = -1;
+      continue;
+    }
+    const int g = (int)(unsigned)(key & 0xffffffffull);
+    const FaceSetup s = face_setup(faces, scr, g, V, near, tx0, ty0, tx1, ty1);
+    long e0, e1, e2;
+    edges_at(s, j, i, e0, e1, e2);
+    float w0, w1, w2;
+    const float iz = inv_depth(s, e0, e1, e2, w0, w1, w2);
+    // perspective-correct weights w_k q_k / (sum), then the interpolated normal
+    const float p0 = w0 * s.q0 / iz, p1 = w1 * s.q1 / iz, p2 = w2 * s.q2 / iz;
+    const F3 n0 = *(const F3*)(nrm + (long)s.i0 * 3), n1 = *(const F3*)(nrm + (long)s.i1 * 3), n2 = *(const F3*)(nrm + (long)s.i2 * 3);
+    const F3 n = unit_or_z(F3{p0 * n0.x + p1 * n1.x + p2 * n2.x, p0 * n0.y + p1 * n1.y + p2 * n2.y, p0 * n0.z + p1 * n1.z + p2 * n2.z});
+    float diff = 0.f;
+    for (int k = 0; k < n_lights; ++k) {
+      const float ndl = n.x * lights[4 * k] + n.y * lights[4 * k + 1] + n.z * lights[4 * k + 2];
+      diff += lights[4 * k + 3] * fmaxf(0.f, ndl);
+    }
+    diff *= 0.318309886183790672f;
+    const float cr = fminf(fmaxf(base_r * (amb_r + diff), 0.f), 1.f), cg = fminf(fmaxf(base_g * (amb_g + diff), 0.f), 1.f),
+                cb = fminf(fmaxf(base_b * (amb_b + diff), 0.f), 1.f);
+    const unsigned ur = (unsigned)floorf(255.f * cr + 0.5f), ug = (unsigned)floorf(255.f * cg + 0.5f),
+                   ub = (unsigned)floorf(255.f * cb + 0.5f);
+    rgba[o] = ur | (ug << 8) | (ub << 16) | 0xff000000u;
+    depth[o] = __uint_as_float((unsigned)(key >> 32));
+    if (face_id != nullptr) face_id[o] = g;
+  }
+}
+
+}  // namespace
+
+extern "C" int msmd_render_vertices(const float* verts, const int* faces, const int* csr_offsets, const int* csr_faces,
+                                    const float* view, const float* t_center, const float* rot, float* screen,
+                                    float* normals, int B, int V, int F, float focal, int H, int W, msmd_stream_t stream) {
+  if (B <= 0 || V <= 0 || F <= 0 || H <= 0 || W <= 0 || (rot != nullptr && t_center == nullptr)) return 1;
+  const long n = (long)B * V;
+  if ((n + 255) / 256 > 2147483647L) return 1;
+  hipLaunchKernelGGL(render_vertices_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, verts, faces,
+                     csr_offsets, csr_faces, view, t_center, rot, screen, normals, B, V, F, focal, (float)W, (float)H);
+  MSMD_RETURN_LAST();
+}
+
+extern "C" int msmd_render_raster(const float* screen, const float* normals, const int* faces, const float* shade,
+                                  const float* lights, int n_lights, void* rgba, float* depth, int* face_id, int B, int V,
+                                  int F, int H, int W, float near, float far, unsigned background, msmd_stream_t stream) {
+  if (B <= 0 || V <= 0 || F <= 0 || H <= 0 || W <= 0 || n_lights < 0 || !(near > 0.f) || !(far >= near)) return 1;
+  const int tiles_x = (W + RT_TILE - 1) / RT_TILE, tiles_y = (H + RT_TILE - 1) / RT_TILE;
+  const long grid = (long)B * tiles_x * tiles_y;
+  if (grid > 2147483647L) return 1;
+  hipLaunchKernelGGL(render_raster_kernel, dim3((unsigned)grid), dim3(RT_THREADS), 0, (hipStream_t)stream, screen, normals, faces,
+                     shade, lights, n_lights, (unsigned*)rgba, depth, face_id, V, F, H, W, tiles_x, tiles_y, near, far, background);
+  MSMD_RETURN_LAST();
+}

@@ -12,6 +12,8 @@ SURVEY.md section 8(f) n3, the callers either side of the sampler:
   * ``infer_coeffs_batch`` -- many clips at once: window i of every clip that still has one goes through ONE
     ``model.sample`` call (the sampler is launch-bound at batch 1: 0.71 ms/step at B = 1 vs 3.5 ms/step at B = 64), one
     encoder pass per distinct padded length; per-clip results equal ``infer_coeffs`` on that clip.
+  * ``render_coeffs`` -- coefficients -> FLAME vertices -> images on the device (utils/renderer.MeshRenderer), the step the
+    reference script leaves as a comment (inference.py:277-279) and its utils/renderer.py serves.
 The reference script's media IO (librosa, cv2, wav / video writing) stays outside the hot path.
 """
 from __future__ import annotations
@@ -28,6 +30,7 @@ import torch.nn.functional as F
 from .model import get_diffusion_model
 from .sampler import DenseGuide
 from .style_encoder import get_style_encoder
+from .utils.common import coef_dict_to_vertices, get_coef_dict
 from .utils.model_common import load_args
 
 
@@ -172,6 +175,26 @@ def denormalize_coeffs(overall_coef, coef_stats):
             overall_coef[0, :, -3:] * st["pose_std"] + st["pose_mean"])
 
 
+@torch.no_grad()
+def render_coeffs(coef, shape_coef, flame, coef_stats, renderer, chunk=512, *, with_global_pose=True):
+    """Motion coefficients (T, C) or (1, T, C) -> frames (T, H, W, 3) uint8 on the device: get_coef_dict -> coef_dict_to_vertices
+    -> renderer.render_vertices on FLAME's faces, `chunk` frames at a time (one chunk's vertices are the only intermediate
+    alive).  coef is in get_coef_dict's layout (50 expression + 4 pose: global rotation, jaw opening); a 53-wide row
+    (expression + head rotation, what `denormalize_coeffs` returns side by side) gets a closed jaw.  coef_stats: None for
+    coefficients in the data's units, or get_coef_dict's denorm_stats (`exp` / `pose` / `shape` means and stds).
+    shape_coef: (1, 100) or (T, 100)."""
+    coef = coef.reshape(-1, coef.shape[-1]).float()
+    if coef.shape[-1] == 53:
+        coef = torch.cat([coef, torch.zeros_like(coef[:, :1])], dim=-1)
+    shape = shape_coef.reshape(-1, shape_coef.shape[-1]).float().expand(coef.shape[0], -1)
+    frames = []
+    for i in range(0, coef.shape[0], chunk):
+        coef_dict = get_coef_dict(coef[i:i + chunk], shape[i:i + chunk], coef_stats, with_global_pose=with_global_pose)
+        verts = coef_dict_to_vertices(coef_dict, flame, flame_batch_size=chunk)
+        frames.append(renderer.render_vertices(verts, flame.faces_tensor)[0])
+    return torch.cat(frames, dim=0)
+
+
 # ----------------------------------------------------------------------------- many clips per denoise step
 @torch.no_grad()
 def infer_coeffs_batch(model, args, audios, shape_coefs, audio_unit, style_feats, cfg_mode=None, cfg_cond=None,
@@ -261,6 +284,10 @@ def build_parser():
     ap.add_argument("--sample_steps", type=int, default=None, help="steps of a few-step solver (default: all)")
     ap.add_argument("--solver", type=str, default="ddpm", choices=["ddpm", "ddim", "dpmpp_2m"])
     ap.add_argument("--eta", type=float, default=0.0, help="DDIM noise scale: 0 deterministic, 1 ancestral")
+    # rendering (the reference script stops before it; 0 = off: the files written are then exactly the two pickles)
+    ap.add_argument("--render_size", type=int, default=0, help="side of the square frames rendered from the result (0: none)")
+    ap.add_argument("--flame_model_path", type=str, default=None, help="FLAME generic_model.pkl (with --render_size)")
+    ap.add_argument("--flame_lmk_embedding_path", type=str, default=None, help="FLAME landmark embedding (with --render_size)")
     return ap
 
 
@@ -277,8 +304,9 @@ def load_audio_16k(path):
 def main(argv=None):
     """The non-media part of reference inference.py:189-279: load model + style encoder, ingest the style clip, z-norm
     the audio, sample the style code, run infer_coeffs per repetition seed, de-normalise and write the two pickles
-    (`overall_exp_code_*`, `overall_head_rot_*`) under <output_dir>/<model>_iter_<iter>/temp/.  Mesh decoding and
-    video rendering of the reference script are not part of this path."""
+    (`overall_exp_code_*`, `overall_head_rot_*`) under <output_dir>/<model>_iter_<iter>/temp/.  With --render_size N > 0 the
+    coefficients are also decoded by FLAME and rendered on the device (render_coeffs), and `frames_<clip>_seed_<s>.npy`
+    ((T, N, N, 3) uint8) is written beside them; encoding a video from the frames stays outside."""
     import os
     args = build_parser().parse_args(argv)
     device = torch.device("cuda")
@@ -299,6 +327,18 @@ def main(argv=None):
     temp = os.path.join(args.output_dir, f"{args.model_name}_iter_{args.model_iter}", "temp")
     os.makedirs(temp, exist_ok=True)
     written = []
+    flame = renderer = None
+    if args.render_size > 0:
+        from .utils.flame import FLAME, FLAMEConfig
+        from .utils.renderer import MeshRenderer
+        from types import SimpleNamespace
+        cfg = SimpleNamespace(**{k: v for k, v in vars(FLAMEConfig).items() if not k.startswith("__")})
+        if args.flame_model_path is not None:
+            cfg.flame_model_path = args.flame_model_path
+        if args.flame_lmk_embedding_path is not None:
+            cfg.flame_lmk_embedding_path = args.flame_lmk_embedding_path
+        flame = FLAME(cfg).to(device)
+        renderer = MeshRenderer((args.render_size, args.render_size))
     for seed in range(args.versions_of_render):
         np.random.seed(seed)
         torch.manual_seed(seed)
@@ -309,6 +349,11 @@ def main(argv=None):
             out = os.path.join(temp, f"overall_{tag}_{clip}_seed_{seed}.pkl")
             with open(out, "wb") as f:
                 pkl.dump(val.cpu().numpy(), f)
+            written.append(out)
+        if renderer is not None:
+            frames = render_coeffs(torch.cat([exp_code, head_rot], dim=-1), shape_coef.reshape(1, -1), flame, None, renderer)
+            out = os.path.join(temp, f"frames_{clip}_seed_{seed}.npy")
+            np.save(out, frames.cpu().numpy())
             written.append(out)
     return written
 

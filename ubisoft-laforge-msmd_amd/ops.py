@@ -1341,3 +1341,69 @@ def unfold_t(xp, T, Kk):
     out = torch.empty(G, Kk * Cg, Mp, device=xp.device, dtype=xp.dtype)
     _lib.check(lib.msmd_unfold_t(_p(xp), _p(out), B, T, Tp, G, Cg, Kk, Mp, _dt(xp), _stream()), "msmd_unfold_t")
     return out
+
+
+# ----------------------------------------------------------------------------- mesh renderer (csrc/render.hip)
+def _render_arg(name, t, dtype, shape=None, optional=False):
+    """The renderer's entry points index raw pointers from the stated sizes: contiguous device tensors of one dtype only."""
+    if t is None and optional:
+        return
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
+        raise TypeError(f"{name} must be a contiguous {dtype} CUDA tensor")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise TypeError(f"{name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
+
+
+def render_vertices(verts, faces_i32, csr_offsets, csr_faces, view, focal, height, width, t_center=None, rot=None):
+    """-> (screen (B, V, 3) = (x_s, y_s, eye depth), normals (B, V, 3) eye-space unit vertex normals): msmd_render_vertices.
+    verts (B, V, 3) fp32; faces (F, 3), csr_offsets (V + 1), csr_faces (3 F) int32 (utils/renderer.vertex_face_csr);
+    view (3, 4) fp32 world -> eye; rot (B, 3) axis-angle about t_center (3), both or neither."""
+    _render_arg("verts", verts, torch.float32)
+    if verts.dim() != 3 or verts.shape[2] != 3:
+        raise TypeError(f"verts must have shape (B, V, 3), got {tuple(verts.shape)}")
+    B, V, _ = verts.shape
+    _render_arg("faces", faces_i32, torch.int32)
+    if faces_i32.dim() != 2 or faces_i32.shape[1] != 3:
+        raise TypeError(f"faces must have shape (F, 3), got {tuple(faces_i32.shape)}")
+    Fc = faces_i32.shape[0]
+    _render_arg("csr_offsets", csr_offsets, torch.int32, (V + 1,))
+    _render_arg("csr_faces", csr_faces, torch.int32, (3 * Fc,))
+    _render_arg("view", view, torch.float32, (3, 4))
+    if (rot is None) != (t_center is None):
+        raise TypeError("rot and t_center are given together")
+    _render_arg("rot", rot, torch.float32, (B, 3), optional=True)
+    _render_arg("t_center", t_center, torch.float32, (3,), optional=True)
+    lib = _lib.load()
+    screen = torch.empty(B, V, 3, device=verts.device, dtype=torch.float32)
+    normals = torch.empty(B, V, 3, device=verts.device, dtype=torch.float32)
+    _lib.check(lib.msmd_render_vertices(_p(verts), _p(faces_i32), _p(csr_offsets), _p(csr_faces), _p(view), _p(t_center),
+                                        _p(rot), _p(screen), _p(normals), B, V, Fc, float(focal), int(height), int(width),
+                                        _stream()), "msmd_render_vertices")
+    return screen, normals
+
+
+def render_raster(screen, normals, faces_i32, shade, lights, height, width, near, far, background, want_face_id=False):
+    """-> (rgba (B, H, W, 4) uint8, depth (B, H, W) fp32, face_id (B, H, W) int32 or None): msmd_render_raster.
+    screen / normals (B, V, 3) fp32 as render_vertices returns them; shade (6) = base rgb, ambient rgb; lights (L, 4) =
+    eye-space unit direction towards the light, intensity; background = R | G << 8 | B << 16 | A << 24."""
+    _render_arg("screen", screen, torch.float32)
+    if screen.dim() != 3 or screen.shape[2] != 3:
+        raise TypeError(f"screen must have shape (B, V, 3), got {tuple(screen.shape)}")
+    B, V, _ = screen.shape
+    _render_arg("normals", normals, torch.float32, (B, V, 3))
+    _render_arg("faces", faces_i32, torch.int32)
+    if faces_i32.dim() != 2 or faces_i32.shape[1] != 3:
+        raise TypeError(f"faces must have shape (F, 3), got {tuple(faces_i32.shape)}")
+    _render_arg("shade", shade, torch.float32, (6,))
+    _render_arg("lights", lights, torch.float32)
+    if lights.dim() != 2 or lights.shape[1] != 4:
+        raise TypeError(f"lights must have shape (L, 4), got {tuple(lights.shape)}")
+    H, W = int(height), int(width)
+    lib = _lib.load()
+    rgba = torch.empty(B, H, W, 4, device=screen.device, dtype=torch.uint8)
+    depth = torch.empty(B, H, W, device=screen.device, dtype=torch.float32)
+    face_id = torch.empty(B, H, W, device=screen.device, dtype=torch.int32) if want_face_id else None
+    _lib.check(lib.msmd_render_raster(_p(screen), _p(normals), _p(faces_i32), _p(shade), _p(lights), lights.shape[0], _p(rgba),
+                                      _p(depth), _p(face_id), B, V, faces_i32.shape[0], H, W, float(near), float(far),
+                                      int(background) & 0xffffffff, _stream()), "msmd_render_raster")
+    return rgba, depth, face_id

@@ -1,0 +1,179 @@
+"""Mesh renderer on the MI355X (surface of reference utils/renderer.py:14-128, which draws through pyrender / EGL).
+
+An Instinct card has no graphics pipe, so the image is made by two compute launches (csrc/render.hip):
+vertex normals + camera + projection, then a z-buffered 64 x 64-tile rasteriser with Lambert shading.  Coverage and depth
+follow the OpenGL conventions the reference's renderer works under (pixel centres at +0.5, top-left fill rule, row 0 at the
+top, eye depth with 0 for the background as pyrender returns it); the shading model is this project's own (Lambert + ambient on
+the reference's base colour, lights and ambient level), not pyrender's metallic-roughness shader, so colours are not pixel-equal.
+There is NO CLIPPING: a face with a vertex nearer than `near` is dropped whole.  Texture (tex_img) is out of scope.
+
+``render_mesh`` keeps the reference's signature and returns numpy arrays; ``render_vertices`` takes the (B, V, 3) device
+tensor FLAME produces and leaves colour and depth on the device.
+"""
+from __future__ import annotations
+
+import hashlib
+
+import numpy as np
+
+import torch
+
+from .. import ops
+
+
+def vertex_face_csr(faces, n_vertices):
+    """Vertex -> incident-face table of a triangle list: (offsets (V + 1) int32, face ids (3 F) int32).  The faces of vertex
+    v are ids[offsets[v]:offsets[v + 1]], ascending, each face once (a face that repeats a vertex is still one face);
+    the tail of `ids` beyond offsets[V] is padding (-1).  Raises ValueError on a vertex id outside [0, V)."""
+    f = np.asarray(faces).astype(np.int64).reshape(-1, 3)
+    V, Fc = int(n_vertices), f.shape[0]
+    if Fc == 0:
+        raise ValueError("faces is empty")
+    if f.min() < 0 or f.max() >= V:
+        raise ValueError(f"faces refer to vertices outside [0, {V})")
+    pairs = np.unique(f.reshape(-1) * Fc + np.repeat(np.arange(Fc, dtype=np.int64), 3))    # sorted by (vertex, face)
+    vert, face = pairs // Fc, pairs % Fc
+    offsets = np.zeros(V + 1, np.int64)
+    np.cumsum(np.bincount(vert, minlength=V), out=offsets[1:])
+    ids = np.full(3 * Fc, -1, np.int32)
+    ids[:face.shape[0]] = face
+    return offsets.astype(np.int32), ids
+
+
+def rodrigues(r):
+    """3 x 3 rotation of the axis-angle vector r as cv2.Rodrigues defines it: angle = |r|, identity at 0 (float64)."""
+    r = np.asarray(r, np.float64).reshape(3)
+    th = float(np.sqrt(r @ r))
+    if th == 0.0:
+        return np.eye(3)
+    k = r / th
+    K = np.array([[0.0, -k[2], k[1]], [k[2], 0.0, -k[0]], [-k[1], k[0], 0.0]])
+    return np.cos(th) * np.eye(3) + (1.0 - np.cos(th)) * np.outer(k, k) + np.sin(th) * K
+
+
+class MeshRenderer:
+    def __init__(self, size, fov=16 / 180 * np.pi, camera_pose=None, light_pose=None, black_bg=False):
+        self.width, self.height = int(size[0]), int(size[1])       # the reference hands `size` on as (width, height)
+        if not (0 < self.width <= 16384 and 0 < self.height <= 16384):
+            raise ValueError(f"size {size} is outside (0, 16384]")
+        self.fov = float(fov)
+        self.frustum = {"near": 0.01, "far": 3.0}
+        self.base_color = np.array([0.3, 0.3, 0.3])
+        self.ambient = np.array([0.2, 0.2, 0.2])
+        self.light_intensity = 2.0
+        self.light_angle = np.pi / 6.0
+        self.bg_color = (0, 0, 0) if black_bg else (255, 255, 255)
+        if camera_pose is None:
+            camera_pose = np.eye(4)
+            camera_pose[:3, 3] = np.array([0, 0, 1])
+        if light_pose is None:
+            light_pose = np.eye(4)
+            light_pose[:3, 3] = np.array([0, 0, 1])
+        self._consts = {}          # device -> (view, shade, lights)
+        self._csr = {}             # faces key -> (faces int32, offsets, ids) on the device
+        self.set_camera_pose(camera_pose)
+        self.set_lighting_pose(light_pose)
+
+    # ------------------------------------------------------------------ scene state
+    def set_camera_pose(self, camera_pose):
+        self.camera_pose = np.array(camera_pose, np.float64)
+        self._consts.clear()
+
+    def set_lighting_pose(self, light_pose):
+        self.light_pose = np.array(light_pose, np.float64)
+        self.light_poses = self._get_light_poses(self.light_angle, self.light_pose.copy())
+        self._consts.clear()
+
+    @staticmethod
+    def _get_light_poses(light_angle, light_pose):
+        """Five poses: the given one and four whose POSITION is turned by +-light_angle about x and y (reference
+        utils/renderer.py:110-128).  The rotation part is left alone and a directional light has no position, so all five
+        shine along the given pose's -z axis: kept as the reference has it."""
+        origin = light_pose[:3, 3].copy()
+        poses = [light_pose.copy()]
+        for axis in ([light_angle, 0, 0], [-light_angle, 0, 0], [0, -light_angle, 0], [0, light_angle, 0]):
+            p = light_pose.copy()
+            p[:3, 3] = rodrigues(axis) @ origin
+            poses.append(p)
+        return poses
+
+    def _device_consts(self, device):
+        key = str(device)
+        if key not in self._consts:
+            world_to_eye = np.linalg.inv(self.camera_pose)
+            lights = np.zeros((len(self.light_poses), 4), np.float32)
+            for k, pose in enumerate(self.light_poses):
+                d = world_to_eye[:3, :3] @ pose[:3, 2]                 # towards the light: the pose's +z axis, in eye space
+                lights[k, :3] = d / np.linalg.norm(d)
+                lights[k, 3] = self.light_intensity
+            shade = np.concatenate([self.base_color, self.ambient]).astype(np.float32)
+            view = np.ascontiguousarray(world_to_eye[:3, :], np.float32)
+            self._consts[key] = tuple(torch.from_numpy(a).to(device) for a in (view, shade, lights))
+        return self._consts[key]
+
+    def _tables(self, faces, n_vertices, device):
+        """faces (tensor or array) -> (faces int32 (F, 3), csr offsets, csr face ids) on `device`, cached per faces object
+        (a tensor by its storage and version, an array by its contents)."""
+        if torch.is_tensor(faces):
+            key = ("t", faces.data_ptr(), tuple(faces.shape), faces.dtype, str(faces.device), faces._version, n_vertices, str(device))
+        else:
+            faces = np.ascontiguousarray(faces)
+            key = ("n", hashlib.sha1(faces.tobytes()).hexdigest(), faces.shape, str(faces.dtype), n_vertices, str(device))
+        hit = self._csr.get(key)
+        if hit is None:
+            host = faces.detach().cpu().numpy() if torch.is_tensor(faces) else faces
+            host = host.astype(np.int64).reshape(-1, 3)
+            off, ids = vertex_face_csr(host, n_vertices)
+            if len(self._csr) >= 8:
+                self._csr.pop(next(iter(self._csr)))
+            # the tensor itself is kept with its tables, so its storage cannot be recycled under the key
+            hit = (faces, torch.from_numpy(host.astype(np.int32)).to(device), torch.from_numpy(off).to(device),
+                   torch.from_numpy(ids).to(device))
+            self._csr[key] = hit
+        return hit[1:]
+
+    # ------------------------------------------------------------------ rendering
+    def render_vertices(self, vertices, faces, t_center=None, rot=None, return_face_id=False, return_screen=False):
+        """vertices (B, V, 3) CUDA tensor (fp32, or fp16 / bf16: cast) -> colour (B, H, W, 3) uint8 (a view of the RGBA
+        buffer) and eye depth (B, H, W) fp32 (0 = background), both on the device.  rot: (3,) or (B, 3) axis-angle about
+        t_center (3,) per frame.  return_face_id appends the winning face id per pixel (int32, -1 = background);
+        return_screen appends the vertex stage's screen (B, V, 3) = (x_s, y_s, depth) and eye-space normals (B, V, 3)."""
+        if not torch.is_tensor(vertices) or not vertices.is_cuda or vertices.dim() != 3 or vertices.shape[2] != 3:
+            raise TypeError("vertices must be a (B, V, 3) CUDA tensor")
+        device = vertices.device
+        verts = vertices.detach().float().contiguous()
+        B, V, _ = verts.shape
+        faces_d, off, ids = self._tables(faces, V, device)
+        view, shade, lights = self._device_consts(device)
+        rot_d = tc_d = None
+        if rot is not None:
+            rot_d = torch.as_tensor(rot, dtype=torch.float32, device=device).reshape(-1, 3).expand(B, 3).contiguous()
+            tc = np.zeros(3) if t_center is None else t_center
+            tc_d = torch.as_tensor(tc, dtype=torch.float32, device=device).reshape(3).contiguous()
+        focal = 1.0 / np.tan(self.fov / 2.0)
+        screen, normals = ops.render_vertices(verts, faces_d, off, ids, view, focal, self.height, self.width, tc_d, rot_d)
+        r, g, b = self.bg_color
+        rgba, depth, face_id = ops.render_raster(screen, normals, faces_d, shade, lights, self.height, self.width,
+                                                 self.frustum["near"], self.frustum["far"], r | g << 8 | b << 16 | 255 << 24,
+                                                 want_face_id=return_face_id)
+        out = (rgba[..., :3], depth)
+        if return_face_id:
+            out += (face_id,)
+        if return_screen:
+            out += (screen, normals)
+        return out
+
+    def render_mesh(self, mesh, t_center, rot=np.zeros(3), tex_img=None, tex_uv=None, camera_pose=None, light_pose=None):
+        """One mesh (any object with .v (V, 3) and .f (F, 3)) turned by `rot` about `t_center` -> (colour (H, W, 3) uint8,
+        depth (H, W) float32) numpy arrays, as the reference returns them.  camera_pose / light_pose, when given, replace
+        the renderer's (and stay, as in the reference)."""
+        if tex_img is not None:
+            raise NotImplementedError("textured rendering is not built (FLAMETex is outside this project's scope)")
+        if camera_pose is not None:
+            self.set_camera_pose(camera_pose)
+        if light_pose is not None:
+            self.set_lighting_pose(light_pose)
+        v = torch.from_numpy(np.ascontiguousarray(np.asarray(mesh.v, np.float32))).to("cuda").unsqueeze(0)
+        color, depth = self.render_vertices(v, np.asarray(mesh.f), t_center=np.asarray(t_center, np.float64).reshape(3),
+                                            rot=np.asarray(rot, np.float64).reshape(3))
+        return color[0].contiguous().cpu().numpy(), depth[0].cpu().numpy()
