@@ -744,6 +744,44 @@ int msmd_render_raster(const float* screen, const float* normals, const int* fac
                        const float* lights, int n_lights, void* rgba, float* depth, int* face_id, int B, int V, int F,
                        int H, int W, float near, float far, unsigned background, msmd_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Audio front end (the reference calls librosa.load(path, sr=16000), inference.py:232): interleaved PCM of any rate and
+ * channel count -> 16 kHz mono fp32, z-normalised per clip.  One call of each entry point
+ * (three launches) for a ragged group of clips that share the input rate and the sample type; every step is deterministic
+ * and a clip's bits do not depend on its group.
+ *
+ * Definition, fs_out = 16000, g = gcd(fs_in, fs_out), L = fs_out / g, M = fs_in / g:
+ *   downmix   x[k] = (sum_c pcm[k, c]) / C: fp32, summed in channel order, one correctly rounded division; int16 samples
+ *             are scaled by 2^-15 first; x is zero outside [0, N);
+ *   filter    s = rho min(1, L / M), rho = 0.9475937167399596, beta = 14.769656459379492, 64 zero crossings:
+ *             h(t) = s sinc(s t) I0(beta sqrt(1 - (s t / 64)^2)) / I0(beta) for |s t| < 64, else 0 (t in input samples,
+ *             sinc(u) = sin(pi u) / (pi u)); no per-phase renormalisation;
+ *   output    y[n] = sum_k x[k] h(n M / L - k), n = 0 .. ceil(N L / M) - 1; all index arithmetic in 64 bits;
+ *   same rate fs_in == fs_out: y = x exactly, no filter (taps = 0, L = M = 1);
+ *   z-norm    (y - mean) / (std + 1e-5), population std, per clip over y; sums and sums of squares in double, one partial
+ *             pair per run of MSMD_AUDIO_RUN outputs, combined in run order; no floating-point atomics.
+ *
+ * desc (n_clips, 5) int64 on the device, per clip: [offset of its first sample in pcm (in samples, not frames), frames N,
+ *   channels C, offset of its first output in out, output length ceil(N L / M)].
+ * bank (taps, L) fp32, taps = 2 ceil(64 / s) + 2, half = taps / 2 - 1: bank[i][r] = h(((r M) mod L) / L - (i - half)), the
+ *   tap-major polyphase table over the OUTPUT's phase order r = n mod L (utils/audio.filter_bank builds it in float64).
+ *   Output n with k0 = n M div L is sum_i x[k0 + i - half] bank[i][n mod L]: four interleaved fma chains over i, added as
+ *   (a0 + a1) + (a2 + a3).
+ * msmd_audio_resample: pcm (pcm_elems samples, int16 if is_int16 else fp32) -> out (out_elems) and partials
+ *   (n_clips, ceil(max_out_len / MSMD_AUDIO_RUN), 2) double = each run's (sum, sum of squares); rows past a clip's last
+ *   run are not written.  max_out_len = the longest output of the group.  The staged span of a run,
+ *   (MSMD_AUDIO_RUN - 1) M div L + 2 + taps samples, must fit 64 KB of LDS (returns 1 otherwise: rates above ~650 kHz).
+ *   Reads and writes the descriptors would place outside pcm_elems / out_elems are dropped.
+ * msmd_audio_znorm: two launches.  One wave per clip adds the clip's partial pairs in run order and leaves stats (n_clips, 2)
+ *   double = (mean, 1 / (std + 1e-5)); then out is normalised in place from stats.  Linear in the clips' lengths.
+ * n_clips <= 65535 per call (the clip is the grid's y index). */
+#define MSMD_AUDIO_RUN 256
+int msmd_audio_resample(const void* pcm, long pcm_elems, int is_int16, const long* desc, int n_clips, long max_out_len,
+                        int L, int M, int taps, const float* bank, float* out, long out_elems, double* partials,
+                        msmd_stream_t stream);
+int msmd_audio_znorm(float* out, long out_elems, const long* desc, int n_clips, long max_out_len, const double* partials,
+                     double* stats, msmd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,7 +14,8 @@ SURVEY.md section 8(f) n3, the callers either side of the sampler:
     encoder pass per distinct padded length; per-clip results equal ``infer_coeffs`` on that clip.
   * ``render_coeffs`` -- coefficients -> FLAME vertices -> images on the device (utils/renderer.MeshRenderer), the step the
     reference script leaves as a comment (inference.py:277-279) and its utils/renderer.py serves.
-The reference script's media IO (librosa, cv2, wav / video writing) stays outside the hot path.
+  * ``load_audio_16k`` -- a `.wav` of any rate and channel count -> 16 kHz mono on the device (utils/audio.py, csrc/audio_io.hip).
+The rest of the reference script's media IO (compressed codecs, cv2, video writing) stays outside the hot path.
 """
 from __future__ import annotations
 
@@ -291,10 +292,15 @@ def build_parser():
     return ap
 
 
-def load_audio_16k(path):
-    """16 kHz mono samples from a decoded file (.npy / pickle of a float array).  Decoding compressed media (the
-    reference calls librosa.load, inference.py:226) is outside the hot path; hand this function the decoded samples."""
+def load_audio_16k(path, device="cuda"):
+    """16 kHz mono float32 samples, un-normalised.  A `.wav` of any rate and channel count is read, downmixed and resampled on
+    the device (utils/audio.load_clips; the reference calls librosa.load(path, sr=16000), inference.py:232); a `.npy` or a
+    pickle holds samples somebody else has already decoded to 16 kHz mono (`device` is not used for those).  The `.wav`
+    suffix is matched in either case (recorders write `.WAV`).  Compressed codecs stay outside."""
     path = str(path)
+    if path.lower().endswith(".wav"):
+        from .utils.audio import load_clips
+        return load_clips([path], device, normalize=False)[0].cpu().numpy()
     if path.endswith(".npy"):
         return np.load(path).astype(np.float32)
     with open(path, "rb") as f:
@@ -314,9 +320,13 @@ def main(argv=None):
     motion_coeff, shape_coef = query_for_motion_coeff(args, args.style_clip_exp_code_path, args.style_clip_head_rot_path,
                                                       device=device)
     shape_coef = shape_coef.unsqueeze(1)
-    audio = load_audio_16k(args.audio_clip)
-    audio = (audio - audio.mean()) / (audio.std() + 1e-5)
-    audio_tensor = torch.from_numpy(audio).float().to(device)
+    if args.audio_clip.lower().endswith(".wav"):
+        from .utils.audio import load_clips
+        audio_tensor = load_clips([args.audio_clip], device, normalize=True)[0]
+    else:
+        audio = load_audio_16k(args.audio_clip)
+        audio = (audio - audio.mean()) / (audio.std() + 1e-5)
+        audio_tensor = torch.from_numpy(audio).float().to(device)
     style_clip = motion_coeff[:, :100, :]
     style_coeff = style_enc.sample(style_clip) if model_args.style_enc_model_style.startswith("vae") else style_enc(style_clip)
     with open(args.coef_dict_path, "rb") as f:

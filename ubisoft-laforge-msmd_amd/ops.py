@@ -1407,3 +1407,78 @@ def render_raster(screen, normals, faces_i32, shade, lights, height, width, near
                                       _p(depth), _p(face_id), B, V, faces_i32.shape[0], H, W, float(near), float(far),
                                       int(background) & 0xffffffff, _stream()), "msmd_render_raster")
     return rgba, depth, face_id
+
+
+# ----------------------------------------------------------------------------- audio front end (csrc/audio_io.hip)
+AUDIO_RUN = 256          # MSMD_AUDIO_RUN: outputs per workgroup of msmd_audio_resample = outputs per partial-sum pair
+AUDIO_MAX_CLIPS = 65535  # clips per call of the audio entry points
+
+
+def _audio_desc(desc, desc_host, pcm_elems=None):
+    """desc (n, 5) int64 on the device and the host array it was copied from.  The kernels index raw pointers from these
+    numbers, so the host copy is checked here: every clip inside the PCM buffer, output ranges disjoint and in order."""
+    _render_arg("desc", desc, torch.int64)
+    h = desc_host.numpy() if torch.is_tensor(desc_host) else desc_host
+    if h.ndim != 2 or h.shape[1] != 5 or h.shape[0] == 0 or str(h.dtype) != "int64" or tuple(desc.shape) != tuple(h.shape):
+        raise TypeError("desc_host must be the (n_clips, 5) int64 array desc was copied from")
+    if h.shape[0] > AUDIO_MAX_CLIPS:
+        raise ValueError(f"{h.shape[0]} clips in one call: the audio entry points take at most {AUDIO_MAX_CLIPS} (the clip is the "
+                         "grid's y index); utils/audio.load_clips splits larger groups")
+    end = 0
+    for in_off, frames, channels, out_off, out_len in h.tolist():
+        if frames <= 0 or channels <= 0 or out_len <= 0 or in_off < 0 or out_off < end:
+            raise ValueError(f"bad clip descriptor {(in_off, frames, channels, out_off, out_len)}")
+        if pcm_elems is not None and in_off + frames * channels > pcm_elems:
+            raise ValueError(f"clip descriptor {(in_off, frames, channels)} runs past the {pcm_elems} PCM samples")
+        end = out_off + out_len
+    return h, end
+
+
+def resample_audio(pcm, desc, desc_host, bank, L, M):
+    """-> (out (sum of output lengths) fp32 16 kHz mono, partials (n_clips, runs, 2) float64): msmd_audio_resample.
+    pcm: 1-D int16 or fp32 interleaved samples of a group of clips of one rate; desc / desc_host (n_clips, 5) int64 = [sample
+    offset in pcm, frames, channels, offset in out, output length ceil(frames L / M)], on the device and on the host;
+    bank (taps, L) fp32 from utils/audio.filter_bank, or None with L = M = 1 (same rate: the downmix itself)."""
+    if not torch.is_tensor(pcm) or not pcm.is_cuda or pcm.dim() != 1 or not pcm.is_contiguous() or \
+            pcm.dtype not in (torch.int16, torch.float32):
+        raise TypeError("pcm must be a contiguous 1-D int16 or float32 CUDA tensor")
+    h, total = _audio_desc(desc, desc_host, pcm.numel())
+    L, M = int(L), int(M)
+    for _, frames, _, _, out_len in h.tolist():
+        if out_len != (frames * L + M - 1) // M:
+            raise ValueError(f"output length {out_len} is not ceil({frames} * {L} / {M})")
+    if bank is None:
+        if (L, M) != (1, 1):
+            raise ValueError("resample_audio: no filter bank is the same-rate bypass, L = M = 1")
+        taps = 0
+    else:
+        _render_arg("bank", bank, torch.float32)
+        if bank.dim() != 2 or bank.shape[1] != L:
+            raise TypeError(f"bank must have shape (taps, {L}), got {tuple(bank.shape)}")
+        taps = bank.shape[0]
+    lib = _lib.load()
+    max_out = int(h[:, 4].max())
+    out = torch.empty(total, device=pcm.device, dtype=torch.float32)
+    partials = torch.empty(h.shape[0], (max_out + AUDIO_RUN - 1) // AUDIO_RUN, 2, device=pcm.device, dtype=torch.float64)
+    code = lib.msmd_audio_resample(_p(pcm), pcm.numel(), int(pcm.dtype == torch.int16), _p(desc), h.shape[0], max_out, L, M,
+                                   taps, _p(bank), _p(out), total, _p(partials), _stream())
+    if code == 1:
+        raise ValueError(f"msmd_audio_resample does not take L = {L}, M = {M}, taps = {taps}: a run's staged span of "
+                         f"{(AUDIO_RUN - 1) * M // L + 2 + taps} samples must fit 64 KB of LDS, taps even and >= 4 (or 0 with L = M = 1)")
+    _lib.check(code, "msmd_audio_resample")
+    return out, partials
+
+
+def znorm_audio(out, desc, desc_host, partials):
+    """In place (y - mean) / (std + 1e-5) per clip, population std: msmd_audio_znorm on what resample_audio returned (one
+    wave per clip adds its partial sums in run order, then the samples are normalised)."""
+    _render_arg("out", out, torch.float32)
+    h, total = _audio_desc(desc, desc_host)
+    max_out = int(h[:, 4].max())
+    _render_arg("partials", partials, torch.float64, (h.shape[0], (max_out + AUDIO_RUN - 1) // AUDIO_RUN, 2))
+    if out.dim() != 1 or out.numel() < total:
+        raise TypeError(f"out must be 1-D with at least {total} samples")
+    stats = torch.empty(h.shape[0], 2, device=out.device, dtype=torch.float64)
+    _lib.check(_lib.load().msmd_audio_znorm(_p(out), out.numel(), _p(desc), h.shape[0], max_out, _p(partials), _p(stats),
+                                            _stream()), "msmd_audio_znorm")
+    return out
