@@ -782,6 +782,51 @@ int msmd_audio_resample(const void* pcm, long pcm_elems, int is_int16, const lon
 int msmd_audio_znorm(float* out, long out_elems, const long* desc, int n_clips, long max_out_len, const double* partials,
                      double* stats, msmd_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Baseline JPEG encoder: frames (B, H, W, 3 | 4) uint8 on the device -> one JFIF file per frame, back to
+ * back in one byte stream.  The reference hands its frames to ffmpeg (utils/media.py); here a Motion-JPEG AVI is written
+ * from these bytes by utils/media.py.  Everything is integer arithmetic: the bytes are a pure function of the pixels.
+ *
+ * Definition (1 <= H, W <= MSMD_JPEG_MAX_SIDE, quality in [1, 100], `>>` arithmetic, `div` floor division):
+ *   input     pixel (y, x) of frame b at frames + b frame_stride + y row_stride + x pixel_stride (bytes), R, G, B in that
+ *             order; pixel_stride 3 or 4, a fourth byte is ignored.  With pixel_stride 4 and every stride and the base a
+ *             multiple of 4 the kernel loads 4 bytes per pixel: the fourth byte of the last pixel must be readable.
+ *   padding   to multiples of 8 by repeating the last column and row; SOF0 carries the true H and W.
+ *   colour    Y  = (19595 R + 38470 G + 7471 B + 32768) >> 16
+ *             Cb = clamp(((-11059 R - 21709 G + 32768 B + 32768) >> 16) + 128, 0, 255)
+ *             Cr = clamp(((32768 R - 27439 G - 5329 B + 32768) >> 16) + 128, 0, 255);  4:4:4, an MCU is (Y, Cb, Cr) of 8 x 8.
+ *   DCT       x = sample - 128; M[k][n] = rint(2^15 c_k cos((2 n + 1) k pi / 16)), c_0 = 1 / (2 sqrt 2), c_k = 1 / 2;
+ *             C = M X M^T exactly, no intermediate rounding: rows in int32 (< 2^24), columns in int64 (< 2^41); C is the
+ *             DCT scaled by 2^30 and within 0.042 (< 1/16) of the real-valued DCT for every input.
+ *   quantiser Q = clamp((base s + 50) div 100, 1, 255), s = 5000 div q below 50, else 200 - 2 q, base = T.81 Annex K.1;
+ *             value = sign(C) ((2 |C| + d) div (2 d)), d = Q 2^30 (round half away from zero); AC clamped to +-1023.
+ *   entropy   zig-zag order; Annex K.3 typical Huffman tables; DC difference per component (clamped to +-2047, which the
+ *             ranges above never reach); restart interval MSMD_JPEG_RESTART_INTERVAL MCUs in raster order whatever
+ *             the width: predictors reset, the interval's last byte filled with 1-bits, 0xFF -> 0xFF 0x00 inside it, RSTn
+ *             (n = interval index mod 8) between intervals.
+ *   file      header (SOI, APP0 JFIF 1.01 density 1:1, DQT x 2, SOF0, DHT x 4, DRI, SOS: the same bytes for every frame of
+ *             a call, built by the caller) + scan + EOI.
+ *
+ * msmd_jpeg_intervals: ceil(ceil(H/8) ceil(W/8) / 32), the intervals of one frame (host arithmetic only; -1 if out of range).
+ * msmd_jpeg_coefficients, one workgroup per (frame, interval): coef (B, n_int, 32, 3, 64) int16, quantised, zig-zag order;
+ *   the MCUs of the last interval past the frame's last MCU are zeros.
+ * msmd_jpeg_measure, three launches: the entropy coder run for its lengths only, then two scans.  interval_len (B, n_int)
+ *   int32 = stuffed bytes of each interval; interval_rel (B, n_int) int64 = offset of the interval in its frame's file;
+ *   frame_size (B) int64; offsets (B + 1) int64 = where each file starts in the stream, offsets[B] = the stream's length
+ *   (the one number the host has to read before it can allocate `out`).
+ * msmd_jpeg_write, one launch: the entropy coder again, each interval written at offsets[b] + interval_rel[b, i] with its
+ *   RSTn / EOI behind it, and `header` (header_len bytes on the device) at each file's start.  Bytes that would fall outside
+ *   [0, out_bytes) are dropped. */
+#define MSMD_JPEG_RESTART_INTERVAL 32
+#define MSMD_JPEG_MAX_SIDE 16384
+int msmd_jpeg_intervals(int H, int W);
+int msmd_jpeg_coefficients(const void* frames, long frame_stride, long row_stride, int pixel_stride, int B, int H, int W,
+                           int quality, short* coef, msmd_stream_t stream);
+int msmd_jpeg_measure(const short* coef, int B, int H, int W, int header_len, int* interval_len, long* interval_rel,
+                      long* frame_size, long* offsets, msmd_stream_t stream);
+int msmd_jpeg_write(const short* coef, int B, int H, int W, const void* header, int header_len, const long* interval_rel,
+                    const long* offsets, void* out, long out_bytes, msmd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

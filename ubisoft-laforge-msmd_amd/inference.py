@@ -15,7 +15,9 @@ SURVEY.md section 8(f) n3, the callers either side of the sampler:
   * ``render_coeffs`` -- coefficients -> FLAME vertices -> images on the device (utils/renderer.MeshRenderer), the step the
     reference script leaves as a comment (inference.py:277-279) and its utils/renderer.py serves.
   * ``load_audio_16k`` -- a `.wav` of any rate and channel count -> 16 kHz mono on the device (utils/audio.py, csrc/audio_io.hip).
-The rest of the reference script's media IO (compressed codecs, cv2, video writing) stays outside the hot path.
+  * ``--video`` -- the frames, JPEG-compressed on the device chunk by chunk (csrc/jpeg.hip), and the input WAV as one
+    Motion-JPEG AVI (utils/media.py), where the reference calls ffmpeg (utils/media.py:combine_frames_and_audio).
+The rest of the reference script's media IO (compressed audio codecs, cv2, H.264) stays outside.
 """
 from __future__ import annotations
 
@@ -177,6 +179,20 @@ def denormalize_coeffs(overall_coef, coef_stats):
 
 
 @torch.no_grad()
+def render_coeffs_chunks(coef, shape_coef, flame, coef_stats, renderer, chunk=512, *, with_global_pose=True):
+    """`render_coeffs` as a generator: yields the frames of `chunk` coefficients at a time, (n, H, W, 3) uint8 views of the
+    renderer's RGBA buffer, so a consumer that compresses each chunk keeps one chunk of raw pixels alive."""
+    coef = coef.reshape(-1, coef.shape[-1]).float()
+    if coef.shape[-1] == 53:
+        coef = torch.cat([coef, torch.zeros_like(coef[:, :1])], dim=-1)
+    shape = shape_coef.reshape(-1, shape_coef.shape[-1]).float().expand(coef.shape[0], -1)
+    for i in range(0, coef.shape[0], chunk):
+        coef_dict = get_coef_dict(coef[i:i + chunk], shape[i:i + chunk], coef_stats, with_global_pose=with_global_pose)
+        verts = coef_dict_to_vertices(coef_dict, flame, flame_batch_size=chunk)
+        yield renderer.render_vertices(verts, flame.faces_tensor)[0]
+
+
+@torch.no_grad()
 def render_coeffs(coef, shape_coef, flame, coef_stats, renderer, chunk=512, *, with_global_pose=True):
     """Motion coefficients (T, C) or (1, T, C) -> frames (T, H, W, 3) uint8 on the device: get_coef_dict -> coef_dict_to_vertices
     -> renderer.render_vertices on FLAME's faces, `chunk` frames at a time (one chunk's vertices are the only intermediate
@@ -184,16 +200,8 @@ def render_coeffs(coef, shape_coef, flame, coef_stats, renderer, chunk=512, *, w
     (expression + head rotation, what `denormalize_coeffs` returns side by side) gets a closed jaw.  coef_stats: None for
     coefficients in the data's units, or get_coef_dict's denorm_stats (`exp` / `pose` / `shape` means and stds).
     shape_coef: (1, 100) or (T, 100)."""
-    coef = coef.reshape(-1, coef.shape[-1]).float()
-    if coef.shape[-1] == 53:
-        coef = torch.cat([coef, torch.zeros_like(coef[:, :1])], dim=-1)
-    shape = shape_coef.reshape(-1, shape_coef.shape[-1]).float().expand(coef.shape[0], -1)
-    frames = []
-    for i in range(0, coef.shape[0], chunk):
-        coef_dict = get_coef_dict(coef[i:i + chunk], shape[i:i + chunk], coef_stats, with_global_pose=with_global_pose)
-        verts = coef_dict_to_vertices(coef_dict, flame, flame_batch_size=chunk)
-        frames.append(renderer.render_vertices(verts, flame.faces_tensor)[0])
-    return torch.cat(frames, dim=0)
+    return torch.cat(list(render_coeffs_chunks(coef, shape_coef, flame, coef_stats, renderer, chunk,
+                                               with_global_pose=with_global_pose)), dim=0)
 
 
 # ----------------------------------------------------------------------------- many clips per denoise step
@@ -289,7 +297,22 @@ def build_parser():
     ap.add_argument("--render_size", type=int, default=0, help="side of the square frames rendered from the result (0: none)")
     ap.add_argument("--flame_model_path", type=str, default=None, help="FLAME generic_model.pkl (with --render_size)")
     ap.add_argument("--flame_lmk_embedding_path", type=str, default=None, help="FLAME landmark embedding (with --render_size)")
+    # video (the reference pipes frames and audio through ffmpeg; here a Motion-JPEG AVI is written, utils/media.py)
+    ap.add_argument("--video", action="store_true", help="write video_<clip>_seed_<s>.avi instead of the raw frames "
+                                                         "(needs --render_size > 0)")
+    ap.add_argument("--video_quality", type=int, default=90, help="JPEG quality of the video's frames, 1 .. 100")
     return ap
+
+
+def parse_args(argv=None):
+    """build_parser().parse_args with the checks that span flags: --video needs --render_size > 0 and a quality in [1, 100]."""
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    if args.video and args.render_size <= 0:
+        ap.error("--video needs --render_size > 0: there are no frames to encode")
+    if not 1 <= args.video_quality <= 100:
+        ap.error(f"--video_quality {args.video_quality} is outside [1, 100]")
+    return args
 
 
 def load_audio_16k(path, device="cuda"):
@@ -312,9 +335,11 @@ def main(argv=None):
     the audio, sample the style code, run infer_coeffs per repetition seed, de-normalise and write the two pickles
     (`overall_exp_code_*`, `overall_head_rot_*`) under <output_dir>/<model>_iter_<iter>/temp/.  With --render_size N > 0 the
     coefficients are also decoded by FLAME and rendered on the device (render_coeffs), and `frames_<clip>_seed_<s>.npy`
-    ((T, N, N, 3) uint8) is written beside them; encoding a video from the frames stays outside."""
+    ((T, N, N, 3) uint8) is written beside them.  With --video as well, `video_<clip>_seed_<s>.avi` is written in its place: the
+    frames are JPEG-compressed on the device chunk by chunk as they are rendered (so one chunk of raw pixels is alive at a
+    time), at model_args.fps, with --audio_clip as the sound track when it is a `.wav` and silent otherwise."""
     import os
-    args = build_parser().parse_args(argv)
+    args = parse_args(argv)
     device = torch.device("cuda")
     model, style_enc, model_args = load_model(args.model_root, args.model_name, args.model_iter, device)
     motion_coeff, shape_coef = query_for_motion_coeff(args, args.style_clip_exp_code_path, args.style_clip_head_rot_path,
@@ -360,7 +385,20 @@ def main(argv=None):
             with open(out, "wb") as f:
                 pkl.dump(val.cpu().numpy(), f)
             written.append(out)
-        if renderer is not None:
+        if renderer is not None and args.video:
+            from .utils import media
+            jpegs = []
+            for part in render_coeffs_chunks(torch.cat([exp_code, head_rot], dim=-1), shape_coef.reshape(1, -1), flame, None,
+                                             renderer, chunk=256):
+                jpegs += media.encode_jpeg(part, args.video_quality)
+            sound = None
+            if args.audio_clip.lower().endswith(".wav"):
+                from .utils.audio import read_wav
+                sound = read_wav(args.audio_clip)
+            out = os.path.join(temp, f"video_{clip}_seed_{seed}.avi")
+            media.write_avi(out, jpegs, model_args.fps, (args.render_size, args.render_size), sound)
+            written.append(out)
+        elif renderer is not None:
             frames = render_coeffs(torch.cat([exp_code, head_rot], dim=-1), shape_coef.reshape(1, -1), flame, None, renderer)
             out = os.path.join(temp, f"frames_{clip}_seed_{seed}.npy")
             np.save(out, frames.cpu().numpy())

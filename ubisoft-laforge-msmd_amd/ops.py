@@ -1409,8 +1409,140 @@ def render_raster(screen, normals, faces_i32, shade, lights, height, width, near
     return rgba, depth, face_id
 
 
+# ----------------------------------------------------------------------------- JPEG encoder (csrc/jpeg.hip)
+JPEG_RESTART_INTERVAL = 32      # MSMD_JPEG_RESTART_INTERVAL
+JPEG_MAX_SIDE = 16384           # MSMD_JPEG_MAX_SIDE
+# ITU-T T.81 Annex K.1 quantisation tables (natural order) and Annex K.3 typical Huffman tables (BITS, HUFFVAL): the header's
+# copy; the kernels carry their own in csrc/jpeg.hip and tests/test_video_gpu.py holds the two together through the decoder.
+JPEG_BASE_LUMA = (
+    16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+    18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112,
+    100, 103, 99)
+JPEG_BASE_CHROMA = (
+    17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99,
+    99) + (99,) * 32
+JPEG_ZIGZAG = (0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21,
+               28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54,
+               47, 55, 62, 63)       # zig-zag position -> natural index
+_JPEG_AC_LUMA_VALS = bytes.fromhex(
+    "01020300041105122131410613516107227114328191a1082342b1c11552d1f02433627282090a161718191a25262728292a3435363738393a4344"
+    "45464748494a535455565758595a636465666768696a737475767778797a838485868788898a92939495969798999aa2a3a4a5a6a7a8a9aab2b3b4"
+    "b5b6b7b8b9bac2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae1e2e3e4e5e6e7e8e9eaf1f2f3f4f5f6f7f8f9fa")
+_JPEG_AC_CHROMA_VALS = bytes.fromhex(
+    "000102031104052131061241510761711322328108144291a1b1c109233352f0156272d10a162434e125f11718191a262728292a35363738393a43"
+    "4445464748494a535455565758595a636465666768696a737475767778797a82838485868788898a92939495969798999aa2a3a4a5a6a7a8a9aab2"
+    "b3b4b5b6b7b8b9bac2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae2e3e4e5e6e7e8e9eaf2f3f4f5f6f7f8f9fa")
+# (table class, table id, BITS, HUFFVAL) in the order the DHT segments are written
+JPEG_HUFFMAN = (
+    (0, 0, bytes((0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0)), bytes(range(12))),
+    (1, 0, bytes((0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d)), _JPEG_AC_LUMA_VALS),
+    (0, 1, bytes((0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0)), bytes(range(12))),
+    (1, 1, bytes((0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77)), _JPEG_AC_CHROMA_VALS),
+)
+
+
+def jpeg_quant_table(base, quality):
+    """The libjpeg quality rule on an Annex K base table -> 64 values in natural order, each in [1, 255]."""
+    q = int(quality)
+    if q != quality or not 1 <= q <= 100:
+        raise ValueError(f"JPEG quality must be an integer in [1, 100], got {quality!r}")
+    s = 5000 // q if q < 50 else 200 - 2 * q
+    return tuple(min(max((b * s + 50) // 100, 1), 255) for b in base)
+
+
+def jpeg_header(height, width, quality):
+    """SOI .. SOS of the files msmd_jpeg_write produces: the same bytes for every frame of a call."""
+    import struct
+    H, W = int(height), int(width)
+    if not (1 <= H <= JPEG_MAX_SIDE and 1 <= W <= JPEG_MAX_SIDE):
+        raise ValueError(f"JPEG frame size {H} x {W} is outside [1, {JPEG_MAX_SIDE}]")
+
+    def seg(marker, body):
+        return bytes((0xFF, marker)) + struct.pack(">H", len(body) + 2) + body
+    out = [b"\xff\xd8", seg(0xE0, b"JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00")]
+    for tid, base in ((0, JPEG_BASE_LUMA), (1, JPEG_BASE_CHROMA)):
+        t = jpeg_quant_table(base, quality)
+        out.append(seg(0xDB, bytes((tid,)) + bytes(t[n] for n in JPEG_ZIGZAG)))
+    out.append(seg(0xC0, struct.pack(">BHHB", 8, H, W, 3) + bytes((1, 0x11, 0, 2, 0x11, 1, 3, 0x11, 1))))
+    for cls, tid, bits, vals in JPEG_HUFFMAN:
+        out.append(seg(0xC4, bytes((cls << 4 | tid,)) + bits + vals))
+    out.append(seg(0xDD, struct.pack(">H", JPEG_RESTART_INTERVAL)))
+    out.append(seg(0xDA, bytes((3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0))))
+    return b"".join(out)
+
+
+def _jpeg_frames(frames, quality):
+    """Checks of the encoder's input -> (B, H, W, frame stride, row stride, pixel stride).  The kernels index raw pointers
+    from these numbers."""
+    if not torch.is_tensor(frames) or frames.dtype != torch.uint8:
+        raise TypeError("frames must be a uint8 tensor")
+    if not frames.is_cuda:
+        raise TypeError("frames must be on the MI355X (cuda) device; there is no CPU encoder")
+    if frames.dim() != 4 or frames.shape[3] not in (3, 4):
+        raise TypeError(f"frames must have shape (B, H, W, 3 | 4), got {tuple(frames.shape)}")
+    jpeg_quant_table(JPEG_BASE_LUMA, quality)
+    B, H, W, C = frames.shape
+    if B < 1 or not (1 <= H <= JPEG_MAX_SIDE and 1 <= W <= JPEG_MAX_SIDE):
+        raise ValueError(f"frames of shape {tuple(frames.shape)}: B >= 1 and 1 <= H, W <= {JPEG_MAX_SIDE} are required")
+    sb, sh, sw, sc = frames.stride()
+    if sc != 1 or sw not in (3, 4) or sw < C or sh < W * sw - (sw - C) or (B > 1 and sb < H * sh - (sh - W * sw)) :
+        raise TypeError(f"frames with strides {frames.stride()}: channels must be adjacent bytes, pixels 3 or 4 bytes apart, "
+                        "rows and frames must not overlap (call .contiguous())")
+    if sw == 4 and C == 3:
+        # the (B, H, W, 3) view of an RGBA buffer: the kernel reads whole 4-byte pixels, so the last alpha byte must exist
+        last = frames.storage_offset() + (B - 1) * sb + (H - 1) * sh + (W - 1) * sw + 4
+        if last > frames.untyped_storage().nbytes():
+            raise TypeError("frames is a 3-channel view with 4-byte pixels whose storage ends before the last pixel's 4th byte")
+    return B, H, W, sb, sh, sw
+
+
+def jpeg_coefficients(frames, quality=90):
+    """-> (B, n_mcu, 3, 64) int16: the quantised DCT coefficients of every MCU (Y, Cb, Cr) in zig-zag order, MCUs in raster
+    order over the frame padded to multiples of 8: msmd_jpeg_coefficients."""
+    B, H, W, sb, sh, sw = _jpeg_frames(frames, quality)
+    lib = _lib.load()
+    n_int = lib.msmd_jpeg_intervals(H, W)
+    coef = torch.empty(B, n_int * JPEG_RESTART_INTERVAL, 3, 64, device=frames.device, dtype=torch.int16)
+    _lib.check(lib.msmd_jpeg_coefficients(_p(frames), sb, sh, sw, B, H, W, int(quality), _p(coef), _stream()), "msmd_jpeg_coefficients")
+    return coef[:, :((H + 7) // 8) * ((W + 7) // 8)]
+
+
+_JPEG_HEADERS = {}
+
+
+def jpeg_encode(frames, quality=90):
+    """frames (B, H, W, 3 | 4) uint8 on the device (alpha ignored; a row stride larger than the row and the renderer's
+    (B, H, W, 3) view of its RGBA buffer are taken as they are) -> (stream (n,) uint8, offsets (B + 1,) int64), both on the
+    device: frame b is the JFIF file stream[offsets[b]:offsets[b + 1]].  Baseline, 4:4:4, Annex K tables, restart interval 32;
+    the bytes are a pure function of the pixels.  Five launches and one host read (the stream's length)."""
+    B, H, W, sb, sh, sw = _jpeg_frames(frames, quality)
+    lib = _lib.load()
+    dev = frames.device
+    key = (H, W, int(quality), str(dev))
+    header = _JPEG_HEADERS.get(key)
+    if header is None:
+        if len(_JPEG_HEADERS) >= 16:
+            _JPEG_HEADERS.pop(next(iter(_JPEG_HEADERS)))
+        header = _JPEG_HEADERS[key] = torch.frombuffer(bytearray(jpeg_header(H, W, quality)), dtype=torch.uint8).to(dev)
+    n_int = lib.msmd_jpeg_intervals(H, W)
+    coef = torch.empty(B * n_int * JPEG_RESTART_INTERVAL * 3 * 64, device=dev, dtype=torch.int16)
+    interval_len = torch.empty(B * n_int, device=dev, dtype=torch.int32)
+    interval_rel = torch.empty(B * n_int, device=dev, dtype=torch.int64)
+    frame_size = torch.empty(B, device=dev, dtype=torch.int64)
+    offsets = torch.empty(B + 1, device=dev, dtype=torch.int64)
+    st = _stream()
+    _lib.check(lib.msmd_jpeg_coefficients(_p(frames), sb, sh, sw, B, H, W, int(quality), _p(coef), st), "msmd_jpeg_coefficients")
+    _lib.check(lib.msmd_jpeg_measure(_p(coef), B, H, W, header.numel(), _p(interval_len), _p(interval_rel), _p(frame_size),
+                                     _p(offsets), st), "msmd_jpeg_measure")
+    total = int(offsets[B].item())                      # the one device-to-host read: the output cannot be allocated without it
+    out = torch.empty(total, device=dev, dtype=torch.uint8)
+    _lib.check(lib.msmd_jpeg_write(_p(coef), B, H, W, _p(header), header.numel(), _p(interval_rel), _p(offsets), _p(out), total,
+                                   st), "msmd_jpeg_write")
+    return out, offsets
+
+
 # ----------------------------------------------------------------------------- audio front end (csrc/audio_io.hip)
-AUDIO_RUN = 256          # MSMD_AUDIO_RUN: outputs per workgroup of msmd_audio_resample = outputs per partial-sum pair
+AUDIO_RUN = 256         # MSMD_AUDIO_RUN: outputs per workgroup of msmd_audio_resample = outputs per partial-sum pair
 AUDIO_MAX_CLIPS = 65535  # clips per call of the audio entry points
 
 
