@@ -745,6 +745,44 @@ int msmd_render_raster(const float* screen, const float* normals, const int* fac
                        int H, int W, float near, float far, unsigned background, msmd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Textured shading (the reference's render_mesh(tex_img, tex_uv)).  A deferred, pixel-parallel pass behind
+ * msmd_render_raster: it reads that launch's face_id buffer and overwrites rgba at the covered pixels.  The conventions are
+ * the ordinary OpenGL / OBJ ones (GL_REPEAT, GL_LINEAR magnification, GL_LINEAR_MIPMAP_LINEAR minification, v up, no sRGB
+ * conversion), stated here because they are this project's: there is no pixel parity with pyrender.
+ *
+ * Pyramid of a (Ht, Wt, 3 | 4) uint8 image (alpha ignored), 1 <= Ht, Wt <= 4096, any size: L = 1 + floor(log2(max(Ht, Wt)))
+ *   levels, level l + 1 of size max(1, H_l >> 1) x max(1, W_l >> 1), stored one after the other as fp32 RGBA texels (16
+ *   bytes, values 0 .. 255, the fourth component 0).  Level 0 is the image's bytes converted; texel (y, x) of level l + 1 is
+ *   ((a + b) + (c + d)) * 0.25f in fp32 with a = (2y, 2x), b = (2y, min(2x + 1, W_l - 1)), c = (min(2y + 1, H_l - 1), 2x),
+ *   d = (min(2y + 1, H_l - 1), min(2x + 1, W_l - 1)) of level l as stored; a trailing odd row or column is not read.
+ * msmd_texture_texels: host only; the pyramid's texel count, or -1 outside the limits.
+ * msmd_texture_mips: img (Ht, Wt, channels) uint8, channels 3 or 4 -> pyramid (msmd_texture_texels(Ht, Wt), 4) fp32; one
+ *   launch per level.
+ * msmd_render_shade_textured, a wave per 64-pixel row segment: at every pixel with 0 <= face_id < F
+ *   - corner coordinates (u_k, v_k) = vt[ft[f, k]], vt (Nt, 2) fp32, ft (F, 3) int32 per-corner indices in the face order of
+ *     `faces`, swapped with the vertices where face_setup orients the face; an index outside [0, Nt) gives (0, 0);
+ *   - u, v interpolated unwrapped with the shading pass's perspective-correct weights p_k = w_k q_k / iz;
+ *   - level of detail, analytic per pixel: with D = sum w_k q_k, N_u = sum w_k q_k u_k and the exact per-pixel steps
+ *     dw_k/dj = a_k / A, dw_k/di = c_k / A (integer edge steps over the doubled area), du/dj = (dN_u/dj - u dD/dj) / D and
+ *     likewise for v and i; rho_j^2 = (Wt du/dj)^2 + (Ht dv/dj)^2, lambda = 0.5 log2(max(rho_j^2, rho_i^2)) clamped to
+ *     [0, L - 1]; a lambda that is not finite (or has a rho^2 that is not) is 0;
+ *   - level l at (u, v): a u or v that is not finite is 0; U = u - floor(u), x = U W_l - 0.5, y = (1 - (v - floor(v))) H_l -
+ *     0.5 (row 0 is the top of the image, v = 0 its bottom edge), x0 = floor(x), fx = x - x0, columns x0 mod W_l and
+ *     (x0 + 1) mod W_l (mathematical modulo), rows likewise, c = (1 - fy)((1 - fx) t00 + fx t10) + fy((1 - fx) t01 + fx t11);
+ *   - trilinear: l0 = min(floor(lambda), L - 1), l1 = min(l0 + 1, L - 1), f = lambda - l0, T = (1 - f) c_l0 + f c_l1;
+ *   - colour = clamp((T / 255)(ambient + diffuse), 0, 1), floor(255 c + 0.5), alpha 255: msmd_render_raster's lighting
+ *     (the same device function) with the base colour replaced by the texel;
+ *   - uvl (B, H, W, 3) fp32 or NULL: (u, v, lambda) as sampled (u and v after the not-finite rule, unwrapped; lambda
+ *     clamped), zeros where face_id is outside [0, F).
+ *   Depth and face_id are not written and pixels outside the mesh are left as they are. */
+long msmd_texture_texels(int Ht, int Wt);
+int msmd_texture_mips(const void* img, int Ht, int Wt, int channels, float* pyramid, msmd_stream_t stream);
+int msmd_render_shade_textured(const float* screen, const float* normals, const int* faces, const float* vt, const int* ft,
+                               const float* pyramid, int Ht, int Wt, const float* shade, const float* lights,
+                               int n_lights, const int* face_id, void* rgba, float* uvl, int B, int V, int F, int Nt,
+                               int H, int W, float near, msmd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Audio front end (the reference calls librosa.load(path, sr=16000), inference.py:232): interleaved PCM of any rate and
  * channel count -> 16 kHz mono fp32, z-normalised per clip.  One call of each entry point
  * (three launches) for a ragged group of clips that share the input rate and the sample type; every step is deterministic

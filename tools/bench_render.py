@@ -6,8 +6,17 @@ the bytes/s of what the launch stores (vertex stage: screen + normals; raster st
 frames/s.  Needs an MI355X; there is no CPU path.
 
     python tools/bench_render.py [--out profiles/r08_render.txt]
+
+--texture N adds the textured shading pass with an N x N noise texture in longitude / latitude coordinates:
+per size, the untextured raster launch, the textured pass alone and the two together, timed in turn within every round (so
+the three share the clock state), per frame, and the textured pass with a 1 x 1 texture: the set-up, lighting and stores that
+stage (C) of the raster launch also does for every covered pixel, which is wasted work under a texture.  --parent_lib PATH names another build of the library (the parent commit's):
+its msmd_render_raster is timed in the same rounds, which is the only untextured time of the parent there is to compare with.
+
+    python tools/bench_render.py --texture 1024 [--parent_lib /path/to/parent/libmsmd_hip.so] [--out profiles/r11_texture.txt]
 """
 import argparse
+import ctypes
 import os
 import sys
 
@@ -33,10 +42,80 @@ def timed(fn, reps=9, warmup=3):
     return float(np.median(ms)), float(min(ms)), float(max(ms))
 
 
+def timed_in_turn(fns, reps=9, warmup=3):
+    """Medians (ms) of several launches timed one after the other within every round."""
+    for _ in range(warmup):
+        for fn in fns:
+            fn()
+    ms = [[] for _ in fns]
+    for _ in range(reps):
+        for k, fn in enumerate(fns):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            ms[k].append(a.elapsed_time(b))
+    return [(float(np.median(m)), float(min(m)), float(max(m))) for m in ms]
+
+
+def bench_texture(args, dev, v, f, verts, rot, tc, lines):
+    from msmd_amd import _lib
+    B, V = verts.shape[:2]
+    N = args.texture
+    img = torch.from_numpy(np.floor(synth.uniform01("bench_render/texture", N * N * 3) * np.float32(256)).astype(np.uint8)
+                           .reshape(N, N, 3)).to(dev)
+    pyramid = ops.texture_pyramid(img)
+    pyramid1 = ops.texture_pyramid(img[:1, :1].contiguous())      # one texel: the pass without its texture traffic
+    vt = np.stack([np.arctan2(v[:, 0], v[:, 2]) / (2 * np.pi) + 0.5, np.arcsin(np.clip(v[:, 1] / 0.09, -1, 1)) / np.pi + 0.5], axis=1)
+    vt_d, ft_d = torch.from_numpy(vt.astype(np.float32)).to(dev), torch.from_numpy(f).to(dev)
+    parent = None
+    if args.parent_lib:
+        _lib.load()
+        parent = ctypes.CDLL(args.parent_lib).msmd_render_raster
+        parent.argtypes, parent.restype = _lib.PROTOS["msmd_render_raster"], ctypes.c_int
+    for size in (512, 256):
+        r = MeshRenderer((size, size))
+        faces, off, ids = r._tables(torch.from_numpy(f).to(dev), V, dev)
+        view, shade, lights = r._device_consts(dev)
+        near, far = r.frustum["near"], r.frustum["far"]
+        screen, normals = ops.render_vertices(verts, faces, off, ids, view, 1.0 / np.tan(r.fov / 2.0), size, size, tc, rot)
+        rgba, depth, fid = ops.render_raster(screen, normals, faces, shade, lights, size, size, near, far, 0xffffffff, want_face_id=True)
+        raster = lambda: ops.render_raster(screen, normals, faces, shade, lights, size, size, near, far, 0xffffffff, want_face_id=True)
+        shade_t = lambda: ops.render_shade_textured(screen, normals, faces, vt_d, ft_d, pyramid, N, N, shade, lights, fid, rgba, near)
+        both = lambda: (raster(), shade_t())
+        shade_1 = lambda: ops.render_shade_textured(screen, normals, faces, vt_d, ft_d, pyramid1, 1, 1, shade, lights, fid, rgba, near)
+        fns, names = [raster, shade_t, both], ["msmd_render_raster (untextured, with face ids)", "msmd_render_shade_textured",
+                                               "raster + textured pass"]
+        if parent is not None:
+            stream = torch.cuda.current_stream().cuda_stream
+            fns.append(lambda: parent(screen.data_ptr(), normals.data_ptr(), faces.data_ptr(), shade.data_ptr(), lights.data_ptr(),
+                                      lights.shape[0], rgba.data_ptr(), depth.data_ptr(), fid.data_ptr(), B, V, faces.shape[0], size, size,
+                                      near, far, 0xffffffff, stream))
+            names.append("parent build's msmd_render_raster")
+        uvl = ops.render_shade_textured(screen, normals, faces, vt_d, ft_d, pyramid, N, N, shade, lights, fid, rgba, near, want_uvl=True)
+        cov = fid >= 0
+        lam = uvl[..., 2][cov]
+        fns.append(shade_1)
+        names.append("msmd_render_shade_textured with a 1 x 1 texture (set-up, lighting and stores: what stage (C) of the raster "
+                     "launch repeats)")
+        res = timed_in_turn(fns)
+        for name, (med, lo, hi) in zip(names, res):
+            lines.append(f"{name} B={B} {size}x{size} texture {N}x{N}: median {med:.4f} ms (min {lo:.4f}, max {hi:.4f}, 9 rounds in "
+                         f"turn), {med / B * 1e3:.2f} us / frame")
+        lines.append(f"textured / untextured per frame {size}x{size}: {res[2][0] / res[0][0]:.3f}"
+                     + (f"; against the parent build's untextured raster: {res[2][0] / res[3][0]:.3f} (this build's untextured raster / "
+                        f"the parent's: {res[0][0] / res[3][0]:.3f})" if parent is not None else "")
+                     + f"; {100 * float(cov.float().mean()):.1f} % of the pixels covered, mean level of detail {float(lam.mean()):.2f}; the "
+                     f"untextured shading of those pixels inside the raster launch is wasted work under a texture")
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=100)
     ap.add_argument("--out", type=str, default=None)
+    ap.add_argument("--texture", type=int, default=0, help="side of a noise texture: time the textured pass too (0: do not)")
+    ap.add_argument("--parent_lib", type=str, default=None, help="another build of the library whose raster launch is timed in turn")
     args = ap.parse_args(argv)
     assert torch.cuda.is_available(), "bench_render needs an MI355X"
     dev = torch.device("cuda:0")
@@ -63,6 +142,8 @@ def main(argv=None):
             lines.append(f"{name} B={B} V={V} F={Fc} {size}x{size}: median {med:.4f} ms (min {lo:.4f}, max {hi:.4f}, 9 runs), "
                          f"{B / med * 1e3:.0f} frames/s, {nbytes / med * 1e3 / 1e9:.2f} GB/s stored")
         lines.append(f"both launches {size}x{size}: {B / (tv[0] + tr[0]) * 1e3:.0f} frames/s, {100 * covered:.1f} % of the pixels covered")
+    if args.texture > 0:
+        bench_texture(args, dev, v, f, verts, rot, tc, lines)
     text = "\n".join(lines)
     print(text)
     if args.out:

@@ -1,6 +1,8 @@
 // Compute mesh renderer: vertex normals + camera, then a z-buffered tile rasteriser with Lambert shading.
 // An Instinct card has no graphics pipe; this turns the (B, V, 3) vertices msmd_lbs_skin_v2 leaves on the device into images
 // there.  Two launches per batch of frames, no host synchronisation, no global atomics, bit-identical from run to run.
+// A texture adds a mip pyramid (built once per image) and a third, deferred launch that shades the covered pixels from it
+// (DESIGN.md 5.14).
 #include "common.h"
 
 namespace {
@@ -156,6 +158,20 @@ __device__ __forceinline__ float inv_depth(const FaceSetup& s, long e0, long e1,
   return fmaf(w2, s.q2, fmaf(w1, s.q1, __fmul_rn(w0, s.q0)));
 }
 
+// (1 / pi) sum_k I_k max(0, n . l_k) with n the perspective-correct interpolated vertex normal, renormalised: the lighting of
+// the untextured and the textured pass, from ONE routine
+__device__ __forceinline__ float lambert_diffuse(const float* __restrict__ nrm, const FaceSetup& s, float p0, float p1, float p2,
+                                                 const float* __restrict__ lights, int n_lights) {
+  const F3 n0 = *(const F3*)(nrm + (long)s.i0 * 3), n1 = *(const F3*)(nrm + (long)s.i1 * 3), n2 = *(const F3*)(nrm + (long)s.i2 * 3);
+  const F3 n = unit_or_z(F3{p0 * n0.x + p1 * n1.x + p2 * n2.x, p0 * n0.y + p1 * n1.y + p2 * n2.y, p0 * n0.z + p1 * n1.z + p2 * n2.z});
+  float diff = 0.f;
+  for (int k = 0; k < n_lights; ++k) {
+    const float ndl = n.x * lights[4 * k] + n.y * lights[4 * k + 1] + n.z * lights[4 * k + 2];
+    diff += lights[4 * k + 3] * fmaxf(0.f, ndl);
+  }
+  return diff * 0.318309886183790672f;
+}
+
 __device__ __forceinline__ void fragment(const FaceSetup& s, int f, int j, int i, long e0, long e1, long e2, long b0, long b1,
                                          long b2, float near, float far, int tx0, int ty0, unsigned long long* s_key) {
   if ((e0 + b0) < 0 || (e1 + b1) < 0 || (e2 + b2) < 0) return;
@@ -279,14 +295,7 @@ __global__ __launch_bounds__(RT_THREADS) void render_raster_kernel(const float* 
     const float iz = inv_depth(s, e0, e1, e2, w0, w1, w2);
     // perspective-correct weights w_k q_k / (sum), then the interpolated normal
     const float p0 = w0 * s.q0 / iz, p1 = w1 * s.q1 / iz, p2 = w2 * s.q2 / iz;
-    const F3 n0 = *(const F3*)(nrm + (long)s.i0 * 3), n1 = *(const F3*)(nrm + (long)s.i1 * 3), n2 = *(const F3*)(nrm + (long)s.i2 * 3);
-    const F3 n = unit_or_z(F3{p0 * n0.x + p1 * n1.x + p2 * n2.x, p0 * n0.y + p1 * n1.y + p2 * n2.y, p0 * n0.z + p1 * n1.z + p2 * n2.z});
-    float diff = 0.f;
-    for (int k = 0; k < n_lights; ++k) {
-      const float ndl = n.x * lights[4 * k] + n.y * lights[4 * k + 1] + n.z * lights[4 * k + 2];
-      diff += lights[4 * k + 3] * fmaxf(0.f, ndl);
-    }
-    diff *= 0.318309886183790672f;
+    const float diff = lambert_diffuse(nrm, s, p0, p1, p2, lights, n_lights);
     const float cr = fminf(fmaxf(base_r * (amb_r + diff), 0.f), 1.f), cg = fminf(fmaxf(base_g * (amb_g + diff), 0.f), 1.f),
                 cb = fminf(fmaxf(base_b * (amb_b + diff), 0.f), 1.f);
     const unsigned ur = (unsigned)floorf(255.f * cr + 0.5f), ug = (unsigned)floorf(255.f * cg + 0.5f),
@@ -297,7 +306,182 @@ __global__ __launch_bounds__(RT_THREADS) void render_raster_kernel(const float* 
   }
 }
 
+// ------------------------------------------------------------------------------------------------ texture
+#define TX_MAX_SIDE 4096
+#define TX_MAX_LEVELS 13           // 1 + log2(4096)
+#define TX_ROWS 16                 // rows of a 64-pixel-wide strip per workgroup: a wave stores one row segment per step
+#define TX_THREADS 256
+
+__global__ __launch_bounds__(256) void texture_level0_kernel(const unsigned char* __restrict__ img, float4* __restrict__ out, int n,
+                                                             int channels) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= n) return;
+  const unsigned char* p = img + (long)t * channels;
+  out[t] = make_float4((float)p[0], (float)p[1], (float)p[2], 0.f);
+}
+
+// level l + 1 from level l as it is stored: ((a + b) + (c + d)) * 0.25f, the right / lower neighbour clamped to the level
+__global__ __launch_bounds__(256) void texture_reduce_kernel(const float4* __restrict__ src, float4* __restrict__ dst, int Hs, int Ws,
+                                                             int Hd, int Wd) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= Hd * Wd) return;
+  const int y = t / Wd, x = t - y * Wd;
+  const int x0 = 2 * x, x1 = min(2 * x + 1, Ws - 1), y0 = 2 * y, y1 = min(2 * y + 1, Hs - 1);
+  const float4 a = src[(long)y0 * Ws + x0], b = src[(long)y0 * Ws + x1], c = src[(long)y1 * Ws + x0], d = src[(long)y1 * Ws + x1];
+  dst[t] = make_float4(((a.x + b.x) + (c.x + d.x)) * 0.25f, ((a.y + b.y) + (c.y + d.y)) * 0.25f,
+                       ((a.z + b.z) + (c.z + d.z)) * 0.25f, ((a.w + b.w) + (c.w + d.w)) * 0.25f);
+}
+
+__device__ __forceinline__ bool finite_f(float x) { return fabsf(x) <= 3.402823466e+38f; }   // false for NaN and +-inf
+
+// GL_REPEAT bilinear tap of one level at U, Vv in [0, 1]: four 16-byte texels
+__device__ __forceinline__ F3 texture_bilinear(const float4* __restrict__ lvl, int Wl, int Hl, float U, float Vv) {
+  const float x = U * (float)Wl - 0.5f, y = (1.f - Vv) * (float)Hl - 0.5f;
+  const float xf = floorf(x), yf = floorf(y);
+  const float fx = x - xf, fy = y - yf;
+  // x0 is in [-1, W_l - 1], so the mathematical modulo is one conditional each; the clamp keeps any other value in the level
+  int x0 = (int)xf, y0 = (int)yf;
+  if (x0 < 0) x0 += Wl;
+  if (y0 < 0) y0 += Hl;
+  x0 = min(max(x0, 0), Wl - 1);
+  y0 = min(max(y0, 0), Hl - 1);
+  const int x1 = x0 + 1 < Wl ? x0 + 1 : 0, y1 = y0 + 1 < Hl ? y0 + 1 : 0;
+  const float4 t00 = lvl[y0 * Wl + x0], t10 = lvl[y0 * Wl + x1], t01 = lvl[y1 * Wl + x0], t11 = lvl[y1 * Wl + x1];
+  const float gx = 1.f - fx, gy = 1.f - fy;
+  return F3{gy * (gx * t00.x + fx * t10.x) + fy * (gx * t01.x + fx * t11.x),
+            gy * (gx * t00.y + fx * t10.y) + fy * (gx * t01.y + fx * t11.y),
+            gy * (gx * t00.z + fx * t10.z) + fy * (gx * t01.z + fx * t11.z)};
+}
+
+// One workgroup per (frame, 64 x 16 strip); pixel-parallel in stage (C)'s mapping, so a wave reads 64 contiguous face ids and
+// stores 256 contiguous bytes of RGBA per step.  The face's set-up, the barycentrics and the lighting are the routines of the
+// raster pass; the level table (offset, width, height of every level) is built once per workgroup in LDS.
+__global__ __launch_bounds__(TX_THREADS) void render_shade_textured_kernel(
+    const float* __restrict__ screen, const float* __restrict__ normals, const int* __restrict__ faces, const float* __restrict__ vt,
+    const int* __restrict__ ft, const float4* __restrict__ pyramid, const float* __restrict__ shade, const float* __restrict__ lights,
+    int n_lights, const int* __restrict__ face_id, unsigned* __restrict__ rgba, float* __restrict__ uvl, int V, int F, int Nt,
+    int Ht, int Wt, int L, int H, int W, int tiles_x, int strips_y, float near) {
+  __shared__ int s_off[TX_MAX_LEVELS], s_w[TX_MAX_LEVELS], s_h[TX_MAX_LEVELS];
+  const int tid = threadIdx.x;
+  if (tid < L) {
+    int off = 0, w = Wt, h = Ht;
+    for (int l = 0; l < tid; ++l) {
+      off += w * h;
+      w = max(1, w >> 1);
+      h = max(1, h >> 1);
+    }
+    s_off[tid] = off; s_w[tid] = w; s_h[tid] = h;
+  }
+  __syncthreads();
+  const int per_frame = tiles_x * strips_y;
+  const int b = blockIdx.x / per_frame, rest = blockIdx.x - b * per_frame;
+  const int sy = rest / tiles_x, tx = rest - sy * tiles_x;
+  const int tx0 = tx * RT_TILE, ty0 = sy * TX_ROWS;
+  const float* scr = screen + (long)b * V * 3;
+  const float* nrm = normals + (long)b * V * 3;
+  const float amb_r = shade[3], amb_g = shade[4], amb_b = shade[5];
+  const float Wtf = (float)Wt, Htf = (float)Ht, top = (float)(L - 1);
+  for (int p = tid; p < RT_TILE * TX_ROWS; p += TX_THREADS) {
+    const int i = ty0 + p / RT_TILE, j = tx0 + p % RT_TILE;
+    if (i >= H || j >= W) continue;
+    const long o = ((long)b * H + i) * W + j;
+    const int g = face_id[o];
+    FaceSetup s;
+    s.ok = false;
+    if ((unsigned)g < (unsigned)F) s = face_setup(faces, scr, g, V, near, 0, 0, W - 1, H - 1);
+    if (!s.ok) {                      // background, or a face id the raster pass cannot have written
+      if (uvl != nullptr) *(F3*)(uvl + o * 3) = F3{0.f, 0.f, 0.f};
+      continue;
+    }
+    long e0, e1, e2;
+    edges_at(s, j, i, e0, e1, e2);
+    float w0, w1, w2;
+    const float iz = inv_depth(s, e0, e1, e2, w0, w1, w2);
+    const float p0 = w0 * s.q0 / iz, p1 = w1 * s.q1 / iz, p2 = w2 * s.q2 / iz;
+    // per-corner texture coordinates in the face's oriented order: face_setup swapped corners 1 and 2 iff it swapped the ids
+    const I3 ti = *(const I3*)(ft + (long)g * 3);
+    const bool swapped = s.i1 != faces[(long)g * 3 + 1];
+    const int k0 = ti.a, k1 = swapped ? ti.c : ti.b, k2 = swapped ? ti.b : ti.c;
+    float2 t0 = make_float2(0.f, 0.f), t1 = t0, t2 = t0;
+    if ((unsigned)k0 < (unsigned)Nt) t0 = *(const float2*)(vt + (long)k0 * 2);
+    if ((unsigned)k1 < (unsigned)Nt) t1 = *(const float2*)(vt + (long)k1 * 2);
+    if ((unsigned)k2 < (unsigned)Nt) t2 = *(const float2*)(vt + (long)k2 * 2);
+    const float u = (p0 * t0.x + p1 * t1.x) + p2 * t2.x, v = (p0 * t0.y + p1 * t1.y) + p2 * t2.y;
+    // analytic level of detail: d w_k / d j = a_k / A, d w_k / d i = c_k / A with stage (B)'s integer edge steps
+    const float A = (float)s.area;
+    const float g0 = s.q0 * ((float)(-256L * (s.y2 - s.y1)) / A), g1 = s.q1 * ((float)(-256L * (s.y0 - s.y2)) / A),
+                g2 = s.q2 * ((float)(-256L * (s.y1 - s.y0)) / A);
+    const float h0 = s.q0 * ((float)(256L * (s.x2 - s.x1)) / A), h1 = s.q1 * ((float)(256L * (s.x0 - s.x2)) / A),
+                h2 = s.q2 * ((float)(256L * (s.x1 - s.x0)) / A);
+    const float dDj = (g0 + g1) + g2, dDi = (h0 + h1) + h2;
+    const float duj = (((g0 * t0.x + g1 * t1.x) + g2 * t2.x) - u * dDj) / iz, dvj = (((g0 * t0.y + g1 * t1.y) + g2 * t2.y) - v * dDj) / iz;
+    const float dui = (((h0 * t0.x + h1 * t1.x) + h2 * t2.x) - u * dDi) / iz, dvi = (((h0 * t0.y + h1 * t1.y) + h2 * t2.y) - v * dDi) / iz;
+    const float rj2 = (Wtf * duj) * (Wtf * duj) + (Htf * dvj) * (Htf * dvj), ri2 = (Wtf * dui) * (Wtf * dui) + (Htf * dvi) * (Htf * dvi);
+    float lam = 0.5f * log2f(fmaxf(rj2, ri2));
+    if (!(finite_f(rj2) && finite_f(ri2) && finite_f(lam))) lam = 0.f;
+    lam = fminf(fmaxf(lam, 0.f), top);
+    const float us = finite_f(u) ? u : 0.f, vs = finite_f(v) ? v : 0.f;
+    const float U = us - floorf(us), Vv = vs - floorf(vs);
+    const int l0 = min((int)floorf(lam), L - 1), l1 = min(l0 + 1, L - 1);
+    const float fl = lam - (float)l0;
+    const F3 c0 = texture_bilinear(pyramid + s_off[l0], s_w[l0], s_h[l0], U, Vv);
+    const F3 c1 = texture_bilinear(pyramid + s_off[l1], s_w[l1], s_h[l1], U, Vv);
+    const float gl = 1.f - fl;
+    const float Tr = gl * c0.x + fl * c1.x, Tg = gl * c0.y + fl * c1.y, Tb = gl * c0.z + fl * c1.z;
+    const float diff = lambert_diffuse(nrm, s, p0, p1, p2, lights, n_lights);
+    const float cr = fminf(fmaxf((Tr / 255.f) * (amb_r + diff), 0.f), 1.f), cg = fminf(fmaxf((Tg / 255.f) * (amb_g + diff), 0.f), 1.f),
+                cb = fminf(fmaxf((Tb / 255.f) * (amb_b + diff), 0.f), 1.f);
+    const unsigned ur = (unsigned)floorf(255.f * cr + 0.5f), ug = (unsigned)floorf(255.f * cg + 0.5f),
+                   ub = (unsigned)floorf(255.f * cb + 0.5f);
+    rgba[o] = ur | (ug << 8) | (ub << 16) | 0xff000000u;
+    if (uvl != nullptr) *(F3*)(uvl + o * 3) = F3{us, vs, lam};
+  }
+}
+
 }  // namespace
+
+extern "C" long msmd_texture_texels(int Ht, int Wt) {
+  if (Ht < 1 || Wt < 1 || Ht > TX_MAX_SIDE || Wt > TX_MAX_SIDE) return -1;
+  long n = 0;
+  for (int h = Ht, w = Wt;; h = h > 1 ? h >> 1 : 1, w = w > 1 ? w >> 1 : 1) {
+    n += (long)h * w;
+    if (h == 1 && w == 1) break;
+  }
+  return n;
+}
+
+extern "C" int msmd_texture_mips(const void* img, int Ht, int Wt, int channels, float* pyramid, msmd_stream_t stream) {
+  if (msmd_texture_texels(Ht, Wt) < 0 || (channels != 3 && channels != 4)) return 1;
+  float4* level = (float4*)pyramid;
+  int h = Ht, w = Wt;
+  hipLaunchKernelGGL(texture_level0_kernel, dim3((unsigned)((h * w + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     (const unsigned char*)img, level, h * w, channels);
+  while (h > 1 || w > 1) {
+    const int hd = h > 1 ? h >> 1 : 1, wd = w > 1 ? w >> 1 : 1;
+    float4* next = level + (long)h * w;
+    hipLaunchKernelGGL(texture_reduce_kernel, dim3((unsigned)((hd * wd + 255) / 256)), dim3(256), 0, (hipStream_t)stream, level, next,
+                       h, w, hd, wd);
+    level = next; h = hd; w = wd;
+  }
+  MSMD_RETURN_LAST();
+}
+
+extern "C" int msmd_render_shade_textured(const float* screen, const float* normals, const int* faces, const float* vt, const int* ft,
+                                          const float* pyramid, int Ht, int Wt, const float* shade, const float* lights,
+                                          int n_lights, const int* face_id, void* rgba, float* uvl, int B, int V, int F, int Nt,
+                                          int H, int W, float near, msmd_stream_t stream) {
+  if (B <= 0 || V <= 0 || F <= 0 || Nt <= 0 || H <= 0 || W <= 0 || n_lights < 0 || !(near > 0.f) || face_id == nullptr ||
+      msmd_texture_texels(Ht, Wt) < 0) return 1;
+  int L = 1;
+  for (int m = Ht > Wt ? Ht : Wt; m > 1; m >>= 1) ++L;
+  const int tiles_x = (W + RT_TILE - 1) / RT_TILE, strips_y = (H + TX_ROWS - 1) / TX_ROWS;
+  const long grid = (long)B * tiles_x * strips_y;
+  if (grid > 2147483647L) return 1;
+  hipLaunchKernelGGL(render_shade_textured_kernel, dim3((unsigned)grid), dim3(TX_THREADS), 0, (hipStream_t)stream, screen, normals,
+                     faces, vt, ft, (const float4*)pyramid, shade, lights, n_lights, face_id, (unsigned*)rgba, uvl, V, F, Nt, Ht, Wt, L,
+                     H, W, tiles_x, strips_y, near);
+  MSMD_RETURN_LAST();
+}
 
 extern "C" int msmd_render_vertices(const float* verts, const int* faces, const int* csr_offsets, const int* csr_faces,
                                     const float* view, const float* t_center, const float* rot, float* screen,

@@ -17,6 +17,7 @@ SURVEY.md section 8(f) n3, the callers either side of the sampler:
   * ``load_audio_16k`` -- a `.wav` of any rate and channel count -> 16 kHz mono on the device (utils/audio.py, csrc/audio_io.hip).
   * ``--video`` -- the frames, JPEG-compressed on the device chunk by chunk (csrc/jpeg.hip), and the input WAV as one
     Motion-JPEG AVI (utils/media.py), where the reference calls ffmpeg (utils/media.py:combine_frames_and_audio).
+  * ``--texture`` -- an `.npz` with `tex_img`, `vt`, `ft`: the frames are drawn with that texture.
 The rest of the reference script's media IO (compressed audio codecs, cv2, H.264) stays outside.
 """
 from __future__ import annotations
@@ -179,9 +180,11 @@ def denormalize_coeffs(overall_coef, coef_stats):
 
 
 @torch.no_grad()
-def render_coeffs_chunks(coef, shape_coef, flame, coef_stats, renderer, chunk=512, *, with_global_pose=True):
+def render_coeffs_chunks(coef, shape_coef, flame, coef_stats, renderer, chunk=512, *, with_global_pose=True, tex_img=None,
+                         tex_uv=None):
     """`render_coeffs` as a generator: yields the frames of `chunk` coefficients at a time, (n, H, W, 3) uint8 views of the
-    renderer's RGBA buffer, so a consumer that compresses each chunk keeps one chunk of raw pixels alive."""
+    renderer's RGBA buffer, so a consumer that compresses each chunk keeps one chunk of raw pixels alive.  tex_img / tex_uv:
+    a texture for FLAME's faces, as MeshRenderer.render_vertices takes it."""
     coef = coef.reshape(-1, coef.shape[-1]).float()
     if coef.shape[-1] == 53:
         coef = torch.cat([coef, torch.zeros_like(coef[:, :1])], dim=-1)
@@ -189,19 +192,20 @@ def render_coeffs_chunks(coef, shape_coef, flame, coef_stats, renderer, chunk=51
     for i in range(0, coef.shape[0], chunk):
         coef_dict = get_coef_dict(coef[i:i + chunk], shape[i:i + chunk], coef_stats, with_global_pose=with_global_pose)
         verts = coef_dict_to_vertices(coef_dict, flame, flame_batch_size=chunk)
-        yield renderer.render_vertices(verts, flame.faces_tensor)[0]
+        yield renderer.render_vertices(verts, flame.faces_tensor, tex_img=tex_img, tex_uv=tex_uv)[0]
 
 
 @torch.no_grad()
-def render_coeffs(coef, shape_coef, flame, coef_stats, renderer, chunk=512, *, with_global_pose=True):
+def render_coeffs(coef, shape_coef, flame, coef_stats, renderer, chunk=512, *, with_global_pose=True, tex_img=None, tex_uv=None):
     """Motion coefficients (T, C) or (1, T, C) -> frames (T, H, W, 3) uint8 on the device: get_coef_dict -> coef_dict_to_vertices
     -> renderer.render_vertices on FLAME's faces, `chunk` frames at a time (one chunk's vertices are the only intermediate
     alive).  coef is in get_coef_dict's layout (50 expression + 4 pose: global rotation, jaw opening); a 53-wide row
     (expression + head rotation, what `denormalize_coeffs` returns side by side) gets a closed jaw.  coef_stats: None for
     coefficients in the data's units, or get_coef_dict's denorm_stats (`exp` / `pose` / `shape` means and stds).
-    shape_coef: (1, 100) or (T, 100)."""
+    shape_coef: (1, 100) or (T, 100).  tex_img (Ht, Wt, 3 | 4) uint8 with tex_uv = {'vt', 'ft'} draws the frames textured
+    (MeshRenderer.render_vertices)."""
     return torch.cat(list(render_coeffs_chunks(coef, shape_coef, flame, coef_stats, renderer, chunk,
-                                               with_global_pose=with_global_pose)), dim=0)
+                                               with_global_pose=with_global_pose, tex_img=tex_img, tex_uv=tex_uv)), dim=0)
 
 
 # ----------------------------------------------------------------------------- many clips per denoise step
@@ -297,6 +301,9 @@ def build_parser():
     ap.add_argument("--render_size", type=int, default=0, help="side of the square frames rendered from the result (0: none)")
     ap.add_argument("--flame_model_path", type=str, default=None, help="FLAME generic_model.pkl (with --render_size)")
     ap.add_argument("--flame_lmk_embedding_path", type=str, default=None, help="FLAME landmark embedding (with --render_size)")
+    ap.add_argument("--texture", type=str, default=None, help=".npz with tex_img (Ht, Wt, 3 | 4) uint8, vt (Nt, 2) and ft (F, 3) "
+                                                              "for FLAME's faces: the frames are drawn textured "
+                                                              "(needs --render_size > 0)")
     # video (the reference pipes frames and audio through ffmpeg; here a Motion-JPEG AVI is written, utils/media.py)
     ap.add_argument("--video", action="store_true", help="write video_<clip>_seed_<s>.avi instead of the raw frames "
                                                          "(needs --render_size > 0)")
@@ -305,14 +312,26 @@ def build_parser():
 
 
 def parse_args(argv=None):
-    """build_parser().parse_args with the checks that span flags: --video needs --render_size > 0 and a quality in [1, 100]."""
+    """build_parser().parse_args with the checks that span flags: --video and --texture need --render_size > 0, and the
+    quality lies in [1, 100]."""
     ap = build_parser()
     args = ap.parse_args(argv)
     if args.video and args.render_size <= 0:
         ap.error("--video needs --render_size > 0: there are no frames to encode")
+    if args.texture is not None and args.render_size <= 0:
+        ap.error("--texture needs --render_size > 0: there are no frames to draw it on")
     if not 1 <= args.video_quality <= 100:
         ap.error(f"--video_quality {args.video_quality} is outside [1, 100]")
     return args
+
+
+def load_texture(path):
+    """--texture's `.npz` -> (tex_img, {'vt', 'ft'}) as MeshRenderer takes them."""
+    with np.load(path) as z:
+        missing = [k for k in ("tex_img", "vt", "ft") if k not in z.files]
+        if missing:
+            raise ValueError(f"{path} lacks {missing}: a texture file holds tex_img, vt and ft")
+        return z["tex_img"], {"vt": z["vt"], "ft": z["ft"]}
 
 
 def load_audio_16k(path, device="cuda"):
@@ -337,7 +356,8 @@ def main(argv=None):
     coefficients are also decoded by FLAME and rendered on the device (render_coeffs), and `frames_<clip>_seed_<s>.npy`
     ((T, N, N, 3) uint8) is written beside them.  With --video as well, `video_<clip>_seed_<s>.avi` is written in its place: the
     frames are JPEG-compressed on the device chunk by chunk as they are rendered (so one chunk of raw pixels is alive at a
-    time), at model_args.fps, with --audio_clip as the sound track when it is a `.wav` and silent otherwise."""
+    time), at model_args.fps, with --audio_clip as the sound track when it is a `.wav` and silent otherwise.  --texture PATH
+    (an `.npz` with tex_img, vt, ft) draws the frames textured, in either form."""
     import os
     args = parse_args(argv)
     device = torch.device("cuda")
@@ -363,6 +383,7 @@ def main(argv=None):
     os.makedirs(temp, exist_ok=True)
     written = []
     flame = renderer = None
+    tex_img, tex_uv = load_texture(args.texture) if args.texture is not None else (None, None)
     if args.render_size > 0:
         from .utils.flame import FLAME, FLAMEConfig
         from .utils.renderer import MeshRenderer
@@ -389,7 +410,7 @@ def main(argv=None):
             from .utils import media
             jpegs = []
             for part in render_coeffs_chunks(torch.cat([exp_code, head_rot], dim=-1), shape_coef.reshape(1, -1), flame, None,
-                                             renderer, chunk=256):
+                                             renderer, chunk=256, tex_img=tex_img, tex_uv=tex_uv):
                 jpegs += media.encode_jpeg(part, args.video_quality)
             sound = None
             if args.audio_clip.lower().endswith(".wav"):
@@ -399,7 +420,8 @@ def main(argv=None):
             media.write_avi(out, jpegs, model_args.fps, (args.render_size, args.render_size), sound)
             written.append(out)
         elif renderer is not None:
-            frames = render_coeffs(torch.cat([exp_code, head_rot], dim=-1), shape_coef.reshape(1, -1), flame, None, renderer)
+            frames = render_coeffs(torch.cat([exp_code, head_rot], dim=-1), shape_coef.reshape(1, -1), flame, None, renderer,
+                                   tex_img=tex_img, tex_uv=tex_uv)
             out = os.path.join(temp, f"frames_{clip}_seed_{seed}.npy")
             np.save(out, frames.cpu().numpy())
             written.append(out)

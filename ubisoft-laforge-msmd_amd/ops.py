@@ -1409,6 +1409,67 @@ def render_raster(screen, normals, faces_i32, shade, lights, height, width, near
     return rgba, depth, face_id
 
 
+TEXTURE_MAX_SIDE = 4096         # TX_MAX_SIDE in csrc/render.hip
+
+
+def texture_pyramid(img_u8):
+    """(Ht, Wt, 3 | 4) uint8 image on the device (alpha ignored) -> its mip pyramid, (n_texels, 4) fp32 RGBA texels with the
+    levels one after the other (level l + 1 is max(1, H_l >> 1) x max(1, W_l >> 1)): msmd_texture_mips."""
+    _render_arg("img", img_u8, torch.uint8)
+    if img_u8.dim() != 3 or img_u8.shape[2] not in (3, 4):
+        raise TypeError(f"img must have shape (Ht, Wt, 3) or (Ht, Wt, 4), got {tuple(img_u8.shape)}")
+    Ht, Wt, C = img_u8.shape
+    lib = _lib.load()
+    n = lib.msmd_texture_texels(Ht, Wt)
+    if n < 0:
+        raise ValueError(f"a {Ht} x {Wt} texture is outside [1, {TEXTURE_MAX_SIDE}]")
+    pyramid = torch.empty(n, 4, device=img_u8.device, dtype=torch.float32)
+    _lib.check(lib.msmd_texture_mips(_p(img_u8), Ht, Wt, C, _p(pyramid), _stream()), "msmd_texture_mips")
+    return pyramid
+
+
+def render_shade_textured(screen, normals, faces_i32, vt, ft, pyramid, tex_height, tex_width, shade, lights, face_id, rgba, near,
+                          want_uvl=False):
+    """Overwrites rgba (B, H, W, 4) uint8 at the pixels face_id (B, H, W) int32 marks as covered with the mip-mapped,
+    trilinearly sampled texture under render_raster's lighting: msmd_render_shade_textured.  screen / normals / faces / shade /
+    lights as render_raster takes them; vt (Nt, 2) fp32, ft (F, 3) int32 per-corner indices into vt; pyramid as
+    texture_pyramid returns it for a tex_height x tex_width image.  -> uvl (B, H, W, 3) fp32 = (u, v, lambda) per pixel (zeros
+    on the background) if want_uvl, else None."""
+    _render_arg("screen", screen, torch.float32)
+    if screen.dim() != 3 or screen.shape[2] != 3:
+        raise TypeError(f"screen must have shape (B, V, 3), got {tuple(screen.shape)}")
+    B, V, _ = screen.shape
+    _render_arg("normals", normals, torch.float32, (B, V, 3))
+    _render_arg("faces", faces_i32, torch.int32)
+    if faces_i32.dim() != 2 or faces_i32.shape[1] != 3:
+        raise TypeError(f"faces must have shape (F, 3), got {tuple(faces_i32.shape)}")
+    Fc = faces_i32.shape[0]
+    _render_arg("vt", vt, torch.float32)
+    if vt.dim() != 2 or vt.shape[1] != 2 or vt.shape[0] == 0:
+        raise TypeError(f"vt must have shape (Nt, 2), got {tuple(vt.shape)}")
+    _render_arg("ft", ft, torch.int32, (Fc, 3))
+    _render_arg("shade", shade, torch.float32, (6,))
+    _render_arg("lights", lights, torch.float32)
+    if lights.dim() != 2 or lights.shape[1] != 4:
+        raise TypeError(f"lights must have shape (L, 4), got {tuple(lights.shape)}")
+    _render_arg("face_id", face_id, torch.int32)
+    if face_id.dim() != 3 or face_id.shape[0] != B:
+        raise TypeError(f"face_id must have shape ({B}, H, W), got {tuple(face_id.shape)}")
+    H, W = face_id.shape[1:]
+    _render_arg("rgba", rgba, torch.uint8, (B, H, W, 4))
+    lib = _lib.load()
+    Ht, Wt = int(tex_height), int(tex_width)
+    n = lib.msmd_texture_texels(Ht, Wt)
+    if n < 0:
+        raise ValueError(f"a {Ht} x {Wt} texture is outside [1, {TEXTURE_MAX_SIDE}]")
+    _render_arg("pyramid", pyramid, torch.float32, (n, 4))
+    uvl = torch.empty(B, H, W, 3, device=screen.device, dtype=torch.float32) if want_uvl else None
+    _lib.check(lib.msmd_render_shade_textured(_p(screen), _p(normals), _p(faces_i32), _p(vt), _p(ft), _p(pyramid), Ht, Wt,
+                                              _p(shade), _p(lights), lights.shape[0], _p(face_id), _p(rgba), _p(uvl), B, V, Fc,
+                                              vt.shape[0], H, W, float(near), _stream()), "msmd_render_shade_textured")
+    return uvl
+
+
 # ----------------------------------------------------------------------------- JPEG encoder (csrc/jpeg.hip, DESIGN.md 5.13)
 JPEG_RESTART_INTERVAL = 32      # MSMD_JPEG_RESTART_INTERVAL
 JPEG_MAX_SIDE = 16384           # MSMD_JPEG_MAX_SIDE

@@ -1,11 +1,17 @@
 """Mesh renderer on the MI355X (surface of reference utils/renderer.py:14-128, which draws through pyrender / EGL).
 
 An Instinct card has no graphics pipe, so the image is made by two compute launches (csrc/render.hip):
-vertex normals + camera + projection, then a z-buffered 64 x 64-tile rasteriser with Lambert shading.  Coverage and depth
+vertex normals + camera + projection, then a z-buffered 64 x 64-tile rasteriser with Lambert shading; a texture adds a third,
+deferred launch that shades the covered pixels from a mip pyramid.  Coverage and depth
 follow the OpenGL conventions the reference's renderer works under (pixel centres at +0.5, top-left fill rule, row 0 at the
 top, eye depth with 0 for the background as pyrender returns it); the shading model is this project's own (Lambert + ambient on
 the reference's base colour, lights and ambient level), not pyrender's metallic-roughness shader, so colours are not pixel-equal.
-There is NO CLIPPING: a face with a vertex nearer than `near` is dropped whole.  Texture (tex_img) is out of scope.
+There is NO CLIPPING: a face with a vertex nearer than `near` is dropped whole.
+
+Texture (tex_img + tex_uv = {'vt', 'ft'}) follows the ordinary OpenGL / OBJ conventions: GL_REPEAT wrap, GL_LINEAR
+magnification, GL_LINEAR_MIPMAP_LINEAR minification with an analytic per-pixel level of detail, v up, no sRGB conversion.  The
+texel replaces the base colour of the shading model above.  `vt` is indexed per corner through `ft`, so a seam needs no
+duplicated vertex (the reference writes an OBJ file and reloads it for that), and normals stay those of the topology `f`.
 
 ``render_mesh`` keeps the reference's signature and returns numpy arrays; ``render_vertices`` takes the (B, V, 3) device
 tensor FLAME produces and leaves colour and depth on the device.
@@ -40,6 +46,43 @@ def vertex_face_csr(faces, n_vertices):
     return offsets.astype(np.int32), ids
 
 
+def validate_texture(tex_img, tex_uv, n_faces):
+    """tex_img (Ht, Wt, 3 | 4) uint8 with 1 <= Ht, Wt <= 4096 and tex_uv = {'vt': (Nt, 2) float, 'ft': (F, 3) integer} with F =
+    n_faces -> (image, vt float32, ft int32), contiguous numpy arrays.  TypeError for a wrong container, shape or dtype (an
+    image that is not uint8 included), ValueError for an image size outside the limits, `ft` rows != n_faces or an `ft` entry
+    outside [0, Nt)."""
+    img = np.asarray(tex_img)
+    if img.dtype != np.uint8:
+        raise TypeError(f"tex_img must be uint8, got {img.dtype}")
+    if img.ndim != 3 or img.shape[2] not in (3, 4):
+        raise TypeError(f"tex_img must have shape (Ht, Wt, 3) or (Ht, Wt, 4), got {img.shape}")
+    if not (1 <= img.shape[0] <= ops.TEXTURE_MAX_SIDE and 1 <= img.shape[1] <= ops.TEXTURE_MAX_SIDE):
+        raise ValueError(f"a {img.shape[0]} x {img.shape[1]} texture is outside [1, {ops.TEXTURE_MAX_SIDE}]")
+    try:
+        vt, ft = tex_uv["vt"], tex_uv["ft"]
+    except (TypeError, KeyError, IndexError) as e:
+        raise TypeError("tex_uv must be a mapping with 'vt' (Nt, 2) and 'ft' (F, 3)") from e
+    vt, ft = np.asarray(vt), np.asarray(ft)
+    if not np.issubdtype(vt.dtype, np.floating) or vt.ndim != 2 or vt.shape[1] != 2 or vt.shape[0] == 0:
+        raise TypeError(f"tex_uv['vt'] must be a float (Nt, 2) array, got {vt.dtype} {vt.shape}")
+    if not np.issubdtype(ft.dtype, np.integer) or ft.ndim != 2 or ft.shape[1] != 3:
+        raise TypeError(f"tex_uv['ft'] must be an integer (F, 3) array, got {ft.dtype} {ft.shape}")
+    if ft.shape[0] != int(n_faces):
+        raise ValueError(f"tex_uv['ft'] has {ft.shape[0]} rows for {int(n_faces)} faces")
+    ft = ft.astype(np.int64)
+    if ft.min() < 0 or ft.max() >= vt.shape[0]:
+        raise ValueError(f"tex_uv['ft'] refers to texture coordinates outside [0, {vt.shape[0]})")
+    return np.ascontiguousarray(img), np.ascontiguousarray(vt, np.float32), np.ascontiguousarray(ft.astype(np.int32))
+
+
+def _content_key(x):
+    """Cache key of a tensor (its storage and version) or of anything numpy reads (its contents)."""
+    if torch.is_tensor(x):
+        return ("t", x.data_ptr(), tuple(x.shape), x.dtype, str(x.device), x._version)
+    x = np.ascontiguousarray(x)
+    return ("n", hashlib.sha1(x.tobytes()).hexdigest(), x.shape, str(x.dtype))
+
+
 def rodrigues(r):
     """3 x 3 rotation of the axis-angle vector r as cv2.Rodrigues defines it: angle = |r|, identity at 0 (float64)."""
     r = np.asarray(r, np.float64).reshape(3)
@@ -71,6 +114,7 @@ class MeshRenderer:
             light_pose[:3, 3] = np.array([0, 0, 1])
         self._consts = {}          # device -> (view, shade, lights)
         self._csr = {}             # faces key -> (faces int32, offsets, ids) on the device
+        self._tex = {}             # texture key -> (pyramid, vt, ft, Ht, Wt) on the device
         self.set_camera_pose(camera_pose)
         self.set_lighting_pose(light_pose)
 
@@ -132,12 +176,42 @@ class MeshRenderer:
             self._csr[key] = hit
         return hit[1:]
 
+    def _texture(self, tex_img, tex_uv, n_faces, device):
+        """tex_img, tex_uv -> (pyramid (n_texels, 4) fp32, vt (Nt, 2) fp32, ft (F, 3) int32, Ht, Wt) on `device`, cached per
+        texture (tensors by their storage and version, arrays by their contents); at most 4 textures are kept."""
+        try:
+            parts = (tex_img, tex_uv["vt"], tex_uv["ft"])
+        except (TypeError, KeyError, IndexError) as e:
+            raise TypeError("tex_uv must be a mapping with 'vt' (Nt, 2) and 'ft' (F, 3)") from e
+        key = tuple(_content_key(x) for x in parts) + (int(n_faces), str(device))
+        hit = self._tex.get(key)
+        if hit is None:
+            host = [x.detach().cpu().numpy() if torch.is_tensor(x) else x for x in parts]
+            img, vt, ft = validate_texture(host[0], {"vt": host[1], "ft": host[2]}, n_faces)
+            pyramid = ops.texture_pyramid(torch.from_numpy(img).to(device))
+            if len(self._tex) >= 4:
+                self._tex.pop(next(iter(self._tex)))
+            # the objects themselves are kept with their tables, so a tensor's storage cannot be recycled under the key
+            hit = (parts, pyramid, torch.from_numpy(vt).to(device), torch.from_numpy(ft).to(device), img.shape[0], img.shape[1])
+            self._tex[key] = hit
+        return hit[1:]
+
     # ------------------------------------------------------------------ rendering
-    def render_vertices(self, vertices, faces, t_center=None, rot=None, return_face_id=False, return_screen=False):
+    def render_vertices(self, vertices, faces, t_center=None, rot=None, return_face_id=False, return_screen=False, tex_img=None,
+                        tex_uv=None, return_uv=False):
         """vertices (B, V, 3) CUDA tensor (fp32, or fp16 / bf16: cast) -> colour (B, H, W, 3) uint8 (a view of the RGBA
         buffer) and eye depth (B, H, W) fp32 (0 = background), both on the device.  rot: (3,) or (B, 3) axis-angle about
         t_center (3,) per frame.  return_face_id appends the winning face id per pixel (int32, -1 = background);
-        return_screen appends the vertex stage's screen (B, V, 3) = (x_s, y_s, depth) and eye-space normals (B, V, 3)."""
+        return_screen appends the vertex stage's screen (B, V, 3) = (x_s, y_s, depth) and eye-space normals (B, V, 3).
+        tex_img (Ht, Wt, 3 | 4) uint8 with tex_uv = {'vt': (Nt, 2), 'ft': (F, 3)} (validate_texture) draws the mesh textured;
+        return_uv (textured only) appends (u, v, level of detail) per pixel, (B, H, W, 3) fp32 with zeros on the background."""
+        if (tex_img is None) != (tex_uv is None):
+            if tex_uv is None:
+                raise NotImplementedError("a texture needs a uv table: tex_uv = {'vt', 'ft'} (there are no default per-vertex "
+                                          "texture coordinates)")
+            raise TypeError("tex_uv is given without tex_img")
+        if return_uv and tex_img is None:
+            raise TypeError("return_uv needs tex_img and tex_uv")
         if not torch.is_tensor(vertices) or not vertices.is_cuda or vertices.dim() != 3 or vertices.shape[2] != 3:
             raise TypeError("vertices must be a (B, V, 3) CUDA tensor")
         device = vertices.device
@@ -155,25 +229,34 @@ class MeshRenderer:
         r, g, b = self.bg_color
         rgba, depth, face_id = ops.render_raster(screen, normals, faces_d, shade, lights, self.height, self.width,
                                                  self.frustum["near"], self.frustum["far"], r | g << 8 | b << 16 | 255 << 24,
-                                                 want_face_id=return_face_id)
+                                                 want_face_id=return_face_id or tex_img is not None)
+        uvl = None
+        if tex_img is not None:
+            pyramid, vt, ft, tex_h, tex_w = self._texture(tex_img, tex_uv, faces_d.shape[0], device)
+            uvl = ops.render_shade_textured(screen, normals, faces_d, vt, ft, pyramid, tex_h, tex_w, shade, lights, face_id, rgba,
+                                            self.frustum["near"], want_uvl=return_uv)
         out = (rgba[..., :3], depth)
         if return_face_id:
             out += (face_id,)
         if return_screen:
             out += (screen, normals)
+        if return_uv:
+            out += (uvl,)
         return out
 
     def render_mesh(self, mesh, t_center, rot=np.zeros(3), tex_img=None, tex_uv=None, camera_pose=None, light_pose=None):
         """One mesh (any object with .v (V, 3) and .f (F, 3)) turned by `rot` about `t_center` -> (colour (H, W, 3) uint8,
         depth (H, W) float32) numpy arrays, as the reference returns them.  camera_pose / light_pose, when given, replace
-        the renderer's (and stay, as in the reference)."""
-        if tex_img is not None:
-            raise NotImplementedError("textured rendering is not built (FLAMETex is outside this project's scope)")
+        the renderer's (and stay, as in the reference).  tex_img (Ht, Wt, 3 | 4) uint8 with tex_uv = {'vt': (Nt, 2), 'ft': (F, 3)}
+        draws the mesh textured (render_vertices); tex_img without tex_uv is refused."""
+        if tex_img is not None and tex_uv is None:
+            raise NotImplementedError("a texture needs a uv table: tex_uv = {'vt', 'ft'} (there are no default per-vertex "
+                                      "texture coordinates)")
         if camera_pose is not None:
             self.set_camera_pose(camera_pose)
         if light_pose is not None:
             self.set_lighting_pose(light_pose)
         v = torch.from_numpy(np.ascontiguousarray(np.asarray(mesh.v, np.float32))).to("cuda").unsqueeze(0)
         color, depth = self.render_vertices(v, np.asarray(mesh.f), t_center=np.asarray(t_center, np.float64).reshape(3),
-                                            rot=np.asarray(rot, np.float64).reshape(3))
+                                            rot=np.asarray(rot, np.float64).reshape(3), tex_img=tex_img, tex_uv=tex_uv)
         return color[0].contiguous().cpu().numpy(), depth[0].cpu().numpy()
