@@ -16,6 +16,7 @@ import torch
 import torch.nn as nn
 
 from . import init, ops, shapes, synth
+from .blocks import Rows, add, materialise, norm, project
 from .utils.model_common import ParamTree, PositionalEncoding, enc_dec_mask, sinusoid_table  # noqa: F401  (enc_dec_mask re-exported)
 
 
@@ -342,155 +343,106 @@ class DenoisingNetwork_MSMD(nn.Module):
 
     def trunk(self, feats, tok0, mem, dtype, kv_list=None, row0_add=None, cross_list=None):
         """feature_proj + PE + 8 post-LN decoder layers + motion_dec head.  feats: packed (N, 111, Kpad);
-        tok0 (N, d); mem (N, 110, d).  Returns dec (N, 110, dm+nb) fp32."""
+        tok0 (N, d); mem (N, 110, d).  Returns dec (N, 110, dm+nb) fp32.
+
+        One layer body; msmd_amd.blocks realises each LayerNorm:
+          * fold (16-bit modes, ops.FOLD_LN): u = the un-normalised rows a residual GEMM stored, with their row statistics;
+            the LayerNorms are applied where their output is consumed -- as the next GEMM's operand (folded weights) and
+            as the next residual (r_stats).  General masked path: all three norms, only the last layer's norm3 is a kernel
+            of its own.  Diagonal path: norm3 of every layer but the last, and norm1 with the fused person query;
+          * split (f16x2): the parity-grade speed mode.  LayerNorms write fp32 (residual) and split (next GEMM operand) rows
+            in one pass; Q / K / V, attention outputs and the FFN hidden layer move between kernels in split storage."""
         P = self.pack(dtype)
         d, H = self.feature_dim, self.n_heads
         N, Tn, _ = feats.shape
         x = ops.gemm(feats, *P.fp)
         ops.add_pe_token(x, P.pe, tok0, row0_add)
         scale = (d // H) ** -0.5
-        if P.split:
-            return self._trunk_split(P, x, mem, kv_list, cross_list, scale)
+        split = P.split
+        fold = P.fold and ops.FOLD_LN
         # the fast path pays when R is hoisted over many calls (the sampler passes cross_list); for a single forward
         # the general masked kernels are as fast (measured 5.37 vs 5.46 ms on the bench step), so it stays opt-in there
-        diag = P.diag and getattr(self, "diag_fast_path", True) and (cross_list is not None or
-                                                                     getattr(self, "diag_single_pass", False))
+        # (and the split mode has no single-pass form)
+        diag = P.diag and getattr(self, "diag_fast_path", True) and (
+            cross_list is not None or (getattr(self, "diag_single_pass", False) and not split))
         if diag and cross_list is None:
             if kv_list is None:
                 kv_list = self.memory_kv(mem, dtype)
             cross_list = self.memory_cross(kv_list, dtype)
-        fold = P.fold and ops.FOLD_LN
-        if kv_list is None and not diag:
+        if kv_list is None and not diag and not split:
             kv_list = self.memory_kv(mem, dtype, stacked=True)
-        if fold and not diag:
-            # post-LN decoder layers without LayerNorm launches: u* = the un-normalised rows a residual GEMM stored, st* their
-            # row statistics; the three LayerNorms are applied where their output is consumed -- as the next GEMM's operand
-            # (folded weights) and as the next residual (r_stats).  Only the last layer's norm3 is a kernel of its own.
-            u = st = ln = None
-            for li, L in enumerate(P.layers):
-                if li == 0:
-                    qkv = ops.gemm(x, L.sa_w, L.sa_b)
-                else:
-                    qkv = ops.gemm_ln(u, L.f_sa[0], L.f_sa[2], a_stats=st, w_colsum=L.f_sa[1])
-                a = ops.attention(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], H, scale,
-                                  prefetch=(L.sa_ow, L.f_caq[0], L.ca_ow))      # the weights the next launches read
-                if li == 0:
-                    u1, st1 = ops.gemm_ln(a, L.sa_ow, L.sa_ob, x, stats_out=True)
-                else:
-                    u1, st1 = ops.gemm_ln(a, L.sa_ow, L.sa_ob, u, r_stats=st, r_gamma=ln[0], r_beta=ln[1], stats_out=True)
-                kv = kv_list[li] if kv_list is not None else ops.gemm(mem, L.ca_kvw, L.ca_kvb)
-                q = ops.gemm_ln(u1, L.f_caq[0], L.f_caq[2], a_stats=st1, w_colsum=L.f_caq[1])
-                nxt = P.layers[li + 1].f_sa[0] if li + 1 < len(P.layers) else P.md0[0]
-                c = ops.attention(q, kv[..., :d], kv[..., d:], H, scale, mask=P.mask, prefetch=(L.f_l1[0], L.l2[0], nxt))
-                u2, st2 = ops.gemm_ln(c, L.ca_ow, L.ca_ob, u1, r_stats=st1, r_gamma=L.n1[0], r_beta=L.n1[1], stats_out=True)
-                f = ops.gemm_ln(u2, L.f_l1[0], L.f_l1[2], act=ops.ACT_GELU, a_stats=st2, w_colsum=L.f_l1[1])
-                u, st = ops.gemm_ln(f, L.l2[0], L.l2[1], u2, r_stats=st2, r_gamma=L.n2[0], r_beta=L.n2[1], stats_out=True)
-                ln = L.n3
-            x = ops.layernorm(u, *ln)
-        u = st = ln = None        # diagonal path with fold: the previous layer's un-normalised norm3 input
-        # Diagonal path: after a layer's self-attention only ROW 0 of a sequence (the person token) depends on that layer's real
-        # cross-attention, and everything from there to the next layer's self-attention is row-wise.  The output is rows 1..
-        # (motion_dec below), so the LAST layer's person chain (query + Tq = 1 attention + 192-row out-projection, ~50 us of
-        # latency-bound launches) feeds nothing: skipped, same bits in every returned row (sampler B = 64: -1.0 .. -1.4 %).
-        # (Round 6 also ran the chain of the other layers -- with norm1 / norm2 / FFN on those rows alone -- as a compact (N, d)
-        # problem on a forked stream beside the main stream's norm + FFN, rejoining rows and statistics by a scatter kernel:
-        # correct, +0.8 % on one lane (five more small launches and a K = 2048 GEMM of 192 rows are as long as the main
-        # stream's FFN), and two lanes already hide the chain: removed, DESIGN.md section 5.)
-        n_layers = len(P.layers)
-        for li, L in enumerate(P.layers if not (fold and not diag) else ()):
-            if u is None:
-                qkv = ops.gemm(x, L.sa_w, L.sa_b)
-            else:
-                qkv = ops.gemm_ln(u, L.f_sa[0], L.f_sa[2], a_stats=st, w_colsum=L.f_sa[1])
-            nxt = None
-            if li + 1 < len(P.layers):
-                nxt = P.layers[li + 1].f_sa[0] if (fold and diag) else P.layers[li + 1].sa_w
-            a = ops.attention(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], H, scale,
-                              prefetch=None if P.split else (L.sa_ow, L.l1[0], L.l2[0], nxt))   # the layer's next weights
-            # (one launch for any N: choosing by the sequence count made a clip's result depend on the batch around it;
-            # against the two-launch form it is -1 % at N = 192 sequences and +1.5 % at N = 3)
-            fused_pq = getattr(self, "fused_person_query", True)
-            # norm1 without a launch of its own (diagonal path, fused person query): its two consumers apply it -- the
-            # person-token query projection through folded weights, the norm2 launch as its first stage (layernorm_pre)
-            fold_n1 = fold and diag and fused_pq
-            u1 = ops.gemm(a, L.sa_ow, L.sa_ob, residual=x) if u is None else \
-                ops.gemm_ln(a, L.sa_ow, L.sa_ob, u, r_stats=st, r_gamma=ln[0], r_beta=ln[1])
-            if not fold_n1:
-                x = ops.layernorm(u1, *L.n1)
-            kv = kv_list[li] if kv_list is not None else ops.gemm(mem, L.ca_kvw, L.ca_kvb)
-            last = li + 1 == n_layers
-            if diag and last and getattr(self, "skip_dead_person_chain", True):
-                # rows 1.. of the output do not see this layer's person token: R[:, 0] keeps whatever it holds
-                R = cross_list[li]
-                x = ops.layernorm_pre(u1, *L.n1, R, *L.n2) if fold_n1 else ops.layernorm(x, *L.n2, residual=R)
-            elif diag:
-                # only the person token (row 0) has a real softmax; rows t >= 1 come from the precomputed R
-                R = cross_list[li]
-                # same-box A/B in the sampler graph: fused -1 % at N = 192 sequences, +1.5 % at N = 3 (a longer serial
-                # chain per wave than the two more parallel launches), so it is used from 64 sequences up
-                if fold_n1:
-                    a0 = ops.person_query_attention(u1, L.f_caq[0], L.f_caq[2], kv, H, scale, wq_colsum=L.f_caq[1])
-                elif fused_pq:
-                    a0 = ops.person_query_attention(x, L.ca_qw_valu, L.ca_qb, kv, H, scale)      # (N, d), one launch
-                else:
-                    q0 = ops.gemm(x, L.ca_qw, L.ca_qb, M=N, K=d, lda=Tn * d)                    # (N, d) from x[:, 0]
-                    a0 = ops.attention(q0.view(N, 1, d), kv[..., :d], kv[..., d:], H, scale)     # (N, 1, d)
-                ops.gemm(a0, L.ca_ow, L.ca_ob, None, ops.ACT_NONE, out=R, M=N, K=d, ldc=Tn * d)  # -> R[:, 0]
-                x = ops.layernorm_pre(u1, *L.n1, R, *L.n2) if fold_n1 else ops.layernorm(x, *L.n2, residual=R)
-            else:
-                q = ops.gemm(x, L.ca_qw, L.ca_qb)
-                c = ops.attention(q, kv[..., :d], kv[..., d:], H, scale, mask=P.mask)
-                x = ops.layernorm(ops.gemm(c, L.ca_ow, L.ca_ob, residual=x), *L.n2)
-            f = ops.gemm(x, *L.l1, act=ops.ACT_GELU)
-            if fold and diag and li + 1 < len(P.layers):
-                # norm3 is consumed by the next layer's QKV GEMM and out-projection residual only: folded into them
-                u, st = ops.gemm_ln(f, L.l2[0], L.l2[1], x, stats_out=True)
-                ln = L.n3
-            else:
-                x = ops.layernorm(ops.gemm(f, *L.l2, residual=x), *L.n3)
-        # motion_dec on rows 1.. (windowed view of x, no copy)
-        Lm = Tn - 1
-        h = torch.empty(N, Lm, d // 2, device=x.device, dtype=dtype)
-        xs = ops.to_split(x) if P.split else x
-        ops.gemm(xs[:, 1:], *P.md0, None, ops.ACT_GELU, out=h, M=N * Lm, K=d, lda=d, rows_per_batch=Lm,
-                 a_batch_stride=Tn * d)
-        return ops.gemm(h, *P.md2, out_dtype=torch.float32)
-
-    def _trunk_split(self, P, x, mem, kv_list, cross_list, scale):
-        """The decoder layers + motion_dec head of `trunk` in the parity-grade speed mode (x: fp32 (N, Tn, d) after the
-        PE / token add).  LayerNorms write fp32 (residual) and split (next GEMM operand) rows in one pass; Q / K / V,
-        attention outputs and the FFN hidden layer move between kernels in split storage.  With the diagonal mask and a
-        hoisted cross_list (sampler) only the person row runs a real cross-attention, as in the other modes."""
-        d, H = self.feature_dim, self.n_heads
-        N, Tn, _ = x.shape
-        diag = P.diag and getattr(self, "diag_fast_path", True) and cross_list is not None
-        xs = ops.to_split(x)
+        # (one launch for any N: choosing by the sequence count made a clip's result depend on the batch around it;
+        # against the two-launch form it is -1 % at N = 192 sequences and +1.5 % at N = 3.  Same-box A/B in the sampler
+        # graph: fused -1 % at N = 192 sequences, +1.5 % at N = 3 -- a longer serial chain per wave than the two more
+        # parallel launches.)  The split mode has the fused form only.
+        fused_pq = getattr(self, "fused_person_query", True) or split
+        skip_dead = getattr(self, "skip_dead_person_chain", True)
+        x = Rows(x, xs=ops.to_split(x) if split else None)
         mem_s = None
         for li, L in enumerate(P.layers):
-            qkv = ops.gemm(xs, L.sa_w, L.sa_b, out_dtype=ops.SPLIT)
-            a = ops.attention(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], H, scale)
-            x, xs = ops.layernorm(ops.gemm(a, L.sa_ow, L.sa_ob, residual=x), *L.n1, split="both")
-            if diag:
-                R, kv = cross_list[li], kv_list[li]                                      # fp32 R (N, Tn, d); kv fp32
-                if not (li + 1 == len(P.layers) and getattr(self, "skip_dead_person_chain", True)):   # (see trunk)
-                    a0 = ops.person_query_attention(x, L.ca_qw_valu, L.ca_qb, kv, H, scale)   # (N, d) fp32, vector ALU
-                    ops.gemm(a0, L.ca_ow, L.ca_ob, None, ops.ACT_NONE, out=R, M=N, K=d, ldc=Tn * d)
-                x, xs = ops.layernorm(x, *L.n2, residual=R, split="both")
-            else:
-                if kv_list is not None:
+            nxt = P.layers[li + 1] if li + 1 < len(P.layers) else None
+            f_sa, f_caq, f_l1 = (L.f_sa, L.f_caq, L.f_l1) if fold else (None, None, None)
+            qkv = project(x, L.sa_w, L.sa_b, f_sa)
+            # the attention launches pull the weights the next launches read through the memory-side cache
+            if split:
+                prefetch = None
+            elif fold and not diag:
+                prefetch = (L.sa_ow, f_caq[0], L.ca_ow)
+            else:                                                                     # the layer's next weights
+                prefetch = (L.sa_ow, L.l1[0], L.l2[0], (nxt.f_sa[0] if fold else nxt.sa_w) if nxt else None)
+            a = ops.attention(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], H, scale, prefetch=prefetch)
+            x = add(a, L.sa_ow, L.sa_ob, x, stats=fold and not diag)
+            if not diag:
+                x = norm(x, L.n1, defer=fold, split=split)
+                if not split:
+                    kv = kv_list[li]
+                elif kv_list is not None:
                     kv = ops.to_split(kv_list[li])
                 else:
                     mem_s = ops.to_split(mem) if mem_s is None else mem_s
                     kv = ops.gemm(mem_s, L.ca_kvw, L.ca_kvb, out_dtype=ops.SPLIT)
-                q = ops.gemm(xs, L.ca_qw, L.ca_qb, out_dtype=ops.SPLIT)
-                c = ops.attention(q, kv[..., :d], kv[..., d:], H, scale, mask=P.mask)
-                x, xs = ops.layernorm(ops.gemm(c, L.ca_ow, L.ca_ob, residual=x), *L.n2, split="both")
-            f = ops.gemm(xs, *L.l1, act=ops.ACT_GELU, out_dtype=ops.SPLIT)
-            x, xs = ops.layernorm(ops.gemm(f, *L.l2, residual=x), *L.n3, split="both")
+                q = project(x, L.ca_qw, L.ca_qb, f_caq)
+                c = ops.attention(q, kv[..., :d], kv[..., d:], H, scale, mask=P.mask,
+                                  prefetch=(f_l1[0], L.l2[0], nxt.f_sa[0] if nxt else P.md0[0]) if fold else None)
+                x = norm(add(c, L.ca_ow, L.ca_ob, x, stats=fold), L.n2, defer=fold, split=split)
+            else:
+                # Diagonal path: only the person token (row 0) has a real softmax; rows t >= 1 come from the precomputed R.
+                # norm1 without a launch of its own (fold, fused person query): its two consumers apply it -- the
+                # person-token query projection through folded weights, the norm2 launch as its first stage (layernorm_pre)
+                x = norm(x, L.n1, defer=fold and fused_pq, split=split)
+                kv = kv_list[li] if kv_list is not None else ops.gemm(mem, L.ca_kvw, L.ca_kvb)
+                R = cross_list[li]
+                # After a layer's self-attention only ROW 0 of a sequence (the person token) depends on that layer's real
+                # cross-attention, and everything from there to the next layer's self-attention is row-wise.  The output is
+                # rows 1.. (motion_dec below), so the LAST layer's person chain (query + Tq = 1 attention + 192-row
+                # out-projection, ~50 us of latency-bound launches) feeds nothing: skipped, same bits in every returned row
+                # (sampler B = 64: -1.0 .. -1.4 %); R[:, 0] keeps whatever it holds.
+                # (Round 6 also ran the chain of the other layers -- with norm1 / norm2 / FFN on those rows alone -- as a
+                # compact (N, d) problem on a forked stream beside the main stream's norm + FFN, rejoining rows and
+                # statistics by a scatter kernel: correct, +0.8 % on one lane (five more small launches and a K = 2048 GEMM
+                # of 192 rows are as long as the main stream's FFN), and two lanes already hide the chain: removed,
+                # DESIGN.md section 5.)
+                if not (nxt is None and skip_dead):
+                    if x.ln is not None:
+                        a0 = ops.person_query_attention(x.x, f_caq[0], f_caq[2], kv, H, scale, wq_colsum=f_caq[1])
+                    elif fused_pq:
+                        a0 = ops.person_query_attention(x.x, L.ca_qw_valu, L.ca_qb, kv, H, scale)   # (N, d), one launch
+                    else:
+                        q0 = ops.gemm(x.x, L.ca_qw, L.ca_qb, M=N, K=d, lda=Tn * d)                  # (N, d) from x[:, 0]
+                        a0 = ops.attention(q0.view(N, 1, d), kv[..., :d], kv[..., d:], H, scale)    # (N, 1, d)
+                    ops.gemm(a0, L.ca_ow, L.ca_ob, None, ops.ACT_NONE, out=R, M=N, K=d, ldc=Tn * d)  # -> R[:, 0]
+                x = norm(x, L.n2, split=split, residual=R)
+            f = project(x, *L.l1, f_l1, act=ops.ACT_GELU)
+            # norm3 is consumed by the next layer's QKV GEMM and out-projection residual only: folded into them (the
+            # diagonal path's last layer hands real rows to motion_dec)
+            fold_n3 = fold and not (diag and nxt is None)
+            x = norm(add(f, *L.l2, x, stats=fold_n3), L.n3, defer=fold_n3, split=split)
+        x = materialise(x)
+        # motion_dec on rows 1.. (windowed view of x, no copy)
         Lm = Tn - 1
-        h = ops.empty((N, Lm, d // 2), x.device, ops.SPLIT)
-        ops.gemm(xs[:, 1:], *P.md0, None, ops.ACT_GELU, out=h, M=N * Lm, K=d, lda=d, rows_per_batch=Lm,
-                 a_batch_stride=Tn * d)
+        h = ops.empty((N, Lm, d // 2), x.x.device, ops.SPLIT if split else dtype)
+        ops.gemm((x.xs if split else x.x)[:, 1:], *P.md0, None, ops.ACT_GELU, out=h, M=N * Lm, K=d, lda=d,
+                 rows_per_batch=Lm, a_batch_stride=Tn * d)
         return ops.gemm(h, *P.md2, out_dtype=torch.float32)
 
     def forward(self, motion_feat, audio_feat, person_feat, static_style_feat, prev_motion_feat, prev_audio_feat, step,

@@ -21,6 +21,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops, shapes, synth
+from ..blocks import Rows, add, materialise, norm, project
 from .model_common import ParamTree, pad_audio_plan
 
 CONV_KERNEL = shapes.CONV_KERNEL
@@ -381,16 +382,28 @@ class Wav2Vec2Model(nn.Module):
         return x
 
     def encode_features(self, x, dtype):
-        """feature projection + positional conv + transformer layers on (B, T, 512) -> (B, T, 768)."""
+        """feature projection + positional conv + transformer layers on (B, T, 512) -> (B, T, 768).
+
+        One layer body for the post-LN (wav2vec2 / HuBERT-base) and the pre-LN (do_stable_layer_norm) block; how each
+        LayerNorm is realised is the business of msmd_amd.blocks:
+          * fold (16-bit modes, ops.FOLD_LN): no LayerNorm launches inside the blocks.  Every residual GEMM also writes the
+            row statistics of what it stored; LN(u) is applied on the fly where it is the next GEMM's operand (folded
+            weights) and where it is the next residual (include/msmd_hip.h msmd_gemm_ln).  Only the norm behind the
+            positional conv (no statistics yet) and the one after the last layer are kernels of their own;
+          * split (f16x2, post-LN): the parity-grade speed mode.  LayerNorm writes the row twice in one pass (fp32 = the next
+            residual, split = the next GEMM's A operand); the QKV GEMM writes split Q / K / V, the split attention writes
+            split O, the FFN's GELU output goes GEMM -> GEMM in split storage; every residual add and LayerNorm input stays
+            fp32.  No standalone conversion pass.  (The pre-LN block with split weights keeps fp32 rows: ops.gemm converts
+            its operand.)"""
         P = self.pack(dtype)
         c = self.config
         B, T, _ = x.shape
-        H = c.num_attention_heads
-        d = c.hidden_size
-        if P.split and not c.do_stable_layer_norm:
-            return self._encode_features_split(x, P)
-        h = ops.layernorm(x, *P.fp_ln, eps=c.layer_norm_eps)
-        h = ops.gemm(h, P.fp_w, P.fp_b)
+        H, d, eps = c.num_attention_heads, c.hidden_size, c.layer_norm_eps
+        scale = (d // H) ** -0.5
+        pre = c.do_stable_layer_norm      # HubertEncoderStableLayerNorm: pre-LN blocks, ONE LayerNorm after the last layer
+        split = P.split and not pre
+        fold = P.fold and ops.FOLD_LN
+        h = ops.gemm(ops.layernorm(x, *P.fp_ln, eps=eps, split="only" if split else None), P.fp_w, P.fp_b)
         # positional grouped conv (k=128, pad=64, drop last frame) as G windowed GEMMs + GELU + residual
         G, cg, kpos = c.num_conv_pos_embedding_groups, d // c.num_conv_pos_embedding_groups, c.num_conv_pos_embeddings
         cgp = P.pos_cg
@@ -404,96 +417,32 @@ class Wav2Vec2Model(nn.Module):
             ops.gemm(xp, P.pos_w, P.pos_b, h, ops.ACT_GELU, out=y, M=B * T, N=cg, K=kpos * cgp, lda=cgp, rows_per_batch=T,
                      a_batch_stride=G * Tp * cgp, ldw=kpos * cgp, ldc=d, batch=G, strideA=Tp * cgp,
                      strideW=cg * kpos * cgp, strideC=cg, strideBias=cg, strideR=cg)
-        scale, eps = (d // H) ** -0.5, c.layer_norm_eps
-        if P.fold and ops.FOLD_LN and c.do_stable_layer_norm:
-            # pre-LN blocks without LayerNorm launches: every residual GEMM also writes the row statistics of what it
-            # stored, the GEMM that consumes LN(h) applies them in its epilogue (include/msmd_hip.h msmd_gemm_ln)
-            h, st = y, None                     # y comes from the grouped positional conv: no statistics yet
-            for li, L in enumerate(P.layers):
-                if st is None:
-                    qkv = ops.gemm(ops.layernorm(h, *L.ln1, eps=eps), L.wqkv, L.bqkv)
-                else:
-                    qkv = ops.gemm_ln(h, L.f_qkv[0], L.f_qkv[2], a_stats=st, w_colsum=L.f_qkv[1], eps=eps)
-                nxt = P.layers[li + 1].f_qkv[0] if li + 1 < len(P.layers) else None
-                a = ops.attention(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], H, scale,
-                                  prefetch=(L.wo, L.f_w1[0], L.w2, nxt))
-                h, st = ops.gemm_ln(a, L.wo, L.bo, h, stats_out=True)
-                f = ops.gemm_ln(h, L.f_w1[0], L.f_w1[2], act=ops.ACT_GELU, a_stats=st, w_colsum=L.f_w1[1], eps=eps)
-                h, st = ops.gemm_ln(f, L.w2, L.b2, h, stats_out=True)
-            return ops.layernorm(h, *P.enc_ln, eps=eps)
-        if c.do_stable_layer_norm:
-            # HubertEncoderStableLayerNorm: pre-LN blocks, ONE LayerNorm after the last layer
-            h = y
-            for L in P.layers:
-                qkv = ops.gemm(ops.layernorm(h, *L.ln1, eps=c.layer_norm_eps), L.wqkv, L.bqkv)
-                a = ops.attention(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], H, (d // H) ** -0.5)
-                h = ops.gemm(a, L.wo, L.bo, residual=h)
-                f = ops.gemm(ops.layernorm(h, *L.ln2, eps=c.layer_norm_eps), L.w1, L.b1, act=ops.ACT_GELU)
-                h = ops.gemm(f, L.w2, L.b2, residual=h)
-            return ops.layernorm(h, *P.enc_ln, eps=c.layer_norm_eps)
-        h = ops.layernorm(y, *P.enc_ln, eps=c.layer_norm_eps)
-        if P.fold and ops.FOLD_LN:
-            # post-LN blocks without LayerNorm launches: u = the un-normalised rows a residual GEMM stored (+ their row
-            # statistics); LN(u) is applied on the fly where it is the next GEMM's operand (folded weights) and where it
-            # is the next residual (r_stats).  Only the last layer's LN2 is a kernel of its own.
-            u = st = ln = None
-            for n, L in enumerate(P.layers):
-                if n == 0:
-                    qkv = ops.gemm(h, L.wqkv, L.bqkv)
-                else:
-                    qkv = ops.gemm_ln(u, L.f_qkv[0], L.f_qkv[2], a_stats=st, w_colsum=L.f_qkv[1], eps=eps)
-                nxt = P.layers[n + 1].f_qkv[0] if n + 1 < len(P.layers) else None
-                a = ops.attention(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], H, scale,
-                                  prefetch=(L.wo, L.f_w1[0], L.w2, nxt))
-                if n == 0:
-                    u1, st1 = ops.gemm_ln(a, L.wo, L.bo, h, stats_out=True)
-                else:
-                    u1, st1 = ops.gemm_ln(a, L.wo, L.bo, u, r_stats=st, r_gamma=ln[0], r_beta=ln[1], stats_out=True, eps=eps)
-                f = ops.gemm_ln(u1, L.f_w1[0], L.f_w1[2], act=ops.ACT_GELU, a_stats=st1, w_colsum=L.f_w1[1], eps=eps)
-                u, st = ops.gemm_ln(f, L.w2, L.b2, u1, r_stats=st1, r_gamma=L.ln1[0], r_beta=L.ln1[1], stats_out=True, eps=eps)
-                ln = L.ln2
-            return ops.layernorm(u, *ln, eps=eps)
+        h = Rows(y)                         # y comes from the grouped positional conv: no statistics yet
+        if not pre:
+            h = norm(h, P.enc_ln, split=split, eps=eps)
         for li, L in enumerate(P.layers):
-            qkv = ops.gemm(h, L.wqkv, L.bqkv)
-            nxt = P.layers[li + 1].wqkv if li + 1 < len(P.layers) else None
-            a = ops.attention(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], H, (d // H) ** -0.5,
-                              prefetch=None if P.split else (L.wo, L.w1, L.w2, nxt))
-            h = ops.layernorm(ops.gemm(a, L.wo, L.bo, residual=h), *L.ln1, eps=c.layer_norm_eps)
-            f = ops.gemm(h, L.w1, L.b1, act=ops.ACT_GELU)
-            h = ops.layernorm(ops.gemm(f, L.w2, L.b2, residual=h), *L.ln2, eps=c.layer_norm_eps)
-        return h
-
-    def _encode_features_split(self, x, P):
-        """encode_features (post-LN encoder) in the parity-grade speed mode.  Data flow per layer: LayerNorm writes the
-        row twice in one pass (fp32 = the next residual, split = the next GEMM's A operand); the QKV GEMM writes split
-        Q / K / V, the split attention writes split O, the FFN's GELU output goes GEMM -> GEMM in split storage; every
-        residual add and LayerNorm input stays fp32.  No standalone conversion pass."""
-        c = self.config
-        B, T, _ = x.shape
-        H, d, eps = c.num_attention_heads, c.hidden_size, c.layer_norm_eps
-        h = ops.gemm(ops.layernorm(x, *P.fp_ln, eps=eps, split="only"), P.fp_w, P.fp_b)          # fp32 (B, T, d)
-        G, cg, kpos = c.num_conv_pos_embedding_groups, d // c.num_conv_pos_embedding_groups, c.num_conv_pos_embeddings
-        cgp = P.pos_cg
-        xp = ops.group_pad(h, G, kpos // 2, cg_out=cgp, split=True)
-        Tp = T + kpos
-        y = torch.empty_like(h)
-        ops.gemm(xp, P.pos_w, P.pos_b, h, ops.ACT_GELU, out=y, M=B * T, N=cg, K=kpos * cgp, lda=cgp, rows_per_batch=T,
-                 a_batch_stride=G * Tp * cgp, ldw=kpos * cgp, ldc=d, batch=G, strideA=Tp * cgp, strideW=cg * kpos * cgp,
-                 strideC=cg, strideBias=cg, strideR=cg)
-        h, hs = ops.layernorm(y, *P.enc_ln, eps=eps, split="both")
-        scale = (d // H) ** -0.5
-        for li, L in enumerate(P.layers):
-            qkv = ops.gemm(hs, L.wqkv, L.bqkv, out_dtype=ops.SPLIT)
-            # (no weight prefetch here: measured 8.90 -> 8.99 ms -- the three-MFMA GEMMs hide the cold weights themselves)
-            a = ops.attention(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], H, scale)           # split out
-            h, hs = ops.layernorm(ops.gemm(a, L.wo, L.bo, residual=h), *L.ln1, eps=eps, split="both")
-            f = ops.gemm(hs, L.w1, L.b1, act=ops.ACT_GELU, out_dtype=ops.SPLIT)
-            t = ops.gemm(f, L.w2, L.b2, residual=h)
-            if li + 1 < len(P.layers):
-                h, hs = ops.layernorm(t, *L.ln2, eps=eps, split="both")
+            nxt = P.layers[li + 1] if li + 1 < len(P.layers) else None
+            f_qkv, f_w1 = (L.f_qkv, L.f_w1) if fold else (None, None)
+            qkv = project(norm(h, L.ln1, defer=fold, eps=eps) if pre else h, L.wqkv, L.bqkv, f_qkv, eps=eps)
+            # the attention launch pulls the weights of the launches behind it through the memory-side cache
+            if fold:
+                prefetch = (L.wo, f_w1[0], L.w2, nxt.f_qkv[0] if nxt else None)
+            elif pre or split:
+                # (split: measured 8.90 -> 8.99 ms -- the three-MFMA GEMMs hide the cold weights themselves)
+                prefetch = None
             else:
-                h = ops.layernorm(t, *L.ln2, eps=eps)
-        return h
+                prefetch = (L.wo, L.w1, L.w2, nxt.wqkv if nxt else None)
+            a = ops.attention(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], H, scale, prefetch=prefetch)
+            h = add(a, L.wo, L.bo, h, stats=fold, eps=eps)
+            if not pre:
+                h = norm(h, L.ln1, defer=fold, split=split, eps=eps)
+            f = project(norm(h, L.ln2, defer=fold, eps=eps) if pre else h, L.w1, L.b1, f_w1, act=ops.ACT_GELU, eps=eps)
+            h = add(f, L.w2, L.b2, h, stats=fold, eps=eps)
+            if not pre:     # the last layer's rows leave as fp32 alone
+                h = norm(h, L.ln2, defer=fold, split=split and nxt is not None, eps=eps)
+        if pre:
+            h = norm(h, P.enc_ln, defer=fold, eps=eps)
+        return materialise(h, eps=eps).x
 
     def encode(self, audio, output_fps=25, frame_num=None, dtype=torch.bfloat16, pad=True):
         """Whole encoder from raw (B, L) audio; pad=True applies the reference's pad_audio plan
