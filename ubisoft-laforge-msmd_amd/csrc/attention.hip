@@ -9,6 +9,7 @@
 //   bf16: ds_read_b64_tr_b16 transposed reads from a row-major [key][d] LDS image (no transpose pass),
 //   fp32: ds_read_b32 from a padded [key][d] image (parity mode, exact fp32 MFMA 16x16x4).
 #include "common.h"
+#include "attention_tiles.h"
 
 struct AttnArgs {
   const void* Q; const void* K; const void* V; void* O;
@@ -25,7 +26,92 @@ struct AttnArgs {
   long pf_bytes[4] = {0, 0, 0, 0};
 };
 
-typedef short s16x4 __attribute__((ext_vector_type(4)));
+// ---- Pieces the three forward kernels share (the LDS layouts: attention_tiles.h).  They take scalars and fragments by VALUE,
+// not the argument struct: only in that form does every kernel keep the register allocation it had with the code inline.
+// Lane / query geometry of a workgroup of NW waves: wave wid owns 16 queries, the lane's is `query` (fr = lane & 15 on the MFMA
+// lane, fq = lane >> 4 the accumulator row group).  (Clamping it to qrow in here moved a kernarg load behind the prologue's first wait.)
+struct AttnLane { int tid, lane, wid, fr, fq, b, h, query; };
+template <int NW> __device__ __forceinline__ AttnLane attn_lane() {
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int fr = lane & 15, fq = lane >> 4;
+  const int b = blockIdx.z, h = blockIdx.y;
+  const int query = blockIdx.x * (16 * NW) + wid * 16 + fr;
+  return {tid, lane, wid, fr, fq, b, h, query};
+}
+// Weight-prefetch sweep (msmd_attention_prefetch): every wave of the grid loads 1 KB (16 bytes per lane) per step, the wave at
+// byte `wave0` first, `stride` bytes further on every step; of a range only its whole 1 KB wave-loads are issued
+struct PfSweep { long stride, wave0; };
+__device__ __forceinline__ PfSweep pf_sweep(int nt, int tid) {
+  const long stride = (long)gridDim.x * gridDim.y * gridDim.z * nt * 16;
+  const long wave0 = ((((long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * nt + (tid & ~63)) * 16;
+  return {stride, wave0};
+}
+// Ragged-tile and explicit-mask test of a 64-key tile (query = lane & 15; keys kv0 + 16 f + 4 fq + e).  The caller runs it only
+// where a test can fail: `kv0 + 64 > Tk || mask`, the last, ragged tile and an explicit mask (both wave-uniform conditions)
+__device__ __forceinline__ void mask_tile(const uint8_t* mask, int Tk, int kv0, int qrow, int fq, f32x4 (&s)[4]) {
+#pragma unroll
+  for (int f = 0; f < 4; ++f)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int key = kv0 + 16 * f + 4 * fq + e;
+      bool dead = key >= Tk;
+      if (mask && !dead) dead = mask[(long)qrow * Tk + key] != 0;
+      if (dead) s[f][e] = -INFINITY;    // (fragments f >= nf are all dead: their exp is skipped, p = 0)
+    }
+}
+
+// Dropout of the fragment pair (s[2 pr], s[2 pr + 1]) = keys 32 block .. 32 block + 31 of the row: one generator block per
+// fragment pair (common.h: dropout_value16), the same Philox stream in every forward kernel and in the backward
+__device__ __forceinline__ unsigned long dropout_rowbase(int H, int Tq, int b, int h, int qrow) { return ((unsigned long)(b * H + h) * Tq + qrow) * 128ul; }
+template <int NF> __device__ __forceinline__ void dropout_pair(const unsigned long* rng_state, unsigned site, unsigned thr, unsigned long rowbase,
+                                             int block, int fq, int pr, f32x4 (&s)[NF]) {
+  const Philox4 r = dropout_bits(rng_state, site, rowbase + (unsigned long)(4 * block + fq));
+#pragma unroll
+  for (int o = 0; o < 2; ++o) {
+    if (2 * pr + o >= NF) continue;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) s[2 * pr + o][e] = dropout_value16(r, e, o) >= thr ? s[2 * pr + o][e] : 0.f;
+  }
+}
+
+// O^T += V^T . P^T over one fragment pair (32 keys per MFMA), 16-bit form.  pv_pack16: the pair's probabilities s0 / s1 as the
+// B operand.  pv_step16: the MFMA of 16-column block d; r0 / r1 = the V image rows this lane addresses for the two fragments
+// (transposed read: lane i = 4 q' + p' of each 16-lane group addresses row key0 + q', cols d0 + 4 p')
+template <typename T> __device__ __forceinline__ u32x4 pv_pack16(const f32x4 s0, const f32x4 s1) {
+  const typename Vec8T<T>::type pbv = {(T)s0[0], (T)s0[1], (T)s0[2], (T)s0[3], (T)s1[0], (T)s1[1], (T)s1[2], (T)s1[3]};
+  return __builtin_bit_cast(u32x4, pbv);
+}
+template <typename T> __device__ __forceinline__ f32x4 pv_step16(const unsigned char* sV, int r0, int r1, int d, int pp, const u32x4 pb, const f32x4 acc) {
+  const u32x2 v0 = tr_read(sV + img_tr(r0, d, pp)), v1 = tr_read(sV + img_tr(r1, d, pp));
+  return mfma16<T>(u32x4{v0[0], v0[1], v1[0], v1[1]}, pb, acc);
+}
+// ... split-pair form of the step: ph / pl = the probabilities split in registers, O = Vh.Ph + (Vh.Pl + Vl.Ph) / 2048 (o0 + o1 / 2048)
+__device__ __forceinline__ void pv_step_split(const unsigned char* sV, int r0, int r1, int d, int pp, const u32x4 ph, const u32x4 pl,
+                                              f32x4& o0, f32x4& o1) {
+  const int ch = (d >> 1) * 8 + (d & 1) * 2 + (pp >> 1);   // hi chunk of this d block; lo is 4 chunks further
+  const int b8 = (pp & 1) * 8;
+  const u32x2 h0 = tr_read(sV + vsplit_off(r0, ch) + b8), h1 = tr_read(sV + vsplit_off(r1, ch) + b8);
+  const u32x2 l0 = tr_read(sV + vsplit_off(r0, ch + 4) + b8), l1 = tr_read(sV + vsplit_off(r1, ch + 4) + b8);
+  const u32x4 vh = u32x4{h0[0], h0[1], h1[0], h1[1]}, vl = u32x4{l0[0], l0[1], l1[0], l1[1]};
+  o0 = mfma16<f16_t>(vh, ph, o0);
+  o1 = mfma16<f16_t>(vh, pl, o1);
+  o1 = mfma16<f16_t>(vl, ph, o1);
+}
+
+// acc_o[d][e] = O^T[dim 16 d + 4 fq + e][query] -> the query's 64-element row Op, scaled by inv = 1 / (l (1 - p_drop)) on the way out
+template <typename T> __device__ __forceinline__ void store_o(float inv, T* Op, int fq, const f32x4 (&acc_o)[4]) {
+#pragma unroll
+  for (int d = 0; d < 4; ++d) {
+    float o[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = acc_o[d][e] * inv;
+    if constexpr (sizeof(T) == 2)
+      *(typename Vec4T<T>::type*)(Op + 16 * d + 4 * fq) = pack4<T>(o[0], o[1], o[2], o[3]);
+    else
+      *(f32x4*)(Op + 16 * d + 4 * fq) = f32x4{o[0], o[1], o[2], o[3]};
+  }
+}
+
 
 // NW waves per workgroup = 16 NW query rows sharing every staged K / V tile (short sequences fit one workgroup per
 // (batch, head): T = 111 -> 7 waves, T = 200 -> 13 waves, so K / V are read from HBM / L2 once instead of once per
@@ -40,12 +126,9 @@ __global__ __launch_bounds__(64 * NW) void attn_kernel(const AttnArgs p) {
   unsigned char* sK = smem;
   unsigned char* sV = smem + 64 * KROW;
 
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int fr = lane & 15, fq = lane >> 4;
-  const int b = blockIdx.z, h = blockIdx.y;
   constexpr int NT = 64 * NW;
-  const int query = blockIdx.x * (16 * NW) + wid * 16 + fr;
-  const int qrow = query < p.Tq ? query : p.Tq - 1;
+  const auto [tid, lane, wid, fr, fq, b, h, query] = attn_lane<NW>();
+  const int qrow = query < p.Tq ? query : p.Tq - 1;   // the row it reads (clamped: a lane past Tq computes and stores nothing)
   const T* Qp = (const T*)p.Q + (long)b * p.qb + (long)qrow * p.qt + h * 64;
   const T* Kb = (const T*)p.K + (long)b * p.kb + h * 64;
   const T* Vb = (const T*)p.V + (long)b * p.vb + h * 64;
@@ -64,7 +147,7 @@ __global__ __launch_bounds__(64 * NW) void attn_kernel(const AttnArgs p) {
   // t is being multiplied, so the staging latency (~2 us per 64-key tile) is off the critical path.
   constexpr int NPF = (64 * NCH + NT - 1) / NT;   // 16-byte chunks of each of K, V a thread carries per tile
   u32x4 pk[NPF], pv[NPF];
-  auto prefetch = [&](int kv0) {
+  auto prefetch = [&, tid = tid](int kv0) {   // (C++17 lambdas cannot capture a structured binding: tid by copy)
 #pragma unroll
     for (int i = 0; i < NPF; ++i) {
       // unconditional loads of clamped keys (zeroed on the way into LDS): loads under a run-time test go out one piece at a time
@@ -83,8 +166,7 @@ __global__ __launch_bounds__(64 * NW) void attn_kernel(const AttnArgs p) {
   if (p.pf_bytes[0] > 0) {
     typedef __attribute__((address_space(3))) void lds_sink_t;
     typedef __attribute__((address_space(1))) const void gbl_src_t;
-    const long stride = (long)gridDim.x * gridDim.y * gridDim.z * NT * 16;
-    const long wave0 = ((((long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * NT + (tid & ~63)) * 16;
+    const auto [stride, wave0] = pf_sweep(NT, tid);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const char* base = (const char*)p.pf_ptr[r];
@@ -103,13 +185,8 @@ __global__ __launch_bounds__(64 * NW) void attn_kernel(const AttnArgs p) {
         const int row = c / NCH, ch = c % NCH;
         const bool live = kv0 + row < p.Tk;
         const u32x4 kk = live ? pk[i] : u32x4{0, 0, 0, 0}, vv = live ? pv[i] : u32x4{0, 0, 0, 0};
-        if constexpr (BF) {
-          *(u32x4*)(sK + row * 128 + ((ch ^ ((row >> 1) & 7)) << 4)) = kk;
-          *(u32x4*)(sV + row * 128 + ((((ch >> 1) ^ ((row >> 1) & 3)) << 5) + ((ch & 1) << 4))) = vv;
-        } else {
-          *(u32x4*)(sK + row * 256 + ((ch ^ (row & 15)) << 4)) = kk;
-          *(u32x4*)(sV + row * 272 + (ch << 4)) = vv;
-        }
+        *(u32x4*)(sK + (BF ? k16_off(row, ch) : k256_off(row, ch))) = kk;
+        *(u32x4*)(sV + (BF ? img_off(row, ch) : v32_off(row, ch))) = vv;
       }
     }
     __syncthreads();
@@ -127,13 +204,13 @@ __global__ __launch_bounds__(64 * NW) void attn_kernel(const AttnArgs p) {
       if constexpr (BF) {
 #pragma unroll
         for (int g = 0; g < 2; ++g) {
-          const u32x4 a = *(const u32x4*)(sK + row * 128 + (((4 * g + fq) ^ ((row >> 1) & 7)) << 4));
+          const u32x4 a = *(const u32x4*)(sK + k16_off(row, 4 * g + fq));
           s[f] = mfma16<T>(a, qf[g], s[f]);
         }
       } else {
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-          const u32x4 a = *(const u32x4*)(sK + row * 256 + (((4 * g + fq) ^ (row & 15)) << 4));
+          const u32x4 a = *(const u32x4*)(sK + k256_off(row, 4 * g + fq));
 #pragma unroll
           for (int e = 0; e < 4; ++e)
             s[f] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a[e]), __uint_as_float(qf[g][e]), s[f], 0, 0, 0);
@@ -143,17 +220,7 @@ __global__ __launch_bounds__(64 * NW) void attn_kernel(const AttnArgs p) {
 
     // ---- mask, online softmax (query = lane & 15; keys 16 f + 4 fq + e).  Keys are only tested where a test can fail:
     // in the last, ragged tile and under an explicit mask (both wave-uniform conditions).
-    if (kv0 + 64 > p.Tk || p.mask) {
-#pragma unroll
-      for (int f = 0; f < 4; ++f)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int key = kv0 + 16 * f + 4 * fq + e;
-          bool dead = key >= p.Tk;
-          if (p.mask && !dead) dead = p.mask[(long)qrow * p.Tk + key] != 0;
-          if (dead) s[f][e] = -INFINITY;    // (fragments f >= nf are all dead: their exp below is skipped, p = 0)
-        }
-    }
+    if (kv0 + 64 > p.Tk || p.mask) mask_tile(p.mask, p.Tk, kv0, qrow, fq, s);
     float mx = -INFINITY, ps = 0.f, alpha;
     if constexpr (BF) {
       // 16-bit storage mode: p = exp2(s c - m c) with c = scale log2(e) > 0 -- ONE fma + ONE v_exp_f32 per score (was
@@ -208,15 +275,9 @@ __global__ __launch_bounds__(64 * NW) void attn_kernel(const AttnArgs p) {
     l_run = l_run * alpha + ps;
     if (p.p_drop > 0.f) {  // drop probabilities AFTER the softmax denominator; the 1/(1-p) factor is applied to O
       const unsigned thr = dropout_threshold16(p.p_drop);
-      const unsigned long rowbase = ((unsigned long)(b * p.H + h) * p.Tq + qrow) * 128ul;
+      const unsigned long rowbase = dropout_rowbase(p.H, p.Tq, b, h, qrow);
 #pragma unroll
-      for (int pr = 0; pr < 2; ++pr) {   // one generator block per fragment pair (common.h: dropout_value16)
-        const Philox4 r = dropout_bits(p.rng_state, p.site, rowbase + (unsigned long)(4 * ((kv0 >> 5) + pr) + fq));
-#pragma unroll
-        for (int o = 0; o < 2; ++o)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) s[2 * pr + o][e] = dropout_value16(r, e, o) >= thr ? s[2 * pr + o][e] : 0.f;
-      }
+      for (int pr = 0; pr < 2; ++pr) dropout_pair(p.rng_state, p.site, thr, rowbase, (kv0 >> 5) + pr, fq, pr, s);
     }
     if (!__all(alpha == 1.0f)) {   // the running maximum moved for some query of this wave: rescale the accumulators
 #pragma unroll
@@ -231,22 +292,12 @@ __global__ __launch_bounds__(64 * NW) void attn_kernel(const AttnArgs p) {
       for (int pr = 0; pr < 2; ++pr) {
         const int f0 = 2 * pr, f1 = 2 * pr + 1;
         if (f0 >= nf) continue;      // this pair of key fragments is padding
-        typedef typename Vec8T<T>::type V8;
-        const V8 pbv = V8{(T)s[f0][0], (T)s[f0][1], (T)s[f0][2], (T)s[f0][3],
-                          (T)s[f1][0], (T)s[f1][1], (T)s[f1][2], (T)s[f1][3]};
-        const u32x4 pb = __builtin_bit_cast(u32x4, pbv);
-        // transposed read: lane i = 4 q' + p' of each 16-lane group addresses row key0 + q', cols d0 + 4 p'
+        const u32x4 pb = pv_pack16<T>(s[f0], s[f1]);
         const int qp = fr >> 2, pp = fr & 3;
 #pragma unroll
         for (int d = 0; d < 4; ++d) {
           const int r0 = 16 * f0 + 4 * fq + qp, r1 = 16 * f1 + 4 * fq + qp;
-          const s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-              (s16x4 __attribute__((address_space(3)))*)(sV + r0 * 128 + ((d ^ ((r0 >> 1) & 3)) << 5) + pp * 8));
-          const s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-              (s16x4 __attribute__((address_space(3)))*)(sV + r1 * 128 + ((d ^ ((r1 >> 1) & 3)) << 5) + pp * 8));
-          typedef short s16x8 __attribute__((ext_vector_type(8)));
-          const s16x8 va = s16x8{v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-          acc_o[d] = mfma16<T>(__builtin_bit_cast(u32x4, va), pb, acc_o[d]);
+          acc_o[d] = pv_step16<T>(sV, r0, r1, d, pp, pb, acc_o[d]);
         }
       }
     } else {
@@ -257,27 +308,15 @@ __global__ __launch_bounds__(64 * NW) void attn_kernel(const AttnArgs p) {
           const int krow = 16 * f + 4 * fq + e;
 #pragma unroll
           for (int d = 0; d < 4; ++d) {
-            const float a = *(const float*)(sV + krow * 272 + (16 * d + fr) * 4);
+            const float a = *(const float*)(sV + v32_off(krow, 0) + (16 * d + fr) * 4);
             acc_o[d] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, s[f][e], acc_o[d], 0, 0, 0);
           }
         }
     }
   }
 
-  if (query < p.Tq) {
-    const float inv = 1.0f / (l_run * (1.0f - p.p_drop));
-    T* Op = (T*)p.O + (long)b * p.ob + (long)query * p.ot + h * 64;
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-      float o[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = acc_o[d][e] * inv;
-      if constexpr (BF)
-        *(typename Vec4T<T>::type*)(Op + 16 * d + 4 * fq) = pack4<T>(o[0], o[1], o[2], o[3]);
-      else
-        *(f32x4*)(Op + 16 * d + 4 * fq) = f32x4{o[0], o[1], o[2], o[3]};
-    }
-  }
+  if (query < p.Tq)
+    store_o<T>(1.0f / (l_run * (1.0f - p.p_drop)), (T*)p.O + (long)b * p.ob + (long)query * p.ot + h * 64, fq, acc_o);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -302,11 +341,8 @@ __global__ __launch_bounds__(64 * NW) void attn_whole_kernel(const AttnArgs p) {
   // workgroups share a CU where the full 208-row images allowed three) + 1 KB prefetch sink
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* sK = smem;
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int fr = lane & 15, fq = lane >> 4;
-  const int b = blockIdx.z, h = blockIdx.y;
-  const int query = blockIdx.x * (16 * NW) + wid * 16 + fr;
-  const int qrow = query < p.Tq ? query : p.Tq - 1;
+  const auto [tid, lane, wid, fr, fq, b, h, query] = attn_lane<NW>();
+  const int qrow = query < p.Tq ? query : p.Tq - 1;   // the row it reads (clamped: a lane past Tq computes and stores nothing)
   const T* Qp = (const T*)p.Q + (long)b * p.qb + (long)qrow * p.qt + h * 64;
   const T* Kb = (const T*)p.K + (long)b * p.kb + h * 64;
   const T* Vb = (const T*)p.V + (long)b * p.vb + h * 64;
@@ -335,8 +371,8 @@ __global__ __launch_bounds__(64 * NW) void attn_whole_kernel(const AttnArgs p) {
     const int c = tid + i * NT, row = c >> 3, ch = c & 7;
     if (row < rows) {
       const bool live = row < p.Tk;
-      *(u32x4*)(sK + row * 128 + ((ch ^ ((row >> 1) & 7)) << 4)) = live ? pk[i] : u32x4{0, 0, 0, 0};
-      *(u32x4*)(sV + row * 128 + ((((ch >> 1) ^ ((row >> 1) & 3)) << 5) + ((ch & 1) << 4))) = live ? pv[i] : u32x4{0, 0, 0, 0};
+      *(u32x4*)(sK + k16_off(row, ch)) = live ? pk[i] : u32x4{0, 0, 0, 0};
+      *(u32x4*)(sV + img_off(row, ch)) = live ? pv[i] : u32x4{0, 0, 0, 0};
     }
   }
   __syncthreads();
@@ -352,8 +388,7 @@ __global__ __launch_bounds__(64 * NW) void attn_whole_kernel(const AttnArgs p) {
     typedef __attribute__((address_space(3))) void lds_sink_t;
     const unsigned sink_lds = (unsigned)(uintptr_t)(lds_sink_t*)smem + 2 * rows * 128;   // LDS byte address of the sink (M0 for the DMA)
     unsigned m0_keep;                                                         // M0 is restored around every DMA
-    const long stride = (long)gridDim.x * gridDim.y * gridDim.z * NT * 16;
-    const long wave0 = ((((long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * NT + (tid & ~63)) * 16;
+    const auto [stride, wave0] = pf_sweep(NT, tid);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const char* base = (const char*)p.pf_ptr[r];
@@ -376,7 +411,7 @@ __global__ __launch_bounds__(64 * NW) void attn_whole_kernel(const AttnArgs p) {
     const int row = 16 * f + fr;
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
-      const u32x4 a = *(const u32x4*)(sK + row * 128 + (((4 * g + fq) ^ ((row >> 1) & 7)) << 4));
+      const u32x4 a = *(const u32x4*)(sK + k16_off(row, 4 * g + fq));
       s[f] = mfma16<T>(a, qf[g], s[f]);
     }
   }
@@ -430,17 +465,11 @@ __global__ __launch_bounds__(64 * NW) void attn_whole_kernel(const AttnArgs p) {
   if (p.p_drop > 0.f) {   // training: drop probabilities AFTER the denominator (same Philox stream as attn_kernel and the
                           // backward: common.h dropout_value16); the 1 / (1 - p) factor goes on O
     const unsigned thr = dropout_threshold16(p.p_drop);
-    const unsigned long rowbase = ((unsigned long)(b * p.H + h) * p.Tq + qrow) * 128ul;
+    const unsigned long rowbase = dropout_rowbase(p.H, p.Tq, b, h, qrow);
 #pragma unroll
     for (int pr = 0; pr < (NF + 1) / 2; ++pr) {   // one generator block per fragment pair (common.h: dropout_value16)
       if (2 * pr >= nf) continue;
-      const Philox4 r = dropout_bits(p.rng_state, p.site, rowbase + (unsigned long)(4 * pr + fq));
-#pragma unroll
-      for (int o = 0; o < 2; ++o) {
-        if (2 * pr + o >= NF) continue;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) s[2 * pr + o][e] = dropout_value16(r, e, o) >= thr ? s[2 * pr + o][e] : 0.f;
-      }
+      dropout_pair(p.rng_state, p.site, thr, rowbase, pr, fq, pr, s);
     }
   }
 
@@ -448,34 +477,19 @@ __global__ __launch_bounds__(64 * NW) void attn_whole_kernel(const AttnArgs p) {
   f32x4 acc_o[4];
 #pragma unroll
   for (int d = 0; d < 4; ++d) acc_o[d] = f32x4{0.f, 0.f, 0.f, 0.f};
-  typedef typename Vec8T<T>::type V8;
-  typedef short s16x8 __attribute__((ext_vector_type(8)));
   const int qp = fr >> 2, pp = fr & 3;
 #pragma unroll
   for (int pr = 0; pr < (NF + 1) / 2; ++pr) {
     const int f0 = 2 * pr, f1 = 2 * pr + 1;
     if (f0 >= nf) continue;
     const f32x4 s1 = f1 < NF ? s[f1 < NF ? f1 : 0] : f32x4{0.f, 0.f, 0.f, 0.f};   // (f1 >= nf: zeros from the S loop)
-    const V8 pbv = V8{(T)s[f0][0], (T)s[f0][1], (T)s[f0][2], (T)s[f0][3], (T)s1[0], (T)s1[1], (T)s1[2], (T)s1[3]};
-    const u32x4 pb = __builtin_bit_cast(u32x4, pbv);
+    const u32x4 pb = pv_pack16<T>(s[f0], s1);
     const int r0 = 16 * f0 + 4 * fq + qp, r1 = f1 < NF ? r0 + 16 : r0;   // f1's rows are staged (zero-filled); past NF: any valid row, p = 0
 #pragma unroll
-    for (int d = 0; d < 4; ++d) {
-      const s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-          (s16x4 __attribute__((address_space(3)))*)(sV + r0 * 128 + ((d ^ ((r0 >> 1) & 3)) << 5) + pp * 8));
-      const s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-          (s16x4 __attribute__((address_space(3)))*)(sV + r1 * 128 + ((d ^ ((r1 >> 1) & 3)) << 5) + pp * 8));
-      const s16x8 va = s16x8{v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-      acc_o[d] = mfma16<T>(__builtin_bit_cast(u32x4, va), pb, acc_o[d]);
-    }
+    for (int d = 0; d < 4; ++d) acc_o[d] = pv_step16<T>(sV, r0, r1, d, pp, pb, acc_o[d]);
   }
-  if (query < p.Tq) {
-    const float inv = 1.0f / (ps * (1.0f - p.p_drop));
-    T* Op = (T*)p.O + (long)b * p.ob + (long)query * p.ot + h * 64;
-#pragma unroll
-    for (int d = 0; d < 4; ++d)
-      *(typename Vec4T<T>::type*)(Op + 16 * d + 4 * fq) = pack4<T>(acc_o[d][0] * inv, acc_o[d][1] * inv, acc_o[d][2] * inv, acc_o[d][3] * inv);
-  }
+  if (query < p.Tq)
+    store_o<T>(1.0f / (ps * (1.0f - p.p_drop)), (T*)p.O + (long)b * p.ob + (long)query * p.ot + h * 64, fq, acc_o);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the prefetch loads land in this workgroup's LDS: wait before it is freed
 }
 
@@ -487,19 +501,15 @@ __global__ __launch_bounds__(64 * NW) void attn_whole_kernel(const AttnArgs p) {
 // Same structure as attn_kernel (S computed swapped, V^T operand by ds_read_b64_tr_b16 from the row-major image);
 // LDS rows are 256 bytes: K chunks XOR (row & 15) (conflict-free ds_read_b128), V chunks XOR the dual-use pattern of
 // cdna_hip_programming.md T10 (b).  TO = float (fp32 O) or f16_t (O in split storage for the out-projection GEMM).
-__device__ __forceinline__ int vsw(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
 
 template <typename TO, int NW>
 __global__ __launch_bounds__(64 * NW) void attn_split_kernel(const AttnArgs p) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[2 * 64 * 256];
   unsigned char* sK = smem;
   unsigned char* sV = smem + 64 * 256;
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int fr = lane & 15, fq = lane >> 4;
-  const int b = blockIdx.z, h = blockIdx.y;
   constexpr int NT = 64 * NW;
-  const int query = blockIdx.x * (16 * NW) + wid * 16 + fr;
-  const int qrow = query < p.Tq ? query : p.Tq - 1;
+  const auto [tid, lane, wid, fr, fq, b, h, query] = attn_lane<NW>();
+  const int qrow = query < p.Tq ? query : p.Tq - 1;   // the row it reads (clamped: a lane past Tq computes and stores nothing)
   const f16_t* Qp = (const f16_t*)p.Q + 2 * ((long)b * p.qb + (long)qrow * p.qt) + h * 128;
   const f16_t* Kb = (const f16_t*)p.K + 2 * (long)b * p.kb + h * 128;
   const f16_t* Vb = (const f16_t*)p.V + 2 * (long)b * p.vb + h * 128;
@@ -519,7 +529,7 @@ __global__ __launch_bounds__(64 * NW) void attn_split_kernel(const AttnArgs p) {
   u32x4 pk[NPF], pv[NPF];
   // (unconditional loads of clamped keys, zeroed on the way into LDS: loads under a run-time test are closed with
   // s_waitcnt vmcnt(0) per block, i.e. they go out one piece at a time -- see attn_whole_kernel)
-  auto prefetch = [&](int kv0) {
+  auto prefetch = [&, tid = tid](int kv0) {   // (C++17 lambdas cannot capture a structured binding: tid by copy)
 #pragma unroll
     for (int i = 0; i < NPF; ++i) {
       const int c = min(tid + i * NT, 64 * 16 - 1);
@@ -539,8 +549,8 @@ __global__ __launch_bounds__(64 * NW) void attn_split_kernel(const AttnArgs p) {
       if (c < 64 * 16) {
         const int row = c >> 4, ch = c & 15;
         const bool live = kv0 + row < p.Tk;
-        *(u32x4*)(sK + row * 256 + ((ch ^ (row & 15)) << 4)) = live ? pk[i] : u32x4{0, 0, 0, 0};
-        *(u32x4*)(sV + row * 256 + ((ch ^ vsw(row)) << 4)) = live ? pv[i] : u32x4{0, 0, 0, 0};
+        *(u32x4*)(sK + k256_off(row, ch)) = live ? pk[i] : u32x4{0, 0, 0, 0};
+        *(u32x4*)(sV + vsplit_off(row, ch)) = live ? pv[i] : u32x4{0, 0, 0, 0};
       }
     }
     __syncthreads();
@@ -556,8 +566,8 @@ __global__ __launch_bounds__(64 * NW) void attn_split_kernel(const AttnArgs p) {
       const int row = 16 * f + fr;
 #pragma unroll
       for (int g = 0; g < 2; ++g) {
-        const u32x4 kh = *(const u32x4*)(sK + row * 256 + (((8 * g + fq) ^ (row & 15)) << 4));
-        const u32x4 kl = *(const u32x4*)(sK + row * 256 + (((8 * g + 4 + fq) ^ (row & 15)) << 4));
+        const u32x4 kh = *(const u32x4*)(sK + k256_off(row, 8 * g + fq));
+        const u32x4 kl = *(const u32x4*)(sK + k256_off(row, 8 * g + 4 + fq));
         s0 = mfma16<f16_t>(kh, qh[g], s0);
         s1 = mfma16<f16_t>(kh, ql[g], s1);
         s1 = mfma16<f16_t>(kl, qh[g], s1);
@@ -567,17 +577,7 @@ __global__ __launch_bounds__(64 * NW) void attn_split_kernel(const AttnArgs p) {
     }
 
     // keys are only tested where a test can fail: the ragged last tile and an explicit mask (wave-uniform conditions)
-    if (kv0 + 64 > p.Tk || p.mask) {
-#pragma unroll
-      for (int f = 0; f < 4; ++f)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int key = kv0 + 16 * f + 4 * fq + e;
-          bool dead = key >= p.Tk;
-          if (p.mask && !dead) dead = p.mask[(long)qrow * p.Tk + key] != 0;
-          if (dead) s[f][e] = -INFINITY;
-        }
-    }
+    if (kv0 + 64 > p.Tk || p.mask) mask_tile(p.mask, p.Tk, kv0, qrow, fq, s);
     float mx = -INFINITY;
 #pragma unroll
     for (int f = 0; f < 4; ++f)
@@ -624,22 +624,8 @@ __global__ __launch_bounds__(64 * NW) void attn_split_kernel(const AttnArgs p) {
       }
       const u32x4 ph = __builtin_bit_cast(u32x4, phv), pl = __builtin_bit_cast(u32x4, plv);
       const int r0 = 16 * f0 + 4 * fq + qp, r1 = 16 * f1 + 4 * fq + qp;
-      typedef short s16x8 __attribute__((ext_vector_type(8)));
-      typedef s16x4 __attribute__((address_space(3)))* lds_s16x4_ptr;
 #pragma unroll
-      for (int d = 0; d < 4; ++d) {
-        const int ch = (d >> 1) * 8 + (d & 1) * 2 + (pp >> 1);   // hi chunk of this d block; lo is 4 chunks further
-        const int b8 = (pp & 1) * 8;
-        const s16x4 h0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(sV + r0 * 256 + ((ch ^ vsw(r0)) << 4) + b8));
-        const s16x4 h1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(sV + r1 * 256 + ((ch ^ vsw(r1)) << 4) + b8));
-        const s16x4 l0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(sV + r0 * 256 + (((ch + 4) ^ vsw(r0)) << 4) + b8));
-        const s16x4 l1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(sV + r1 * 256 + (((ch + 4) ^ vsw(r1)) << 4) + b8));
-        const u32x4 vh = __builtin_bit_cast(u32x4, (s16x8{h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]}));
-        const u32x4 vl = __builtin_bit_cast(u32x4, (s16x8{l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]}));
-        o0[d] = mfma16<f16_t>(vh, ph, o0[d]);
-        o1[d] = mfma16<f16_t>(vh, pl, o1[d]);
-        o1[d] = mfma16<f16_t>(vl, ph, o1[d]);
-      }
+      for (int d = 0; d < 4; ++d) pv_step_split(sV, r0, r1, d, pp, ph, pl, o0[d], o1[d]);
     }
   }
 
@@ -678,68 +664,77 @@ static int attn_waves(int Tq, int H, int B) {
   return best;
 }
 
+// The tiled kernels (K = TiledKernel: attn_kernel<T, .>, SplitKernel: attn_split_kernel<T, .>): waves per workgroup -> instantiation
+typedef void (*attn_fn)(const AttnArgs);
+struct TiledKernel { template <typename T, int NW> static attn_fn get() { return attn_kernel<T, NW>; } };
+struct SplitKernel { template <typename T, int NW> static attn_fn get() { return attn_split_kernel<T, NW>; } };
+template <typename K, typename T> static int launch_tiled(const AttnArgs& p, hipStream_t st) {
+  const int nw = attn_waves(p.Tq, p.H, p.B);
+  const attn_fn fn = nw == 4 ? K::template get<T, 4>() : nw == 7 ? K::template get<T, 7>()
+                   : nw == 13 ? K::template get<T, 13>() : K::template get<T, 16>();
+  dim3 grid((p.Tq + 16 * nw - 1) / (16 * nw), p.H, p.B), block(64 * nw);
+  hipLaunchKernelGGL(fn, grid, block, 0, st, p);
+  MSMD_RETURN_LAST();
+}
+
+// attn_whole_kernel<T, NW, NF>: the LDS allocation is sized by Tk (whole fragment pairs of rows + the 1 KB sink)
+template <typename T, int NW, int NF> static int launch_whole(const AttnArgs& p, hipStream_t st) {
+  constexpr int lds_max = 2 * 16 * NF * 128 + 1024;
+  const int rows = std::min((((p.Tk + 15) / 16 + 1) & ~1) * 16, 16 * NF);
+  const int lds = 2 * rows * 128 + 1024;
+  static bool attr = false;
+  auto k = attn_whole_kernel<T, NW, NF>;
+  if (!attr) { (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max); attr = true; }
+  dim3 grid((p.Tq + 16 * NW - 1) / (16 * NW), p.H, p.B);
+  hipLaunchKernelGGL(k, grid, dim3(64 * NW), lds, st, p);
+  MSMD_RETURN_LAST();
+}
+
+// short sequences: all keys staged once, plain softmax (attn_whole_kernel).  One workgroup per (batch, head) when the
+// queries fit (K / V read once): in the forward step T = 200 runs 16.4 us with 13 waves against 17.5 with 7 (two
+// workgroups per head) and 19.8 for attn_kernel; T = 111 6.6 us with 7 waves against 7.8.
+template <typename T> static int launch_whole_for(const AttnArgs& p, hipStream_t st) {
+  if (p.Tk > 16 * ATTN_WHOLE_NF) return launch_whole<T, 9, 17>(p, st);
+  if (p.Tq <= 112) return launch_whole<T, 7, ATTN_WHOLE_NF>(p, st);
+  return launch_whole<T, 13, ATTN_WHOLE_NF>(p, st);
+}
+
+// Checks and the AttnArgs fill every entry shares: Q / K / V strides multiples of `unit` elements and O strides of `o_unit`
+// (4 / 8 elements: 16-byte chunks; 32: whole blocks of split storage), 16-byte aligned pointers.  false = bad arguments
+static bool attn_args(AttnArgs& p, const void* Q, const void* K, const void* V, void* O, int B, int H, int Tq, int Tk,
+                      long q_bstride, long q_tstride, long k_bstride, long k_tstride, long v_bstride, long v_tstride,
+                      long o_bstride, long o_tstride, float scale, const uint8_t* mask, int unit, int o_unit) {
+  if (B <= 0 || H <= 0 || Tq <= 0 || Tk <= 0 || !Q || !K || !V || !O) return false;
+  if (q_tstride % unit || k_tstride % unit || v_tstride % unit || o_tstride % o_unit || q_bstride % unit ||
+      k_bstride % unit || v_bstride % unit || o_bstride % o_unit)
+    return false;
+  if (((uintptr_t)Q & 15) || ((uintptr_t)K & 15) || ((uintptr_t)V & 15) || ((uintptr_t)O & 15)) return false;
+  p = AttnArgs{Q, K, V, O, B, H, Tq, Tk, q_bstride, q_tstride, k_bstride, k_tstride, v_bstride, v_tstride,
+               o_bstride, o_tstride, scale, mask, 0.f, nullptr, 0u};
+  return true;
+}
+
 static int attention_impl(const void* Q, const void* K, const void* V, void* O, int B, int H, int Tq, int Tk,
                           long q_bstride, long q_tstride, long k_bstride, long k_tstride, long v_bstride,
                           long v_tstride, long o_bstride, long o_tstride, float scale, const uint8_t* mask,
                           float p_drop, const unsigned long* rng_state, unsigned site, int dtype,
                           msmd_stream_t stream, const void* const* pf_ptrs = nullptr, const long* pf_bytes = nullptr,
                           int n_pf = 0) {
-  if (B <= 0 || H <= 0 || Tq <= 0 || Tk <= 0 || !Q || !K || !V || !O || !(scale > 0.f)) return 1;
-  if (!(p_drop >= 0.f && p_drop < 1.f) || (p_drop > 0.f && (!rng_state || Tk > 512))) return 1;
-  const int E = dtype == MSMD_F32 ? 4 : 8;
-  if (q_tstride % E || k_tstride % E || v_tstride % E || o_tstride % 4 || q_bstride % E || k_bstride % E ||
-      v_bstride % E || o_bstride % 4)
+  AttnArgs p;
+  if (!attn_args(p, Q, K, V, O, B, H, Tq, Tk, q_bstride, q_tstride, k_bstride, k_tstride, v_bstride, v_tstride, o_bstride,
+                 o_tstride, scale, mask, dtype == MSMD_F32 ? 4 : 8, 4) || !(scale > 0.f))
     return 1;
-  if (((uintptr_t)Q & 15) || ((uintptr_t)K & 15) || ((uintptr_t)V & 15) || ((uintptr_t)O & 15)) return 1;
-  AttnArgs p{Q, K, V, O, B, H, Tq, Tk, q_bstride, q_tstride, k_bstride, k_tstride, v_bstride, v_tstride,
-             o_bstride, o_tstride, scale, mask, p_drop, rng_state, site};
+  if (!(p_drop >= 0.f && p_drop < 1.f) || (p_drop > 0.f && (!rng_state || Tk > 512))) return 1;
+  p.p_drop = p_drop; p.rng_state = rng_state; p.site = site;
   if (n_pf < 0 || n_pf > 4 || (n_pf > 0 && (!pf_ptrs || !pf_bytes))) return 1;
   for (int i = 0, j = 0; i < n_pf; ++i)
     if (pf_ptrs[i] && pf_bytes[i] >= 16 && ((uintptr_t)pf_ptrs[i] & 15) == 0) { p.pf_ptr[j] = pf_ptrs[i]; p.pf_bytes[j] = pf_bytes[i]; ++j; }
-  int nw = attn_waves(Tq, H, B);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype != MSMD_F32 && Tk <= 272) {
-    // short sequences: all keys staged once, plain softmax (attn_whole_kernel).  One workgroup per (batch, head) when the
-    // queries fit (K / V read once): in the forward step T = 200 runs 16.4 us with 13 waves against 17.5 with 7 (two
-    // workgroups per head) and 19.8 for attn_kernel; T = 111 6.6 us with 7 waves against 7.8.
-#define MSMD_ATTN_W(T, NWV, NFV)                                                                                     \
-  do {                                                                                                               \
-    constexpr int lds_max_ = 2 * 16 * NFV * 128 + 1024;                                                              \
-    const int rows_ = std::min((((Tk + 15) / 16 + 1) & ~1) * 16, 16 * NFV);                                           \
-    const int lds_ = 2 * rows_ * 128 + 1024;                                                                         \
-    static bool attr_ = false;                                                                                       \
-    auto k_ = attn_whole_kernel<T, NWV, NFV>;                                                                         \
-    if (!attr_) { (void)hipFuncSetAttribute((const void*)k_, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max_); attr_ = true; } \
-    dim3 grid_((Tq + 16 * NWV - 1) / (16 * NWV), H, B);                                                               \
-    hipLaunchKernelGGL(k_, grid_, dim3(64 * NWV), lds_, st, p);                                                       \
-  } while (0)
-#define MSMD_ATTN_WT(T)                                                                  \
-  do {                                                                                   \
-    if (Tk <= 16 * ATTN_WHOLE_NF) {                                                      \
-      if (Tq <= 112) MSMD_ATTN_W(T, 7, ATTN_WHOLE_NF);                                   \
-      else MSMD_ATTN_W(T, 13, ATTN_WHOLE_NF);                                            \
-    } else MSMD_ATTN_W(T, 9, 17);                                                        \
-  } while (0)
-    if (dtype == MSMD_BF16) MSMD_ATTN_WT(bf16_t);
-    else MSMD_ATTN_WT(f16_t);
-#undef MSMD_ATTN_WT
-#undef MSMD_ATTN_W
-    MSMD_RETURN_LAST();
-  }
-  dim3 grid((Tq + 16 * nw - 1) / (16 * nw), H, B), block(64 * nw);
-#define MSMD_ATTN(T)                                                                                   \
-  do {                                                                                                 \
-    if (nw == 4) hipLaunchKernelGGL((attn_kernel<T, 4>), grid, block, 0, st, p);                       \
-    else if (nw == 7) hipLaunchKernelGGL((attn_kernel<T, 7>), grid, block, 0, st, p);                  \
-    else if (nw == 13) hipLaunchKernelGGL((attn_kernel<T, 13>), grid, block, 0, st, p);                \
-    else hipLaunchKernelGGL((attn_kernel<T, 16>), grid, block, 0, st, p);                              \
-  } while (0)
-  if (dtype == MSMD_BF16) MSMD_ATTN(bf16_t);
-  else if (dtype == MSMD_F16) MSMD_ATTN(f16_t);
-  else if (dtype == MSMD_F32) MSMD_ATTN(float);
-  else return 1;
-#undef MSMD_ATTN
-  MSMD_RETURN_LAST();
+  if (dtype != MSMD_F32 && Tk <= 272) return dtype == MSMD_BF16 ? launch_whole_for<bf16_t>(p, st) : launch_whole_for<f16_t>(p, st);
+  if (dtype == MSMD_BF16) return launch_tiled<TiledKernel, bf16_t>(p, st);
+  if (dtype == MSMD_F16) return launch_tiled<TiledKernel, f16_t>(p, st);
+  if (dtype == MSMD_F32) return launch_tiled<TiledKernel, float>(p, st);
+  return 1;
 }
 
 extern "C" int msmd_attention(const void* Q, const void* K, const void* V, void* O, int B, int H, int Tq, int Tk,
@@ -751,7 +746,8 @@ extern "C" int msmd_attention(const void* Q, const void* K, const void* V, void*
 }
 
 // msmd_attention that also pulls up to four byte ranges (the weights the NEXT kernels will read) through the memory-side
-// cache while it runs (16-bit modes, Tk <= 208: the whole-sequence kernel; other shapes ignore the ranges).
+// cache while it runs: the whole-sequence kernel (16-bit modes, Tk <= 272) and attn_kernel (every other shape and fp32) both
+// sweep them; msmd_attention_f16x2 has no such entry.
 extern "C" int msmd_attention_prefetch(const void* Q, const void* K, const void* V, void* O, int B, int H, int Tq, int Tk,
                                        long q_bstride, long q_tstride, long k_bstride, long k_tstride, long v_bstride,
                                        long v_tstride, long o_bstride, long o_tstride, float scale, const uint8_t* mask,
@@ -791,27 +787,13 @@ extern "C" int msmd_attention_f16x2(const void* Q, const void* K, const void* V,
                                     long q_bstride, long q_tstride, long k_bstride, long k_tstride, long v_bstride,
                                     long v_tstride, long o_bstride, long o_tstride, float scale, const uint8_t* mask,
                                     int out_dtype, msmd_stream_t stream) {
-  if (B <= 0 || H <= 0 || Tq <= 0 || Tk <= 0 || !Q || !K || !V || !O) return 1;
   if (out_dtype != MSMD_F32 && out_dtype != MSMD_F16X2) return 1;
-  if (q_tstride % 32 || k_tstride % 32 || v_tstride % 32 || q_bstride % 32 || k_bstride % 32 || v_bstride % 32) return 1;
-  if (out_dtype == MSMD_F16X2 ? (o_tstride % 32 || o_bstride % 32) : (o_tstride % 4 || o_bstride % 4)) return 1;
-  if (((uintptr_t)Q & 15) || ((uintptr_t)K & 15) || ((uintptr_t)V & 15) || ((uintptr_t)O & 15)) return 1;
-  AttnArgs p{Q, K, V, O, B, H, Tq, Tk, q_bstride, q_tstride, k_bstride, k_tstride, v_bstride, v_tstride,
-             o_bstride, o_tstride, scale, mask, 0.f, nullptr, 0u};
-  const int nw = attn_waves(Tq, H, B);
-  dim3 grid((Tq + 16 * nw - 1) / (16 * nw), H, B), block(64 * nw);
+  AttnArgs p;
+  if (!attn_args(p, Q, K, V, O, B, H, Tq, Tk, q_bstride, q_tstride, k_bstride, k_tstride, v_bstride, v_tstride, o_bstride,
+                 o_tstride, scale, mask, 32, out_dtype == MSMD_F16X2 ? 32 : 4))
+    return 1;
   hipStream_t st = (hipStream_t)stream;
-#define MSMD_ATTN_S(TO)                                                                                \
-  do {                                                                                                 \
-    if (nw == 4) hipLaunchKernelGGL((attn_split_kernel<TO, 4>), grid, block, 0, st, p);                \
-    else if (nw == 7) hipLaunchKernelGGL((attn_split_kernel<TO, 7>), grid, block, 0, st, p);           \
-    else if (nw == 13) hipLaunchKernelGGL((attn_split_kernel<TO, 13>), grid, block, 0, st, p);         \
-    else hipLaunchKernelGGL((attn_split_kernel<TO, 16>), grid, block, 0, st, p);                       \
-  } while (0)
-  if (out_dtype == MSMD_F32) MSMD_ATTN_S(float);
-  else MSMD_ATTN_S(f16_t);
-#undef MSMD_ATTN_S
-  MSMD_RETURN_LAST();
+  return out_dtype == MSMD_F32 ? launch_tiled<SplitKernel, float>(p, st) : launch_tiled<SplitKernel, f16_t>(p, st);
 }
 
 

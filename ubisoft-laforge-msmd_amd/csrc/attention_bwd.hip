@@ -12,17 +12,15 @@
 //     dV^T += dO^T P,  dK^T += Q^T dS   (both operands via transposing reads; fp32 accumulators live in registers
 //                                        across all q tiles)
 // K, V stay resident in LDS for the whole workgroup; Q / dO are staged per tile.  All [rows][64] images share one
-// XOR swizzle of 32-byte blocks that serves row reads and transposed reads.
+// XOR swizzle of 32-byte blocks that serves row reads and transposed reads (attention_tiles.h: img_off, img_tr, tr_read).
 //
 // Reference semantics: autograd of HF Wav2Vec2Attention (utils/wav2vec2.py:111 -> transformers) and of
 // nn.MultiheadAttention inside nn.TransformerDecoderLayer / nn.TransformerEncoderLayer (model.py:874-878,
 // style_encoder.py:158) under loss.backward() (training_script.py:196); eval-mode (no attention dropout).
 #include "common.h"
+#include "attention_tiles.h"
 
 namespace {
-
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 struct AbArgs {
   const bf16_t *Q, *K, *V, *dO;
@@ -36,19 +34,6 @@ struct AbArgs {
   unsigned site;
 };
 
-// byte offset of 16-byte chunk ch (0..7) of row `row` in a [rows][64] bf16 image
-__device__ __forceinline__ int img_off(int row, int ch) {
-  return row * 128 + (((((ch >> 1) ^ ((row >> 1) & 3)) << 1) | (ch & 1)) << 4);
-}
-// address a lane supplies for a transposed read of rows r0..r0+3 (lane's row = r0 + q'), 16-column block db
-__device__ __forceinline__ int img_tr(int row, int db, int pp) {
-  return row * 128 + ((db ^ ((row >> 1) & 3)) << 5) + pp * 8;
-}
-__device__ __forceinline__ u32x2 tr_read(const unsigned char* p) {
-  typedef short s16x4 __attribute__((ext_vector_type(4)));
-  const s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)p);
-  return __builtin_bit_cast(u32x2, v);
-}
 __device__ __forceinline__ bf16x8 frag8(const u32x2 lo, const u32x2 hi) {
   return __builtin_bit_cast(bf16x8, (u32x4{lo[0], lo[1], hi[0], hi[1]}));
 }

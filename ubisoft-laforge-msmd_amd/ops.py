@@ -527,82 +527,49 @@ def _prefetch_ranges(tensors):
     return ptrs, nbytes, len(ts)
 
 
+def _attn_args(mask, scale, n_heads, q, k, v, *rest):
+    """The leading arguments of every attention entry, in the C order: pointers of q, k, v and `rest`, B, H, Tq, Tk, the
+    batch and row stride of each tensor, the scale, the (Tq, Tk) mask (checked here)."""
+    B, Tq, _ = q.shape
+    Tk = k.shape[1]
+    if mask is not None:
+        assert mask.dtype in (torch.bool, torch.uint8) and mask.shape == (Tq, Tk) and mask.is_contiguous()
+    ts = (q, k, v) + rest
+    return (*[_p(t) for t in ts], B, n_heads, Tq, Tk, *[t.stride(i) for t in ts for i in (0, 1)], float(scale), _p(mask))
+
+
 def attention(q, k, v, n_heads, scale, mask=None, out=None, p_drop=0.0, rng_state=None, site=0, out_dtype=None,
               prefetch=None):
     """q: (B, Tq, H*64) view, k/v: (B, Tk, H*64) views (last dim contiguous; may be slices of a packed QKV).
-    Split q / k / v (parity-grade speed mode): msmd_attention_f16x2; out_dtype SPLIT (default) or torch.float32."""
+    Split q / k / v (parity-grade speed mode): msmd_attention_f16x2; out_dtype SPLIT (default) or torch.float32.
+    Entry per case: split -> msmd_attention_f16x2 (no dropout, prefetch ignored); otherwise msmd_attention,
+    msmd_attention_prefetch, msmd_attention_dropout or msmd_attention_dropout_prefetch by p_drop > 0 and prefetch."""
     _need_cuda(q, k, v)
     lib = _lib.load()
     B, Tq, d = q.shape
-    Tk = k.shape[1]
     assert d == n_heads * 64 and q.stride(-1) == 1 and k.stride(-1) == 1 and v.stride(-1) == 1
-    if isinstance(q, Split):
-        if not (isinstance(k, Split) and isinstance(v, Split)) or p_drop > 0.0:
-            raise TypeError("split attention: q, k, v must all be Split (inference only)")
-        if out is None:
-            out = empty((B, Tq, d), q.device, out_dtype or SPLIT)
-        m = None
-        if mask is not None:
-            assert mask.dtype in (torch.bool, torch.uint8) and mask.shape == (Tq, Tk) and mask.is_contiguous()
-            m = mask
-        _lib.check(lib.msmd_attention_f16x2(_p(q), _p(k), _p(v), _p(out), B, n_heads, Tq, Tk, q.stride(0), q.stride(1),
-                                            k.stride(0), k.stride(1), v.stride(0), v.stride(1), out.stride(0),
-                                            out.stride(1), float(scale), _p(m), _dt(out), _stream()),
-                   "msmd_attention_f16x2")
-        return out
+    split = isinstance(q, Split)
+    if split and (not (isinstance(k, Split) and isinstance(v, Split)) or p_drop > 0.0):
+        raise TypeError("split attention: q, k, v must all be Split (inference only)")
     if out is None:
-        out = torch.empty(B, Tq, d, device=q.device, dtype=q.dtype)
-    m = None
-    if mask is not None:
-        assert mask.dtype in (torch.bool, torch.uint8) and mask.shape == (Tq, Tk) and mask.is_contiguous()
-        m = mask
-    if p_drop > 0.0 and prefetch and PREFETCH_WEIGHTS:
-        ptrs, nbytes, n = _prefetch_ranges(prefetch)
-        _lib.check(lib.msmd_attention_dropout_prefetch(_p(q), _p(k), _p(v), _p(out), B, n_heads, Tq, Tk, q.stride(0),
-                                                       q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1),
-                                                       out.stride(0), out.stride(1), float(scale), _p(m), float(p_drop),
-                                                       _p(rng_state), int(site), _dt(q), ptrs, nbytes, n, _stream()),
-                   "msmd_attention_dropout_prefetch")
-        return out
-    if p_drop > 0.0:
-        _lib.check(lib.msmd_attention_dropout(_p(q), _p(k), _p(v), _p(out), B, n_heads, Tq, Tk, q.stride(0),
-                                              q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1),
-                                              out.stride(0), out.stride(1), float(scale), _p(m), float(p_drop),
-                                              _p(rng_state), int(site), _dt(q), _stream()), "msmd_attention_dropout")
-        return out
-    if prefetch and PREFETCH_WEIGHTS:
-        # up to four tensors (the weights of the GEMMs that follow) pulled through the memory-side cache by this launch
-        ptrs, nbytes, n = _prefetch_ranges(prefetch)
-        _lib.check(lib.msmd_attention_prefetch(_p(q), _p(k), _p(v), _p(out), B, n_heads, Tq, Tk, q.stride(0), q.stride(1),
-                                               k.stride(0), k.stride(1), v.stride(0), v.stride(1), out.stride(0),
-                                               out.stride(1), float(scale), _p(m), _dt(q), ptrs, nbytes, n,
-                                               _stream()), "msmd_attention_prefetch")
-        return out
-    _lib.check(lib.msmd_attention(_p(q), _p(k), _p(v), _p(out), B, n_heads, Tq, Tk, q.stride(0), q.stride(1),
-                                  k.stride(0), k.stride(1), v.stride(0), v.stride(1), out.stride(0), out.stride(1),
-                                  float(scale), _p(m), _dt(q), _stream()), "msmd_attention")
+        out = empty((B, Tq, d), q.device, out_dtype or SPLIT) if split else torch.empty(B, Tq, d, device=q.device, dtype=q.dtype)
+    args = _attn_args(mask, scale, n_heads, q, k, v, out)
+    drop = (float(p_drop), _p(rng_state), int(site)) if p_drop > 0.0 else ()
+    # up to four tensors (the weights of the GEMMs that follow) pulled through the memory-side cache by this launch
+    pf = _prefetch_ranges(prefetch) if prefetch and PREFETCH_WEIGHTS and not split else ()
+    name = "msmd_attention_f16x2" if split else "msmd_attention" + ("_dropout" if drop else "") + ("_prefetch" if pf else "")
+    _lib.check(getattr(lib, name)(*args, *drop, _dt(out if split else q), *pf, _stream()), name)
     return out
 
 
 def attention_bwd(q, k, v, do, dq, dk, dv, n_heads, scale, mask=None, p_drop=0.0, rng_state=None, site=0):
     """Fused backward of `attention` (bf16, Tk <= 256): fills dq / dk / dv (views with last dim contiguous)."""
     _need_cuda(q, k, v, do, dq, dk, dv)
-    lib = _lib.load()
-    B, Tq, d = q.shape
-    Tk = k.shape[1]
     for t in (q, k, v, do, dq, dk, dv):
         if t.dtype != torch.bfloat16 or t.stride(-1) != 1:
             raise TypeError("attention_bwd takes bf16 tensors with a contiguous last dim")
-    m = None
-    if mask is not None:
-        assert mask.dtype in (torch.bool, torch.uint8) and mask.shape == (Tq, Tk) and mask.is_contiguous()
-        m = mask
-    _lib.check(lib.msmd_attention_bwd(_p(q), _p(k), _p(v), _p(do), _p(dq), _p(dk), _p(dv), B, n_heads, Tq, Tk,
-                                      q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1),
-                                      do.stride(0), do.stride(1), dq.stride(0), dq.stride(1), dk.stride(0),
-                                      dk.stride(1), dv.stride(0), dv.stride(1), float(scale), _p(m), float(p_drop),
-                                      _p(rng_state), int(site), _stream()),
-               "msmd_attention_bwd")
+    _lib.check(_lib.load().msmd_attention_bwd(*_attn_args(mask, scale, n_heads, q, k, v, do, dq, dk, dv), float(p_drop),
+                                              _p(rng_state), int(site), _stream()), "msmd_attention_bwd")
 
 
 def dynamic_threshold_(res, L, ratio, dt_min, dt_max):
