@@ -14,6 +14,7 @@
 // columns of one row: 16-B (fp32) / 8-B (bf16) epilogue stores and a float4 bias load.
 // bf16: v_mfma_f32_16x16x32_bf16; fp32 parity mode: v_mfma_f32_16x16x4_f32 (exact fp32 FMA chain).
 #include "common.h"
+#include <atomic>
 #include <utility>
 
 struct GemmArgs {
@@ -28,8 +29,7 @@ struct GemmArgs {
   // residual add; the keep mask is Philox(rng, site, (m * N + n) / 4), i.e. msmd_dropout's on a contiguous (M, N) C
   void* Z; float p_drop; const unsigned long* rng; unsigned site;
   int xn;  // XCDs along N (1, 2 or 4): the 8 XCDs form an (8 / xn) x xn grid over (M tiles, N tiles)
-  int flags;  // MSMD_GEMM_* bits 16.. of `act`, shifted down: 1 = write-through (sc1) output stores, 2 = paired 16-B stores;
-              // 8 (internal, msmd_gemm_actbwd) = Z is an INPUT: C = keep_mask / (1 - p) * act'(Z) * (A W^T), no bias / residual
+  int flags;  // GF_* below
   // LayerNorm folded into the GEMMs around it (msmd_gemm_ln; all NULL for plain calls):
   //   a_stats (a_nt, M, 2): A holds UN-normalised rows u, the partial (sum, sum of squares) of each row over 64-column
   //     slabs; W carries gamma folded in, w_colsum[n] = sum_k W'[n][k], bias carries beta . W:  y = rstd (acc - mu s[n]) + c[n]
@@ -38,9 +38,44 @@ struct GemmArgs {
   const float* a_stats = nullptr; int a_nt = 0; const float* w_colsum = nullptr;
   const float* r_stats = nullptr; int r_nt = 0; const float* r_gamma = nullptr; const float* r_beta = nullptr;
   float* stats_out = nullptr; float ln_eps = 1e-5f;
-  // flags bit 2 (MSMD_GEMM_STAGGER): the workgroups dispatched second onto their CU start `stagger_ticks` (100 MHz) late
+  // GF_STAGGER (MSMD_GEMM_STAGGER): the workgroups dispatched second onto their CU start `stagger_ticks` (100 MHz) late
   int stagger_ticks = 0;
 };
+
+// GemmArgs::flags: the MSMD_GEMM_* bits 16-18 of `act` shifted down to bits 0-2, bits 19-21 to bits 4-6 (gemm_unpack_act).
+enum : int {
+  GF_WRITE_THROUGH = 1, GF_PAIRED_STORES = 2, GF_STAGGER = 4,      // how the output is stored; when a CU's second workgroup starts
+  GF_ACT_BWD = 8,      // internal (msmd_gemm_actbwd): Z is an INPUT: C = keep_mask / (1 - p) * act'(Z) * (A W^T), no bias / residual
+  GF_ONE_TILE = 16, GF_NO_256 = 32,      // opt out of the persistent form / of the 256 x 256 kernel as the library's own choice (A/B)
+  GF_W_BELOW_32 = 64,      // split operands: |W| < 32 everywhere
+};
+struct GemmActWord { int act, hint, flags; };   // MSMD_ACT_*, the caller's variant (0 = the library's own choice), GF_*
+static constexpr GemmActWord gemm_unpack_act(int act) {
+  return {act & 0xff, (act >> 8) & 0xff, ((act >> 16) & 7) | (((act >> 19) & 7) << 4)};
+}
+static_assert(gemm_unpack_act(MSMD_GEMM_WRITE_THROUGH).flags == GF_WRITE_THROUGH && gemm_unpack_act(MSMD_GEMM_PAIRED_STORES).flags == GF_PAIRED_STORES &&
+              gemm_unpack_act(MSMD_GEMM_STAGGER).flags == GF_STAGGER && gemm_unpack_act(MSMD_GEMM_ONE_TILE_PER_WORKGROUP).flags == GF_ONE_TILE &&
+              gemm_unpack_act(MSMD_GEMM_NO_256_TILE).flags == GF_NO_256 && gemm_unpack_act(MSMD_GEMM_W_BELOW_32).flags == GF_W_BELOW_32 && gemm_unpack_act(~0).flags == (0x7f & ~GF_ACT_BWD),
+              "internal flag bits follow include/msmd_hip.h; no bit of `act` sets the internal one");
+// Kernel variants: what the plans return, msmd_gemm_route reports and MSMD_GEMM_VARIANT names.
+enum : int {
+  GV_GENERIC = 0,       // gemm_kernel: fp32 operands, K % 64 != 0
+  GV_SPLIT_128 = 1, GV_SPLIT_64 = 5,      // split pairs: 128 x 128 (64 KB, 2 workgroups / CU: default), 64 x 64 (small grids)
+  GV_64_DEEP = 9, GV_64 = 12,      // 64 x 64 with a 4- / 2-stage ring: grids that would not fill the chip
+  GV_256x64 = 14,       // narrow outputs (N <= 64): the positional conv; 16-bit and split pairs
+  GV_192 = 15,          // 192 x 128, tall grids (M >= 16 k): 80 KB, still 2 workgroups / CU
+  GV_128 = 17,          // 128 x 128, 8 waves (4 x 2), 2-stage ring, fragment reads of both k-steps issued first
+  GV_128_AB = 13, GV_128_ONE_AB = 66,      // A/B forms of 17, bf16 only: the compiler's own read / multiply interleave; ONE kernel with every epilogue
+  GV_256 = 80,          // 256 x 256, 8-phase schedule, one workgroup per CU (gemm8_kernel); 16-bit and split pairs
+};
+
+// The epilogues an instantiation carries, and the EPIA code of the kernels' integer template parameter: the family + 10 * (1 +
+// activation) when the activation is a constant of the kernel too, the family alone (ACT_RUNTIME) when it is read from p.act.
+enum GemmEpi : int { EPI_ALL = 0, EPI_PLAIN = 1, EPI_LN_OPERAND = 2, EPI_LN_RESIDUAL = 3 };
+constexpr int ACT_RUNTIME = -1;
+constexpr int epia(GemmEpi e, int act) { return e + 10 * (1 + act); }
+constexpr GemmEpi epia_family(int code) { return (GemmEpi)(code % 10); }
+constexpr int epia_act(int code) { return code / 10 - 1; }
 
 template <typename T> struct Mfma;
 template <> struct Mfma<bf16_t> {
@@ -79,7 +114,8 @@ __device__ __forceinline__ long a_row_offset(const GemmArgs& p, int m) {
   return (long)q * p.a_batch_stride + (long)r * p.lda;
 }
 
-// Epilogue shared by both kernels: lane holds row m = ..+fr, columns n = ..+fq*4 + {0..3} of each 16x16 fragment.
+// Epilogue of the fragment kernels (gemm_kernel, gemm2_kernel, gemm2p_kernel, gemm2s_kernel; gemm8_kernel stores through LDS and
+// shares only act_out_c): lane holds row m = ..+fr, columns n = ..+fq*4 + {0..3} of each 16x16 fragment.
 template <typename TO> __device__ __forceinline__ float act_out(float x, int act) {
   // 16-bit outputs: the transcendental-free GELU (|err| <= 5.5e-5, common.h) is below their own rounding;
   // fp32 outputs (parity mode) use the exact erff.
@@ -120,18 +156,18 @@ template <typename TO> __device__ __forceinline__ void store4_out(TO* p, const f
 }
 
 // Interior tiles (fully inside M x N, vector-aligned): straight-line code, no per-element bounds checks.
-// AB: the kernel also serves msmd_gemm_actbwd (flags bit 3).  Only the LDS-DMA 16-bit kernels carry that code: in the v1 /
+// AB: the kernel also serves msmd_gemm_actbwd (GF_ACT_BWD).  Only the LDS-DMA 16-bit kernels carry that code: in the v1 /
 // fp32 kernels it cost 272 bytes of scratch (fp32 mode 23.8 -> 34 ms).
 // LEAN: the inference epilogue only (no pre-activation copy, no dropout, no activation backward): the launcher sends calls that
 // carry those to the kernels that compile them in.
 template <typename TO, int FM, int FN, bool AB, bool LEAN, int ACT>
-__device__ __forceinline__ void gemm_epilogue_interior_a(const GemmArgs& p, const f32x4 (&acc)[FN][FM], int z, int m_base,
+__device__ __forceinline__ void gemm_epilogue_interior(const GemmArgs& p, const f32x4 (&acc)[FN][FM], int z, int m_base,
                                                          int n_base, int fr, int fq) {
   TO* __restrict__ C = (TO*)p.C + (z / p.batch_inner) * p.strideC + (z % p.batch_inner) * p.strideC2 +
                        (long)(m_base + fr) * p.ldc + n_base + fq * 4;
   const TO* __restrict__ R = p.R ? (const TO*)p.R + z * p.strideR + (long)(m_base + fr) * p.ldr + n_base + fq * 4 : nullptr;
   const float* __restrict__ bias = p.bias ? p.bias + z * p.strideBias + n_base + fq * 4 : nullptr;
-  const bool wt = p.flags & 1;
+  const bool wt = p.flags & GF_WRITE_THROUGH;
   f32x4 bv[FN];
 #pragma unroll
   for (int i = 0; i < FN; ++i) bv[i] = bias ? *(const f32x4*)(bias + i * 16) : f32x4{0.f, 0.f, 0.f, 0.f};
@@ -155,7 +191,7 @@ __device__ __forceinline__ void gemm_epilogue_interior_a(const GemmArgs& p, cons
     TO* crow = C + (long)j * 16 * p.ldc;
 #pragma unroll
     for (int e = 0; e < 4; ++e) v[e] = acc[i][j][e] + bv[i][e];
-    if (AB && (p.flags & 8)) {    // the backward of y = dropout(act(z)) applied to this data gradient: z read where C goes
+    if (AB && (p.flags & GF_ACT_BWD)) {    // the backward of y = dropout(act(z)) applied to this data gradient: z read where C goes
       const V4 z4 = *(const V4*)((const TO*)p.Z + (crow + i * 16 - (TO*)p.C));
 #pragma unroll
       for (int e = 0; e < 4; ++e) v[e] *= act_grad_fast((float)z4[e], ACT >= 0 ? ACT : p.act);
@@ -180,7 +216,7 @@ __device__ __forceinline__ void gemm_epilogue_interior_a(const GemmArgs& p, cons
     }
   };
   if constexpr (sizeof(TO) == 2 && FM % 2 == 0) {
-    if (p.flags & 2) {
+    if (p.flags & GF_PAIRED_STORES) {
       // Paired 16-byte stores: lanes l and l ^ 16 hold columns 4 fq .. 4 fq + 3 and the next four of the same rows.
       // They swap one fragment row each (even fq keeps row j0 and takes the partner's half of it, odd fq keeps row
       // j0 + 1), so every lane issues ONE 16-byte store per fragment-row pair instead of two 8-byte ones.
@@ -223,7 +259,7 @@ template <typename TO, int FM, int FN, bool AB = false, bool LEAN = false, int A
 __device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, const f32x4 (&acc)[FN][FM], int z, int m_base,
                                               int n_base, int fr, int fq) {
   if (p.vec_ok && m_base + FM * 16 <= p.M && n_base + FN * 16 <= p.N) {
-    gemm_epilogue_interior_a<TO, FM, FN, AB, LEAN, ACT>(p, acc, z, m_base, n_base, fr, fq);
+    gemm_epilogue_interior<TO, FM, FN, AB, LEAN, ACT>(p, acc, z, m_base, n_base, fr, fq);
     return;
   }
   TO* __restrict__ C = (TO*)p.C + (z / p.batch_inner) * p.strideC + (z % p.batch_inner) * p.strideC2;
@@ -246,7 +282,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, const f32x4 (&a
 #pragma unroll
       for (int e = 0; e < 4; ++e) v[e] = acc[i][j][e] + bv[e];
       TO* cp = C + (long)m * p.ldc + n;
-      if (AB && (p.flags & 8)) {
+      if (AB && (p.flags & GF_ACT_BWD)) {
         const TO* zp = (const TO*)p.Z + (cp - (TO*)p.C);
 #pragma unroll
         for (int e = 0; e < 4; ++e)
@@ -283,7 +319,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, const f32x4 (&a
             for (int e = 0; e < 4; ++e) v[e] += (float)r[e];
           }
         }
-        store4_out<TO>(cp, v, p.flags & 1);
+        store4_out<TO>(cp, v, p.flags & GF_WRITE_THROUGH);
       } else {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -340,9 +376,9 @@ __device__ __forceinline__ void ln_finish(const float* stats, int nt, int M, int
 // the statistics of the stored rows written when stats_out is given.  Every load of the epilogue (bias, column sums or
 // gamma / beta, the residual fragments) is issued up front, unconditionally: with run-time "is this pointer set" tests
 // inside the fragment loops the compiler serialises them into one L2 round trip per fragment column (+4 us per launch).
-template <typename TO, int FM, int FN, int MODE, int ACT>
-__device__ __forceinline__ void gemm_epilogue_ln_a(const GemmArgs& p, const f32x4 (&acc)[FN][FM], int m_base, int n_base,
-                                                   int fr, int fq, const f32x2 (&raw)[FM][4]) {
+template <typename TO, int FM, int FN, int MODE, int ACT = -1>
+__device__ __forceinline__ void gemm_epilogue_ln(const GemmArgs& p, const f32x4 (&acc)[FN][FM], int m_base, int n_base,
+                                                 int fr, int fq, const f32x2 (&raw)[FM][4]) {
   static_assert((FN == 4 || FN == 2) && (FM >= 2 && FM <= 4), "one wave = one statistics slab of 16 FN columns, 2 to 4 fragment rows");
   constexpr int SLAB = FN * 16;
   // fragment columns whose operands are requested together: all of them for the two-row tiles; two at a time for the
@@ -364,7 +400,7 @@ __device__ __forceinline__ void gemm_epilogue_ln_a(const GemmArgs& p, const f32x
 #pragma unroll
   for (int j = 0; j < FM; ++j) rowS[j] = rowQ[j] = tS[j] = tQ[j] = prS[j] = prQ[j] = 0.f;
   const bool odd = fq & 1;
-  const bool pair = sizeof(TO) == 2 && (p.flags & 2);
+  const bool pair = sizeof(TO) == 2 && (p.flags & GF_PAIRED_STORES);
 #pragma unroll
   for (int i0 = 0; i0 < FN; i0 += IB) {
     f32x4 bv[IB], xv[IB], yv[IB];
@@ -460,12 +496,6 @@ __device__ __forceinline__ void gemm_epilogue_ln_a(const GemmArgs& p, const f32x
       }
     }
   }
-}
-
-template <typename TO, int FM, int FN, int MODE, int ACT = -1>
-__device__ __forceinline__ void gemm_epilogue_ln(const GemmArgs& p, const f32x4 (&acc)[FN][FM], int m_base, int n_base,
-                                                 int fr, int fq, const f32x2 (&raw)[FM][4]) {
-  gemm_epilogue_ln_a<TO, FM, FN, MODE, ACT>(p, acc, m_base, n_base, fr, fq, raw);
 }
 
 template <typename T, typename TO, int BM, int BN>
@@ -587,8 +617,8 @@ template <typename TO, int BM, int BN, int WM, int WN, int NSTAGE, bool PIPE = f
 // (the 192-row tile's LayerNorm epilogues drifted to 145 once, i.e. to one workgroup per CU: HuBERT-large 18.7 -> 21.4 ms).
 // Its everything-epilogue instantiation (EPI 0: dropout / pre-activation copies on a tall grid, no caller on the path) does not
 // fit 128 without spilling and keeps the register count the compiler picks.
-__global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8 && NSTAGE * (BM + BN) * 128 <= 80 * 1024 && (EPIA % 10 != 0 || BM * BN <= 128 * 128)) ? 4 : 1) void gemm2_kernel(const GemmArgs p) {
-  constexpr int EPI = EPIA % 10, ACTK = EPIA / 10 - 1;
+__global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8 && NSTAGE * (BM + BN) * 128 <= 80 * 1024 && (epia_family(EPIA) != EPI_ALL || BM * BN <= 128 * 128)) ? 4 : 1) void gemm2_kernel(const GemmArgs p) {
+  constexpr int EPI = epia_family(EPIA), ACTK = epia_act(EPIA);
   constexpr int NW = WM * WN, NT = NW * 64;
   constexpr int STAGE = (BM + BN) * 128;
   constexpr int LPT = (BM + BN) * 8 / NT;  // LDS-DMA instructions per thread per K tile
@@ -751,7 +781,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8 && NSTAGE * (BM + BN) *
 // order and the epilogue are gemm2_kernel's: results are bit-identical.
 template <typename TO, int BM, int BN, int WM, int WN, typename TI, int EPIA>
 __global__ __launch_bounds__(WM * WN * 64, 4) void gemm2p_kernel(const GemmArgs p) {
-  constexpr int EPI = EPIA % 10, ACTK = EPIA / 10 - 1;
+  constexpr int EPI = epia_family(EPIA), ACTK = epia_act(EPIA);
   constexpr int NW = WM * WN, NT = NW * 64;
   constexpr int STAGE = (BM + BN) * 128;
   constexpr int LPT = (BM + BN) * 8 / NT;
@@ -1115,7 +1145,7 @@ template <typename TI, int EPIA, int SPLIT = 0>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void gemm8_kernel(const GemmArgs p) {
   typedef typename std::conditional<(SPLIT & 3) == 2, float, TI>::type TO;
   constexpr bool WS = (SPLIT & 4) != 0;   // W's hi plane scaled in registers, single accumulator
-  constexpr int EPI = EPIA % 10, ACTK = EPIA / 10 - 1;
+  constexpr int EPI = epia_family(EPIA), ACTK = epia_act(EPIA);
   static_assert(SPLIT == 0 || (EPI == 1 && __is_same(TI, f16_t)), "split operands: fp16 planes, plain epilogue");
   constexpr int HALF = 128 * 128;        // bytes of one half-tile
   constexpr int BUF = 4 * HALF;          // X0 X1 W0 W1
@@ -1293,7 +1323,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   const int nk = p.K / (SPLIT ? 32 : 64);       // K tiles of 128 bytes per operand row
   typedef typename Vec4T<TO>::type V4;
   const bool has_r = p.R != nullptr;
-  const bool wt = p.flags & 1;     // write-through stores (MSMD_GEMM_WRITE_THROUGH): the rows leave the L2 as they are stored
+  const bool wt = p.flags & GF_WRITE_THROUGH;     // write-through stores (MSMD_GEMM_WRITE_THROUGH): the rows leave the L2 as they are stored
 
   // prologue of the first tile: K tile 0 whole, K tile 1 except X1 (which phase 1 of tile 0 stages)
   set_tile(tl);
@@ -1535,7 +1565,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             float S = 0.f, Q = 0.f;
 #pragma unroll
             for (int e = 0; e < 4; ++e) { const float w = (float)o[e]; S += w; Q = fmaf(w, w, Q); }
-            // the association of gemm_epilogue_ln_a: a lane's four columns are fragment i = lane bits 2-3, lane group fq = bits 0-1
+            // the association of gemm_epilogue_ln: a lane's four columns are fragment i = lane bits 2-3, lane group fq = bits 0-1
 #pragma unroll
             for (int d : {4, 8, 1, 2}) { S += __shfl_xor(S, d, 64); Q += __shfl_xor(Q, d, 64); }
             if ((el & 15) == 0 && m < p.M) *(f32x2*)(p.stats_out + ((long)((en0 >> 6) + (el >> 4)) * p.M + m) * 2) = f32x2{S, Q};
@@ -1572,15 +1602,42 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #undef G8_EBAR
 }
 
+// f(std::integral_constant<int, C>) for the C of the compile-time list that equals the run-time `code`: its result (a launcher's:
+// >= 0), or -1 for a code that is not in the list.  Every run-time choice of a kernel's integer template arguments goes through here.
+template <int... CODES, typename F>
+static int dispatch_code(int code, F&& f) {
+  int r = -1;
+  (void)((code == CODES && ((r = f(std::integral_constant<int, CODES>{})), true)) || ...);
+  return r;
+}
 
-// XCD grid over (M, N) tiles (p.mt, p.nt set).  With all 8 XCDs striped along M every L2 streams its own copy of the whole weight
-// matrix from HBM, while the activation rows (the previous kernel's output) are still warm: an XCD of an
-// (8 / xn) x xn grid reads 1 / xn of W and xn / 8 of A, so xn is picked per problem from  0.7 xn |A| + (8 / xn) |W|
-// (the 0.7 fitted on the qkv shape, where 2 x 4 ties with 8 x 1 and both trail 4 x 2).  Forward step, same-graph A/B
-// in both orders: 8 x 1 4.96 ms, 4 x 2 everywhere 4.89, this rule 4.88.
+// Launches KFN on the current device and returns the last error.  More than 64 KB of dynamic LDS has to be allowed per kernel
+// and per DEVICE (hipFuncSetAttribute acts on the current one): once for each, remembered in a bit per device ordinal.
+template <auto KFN>
+static int gemm_launch_kernel(dim3 grid, int threads, int lds, hipStream_t st, const GemmArgs& p) {
+  if (lds > 0) {
+    static std::atomic<unsigned long> allowed{0};
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const unsigned long bit = (unsigned)dev < 64 ? 1UL << dev : 0;      // ordinals past 63: allowed again at every launch
+    if (!(allowed.load(std::memory_order_relaxed) & bit)) {
+      (void)hipFuncSetAttribute((const void*)KFN, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+      allowed.fetch_or(bit, std::memory_order_relaxed);
+    }
+  }
+  hipLaunchKernelGGL(KFN, grid, dim3(threads), lds, st, p);
+  MSMD_RETURN_LAST();
+}
+
+// XCD grid over BM x BN tiles: sets p.mt / p.nt / p.xn and returns the workgroup count, padded to whole XCD blocks.  With all 8 XCDs
+// striped along M every L2 streams its own copy of the whole weight matrix from HBM, while the activation rows (the previous
+// kernel's output) are still warm: an XCD of an (8 / xn) x xn grid reads 1 / xn of W and xn / 8 of A, so xn is picked per problem
+// from  0.7 xn |A| + (8 / xn) |W|  (the 0.7 fitted on the qkv shape, where 2 x 4 ties with 8 x 1 and both trail 4 x 2).  Forward
+// step, same-graph A/B in both orders: 8 x 1 4.96 ms, 4 x 2 everywhere 4.89, this rule 4.88.
 // `lda` is A's row stride in LOGICAL elements, like p.K (the split-pair kernels pass p.lda / 2).  Bytes are counted at 2 per
 // element for every kernel: the split pairs' 4 scale both terms by the same power of two, which no comparison below sees.
-static void gemm2_xcd_grid(GemmArgs& p, long lda) {
+static int gemm2_xcd_grid(GemmArgs& p, int BM, int BN, long lda) {
+  p.mt = (p.M + BM - 1) / BM; p.nt = (p.N + BN - 1) / BN;
   const double a_bytes = 2.0 * p.M * (double)(p.rows_per_batch < p.M ? lda : p.K), w_bytes = 2.0 * p.N * (double)p.K;
   double best = 1e30;
   int want_xn = 1;
@@ -1589,107 +1646,79 @@ static void gemm2_xcd_grid(GemmArgs& p, long lda) {
     if (c < best && p.nt >= xn) { best = c; want_xn = xn; }
   }
   p.xn = p.nt >= want_xn ? want_xn : 1;
-}
-
-// gemm2p_kernel: 512 persistent workgroups (two per CU) over a grid of more than 512 tiles
-template <typename TO, int BM, int BN, int WM, int WN, typename TI, int EPIA>
-static int launch_gemm2p(GemmArgs& p, hipStream_t st) {
-  constexpr int lds = 2 * (BM + BN) * 128;
-  static bool attr_done = false;
-  auto kfn = gemm2p_kernel<TO, BM, BN, WM, WN, TI, EPIA>;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_done = true;
-  }
-  p.stagger_ticks = 0;
-  hipLaunchKernelGGL(kfn, dim3(512, 1, 1), dim3(WM * WN * 64), lds, st, p);
-  MSMD_RETURN_LAST();
-}
-
-template <typename TO, int BM, int BN, int WM, int WN, int NSTAGE, bool PIPE = false, typename TI = bf16_t, int EPI = 0>
-static int launch_gemm2(GemmArgs& p, int batch, hipStream_t st) {
-  constexpr int lds = NSTAGE * (BM + BN) * 128;
-  static bool attr_done = false;
-  auto kfn = gemm2_kernel<TO, BM, BN, WM, WN, NSTAGE, PIPE, TI, EPI>;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_done = true;
-  }
-  p.mt = (p.M + BM - 1) / BM; p.nt = (p.N + BN - 1) / BN;
-  gemm2_xcd_grid(p, p.lda);
   const int xm_n = 8 / p.xn;
-  dim3 grid(((p.mt + xm_n - 1) / xm_n) * ((p.nt + p.xn - 1) / p.xn) * 8, 1, batch);
-  // stagger (flags bit 2): only where the launch runs more than one round of two workgroups per CU
-  p.stagger_ticks = ((p.flags & 4) && batch == 1 && NSTAGE * (BM + BN) * 128 <= 80 * 1024 && (long)p.mt * p.nt > 640)
-                        ? (int)(100.0 * 0.5 * ((p.K / 64) * 0.5 + 3.0)) : 0;
-  hipLaunchKernelGGL(kfn, grid, dim3(WM * WN * 64), lds, st, p);
-  MSMD_RETURN_LAST();
+  return ((p.mt + xm_n - 1) / xm_n) * ((p.nt + p.xn - 1) / p.xn) * 8;
 }
 
-// One instantiation per epilogue family, picked per call (see gemm2_kernel's EPI): the plain inference epilogue, the two
-// LayerNorm forms, and the everything-kernel for training calls (pre-activation copy / dropout / activation backward).
+// gemm2_kernel on `wgs` workgroups per batch (gemm2_xcd_grid's)
+template <typename TO, int BM, int BN, int WM, int WN, int NSTAGE, bool PIPE = false, typename TI = bf16_t, int EPIA = 0>
+static int launch_gemm2(GemmArgs& p, int wgs, int batch, hipStream_t st) {
+  constexpr int lds = NSTAGE * (BM + BN) * 128;
+  // stagger: only where the launch runs more than one round of two workgroups per CU
+  p.stagger_ticks = ((p.flags & GF_STAGGER) && batch == 1 && lds <= 80 * 1024 && (long)p.mt * p.nt > 640)
+                        ? (int)(100.0 * 0.5 * ((p.K / 64) * 0.5 + 3.0)) : 0;
+  return gemm_launch_kernel<gemm2_kernel<TO, BM, BN, WM, WN, NSTAGE, PIPE, TI, EPIA>>(dim3(wgs, 1, batch), WM * WN * 64, lds, st, p);
+}
+
+// The EPIA code of a call: its epilogue family (lnk: the tile has the LayerNorm forms) and the activation where it is a constant
+// of the kernel (none / GELU: what the path launches; ELU and the LayerNorm-residual form with an activation stay run-time).
+static int gemm_epia(const GemmArgs& p, bool lnk) {
+  GemmEpi e = EPI_ALL;      // training calls: pre-activation copy / dropout / activation backward
+  if (lnk && p.a_stats) e = EPI_LN_OPERAND;
+  else if (lnk && (p.r_stats || p.stats_out)) e = EPI_LN_RESIDUAL;
+  else if (!p.a_stats && !p.r_stats && !p.stats_out && !p.Z && !(p.p_drop > 0.f) && !(p.flags & GF_ACT_BWD)) e = EPI_PLAIN;
+  return epia(e, p.act == MSMD_ACT_NONE ? MSMD_ACT_NONE : (p.act == MSMD_ACT_GELU && e != EPI_LN_RESIDUAL) ? MSMD_ACT_GELU : ACT_RUNTIME);
+}
+
+// One instantiation per epilogue family and compiled-in activation, picked per call (see gemm2_kernel's EPI).
 template <typename TO, int BM, int BN, int WM, int WN, int NSTAGE, bool PIPE = false, typename TI = bf16_t>
 static int launch_gemm2_epi(GemmArgs& p, int batch, hipStream_t st) {
   constexpr bool LNK = (BN == 128 || BN == 64) && WN == 2 && (BM / WM / 16 == 2 || BM / WM / 16 == 3) && sizeof(TO) == 2;
-  // every family also with the activation as a constant of the kernel (none / GELU: what the path launches; ELU and the
-  // LayerNorm-residual form with an activation stay run-time)
-  int epi = 0;
-  if (LNK && p.a_stats) epi = 2;
-  else if (LNK && (p.r_stats || p.stats_out)) epi = 3;
-  else if (!p.a_stats && !p.r_stats && !p.stats_out && !p.Z && !(p.p_drop > 0.f) && !(p.flags & 8)) epi = 1;
-  const int a = p.act == MSMD_ACT_NONE ? 10 : (p.act == MSMD_ACT_GELU && epi != 3) ? 20 : 0;
+  const int code = gemm_epia(p, LNK), wgs = gemm2_xcd_grid(p, BM, BN, p.lda);
+  int r;
   if constexpr (LNK && PIPE && NSTAGE == 2 && WM * WN == 8 && BN == 128 && BM == 128) {
-    // more than one round of two workgroups per CU: the persistent form (gemm2p_kernel); flags bit 4 = caller opts out (A/B).
-    // The 128 x 128 tile's plain and LayerNorm-operand epilogues: the LayerNorm-residual one (its launches on the path are
-    // single-round) and the 192-row tile do not fit 128 registers in this form (20-128 bytes of scratch).
-    if (batch == 1 && epi >= 1 && a && !(p.flags & 16)) {
-      p.mt = (p.M + BM - 1) / BM; p.nt = (p.N + BN - 1) / BN;
-      gemm2_xcd_grid(p, p.lda);
-      const int xm_n = 8 / p.xn;
-      if (((p.mt + xm_n - 1) / xm_n) * ((p.nt + p.xn - 1) / p.xn) * 8 > 512) {
-#define MSMD_EPI_CASE(E) case E: return launch_gemm2p<TO, BM, BN, WM, WN, TI, E>(p, st)
-        switch (epi + a) { MSMD_EPI_CASE(11); MSMD_EPI_CASE(21); MSMD_EPI_CASE(12); MSMD_EPI_CASE(22); default: break; }
-#undef MSMD_EPI_CASE
-      }
+    // more than one round of two workgroups per CU: the persistent form (gemm2p_kernel: 512 workgroups, two per CU); GF_ONE_TILE =
+    // the caller opts out (A/B).  The 128 x 128 tile's plain and LayerNorm-operand epilogues: the LayerNorm-residual one (its
+    // launches on the path are single-round) and the 192-row tile do not fit 128 registers in this form (20-128 bytes of scratch).
+    if (batch == 1 && wgs > 512 && !(p.flags & GF_ONE_TILE)) {
+      auto persistent = [&](auto c) { return gemm_launch_kernel<gemm2p_kernel<TO, BM, BN, WM, WN, TI, decltype(c)::value>>(dim3(512), WM * WN * 64, 2 * (BM + BN) * 128, st, p); };
+      if ((r = dispatch_code<11, 21, 12, 22>(code, persistent)) >= 0) return r;
     }
   }
-#define MSMD_EPI_CASE(E) case E: return launch_gemm2<TO, BM, BN, WM, WN, NSTAGE, PIPE, TI, E>(p, batch, st)
+  auto run = [&](auto c) { return launch_gemm2<TO, BM, BN, WM, WN, NSTAGE, PIPE, TI, decltype(c)::value>(p, wgs, batch, st); };
   if constexpr (LNK) {
-    switch (epi + a) { MSMD_EPI_CASE(2); MSMD_EPI_CASE(12); MSMD_EPI_CASE(22); MSMD_EPI_CASE(3); MSMD_EPI_CASE(13); default: break; }
+    if ((r = dispatch_code<2, 12, 22, 3, 13>(code, run)) >= 0) return r;
   }
-  switch (epi + a) { MSMD_EPI_CASE(1); MSMD_EPI_CASE(11); MSMD_EPI_CASE(21); default: break; }
-  if constexpr (sizeof(TI) == 2 && !__is_same(TI, f16_t)) {     // the everything-epilogue is the training step's: bf16 only
-    switch (epi + a) { MSMD_EPI_CASE(10); MSMD_EPI_CASE(20); default: break; }
+  if ((r = dispatch_code<1, 11, 21>(code, run)) >= 0) return r;
+  if constexpr (__is_same(TI, bf16_t)) {     // the everything-epilogue is the training step's: bf16 only
+    if ((r = dispatch_code<10, 20>(code, run)) >= 0) return r;
   }
-#undef MSMD_EPI_CASE
-  return launch_gemm2<TO, BM, BN, WM, WN, NSTAGE, PIPE, TI, 0>(p, batch, st);
+  return run(std::integral_constant<int, 0>{});
 }
 
-// One persistent workgroup per CU: the grid cap is the device's CU count (256 on MI355X; the tile-run logic of the kernel
+// One persistent workgroup per CU: the grid cap is the CURRENT device's CU count (256 on MI355X; the tile-run logic of the kernel
 // works for any workgroup count, the shape rules below are fitted on 256).
 static int gemm8_workgroup_cap() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    cus = n;
-  }
-  return cus;
+  int dev = 0, n = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+  return n;
 }
 
-// gemm8_kernel: which calls it takes, and the launch.  Returns -1 for a call it does not take.
+// element offset of A's last row, plain or windowed
+static long gemm_last_row_offset(const GemmArgs& p) {
+  return p.rows_per_batch < p.M ? ((long)((p.M - 1) / p.rows_per_batch) * p.a_batch_stride + (long)(p.rows_per_batch - 1) * p.lda) : (long)(p.M - 1) * p.lda;
+}
+
+// gemm8_kernel: which calls it takes ...
 static bool gemm8_takes(const GemmArgs& p, int batch, int osz) {
   if (osz != 2 || batch != 1 || p.batch_inner != 1 || (p.N % 256) || (p.K % 64) || p.K < 128 || !p.vec_ok) return false;
-  if (p.Z || p.p_drop > 0.f || (p.flags & 8)) return false;               // inference epilogues only
+  if (p.Z || p.p_drop > 0.f || (p.flags & GF_ACT_BWD)) return false;               // inference epilogues only
   if (((uintptr_t)p.bias & 15) || ((uintptr_t)p.C & 7) || ((uintptr_t)p.R & 7)) return false;
-  {   // the staging offsets are 32-bit byte offsets from A / W
-    const long a_rows = p.rows_per_batch < p.M ? ((long)((p.M - 1) / p.rows_per_batch) * p.a_batch_stride + (long)(p.rows_per_batch - 1) * p.lda) : (long)(p.M - 1) * p.lda;
-    if ((a_rows + p.K) * 2 >= (1L << 32) || ((long)(p.N - 1) * p.ldw + p.K) * 2 >= (1L << 32)) return false;
-  }
-  const int epi = p.a_stats ? 2 : (p.r_stats || p.stats_out) ? 3 : 1;
+  if ((gemm_last_row_offset(p) + p.K) * 2 >= (1L << 32) || ((long)(p.N - 1) * p.ldw + p.K) * 2 >= (1L << 32)) return false;   // 32-bit staging offsets from A / W
+  const GemmEpi epi = epia_family(gemm_epia(p, true));
   if ((p.a_stats || p.r_stats) && ((p.M & 1) || ((uintptr_t)p.a_stats & 15) || ((uintptr_t)p.r_stats & 15))) return false;   // row pairs by 16-byte LDS-DMA
-  if (epi == 2 && (p.R || !p.bias || !p.w_colsum)) return false;
-  if (epi == 3 && (!p.R || !p.bias || p.act != MSMD_ACT_NONE)) return false;
+  if (epi == EPI_LN_OPERAND && (p.R || !p.bias || !p.w_colsum)) return false;
+  if (epi == EPI_LN_RESIDUAL && (!p.R || !p.bias || p.act != MSMD_ACT_NONE)) return false;
   return p.act == MSMD_ACT_NONE || p.act == MSMD_ACT_GELU;
 }
 
@@ -1708,41 +1737,17 @@ static bool gemm8_wins(int M, int N, int K) {
   return fill >= 0.75 && (K >= 1024 || fill >= 0.878);
 }
 
-template <typename TI, int EPIA>
-static int launch_gemm8_e(GemmArgs& p, hipStream_t st) {
-  constexpr int lds = 2 * 4 * 128 * 128 + (EPIA % 10 >= 2 ? 8 * 4096 : 0);   // 128 KB operand ring (its upper half = the epilogue's row block) + the LayerNorm forms' row statistics
-  static bool attr_done = false;
-  auto kfn = gemm8_kernel<TI, EPIA>;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_done = true;
-  }
+// gemm8_kernel, 16-bit or split-pair (KFN, its LDS bytes): one workgroup per 256 x 256 tile up to the CU count
+constexpr int GEMM8_RING = 2 * 4 * 128 * 128;      // 128 KB operand ring (its upper half = the epilogue's row block)
+template <auto KFN, int LDS>
+static int launch_gemm8(GemmArgs& p, hipStream_t st) {
   p.mt = (p.M + 255) / 256; p.nt = p.N / 256;
-  const int tiles = p.mt * p.nt;
+  const int tiles = p.mt * p.nt, cap = gemm8_workgroup_cap();
   // Up to two rounds the launch ends in one burst of output rows: with write-through stores they leave the L2s while the
   // epilogue is still running instead of at the end-of-kernel write-back (6400 x 2304 x 768: 30.3-31.2 -> 28.1-29.3 us, 21312 x
   // 1536 x 512: 50.4 -> 47.3; many-round launches are indifferent or lose: 15968 x 3072 x 1024 101 -> 110)
-  if (tiles <= 512) p.flags |= 1;
-  hipLaunchKernelGGL(kfn, dim3(tiles < gemm8_workgroup_cap() ? tiles : gemm8_workgroup_cap(), 1, 1), dim3(512), lds, st, p);
-  MSMD_RETURN_LAST();
-}
-
-template <typename TO, typename TI>
-static int launch_gemm8(GemmArgs& p, int batch, hipStream_t st) {
-  if constexpr (sizeof(TO) != 2) {
-    return -1;
-  } else {
-    if (!gemm8_takes(p, batch, 2)) return -1;
-    const int epi = p.a_stats ? 2 : (p.r_stats || p.stats_out) ? 3 : 1;
-    switch (epi + (p.act == MSMD_ACT_GELU ? 20 : 10)) {
-      case 11: return launch_gemm8_e<TI, 11>(p, st);
-      case 21: return launch_gemm8_e<TI, 21>(p, st);
-      case 12: return launch_gemm8_e<TI, 12>(p, st);
-      case 22: return launch_gemm8_e<TI, 22>(p, st);
-      case 13: return launch_gemm8_e<TI, 13>(p, st);
-      default: return -1;
-    }
-  }
+  if (tiles <= 512) p.flags |= GF_WRITE_THROUGH;
+  return gemm_launch_kernel<KFN>(dim3(tiles < cap ? tiles : cap), 512, LDS, st, p);
 }
 
 // gemm8_kernel on split-pair operands (SPLIT): the calls it takes, the rule, the launch.  p carries fp16 strides for A / W
@@ -1751,8 +1756,7 @@ static bool gemm8s_takes(const GemmArgs& p, int batch, bool split_out) {
   if (batch != 1 || p.batch_inner != 1 || (p.N % 256) || (p.K % 32) || p.K < 64 || !p.vec_ok) return false;
   if (((uintptr_t)p.bias & 15) || ((uintptr_t)p.C & 15) || ((uintptr_t)p.R & 15)) return false;
   if (split_out ? ((p.ldc % 32) || (p.R && (p.ldr % 32))) : ((p.ldc % 4) || (p.R && (p.ldr % 4)))) return false;
-  const long a_rows = p.rows_per_batch < p.M ? ((long)((p.M - 1) / p.rows_per_batch) * p.a_batch_stride + (long)(p.rows_per_batch - 1) * p.lda) : (long)(p.M - 1) * p.lda;
-  if ((a_rows + 2L * p.K) * 2 >= (1L << 32) || ((long)(p.N - 1) * p.ldw + 2L * p.K) * 2 >= (1L << 32)) return false;   // 32-bit staging offsets
+  if ((gemm_last_row_offset(p) + 2L * p.K) * 2 >= (1L << 32) || ((long)(p.N - 1) * p.ldw + 2L * p.K) * 2 >= (1L << 32)) return false;   // 32-bit staging offsets
   return p.act == MSMD_ACT_NONE || p.act == MSMD_ACT_GELU;
 }
 // ... and which of those it wins (tools/bench_gemm_split.py, us, 128 x 128 gemm2s_kernel -> this kernel folding -> fold-free with
@@ -1770,88 +1774,35 @@ static bool gemm8s_wins(int M, int N, int K, bool w_below_32) {
   const double fill = (double)tiles / (256.0 * (double)((tiles + 255) / 256));
   return fill >= (w_below_32 ? 0.65 : 0.75);
 }
-template <typename TO, int ACTK, int WS>
-static int launch_gemm8s(GemmArgs& p, hipStream_t st) {
-  constexpr int lds = 2 * 4 * 128 * 128;
-  constexpr int SPLIT = (sizeof(TO) == 4 ? 2 : 1) + 4 * WS;
-  static bool attr_done = false;
-  auto kfn = gemm8_kernel<f16_t, 11 + 10 * ACTK, SPLIT>;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_done = true;
-  }
-  p.mt = (p.M + 255) / 256; p.nt = p.N / 256;
-  const int tiles = p.mt * p.nt;
-  if (tiles <= 512) p.flags |= 1;      // write-through stores for launches of up to two rounds (launch_gemm8_e)
-  hipLaunchKernelGGL(kfn, dim3(tiles < gemm8_workgroup_cap() ? tiles : gemm8_workgroup_cap(), 1, 1), dim3(512), lds, st, p);
-  MSMD_RETURN_LAST();
-}
 
-template <typename TO, int BM, int BN, int WM, int WN, int NSTAGE, int ACTK = -1, int WSK = -1>
+// gemm2s_kernel: the W-below-32 form and, on the routed tiles, the activation are constants of the kernel
+template <typename TO, int BM, int BN, int WM, int WN, int NSTAGE>
 static int launch_gemm2s(GemmArgs& p, int batch, hipStream_t st) {
-  if constexpr (WSK == -1) {
-    return (p.flags & 64) ? launch_gemm2s<TO, BM, BN, WM, WN, NSTAGE, ACTK, 1>(p, batch, st)
-                          : launch_gemm2s<TO, BM, BN, WM, WN, NSTAGE, ACTK, 0>(p, batch, st);
-  } else {
-  if constexpr (ACTK == -1 && NSTAGE * (BM + BN) * 128 <= 80 * 1024) {      // the routed tiles: the activation as a constant of the kernel
-    if (p.act == MSMD_ACT_NONE) return launch_gemm2s<TO, BM, BN, WM, WN, NSTAGE, MSMD_ACT_NONE, WSK>(p, batch, st);
-    if (p.act == MSMD_ACT_GELU) return launch_gemm2s<TO, BM, BN, WM, WN, NSTAGE, MSMD_ACT_GELU, WSK>(p, batch, st);
-  }
   constexpr int lds = NSTAGE * (BM + BN) * 128;
-  static bool attr_done = false;
-  auto kfn = gemm2s_kernel<TO, BM, BN, WM, WN, NSTAGE, ACTK, WSK != 0>;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_done = true;
-  }
-  p.mt = (p.M + BM - 1) / BM; p.nt = (p.N + BN - 1) / BN;
-  gemm2_xcd_grid(p, p.lda / 2);      // p.lda is the fp16 stride (doubled by gemm_args)
-  const int xm_n = 8 / p.xn;
-  dim3 grid(((p.mt + xm_n - 1) / xm_n) * ((p.nt + p.xn - 1) / p.xn) * 8, 1, batch);
-  hipLaunchKernelGGL(kfn, grid, dim3(WM * WN * 64), lds, st, p);
-  MSMD_RETURN_LAST();
-  }
+  const dim3 grid(gemm2_xcd_grid(p, BM, BN, p.lda / 2), 1, batch);      // p.lda is the fp16 stride (doubled by gemm_args)
+  return dispatch_code<0, 1>((p.flags & GF_W_BELOW_32) != 0, [&](auto ws) {
+    auto run = [&](auto act) {
+      return gemm_launch_kernel<gemm2s_kernel<TO, BM, BN, WM, WN, NSTAGE, decltype(act)::value, decltype(ws)::value != 0>>(grid, WM * WN * 64, lds, st, p);
+    };
+    int r = -1;
+    if constexpr (lds <= 80 * 1024) r = dispatch_code<MSMD_ACT_NONE, MSMD_ACT_GELU>(p.act, run);
+    return r >= 0 ? r : run(std::integral_constant<int, ACT_RUNTIME>{});
+  });
 }
 
 template <typename TO>
 static int dispatch_gemm2s(GemmArgs& p, int batch, hipStream_t st, int variant) {
   switch (variant) {
-    case 1: return launch_gemm2s<TO, 128, 128, 4, 2, 2>(p, batch, st);   // 64 KB, 2 workgroups / CU (default)
-    case 5: return launch_gemm2s<TO, 64, 64, 2, 2, 4>(p, batch, st);     // small grids
-    case 14: return launch_gemm2s<TO, 256, 64, 8, 1, 2>(p, batch, st);   // narrow outputs (N <= 64): the positional conv
-    case 80:                                                             // 256 x 256 tiles, 8-phase schedule (gemm8_kernel, SPLIT)
+    case GV_SPLIT_128: return launch_gemm2s<TO, 128, 128, 4, 2, 2>(p, batch, st);
+    case GV_SPLIT_64: return launch_gemm2s<TO, 64, 64, 2, 2, 4>(p, batch, st);
+    case GV_256x64: return launch_gemm2s<TO, 256, 64, 8, 1, 2>(p, batch, st);
+    case GV_256:      // gemm8_kernel's SPLIT forms: 1 / 2 = split / fp32 output, + 4 with MSMD_GEMM_W_BELOW_32
       if (!gemm8s_takes(p, batch, sizeof(TO) == 2)) return -1;
-      if (p.flags & 64) return p.act == MSMD_ACT_GELU ? launch_gemm8s<TO, 1, 1>(p, st) : launch_gemm8s<TO, 0, 1>(p, st);   // MSMD_GEMM_W_BELOW_32
-      return p.act == MSMD_ACT_GELU ? launch_gemm8s<TO, 1, 0>(p, st) : launch_gemm8s<TO, 0, 0>(p, st);
-    default: return -1;
-  }
-}
-
-// Product variants: 14 = 256 x 64 for narrow outputs; 17 = 128 x 128, 8 waves (4 x 2), 2-stage ring, fragment reads of both k-steps issued first (default
-// once the grid fills the chip); 13 = the same tile with the compiler's own read / multiply interleave; 9 / 12 = 64 x 64
-// tiles with a 4- / 2-stage ring for grids that would not fill the chip.  Every other family that was built and measured
-// lost and was removed: its numbers are in DESIGN.md section 5 / 5b.
-// The variants dispatch_gemm2 has for operand type TI; gemm16_route asks the same question, so a routed variant always launches.
-template <typename TI>
-static constexpr bool gemm2_has(int variant) {
-  if (variant == 13 || variant == 66) return __is_same(TI, bf16_t);   // the A/B forms of 17: bf16 only
-  return variant == 9 || variant == 12 || variant == 14 || variant == 15 || variant == 17 || variant == 80;
-}
-
-template <typename TO, typename TI>
-static int dispatch_gemm2(GemmArgs& p, int batch, hipStream_t st, int variant) {
-  if (!gemm2_has<TI>(variant)) return -1;
-  if constexpr (__is_same(TI, bf16_t)) {
-    if (variant == 13) return launch_gemm2<TO, 128, 128, 4, 2, 2>(p, batch, st);
-    if (variant == 66) return launch_gemm2<TO, 128, 128, 4, 2, 2, true>(p, batch, st);   // 17 as ONE kernel with every epilogue (round 3's form)
-  }
-  switch (variant) {
-    case 9: return launch_gemm2_epi<TO, 64, 64, 2, 2, 4, false, TI>(p, batch, st);
-    case 12: return launch_gemm2_epi<TO, 64, 64, 2, 2, 2, false, TI>(p, batch, st);
-    case 14: return launch_gemm2_epi<TO, 256, 64, 8, 1, 2, true, TI>(p, batch, st);   // narrow outputs (N <= 64): 8 waves of 32 x 64
-    case 15: return launch_gemm2_epi<TO, 192, 128, 4, 2, 2, true, TI>(p, batch, st);  // tall grids (M >= 16 k): 80 KB, still 2 workgroups / CU
-    case 17: return launch_gemm2_epi<TO, 128, 128, 4, 2, 2, true, TI>(p, batch, st);
-    case 80: return launch_gemm8<TO, TI>(p, batch, st);                               // 256 x 256, 8-phase schedule, one workgroup per CU
+      return dispatch_code<11, 21>(epia(EPI_PLAIN, p.act), [&](auto c) {
+        return dispatch_code<0, 1>((p.flags & GF_W_BELOW_32) != 0, [&](auto ws) {
+          return launch_gemm8<gemm8_kernel<f16_t, decltype(c)::value, (sizeof(TO) == 4 ? 2 : 1) + 4 * decltype(ws)::value>, GEMM8_RING>(p, st);
+        });
+      });
     default: return -1;
   }
 }
@@ -1860,16 +1811,46 @@ template <typename T, typename TO>
 static int launch_gemm(GemmArgs& p, int batch, hipStream_t st) {
   // Small-N / small-M problems use the 64x64 tile (less padding waste, more workgroups).
   const bool small = (p.N <= 64) || ((long)((p.M + 127) / 128) * ((p.N + 127) / 128) * batch < 128);
-  if (small) {
-    p.mt = (p.M + 63) / 64; p.nt = (p.N + 63) / 64;
-    dim3 grid(((p.mt + 7) / 8) * 8 * p.nt, 1, batch);
-    hipLaunchKernelGGL((gemm_kernel<T, TO, 64, 64>), grid, dim3(256), 0, st, p);
-  } else {
-    p.mt = (p.M + 127) / 128; p.nt = (p.N + 127) / 128;
-    dim3 grid(((p.mt + 7) / 8) * 8 * p.nt, 1, batch);
-    hipLaunchKernelGGL((gemm_kernel<T, TO, 128, 128>), grid, dim3(256), 0, st, p);
+  const int B = small ? 64 : 128;
+  p.mt = (p.M + B - 1) / B; p.nt = (p.N + B - 1) / B;
+  const dim3 grid(((p.mt + 7) / 8) * 8 * p.nt, 1, batch);
+  return small ? gemm_launch_kernel<gemm_kernel<T, TO, 64, 64>>(grid, 256, 0, st, p)
+               : gemm_launch_kernel<gemm_kernel<T, TO, 128, 128>>(grid, 256, 0, st, p);
+}
+
+// Every other family that was built and measured lost and was removed: its numbers are in DESIGN.md section 5 / 5b.
+// The LDS-DMA variants dispatch_gemm has for bf16 / fp16 operands; gemm16_route asks the same question, so a routed variant always launches.
+static constexpr bool gemm2_has(int variant, bool bf16) {
+  if (variant == GV_128_AB || variant == GV_128_ONE_AB) return bf16;
+  return variant == GV_64_DEEP || variant == GV_64 || variant == GV_256x64 || variant == GV_192 || variant == GV_128 || variant == GV_256;
+}
+
+// The launcher of a variant for plain (not split-pair) operands TI and output TO
+template <typename TO, typename TI>
+static int dispatch_gemm(GemmArgs& p, int batch, hipStream_t st, int variant) {
+  if (variant == GV_GENERIC) return launch_gemm<TI, TO>(p, batch, st);
+  if constexpr (sizeof(TI) == 2) {
+    if (!gemm2_has(variant, __is_same(TI, bf16_t))) return -1;
+    if constexpr (__is_same(TI, bf16_t)) {
+      if (variant == GV_128_AB) return launch_gemm2<TO, 128, 128, 4, 2, 2>(p, gemm2_xcd_grid(p, 128, 128, p.lda), batch, st);
+      if (variant == GV_128_ONE_AB) return launch_gemm2<TO, 128, 128, 4, 2, 2, true>(p, gemm2_xcd_grid(p, 128, 128, p.lda), batch, st);
+    }
+    switch (variant) {
+      case GV_64_DEEP: return launch_gemm2_epi<TO, 64, 64, 2, 2, 4, false, TI>(p, batch, st);
+      case GV_64: return launch_gemm2_epi<TO, 64, 64, 2, 2, 2, false, TI>(p, batch, st);
+      case GV_256x64: return launch_gemm2_epi<TO, 256, 64, 8, 1, 2, true, TI>(p, batch, st);   // 8 waves of 32 x 64
+      case GV_192: return launch_gemm2_epi<TO, 192, 128, 4, 2, 2, true, TI>(p, batch, st);
+      case GV_128: return launch_gemm2_epi<TO, 128, 128, 4, 2, 2, true, TI>(p, batch, st);
+    }
+    if constexpr (sizeof(TO) == 2) {      // GV_256
+      if (!gemm8_takes(p, batch, 2)) return -1;
+      return dispatch_code<11, 21, 12, 22, 13>(gemm_epia(p, true), [&](auto c) {      // the LayerNorm forms add their row statistics to the ring
+        constexpr int E = decltype(c)::value;
+        return launch_gemm8<gemm8_kernel<TI, E>, GEMM8_RING + (epia_family(E) >= EPI_LN_OPERAND ? 8 * 4096 : 0)>(p, st);
+      });
+    }
   }
-  MSMD_RETURN_LAST();
+  return -1;
 }
 
 // Between 9 600 and 16 000 rows (the training step's M = 12 800: both windows in one batch) the tile follows how full the
@@ -1884,28 +1865,39 @@ static bool tall_rounds_favour_192(int M, long tiles128, long tiles192) {
   return 1.2 * fill192 > 1.03 * fill128;
 }
 
-// The one place a GemmArgs is filled; fields it does not name keep the struct's defaults.  `ab` scales every A / W stride: 2 for
-// split-pair operands (logical sizes in, fp16 strides into the kernel), else 1.  osz = bytes of an output element, 0 for
-// split-pair output (the entry has required whole 32-element blocks: every vector access is aligned).
-static GemmArgs gemm_args(const void* A, const void* W, const float* bias, const void* residual, void* C, int M, int N, int K,
-                          long lda, int rows_per_batch, long a_batch_stride, long ldw, long ldc, long ldr, int act, int flags,
-                          long strideA, long strideW, long strideC, long strideBias, long strideR, int batch_inner,
-                          long strideA2, long strideW2, long strideC2, int osz, int ab = 1) {
+// An entry's arguments by name; a default means "absent".  The plans read it, gemm_args copies it into the kernels' GemmArgs.
+struct GemmCall {
+  const void* A = nullptr; const void* W = nullptr; const float* bias = nullptr; const void* residual = nullptr; void* C = nullptr;
+  int M = 0, N = 0, K = 0, in_dtype = 0, out_dtype = 0;
+  long lda = 0; int rows_per_batch = 0; long a_batch_stride = 0; long ldw = 0, ldc = 0, ldr = 0;
+  int act = 0;      // the entry's word: MSMD_ACT_*, MSMD_GEMM_VARIANT, MSMD_GEMM_* flags (gemm_unpack_act)
+  int batch = 1; long strideA = 0, strideW = 0, strideC = 0, strideBias = 0, strideR = 0;
+  int batch_inner = 1; long strideA2 = 0, strideW2 = 0, strideC2 = 0;
+  void* z_out = nullptr; float p_drop = 0.f; const unsigned long* rng = nullptr; unsigned site = 0; int internal_flags = 0;      // the training epilogue; GF_ACT_BWD
+  // msmd_gemm_ln: the statistics operands, their slab widths, eps
+  const float* a_stats = nullptr; const float* w_colsum = nullptr; const float* r_stats = nullptr; const float* r_gamma = nullptr; const float* r_beta = nullptr;
+  float* stats_out = nullptr; int slab_in = 0, slab_out = 0; float eps = 1e-5f;
+};
+
+// The one place a GemmArgs is filled; fields it does not name keep the struct's defaults.  act / flags: of the unpacked word, as the
+// plan passes them on.  `ab` scales every A / W stride: 2 for split-pair operands (logical sizes in, fp16 strides into the kernel), else 1.
+// osz = bytes of an output element, 0 for split-pair output (the entry has required whole 32-element blocks: every vector access is aligned).
+static GemmArgs gemm_args(const GemmCall& c, int act, int flags, int osz, int ab = 1) {
   GemmArgs p{};
-  if (rows_per_batch <= 0) rows_per_batch = M;
-  p.A = A; p.W = W; p.bias = bias; p.R = residual; p.C = C;
-  p.M = M; p.N = N; p.K = K;
-  p.lda = ab * lda; p.rows_per_batch = rows_per_batch; p.a_batch_stride = ab * a_batch_stride;
-  p.ldw = ab * ldw; p.ldc = ldc; p.ldr = ldr; p.act = act;
+  const int rows_per_batch = c.rows_per_batch <= 0 ? c.M : c.rows_per_batch;
+  p.A = c.A; p.W = c.W; p.bias = c.bias; p.R = c.residual; p.C = c.C;
+  p.M = c.M; p.N = c.N; p.K = c.K;
+  p.lda = ab * c.lda; p.rows_per_batch = rows_per_batch; p.a_batch_stride = ab * c.a_batch_stride;
+  p.ldw = ab * c.ldw; p.ldc = c.ldc; p.ldr = c.ldr; p.act = act;
   p.inv_rpb = 1.0f / (float)rows_per_batch;
-  p.strideA = ab * strideA; p.strideW = ab * strideW; p.strideC = strideC; p.strideBias = strideBias; p.strideR = strideR;
-  p.batch_inner = batch_inner; p.strideA2 = ab * strideA2; p.strideW2 = ab * strideW2; p.strideC2 = strideC2;
+  p.strideA = ab * c.strideA; p.strideW = ab * c.strideW; p.strideC = c.strideC; p.strideBias = c.strideBias; p.strideR = c.strideR;
+  p.batch_inner = c.batch_inner; p.strideA2 = ab * c.strideA2; p.strideW2 = ab * c.strideW2; p.strideC2 = c.strideC2;
   p.xn = 1;
   p.vec_ok = osz == 0 ||
-             ((ldc % 4 == 0) && (strideC % 4 == 0) && (strideC2 % 4 == 0) && (((uintptr_t)C % (4 * osz)) == 0) &&
-              (!residual || ((ldr % 4 == 0) && (strideR % 4 == 0) && (((uintptr_t)residual % (4 * osz)) == 0))));
-  if ((flags & 2) && (osz != 2 || (ldc % 8) || (strideC % 8) || (strideC2 % 8) || ((uintptr_t)C % 16) || !p.vec_ok))
-    flags &= ~2;   // paired stores need 16-byte aligned row pairs
+             ((c.ldc % 4 == 0) && (c.strideC % 4 == 0) && (c.strideC2 % 4 == 0) && (((uintptr_t)c.C % (4 * osz)) == 0) &&
+              (!c.residual || ((c.ldr % 4 == 0) && (c.strideR % 4 == 0) && (((uintptr_t)c.residual % (4 * osz)) == 0))));
+  if ((flags & GF_PAIRED_STORES) && (osz != 2 || (c.ldc % 8) || (c.strideC % 8) || (c.strideC2 % 8) || ((uintptr_t)c.C % 16) || !p.vec_ok))
+    flags &= ~GF_PAIRED_STORES;   // paired stores need 16-byte aligned row pairs
   p.flags = flags;
   return p;
 }
@@ -1913,227 +1905,235 @@ static GemmArgs gemm_args(const void* A, const void* W, const float* bias, const
 // The kernel of a call on split-pair operands: variant 1 / 5 / 14 / 80, -1 for a hint that names none of them.
 static int gemm_split_route(const GemmArgs& p, int nz, bool split_out, int hint, int flags) {
   const bool takes8 = gemm8s_takes(p, nz, split_out);
-  if (hint == 80 && !takes8) hint = 0;   // a hint the call cannot follow
-  if (hint) return (hint == 1 || hint == 5 || hint == 14 || hint == 80) ? hint : -1;
+  if (hint == GV_256 && !takes8) hint = 0;   // a hint the call cannot follow
+  if (hint) return (hint == GV_SPLIT_128 || hint == GV_SPLIT_64 || hint == GV_256x64 || hint == GV_256) ? hint : -1;
   // the library's own choice takes the 256 x 256 kernel only under MSMD_GEMM_W_BELOW_32: there it returns the bits of
   // gemm2s_kernel's WS form, so the row count of a launch never changes a row's result (its folding form, reachable by the
   // variant hint, sums the cross terms in another order than gemm2s_kernel's two accumulators)
-  if (!(flags & 32) && (flags & 64) && takes8 && gemm8s_wins(p.M, p.N, p.K, true)) return 80;
-  if (p.N <= 64) return (long)((p.M + 255) / 256) * nz >= 256 ? 14 : 5;
-  return (long)((p.M + 127) / 128) * ((p.N + 127) / 128) * nz >= 192 ? 1 : 5;
+  if (!(flags & GF_NO_256) && (flags & GF_W_BELOW_32) && takes8 && gemm8s_wins(p.M, p.N, p.K, true)) return GV_256;
+  if (p.N <= 64) return (long)((p.M + 255) / 256) * nz >= 256 ? GV_256x64 : GV_SPLIT_64;
+  return (long)((p.M + 127) / 128) * ((p.N + 127) / 128) * nz >= 192 ? GV_SPLIT_128 : GV_SPLIT_64;
 }
 
-// The kernel of a call on 16-bit operands with K % 64 == 0 (msmd_gemm's family and msmd_gemm_ln): the variant dispatch_gemm2
+// The kernel of a call on 16-bit operands with K % 64 == 0 (msmd_gemm's family and msmd_gemm_ln): the variant dispatch_gemm
 // launches, or 0 for gemm_kernel (a hint that names no variant of this operand type).  Measured on MI355X.
 // Priority of the library's own choice: 256 x 256, the tall 192 x 128 tile, the last-round fill rule, 128 x 128, 256 x 64, 64 x 64.
-// flags bit 5 (MSMD_GEMM_NO_256_TILE) = the caller opts out of the 256 x 256 kernel (A/B).
+// GF_NO_256 (MSMD_GEMM_NO_256_TILE) = the caller opts out of the 256 x 256 kernel (A/B).
 // cols: 0 for a plain call, where every tile is open.  msmd_gemm_ln's statistics slabs name the tile family: 128 = the
 // 128-column tiles (17 / 15; 64-column slabs, which the 256 x 256 kernel writes too), 64 = the 64 x 64 tiles (9 / 12; 32-column
 // slabs, so the 256 x 256 kernel only where the call writes no statistics).  Its hints choose within that family.
 static int gemm16_route(const GemmArgs& p, int nz, int osz, bool bf16, int hint, int flags, int cols = 0) {
   const bool takes8 = (cols != 64 || !p.stats_out) && gemm8_takes(p, nz, osz);
-  const bool rule8 = hint == 0 && !(flags & 32);
+  const bool rule8 = hint == 0 && !(flags & GF_NO_256);
   // a hint the call cannot follow leaves the library's own choice: 80 on a call the kernel does not take, and for msmd_gemm_ln
   // anything but 15 / 17 / 66 inside the 128-column family
-  if (!(hint == 80 ? takes8 : !cols || (cols == 128 && (hint == 15 || hint == 17 || hint == 66)))) hint = 0;
-  if (hint) return (bf16 ? gemm2_has<bf16_t>(hint) : gemm2_has<f16_t>(hint)) ? hint : 0;
+  if (!(hint == GV_256 ? takes8 : !cols || (cols == 128 && (hint == GV_192 || hint == GV_128 || hint == GV_128_ONE_AB)))) hint = 0;
+  if (hint) return gemm2_has(hint, bf16) ? hint : GV_GENERIC;
   const int M = p.M, N = p.N;
   const long tiles128 = (long)((M + 127) / 128) * ((N + 127) / 128) * nz;
   const long tiles192 = (long)((M + 191) / 192) * ((N + 127) / 128) * nz;
   const bool wide = cols ? cols == 128 : N > 64;
-  if (rule8 && takes8 && gemm8_wins(M, N, p.K)) return 80;      // 256 x 256 tiles, 8-phase schedule
+  if (rule8 && takes8 && gemm8_wins(M, N, p.K)) return GV_256;
   // tall grids: 192 x 128 tiles (76.8 FLOP per staged byte instead of 64, still two workgroups per CU).  Measured against
   // the 128 x 128 tile: conv1 454 -> 379 us, 21312 x 512 x 2048 58.7 -> 49.6, 21312 x 2048 x 512 76.6 -> 64.7; worse
   // below ~16 k rows (12800 x 512 x 1024: 22 -> 28 us) and mixed at M = 6400
-  if (wide && M >= 16000 && tiles192 >= 400) return 15;
+  if (wide && M >= 16000 && tiles192 >= 400) return GV_192;
   // inference epilogues only: the 192-row tile's everything-epilogue runs one workgroup per CU
-  if (wide && osz == 2 && !p.Z && !(p.p_drop > 0.f) && !(p.flags & 8) && tall_rounds_favour_192(M, tiles128, tiles192)) return 15;
+  if (wide && osz == 2 && !p.Z && !(p.p_drop > 0.f) && !(p.flags & GF_ACT_BWD) && tall_rounds_favour_192(M, tiles128, tiles192)) return GV_192;
   // the 128 x 128 LDS-DMA kernel (8 waves as 4 x 2, 2-stage ring, fragment reads pipelined) wins once the grid fills the chip at
   // 2 workgroups per CU; below that, 64 x 64 tiles (deep ring for long K) keep more CUs busy
-  if (cols ? wide : wide && tiles128 >= 192) return 17;
-  if (!cols && N <= 64 && (long)((M + 255) / 256) * nz >= 256) return 14;   // the positional conv: 256 x 64 tiles, 140 -> 85 us
-  return p.K >= 1024 ? 9 : 12;
+  if (cols ? wide : wide && tiles128 >= 192) return GV_128;
+  if (!cols && N <= 64 && (long)((M + 255) / 256) * nz >= 256) return GV_256x64;   // the positional conv: 256 x 64 tiles, 140 -> 85 us
+  return p.K >= 1024 ? GV_64_DEEP : GV_64;
 }
 
 // The plan of a msmd_gemm / msmd_gemm_ex / msmd_gemm_actbwd / msmd_gemm_batched2 call: checks it, fills p and picks the kernel.
 // Returns the variant gemm_launch will launch, 0 for gemm_kernel, -1 for a call the library rejects.  Host arithmetic only,
 // no HIP call and no state: msmd_gemm_route is this function alone.
-static int gemm_plan(GemmArgs& p, const void* A, const void* W, const float* bias, const void* residual, void* C, int M, int N,
-                     int K, int in_dtype, int out_dtype, long lda, int rows_per_batch, long a_batch_stride, long ldw, long ldc,
-                     long ldr, int act, int batch, long strideA, long strideW, long strideC, long strideBias, long strideR,
-                     int batch_inner, long strideA2, long strideW2, long strideC2, void* z_out, float p_drop,
-                     const unsigned long* rng, unsigned site, int internal_flags) {
-  if (M <= 0 || N <= 0 || K <= 0 || batch <= 0 || batch_inner <= 0 || !A || !W || !C) return -1;
-  const int hint = (act >> 8) & 0xff;  // caller-chosen kernel variant (host-side autotune), 0 = the library's own choice
-  const int flags = ((act >> 16) & 0x7) | (((act >> 19) & 1) << 4) | (((act >> 20) & 1) << 5) | (((act >> 21) & 1) << 6) | internal_flags;  // MSMD_GEMM_WRITE_THROUGH / MSMD_GEMM_PAIRED_STORES (include/msmd_hip.h)
-  act &= 0xff;
-  const int nz = batch * batch_inner;
-  if (in_dtype == MSMD_F16X2) {
+static int gemm_plan(GemmArgs& p, const GemmCall& c) {
+  if (c.M <= 0 || c.N <= 0 || c.K <= 0 || c.batch <= 0 || c.batch_inner <= 0 || !c.A || !c.W || !c.C) return -1;
+  const GemmActWord u = gemm_unpack_act(c.act);
+  const int flags = u.flags | c.internal_flags, nz = c.batch * c.batch_inner;
+  const auto strides_divide = [&](int E) {
+    return !(c.K % E || c.lda % E || c.ldw % E || c.a_batch_stride % E || c.strideA % E || c.strideW % E || c.strideA2 % E || c.strideW2 % E);
+  };
+  if (c.in_dtype == MSMD_F16X2) {
     // split-pair operands: 32-element blocks must stay whole
-    if (out_dtype != MSMD_F32 && out_dtype != MSMD_F16X2) return -1;
-    if (K % 32 || lda % 32 || ldw % 32 || a_batch_stride % 32 || strideA % 32 || strideW % 32 || strideA2 % 32 ||
-        strideW2 % 32 || z_out || p_drop != 0.f)
-      return -1;
-    if (((uintptr_t)A & 15) || ((uintptr_t)W & 15) || ((uintptr_t)C & 15)) return -1;
-    if (out_dtype == MSMD_F16X2) {
-      if ((N & 3) || ldc % 32 || strideC % 32 || strideC2 % 32 || (residual && (ldr % 32 || strideR % 32))) return -1;
-      if (bias && (((uintptr_t)bias & 15) || (strideBias & 3))) return -1;
+    if (c.out_dtype != MSMD_F32 && c.out_dtype != MSMD_F16X2) return -1;
+    if (!strides_divide(32) || c.z_out || c.p_drop != 0.f) return -1;
+    if (((uintptr_t)c.A & 15) || ((uintptr_t)c.W & 15) || ((uintptr_t)c.C & 15)) return -1;
+    if (c.out_dtype == MSMD_F16X2) {
+      if ((c.N & 3) || c.ldc % 32 || c.strideC % 32 || c.strideC2 % 32 || (c.residual && (c.ldr % 32 || c.strideR % 32))) return -1;
+      if (c.bias && (((uintptr_t)c.bias & 15) || (c.strideBias & 3))) return -1;
     }
-    p = gemm_args(A, W, bias, residual, C, M, N, K, lda, rows_per_batch, a_batch_stride, ldw, ldc, ldr, act, flags & (1 | 64),
-                  strideA, strideW, strideC, strideBias, strideR, batch_inner, strideA2, strideW2, strideC2,
-                  out_dtype == MSMD_F32 ? 4 : 0, 2);
-    return gemm_split_route(p, nz, out_dtype == MSMD_F16X2, hint, flags);
+    p = gemm_args(c, u.act, flags & (GF_WRITE_THROUGH | GF_W_BELOW_32), c.out_dtype == MSMD_F32 ? 4 : 0, 2);
+    return gemm_split_route(p, nz, c.out_dtype == MSMD_F16X2, u.hint, flags);
   }
-  if (in_dtype == MSMD_F32 ? (out_dtype != MSMD_F32 && out_dtype != MSMD_F16 && out_dtype != MSMD_BF16)
-                           : ((in_dtype != MSMD_F16 && in_dtype != MSMD_BF16) || (out_dtype != in_dtype && out_dtype != MSMD_F32)))
+  if (c.in_dtype == MSMD_F32 ? (c.out_dtype != MSMD_F32 && c.out_dtype != MSMD_F16 && c.out_dtype != MSMD_BF16)
+                             : ((c.in_dtype != MSMD_F16 && c.in_dtype != MSMD_BF16) || (c.out_dtype != c.in_dtype && c.out_dtype != MSMD_F32)))
     return -1;
-  const int E = in_dtype == MSMD_F32 ? 4 : 8;
-  if (K % E || lda % E || ldw % E || a_batch_stride % E || strideA % E || strideW % E || strideA2 % E || strideW2 % E)
-    return -1;
-  if (((uintptr_t)A & 15) || ((uintptr_t)W & 15)) return -1;
-  if (p_drop != 0.f && (!(p_drop > 0.f && p_drop < 1.f) || !rng || (N & 3) || ldc != N || batch != 1 || batch_inner != 1))
+  if (!strides_divide(c.in_dtype == MSMD_F32 ? 4 : 8)) return -1;
+  if (((uintptr_t)c.A & 15) || ((uintptr_t)c.W & 15)) return -1;
+  if (c.p_drop != 0.f && (!(c.p_drop > 0.f && c.p_drop < 1.f) || !c.rng || (c.N & 3) || c.ldc != c.N || c.batch != 1 || c.batch_inner != 1))
     return -1;  // the mask index assumes one contiguous (M, N) output
-  const int osz = out_dtype == MSMD_F32 ? 4 : 2;
-  p = gemm_args(A, W, bias, residual, C, M, N, K, lda, rows_per_batch, a_batch_stride, ldw, ldc, ldr, act, flags, strideA,
-                strideW, strideC, strideBias, strideR, batch_inner, strideA2, strideW2, strideC2, osz);
-  p.Z = z_out; p.p_drop = p_drop; p.rng = rng; p.site = site;     // the training epilogue (msmd_gemm_ex, msmd_gemm_actbwd)
-  if (in_dtype == MSMD_F32 || (K % 64)) return 0;    // the LDS-DMA kernels: 16-bit operands in whole 128-byte K tiles
-  return gemm16_route(p, nz, osz, in_dtype == MSMD_BF16, hint, flags);
+  const int osz = c.out_dtype == MSMD_F32 ? 4 : 2;
+  p = gemm_args(c, u.act, flags, osz);
+  p.Z = c.z_out; p.p_drop = c.p_drop; p.rng = c.rng; p.site = c.site;     // the training epilogue (msmd_gemm_ex, msmd_gemm_actbwd)
+  if (c.in_dtype == MSMD_F32 || (c.K % 64)) return GV_GENERIC;    // the LDS-DMA kernels: 16-bit operands in whole 128-byte K tiles
+  return gemm16_route(p, nz, osz, c.in_dtype == MSMD_BF16, u.hint, flags);
 }
 
+// One dispatch from the (in, out) dtype pair, which the plan has accepted, to the template types.  -1: no such kernel.
 static int gemm_launch(GemmArgs& p, int in_dtype, int out_dtype, int nz, int variant, hipStream_t st) {
-  int r = -1;
-  if (in_dtype == MSMD_F16X2) r = out_dtype == MSMD_F32 ? dispatch_gemm2s<float>(p, nz, st, variant) : dispatch_gemm2s<f16_t>(p, nz, st, variant);
-  else if (variant && in_dtype == MSMD_BF16) r = out_dtype == MSMD_BF16 ? dispatch_gemm2<bf16_t, bf16_t>(p, nz, st, variant) : dispatch_gemm2<float, bf16_t>(p, nz, st, variant);
-  else if (variant) r = out_dtype == MSMD_F16 ? dispatch_gemm2<f16_t, f16_t>(p, nz, st, variant) : dispatch_gemm2<float, f16_t>(p, nz, st, variant);
-  else if (in_dtype == MSMD_F16 && out_dtype == MSMD_F16) r = launch_gemm<f16_t, f16_t>(p, nz, st);
-  else if (in_dtype == MSMD_F16 && out_dtype == MSMD_F32) r = launch_gemm<f16_t, float>(p, nz, st);
-  else if (in_dtype == MSMD_F32 && out_dtype == MSMD_F16) r = launch_gemm<float, f16_t>(p, nz, st);
-  else if (in_dtype == MSMD_BF16 && out_dtype == MSMD_BF16) r = launch_gemm<bf16_t, bf16_t>(p, nz, st);
-  else if (in_dtype == MSMD_BF16 && out_dtype == MSMD_F32) r = launch_gemm<bf16_t, float>(p, nz, st);
-  else if (in_dtype == MSMD_F32 && out_dtype == MSMD_F32) r = launch_gemm<float, float>(p, nz, st);
-  else if (in_dtype == MSMD_F32 && out_dtype == MSMD_BF16) r = launch_gemm<float, bf16_t>(p, nz, st);
-  return r >= 0 ? r : 1;     // a variant the plan chose and the dispatch does not have is an error, never another kernel
+  switch (in_dtype * 4 + out_dtype) {
+    case MSMD_F16X2 * 4 + MSMD_F32: return dispatch_gemm2s<float>(p, nz, st, variant);
+    case MSMD_F16X2 * 4 + MSMD_F16X2: return dispatch_gemm2s<f16_t>(p, nz, st, variant);
+    case MSMD_BF16 * 4 + MSMD_BF16: return dispatch_gemm<bf16_t, bf16_t>(p, nz, st, variant);
+    case MSMD_BF16 * 4 + MSMD_F32: return dispatch_gemm<float, bf16_t>(p, nz, st, variant);
+    case MSMD_F16 * 4 + MSMD_F16: return dispatch_gemm<f16_t, f16_t>(p, nz, st, variant);
+    case MSMD_F16 * 4 + MSMD_F32: return dispatch_gemm<float, f16_t>(p, nz, st, variant);
+    case MSMD_F32 * 4 + MSMD_F32: return dispatch_gemm<float, float>(p, nz, st, variant);
+    case MSMD_F32 * 4 + MSMD_F16: return dispatch_gemm<f16_t, float>(p, nz, st, variant);
+    case MSMD_F32 * 4 + MSMD_BF16: return dispatch_gemm<bf16_t, float>(p, nz, st, variant);
+  }
+  return -1;
 }
 
-static int gemm_impl(const void* A, const void* W, const float* bias, const void* residual, void* C, int M, int N, int K,
-                     int in_dtype, int out_dtype, long lda, int rows_per_batch, long a_batch_stride, long ldw, long ldc,
-                     long ldr, int act, int batch, long strideA, long strideW, long strideC, long strideBias,
-                     long strideR, int batch_inner, long strideA2, long strideW2, long strideC2, msmd_stream_t stream,
-                     void* z_out = nullptr, float p_drop = 0.f, const unsigned long* rng = nullptr, unsigned site = 0,
-                     int internal_flags = 0) {
+// An entry: the plan, then the launch.
+static int gemm_run(int (*plan)(GemmArgs&, const GemmCall&), const GemmCall& c, msmd_stream_t stream) {
   GemmArgs p;
-  const int variant = gemm_plan(p, A, W, bias, residual, C, M, N, K, in_dtype, out_dtype, lda, rows_per_batch, a_batch_stride,
-                                ldw, ldc, ldr, act, batch, strideA, strideW, strideC, strideBias, strideR, batch_inner,
-                                strideA2, strideW2, strideC2, z_out, p_drop, rng, site, internal_flags);
-  return variant < 0 ? 1 : gemm_launch(p, in_dtype, out_dtype, batch * batch_inner, variant, (hipStream_t)stream);
+  const int variant = plan(p, c);
+  const int r = variant < 0 ? -1 : gemm_launch(p, c.in_dtype, c.out_dtype, c.batch * c.batch_inner, variant, (hipStream_t)stream);
+  return r >= 0 ? r : 1;     // a call the plan rejects; a variant the plan chose and the dispatch does not have is an error, never another kernel
 }
 
-extern "C" int msmd_gemm(const void* A, const void* W, const float* bias, const void* residual, void* C, int M,
-                         int N, int K, int in_dtype, int out_dtype, long lda, int rows_per_batch,
-                         long a_batch_stride, long ldw, long ldc, long ldr, int act, int batch, long strideA,
-                         long strideW, long strideC, long strideBias, long strideR, msmd_stream_t stream) {
-  return gemm_impl(A, W, bias, residual, C, M, N, K, in_dtype, out_dtype, lda, rows_per_batch, a_batch_stride, ldw, ldc,
-                   ldr, act, batch, strideA, strideW, strideC, strideBias, strideR, 1, 0, 0, 0, stream);
+// The call record of msmd_gemm_ex's argument list (msmd_gemm: the same without the training epilogue; msmd_gemm_route)
+static GemmCall gemm_ex_call(const void* A, const void* W, const float* bias, const void* residual, void* C, int M, int N, int K, int in_dtype,
+                             int out_dtype, long lda, int rows_per_batch, long a_batch_stride, long ldw, long ldc, long ldr, int act, int batch,
+                             long strideA, long strideW, long strideC, long strideBias, long strideR, void* z_out, float p_drop,
+                             const unsigned long* rng_state, unsigned int site) {
+  GemmCall c;
+  c.A = A; c.W = W; c.bias = bias; c.residual = residual; c.C = C;
+  c.M = M; c.N = N; c.K = K; c.in_dtype = in_dtype; c.out_dtype = out_dtype;
+  c.lda = lda; c.rows_per_batch = rows_per_batch; c.a_batch_stride = a_batch_stride; c.ldw = ldw; c.ldc = ldc; c.ldr = ldr;
+  c.act = act; c.batch = batch;
+  c.strideA = strideA; c.strideW = strideW; c.strideC = strideC; c.strideBias = strideBias; c.strideR = strideR;
+  c.z_out = z_out; c.p_drop = p_drop; c.rng = rng_state; c.site = site;
+  return c;
+}
+
+extern "C" int msmd_gemm_ex(const void* A, const void* W, const float* bias, const void* residual, void* C, int M, int N, int K, int in_dtype,
+                            int out_dtype, long lda, int rows_per_batch, long a_batch_stride, long ldw, long ldc, long ldr, int act, int batch,
+                            long strideA, long strideW, long strideC, long strideBias, long strideR, void* z_out, float p_drop,
+                            const unsigned long* rng_state, unsigned int site, msmd_stream_t stream) {
+  return gemm_run(gemm_plan, gemm_ex_call(A, W, bias, residual, C, M, N, K, in_dtype, out_dtype, lda, rows_per_batch, a_batch_stride, ldw, ldc, ldr,
+                                          act, batch, strideA, strideW, strideC, strideBias, strideR, z_out, p_drop, rng_state, site), stream);
+}
+
+extern "C" int msmd_gemm(const void* A, const void* W, const float* bias, const void* residual, void* C, int M, int N, int K, int in_dtype,
+                         int out_dtype, long lda, int rows_per_batch, long a_batch_stride, long ldw, long ldc, long ldr, int act, int batch,
+                         long strideA, long strideW, long strideC, long strideBias, long strideR, msmd_stream_t stream) {
+  return msmd_gemm_ex(A, W, bias, residual, C, M, N, K, in_dtype, out_dtype, lda, rows_per_batch, a_batch_stride, ldw, ldc, ldr,
+                      act, batch, strideA, strideW, strideC, strideBias, strideR, nullptr, 0.f, nullptr, 0, stream);
+}
+
+// What msmd_gemm_ex (and msmd_gemm: z_out = NULL, p_drop = 0) would launch for the same arguments: the variant, 0 for
+// gemm_kernel, -1 for a call it rejects.  Launches nothing.
+extern "C" int msmd_gemm_route(const void* A, const void* W, const float* bias, const void* residual, void* C, int M, int N, int K, int in_dtype,
+                               int out_dtype, long lda, int rows_per_batch, long a_batch_stride, long ldw, long ldc, long ldr, int act, int batch,
+                               long strideA, long strideW, long strideC, long strideBias, long strideR, void* z_out, float p_drop,
+                               const unsigned long* rng_state, unsigned int site, msmd_stream_t) {
+  GemmArgs p;
+  return gemm_plan(p, gemm_ex_call(A, W, bias, residual, C, M, N, K, in_dtype, out_dtype, lda, rows_per_batch, a_batch_stride, ldw, ldc, ldr,
+                                   act, batch, strideA, strideW, strideC, strideBias, strideR, z_out, p_drop, rng_state, site));
 }
 
 // C = act(LN_A(A) . W^T + bias) + LN_R(residual), with the LayerNorms folded into this GEMM's epilogue and (optionally)
 // the row statistics of C written for the next consumer: see GemmArgs and include/msmd_hip.h.  Plain row-major operands,
 // no batch, 16-bit operands and output.  The statistics' slab width names the kernel that writes them: 64 = the
 // 128 x 128 tile, 32 = the 64 x 64 tile (grids that would not fill the chip with 128 x 128 tiles).
-static int gemm_ln_plan(GemmArgs& p, const void* A, const void* W, const float* bias, const void* residual, void* C, int M, int N,
-                        int K, int in_dtype, int out_dtype, long lda, long ldw, long ldc, long ldr, int act, const float* a_stats,
-                        const float* w_colsum, const float* r_stats, const float* r_gamma, const float* r_beta, float* stats_out,
-                        int slab_in, int slab_out, float eps) {
-  if (M <= 0 || N <= 0 || K <= 0 || !A || !W || !C || (K % 64) || (N % 64)) return -1;
-  if ((in_dtype != MSMD_BF16 && in_dtype != MSMD_F16) || out_dtype != in_dtype) return -1;   // 16-bit rows in and out
-  if ((lda % 8) || (ldw % 8) || (ldc % 4) || (residual && (ldr % 4))) return -1;
-  if (((uintptr_t)A & 15) || ((uintptr_t)W & 15) || ((uintptr_t)C & 15) || ((uintptr_t)residual & 7) || ((uintptr_t)bias & 15)) return -1;
-  if ((a_stats != nullptr) != (w_colsum != nullptr)) return -1;
-  if (!bias || (a_stats && (residual || stats_out)) || (!a_stats && !residual)) return -1;   // the two epilogue modes
-  if (r_stats && (!residual || !r_gamma || !r_beta || a_stats)) return -1;   // one side per call
-  if (((uintptr_t)w_colsum & 15) || ((uintptr_t)r_gamma & 15) || ((uintptr_t)r_beta & 15) || ((uintptr_t)a_stats & 7) ||
-      ((uintptr_t)r_stats & 7) || ((uintptr_t)stats_out & 7))
-    return -1;
-  if ((a_stats || r_stats) && slab_in != 32 && slab_in != 64) return -1;
-  if (stats_out && slab_out != 32 && slab_out != 64) return -1;
-  if ((a_stats && (K % slab_in)) || (r_stats && (N % slab_in))) return -1;
+static int gemm_ln_plan(GemmArgs& p, const GemmCall& c) {
+  const int M = c.M, N = c.N, K = c.K;
+  if (M <= 0 || N <= 0 || K <= 0 || !c.A || !c.W || !c.C || (K % 64) || (N % 64)) return -1;
+  if ((c.in_dtype != MSMD_BF16 && c.in_dtype != MSMD_F16) || c.out_dtype != c.in_dtype) return -1;   // 16-bit rows in and out
+  if ((c.lda % 8) || (c.ldw % 8) || (c.ldc % 4) || (c.residual && (c.ldr % 4))) return -1;
+  if (((uintptr_t)c.A & 15) || ((uintptr_t)c.W & 15) || ((uintptr_t)c.C & 15) || ((uintptr_t)c.residual & 7) || ((uintptr_t)c.bias & 15)) return -1;
+  if ((c.a_stats != nullptr) != (c.w_colsum != nullptr)) return -1;
+  if (!c.bias || (c.a_stats && (c.residual || c.stats_out)) || (!c.a_stats && !c.residual)) return -1;   // the two epilogue modes
+  if (c.r_stats && (!c.residual || !c.r_gamma || !c.r_beta || c.a_stats)) return -1;   // one side per call
+  if (((uintptr_t)c.w_colsum & 15) || ((uintptr_t)c.r_gamma & 15) || ((uintptr_t)c.r_beta & 15)) return -1;
+  if (((uintptr_t)c.a_stats & 7) || ((uintptr_t)c.r_stats & 7) || ((uintptr_t)c.stats_out & 7)) return -1;
+  if ((c.a_stats || c.r_stats) && c.slab_in != 32 && c.slab_in != 64) return -1;
+  if (c.stats_out && c.slab_out != 32 && c.slab_out != 64) return -1;
+  if ((c.a_stats && (K % c.slab_in)) || (c.r_stats && (N % c.slab_in))) return -1;
   // the tile family (gemm16_route's `cols`): the statistics' slab where the call writes them, else by the grid
   const long tiles128 = (long)((M + 127) / 128) * ((N + 127) / 128);
-  const int cols = (stats_out ? slab_out == 64 : (tiles128 >= 192 && (N % 128) == 0)) ? 128 : 64;
+  const int cols = (c.stats_out ? c.slab_out == 64 : (tiles128 >= 192 && (N % 128) == 0)) ? 128 : 64;
   if (cols == 128 && (N % 128)) return -1;
-  // flags: paired 16-byte stores where the rows allow them; MSMD_GEMM_ONE_TILE_PER_WORKGROUP
-  p = gemm_args(A, W, bias, residual, C, M, N, K, lda, M, 0, ldw, ldc, ldr, act & 0xff, 2 | (((act >> 19) & 1) << 4), 0, 0, 0, 0, 0,
-                1, 0, 0, 0, 2);
-  p.a_stats = a_stats; p.a_nt = a_stats ? K / slab_in : 0; p.w_colsum = w_colsum;
-  p.r_stats = r_stats; p.r_nt = r_stats ? N / slab_in : 0; p.r_gamma = r_gamma; p.r_beta = r_beta;
-  p.stats_out = stats_out; p.ln_eps = eps;
+  // of the word's flags this entry honours MSMD_GEMM_ONE_TILE_PER_WORKGROUP and MSMD_GEMM_NO_256_TILE; paired 16-byte stores
+  // always, where the rows allow them
+  const GemmActWord u = gemm_unpack_act(c.act);
+  p = gemm_args(c, u.act, GF_PAIRED_STORES | (u.flags & GF_ONE_TILE), 2);
+  p.a_stats = c.a_stats; p.a_nt = c.a_stats ? K / c.slab_in : 0; p.w_colsum = c.w_colsum;
+  p.r_stats = c.r_stats; p.r_nt = c.r_stats ? N / c.slab_in : 0; p.r_gamma = c.r_gamma; p.r_beta = c.r_beta;
+  p.stats_out = c.stats_out; p.ln_eps = c.eps;
   // the caller's tile hint chooses within the 128-column family (15 = 192 x 128, 17 = 128 x 128, 66 = A/B form of 17) or names
   // the 256 x 256 kernel (80), which writes the same 64-column statistics slabs and reads either width
-  const int variant = gemm16_route(p, 1, 2, in_dtype == MSMD_BF16, (act >> 8) & 0xff, ((act >> 20) & 1) << 5, cols);
-  return variant ? variant : -1;      // no LayerNorm epilogue in gemm_kernel
+  const int variant = gemm16_route(p, 1, 2, c.in_dtype == MSMD_BF16, u.hint, u.flags & GF_NO_256, cols);
+  return variant != GV_GENERIC ? variant : -1;      // no LayerNorm epilogue in gemm_kernel
 }
 
-extern "C" int msmd_gemm_ln(const void* A, const void* W, const float* bias, const void* residual, void* C, int M, int N,
-                            int K, int in_dtype, int out_dtype, long lda, long ldw, long ldc, long ldr, int act,
-                            const float* a_stats, const float* w_colsum, const float* r_stats, const float* r_gamma,
-                            const float* r_beta, float* stats_out, int slab_in, int slab_out, float eps,
-                            msmd_stream_t stream) {
-  GemmArgs p;
-  const int variant = gemm_ln_plan(p, A, W, bias, residual, C, M, N, K, in_dtype, out_dtype, lda, ldw, ldc, ldr, act, a_stats,
-                                   w_colsum, r_stats, r_gamma, r_beta, stats_out, slab_in, slab_out, eps);
-  return variant < 0 ? 1 : gemm_launch(p, in_dtype, out_dtype, 1, variant, (hipStream_t)stream);
+static GemmCall gemm_ln_call(const void* A, const void* W, const float* bias, const void* residual, void* C, int M, int N, int K, int in_dtype,
+                             int out_dtype, long lda, long ldw, long ldc, long ldr, int act, const float* a_stats, const float* w_colsum,
+                             const float* r_stats, const float* r_gamma, const float* r_beta, float* stats_out, int slab_in, int slab_out, float eps) {
+  GemmCall c;
+  c.A = A; c.W = W; c.bias = bias; c.residual = residual; c.C = C;
+  c.M = M; c.N = N; c.K = K; c.in_dtype = in_dtype; c.out_dtype = out_dtype;
+  c.lda = lda; c.ldw = ldw; c.ldc = ldc; c.ldr = ldr; c.act = act;
+  c.a_stats = a_stats; c.w_colsum = w_colsum; c.r_stats = r_stats; c.r_gamma = r_gamma; c.r_beta = r_beta;
+  c.stats_out = stats_out; c.slab_in = slab_in; c.slab_out = slab_out; c.eps = eps;
+  return c;
+}
+
+extern "C" int msmd_gemm_ln(const void* A, const void* W, const float* bias, const void* residual, void* C, int M, int N, int K, int in_dtype,
+                            int out_dtype, long lda, long ldw, long ldc, long ldr, int act, const float* a_stats, const float* w_colsum,
+                            const float* r_stats, const float* r_gamma, const float* r_beta, float* stats_out, int slab_in, int slab_out,
+                            float eps, msmd_stream_t stream) {
+  return gemm_run(gemm_ln_plan, gemm_ln_call(A, W, bias, residual, C, M, N, K, in_dtype, out_dtype, lda, ldw, ldc, ldr, act, a_stats,
+                                             w_colsum, r_stats, r_gamma, r_beta, stats_out, slab_in, slab_out, eps), stream);
 }
 
 // What msmd_gemm_ln would launch for the same arguments: the variant, or -1 for a call it rejects.  Launches nothing.
-extern "C" int msmd_gemm_ln_route(const void* A, const void* W, const float* bias, const void* residual, void* C, int M, int N,
-                                  int K, int in_dtype, int out_dtype, long lda, long ldw, long ldc, long ldr, int act,
-                                  const float* a_stats, const float* w_colsum, const float* r_stats, const float* r_gamma,
-                                  const float* r_beta, float* stats_out, int slab_in, int slab_out, float eps, msmd_stream_t) {
+extern "C" int msmd_gemm_ln_route(const void* A, const void* W, const float* bias, const void* residual, void* C, int M, int N, int K,
+                                  int in_dtype, int out_dtype, long lda, long ldw, long ldc, long ldr, int act, const float* a_stats,
+                                  const float* w_colsum, const float* r_stats, const float* r_gamma, const float* r_beta, float* stats_out,
+                                  int slab_in, int slab_out, float eps, msmd_stream_t) {
   GemmArgs p;
-  return gemm_ln_plan(p, A, W, bias, residual, C, M, N, K, in_dtype, out_dtype, lda, ldw, ldc, ldr, act, a_stats, w_colsum,
-                      r_stats, r_gamma, r_beta, stats_out, slab_in, slab_out, eps);
-}
-
-extern "C" int msmd_gemm_ex(const void* A, const void* W, const float* bias, const void* residual, void* C, int M,
-                            int N, int K, int in_dtype, int out_dtype, long lda, int rows_per_batch,
-                            long a_batch_stride, long ldw, long ldc, long ldr, int act, int batch, long strideA,
-                            long strideW, long strideC, long strideBias, long strideR, void* z_out, float p_drop,
-                            const unsigned long* rng_state, unsigned int site, msmd_stream_t stream) {
-  return gemm_impl(A, W, bias, residual, C, M, N, K, in_dtype, out_dtype, lda, rows_per_batch, a_batch_stride, ldw, ldc,
-                   ldr, act, batch, strideA, strideW, strideC, strideBias, strideR, 1, 0, 0, 0, stream, z_out, p_drop,
-                   rng_state, site);
-}
-
-// What msmd_gemm_ex (and msmd_gemm: z_out = NULL, p_drop = 0) would launch for the same arguments: the variant, 0 for
-// gemm_kernel, -1 for a call it rejects.  Launches nothing.
-extern "C" int msmd_gemm_route(const void* A, const void* W, const float* bias, const void* residual, void* C, int M,
-                               int N, int K, int in_dtype, int out_dtype, long lda, int rows_per_batch,
-                               long a_batch_stride, long ldw, long ldc, long ldr, int act, int batch, long strideA,
-                               long strideW, long strideC, long strideBias, long strideR, void* z_out, float p_drop,
-                               const unsigned long* rng_state, unsigned int site, msmd_stream_t) {
-  GemmArgs p;
-  return gemm_plan(p, A, W, bias, residual, C, M, N, K, in_dtype, out_dtype, lda, rows_per_batch, a_batch_stride, ldw, ldc, ldr,
-                   act, batch, strideA, strideW, strideC, strideBias, strideR, 1, 0, 0, 0, z_out, p_drop, rng_state, site, 0);
+  return gemm_ln_plan(p, gemm_ln_call(A, W, bias, residual, C, M, N, K, in_dtype, out_dtype, lda, ldw, ldc, ldr, act, a_stats,
+                                      w_colsum, r_stats, r_gamma, r_beta, stats_out, slab_in, slab_out, eps));
 }
 
 // dZ = keep_mask / (1 - p) * act'(Z) * (A . W^T): the data gradient of a Linear whose INPUT was dropout(act(Z)) -- the product
 // and the backward of the activation + dropout in one launch (A = the upstream gradient, W = the transposed weight cast,
 // Z = the forward's pre-activation, C and Z contiguous (M, N)).  Replaces msmd_gemm + msmd_act_bwd_dropout / msmd_act_bwd.
-extern "C" int msmd_gemm_actbwd(const void* A, const void* W, const void* Z, void* C, int M, int N, int K, int in_dtype,
-                                int out_dtype, long lda, long ldw, int act, float p_drop, const unsigned long* rng_state,
-                                unsigned int site, msmd_stream_t stream) {
+extern "C" int msmd_gemm_actbwd(const void* A, const void* W, const void* Z, void* C, int M, int N, int K, int in_dtype, int out_dtype, long lda,
+                                long ldw, int act, float p_drop, const unsigned long* rng_state, unsigned int site, msmd_stream_t stream) {
   if (!Z || in_dtype != out_dtype || (in_dtype != MSMD_BF16 && in_dtype != MSMD_F16) || (N & 3) || ((uintptr_t)Z & 7)) return 1;
   if (K % 64) return 1;      // the LDS-DMA kernels only (the others do not carry this epilogue)
-  return gemm_impl(A, W, nullptr, nullptr, C, M, N, K, in_dtype, out_dtype, lda, 0, 0, ldw, N, 0, act & 0x3ffff, 1, 0, 0, 0, 0,
-                   0, 1, 0, 0, 0, stream, const_cast<void*>(Z), p_drop, rng_state, site, 8);
+  GemmCall c;
+  c.A = A; c.W = W; c.C = C; c.M = M; c.N = N; c.K = K; c.in_dtype = in_dtype; c.out_dtype = out_dtype;
+  c.lda = lda; c.ldw = ldw; c.ldc = N; c.act = act & (0xffff | MSMD_GEMM_WRITE_THROUGH | MSMD_GEMM_PAIRED_STORES);
+  c.z_out = const_cast<void*>(Z); c.p_drop = p_drop; c.rng = rng_state; c.site = site; c.internal_flags = GF_ACT_BWD;
+  return gemm_run(gemm_plan, c, stream);
 }
 
-extern "C" int msmd_gemm_batched2(const void* A, const void* W, void* C, int M, int N, int K, int in_dtype,
-                                  int out_dtype, long lda, long ldw, long ldc, int batch_outer, long strideA_o,
-                                  long strideW_o, long strideC_o, int batch_inner, long strideA_i, long strideW_i,
-                                  long strideC_i, msmd_stream_t stream) {
-  return gemm_impl(A, W, nullptr, nullptr, C, M, N, K, in_dtype, out_dtype, lda, 0, 0, ldw, ldc, 0, MSMD_ACT_NONE,
-                   batch_outer, strideA_o, strideW_o, strideC_o, 0, 0, batch_inner, strideA_i, strideW_i, strideC_i,
-                   stream);
+extern "C" int msmd_gemm_batched2(const void* A, const void* W, void* C, int M, int N, int K, int in_dtype, int out_dtype, long lda, long ldw,
+                                  long ldc, int batch_outer, long strideA_o, long strideW_o, long strideC_o, int batch_inner, long strideA_i,
+                                  long strideW_i, long strideC_i, msmd_stream_t stream) {
+  GemmCall c;
+  c.A = A; c.W = W; c.C = C; c.M = M; c.N = N; c.K = K; c.in_dtype = in_dtype; c.out_dtype = out_dtype;
+  c.lda = lda; c.ldw = ldw; c.ldc = ldc; c.act = MSMD_ACT_NONE;
+  c.batch = batch_outer; c.strideA = strideA_o; c.strideW = strideW_o; c.strideC = strideC_o;
+  c.batch_inner = batch_inner; c.strideA2 = strideA_i; c.strideW2 = strideW_i; c.strideC2 = strideC_i;
+  return gemm_run(gemm_plan, c, stream);
 }

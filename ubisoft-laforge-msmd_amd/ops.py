@@ -239,6 +239,26 @@ class gemm_defaults:
         return False
 
 
+def _trace_begin(M, N, K, batch, dt):
+    """Opens the GEMM_FLOPS / GEMM_TRACE bracket of one launch (gemm, gemm_ln, gemm_act_bwd): counts its FLOPs and, with a trace
+    installed, records the first event.  Returns what _trace_end needs, None without a trace."""
+    if GEMM_FLOPS is not None:
+        GEMM_FLOPS[0] += 2.0 * M * N * K * batch
+    if GEMM_TRACE is None:
+        return None
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    return (M, N, K, batch, dt, e0, e1)
+
+
+def _trace_end(t, route=None, args=None):
+    """Closes the bracket: (M, N, K, batch, dtype, e0, e1, on_256).  Last field: did the library run this launch on its
+    256 x 256-tile kernel, asked of the entry's *_route twin with the same arguments."""
+    if t is not None:
+        t[-1].record()
+        GEMM_TRACE.append((*t, route is not None and route(*args) == 80))
+
+
 def _autotune_gemm(lib, args, key, out, residual):
     if torch.cuda.is_current_stream_capturing() or (residual is not None and residual.data_ptr() == out.data_ptr()):
         return 0
@@ -299,11 +319,7 @@ def gemm(a, w, bias=None, residual=None, act=ACT_NONE, out=None, out_dtype=None,
     ldr = residual.stride(-2) if residual is not None and residual.dim() >= 2 else N
     if bias is not None and bias.dtype != torch.float32:
         raise TypeError("bias must be fp32")
-    if GEMM_FLOPS is not None:
-        GEMM_FLOPS[0] += 2.0 * M * N * K * batch
-    if GEMM_TRACE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    trace = _trace_begin(M, N, K, batch, _dt(a))
     if variant is None:
         variant = _GEMM_DEFAULT["split_variant"] if isinstance(a, Split) else _GEMM_DEFAULT["variant"]
         if GEMM_ROUTER is not None and not isinstance(a, Split):
@@ -322,16 +338,13 @@ def gemm(a, w, bias=None, residual=None, act=ACT_NONE, out=None, out_dtype=None,
             v = _autotune_gemm(lib, args, key, out, residual)
         args[16] = act | (v << 8)
     train = z_out is not None or p_drop > 0.0
-    if train or GEMM_TRACE is not None:
+    if train or trace is not None:
         ex = (*args[:-1], _p(z_out), float(p_drop), _p(rng_state), int(site), args[-1])
     if train:
         _lib.check(lib.msmd_gemm_ex(*ex), "msmd_gemm_ex")
     else:
         _lib.check(lib.msmd_gemm(*args), "msmd_gemm")
-    if GEMM_TRACE is not None:
-        e1.record()
-        # last field: did the library run this launch on its 256 x 256-tile kernel
-        GEMM_TRACE.append((M, N, K, batch, _dt(a), e0, e1, lib.msmd_gemm_route(*ex) == 80))
+    _trace_end(trace, lib.msmd_gemm_route, ex if trace is not None else None)
     return out
 
 
@@ -369,20 +382,14 @@ def gemm_ln(a, w, bias=None, residual=None, act=ACT_NONE, out=None, out_dtype=No
     for t in (bias, w_colsum, r_gamma, r_beta, a_stats, r_stats):
         if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
             raise TypeError("gemm_ln: bias / colsum / gamma / beta / stats must be contiguous fp32")
-    if GEMM_FLOPS is not None:
-        GEMM_FLOPS[0] += 2.0 * M * N * K
     ldr = residual.stride(-2) if residual is not None and residual.dim() >= 2 else N
-    if GEMM_TRACE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    trace = _trace_begin(M, N, K, 1, _dt(a))
     hint = 66 if GEMM_LN_ALL_IN_ONE else ((GEMM_LN_ROUTER(M, N, K) or 0) if GEMM_LN_ROUTER is not None else (GEMM_LN_TILE or 0))
     args = (_p(a), _p(w), _p(bias), _p(residual), _p(out), M, N, K, _dt(a), _dt(out), a.stride(-2) if a.dim() >= 2 else K,
             w.stride(0), N, ldr, act | GEMM_LN_FLAGS | (hint << 8), _p(a_stats), _p(w_colsum), _p(r_stats), _p(r_gamma),
             _p(r_beta), _p(st), slab_in, slab_out, float(eps), _stream())
     _lib.check(lib.msmd_gemm_ln(*args), "msmd_gemm_ln")
-    if GEMM_TRACE is not None:
-        e1.record()
-        GEMM_TRACE.append((M, N, K, 1, _dt(a), e0, e1, lib.msmd_gemm_ln_route(*args) == 80))
+    _trace_end(trace, lib.msmd_gemm_ln_route, args)
     return (out, st) if st is not None else out
 
 
@@ -406,17 +413,11 @@ def gemm_act_bwd(dy, wt, z, act, p_drop=0.0, rng_state=None, site=0):
     if z.numel() != M * N or not z.is_contiguous() or not dy.is_contiguous():
         raise ValueError("gemm_act_bwd: z must be the contiguous (M, N) pre-activation")
     out = torch.empty_like(z)
-    if GEMM_FLOPS is not None:
-        GEMM_FLOPS[0] += 2.0 * M * N * K
-    if GEMM_TRACE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    trace = _trace_begin(M, N, K, 1, _dt(dy))
     _lib.check(_lib.load().msmd_gemm_actbwd(_p(dy), _p(wt), _p(z), _p(out), M, N, K, _dt(dy), _dt(out), K, wt.stride(0),
                                             act | (_GEMM_DEFAULT["flags"] & GEMM_PAIRED_STORES), float(p_drop), _p(rng_state),
                                             int(site), _stream()), "msmd_gemm_actbwd")
-    if GEMM_TRACE is not None:
-        e1.record()
-        GEMM_TRACE.append((M, N, K, 1, _dt(dy), e0, e1, False))
+    _trace_end(trace)
     return out
 
 
