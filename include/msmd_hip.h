@@ -783,6 +783,36 @@ int msmd_render_shade_textured(const float* screen, const float* normals, const 
                                int H, int W, float near, msmd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * FLAMETex albedo model (reference utils/flame.py:247-301): a linear texture space over an (Hs, Ws, 3)
+ * image (the reference's is 512 x 512), evaluated for ONE code, nearest-resized to (Hd, Wd) and channel-reversed.
+ *   mean (Hs Ws 3) fp32, basis (Hs Ws 3, n_tex) fp32 row-major and contiguous, code (n_tex) fp32 (reference l.292: row 0 of
+ *   texcode; every copy is the same image, l.300).  1 <= Hs, Ws, Hd, Wd <= 4096, 1 <= n_tex <= 256, else hipErrorInvalidValue
+ *   without a launch.  Row offsets are 64-bit.
+ *   - source index of destination index d (F.interpolate's nearest rule, l.299): min((int)floorf(d * scale), S - 1) in fp32
+ *     with scale = (float)S / (float)D; at 512 -> 256 the even rows and columns;
+ *   - value of channel c at (y, x) (l.296-300): mean[r] + sum_k basis[r, k] code[k], r = (sy(y) Ws + sx(x)) 3 + (2 - c).  The
+ *     three rows of a pixel are one run of 3 n_tex floats; 16 lanes read it, lane l adds columns l, l + 16, ... in
+ *     ascending order by fma, the 16 sums are added by the xor butterfly 8, 4, 2, 1 and the mean is added last.  The order is a
+ *     function of n_tex alone: both formats and every copy hold the same fp32 value.
+ * msmd_flametex_forward: out_format MSMD_TEX_PLANAR_F32 -> out (n_copies, 3, Hd, Wd) fp32; MSMD_TEX_IMAGE_U8 -> out
+ *   (Hd, Wd, 3) uint8 RGB, byte c = floorf(fmaf(255.f, fminf(fmaxf(value_c, 0.f), 1.f), 0.5f)) (NaN gives 0), n_copies must be
+ *   1.  n_copies == 0 succeeds without a launch.  One launch, no allocation, no host synchronisation.
+ * msmd_flametex_backward_workspace: host only; the floats msmd_flametex_backward needs in `workspace` (-1 outside the limits).
+ * msmd_flametex_backward: grad_out (n_copies, 3, Hd, Wd) fp32 -> grad_code (n_tex) fp32,
+ *   grad_code[k] = sum_{c, y, x} basis[r(c, y, x), k] sum_copies grad_out[copy, c, y, x]  (the buffers get no gradient).
+ *   Two launches: a workgroup adds its run of consecutive pixels in pixel order (copies first, in copy order; the channels of
+ *   a column as (row 0 + row 1) + row 2) into its row of the workspace, then each column of the workspace is added in row
+ *   order, 64 consecutive segments first and the 64 segment sums after.  fp32 throughout, no floating-point atomics: the same
+ *   inputs give the same bits on every run. */
+#define MSMD_TEX_PLANAR_F32 0
+#define MSMD_TEX_IMAGE_U8 1
+int msmd_flametex_forward(const float* mean, const float* basis, const float* code, void* out, int out_format, int n_copies,
+                          int Hs, int Ws, int Hd, int Wd, int n_tex, msmd_stream_t stream);
+long msmd_flametex_backward_workspace(int Hd, int Wd, int n_tex);
+int msmd_flametex_backward(const float* basis, const float* grad_out, int n_copies, float* grad_code, float* workspace,
+                           int Hs, int Ws, int Hd, int Wd, int n_tex, msmd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Audio front end (the reference calls librosa.load(path, sr=16000), inference.py:232): interleaved PCM of any rate and
  * channel count -> 16 kHz mono fp32, z-normalised per clip.  One call of each entry point
  * (three launches) for a ragged group of clips that share the input rate and the sample type; every step is deterministic

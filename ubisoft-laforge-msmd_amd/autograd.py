@@ -742,3 +742,29 @@ def layer_norm(x, gamma, beta, post_add=None, sole_consumer=True):
 
 def attention(q, k, v, n_heads, scale, mask=None, p_drop=0.0):
     return AttentionFn.apply(q, k, v, n_heads, scale, mask, _pdrop(p_drop))
+
+
+class FlameTexFn(torch.autograd.Function):
+    """utils/flame.FLAMETex.forward on msmd_flametex_forward / msmd_flametex_backward.  texcode (bs, n_tex)
+    fp32: row 0 is the code and the only row with a gradient (reference utils/flame.py:292); the buffers get none."""
+
+    @staticmethod
+    def forward(ctx, texcode, mean, basis, src_hw, dst_hw):
+        ctx.save_for_backward(basis)
+        ctx.src_hw, ctx.bs = src_hw, texcode.shape[0]
+        return ops.flametex_forward(mean, basis, texcode[0].contiguous(), texcode.shape[0], src_hw, dst_hw)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        (basis,) = ctx.saved_tensors
+        grad = torch.zeros(ctx.bs, basis.shape[1], device=g.device, dtype=torch.float32)      # rows 1.. stay zero
+        ops.flametex_backward(basis, g.float().contiguous(), ctx.src_hw, out=grad[0])
+        return grad, None, None, None, None
+
+
+def flametex(texcode, mean, basis, src_hw=(512, 512), dst_hw=(256, 256)):
+    """texcode (bs, n_tex) on the device, any floating dtype (cast to fp32 by an autograd op, so the gradient returns in its
+    dtype) -> (bs, 3, Hd, Wd) fp32, differentiable once with respect to texcode."""
+    ops._need_cuda(texcode)
+    return FlameTexFn.apply(texcode.float(), mean, basis, src_hw, dst_hw)

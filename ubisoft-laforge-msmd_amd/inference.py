@@ -18,6 +18,8 @@ SURVEY.md section 8(f) n3, the callers either side of the sampler:
   * ``--video`` -- the frames, JPEG-compressed on the device chunk by chunk (csrc/jpeg.hip), and the input WAV as one
     Motion-JPEG AVI (utils/media.py), where the reference calls ffmpeg (utils/media.py:combine_frames_and_audio).
   * ``--texture`` -- an `.npz` with `tex_img`, `vt`, `ft`: the frames are drawn with that texture.
+  * ``--flame_tex`` -- an albedo `.npz` (BFM or FLAME texture space, plus `vt`, `ft`): the texture is evaluated by
+    utils/flame.FLAMETex from ``--tex_code`` (default: the mean face) and the frames are drawn with it.
 The rest of the reference script's media IO (compressed audio codecs, cv2, H.264) stays outside.
 """
 from __future__ import annotations
@@ -304,6 +306,12 @@ def build_parser():
     ap.add_argument("--texture", type=str, default=None, help=".npz with tex_img (Ht, Wt, 3 | 4) uint8, vt (Nt, 2) and ft (F, 3) "
                                                               "for FLAME's faces: the frames are drawn textured "
                                                               "(needs --render_size > 0)")
+    ap.add_argument("--flame_tex", type=str, default=None, help="albedo .npz (MU / PC for BFM, mean / tex_dir for FLAME) that also "
+                                                                "holds vt (Nt, 2) and ft (F, 3): the frames are drawn with the "
+                                                                "FLAMETex texture of --tex_code (needs --render_size > 0)")
+    ap.add_argument("--tex_type", type=str, default="BFM", choices=["BFM", "FLAME"], help="texture space of --flame_tex")
+    ap.add_argument("--tex_code", type=str, default=None, help=".npy texture code, (n_tex,) or (1, n_tex) (default: zeros, the "
+                                                               "mean face; needs --flame_tex)")
     # video (the reference pipes frames and audio through ffmpeg; here a Motion-JPEG AVI is written, utils/media.py)
     ap.add_argument("--video", action="store_true", help="write video_<clip>_seed_<s>.avi instead of the raw frames "
                                                          "(needs --render_size > 0)")
@@ -312,14 +320,20 @@ def build_parser():
 
 
 def parse_args(argv=None):
-    """build_parser().parse_args with the checks that span flags: --video and --texture need --render_size > 0, and the
-    quality lies in [1, 100]."""
+    """build_parser().parse_args with the checks that span flags: --video, --texture and --flame_tex need --render_size > 0,
+    --flame_tex and --texture exclude each other, --tex_code needs --flame_tex, and the quality lies in [1, 100]."""
     ap = build_parser()
     args = ap.parse_args(argv)
     if args.video and args.render_size <= 0:
         ap.error("--video needs --render_size > 0: there are no frames to encode")
     if args.texture is not None and args.render_size <= 0:
         ap.error("--texture needs --render_size > 0: there are no frames to draw it on")
+    if args.flame_tex is not None and args.render_size <= 0:
+        ap.error("--flame_tex needs --render_size > 0: there are no frames to draw it on")
+    if args.flame_tex is not None and args.texture is not None:
+        ap.error("--flame_tex and --texture both name the frames' texture: give one")
+    if args.tex_code is not None and args.flame_tex is None:
+        ap.error("--tex_code needs --flame_tex: there is no texture space to evaluate it in")
     if not 1 <= args.video_quality <= 100:
         ap.error(f"--video_quality {args.video_quality} is outside [1, 100]")
     return args
@@ -332,6 +346,28 @@ def load_texture(path):
         if missing:
             raise ValueError(f"{path} lacks {missing}: a texture file holds tex_img, vt and ft")
         return z["tex_img"], {"vt": z["vt"], "ft": z["ft"]}
+
+
+def load_flame_texture(path, tex_type="BFM", code_path=None, device="cuda"):
+    """--flame_tex's `.npz` -> (tex_img (256, 256, 3) uint8 on the device, {'vt', 'ft'}) as MeshRenderer takes them: the albedo
+    space is loaded into utils/flame.FLAMETex with every component the file holds and evaluated at the code of `code_path`
+    (`.npy`, (n_tex,) or (1, n_tex); None = zeros, the mean face)."""
+    from types import SimpleNamespace
+    from .utils.flame import FLAMETex
+    pc_key = {"BFM": "PC", "FLAME": "tex_dir"}.get(tex_type)
+    if pc_key is None:
+        raise NotImplementedError(f"texture type {tex_type!r} does not exist")
+    with np.load(path) as z:
+        missing = [k for k in ("vt", "ft") if k not in z.files]
+        if missing:
+            raise ValueError(f"{path} lacks {missing}: an albedo file for rendering also holds vt and ft")
+        asset = {k: z[k] for k in z.files}
+    n_tex = asset[pc_key].shape[-1]
+    tex = FLAMETex(SimpleNamespace(tex_type=tex_type, n_tex=n_tex, tex_asset=asset)).to(device)
+    code = np.zeros((1, n_tex), np.float32) if code_path is None else np.load(code_path).astype(np.float32)
+    if code.shape not in ((n_tex,), (1, n_tex)):
+        raise ValueError(f"{code_path} has shape {code.shape}: a texture code is ({n_tex},) or (1, {n_tex})")
+    return tex.image(torch.from_numpy(code.reshape(1, n_tex)).to(device)), {"vt": asset["vt"], "ft": asset["ft"]}
 
 
 def load_audio_16k(path, device="cuda"):
@@ -357,7 +393,8 @@ def main(argv=None):
     ((T, N, N, 3) uint8) is written beside them.  With --video as well, `video_<clip>_seed_<s>.avi` is written in its place: the
     frames are JPEG-compressed on the device chunk by chunk as they are rendered (so one chunk of raw pixels is alive at a
     time), at model_args.fps, with --audio_clip as the sound track when it is a `.wav` and silent otherwise.  --texture PATH
-    (an `.npz` with tex_img, vt, ft) draws the frames textured, in either form."""
+    (an `.npz` with tex_img, vt, ft) draws the frames textured, in either form; --flame_tex PATH (an albedo `.npz` with vt, ft)
+    does so with the FLAMETex texture of --tex_code."""
     import os
     args = parse_args(argv)
     device = torch.device("cuda")
@@ -384,6 +421,8 @@ def main(argv=None):
     written = []
     flame = renderer = None
     tex_img, tex_uv = load_texture(args.texture) if args.texture is not None else (None, None)
+    if args.flame_tex is not None:
+        tex_img, tex_uv = load_flame_texture(args.flame_tex, args.tex_type, args.tex_code, device)
     if args.render_size > 0:
         from .utils.flame import FLAME, FLAMEConfig
         from .utils.renderer import MeshRenderer

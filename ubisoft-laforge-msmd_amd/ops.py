@@ -1438,6 +1438,66 @@ def render_shade_textured(screen, normals, faces_i32, vt, ft, pyramid, tex_heigh
     return uvl
 
 
+# ----------------------------------------------------------------------------- FLAMETex albedo model (csrc/flametex.hip)
+TEX_PLANAR_F32, TEX_IMAGE_U8 = 0, 1     # MSMD_TEX_PLANAR_F32 / MSMD_TEX_IMAGE_U8
+FLAMETEX_MAX_SIDE, FLAMETEX_MAX_TEX = 4096, 256
+
+
+def _flametex_sizes(basis, src_hw, dst_hw):
+    (Hs, Ws), (Hd, Wd) = (int(v) for v in src_hw), (int(v) for v in dst_hw)
+    _render_arg("basis", basis, torch.float32)
+    if basis.dim() != 2:
+        raise TypeError(f"basis must have shape (Hs Ws 3, n_tex), got {tuple(basis.shape)}")
+    n_tex = basis.shape[1]
+    if not all(1 <= v <= FLAMETEX_MAX_SIDE for v in (Hs, Ws, Hd, Wd)) or not 1 <= n_tex <= FLAMETEX_MAX_TEX:
+        raise ValueError(f"flametex: sides {(Hs, Ws, Hd, Wd)} outside [1, {FLAMETEX_MAX_SIDE}] or n_tex = {n_tex} outside "
+                         f"[1, {FLAMETEX_MAX_TEX}]")
+    if basis.shape[0] != Hs * Ws * 3:
+        raise ValueError(f"basis has {basis.shape[0]} rows for a {Hs} x {Ws} x 3 image")
+    return Hs, Ws, Hd, Wd, n_tex
+
+
+def flametex_forward(mean, basis, code, n_copies=1, src_hw=(512, 512), dst_hw=(256, 256), out_format=TEX_PLANAR_F32):
+    """mean (Hs Ws 3) + basis (Hs Ws 3, n_tex) . code (n_tex), nearest-resized to dst_hw and channel-reversed, in one pass over
+    the rows the resize keeps: msmd_flametex_forward.  -> (n_copies, 3, Hd, Wd) fp32 (TEX_PLANAR_F32) or (Hd, Wd, 3) uint8 RGB
+    (TEX_IMAGE_U8, n_copies = 1).  All operands contiguous fp32 on the device."""
+    Hs, Ws, Hd, Wd, n_tex = _flametex_sizes(basis, src_hw, dst_hw)
+    _render_arg("mean", mean, torch.float32, (Hs * Ws * 3,))
+    _render_arg("code", code, torch.float32, (n_tex,))
+    n_copies = int(n_copies)
+    if out_format == TEX_IMAGE_U8:
+        if n_copies != 1:
+            raise ValueError("flametex_forward: the uint8 image has one copy")
+        out = torch.empty(Hd, Wd, 3, device=basis.device, dtype=torch.uint8)
+    elif out_format == TEX_PLANAR_F32:
+        if n_copies < 0:
+            raise ValueError(f"flametex_forward: n_copies = {n_copies}")
+        out = torch.empty(n_copies, 3, Hd, Wd, device=basis.device, dtype=torch.float32)
+    else:
+        raise ValueError(f"flametex_forward: out_format {out_format!r}")
+    _lib.check(_lib.load().msmd_flametex_forward(_p(mean), _p(basis), _p(code), _p(out), out_format, n_copies, Hs, Ws, Hd, Wd,
+                                                 n_tex, _stream()), "msmd_flametex_forward")
+    return out
+
+
+def flametex_backward(basis, grad_out, src_hw=(512, 512), out=None):
+    """grad_out (n_copies, 3, Hd, Wd) fp32 -> the gradient of flametex_forward's code, (n_tex,) fp32, summed over the copies:
+    msmd_flametex_backward (per-workgroup partial sums in a workspace, then one ordered reduction; the same bits every run).
+    out: a contiguous (n_tex,) fp32 tensor to write instead of a new one."""
+    _render_arg("grad_out", grad_out, torch.float32)
+    if grad_out.dim() != 4 or grad_out.shape[1] != 3:
+        raise TypeError(f"grad_out must have shape (n_copies, 3, Hd, Wd), got {tuple(grad_out.shape)}")
+    Hs, Ws, Hd, Wd, n_tex = _flametex_sizes(basis, src_hw, grad_out.shape[2:])
+    lib = _lib.load()
+    workspace = torch.empty(lib.msmd_flametex_backward_workspace(Hd, Wd, n_tex), device=basis.device, dtype=torch.float32)
+    if out is not None:
+        _render_arg("out", out, torch.float32, (n_tex,))
+    grad_code = out if out is not None else torch.empty(n_tex, device=basis.device, dtype=torch.float32)
+    _lib.check(lib.msmd_flametex_backward(_p(basis), _p(grad_out), grad_out.shape[0], _p(grad_code), _p(workspace), Hs, Ws, Hd,
+                                          Wd, n_tex, _stream()), "msmd_flametex_backward")
+    return grad_code
+
+
 # ----------------------------------------------------------------------------- JPEG encoder (csrc/jpeg.hip, DESIGN.md 5.13)
 JPEG_RESTART_INTERVAL = 32      # MSMD_JPEG_RESTART_INTERVAL
 JPEG_MAX_SIDE = 16384           # MSMD_JPEG_MAX_SIDE

@@ -1,4 +1,4 @@
-"""FLAME head model on the MI355X (drop-in surface of reference utils/flame.py:59-244)."""
+"""FLAME head model and FLAMETex albedo model on the MI355X (drop-in surface of reference utils/flame.py:59-301)."""
 from __future__ import annotations
 
 import pickle
@@ -8,6 +8,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from .. import autograd as _ag
 from .. import ops
 from . import lbs as _lbs
 
@@ -16,6 +17,7 @@ FLAMEConfig = SimpleNamespace(
     n_shape=100, n_exp=50, n_tex=50, tex_type="BFM",
     tex_path="/code/models/flame_data/FLAME2020/FLAME_albedo_from_BFM.npz",
     flame_lmk_embedding_path="/code/models/flame_data/landmark_embedding.npy",
+    flame_tex_path="/code/models/flame_data/FLAME2020/FLAME_texture.npz",     # read for tex_type = 'FLAME' (reference l.270)
 )
 
 
@@ -183,3 +185,61 @@ class FLAME(nn.Module):
         if return_lm3d:
             landmarks3d = ops.landmarks(vertices, p["faces"], p["full_idx"], self.full_lmk_bary_coords)
         return vertices, landmarks2d, landmarks3d
+
+
+class FLAMETex(nn.Module):
+    """The linear albedo model over the BFM / FLAME texture spaces: same constructor argument, buffers (`texture_mean`
+    (1, 1, R), `texture_basis` (1, R, n_tex), R = 512 * 512 * 3) and forward signature as the reference class (l.247-301).
+    The number of components is the asset's last dimension (the reference hard-codes 199 / 200), so truncated assets load, and
+    the basis is stored contiguous.  ``config`` may also carry ``tex_asset`` (a dict with the file's keys) in place of the file,
+    as ``asset`` does for FLAME."""
+
+    SRC_HW, DST_HW = (512, 512), (256, 256)
+
+    def __init__(self, config):
+        super().__init__()
+        if config.tex_type == "BFM":
+            mu_key, pc_key, path_attr, scale = "MU", "PC", "tex_path", None
+        elif config.tex_type == "FLAME":
+            mu_key, pc_key, path_attr, scale = "mean", "tex_dir", "flame_tex_path", 255.0
+        else:
+            raise NotImplementedError(f"texture type {config.tex_type!r} does not exist")
+        tex_space = getattr(config, "tex_asset", None)
+        if tex_space is None:
+            tex_space = np.load(getattr(config, path_attr))
+        pc = np.asarray(tex_space[pc_key])
+        n_pc, n_tex = pc.shape[-1], int(config.n_tex)
+        rows = self.SRC_HW[0] * self.SRC_HW[1] * 3
+        texture_mean = np.asarray(tex_space[mu_key]).reshape(1, -1)
+        texture_basis = pc.reshape(-1, n_pc)
+        if texture_basis.shape[0] != rows or texture_mean.shape[1] != rows:
+            raise ValueError(f"the texture space has {texture_basis.shape[0]} basis rows and {texture_mean.shape[1]} mean values, "
+                             f"not 512 x 512 x 3 = {rows}")
+        if not 1 <= n_tex <= n_pc:
+            raise ValueError(f"n_tex = {n_tex} is outside [1, {n_pc}], the asset's number of components")
+        texture_basis = texture_basis[:, :n_tex]
+        if scale is not None:                                       # reference l.272-273: both divided by 255
+            texture_mean, texture_basis = texture_mean / scale, texture_basis / scale
+        self.register_buffer("texture_mean", torch.from_numpy(np.ascontiguousarray(texture_mean)).float()[None, ...])
+        self.register_buffer("texture_basis", torch.from_numpy(np.ascontiguousarray(texture_basis)).float()[None, ...].contiguous())
+
+    def _operands(self, texcode):
+        n_tex = self.texture_basis.shape[2]
+        if texcode.dim() != 2 or texcode.shape[0] < 1 or texcode.shape[1] != n_tex:
+            raise ValueError(f"texcode must have shape (batchsize >= 1, {n_tex}), got {tuple(texcode.shape)}")
+        # the kernels read the module's own buffers, so load_state_dict and in-place edits take effect at the next call
+        return self.texture_mean.reshape(-1).contiguous(), self.texture_basis.reshape(-1, n_tex).contiguous()
+
+    def forward(self, texcode):
+        """texcode: [batchsize, n_tex] (fp32, or fp16 / bf16: cast) -> texture [bz, 3, 256, 256] fp32, range 0-1: the first
+        row's texture for every frame (reference l.285-301).  Differentiable once with respect to texcode; rows 1.. get zeros."""
+        mean, basis = self._operands(texcode)
+        return _ag.flametex(texcode, mean, basis, self.SRC_HW, self.DST_HW)
+
+    @torch.no_grad()
+    def image(self, texcode):
+        """The same texture as a (256, 256, 3) uint8 RGB image on the device, byte = floor(255 clamp(value, 0, 1) + 0.5): what
+        MeshRenderer.render_vertices(tex_img=...) takes."""
+        mean, basis = self._operands(texcode)
+        ops._need_cuda(texcode)
+        return ops.flametex_forward(mean, basis, texcode[0].float().contiguous(), 1, self.SRC_HW, self.DST_HW, ops.TEX_IMAGE_U8)
