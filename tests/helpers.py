@@ -1,5 +1,8 @@
 """Shared test helpers: synthetic state dicts and inputs (same recipes as tests/golden/make_goldens.py)."""
+import contextlib
+import ctypes
 import functools
+import gzip
 
 import numpy as np
 
@@ -86,3 +89,101 @@ def check_ingestion_against_reference(tmp_path, device):
         # same float64 arithmetic in a different association (interp1d's slope form): a few ulp of fp32 after the final cast
         assert float(np.abs(motion.cpu().numpy() - want).max()) <= 1e-6, (n, fps)
         assert float(shape.abs().sum()) == 0.0
+
+
+# ----------------------------------------------------------------------------- launch recording (the launch-sequence tests)
+# aten ops that launch nothing: allocation and metadata (views are skipped by `func.is_view`)
+_ATEN_SILENT = {"detach", "alias", "lift_fresh", "new_empty", "new_empty_strided"}
+
+
+class Recorder:
+    """Proxy of the loaded library: logs `name arg ...` per call made while a wrapped method runs; one list per
+    outermost invocation of a wrapped method.  aten=True also logs every aten op a TorchDispatchMode sees inside the
+    wrapped method (`aten <overload> <output shapes> <dtypes>`), with the backward kept on the calling thread."""
+
+    def __init__(self, lib, aten=False):
+        self.lib, self.depth, self.invocations, self.aten = lib, 0, [], aten
+
+    def __getattr__(self, name):
+        from msmd_amd import _lib
+        fn = getattr(self.lib, name)
+        types = _lib.PROTOS.get(name)
+        if types is None or not self.depth:
+            return fn
+
+        def call(*args):
+            assert len(args) == len(types), name
+            words = [name]
+            for t, a in zip(types, args):
+                if t is ctypes.c_void_p:
+                    words.append("-" if a is None or (isinstance(a, int) and a == 0) else "*")
+                elif t in (ctypes.c_float, ctypes.c_double):
+                    words.append(repr(float(a)))
+                else:
+                    words.append(str(int(a)))
+            self.invocations[-1].append(" ".join(words))
+            return fn(*args)
+        return call
+
+    def _aten_mode(self):
+        import torch
+        from torch.utils._python_dispatch import TorchDispatchMode
+        log = self.invocations[-1]
+
+        class Mode(TorchDispatchMode):
+            def __torch_dispatch__(self, func, types, args=(), kwargs=None):
+                out = func(*args, **(kwargs or {}))
+                name = func.overloadpacket.__name__
+                if not (func.is_view or name in _ATEN_SILENT or name.startswith("empty")):
+                    leaves = out if isinstance(out, (tuple, list)) else (out,)
+                    ts = [t for t in leaves if isinstance(t, torch.Tensor)]
+                    log.append(" ".join(["aten", str(func), ",".join("x".join(map(str, t.shape)) or "()" for t in ts) or "-",
+                                         ",".join(str(t.dtype)[6:] for t in ts) or "-"]))
+                return out
+        return Mode()
+
+    def wrap(self, method):
+        def wrapped(*a, **k):
+            if self.depth:
+                return method(*a, **k)
+            import torch
+            self.invocations.append([])
+            self.depth += 1
+            try:
+                if not self.aten:
+                    return method(*a, **k)
+                with torch.autograd.set_multithreading_enabled(False), self._aten_mode():
+                    return method(*a, **k)
+            finally:
+                self.depth -= 1
+        return wrapped
+
+
+@contextlib.contextmanager
+def recording(methods, aten=False):
+    """Stand a Recorder in for the loaded library while the (owner, attribute) methods in `methods` are wrapped."""
+    from msmd_amd import _lib
+    rec = Recorder(_lib.load(), aten)
+    saved_lib, saved = _lib._lib, [(o, a, getattr(o, a)) for o, a in methods]
+    _lib._lib = rec
+    for o, a, m in saved:
+        setattr(o, a, rec.wrap(m))
+    try:
+        yield rec
+    finally:
+        _lib._lib = saved_lib
+        for o, a, m in saved:
+            setattr(o, a, m)
+
+
+def load_fixture(path):
+    """{case name: [line, ...]} of a `[case]`-sectioned recording (plain text, or gzip of it: `*.gz`); `#` lines are comments."""
+    cases, cur = {}, None
+    with (gzip.open(path, "rt") if path.endswith(".gz") else open(path)) as f:
+        for line in f:
+            line = line.rstrip("\n")
+            if line.startswith("[") and line.endswith("]"):
+                cur = cases.setdefault(line[1:-1], [])
+            elif line and not line.startswith("#"):
+                cur.append(line)
+    return cases

@@ -17,8 +17,6 @@ The recorder stands in for the loaded library (msmd_amd._lib._lib) during one ca
 arguments and forwarded.  Pointer arguments -- the stream included -- are logged as set (`*`) or null (`-`), since addresses
 do not compare between runs; integers and floats as they are.  Only launches made while one of the two methods is on the
 stack count.  Shapes: 3 encoder + 3 decoder layers (a first, a middle and a last layer), 2 clips of 64 000 samples."""
-import contextlib
-import ctypes
 import os
 import sys
 
@@ -31,7 +29,7 @@ os.environ.setdefault("MSMD_SYNTHETIC_WEIGHTS", "1")
 from msmd_amd import _lib, ops, synth  # noqa: E402
 from msmd_amd.config import default_args  # noqa: E402
 
-from helpers import denoiser_inputs  # noqa: E402
+from helpers import denoiser_inputs, load_fixture, recording  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -42,58 +40,10 @@ def dev(x):
     return torch.from_numpy(np.ascontiguousarray(x)).to(DEV)
 
 
-class Recorder:
-    """Proxy of the loaded library: logs `name arg ...` per call made while a wrapped method runs; one list per
-    outermost invocation of a wrapped method."""
-
-    def __init__(self, lib):
-        self.lib, self.depth, self.invocations = lib, 0, []
-
-    def __getattr__(self, name):
-        fn = getattr(self.lib, name)
-        types = _lib.PROTOS.get(name)
-        if types is None or not self.depth:
-            return fn
-
-        def call(*args):
-            assert len(args) == len(types), name
-            words = [name]
-            for t, a in zip(types, args):
-                if t is ctypes.c_void_p:
-                    words.append("-" if a is None or (isinstance(a, int) and a == 0) else "*")
-                elif t in (ctypes.c_float, ctypes.c_double):
-                    words.append(repr(float(a)))
-                else:
-                    words.append(str(int(a)))
-            self.invocations[-1].append(" ".join(words))
-            return fn(*args)
-        return call
-
-    def wrap(self, method):
-        def wrapped(*a, **k):
-            if not self.depth:
-                self.invocations.append([])
-            self.depth += 1
-            try:
-                return method(*a, **k)
-            finally:
-                self.depth -= 1
-        return wrapped
-
-
-@contextlib.contextmanager
-def recording():
+def _recording():
     from msmd_amd.model import DenoisingNetwork_MSMD
     from msmd_amd.utils.wav2vec2 import Wav2Vec2Model
-    rec = Recorder(_lib.load())
-    saved = (_lib._lib, Wav2Vec2Model.encode_features, DenoisingNetwork_MSMD.trunk)
-    _lib._lib = rec
-    Wav2Vec2Model.encode_features = rec.wrap(saved[1])
-    DenoisingNetwork_MSMD.trunk = rec.wrap(saved[2])
-    try:
-        yield rec
-    finally:
-        _lib._lib, Wav2Vec2Model.encode_features, DenoisingNetwork_MSMD.trunk = saved
+    return recording([(Wav2Vec2Model, "encode_features"), (DenoisingNetwork_MSMD, "trunk")])
 
 
 _MODELS = {}
@@ -173,7 +123,7 @@ def record(name):
         setattr(net, k, v)
     old_fold, ops.FOLD_LN = ops.FOLD_LN, fold
     try:
-        with recording() as rec:
+        with _recording() as rec:
             run(model, args)
     finally:
         ops.FOLD_LN = old_fold
@@ -184,21 +134,9 @@ def record(name):
     return rec.invocations[0]
 
 
-def load_fixture():
-    cases, cur = {}, None
-    with open(FIXTURE) as f:
-        for line in f:
-            line = line.rstrip("\n")
-            if line.startswith("[") and line.endswith("]"):
-                cur = cases.setdefault(line[1:-1], [])
-            elif line and not line.startswith("#"):
-                cur.append(line)
-    return cases
-
-
 @pytest.mark.parametrize("name", list(CASES))
 def test_launch_sequence_is_the_recorded_one(name):
-    want = load_fixture()[name]
+    want = load_fixture(FIXTURE)[name]
     got = record(name)
     for i, (g, w) in enumerate(zip(got, want)):
         assert g == w, f"{name}: launch {i} differs\n  recorded: {w}\n  now:      {g}"

@@ -186,66 +186,54 @@ def _mask_u8(mask):
     return e[2]
 
 
+def _wgrad_sink(w, b_ref, want_b, alias):
+    """THE place a weight gradient's destination is chosen -> (wgrad view, bgrad view | None, owners to report as written), or
+    None: the gradient is returned to autograd as a fresh tensor.  A FusedAlias brings its regions of the gradient arena; in
+    direct-gradient mode a leaf parameter's sink is its .grad view of that arena (and its bias's, when that one has one)."""
+    if alias is not None:
+        return alias.wgrad, alias.bgrad, alias.owners
+    if not (DIRECT_GRAD and w.is_leaf and w.grad is not None and w.grad.is_contiguous()):
+        return None
+    if want_b and b_ref is not None and b_ref.grad is not None and b_ref.grad.is_contiguous():
+        return w.grad, b_ref.grad, (w, b_ref)
+    return w.grad, None, (w,)
+
+
 def _param_grads(dz2, xin, w, b_ref, has_b, K, need_w, need_b, alias):
-    """dW, db of y = x W^T + b from dz2 (M, N) and the saved input xin (..., Kp): returned, or -- direct-gradient mode /
-    FusedAlias operands -- added straight into the gradient arena (then None is returned for them)."""
+    """dW, db of y = x W^T + b from dz2 (M, N) and the saved input xin (..., Kp): returned, or added straight into their sink
+    (_wgrad_sink; then None is returned for them)."""
     dtype = xin.dtype
     N = w.shape[0]
     Kp = xin.shape[-1]
     M = xin.numel() // Kp
-    dw = db = None
     want_b = has_b and need_b
-    if alias is not None:
-        fa = alias
-        if dtype == torch.bfloat16 and USE_GEMM_TN and N % 8 == 0 and Kp == K:
-            ops.gemm_tn(dz2, xin.reshape(M, Kp), out=fa.wgrad.view(N, Kp), colsum_out=fa.bgrad, accumulate=True)
-        else:       # the forms the TN kernel does not take (fp32 operands, USE_GEMM_TN off): the generic products, then added
-            dwa, dba = _param_grads(dz2, xin, w, None, has_b, K, True, True, None)
-            fa.wgrad.add_(dwa.reshape(fa.wgrad.shape))
-            if has_b:
-                fa.bgrad.add_(dba.reshape(fa.bgrad.shape))
-        if GRAD_WRITTEN is not None:
-            for o in fa.owners:
-                GRAD_WRITTEN(o)
-        return None, None
-    direct = (DIRECT_GRAD and need_w and dtype == torch.bfloat16 and N % 8 == 0 and Kp == K
-              and w.is_leaf and w.grad is not None and w.grad.is_contiguous() and USE_GEMM_TN)
-    if direct:
-        # accumulate dW (and db) straight into the parameters' .grad views of the flat gradient arena: no fp32
-        # temporary, no autograd add kernel per parameter and window
-        bgrad = None
-        if want_b:
-            b_leaf = b_ref
-            if b_leaf is not None and b_leaf.grad is not None and b_leaf.grad.is_contiguous():
-                bgrad = b_leaf.grad
-        ops.gemm_tn(dz2, xin.reshape(M, Kp), out=w.grad.view(N, Kp), colsum_out=bgrad, accumulate=True)
-        if GRAD_WRITTEN is not None:
-            GRAD_WRITTEN(w)
-            if bgrad is not None:
-                GRAD_WRITTEN(b_ref)
-        if want_b and bgrad is None:
-            db = ops.colsum(dz2)
-    elif need_w and dtype == torch.bfloat16 and N % 8 == 0 and USE_GEMM_TN:
+    if alias is not None:       # an alias has no autograd path: both gradients go into its sink, whatever form computes them
+        need_w, want_b = True, has_b
+    if not need_w:
+        return None, (ops.colsum(dz2) if want_b else None)
+    dw = db = None
+    sink, written = _wgrad_sink(w, b_ref, want_b, alias), ()
+    if dtype == torch.bfloat16 and USE_GEMM_TN:
         # dW = dZ^T X straight from the row-major operands (transposing LDS reads), bias gradient fused
         x2 = xin.reshape(M, Kp)
-        if want_b:
-            dwe, db = ops.gemm_tn(dz2, x2, want_colsum=True)
+        if sink is not None and N % 8 == 0 and Kp == K:
+            # accumulated into the gradient arena: no fp32 temporary, no autograd add kernel per parameter and window
+            wgrad, bgrad, written = sink
+            ops.gemm_tn(dz2, x2, out=wgrad.view(N, Kp), colsum_out=bgrad, accumulate=True)
+            if want_b and bgrad is None:
+                db = ops.colsum(dz2)
         else:
-            dwe = ops.gemm_tn(dz2, x2)
-        dw = dwe[:, :K].reshape(w.shape)
-    elif need_w and dtype == torch.bfloat16 and USE_GEMM_TN and PAD_N_FOR_TN:
-        # N not a multiple of 8 (the 67 / 71-wide motion heads): zero-pad dZ's columns and take the same TN GEMM (3 launches
-        # instead of the 6 of the transposed-operand form below)
-        Np = (N + 7) // 8 * 8
-        dzp = ops.pad_cols(dz2.contiguous(), Np, dtype)
-        x2 = xin.reshape(M, Kp)
-        if want_b:
-            dwe, dbp = ops.gemm_tn(dzp, x2, want_colsum=True)
-            db = dbp[:N]
-        else:
-            dwe = ops.gemm_tn(dzp, x2)
-        dw = dwe[:N, :K].reshape(w.shape)
-    elif need_w:
+            # fresh tensors.  N not a multiple of 8 (the 67 / 71-wide motion heads): dZ's columns are zero-padded for the same
+            # GEMM (3 launches instead of the 6 of the transposed-operand form below)
+            Np = (N + 7) // 8 * 8
+            dzp = dz2 if Np == N else ops.pad_cols(dz2.contiguous(), Np, dtype)
+            if want_b:
+                dwe, db = ops.gemm_tn(dzp, x2, want_colsum=True)
+                db = db if Np == N else db[:N]
+            else:
+                dwe = ops.gemm_tn(dzp, x2)
+            dw = dwe[:N, :K].reshape(w.shape)
+    else:
         dzT = ops.transpose2d(dz2, 8)                      # (N, Mp)
         # x^T with 8 extra rows: row Kp is all ones, so column Kp of the product is the bias gradient
         # (dz^T . 1) for free inside the wgrad GEMM instead of a separate column-sum pass.
@@ -257,8 +245,15 @@ def _param_grads(dz2, xin, w, b_ref, has_b, K, need_w, need_b, alias):
         dw = dwe[:, :K].reshape(w.shape)
         if want_b:
             db = dwe[:, Kp].contiguous()
-    elif want_b:
-        db = ops.colsum(dz2)
+    if alias is not None and dw is not None:        # computed in a form that returns tensors: added into the alias's sink
+        wgrad, bgrad, written = sink
+        wgrad.add_(dw.reshape(wgrad.shape))
+        if has_b:
+            bgrad.add_(db.reshape(bgrad.shape))
+        dw = db = None
+    if GRAD_WRITTEN is not None:
+        for o in written:
+            GRAD_WRITTEN(o)
     return dw, db
 
 
@@ -439,7 +434,6 @@ def ffn(x, w1, b1, w2, b2, p_act, p_out, residual=None, act=ops.ACT_GELU):
 #             bumps its version) and the node falls back to its own msmd_dropout launch.
 FUSE_LN_DROPOUT_BWD = os.environ.get("MSMD_FUSE_LN_DROPOUT_BWD", "1") != "0"
 USE_JUNCTIONS = os.environ.get("MSMD_JUNCTIONS", "1") != "0"
-PAD_N_FOR_TN = os.environ.get("MSMD_PAD_N_FOR_TN", "1") != "0"
 
 
 def _tag_dropout(y, p, site):
@@ -638,53 +632,38 @@ def linear_dropout(x, w, b, p, residual=None, act=ACT_NONE, junction_out=None):
     return dropout(linear(x, w, b, act=act), p, residual)
 
 
-class FusedSelfAttnFn(torch.autograd.Function):
-    """Self-attention on a packed (B, T, 3 d) projection: fused forward (msmd_attention) and fused backward
-    (msmd_attention_bwd, P recomputed); the gradient comes back as ONE packed tensor (no slice / cat glue)."""
+def _qkv_views(x, kv, d):
+    """Q, K, V of d columns each out of a packed (B, T, 3 d) self-attention projection (kv None), or out of q (B, Tq, d) and a
+    packed (B, Tk, 2 d) cross-attention projection."""
+    if kv is None:
+        return x[..., :d], x[..., d:2 * d], x[..., 2 * d:]
+    return x, kv[..., :d], kv[..., d:]
+
+
+class FusedAttnFn(torch.autograd.Function):
+    """Self-attention on a packed (B, T, 3 d) projection x (kv None), or cross-attention of q = x (B, Tq, d) with a packed kv
+    (B, Tk, 2 d): fused forward (msmd_attention) and fused backward (msmd_attention_bwd, P recomputed); the gradients come
+    back packed as the inputs are (no slice / cat glue, no add)."""
 
     @staticmethod
-    def forward(ctx, qkv, n_heads, scale, mask, p_drop, site, prefetch=None):
-        d = qkv.shape[-1] // 3
-        qkv = qkv.contiguous()
+    def forward(ctx, x, kv, n_heads, scale, mask, p_drop, site, prefetch=None):
+        d = x.shape[-1] // 3 if kv is None else x.shape[-1]
+        x, kv = x.contiguous(), (kv.contiguous() if kv is not None else None)
         m8 = _mask_u8(mask)
-        o = ops.attention(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], n_heads, scale, m8, p_drop=p_drop,
-                          rng_state=TrainNoise.state, site=site, prefetch=prefetch)
-        ctx.save_for_backward(qkv, m8)
+        o = ops.attention(*_qkv_views(x, kv, d), n_heads, scale, m8, p_drop=p_drop, rng_state=TrainNoise.state, site=site,
+                          prefetch=prefetch)
+        ctx.save_for_backward(x, kv, m8)
         ctx.cfg = (n_heads, scale, d, p_drop, site)
         return o
 
     @staticmethod
     def backward(ctx, do):
-        qkv, m8 = ctx.saved_tensors
+        x, kv, m8 = ctx.saved_tensors
         H, scale, d, p_drop, site = ctx.cfg
-        dqkv = torch.empty_like(qkv)
-        ops.attention_bwd(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], do.contiguous(), dqkv[..., :d],
-                          dqkv[..., d:2 * d], dqkv[..., 2 * d:], H, scale, m8, p_drop, TrainNoise.state, site)
-        return dqkv, None, None, None, None, None, None
-
-
-class FusedCrossAttnFn(torch.autograd.Function):
-    """Cross-attention: q (B, Tq, d), packed kv (B, Tk, 2 d)."""
-
-    @staticmethod
-    def forward(ctx, q, kv, n_heads, scale, mask, p_drop, site):
-        d = q.shape[-1]
-        q, kv = q.contiguous(), kv.contiguous()
-        m8 = _mask_u8(mask)
-        o = ops.attention(q, kv[..., :d], kv[..., d:], n_heads, scale, m8, p_drop=p_drop, rng_state=TrainNoise.state,
-                          site=site)
-        ctx.save_for_backward(q, kv, m8)
-        ctx.cfg = (n_heads, scale, d, p_drop, site)
-        return o
-
-    @staticmethod
-    def backward(ctx, do):
-        q, kv, m8 = ctx.saved_tensors
-        H, scale, d, p_drop, site = ctx.cfg
-        dq, dkv = torch.empty_like(q), torch.empty_like(kv)
-        ops.attention_bwd(q, kv[..., :d], kv[..., d:], do.contiguous(), dq, dkv[..., :d], dkv[..., d:], H, scale, m8,
-                          p_drop, TrainNoise.state, site)
-        return dq, dkv, None, None, None, None, None
+        dx, dkv = torch.empty_like(x), (torch.empty_like(kv) if kv is not None else None)
+        ops.attention_bwd(*_qkv_views(x, kv, d), do.contiguous(), *_qkv_views(dx, dkv, d), H, scale, m8, p_drop,
+                          TrainNoise.state, site)
+        return dx, dkv, None, None, None, None, None, None
 
 
 FUSED_ATTENTION = True
@@ -711,7 +690,7 @@ def self_attention(qkv, n_heads, scale, mask=None, p_drop=0.0, prefetch=None):
     d = qkv.shape[-1] // 3
     p_drop = _pdrop(p_drop)
     if _fusable(qkv, qkv.shape[1]):
-        return FusedSelfAttnFn.apply(qkv, n_heads, scale, mask, p_drop, TrainNoise.next_site() if p_drop else 0, prefetch)
+        return FusedAttnFn.apply(qkv, None, n_heads, scale, mask, p_drop, TrainNoise.next_site() if p_drop else 0, prefetch)
     return attention(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], n_heads, scale, mask, p_drop)
 
 
@@ -719,7 +698,7 @@ def cross_attention(q, kv, n_heads, scale, mask=None, p_drop=0.0):
     d = q.shape[-1]
     p_drop = _pdrop(p_drop)
     if _fusable(q, kv.shape[1]):
-        return FusedCrossAttnFn.apply(q, kv, n_heads, scale, mask, p_drop, TrainNoise.next_site() if p_drop else 0)
+        return FusedAttnFn.apply(q, kv, n_heads, scale, mask, p_drop, TrainNoise.next_site() if p_drop else 0)
     return attention(q, kv[..., :d], kv[..., d:], n_heads, scale, mask, p_drop)
 
 

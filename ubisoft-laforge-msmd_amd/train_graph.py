@@ -16,6 +16,7 @@ feature extractor runs the no-grad inference kernels (reference model.py:97: `_f
 from __future__ import annotations
 
 import os
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -24,11 +25,9 @@ from . import autograd as ag
 from . import ops
 from .utils.model_common import pad_audio_plan
 from .utils.wav2vec2 import compute_mask_indices, compute_mask_indices_hf
-from .utils.wav2vec2 import CONV_KERNEL, CONV_STRIDE  # noqa: F401
 
 
 USE_CONV3_FN = os.environ.get("MSMD_CONV3_FN", "1") != "0"
-USE_LAYERDROP_FN = os.environ.get("MSMD_LAYERDROP_FN", "1") != "0"
 
 
 def _p(tree, name):
@@ -189,6 +188,106 @@ class NullTokenSelectFn(torch.autograd.Function):
         return None, d_token.reshape(ctx.token_shape).to(ctx.token_dtype), g * (1 - mf)
 
 
+# ----------------------------------------------------------------------------- the transformer layer, written once
+def _residual_block(x, attend, wo, bo, ln, p, pre_ln=False, junction=True):
+    """x + dropout_p(out_proj(attend(.))) around one LayerNorm: THE place where a training layer's dropout / residual /
+    LayerNorm order is written (the encoder's two layer forms, the decoder's self- and cross-attention steps, the style
+    encoder's layer).  attend(rows, J) maps the block's input -- the normed rows in a pre-LN block -- to what feeds the
+    out-projection and hands J to the projection that reads those rows.
+    post-LN: LayerNorm(x + ...); x feeds the projection AND is the residual: one gradient through the Junction, no add.
+             junction=False keeps autograd's add (the style encoder's layer).
+    pre-LN : x + ...(LayerNorm(x)); the LayerNorm is not the only consumer of x, and there is no junction."""
+    if pre_ln:
+        return ag.linear_dropout(attend(ag.layer_norm(x, *ln, sole_consumer=False), None), wo, bo, p, residual=x)
+    J = ag.Junction() if junction else None
+    return ag.layer_norm(ag.linear_dropout(attend(x, J), wo, bo, p, residual=x, junction_out=J), *ln)
+
+
+def _ffn_block(x, w1, b1, w2, b2, ln, p_act, p_out, pre_ln=False, fused=True):
+    """The feed-forward block around the same LayerNorm placement.  fused: ag.ffn, one autograd node where the shapes allow
+    it (its backward's middle is one launch); False: always the two linear_dropout nodes."""
+    h = ag.layer_norm(x, *ln, sole_consumer=False) if pre_ln else x
+    if fused:
+        y = ag.ffn(h, w1, b1, w2, b2, p_act, p_out, residual=x)
+    else:
+        y = ag.linear_dropout(ag.linear_dropout(h, w1, b1, p_act, act=ops.ACT_GELU), w2, b2, p_out, residual=x)
+    return y if pre_ln else ag.layer_norm(y, *ln)
+
+
+def _pair(g, stem):
+    return g(stem + "weight"), g(stem + "bias")
+
+
+class LayerParams(SimpleNamespace):
+    """What a layer body reads, built once per layer by the constructor of its naming family: qkv (and, in the decoder, q /
+    kv) are PROJECTIONS rows, junction -> rows -- whether their operand is a FusedAlias view of the arenas, a torch.cat of
+    three parameters or row slices of one is settled by the constructor; out / cross_out (w, b); ffn (w1, b1, w2, b2);
+    ln1 .. ln3 (gamma, beta); prefetch for the attention launch."""
+    prefetch = None
+
+
+def _hf_encoder_layer(enc, n):
+    """Hugging Face Wav2Vec2 / HuBERT encoder layer n."""
+    g, p = enc.get_parameter, f"encoder.layers.{n}."
+    fused = lambda k: ag.FUSED.get(("enc_qkv", id(enc), k)) if ag.DIRECT_GRAD else None
+    fa = fused(n)
+    if fa is not None:      # Q | K | V sit next to each other in the arenas: the fused operand is a view
+        qkv = lambda t, j=None: ag.linear_alias(t, fa, junction_in=j)
+    else:
+        wqkv, bqkv = (torch.cat([g(p + f"attention.{k}_proj.{kind}") for k in "qkv"], 0) for kind in ("weight", "bias"))
+        qkv = lambda t, j=None: ag.linear(t, wqkv, bqkv, junction_in=j)
+    out, ffn = _pair(g, p + "attention.out_proj."), _pair(g, p + "feed_forward.intermediate_dense.") + \
+        _pair(g, p + "feed_forward.output_dense.")
+    # the attention launch also pulls the layer's remaining weight casts (and the next layer's QKV) through the
+    # memory-side cache: the GEMMs behind it would otherwise read them from HBM inside their K loops (DESIGN 5c)
+    nfa = fused(n + 1)
+    pf = tuple(t for t in (ag.cast_of(out[0]), ag.cast_of(ffn[0]), ag.cast_of(ffn[2]),
+                           ag.cast_of(nfa.w) if nfa is not None else None) if t is not None) or None
+    return LayerParams(qkv=qkv, out=out, ln1=_pair(g, p + "layer_norm."), ffn=ffn, ln2=_pair(g, p + "final_layer_norm."),
+                       prefetch=pf)
+
+
+def _torch_encoder_layer(g, p):
+    """nn.TransformerEncoderLayer at prefix p (and the self-attention / FFN part of nn.TransformerDecoderLayer)."""
+    w, b = g(p + "self_attn.in_proj_weight"), g(p + "self_attn.in_proj_bias")
+    return LayerParams(qkv=lambda t, j=None: ag.linear(t, w, b, junction_in=j), out=_pair(g, p + "self_attn.out_proj."),
+                       ln1=_pair(g, p + "norm1."), ffn=_pair(g, p + "linear1.") + _pair(g, p + "linear2."),
+                       ln2=_pair(g, p + "norm2."))
+
+
+def _torch_decoder_layer(net, n):
+    """nn.TransformerDecoderLayer n of the denoiser: ln2 follows the cross-attention step, ln3 the FFN."""
+    g, p, d = net.get_parameter, f"transformer.layers.{n}.", net.feature_dim
+    L = _torch_encoder_layer(g, p)
+    fq = ag.FUSED.get(("dec_q", id(net), n)) if ag.DIRECT_GRAD else None
+    if fq is not None:      # rows of in_proj_weight as arena views: no slice nodes, gradients straight into the arena
+        fkv = ag.FUSED[("dec_kv", id(net), n)]
+        L.q, L.kv = (lambda t, j=None: ag.linear_alias(t, fq, junction_in=j)), (lambda t: ag.linear_alias(t, fkv))
+    else:                   # the row slices are autograd nodes: made where the projection runs, as part of it
+        w, b = g(p + "multihead_attn.in_proj_weight"), g(p + "multihead_attn.in_proj_bias")
+        L.q, L.kv = (lambda t, j=None: ag.linear(t, w[:d], b[:d], junction_in=j)), (lambda t: ag.linear(t, w[d:], b[d:]))
+    L.cross_out, L.ln3 = _pair(g, p + "multihead_attn.out_proj."), _pair(g, p + "norm3.")
+    return L
+
+
+def _layerdrop(p, groups, h):
+    """LayerDrop (HF Wav2Vec2Encoder) for one layer -> (skip the layer outright, per-row select flag or None), one coin per
+    block of rows.  Eager mode draws on the host (as HF's torch.rand([])) and skips for real when every block skips;
+    graph-safe mode always computes the layer and selects on a device-side draw."""
+    noise = ag.TrainNoise
+    if not (noise.active and p > 0):
+        return False, None
+    if noise.graph_safe:
+        coins = torch.rand((groups, 1, 1) if groups > 1 else (), device=h.device) < p
+    else:
+        rng = noise.host_rng if noise.host_rng is not None else np.random
+        drawn = [rng.rand() < p for _ in range(groups)]
+        if all(drawn) or not any(drawn):
+            return all(drawn), None
+        coins = torch.tensor(drawn, device=h.device).view(groups, 1, 1)   # some blocks skip: compute the layer, select
+    return False, coins.repeat_interleave(h.shape[0] // groups, 0) if groups > 1 else coins
+
+
 def audio_encoder_train(enc, audio, output_fps, frame_num, dtype, groups=1):
     """Differentiable counterpart of Wav2Vec2Model.encode (utils/wav2vec2.py): (B, L) audio -> (B, frame_num, 768).
     groups > 1: the batch is `groups` equal blocks of rows that the reference would have encoded in separate calls (the two
@@ -226,61 +325,17 @@ def audio_encoder_train(enc, audio, output_fps, frame_num, dtype, groups=1):
     h = ag.dropout(h, c.hidden_dropout)
     d, H = c.hidden_size, c.num_attention_heads
     for n in range(c.num_hidden_layers):
-        # LayerDrop (HF Wav2Vec2Encoder): skip the layer with probability layerdrop.  Eager mode skips for real (host
-        # draw, as HF's torch.rand([])); graph-safe mode computes the layer and selects on a device-side draw.
-        skip_flag = None
-        if noise.active and c.layerdrop > 0:
-            if noise.graph_safe:
-                skip_flag = torch.rand((), device=h.device) < c.layerdrop if groups == 1 else \
-                    (torch.rand((groups, 1, 1), device=h.device) < c.layerdrop).repeat_interleave(h.shape[0] // groups, 0)
-            else:
-                rng = noise.host_rng if noise.host_rng is not None else np.random
-                coins = [rng.rand() < c.layerdrop for _ in range(groups)]
-                if all(coins):
-                    continue
-                if any(coins):      # some blocks skip this layer: compute it and select per block
-                    skip_flag = torch.tensor(coins, device=h.device).view(groups, 1, 1).repeat_interleave(h.shape[0] // groups, 0)
+        skip, skip_flag = _layerdrop(c.layerdrop, groups, h)
+        if skip:
+            continue
+        L = _hf_encoder_layer(enc, n)
+        attend = lambda t, J: ag.self_attention(L.qkv(t, J), H, (d // H) ** -0.5, p_drop=c.attention_dropout,
+                                                prefetch=L.prefetch)
         h_in = h
-        p = f"encoder.layers.{n}."
-        wq, wk, wv = (g(p + f"attention.{k}_proj.weight") for k in "qkv")
-        bq, bk, bv = (g(p + f"attention.{k}_proj.bias") for k in "qkv")
-        ln1 = (g(p + "layer_norm.weight"), g(p + "layer_norm.bias"))
-        ln2 = (g(p + "final_layer_norm.weight"), g(p + "final_layer_norm.bias"))
-        fa = ag.FUSED.get(("enc_qkv", id(enc), n)) if ag.DIRECT_GRAD else None
-        J = ag.Junction()       # h feeds the QKV projection and is the out-projection's residual (post-LN branch)
-        if fa is not None:      # Q | K | V sit next to each other in the arenas: the fused operand is a view
-            qkv_proj = lambda t, j=None: ag.linear_alias(t, fa, junction_in=j)
-        else:
-            wqkv, bqkv = torch.cat([wq, wk, wv], 0), torch.cat([bq, bk, bv], 0)
-            qkv_proj = lambda t, j=None: ag.linear(t, wqkv, bqkv, junction_in=j)
-        # the attention launch also pulls the layer's remaining weight casts (and the next layer's QKV) through the
-        # memory-side cache: the GEMMs behind it would otherwise read them from HBM inside their K loops
-        nfa = ag.FUSED.get(("enc_qkv", id(enc), n + 1)) if ag.DIRECT_GRAD else None
-        pf = tuple(t for t in (ag.cast_of(g(p + "attention.out_proj.weight")),
-                               ag.cast_of(g(p + "feed_forward.intermediate_dense.weight")),
-                               ag.cast_of(g(p + "feed_forward.output_dense.weight")),
-                               ag.cast_of(nfa.w) if nfa is not None else None) if t is not None) or None
-        if stable:   # HubertEncoderLayerStableLayerNorm
-            a = ag.self_attention(qkv_proj(ag.layer_norm(h, *ln1, sole_consumer=False)), H, (d // H) ** -0.5,
-                                  p_drop=c.attention_dropout, prefetch=pf)
-            h = ag.linear_dropout(a, g(p + "attention.out_proj.weight"), g(p + "attention.out_proj.bias"),
-                                  c.hidden_dropout, residual=h)
-            h = ag.ffn(ag.layer_norm(h, *ln2, sole_consumer=False), g(p + "feed_forward.intermediate_dense.weight"),
-                       g(p + "feed_forward.intermediate_dense.bias"), g(p + "feed_forward.output_dense.weight"),
-                       g(p + "feed_forward.output_dense.bias"), c.activation_dropout, c.hidden_dropout, residual=h)
-        else:
-            a = ag.self_attention(qkv_proj(h, J), H, (d // H) ** -0.5, p_drop=c.attention_dropout, prefetch=pf)
-            h = ag.layer_norm(ag.linear_dropout(a, g(p + "attention.out_proj.weight"),
-                                                g(p + "attention.out_proj.bias"), c.hidden_dropout, residual=h,
-                                                junction_out=J), *ln1)
-            # feed-forward block as one autograd node: its backward's middle (linear2's data gradient + dropout + GELU
-            # backward) is one launch
-            h = ag.layer_norm(ag.ffn(h, g(p + "feed_forward.intermediate_dense.weight"),
-                                     g(p + "feed_forward.intermediate_dense.bias"),
-                                     g(p + "feed_forward.output_dense.weight"), g(p + "feed_forward.output_dense.bias"),
-                                     c.activation_dropout, c.hidden_dropout, residual=h), *ln2)
+        h = _residual_block(h, attend, *L.out, L.ln1, c.hidden_dropout, pre_ln=stable)
+        h = _ffn_block(h, *L.ffn, L.ln2, c.activation_dropout, c.hidden_dropout, pre_ln=stable)
         if skip_flag is not None:
-            h = LayerDropSelectFn.apply(skip_flag, h_in, h) if USE_LAYERDROP_FN else torch.where(skip_flag, h_in, h)
+            h = LayerDropSelectFn.apply(skip_flag, h_in, h)
     if stable:
         h = ag.layer_norm(h, g("encoder.layer_norm.weight"), g("encoder.layer_norm.bias"))
     return h
@@ -412,27 +467,11 @@ def denoiser_train(net, motion_noisy, audio_feat, person_feat, static_style_feat
     mask = net.alignment_mask
     pd = 0.1  # nn.TransformerDecoderLayer default dropout (model.py:874-877 passes none): dropout1-3, FFN, attention
     for n in range(net.n_layers):
-        p = f"transformer.layers.{n}."
-        J1, J2 = ag.Junction(), ag.Junction()   # x -> (QKV | Q projection, the block's residual): one gradient, no add
-        qkv = ag.linear(x, g(p + "self_attn.in_proj_weight"), g(p + "self_attn.in_proj_bias"), junction_in=J1)
-        a = ag.self_attention(qkv, H, scale, p_drop=pd)
-        x = ag.layer_norm(ag.linear_dropout(a, g(p + "self_attn.out_proj.weight"), g(p + "self_attn.out_proj.bias"), pd,
-                                            residual=x, junction_out=J1), g(p + "norm1.weight"), g(p + "norm1.bias"))
-        fq = ag.FUSED.get(("dec_q", id(net), n)) if ag.DIRECT_GRAD else None
-        if fq is not None:      # rows of in_proj_weight as arena views: no slice nodes, gradients straight into the arena
-            q = ag.linear_alias(x, fq, junction_in=J2)
-            kv = ag.linear_alias(mem, ag.FUSED[("dec_kv", id(net), n)])
-        else:
-            w, b = g(p + "multihead_attn.in_proj_weight"), g(p + "multihead_attn.in_proj_bias")
-            q = ag.linear(x, w[:d], b[:d], junction_in=J2)
-            kv = ag.linear(mem, w[d:], b[d:])
-        cattn = ag.cross_attention(q, kv, H, scale, mask, p_drop=pd)
-        x = ag.layer_norm(ag.linear_dropout(cattn, g(p + "multihead_attn.out_proj.weight"),
-                                            g(p + "multihead_attn.out_proj.bias"), pd, residual=x, junction_out=J2),
-                          g(p + "norm2.weight"), g(p + "norm2.bias"))
-        x = ag.layer_norm(ag.ffn(x, g(p + "linear1.weight"), g(p + "linear1.bias"), g(p + "linear2.weight"),
-                                 g(p + "linear2.bias"), pd, pd, residual=x),
-                          g(p + "norm3.weight"), g(p + "norm3.bias"))
+        L = _torch_decoder_layer(net, n)
+        x = _residual_block(x, lambda t, J: ag.self_attention(L.qkv(t, J), H, scale, p_drop=pd), *L.out, L.ln1, pd)
+        x = _residual_block(x, lambda t, J: ag.cross_attention(L.q(t, J), L.kv(mem), H, scale, mask, p_drop=pd),
+                            *L.cross_out, L.ln2, pd)
+        x = _ffn_block(x, *L.ffn, L.ln3, pd, pd)
     dec = ag.linear(ag.linear(x[:, 1:].contiguous(), g("motion_dec.0.weight"), g("motion_dec.0.bias"),
                               act=ops.ACT_GELU), g("motion_dec.2.weight"), g("motion_dec.2.bias")).float()
     s = static_style_feat.reshape(N, -1).to(dtype)
@@ -514,15 +553,12 @@ def style_encoder_train(se, motion_coef, dtype):
     x = ag.layer_norm(conv_drop_elu(x, "input_layers.7", 0.2), g("input_layers.11.weight"), g("input_layers.11.bias"),
                       post_add=se.PE.pe[0, T].float().contiguous())
     x = ag.dropout(x, 0.1)                                   # PositionalEncoding dropout (utils/model_common.py:101)
-    d = se.conv_feature_dim
     pd = 0.1                                                 # nn.TransformerEncoderLayer default dropout
-    qkv = ag.linear(x, g("encoder.self_attn.in_proj_weight"), g("encoder.self_attn.in_proj_bias"))
-    a = ag.self_attention(qkv, 8, 64 ** -0.5, p_drop=pd)
-    x = ag.layer_norm(ag.linear_dropout(a, g("encoder.self_attn.out_proj.weight"), g("encoder.self_attn.out_proj.bias"),
-                                        pd, residual=x), g("encoder.norm1.weight"), g("encoder.norm1.bias"))
-    f = ag.linear_dropout(x, g("encoder.linear1.weight"), g("encoder.linear1.bias"), pd, act=ops.ACT_GELU)
-    x = ag.layer_norm(ag.linear_dropout(f, g("encoder.linear2.weight"), g("encoder.linear2.bias"), pd, residual=x),
-                      g("encoder.norm2.weight"), g("encoder.norm2.bias"))
+    L = _torch_encoder_layer(g, "encoder.")
+    x = _residual_block(x, lambda t, J: ag.self_attention(L.qkv(t, J), 8, 64 ** -0.5, p_drop=pd), *L.out, L.ln1, pd,
+                        junction=False)
+    # the two-node form on purpose: ag.ffn would take these shapes in bf16 and launch differently
+    x = _ffn_block(x, *L.ffn, L.ln2, pd, pd, fused=False)
     x = ag.layer_norm(conv_drop_elu(x, "output_layers.1", 0.1), g("output_layers.5.weight"), g("output_layers.5.bias"))
     x = _conv3(x, g("output_layers.7.weight"), g("output_layers.7.bias"), ops.ACT_NONE)
     out = x.float().mean(dim=1)
@@ -574,18 +610,18 @@ def _masked_mean(v, mask):
     return (v * w).sum() / (mask.sum().to(v.dtype) * per_row).clamp(min=1.0)
 
 
-def loss_no_vert_train(args, is_starting_sample, motion_coef_gt, target, prev_motion_coef, end_idx=None, halve=True):
-    """Differentiable restatement of reference utils/common.py:198-442 (target='sample', l2/l1) on (N, 110, 67)
-    tensors with PyTorch autograd ops (plumbing-sized data; the forward-only HIP versions live in utils/common.py).
-    Returns the reference's 7-tuple; halve=False returns the first six terms WITHOUT their final / 2 (the caller applies the
-    factor where it weights the terms: Trainer._combine_losses), the seventh is never halved."""
-    crit = (lambda a, b: (a - b) ** 2) if args.criterion.lower() == "l2" else (lambda a, b: (a - b).abs())
+def _loss_window(args, is_starting_sample, motion_coef_gt, target, prev_motion_coef, end_idx):
+    """The frames a window's losses run over -> (gt, pred, mask, prefix): window 0 drops the n_prev start frames of the
+    prediction; window 1 puts the previous window's frames in front of the ground truth (and, under no_constrain_prev, in place
+    of the prediction's: reference utils/common.py:245-246, their mask rows then off: :382-385).  mask (N, T) bool: frames
+    before end_idx; prefix: the number of leading frames, negative when they are masked out (msmd_masked_seq_loss)."""
     n_prev = args.n_prev_motions
+    free_prev = bool(getattr(args, "no_constrain_prev", False))
     if is_starting_sample:
         target = target[:, n_prev:]
     else:
         motion_coef_gt = torch.cat([prev_motion_coef, motion_coef_gt], dim=1)
-        if getattr(args, "no_constrain_prev", False):     # reference utils/common.py:245-246
+        if free_prev:
             target = torch.cat([prev_motion_coef, target[:, n_prev:]], dim=1)
     N = target.shape[0]
     if end_idx is None:
@@ -593,15 +629,23 @@ def loss_no_vert_train(args, is_starting_sample, motion_coef_gt, target, prev_mo
     else:
         mask = torch.arange(args.n_motions, device=target.device).expand(N, -1) < end_idx.unsqueeze(1)
     if not is_starting_sample:
-        lead = torch.zeros_like if getattr(args, "no_constrain_prev", False) else torch.ones_like   # common.py:382-385
-        mask = torch.cat([lead(mask[:, :n_prev]), mask], dim=1)
+        mask = torch.cat([(torch.zeros_like if free_prev else torch.ones_like)(mask[:, :n_prev]), mask], dim=1)
+    return motion_coef_gt, target, mask, 0 if is_starting_sample else (-n_prev if free_prev else n_prev)
+
+
+def loss_no_vert_train(args, is_starting_sample, motion_coef_gt, target, prev_motion_coef, end_idx=None, halve=True):
+    """Differentiable restatement of reference utils/common.py:198-442 (target='sample', l2/l1) on (N, 110, 67)
+    tensors with PyTorch autograd ops (plumbing-sized data; the forward-only HIP versions live in utils/common.py).
+    Returns the reference's 7-tuple; halve=False returns the first six terms WITHOUT their final / 2 (the caller applies the
+    factor where it weights the terms: Trainer._combine_losses), the seventh is never halved."""
+    crit = (lambda a, b: (a - b) ** 2) if args.criterion.lower() == "l2" else (lambda a, b: (a - b).abs())
+    n_prev = args.n_prev_motions
+    gt, pr, mask, prefix = _loss_window(args, is_starting_sample, motion_coef_gt, target, prev_motion_coef, end_idx)
     d1 = lambda x: x[:, 1:] - x[:, :-1]
-    gt, pr = motion_coef_gt, target
     C = pr.shape[-1]
     if pr.is_cuda:
         # every term is a masked mean of crit(D^k gt, D^k pred) over a column range: six msmd_masked_seq_loss launches
         # forward, six backward launches adding into ONE gradient buffer (instead of ~400 elementwise launches fwd + bwd)
-        prefix = 0 if is_starting_sample else (-n_prev if getattr(args, "no_constrain_prev", False) else n_prev)
         specs = ((0, 0, 0, C), (1, 0, 0, C - 3), (1, 0, C - 3, C), (2, 1, 0, C - 3), (2, 1, C - 3, C), (0, 0, C - 3, C))
         l_noise, vel_a, vel_b, sm_a, sm_b, l_head = SeqLossTermsFn.apply(
             pr, gt, end_idx, prefix, 0 if args.criterion.lower() == "l2" else 1, specs)
@@ -634,18 +678,24 @@ def loss_no_vert_train(args, is_starting_sample, motion_coef_gt, target, prev_mo
 
 
 class SeqLossTermsFn(torch.autograd.Function):
-    """A tuple of masked sequence-loss terms on one (N, T, C) prediction: specs = ((order, mode, c_lo, c_hi), ...), each
+    """A tuple of masked sequence-loss terms on one (N, T, C) prediction: specs = ((order, mode, c_lo, c_hi) | None, ...), each
     one msmd_masked_seq_loss launch (mean over valid frames of the mean over columns [c_lo, c_hi) of crit on the
-    order-th temporal difference; mode 1 compares the prediction's difference with 0).  The backward ADDS every term's
-    gradient into one (N, T, C) buffer (msmd_masked_seq_loss_bwd).  Reference: utils/common.py:198-442."""
+    order-th temporal difference; mode 1 compares the prediction's difference with 0); None: a term nobody wants, a zero
+    without a launch here or in the backward.  The backward ADDS every term's gradient into one (N, T, C) buffer
+    (msmd_masked_seq_loss_bwd) -- for the vertex-space terms on (N, T, 15069) sequences instead of autograd's chain of
+    (N, T, 5023, 3) temporaries per term.  Reference: utils/common.py:198-442, 486-513, 566-574."""
 
     @staticmethod
     def forward(ctx, pred, gt, end_idx, prefix, crit, specs):
         pred, gt = pred.float().contiguous(), gt.float().contiguous()
         e32 = end_idx.to(torch.int32).contiguous() if end_idx is not None else None
         outs, wss = [], []
-        for order, mode, c_lo, c_hi in specs:
-            v, ws = ops.masked_seq_loss(gt, pred, e32, c_lo, c_hi, order, prefix, crit, mode, return_ws=True)
+        for spec in specs:
+            if spec is None:
+                v, ws = pred.new_zeros(()), None
+            else:
+                order, mode, c_lo, c_hi = spec
+                v, ws = ops.masked_seq_loss(gt, pred, e32, c_lo, c_hi, order, prefix, crit, mode, return_ws=True)
             outs.append(v)
             wss.append(ws)
         ctx.save_for_backward(pred, gt)
@@ -657,44 +707,10 @@ class SeqLossTermsFn(torch.autograd.Function):
         pred, gt = ctx.saved_tensors
         e32, prefix, crit, specs, wss = ctx.misc
         grad = torch.zeros_like(pred)
-        for (order, mode, c_lo, c_hi), ws, g in zip(specs, wss, gs):
-            if g is not None:
+        for spec, ws, g in zip(specs, wss, gs):
+            if spec is not None and g is not None:
+                order, mode, c_lo, c_hi = spec
                 ops.masked_seq_loss_bwd_(grad, gt, pred, e32, ws, g, c_lo, c_hi, order, prefix, crit, mode)
-        return grad, None, None, None, None, None
-
-
-class VertexSeqLossFn(torch.autograd.Function):
-    """The three vertex-space terms of reference utils/common.py:486-513, 566-574 on (N, T, 15069) vertex sequences:
-    masked means of crit(gt - pred), of crit on first differences, and of crit(second difference of pred) -- each
-    one msmd_masked_seq_loss launch; the backward ADDS the three gradients into ONE (N, T, 15069) buffer
-    (msmd_masked_seq_loss_bwd), instead of autograd's chain of (N, T, 5023, 3) temporaries per term."""
-
-    @staticmethod
-    def forward(ctx, pred, gt, end_idx, prefix, crit, want):
-        pred, gt = pred.float().contiguous(), gt.float().contiguous()
-        C = pred.shape[-1]
-        e32 = end_idx.to(torch.int32).contiguous() if end_idx is not None else None
-        outs, wss = [], []
-        for k, (order, mode) in enumerate(((0, 0), (1, 0), (2, 1))):
-            if want[k]:
-                v, ws = ops.masked_seq_loss(gt, pred, e32, 0, C, order, prefix, crit, mode, return_ws=True)
-            else:
-                v, ws = pred.new_zeros(()), None
-            outs.append(v)
-            wss.append(ws)
-        ctx.save_for_backward(pred, gt)
-        ctx.misc = (e32, prefix, crit, want, wss)
-        return tuple(outs)
-
-    @staticmethod
-    def backward(ctx, g0, g1, g2):
-        pred, gt = ctx.saved_tensors
-        e32, prefix, crit, want, wss = ctx.misc
-        C = pred.shape[-1]
-        grad = torch.zeros_like(pred)
-        for k, (order, mode, g) in enumerate(((0, 0, g0), (1, 0, g1), (2, 1, g2))):
-            if want[k] and g is not None:
-                ops.masked_seq_loss_bwd_(grad, gt, pred, e32, wss[k], g, 0, C, order, prefix, crit, mode)
         return grad, None, None, None, None, None
 
 
@@ -703,31 +719,15 @@ def loss_vert_train(args, is_starting_sample, shape_coef, motion_coef_gt, target
     """Differentiable restatement of the reference's vertex-space loss (utils/common.py:456-620, target='sample',
     legacy 54-d motion = 50 expression + 4 pose coefficients): parameter-space noise / head terms with autograd ops on
     (N, 110, 54) tensors, the vertex / velocity / smoothness terms through FLAME (differentiable pass of
-    utils.flame.FLAME.forward) and VertexSeqLossFn.  Returns the reference's dict."""
+    utils.flame.FLAME.forward) and SeqLossTermsFn.  Returns the reference's dict."""
     from .utils.common import get_coef_dict
     l2 = args.criterion.lower() == "l2"
     crit = (lambda a, b: (a - b) ** 2) if l2 else (lambda a, b: (a - b).abs())
     n_prev = args.n_prev_motions
-    if is_starting_sample:
-        target = target[:, n_prev:]
-        prefix = 0
-    else:
-        motion_coef_gt = torch.cat([prev_motion_coef, motion_coef_gt], dim=1)
-        if getattr(args, "no_constrain_prev", False):
-            target = torch.cat([prev_motion_coef, target[:, n_prev:]], dim=1)
-        prefix = n_prev
-    N, T = target.shape[0], target.shape[1]
-    if end_idx is None:
-        mask = torch.ones((N, args.n_motions), dtype=torch.bool, device=target.device)
-    else:
-        mask = torch.arange(args.n_motions, device=target.device).expand(N, -1) < end_idx.unsqueeze(1)
-    if not is_starting_sample:
-        lead = torch.zeros_like if getattr(args, "no_constrain_prev", False) else torch.ones_like
-        mask = torch.cat([lead(mask[:, :n_prev]), mask], dim=1)
-        if getattr(args, "no_constrain_prev", False):
-            prefix = -prefix
+    gt, pr, mask, prefix = _loss_window(args, is_starting_sample, motion_coef_gt, target, prev_motion_coef, end_idx)
+    N, T = pr.shape[0], pr.shape[1]
     d1 = lambda x: x[:, 1:] - x[:, :-1]
-    gt, pr = motion_coef_gt.float(), target.float()
+    gt, pr = gt.float(), pr.float()
     out = {"noise": _masked_mean(crit(gt, pr), mask) / 2, "vert": 0, "vel": 0, "smooth": 0, "head_angle": 0, "head_vel": 0,
            "head_smooth": 0, "head_trans": None}
     if args.l_vert > 0 or args.l_vel > 0:
@@ -740,8 +740,10 @@ def loss_vert_train(args, is_starting_sample, shape_coef, motion_coef_gt, target
                        return_lm2d=False, return_lm3d=False)[0].view(N, T, -1)
         vp = flame(cp["shape"].reshape(-1, 100), cp["exp"].reshape(-1, 50), cp["pose"].reshape(-1, 6),
                    return_lm2d=False, return_lm3d=False)[0].view(N, T, -1)
-        lv, lvel, lsm = VertexSeqLossFn.apply(vp, vg, end_idx, prefix, 0 if l2 else 1,
-                                              (args.l_vert > 0, args.l_vel > 0, args.l_smooth > 0))
+        C = vp.shape[-1]     # vertex error, its first difference, the prediction's second difference: all columns
+        specs = tuple(spec if w > 0 else None for spec, w in (((0, 0, 0, C), args.l_vert), ((1, 0, 0, C), args.l_vel),
+                                                              ((2, 1, 0, C), args.l_smooth)))
+        lv, lvel, lsm = SeqLossTermsFn.apply(vp, vg, end_idx, prefix, 0 if l2 else 1, specs)
         out["vert"], out["vel"], out["smooth"] = lv / 2, lvel / 2, lsm / 2
     if not args.no_head_pose:
         hg, hp = gt[:, :, 50:53], pr[:, :, 50:53]

@@ -321,11 +321,8 @@ class Trainer:
         is window i truncated); `cross` = [bool | 0-d bool device tensor] * 2 (use the other window's style).
         Everything stochastic that is not in `draws` is drawn ON THE DEVICE, and nothing reads back to the host,
         so the whole function can be captured in a hipGraph."""
-        args, model, se = self.args, self.model, self.style_enc
+        model = self.model
         dtype = model.compute_dtype
-        audio_pair, motion_pair, shape = batch
-        B = audio_pair[0].shape[0]
-        n_prev = args.n_prev_motions
         lw = dict(self.loss_weights)
         lw["kl_div"] *= self.reducer.kl_weight_scale
         noise = ag.TrainNoise
@@ -347,11 +344,8 @@ class Trainer:
     def _two_windows_in_turn(self, batch, draws, trunc, cross, lw, dtype):
         """The reference's order (training_script.py:99-195): window 0 through the whole model, then window 1.  Kept as the
         comparison form of _two_windows_batched (MSMD_TRAIN_BATCH_WINDOWS=0)."""
-        args, model, se = self.args, self.model, self.style_enc
+        model, se = self.model, self.style_enc
         audio_pair, motion_pair, shape = batch
-        B = audio_pair[0].shape[0]
-        n_prev = args.n_prev_motions
-        noise = ag.TrainNoise
         styles, mus, logvars = [], [], []
         for i in range(2):
             mu, logvar = tg.style_encoder_train(se, motion_pair[i], dtype)
@@ -362,62 +356,18 @@ class Trainer:
         terms = {k: [] for k in lw}     # every loss term of both windows, summed per key and weighted in ONE pass below
         prev_motion = prev_audio = None
         for i in range(2):
-            audio, motion = audio_pair[i], motion_pair[i]
-            if torch.is_tensor(cross[i]):
-                style = torch.where(cross[i], styles[1 - i], styles[i])
-            else:
-                style = styles[1 - i] if cross[i] else styles[i]
-            if "end_idx" in draws:
-                end_idx = draws["end_idx"][i]
-            else:
-                end_idx = torch.randint(1, args.n_motions, (B,), device=self.device) if trunc[i] else None
-            if end_idx is not None:
-                # reference utils/common.py:816-832: audio is cut at (end_idx * audio_unit).long() with the DATASET's
-                # audio_unit = 16000 / fps (a float: 533.33 at 30 fps) and both tensors padded per args.pad_mode
-                e32 = end_idx.to(torch.int32).contiguous()
-                a32 = (end_idx.to(torch.float32) * self.audio_unit).long().to(torch.int32).contiguous()
-                audio_in = ops.truncate_rows_(audio.float().clone().contiguous(), a32, 1, self.pad_replicate)
-                motion_in = ops.truncate_rows_(motion.float().clone().contiguous(), e32, 1, self.pad_replicate)
-                indicator = (torch.arange(args.n_motions, device=self.device).expand(B, -1) < end_idx.unsqueeze(1)).float()
-            else:
-                audio_in, motion_in = audio, motion
-                indicator = torch.ones(B, args.n_motions, device=self.device)
-            ts = draws["t"][i] if "t" in draws else model.diffusion_sched.uniform_sample_t_device(B)
-            eps = draws["eps"][i] if "eps" in draws else torch.randn_like(motion_in)
-            ns, na = self._cfg_masks(draws, i, B)
-            shape_in = torch.zeros_like(shape) if getattr(args, "do_ignore_shape", False) else shape
-            _, target, _, audio_feat = tg.msmd_forward_train(model, motion_in, audio_in, shape_in, style, prev_motion,
-                                                             prev_audio, ts, indicator, eps, ns, na)
+            W = self._window_inputs(i, batch, draws, trunc, cross, styles)
+            _, target, _, audio_feat = tg.msmd_forward_train(model, W["motion_in"], W["audio_in"], W["shape_in"], W["style"],
+                                                             prev_motion, prev_audio, W["ts"], W["indicator"], W["eps"],
+                                                             W["ns"], W["na"])
             if i == 0:
-                if end_idx is not None:  # truncated: hand over the COMPLETE clip's features (training_script.py:152-155)
-                    prev_motion = motion[:, -n_prev:]
-                    with torch.no_grad():
-                        if noise.active:   # the reference's extra pass also runs under model.train()
-                            prev_audio = tg.audio_feat_train(model, audio, model.n_motions, dtype).float()[:, -n_prev:]
-                        else:
-                            prev_audio = model.extract_audio_feature(audio)[:, -n_prev:]
-                else:
-                    prev_motion = motion_in[:, -n_prev:].detach()
-                    prev_audio = audio_feat[:, -n_prev:]
-            if self.vertex_space:
-                ld = tg.loss_vert_train(args, i == 0, shape, motion_in, target, prev_motion if i == 1 else None,
-                                        self.coef_stats, self.flame, end_idx)
-                pairs = ld.items()
-            else:
-                tup = tg.loss_no_vert_train(args, i == 0, motion_in, target, prev_motion if i == 1 else None, end_idx,
-                                            halve=False)     # the / 2 of the first six terms rides in _combine_losses
-                pairs = zip(("noise", "vel", "smooth", "head_angle", "head_vel", "head_smooth", "head_trans"),
-                            [(v, 0.5) for v in tup[:6]] + [(tup[6], 1.0)])
-            for key, val in pairs:
-                val, sc = val if isinstance(val, tuple) else (val, 1.0)
-                if val is not None and torch.is_tensor(val) and lw.get(key, 0) > 0:
-                    terms[key].append((val, sc))
-            terms["kl_div"].append((tg.kl_train(mus[i], logvars[i]), 1.0))
+                prev_motion, prev_audio = self._hand_off(batch, W, audio_feat, dtype)
+            self._loss_terms(i, W, target, prev_motion, shape, mus[i], logvars[i], terms, lw)
         return terms
 
     def _window_inputs(self, i, batch, draws, trunc, cross, styles):
-        """What window i feeds the model, drawn / derived exactly as the in-turn form does (reference training_script.py
-        :120-150, utils/common.py:816-832 for the truncation)."""
+        """THE place a window's inputs are drawn / derived (reference training_script.py:120-150, utils/common.py:816-832 for
+        the truncation).  Device RNG draws happen here, in this order."""
         args, model = self.args, self.model
         audio_pair, motion_pair, shape = batch
         B = audio_pair[0].shape[0]
@@ -431,6 +381,8 @@ class Trainer:
         else:
             end_idx = torch.randint(1, args.n_motions, (B,), device=self.device) if trunc[i] else None
         if end_idx is not None:
+            # reference utils/common.py:816-832: audio is cut at (end_idx * audio_unit).long() with the DATASET's
+            # audio_unit = 16000 / fps (a float: 533.33 at 30 fps) and both tensors padded per args.pad_mode
             e32 = end_idx.to(torch.int32).contiguous()
             a32 = (end_idx.to(torch.float32) * self.audio_unit).long().to(torch.int32).contiguous()
             audio_in = ops.truncate_rows_(audio.float().clone().contiguous(), a32, 1, self.pad_replicate)
@@ -443,8 +395,41 @@ class Trainer:
         eps = draws["eps"][i] if "eps" in draws else torch.randn_like(motion_in)
         ns, na = self._cfg_masks(draws, i, B)
         shape_in = torch.zeros_like(shape) if getattr(args, "do_ignore_shape", False) else shape
-        return dict(style=style, end_idx=end_idx, audio_in=audio_in, motion_in=motion_in, indicator=indicator,
-                    ts=torch.as_tensor(ts, device=self.device, dtype=torch.long), eps=eps, ns=ns, na=na, shape_in=shape_in)
+        return dict(style=style, end_idx=end_idx, audio_in=audio_in, motion_in=motion_in, indicator=indicator, ts=ts, eps=eps,
+                    ns=ns, na=na, shape_in=shape_in)
+
+    def _hand_off(self, batch, W0, audio_feat, dtype):
+        """(prev_motion, prev_audio) of window 1: the last n_prev frames of window 0's ground-truth motion and of its
+        (detached) audio features `audio_feat` (reference training_script.py:152-160)."""
+        model, n_prev = self.model, self.args.n_prev_motions
+        if W0["end_idx"] is None:
+            return W0["motion_in"][:, -n_prev:].detach(), audio_feat[:, -n_prev:].detach()
+        # truncated: hand over the COMPLETE clip's features (training_script.py:152-155)
+        audio = batch[0][0]
+        with torch.no_grad():
+            if ag.TrainNoise.active:   # the reference's extra pass also runs under model.train()
+                prev_audio = tg.audio_feat_train(model, audio, model.n_motions, dtype).float()[:, -n_prev:]
+            else:
+                prev_audio = model.extract_audio_feature(audio)[:, -n_prev:]
+        return batch[1][0][:, -n_prev:], prev_audio
+
+    def _loss_terms(self, i, W, target, prev_motion, shape, mu, logvar, terms, lw):
+        """Append window i's loss terms to `terms` as (value, constant factor) per key."""
+        args = self.args
+        prev = prev_motion if i == 1 else None
+        if self.vertex_space:
+            pairs = tg.loss_vert_train(args, i == 0, shape, W["motion_in"], target, prev, self.coef_stats, self.flame,
+                                       W["end_idx"]).items()
+        else:
+            tup = tg.loss_no_vert_train(args, i == 0, W["motion_in"], target, prev, W["end_idx"],
+                                        halve=False)     # the / 2 of the first six terms rides in _combine_losses
+            pairs = zip(("noise", "vel", "smooth", "head_angle", "head_vel", "head_smooth", "head_trans"),
+                        [(v, 0.5) for v in tup[:6]] + [(tup[6], 1.0)])
+        for key, val in pairs:
+            val, sc = val if isinstance(val, tuple) else (val, 1.0)
+            if val is not None and torch.is_tensor(val) and lw.get(key, 0) > 0:
+                terms[key].append((val, sc))
+        terms["kl_div"].append((tg.kl_train(mu, logvar), 1.0))
 
     def _two_windows_batched(self, batch, draws, trunc, cross, lw, dtype):
         """Both windows through every network as ONE batch of 2 B rows.  Window 1 takes from window 0 only the last
@@ -454,11 +439,9 @@ class Trainer:
         rows], window 1's hand-off read from the encoder's output in between.  Per row the arithmetic is the in-turn form's
         (GEMM rows are independent); weight gradients sum 2 B rows in one product instead of two accumulated ones.  Train-mode
         noise keeps the reference's granularity: one SpecAugment mask and one LayerDrop coin per window and layer."""
-        args, model, se = self.args, self.model, self.style_enc
+        model, se = self.model, self.style_enc
         audio_pair, motion_pair, shape = batch
         B = audio_pair[0].shape[0]
-        n_prev = args.n_prev_motions
-        noise = ag.TrainNoise
         mu2, logvar2 = tg.style_encoder_train(se, torch.cat([motion_pair[0], motion_pair[1]], 0), dtype)
         styles, mus, logvars = [], [], []
         for i in range(2):
@@ -468,19 +451,13 @@ class Trainer:
             mus.append(mu)
             logvars.append(logvar)
         terms = {k: [] for k in lw}
-        W = [self._window_inputs(i, batch, draws, trunc, cross, styles) for i in range(2)]
+        W = []
+        for i in range(2):
+            W.append(self._window_inputs(i, batch, draws, trunc, cross, styles))
+            W[i]["ts"] = torch.as_tensor(W[i]["ts"], device=self.device, dtype=torch.long)    # a tensor to concatenate
         feat2 = tg.audio_feat_train(model, torch.cat([W[0]["audio_in"].float(), W[1]["audio_in"].float()], 0), model.n_motions, dtype,
                                     groups=2).float()
-        if W[0]["end_idx"] is not None:  # truncated: hand over the COMPLETE clip's features (training_script.py:152-155)
-            prev_motion = motion_pair[0][:, -n_prev:]
-            with torch.no_grad():
-                if noise.active:   # the reference's extra pass also runs under model.train()
-                    prev_audio = tg.audio_feat_train(model, audio_pair[0], model.n_motions, dtype).float()[:, -n_prev:]
-                else:
-                    prev_audio = model.extract_audio_feature(audio_pair[0])[:, -n_prev:]
-        else:
-            prev_motion = W[0]["motion_in"][:, -n_prev:].detach()
-            prev_audio = feat2[:B, -n_prev:].detach()
+        prev_motion, prev_audio = self._hand_off(batch, W[0], feat2[:B], dtype)
         cat = lambda k: torch.cat([W[0][k], W[1][k]], 0)
         masks = []
         for k in ("ns", "na"):
@@ -495,21 +472,7 @@ class Trainer:
         _, target2, _, _ = tg.msmd_forward_train(model, cat("motion_in"), feat2, cat("shape_in"), cat("style"), prev_m2, prev_a2,
                                                  cat("ts"), cat("indicator"), cat("eps"), masks[0], masks[1])
         for i in range(2):
-            motion_in, end_idx, target = W[i]["motion_in"], W[i]["end_idx"], target2[i * B:(i + 1) * B]
-            if self.vertex_space:
-                ld = tg.loss_vert_train(args, i == 0, shape, motion_in, target, prev_motion if i == 1 else None,
-                                        self.coef_stats, self.flame, end_idx)
-                pairs = ld.items()
-            else:
-                tup = tg.loss_no_vert_train(args, i == 0, motion_in, target, prev_motion if i == 1 else None, end_idx,
-                                            halve=False)     # the / 2 of the first six terms rides in _combine_losses
-                pairs = zip(("noise", "vel", "smooth", "head_angle", "head_vel", "head_smooth", "head_trans"),
-                            [(v, 0.5) for v in tup[:6]] + [(tup[6], 1.0)])
-            for key, val in pairs:
-                val, sc = val if isinstance(val, tuple) else (val, 1.0)
-                if val is not None and torch.is_tensor(val) and lw.get(key, 0) > 0:
-                    terms[key].append((val, sc))
-            terms["kl_div"].append((tg.kl_train(mus[i], logvars[i]), 1.0))
+            self._loss_terms(i, W[i], target2[i * B:(i + 1) * B], prev_motion, shape, mus[i], logvars[i], terms, lw)
         return terms
 
     def _combine_losses(self, terms, lw):
@@ -518,9 +481,6 @@ class Trainer:
         the backward).  Same arithmetic order per key is NOT kept (fp32 sums of <= 4 terms); reference: training_script.py
         :163-195 (loss_dict accumulation and the weighted sum)."""
         keys = list(lw)
-        if os.environ.get("MSMD_STACK_LOSSES", "1") == "0":     # the term-by-term form, kept for comparison
-            losses = {k: sum((t * sc if sc != 1.0 else t for t, sc in terms[k]), torch.zeros((), device=self.device)) for k in keys}
-            return losses, sum(losses[k] * lw[k] for k in keys if lw[k] > 0)
         flat, owner, scales = [], [], []
         for j, k in enumerate(keys):
             for t, sc in terms[k]:      # sc: a constant factor of the term (the reference's / 2), applied in the selection matrix
