@@ -960,3 +960,282 @@ def test_layernorm_pre_and_folded_person_query(dtype):
     tol = 3e-2 if dtype == torch.bfloat16 else 4e-3
     assert maxabs(a_got.float().cpu().numpy(), a_ref.float().cpu().numpy()) < tol
 
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# The step kernels are written once (cfg_ddpm_kernel<kDev>, one pack_input_kernel) and every storage-type choice goes
+# through dispatch_dtype: the host / device forms agree by construction, and a code outside an entry's type list is refused.
+def cfg_ddpm_numpy(x, res, z, scales, n_entries, L, mode, target, c0, c1, sg):
+    """The restatement of test_cfg_ddpm_step_matches_reference_inplace_semantics for any entry count, with the
+    target == 1 ('noise') line."""
+    r = [c.copy() for c in np.split(res, n_entries, axis=0)]
+    theta = r[0][:, -L:]
+    for i in range(n_entries - 1):
+        theta += scales[i] * (r[i + 1][:, -L:] - (r[0] if mode == 1 else r[i])[:, -L:])
+    zz = z if z is not None else np.float32(0)
+    return c0 * x + c1 * theta + sg * zz if target == 0 else c0 * (x - c1 * theta) + sg * zz
+
+
+@pytest.mark.parametrize("with_z", [True, False])
+@pytest.mark.parametrize("target", [0, 1])
+@pytest.mark.parametrize("mode", [0, 1])
+@pytest.mark.parametrize("n_entries", [1, 2, 3])
+def test_cfg_ddpm_step_host_form_equals_device_form(n_entries, mode, target, with_z):
+    """msmd_cfg_ddpm_step (host scalars) and msmd_cfg_ddpm_step_dev (coefs[0..2] on the device) launch one kernel body:
+    equal bits, and <= 2e-6 (fp32 noise on O(1) values, the bound of the test above) against numpy.  B L dm = 7437 is
+    no multiple of the 256-thread block."""
+    o = ops()
+    B, L, Lp, dm = 3, 37, 5, 67
+    res = synth.normalish(f"ddpm2/res{n_entries}", (n_entries * B, Lp + L, dm))
+    x = synth.normalish("ddpm2/x", (B, L, dm))
+    z = synth.normalish("ddpm2/z", (B, L, dm)) if with_z else None
+    scales = np.array([1.3, 0.9], np.float32)[:max(n_entries - 1, 1)]
+    c0, c1, sg = np.float32(0.7), np.float32(0.25), np.float32(0.1)
+    ref = cfg_ddpm_numpy(x, res, z, scales, n_entries, L, mode, target, c0, c1, sg)
+    zd = dev(z) if with_z else None
+    x_host, x_dev = dev(x).clone(), dev(x).clone()
+    o.cfg_ddpm_step(x_host, dev(res), zd, dev(scales), n_entries, Lp, mode, target, c0, c1, sg)
+    o.cfg_ddpm_step_dev(x_dev, dev(res), zd, dev(scales), dev(np.array([c0, c1, sg], np.float32)), n_entries, Lp, mode, target)
+    torch.cuda.synchronize()
+    err = maxabs(x_host.cpu().numpy(), ref)
+    print(f"ddpm host/dev n_entries={n_entries} mode={mode} target={target} z={with_z}: max|host - numpy| = {err:.3e}")
+    assert torch.equal(x_host, x_dev)
+    assert err <= 2e-6
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float16, torch.bfloat16])
+@pytest.mark.parametrize("with_ind", [True, False])
+def test_pack_input_q_sample_form(with_ind, dtype):
+    """The q-sample form (eps, c0, c1) through the one pack kernel, N = 4 rows over motion_batch = 2 clips (CFG entries share
+    x_t): exact in fp32, one rounding of the output type otherwise."""
+    o = ops()
+    N, MB, L, Lp, dm, Kpad = 4, 2, 7, 3, 5, 8
+    motion = dev(synth.normalish("pack/motion", (MB, L, dm)))
+    eps = dev(synth.normalish("pack/eps", (MB, L, dm)))
+    prev = dev(synth.normalish("pack/prev", (N, Lp, dm)))
+    ind = dev(synth.normalish("pack/ind", (N, L))) if with_ind else None
+    c0 = dev(np.array([0.8, 0.3], np.float32))
+    c1 = dev(np.array([0.6, 0.95], np.float32))
+    feats = torch.full((N, 1 + Lp + L, Kpad), 7.0, device=DEV, dtype=dtype)
+    o.denoiser_pack_input(motion, prev, ind, feats, eps, c0, c1)
+    torch.cuda.synchronize()
+    ref = torch.zeros(N, 1 + Lp + L, Kpad, device=DEV, dtype=torch.float32)
+    ref[:, 1:1 + Lp, :dm] = prev
+    # c0 v + c1 eps as the kernel contracts it: one rounding of c1 eps, then one fused multiply-add (computed in float64:
+    # the product c0 v of two fp32 numbers is exact there, and so is its sum with an fp32 number up to one rounding)
+    p = (c1[:, None, None] * eps).double()
+    xt = (c0[:, None, None].double() * motion.double() + p).float()
+    ref[:, 1 + Lp:, :dm] = xt.repeat(N // MB, 1, 1)
+    if with_ind:
+        ref[:, 1 + Lp:, dm] = ind
+    assert torch.equal(feats, ref.to(dtype)), float((feats.float() - ref).abs().max())
+
+
+_SENTINEL = 1234.5
+
+
+def _unknown_dtype_cases():
+    """name -> fn(lib, st) -> list of (codes, call, outputs): every entry of diffusion / norm / audio / backward.hip that takes a
+    storage-type code.  All buffers are fp32-sized for the shapes given (<= 64 x 64), so whichever typed kernel a broken
+    dispatch launched would stay in bounds; outputs hold _SENTINEL."""
+    def out(*shape):
+        return torch.full(shape, _SENTINEL, device=DEV, dtype=torch.float32)
+
+    keep = []          # the inputs stay allocated for as long as the table lives
+
+    def inp(*shape):
+        keep.append(torch.ones(shape, device=DEV, dtype=torch.float32))
+        return keep[-1]
+
+    def ints(*v):
+        keep.append(torch.tensor(v, device=DEV, dtype=torch.int32))
+        return keep[-1]
+
+    P = lambda t: None if t is None else t.data_ptr()
+    one = [(7,), (3,)]                    # one code: junk, and MSMD_F16X2 where the entry has no split form
+    pair = [(7, 0), (0, 7), (3, 0), (0, 3), (1, 2), (2, 1)]   # (in, out): junk, split, and one 16-bit type into the other
+    cases = {}
+
+    def case(name, codes):
+        def deco(fn):
+            cases[name] = (codes, fn)
+            return fn
+        return deco
+
+    @case("msmd_denoiser_pack_input", one)
+    def _(lib, st, c):
+        f = out(2, 6, 8)
+        return lib.msmd_denoiser_pack_input(P(inp(1, 3, 5)), None, None, None, P(inp(2, 2, 5)), None, P(f), 2, 3, 2, 5, 8, 1, *c, st), [f]
+
+    @case("msmd_denoiser_pack_input_guided", one)
+    def _(lib, st, c):
+        f, m = out(2, 6, 8), torch.ones(1, 3, device=DEV, dtype=torch.uint8)
+        keep.append(m)
+        return lib.msmd_denoiser_pack_input_guided(P(inp(1, 3, 5)), None, None, None, P(inp(2, 2, 5)), None, P(m), P(inp(1, 3, 5)),
+                                                   P(f), 2, 3, 2, 5, 8, 1, *c, st), [f]
+
+    @case("msmd_add_pe_token[8-wide]", one)
+    def _(lib, st, c):
+        x = out(2, 4, 16)
+        return lib.msmd_add_pe_token(P(x), P(inp(4, 16)), P(inp(2, 16)), None, 2, 4, 16, *c, st), [x]
+
+    @case("msmd_add_pe_token[scalar]", one)
+    def _(lib, st, c):
+        x = out(2, 4, 5)
+        return lib.msmd_add_pe_token(P(x), P(inp(4, 5)), P(inp(2, 5)), None, 2, 4, 5, *c, st), [x]
+
+    @case("msmd_heads_static_mix", one)
+    def _(lib, st, c):
+        o_ = out(2, 3, 5)
+        return lib.msmd_heads_static_mix(P(inp(2, 3, 7)), 7, P(inp(1, 2, 5)), P(o_), 2, 3, 5, 2, 1, 0, *c, st), [o_]
+
+    for name, nc in (("msmd_sampler_step_select", 3), ("msmd_sampler_solver_select", 6)):
+        @case(name, one)
+        def _(lib, st, c, name=name, nc=nc):
+            t, row, co = ints(1), out(8), out(6)
+            rc = getattr(lib, name)(P(inp(4, 8)), P(inp(4, nc)), P(t), P(row), P(co), 8, *c, st)
+            return rc, [row, co, t.float() * _SENTINEL]      # the step counter keeps its 1
+
+    @case("msmd_cfg_streams_step", one)
+    def _(lib, st, c):
+        o_ = [out(1, 3, 5) for _ in range(4)] + [out(1, 3, 2)]
+        return lib.msmd_cfg_streams_step(P(o_[0]), P(inp(2, 4, 5)), P(inp(2, 4, 7)), 7, P(inp(1, 2, 5)), None, P(inp(1)), P(o_[1]),
+                                         P(o_[2]), P(o_[3]), P(o_[4]), 0, 1, 2, 1, 3, 1, 5, 2, 1, 0, 0, *c, 0., 1., 1., 1., 0., 0., st), o_
+
+    @case("msmd_cfg_streams_step_dev", one)
+    def _(lib, st, c):
+        o_ = [out(1, 3, 5) for _ in range(4)] + [out(1, 3, 2)]
+        return lib.msmd_cfg_streams_step_dev(P(o_[0]), P(inp(2, 4, 5)), P(inp(2, 4, 7)), 7, P(inp(1, 2, 5)), None, P(inp(1)), P(o_[1]),
+                                             P(o_[2]), P(o_[3]), P(o_[4]), P(inp(6)), P(ints(0)), 1, 2, 1, 3, 1, 5, 2, 1, 0, 0, *c, st), o_
+
+    @case("msmd_pad_cols", pair)
+    def _(lib, st, c):
+        y = out(4, 8)
+        return lib.msmd_pad_cols(P(inp(4, 5)), P(y), 4, 5, 8, *c, st), [y]
+
+    @case("msmd_cast", pair)
+    def _(lib, st, c):
+        y = out(20)
+        return lib.msmd_cast(P(inp(20)), P(y), 20, *c, st), [y]
+
+    @case("msmd_layernorm", pair + [(3, 3), (7, 7)])
+    def _(lib, st, c):
+        y = out(4, 32)
+        return lib.msmd_layernorm(P(inp(4, 32)), None, P(inp(32)), P(inp(32)), None, P(y), 4, 32, 1e-5, 0, *c, st), [y]
+
+    @case("msmd_layernorm_pre", one + [(0,)])        # 16-bit rows only
+    def _(lib, st, c):
+        y = out(4, 32)
+        return lib.msmd_layernorm_pre(P(inp(4, 32)), P(inp(32)), P(inp(32)), None, P(inp(32)), P(inp(32)), P(y), 4, 32, 1e-5, *c, st), [y]
+
+    @case("msmd_mean_time", one)
+    def _(lib, st, c):
+        y = out(2, 8)
+        return lib.msmd_mean_time(P(inp(2, 3, 8)), P(y), 2, 3, 8, *c, st), [y]
+
+    @case("msmd_conv0_gn_gelu", [(7,)])              # MSMD_F16X2 is one of its forms
+    def _(lib, st, c):
+        y = out(1, 7, 8)
+        return lib.msmd_conv0_gn_gelu(P(inp(1, 40)), P(inp(8, 10)), P(inp(1, 8, 2)), P(inp(8)), P(inp(8)), P(y), 1, 40, 0, 0, 8, *c, st), [y]
+
+    @case("msmd_conv0_ln_gelu", one)
+    def _(lib, st, c):
+        y = out(1, 7, 512)
+        return lib.msmd_conv0_ln_gelu(P(inp(1, 40)), P(inp(512, 10)), None, P(inp(512)), P(inp(512)), P(y), 1, 40, 0, 0, 512, 1e-5, *c, st), [y]
+
+    @case("msmd_interp_linear", one)
+    def _(lib, st, c):
+        y = out(1, 6, 8)
+        return lib.msmd_interp_linear(P(inp(1, 4, 8)), P(y), 1, 4, 4, 6, 8, *c, st), [y]
+
+    @case("msmd_group_pad", [(7, 7), (3, 3), (7, 3), (0, 7)])   # (dtype, out_dtype); (0, 3) is its split form
+    def _(lib, st, c):
+        y = out(1, 2, 6, 4)
+        return lib.msmd_group_pad(P(inp(1, 4, 8)), P(y), 1, 4, 2, 4, 4, 1, *c, st), [y]
+
+    @case("msmd_transpose", one)
+    def _(lib, st, c):
+        y = out(8, 4)
+        return lib.msmd_transpose(P(inp(4, 8)), P(y), 4, 8, 8, 4, 1, 0, 0, 1, 0, 0, *c, st), [y]
+
+    @case("msmd_colsum", one)
+    def _(lib, st, c):
+        y = out(16)
+        return lib.msmd_colsum(P(inp(8, 16)), P(y), 8, 16, 16, 0, *c, None, 0, st), [y]
+
+    @case("msmd_act_fwd", one)
+    def _(lib, st, c):
+        y = out(64)
+        return lib.msmd_act_fwd(P(inp(64)), P(y), 64, 1, *c, st), [y]
+
+    @case("msmd_act_bwd", one)
+    def _(lib, st, c):
+        y = out(64)
+        return lib.msmd_act_bwd(P(inp(64)), P(inp(64)), P(y), 64, 1, *c, st), [y]
+
+    @case("msmd_layernorm_bwd", one)
+    def _(lib, st, c):
+        o_ = [out(4, 32), out(32), out(32)]
+        return lib.msmd_layernorm_bwd(P(inp(4, 32)), P(inp(4, 32)), P(inp(32)), P(o_[0]), P(o_[1]), P(o_[2]), 4, 32, 1e-5, *c, None, 0, st), o_
+
+    @case("msmd_layernorm_bwd_dropout", one)
+    def _(lib, st, c):
+        o_ = [out(4, 32), out(4, 32), out(32), out(32)]
+        rng = torch.zeros(2, device=DEV, dtype=torch.int64)
+        keep.append(rng)
+        return lib.msmd_layernorm_bwd_dropout(P(inp(4, 32)), P(inp(4, 32)), P(inp(32)), P(o_[0]), P(o_[1]), P(o_[2]), P(o_[3]), 4, 32,
+                                              1e-5, 0.1, P(rng), 1, *c, None, 0, st), o_
+
+    @case("msmd_softmax_rows", one)
+    def _(lib, st, c):
+        s = out(4, 8)
+        return lib.msmd_softmax_rows(P(s), None, 4, 8, 8, 4, 1.0, *c, st), [s]
+
+    @case("msmd_softmax_bwd_rows", one)
+    def _(lib, st, c):
+        d = out(4, 8)
+        return lib.msmd_softmax_bwd_rows(P(inp(4, 8)), P(d), 4, 8, 8, 1.0, *c, st), [d]
+
+    @case("msmd_unfold_t", one)
+    def _(lib, st, c):
+        y = out(4, 4)
+        return lib.msmd_unfold_t(P(inp(1, 1, 5, 2)), P(y), 1, 4, 5, 1, 2, 2, 4, *c, st), [y]
+
+    @case("msmd_dropout", one)
+    def _(lib, st, c):
+        y, rng = out(64), torch.zeros(2, device=DEV, dtype=torch.int64)
+        keep.append(rng)
+        return lib.msmd_dropout(P(inp(64)), None, P(y), 64, 0.1, P(rng), 1, *c, st), [y]
+
+    @case("msmd_act_bwd_dropout", one)
+    def _(lib, st, c):
+        y, rng = out(64), torch.zeros(2, device=DEV, dtype=torch.int64)
+        keep.append(rng)
+        return lib.msmd_act_bwd_dropout(P(inp(64)), P(inp(64)), P(y), 64, 1, 0.1, P(rng), 1, *c, st), [y]
+
+    return cases
+
+
+# Entries that keep a named fall-through because a caller relies on it (name -> reason).  None does.
+_UNKNOWN_DTYPE_EXEMPT = {}
+
+
+def test_unknown_dtype_codes_are_refused_and_nothing_is_written():
+    """A storage-type code outside an entry's type list (7: no type; 3: MSMD_F16X2 where the entry has no split form; for the
+    converting entries one 16-bit type into the other) returns non-zero and launches nothing: every output keeps its
+    sentinel.  Called on the library directly: ops._dt() would not produce most of these codes."""
+    from msmd_amd import _lib
+    lib = _lib.load()
+    st = torch.cuda.current_stream().cuda_stream
+    bad = []
+    for name, (codes, fn) in _unknown_dtype_cases().items():
+        if name in _UNKNOWN_DTYPE_EXEMPT:
+            continue
+        for c in codes:
+            rc, outs = fn(lib, st, c)
+            torch.cuda.synchronize()
+            if rc == 0:
+                bad.append(f"{name}{c}: returned 0")
+            if not all(bool((o_ == _SENTINEL).all()) for o_ in outs):
+                bad.append(f"{name}{c}: an output was written")
+    assert not bad, bad

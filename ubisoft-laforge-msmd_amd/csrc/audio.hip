@@ -298,31 +298,25 @@ extern "C" int msmd_conv0_gn_gelu(const float* audio, const float* w0, const flo
     if (C & 31) return 1;
     hipLaunchKernelGGL((conv0_gn_gelu_kernel<f16_t, true>), grid, block, 0, (hipStream_t)stream, audio, w0, stats, gamma,
                        beta, (f16_t*)out, L, reflect_len, replicate_len, C, T0);
-  } else if (out_dtype == MSMD_F32)
-    hipLaunchKernelGGL(conv0_gn_gelu_kernel<float>, grid, block, 0, (hipStream_t)stream, audio, w0, stats, gamma, beta,
-                       (float*)out, L, reflect_len, replicate_len, C, T0);
-  else if ((C & 31) == 0 && C <= 1024) {
-    // 16-bit outputs: the conv on the matrix pipe (conv0_mfma_kernel)
-    const size_t lds = (((128 * C0_S + C0_K) * 4 + 15) & ~15) + (size_t)C * 64 + (size_t)C * 8;
-    dim3 g2((T0 + 127) / 128, B);
-    if (out_dtype == MSMD_F16) {
-      static bool attr = false;
-      if (!attr) { (void)hipFuncSetAttribute((const void*)conv0_mfma_kernel<f16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024); attr = true; }
-      hipLaunchKernelGGL(conv0_mfma_kernel<f16_t>, g2, block, lds, (hipStream_t)stream, audio, w0, stats, gamma, beta,
-                         (f16_t*)out, L, reflect_len, replicate_len, C, T0);
-    } else {
-      static bool attr = false;
-      if (!attr) { (void)hipFuncSetAttribute((const void*)conv0_mfma_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024); attr = true; }
-      hipLaunchKernelGGL(conv0_mfma_kernel<bf16_t>, g2, block, lds, (hipStream_t)stream, audio, w0, stats, gamma, beta,
-                         (bf16_t*)out, L, reflect_len, replicate_len, C, T0);
+    MSMD_RETURN_LAST();
+  }
+  return dispatch_dtype<float, f16_t, bf16_t>(out_dtype, [&](auto tag) {
+    typedef MSMD_TAG_T(tag) TO;
+    if constexpr (sizeof(TO) == 2) {
+      if ((C & 31) == 0 && C <= 1024) {   // 16-bit outputs: the conv on the matrix pipe (conv0_mfma_kernel)
+        const size_t lds = (((128 * C0_S + C0_K) * 4 + 15) & ~15) + (size_t)C * 64 + (size_t)C * 8;
+        dim3 g2((T0 + 127) / 128, B);
+        static bool attr = false;   // one per output type
+        if (!attr) { (void)hipFuncSetAttribute((const void*)conv0_mfma_kernel<TO>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024); attr = true; }
+        hipLaunchKernelGGL(conv0_mfma_kernel<TO>, g2, block, lds, (hipStream_t)stream, audio, w0, stats, gamma, beta,
+                           (TO*)out, L, reflect_len, replicate_len, C, T0);
+        MSMD_RETURN_LAST();
+      }
     }
-  } else if (out_dtype == MSMD_F16)
-    hipLaunchKernelGGL(conv0_gn_gelu_kernel<f16_t>, grid, block, 0, (hipStream_t)stream, audio, w0, stats, gamma,
-                       beta, (f16_t*)out, L, reflect_len, replicate_len, C, T0);
-  else
-    hipLaunchKernelGGL(conv0_gn_gelu_kernel<bf16_t>, grid, block, 0, (hipStream_t)stream, audio, w0, stats, gamma,
-                       beta, (bf16_t*)out, L, reflect_len, replicate_len, C, T0);
-  MSMD_RETURN_LAST();
+    hipLaunchKernelGGL(conv0_gn_gelu_kernel<TO>, grid, block, 0, (hipStream_t)stream, audio, w0, stats, gamma, beta,
+                       (TO*)out, L, reflect_len, replicate_len, C, T0);
+    MSMD_RETURN_LAST();
+  });
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -394,16 +388,12 @@ extern "C" int msmd_conv0_ln_gelu(const float* audio, const float* w0, const flo
   const int Lp = L + 4 * reflect_len + 2 * replicate_len;
   const int T0 = (Lp - C0_K) / C0_S + 1;
   dim3 grid((T0 + 63) / 64, B), block(256);
-  if (out_dtype == MSMD_F32)
-    hipLaunchKernelGGL(conv0_ln_gelu_kernel<float>, grid, block, 0, (hipStream_t)stream, audio, w0, bias, gamma, beta,
-                       (float*)out, L, reflect_len, replicate_len, T0, eps);
-  else if (out_dtype == MSMD_F16)
-    hipLaunchKernelGGL(conv0_ln_gelu_kernel<f16_t>, grid, block, 0, (hipStream_t)stream, audio, w0, bias, gamma, beta,
-                       (f16_t*)out, L, reflect_len, replicate_len, T0, eps);
-  else
-    hipLaunchKernelGGL(conv0_ln_gelu_kernel<bf16_t>, grid, block, 0, (hipStream_t)stream, audio, w0, bias, gamma, beta,
-                       (bf16_t*)out, L, reflect_len, replicate_len, T0, eps);
-  MSMD_RETURN_LAST();
+  return dispatch_dtype<float, f16_t, bf16_t>(out_dtype, [&](auto tag) {
+    typedef MSMD_TAG_T(tag) TO;
+    hipLaunchKernelGGL(conv0_ln_gelu_kernel<TO>, grid, block, 0, (hipStream_t)stream, audio, w0, bias, gamma, beta,
+                       (TO*)out, L, reflect_len, replicate_len, T0, eps);
+    MSMD_RETURN_LAST();
+  });
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -431,16 +421,12 @@ extern "C" int msmd_interp_linear(const void* x, void* y, int B, int T_in, int T
                                   msmd_stream_t stream) {
   if (B <= 0 || T_in <= 0 || T_crop <= 0 || T_crop > T_in || T_out <= 0 || C <= 0) return 1;
   dim3 grid((C + 255) / 256, T_out, B), block(256);
-  if (dtype == MSMD_F32)
-    hipLaunchKernelGGL(interp_linear_kernel<float>, grid, block, 0, (hipStream_t)stream, (const float*)x, (float*)y,
-                       T_in, T_crop, T_out, C);
-  else if (dtype == MSMD_F16)
-    hipLaunchKernelGGL(interp_linear_kernel<f16_t>, grid, block, 0, (hipStream_t)stream, (const f16_t*)x,
-                       (f16_t*)y, T_in, T_crop, T_out, C);
-  else
-    hipLaunchKernelGGL(interp_linear_kernel<bf16_t>, grid, block, 0, (hipStream_t)stream, (const bf16_t*)x,
-                       (bf16_t*)y, T_in, T_crop, T_out, C);
-  MSMD_RETURN_LAST();
+  return dispatch_dtype<float, f16_t, bf16_t>(dtype, [&](auto tag) {
+    typedef MSMD_TAG_T(tag) T;
+    hipLaunchKernelGGL(interp_linear_kernel<T>, grid, block, 0, (hipStream_t)stream, (const T*)x, (T*)y, T_in, T_crop,
+                       T_out, C);
+    MSMD_RETURN_LAST();
+  });
 }
 
 // (B, T, G*Cg) -> zero-padded group-major (B, G, T + 2*pad, Cgo) with Cgo >= Cg (extra channels zero).  Output in
@@ -478,13 +464,12 @@ extern "C" int msmd_group_pad(const void* x, void* y, int B, int T, int G, int C
   if (out_dtype == MSMD_F16X2) {
     if (dtype != MSMD_F32 || (Cg_out & 31)) return 1;
     hipLaunchKernelGGL((group_pad_kernel<float, true>), grid, block, 0, st, (const float*)x, y, T, G, Cg, Cg_out, pad);
-  } else if (out_dtype != dtype) {
-    return 1;
-  } else if (dtype == MSMD_F32)
-    hipLaunchKernelGGL((group_pad_kernel<float, false>), grid, block, 0, st, (const float*)x, y, T, G, Cg, Cg_out, pad);
-  else if (dtype == MSMD_F16)
-    hipLaunchKernelGGL((group_pad_kernel<f16_t, false>), grid, block, 0, st, (const f16_t*)x, y, T, G, Cg, Cg_out, pad);
-  else
-    hipLaunchKernelGGL((group_pad_kernel<bf16_t, false>), grid, block, 0, st, (const bf16_t*)x, y, T, G, Cg, Cg_out, pad);
-  MSMD_RETURN_LAST();
+    MSMD_RETURN_LAST();
+  }
+  if (out_dtype != dtype) return 1;
+  return dispatch_dtype<float, f16_t, bf16_t>(dtype, [&](auto tag) {
+    typedef MSMD_TAG_T(tag) TX;
+    hipLaunchKernelGGL((group_pad_kernel<TX, false>), grid, block, 0, st, (const TX*)x, y, T, G, Cg, Cg_out, pad);
+    MSMD_RETURN_LAST();
+  });
 }

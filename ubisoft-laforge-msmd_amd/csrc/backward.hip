@@ -33,15 +33,14 @@ extern "C" int msmd_transpose(const void* x, void* y, int rows, int cols, long l
                               long stride_y, int batch_inner, long stride_x_i, long stride_y_i, int dtype,
                               msmd_stream_t stream) {
   if (rows <= 0 || cols <= 0 || batch <= 0 || batch_inner <= 0) return 1;
-  if (dtype != MSMD_F32 && dtype != MSMD_BF16 && dtype != MSMD_F16) return 1;   // moves bits: any 2- or 4-byte type
   dim3 grid((cols + 63) / 64, (rows + 63) / 64, batch * batch_inner), block(256);
-  if (dtype == MSMD_F32)
-    hipLaunchKernelGGL(transpose_kernel<float>, grid, block, 0, (hipStream_t)stream, (const float*)x, (float*)y, rows,
-                       cols, ldx, ldy, stride_x, stride_y, batch_inner, stride_x_i, stride_y_i);
-  else
-    hipLaunchKernelGGL(transpose_kernel<bf16_t>, grid, block, 0, (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)y,
-                       rows, cols, ldx, ldy, stride_x, stride_y, batch_inner, stride_x_i, stride_y_i);
-  MSMD_RETURN_LAST();
+  // moves bits: fp16 goes through the bf16 kernel (any 2-byte type would)
+  return dispatch_dtype<float, bf16_t>(dtype == MSMD_F16 ? MSMD_BF16 : dtype, [&](auto tag) {
+    typedef MSMD_TAG_T(tag) T;
+    hipLaunchKernelGGL(transpose_kernel<T>, grid, block, 0, (hipStream_t)stream, (const T*)x, (T*)y, rows, cols, ldx, ldy,
+                       stride_x, stride_y, batch_inner, stride_x_i, stride_y_i);
+    MSMD_RETURN_LAST();
+  });
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -97,23 +96,22 @@ extern "C" long msmd_colsum_workspace(long rows, int cols) { return ((rows + 127
 extern "C" int msmd_colsum(const void* x, float* out, long rows, int cols, long ld, int accumulate, int dtype,
                            void* ws, long ws_bytes, msmd_stream_t stream) {
   if (rows <= 0 || cols <= 0) return 1;
-  if (dtype != MSMD_F32 && dtype != MSMD_BF16) return 1;   // fp32 or bf16 only (no fp16 training path)
   hipStream_t st = (hipStream_t)stream;
   const int rpb = 128;
   const int nblocks = (int)((rows + rpb - 1) / rpb);
   float* partial = (ws && ws_bytes >= msmd_colsum_workspace(rows, cols)) ? (float*)ws : nullptr;
-  if (!accumulate && !partial) {
-    hipError_t e = msmd_zero_async(out, (size_t)cols * sizeof(float), st);
-    if (e != hipSuccess) return (int)e;
-  }
   dim3 grid((cols + 255) / 256, (unsigned)nblocks), block(256);
-  if (dtype == MSMD_F32)
-    hipLaunchKernelGGL(colsum_kernel<float>, grid, block, 0, st, (const float*)x, out, rows, cols, ld, rpb, partial);
-  else
-    hipLaunchKernelGGL(colsum_kernel<bf16_t>, grid, block, 0, st, (const bf16_t*)x, out, rows, cols, ld, rpb, partial);
-  if (partial)
-    hipLaunchKernelGGL(colsum_finish_kernel, dim3((cols + 63) / 64), dim3(256), 0, st, partial, out, nblocks, cols, accumulate ? 1 : 0);
-  MSMD_RETURN_LAST();
+  return dispatch_dtype<float, bf16_t>(dtype, [&](auto tag) {   // fp32 or bf16 only (no fp16 training path), here and below
+    typedef MSMD_TAG_T(tag) T;
+    if (!accumulate && !partial) {
+      hipError_t e = msmd_zero_async(out, (size_t)cols * sizeof(float), st);
+      if (e != hipSuccess) return (int)e;
+    }
+    hipLaunchKernelGGL(colsum_kernel<T>, grid, block, 0, st, (const T*)x, out, rows, cols, ld, rpb, partial);
+    if (partial)
+      hipLaunchKernelGGL(colsum_finish_kernel, dim3((cols + 63) / 64), dim3(256), 0, st, partial, out, nblocks, cols, accumulate ? 1 : 0);
+    MSMD_RETURN_LAST();
+  });
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -140,25 +138,21 @@ __global__ void act_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ z
 
 extern "C" int msmd_act_fwd(const void* z, void* y, long n, int act, int dtype, msmd_stream_t stream) {
   if (n <= 0) return 1;
-  if (dtype != MSMD_F32 && dtype != MSMD_BF16) return 1;   // fp32 or bf16 only (no fp16 training path)
   dim3 grid((unsigned)min((n + 255) / 256, (long)8192)), block(256);
-  if (dtype == MSMD_F32)
-    hipLaunchKernelGGL(act_fwd_kernel<float>, grid, block, 0, (hipStream_t)stream, (const float*)z, (float*)y, n, act);
-  else
-    hipLaunchKernelGGL(act_fwd_kernel<bf16_t>, grid, block, 0, (hipStream_t)stream, (const bf16_t*)z, (bf16_t*)y, n, act);
-  MSMD_RETURN_LAST();
+  return dispatch_dtype<float, bf16_t>(dtype, [&](auto tag) {
+    typedef MSMD_TAG_T(tag) T;
+    hipLaunchKernelGGL(act_fwd_kernel<T>, grid, block, 0, (hipStream_t)stream, (const T*)z, (T*)y, n, act);
+    MSMD_RETURN_LAST();
+  });
 }
 extern "C" int msmd_act_bwd(const void* dy, const void* z, void* dz, long n, int act, int dtype, msmd_stream_t stream) {
   if (n <= 0) return 1;
-  if (dtype != MSMD_F32 && dtype != MSMD_BF16) return 1;   // fp32 or bf16 only (no fp16 training path)
   dim3 grid((unsigned)min((n + 255) / 256, (long)8192)), block(256);
-  if (dtype == MSMD_F32)
-    hipLaunchKernelGGL(act_bwd_kernel<float>, grid, block, 0, (hipStream_t)stream, (const float*)dy, (const float*)z,
-                       (float*)dz, n, act);
-  else
-    hipLaunchKernelGGL(act_bwd_kernel<bf16_t>, grid, block, 0, (hipStream_t)stream, (const bf16_t*)dy,
-                       (const bf16_t*)z, (bf16_t*)dz, n, act);
-  MSMD_RETURN_LAST();
+  return dispatch_dtype<float, bf16_t>(dtype, [&](auto tag) {
+    typedef MSMD_TAG_T(tag) T;
+    hipLaunchKernelGGL(act_bwd_kernel<T>, grid, block, 0, (hipStream_t)stream, (const T*)dy, (const T*)z, (T*)dz, n, act);
+    MSMD_RETURN_LAST();
+  });
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -275,10 +269,6 @@ __global__ __launch_bounds__(256) void ln_partial_reduce_kernel(const float* __r
 // dependent ones.  The variance is the two-pass sum of squared deviations, as in msmd_layernorm and the scalar kernel:
 // the one-pass sum x^2 / n - mean^2 cancels in fp32 on rows whose mean is large against their spread (rstd off by 1.5e-2
 // at mean / std = 100, 768 columns).  sum g xhat = rstd sum g (x - mean) keeps the second round independent of rstd.
-template <typename T> struct Vec4;
-template <> struct Vec4<float> { typedef f32x4 type; };
-template <> struct Vec4<bf16_t> { typedef __bf16 type __attribute__((ext_vector_type(4))); };
-
 template <typename T, int NCH>
 __global__ __launch_bounds__(256) void layernorm_bwd4_kernel(const T* __restrict__ dy, const T* __restrict__ x,
                                                              const float* __restrict__ gamma, T* __restrict__ dx,
@@ -287,7 +277,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd4_kernel(const T* __restrict
                                                              float* __restrict__ partial, T* __restrict__ dx_drop,
                                                              float p_drop, const unsigned long* __restrict__ rng_state,
                                                              unsigned site) {
-  typedef typename Vec4<T>::type V4;
+  typedef typename Vec4T<T>::type V4;
   __shared__ float sg[4][NCH * 256 + 4], sb[4][NCH * 256 + 4];
   const unsigned thr = dropout_threshold(p_drop);
   const float drop_c = 1.0f / (1.0f - p_drop);
@@ -410,7 +400,6 @@ static int layernorm_bwd_impl(const void* dy, const void* x, const float* gamma,
                               msmd_stream_t stream, void* dx_drop, float p_drop, const unsigned long* rng_state,
                               unsigned site) {
   if (rows <= 0 || cols <= 0 || cols > 1024) return 1;
-  if (dtype != MSMD_F32 && dtype != MSMD_BF16) return 1;   // fp32 or bf16 only (no fp16 training path)
   if (dx_drop && (!(p_drop > 0.f && p_drop < 1.f) || !rng_state || (cols & 3) || ((uintptr_t)dx_drop & 15) ||
                   ((uintptr_t)dy & 15) || ((uintptr_t)x & 15) || ((uintptr_t)dx & 15)))
     return 1;   // the dropped copy exists in the 4-wide kernels only
@@ -419,38 +408,28 @@ static int layernorm_bwd_impl(const void* dy, const void* x, const float* gamma,
   dim3 grid((rows + rpb - 1) / rpb), block(256);
   hipStream_t st = (hipStream_t)stream;
   const bool aligned = ((uintptr_t)dy % 16 == 0) && ((uintptr_t)x % 16 == 0) && ((uintptr_t)dx % 16 == 0);
-  if (cols % 4 == 0 && aligned) {
-#define LN4(T, NCH)                                                                                                  \
+  return dispatch_dtype<float, bf16_t>(dtype, [&](auto tag) {
+    typedef MSMD_TAG_T(tag) T;
+    if (cols % 4 == 0 && aligned) {
+#define LN4(NCH)                                                                                                     \
   hipLaunchKernelGGL((layernorm_bwd4_kernel<T, NCH>), grid, block, 0, st, (const T*)dy, (const T*)x, gamma, (T*)dx, \
                      dgamma, dbeta, rows, cols, eps, rpb, partial, (T*)dx_drop, p_drop, rng_state, site)
-    if (dtype == MSMD_F32) {
-      if (cols <= 256) LN4(float, 1); else if (cols <= 512) LN4(float, 2); else if (cols <= 768) LN4(float, 3); else LN4(float, 4);
-    } else {
-      if (cols <= 256) LN4(bf16_t, 1); else if (cols <= 512) LN4(bf16_t, 2); else if (cols <= 768) LN4(bf16_t, 3); else LN4(bf16_t, 4);
-    }
+      if (cols <= 256) LN4(1); else if (cols <= 512) LN4(2); else if (cols <= 768) LN4(3); else LN4(4);
 #undef LN4
-  } else if (dtype == MSMD_F32) {
-    if (cols <= 512)
-      hipLaunchKernelGGL((layernorm_bwd_kernel<float, 8>), grid, block, 0, st, (const float*)dy, (const float*)x, gamma,
-                         (float*)dx, dgamma, dbeta, rows, cols, eps, rpb, partial);
-    else
-      hipLaunchKernelGGL((layernorm_bwd_kernel<float, 16>), grid, block, 0, st, (const float*)dy, (const float*)x,
-                         gamma, (float*)dx, dgamma, dbeta, rows, cols, eps, rpb, partial);
-  } else {
-    if (cols <= 512)
-      hipLaunchKernelGGL((layernorm_bwd_kernel<bf16_t, 8>), grid, block, 0, st, (const bf16_t*)dy, (const bf16_t*)x,
-                         gamma, (bf16_t*)dx, dgamma, dbeta, rows, cols, eps, rpb, partial);
-    else if (cols <= 768)
-      hipLaunchKernelGGL((layernorm_bwd_kernel<bf16_t, 12>), grid, block, 0, st, (const bf16_t*)dy, (const bf16_t*)x,
-                         gamma, (bf16_t*)dx, dgamma, dbeta, rows, cols, eps, rpb, partial);
-    else
-      hipLaunchKernelGGL((layernorm_bwd_kernel<bf16_t, 16>), grid, block, 0, st, (const bf16_t*)dy, (const bf16_t*)x,
-                         gamma, (bf16_t*)dx, dgamma, dbeta, rows, cols, eps, rpb, partial);
-  }
-  if (partial)
-    hipLaunchKernelGGL(ln_partial_reduce_kernel, dim3((cols + 31) / 32, 2), dim3(256), 0, st, partial, dgamma, dbeta,
-                       (int)grid.x, cols);
-  MSMD_RETURN_LAST();
+    } else {
+#define LN1(MAXC)                                                                                                    \
+  hipLaunchKernelGGL((layernorm_bwd_kernel<T, MAXC>), grid, block, 0, st, (const T*)dy, (const T*)x, gamma, (T*)dx, \
+                     dgamma, dbeta, rows, cols, eps, rpb, partial)
+      if (cols <= 512) LN1(8);
+      else if constexpr (sizeof(T) == 2) { if (cols <= 768) LN1(12); else LN1(16); }   // the 12-chunk form: bf16 only
+      else LN1(16);
+#undef LN1
+    }
+    if (partial)
+      hipLaunchKernelGGL(ln_partial_reduce_kernel, dim3((cols + 31) / 32, 2), dim3(256), 0, st, partial, dgamma, dbeta,
+                         (int)grid.x, cols);
+    MSMD_RETURN_LAST();
+  });
 }
 
 extern "C" int msmd_layernorm_bwd(const void* dy, const void* x, const float* gamma, void* dx, float* dgamma,
@@ -521,28 +500,23 @@ __global__ __launch_bounds__(256) void softmax_bwd_rows_kernel(const T* __restri
 extern "C" int msmd_softmax_rows(void* s, const uint8_t* mask, long rows, int cols, int ld, int Tq, float scale,
                                  int dtype, msmd_stream_t stream) {
   if (rows <= 0 || cols <= 0 || Tq <= 0 || ld < cols) return 1;
-  if (dtype != MSMD_F32 && dtype != MSMD_BF16) return 1;   // fp32 or bf16 only (no fp16 training path)
   dim3 grid((unsigned)((rows + 3) / 4)), block(256);
-  if (dtype == MSMD_F32)
-    hipLaunchKernelGGL(softmax_rows_kernel<float>, grid, block, 0, (hipStream_t)stream, (float*)s, mask, rows, cols, ld,
-                       Tq, scale);
-  else
-    hipLaunchKernelGGL(softmax_rows_kernel<bf16_t>, grid, block, 0, (hipStream_t)stream, (bf16_t*)s, mask, rows, cols,
-                       ld, Tq, scale);
-  MSMD_RETURN_LAST();
+  return dispatch_dtype<float, bf16_t>(dtype, [&](auto tag) {
+    typedef MSMD_TAG_T(tag) T;
+    hipLaunchKernelGGL(softmax_rows_kernel<T>, grid, block, 0, (hipStream_t)stream, (T*)s, mask, rows, cols, ld, Tq, scale);
+    MSMD_RETURN_LAST();
+  });
 }
 extern "C" int msmd_softmax_bwd_rows(const void* P, void* dP, long rows, int cols, int ld, float scale, int dtype,
                                      msmd_stream_t stream) {
   if (rows <= 0 || cols <= 0 || ld < cols) return 1;
-  if (dtype != MSMD_F32 && dtype != MSMD_BF16) return 1;   // fp32 or bf16 only (no fp16 training path)
   dim3 grid((unsigned)((rows + 3) / 4)), block(256);
-  if (dtype == MSMD_F32)
-    hipLaunchKernelGGL(softmax_bwd_rows_kernel<float>, grid, block, 0, (hipStream_t)stream, (const float*)P,
-                       (float*)dP, rows, cols, ld, scale);
-  else
-    hipLaunchKernelGGL(softmax_bwd_rows_kernel<bf16_t>, grid, block, 0, (hipStream_t)stream, (const bf16_t*)P,
-                       (bf16_t*)dP, rows, cols, ld, scale);
-  MSMD_RETURN_LAST();
+  return dispatch_dtype<float, bf16_t>(dtype, [&](auto tag) {
+    typedef MSMD_TAG_T(tag) T;
+    hipLaunchKernelGGL(softmax_bwd_rows_kernel<T>, grid, block, 0, (hipStream_t)stream, (const T*)P, (T*)dP, rows, cols,
+                       ld, scale);
+    MSMD_RETURN_LAST();
+  });
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -569,15 +543,14 @@ __global__ __launch_bounds__(256) void unfold_t_kernel(const T* __restrict__ xp,
 extern "C" int msmd_unfold_t(const void* xp, void* out, int B, int T, int Tp, int G, int Cg, int Kk, long ld_out,
                              int dtype, msmd_stream_t stream) {
   if (B <= 0 || T <= 0 || Tp < T + Kk - 1 || G <= 0 || Cg <= 0 || Kk <= 0 || ld_out < (long)B * T) return 1;
-  if (dtype != MSMD_F32 && dtype != MSMD_BF16 && dtype != MSMD_F16) return 1;   // moves bits: any 2- or 4-byte type
   dim3 grid((unsigned)min((ld_out + 255) / 256, (long)64), Kk * Cg, G), block(256);
-  if (dtype == MSMD_F32)
-    hipLaunchKernelGGL(unfold_t_kernel<float>, grid, block, 0, (hipStream_t)stream, (const float*)xp, (float*)out, B, T,
-                       Tp, G, Cg, Kk, ld_out);
-  else
-    hipLaunchKernelGGL(unfold_t_kernel<bf16_t>, grid, block, 0, (hipStream_t)stream, (const bf16_t*)xp, (bf16_t*)out, B,
-                       T, Tp, G, Cg, Kk, ld_out);
-  MSMD_RETURN_LAST();
+  // moves bits: fp16 goes through the bf16 kernel (any 2-byte type would)
+  return dispatch_dtype<float, bf16_t>(dtype == MSMD_F16 ? MSMD_BF16 : dtype, [&](auto tag) {
+    typedef MSMD_TAG_T(tag) TX;
+    hipLaunchKernelGGL(unfold_t_kernel<TX>, grid, block, 0, (hipStream_t)stream, (const TX*)xp, (TX*)out, B, T, Tp, G, Cg,
+                       Kk, ld_out);
+    MSMD_RETURN_LAST();
+  });
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -608,15 +581,13 @@ __global__ __launch_bounds__(256) void dropout_kernel(const T* __restrict__ x, c
 extern "C" int msmd_dropout(const void* x, const void* residual, void* y, long n, float p,
                             const unsigned long* rng_state, unsigned int site, int dtype, msmd_stream_t stream) {
   if (n <= 0 || !(p >= 0.f && p < 1.f) || !rng_state) return 1;
-  if (dtype != MSMD_F32 && dtype != MSMD_BF16) return 1;   // fp32 or bf16 only (no fp16 training path)
   dim3 grid((unsigned)min(((n + 3) / 4 + 255) / 256, (long)8192)), block(256);
-  if (dtype == MSMD_F32)
-    hipLaunchKernelGGL(dropout_kernel<float>, grid, block, 0, (hipStream_t)stream, (const float*)x,
-                       (const float*)residual, (float*)y, n, p, rng_state, site);
-  else
-    hipLaunchKernelGGL(dropout_kernel<bf16_t>, grid, block, 0, (hipStream_t)stream, (const bf16_t*)x,
-                       (const bf16_t*)residual, (bf16_t*)y, n, p, rng_state, site);
-  MSMD_RETURN_LAST();
+  return dispatch_dtype<float, bf16_t>(dtype, [&](auto tag) {
+    typedef MSMD_TAG_T(tag) T;
+    hipLaunchKernelGGL(dropout_kernel<T>, grid, block, 0, (hipStream_t)stream, (const T*)x, (const T*)residual, (T*)y, n, p,
+                       rng_state, site);
+    MSMD_RETURN_LAST();
+  });
 }
 
 // dz = dropout_mask(dy) * act'(z): the backward of y = dropout(act(z)) in ONE pass (mask regenerated from the same
@@ -642,15 +613,13 @@ __global__ __launch_bounds__(256) void act_bwd_dropout_kernel(const T* __restric
 extern "C" int msmd_act_bwd_dropout(const void* dy, const void* z, void* dz, long n, int act, float p,
                                     const unsigned long* rng_state, unsigned int site, int dtype, msmd_stream_t stream) {
   if (n <= 0 || !(p > 0.f && p < 1.f) || !rng_state) return 1;
-  if (dtype != MSMD_F32 && dtype != MSMD_BF16) return 1;   // fp32 or bf16 only (no fp16 training path)
   dim3 grid((unsigned)min(((n + 3) / 4 + 255) / 256, (long)8192)), block(256);
-  if (dtype == MSMD_F32)
-    hipLaunchKernelGGL(act_bwd_dropout_kernel<float>, grid, block, 0, (hipStream_t)stream, (const float*)dy,
-                       (const float*)z, (float*)dz, n, act, p, rng_state, site);
-  else
-    hipLaunchKernelGGL(act_bwd_dropout_kernel<bf16_t>, grid, block, 0, (hipStream_t)stream, (const bf16_t*)dy,
-                       (const bf16_t*)z, (bf16_t*)dz, n, act, p, rng_state, site);
-  MSMD_RETURN_LAST();
+  return dispatch_dtype<float, bf16_t>(dtype, [&](auto tag) {
+    typedef MSMD_TAG_T(tag) T;
+    hipLaunchKernelGGL(act_bwd_dropout_kernel<T>, grid, block, 0, (hipStream_t)stream, (const T*)dy, (const T*)z, (T*)dz, n,
+                       act, p, rng_state, site);
+    MSMD_RETURN_LAST();
+  });
 }
 
 // ---------------------------------------------------------------------------------------------------

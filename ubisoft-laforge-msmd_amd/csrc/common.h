@@ -255,3 +255,22 @@ template <typename T> struct Elems16;                     // elements per 16-byt
 template <> struct Elems16<float> { static constexpr int n = 4; };
 template <> struct Elems16<bf16_t> { static constexpr int n = 8; };
 template <> struct Elems16<f16_t> { static constexpr int n = 8; };
+
+// Run-time storage-type dispatch.  f(TypeTag<T>{}) for the T of the compile-time list whose MSMD_* code equals `dtype`: its
+// result (a launcher's), or 1 for a code that names none of them -- the list at a call site IS the entry's table of supported
+// types, and no code runs another type's kernel.  (gemm.hip's dispatch_code is the same fold over integer template arguments.)
+template <typename T> struct TypeTag { typedef T type; };
+template <typename T> struct DtypeCode;
+template <> struct DtypeCode<float> { static constexpr int value = MSMD_F32; };
+template <> struct DtypeCode<bf16_t> { static constexpr int value = MSMD_BF16; };
+template <> struct DtypeCode<f16_t> { static constexpr int value = MSMD_F16; };
+template <typename... Ts, typename F>
+static int dispatch_dtype(int dtype, F&& f) {
+  int r = 1;
+  (void)((dtype == DtypeCode<Ts>::value && ((r = f(TypeTag<Ts>{})), true)) || ...);
+  return r;
+}
+#define MSMD_TAG_T(tag) typename decltype(tag)::type
+// the (in, out) pairs of the converting entries (msmd_pad_cols / msmd_cast, msmd_layernorm): fp32 with every type, each
+// 16-bit type with itself -- never one 16-bit type into the other
+template <typename TI, typename TO> constexpr bool kStoragePair = sizeof(TI) == 4 || sizeof(TO) == 4 || __is_same(TI, TO);

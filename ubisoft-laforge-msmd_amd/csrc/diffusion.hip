@@ -3,10 +3,16 @@
 #include "common.h"
 
 // feats rows 1.. = [prev_motion ; x_t] ++ indicator ++ zero pad; row 0 (person token slot) is zero-filled.
+// guide_mask (nullable; keyframe in-painting of the denoiser INPUT, reference model.py:762-767: motion_in[:, idx, :] = values
+// before every denoiser call): where guide_mask[nm, t] != 0 the motion columns of frame t come from guide_values instead of
+// motion.  The mask / value pair is dense, (motion_batch, L) uint8 / (motion_batch, L, dm) fp32, so a captured launch does not
+// depend on which frames are pinned or how many; the overwrite is per clip and every CFG entry of a clip reads the same
+// overwritten input.  eps (nullable): the q-sample form of the training path (no keyframes there: the entry rejects both).
 template <typename TO>
 __global__ void pack_input_kernel(const float* __restrict__ motion, const float* __restrict__ eps,
                                   const float* __restrict__ c0, const float* __restrict__ c1,
                                   const float* __restrict__ prev, const float* __restrict__ ind,
+                                  const unsigned char* __restrict__ guide_mask, const float* __restrict__ guide_values,
                                   TO* __restrict__ feats, int L, int Lp, int dm, int Kpad, int motion_batch) {
   const int n = blockIdx.y;
   const int Tn = 1 + Lp + L;
@@ -19,58 +25,9 @@ __global__ void pack_input_kernel(const float* __restrict__ motion, const float*
     } else if (r >= Lp) {
       const int t = r - Lp;
       if (k < dm) {
-        v = motion[((long)nm * L + t) * dm + k];
-        if (eps) v = c0[nm] * v + c1[nm] * eps[((long)nm * L + t) * dm + k];
-      } else if (k == dm && ind) {
-        v = ind[(long)n * L + t];
-      }
-    }
-    feats[(long)n * Tn * Kpad + i] = from_f32<TO>(v);
-  }
-}
-
-extern "C" int msmd_denoiser_pack_input(const float* motion, const float* eps, const float* c0, const float* c1,
-                                        const float* prev_motion, const float* indicator, void* feats, int N, int L,
-                                        int Lp, int dm, int Kpad, int motion_batch, int out_dtype,
-                                        msmd_stream_t stream) {
-  if (N <= 0 || L <= 0 || Lp < 0 || dm <= 0 || Kpad < dm + (indicator ? 1 : 0) || motion_batch <= 0) return 1;
-  dim3 grid(((1 + Lp + L) * Kpad + 255) / 256, N), block(256);
-  if (out_dtype == MSMD_F32)
-    hipLaunchKernelGGL(pack_input_kernel<float>, grid, block, 0, (hipStream_t)stream, motion, eps, c0, c1, prev_motion,
-                       indicator, (float*)feats, L, Lp, dm, Kpad, motion_batch);
-  else if (out_dtype == MSMD_F16)
-    hipLaunchKernelGGL(pack_input_kernel<f16_t>, grid, block, 0, (hipStream_t)stream, motion, eps, c0, c1,
-                       prev_motion, indicator, (f16_t*)feats, L, Lp, dm, Kpad, motion_batch);
-  else
-    hipLaunchKernelGGL(pack_input_kernel<bf16_t>, grid, block, 0, (hipStream_t)stream, motion, eps, c0, c1,
-                       prev_motion, indicator, (bf16_t*)feats, L, Lp, dm, Kpad, motion_batch);
-  MSMD_RETURN_LAST();
-}
-
-// msmd_denoiser_pack_input with keyframe in-painting of the denoiser INPUT (reference model.py:762-767: motion_in[:, idx, :] =
-// values before every denoiser call): where guide_mask[nm, t] != 0 the motion columns of frame t come from guide_values
-// instead of motion.  The mask / value pair is dense, (motion_batch, L) uint8 / (motion_batch, L, dm) fp32, so a captured
-// launch does not depend on which frames are pinned or how many; the overwrite is per clip and every CFG entry of a clip
-// reads the same overwritten input.  Prev rows, the indicator column, the zero padding, the person-token row and the
-// conversion are pack_input_kernel's.
-template <typename TO>
-__global__ void pack_input_guided_kernel(const float* __restrict__ motion, const float* __restrict__ prev,
-                                         const float* __restrict__ ind, const unsigned char* __restrict__ guide_mask,
-                                         const float* __restrict__ guide_values, TO* __restrict__ feats, int L, int Lp,
-                                         int dm, int Kpad, int motion_batch) {
-  const int n = blockIdx.y;
-  const int Tn = 1 + Lp + L;
-  const int nm = n % motion_batch;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < Tn * Kpad; i += gridDim.x * blockDim.x) {
-    const int r = i / Kpad - 1, k = i % Kpad;
-    float v = 0.f;
-    if (r >= 0 && r < Lp) {
-      if (k < dm) v = prev[((long)n * Lp + r) * dm + k];
-    } else if (r >= Lp) {
-      const int t = r - Lp;
-      if (k < dm) {
         const long at = ((long)nm * L + t) * dm + k;
-        v = guide_mask[(long)nm * L + t] ? guide_values[at] : motion[at];
+        v = (guide_mask && guide_mask[(long)nm * L + t]) ? guide_values[at] : motion[at];
+        if (eps) v = c0[nm] * v + c1[nm] * eps[at];
       } else if (k == dm && ind) {
         v = ind[(long)n * L + t];
       }
@@ -84,22 +41,23 @@ extern "C" int msmd_denoiser_pack_input_guided(const float* motion, const float*
                                                const unsigned char* guide_mask, const float* guide_values, void* feats,
                                                int N, int L, int Lp, int dm, int Kpad, int motion_batch, int out_dtype,
                                                msmd_stream_t stream) {
-  if (!guide_mask)
-    return msmd_denoiser_pack_input(motion, eps, c0, c1, prev_motion, indicator, feats, N, L, Lp, dm, Kpad, motion_batch,
-                                    out_dtype, stream);
-  if (eps || !guide_values) return 1;  // the q-sample form is the training path: no keyframes there
+  if (guide_mask && (eps || !guide_values)) return 1;  // the q-sample form is the training path: no keyframes there
   if (N <= 0 || L <= 0 || Lp < 0 || dm <= 0 || Kpad < dm + (indicator ? 1 : 0) || motion_batch <= 0) return 1;
   dim3 grid(((1 + Lp + L) * Kpad + 255) / 256, N), block(256);
-  if (out_dtype == MSMD_F32)
-    hipLaunchKernelGGL(pack_input_guided_kernel<float>, grid, block, 0, (hipStream_t)stream, motion, prev_motion,
-                       indicator, guide_mask, guide_values, (float*)feats, L, Lp, dm, Kpad, motion_batch);
-  else if (out_dtype == MSMD_F16)
-    hipLaunchKernelGGL(pack_input_guided_kernel<f16_t>, grid, block, 0, (hipStream_t)stream, motion, prev_motion,
-                       indicator, guide_mask, guide_values, (f16_t*)feats, L, Lp, dm, Kpad, motion_batch);
-  else
-    hipLaunchKernelGGL(pack_input_guided_kernel<bf16_t>, grid, block, 0, (hipStream_t)stream, motion, prev_motion,
-                       indicator, guide_mask, guide_values, (bf16_t*)feats, L, Lp, dm, Kpad, motion_batch);
-  MSMD_RETURN_LAST();
+  return dispatch_dtype<float, f16_t, bf16_t>(out_dtype, [&](auto tag) {
+    typedef MSMD_TAG_T(tag) TO;
+    hipLaunchKernelGGL(pack_input_kernel<TO>, grid, block, 0, (hipStream_t)stream, motion, eps, c0, c1, prev_motion,
+                       indicator, guide_mask, guide_values, (TO*)feats, L, Lp, dm, Kpad, motion_batch);
+    MSMD_RETURN_LAST();
+  });
+}
+
+extern "C" int msmd_denoiser_pack_input(const float* motion, const float* eps, const float* c0, const float* c1,
+                                        const float* prev_motion, const float* indicator, void* feats, int N, int L,
+                                        int Lp, int dm, int Kpad, int motion_batch, int out_dtype,
+                                        msmd_stream_t stream) {
+  return msmd_denoiser_pack_input_guided(motion, eps, c0, c1, prev_motion, indicator, nullptr, nullptr, feats, N, L, Lp,
+                                         dm, Kpad, motion_batch, out_dtype, stream);
 }
 
 // x (N, T, d) += pe (T, d); row 0 = tok0 (N, d) + row0_add (d, optional) + pe[0]  (row 0 of x is overwritten)
@@ -158,25 +116,20 @@ extern "C" int msmd_add_pe_token(void* x, const float* pe, const void* tok0, con
   if (N <= 0 || T <= 0 || d <= 0 || !tok0) return 1;
   if (dtype != MSMD_F32 && (d & 7) == 0 && !(((uintptr_t)x | (uintptr_t)pe | (uintptr_t)tok0 | (uintptr_t)row0_add) & 15)) {
     dim3 grid8((T * (d >> 3) + 255) / 256, N);
-    if (dtype == MSMD_F16)
-      hipLaunchKernelGGL(add_pe_token_v8_kernel<f16_t>, grid8, dim3(256), 0, (hipStream_t)stream, (f16_t*)x, pe,
-                         (const f16_t*)tok0, (const f16_t*)row0_add, T, d);
-    else
-      hipLaunchKernelGGL(add_pe_token_v8_kernel<bf16_t>, grid8, dim3(256), 0, (hipStream_t)stream, (bf16_t*)x, pe,
-                         (const bf16_t*)tok0, (const bf16_t*)row0_add, T, d);
-    MSMD_RETURN_LAST();
+    return dispatch_dtype<f16_t, bf16_t>(dtype, [&](auto tag) {
+      typedef MSMD_TAG_T(tag) TX;
+      hipLaunchKernelGGL(add_pe_token_v8_kernel<TX>, grid8, dim3(256), 0, (hipStream_t)stream, (TX*)x, pe,
+                         (const TX*)tok0, (const TX*)row0_add, T, d);
+      MSMD_RETURN_LAST();
+    });
   }
   dim3 grid((T * d + 255) / 256, N), block(256);
-  if (dtype == MSMD_F32)
-    hipLaunchKernelGGL(add_pe_token_kernel<float>, grid, block, 0, (hipStream_t)stream, (float*)x, pe,
-                       (const float*)tok0, (const float*)row0_add, T, d);
-  else if (dtype == MSMD_F16)
-    hipLaunchKernelGGL(add_pe_token_kernel<f16_t>, grid, block, 0, (hipStream_t)stream, (f16_t*)x, pe,
-                       (const f16_t*)tok0, (const f16_t*)row0_add, T, d);
-  else
-    hipLaunchKernelGGL(add_pe_token_kernel<bf16_t>, grid, block, 0, (hipStream_t)stream, (bf16_t*)x, pe,
-                       (const bf16_t*)tok0, (const bf16_t*)row0_add, T, d);
-  MSMD_RETURN_LAST();
+  return dispatch_dtype<float, f16_t, bf16_t>(dtype, [&](auto tag) {
+    typedef MSMD_TAG_T(tag) TX;
+    hipLaunchKernelGGL(add_pe_token_kernel<TX>, grid, block, 0, (hipStream_t)stream, (TX*)x, pe, (const TX*)tok0,
+                       (const TX*)row0_add, T, d);
+    MSMD_RETURN_LAST();
+  });
 }
 
 // out = dyn + sum_b alpha_b * static_b (dims < dm-3, or all dims when use_head_alpha & 1) ; + sum_b static_b (last 3
@@ -205,59 +158,101 @@ extern "C" int msmd_heads_static_mix(const void* dec, long ld_dec, const void* s
                                      int nb, int stat_batch, int use_head_alpha, int dtype, msmd_stream_t stream) {
   if (N <= 0 || L <= 0 || dm <= 3 || nb <= 0 || stat_batch <= 0) return 1;
   dim3 grid((L * dm + 255) / 256, N), block(256);
-  if (dtype == MSMD_F32)
-    hipLaunchKernelGGL(heads_mix_kernel<float>, grid, block, 0, (hipStream_t)stream, (const float*)dec, ld_dec,
-                       (const float*)stat, out, L, dm, nb, stat_batch, use_head_alpha);
-  else if (dtype == MSMD_F16)
-    hipLaunchKernelGGL(heads_mix_kernel<f16_t>, grid, block, 0, (hipStream_t)stream, (const f16_t*)dec, ld_dec,
-                       (const f16_t*)stat, out, L, dm, nb, stat_batch, use_head_alpha);
-  else
-    hipLaunchKernelGGL(heads_mix_kernel<bf16_t>, grid, block, 0, (hipStream_t)stream, (const bf16_t*)dec, ld_dec,
-                       (const bf16_t*)stat, out, L, dm, nb, stat_batch, use_head_alpha);
-  MSMD_RETURN_LAST();
+  return dispatch_dtype<float, f16_t, bf16_t>(dtype, [&](auto tag) {
+    typedef MSMD_TAG_T(tag) T;
+    hipLaunchKernelGGL(heads_mix_kernel<T>, grid, block, 0, (hipStream_t)stream, (const T*)dec, ld_dec, (const T*)stat,
+                       out, L, dm, nb, stat_batch, use_head_alpha);
+    MSMD_RETURN_LAST();
+  });
 }
 
-// CFG combine + DDPM posterior step, in place on x (B, L, dm).  The reference accumulates theta IN PLACE
-// into entry 0's slice (model.py:407-415): `results[0]` IS the running theta, so
+// ---------------------------------------------------------------------------------------------------
+// The sampler's step kernels (DDPM, few-step solver, solver + diagnostic streams; each with host scalars or, kDev, with the
+// per-step coefficients read from device memory) share what follows: the element's place, the CFG combine, the solver
+// update and the grid.  One grid-stride loop over the B L dm elements of the last L frames each; fp32 throughout.
+struct StepElem {
+  int b, t, k;     // batch entry, frame among the last L, motion column of element i
+  long off;        // the element inside entry 0's (B, Lp + L, dm) slice of res
+  long stride_e;   // from one CFG entry's slice to the next
+};
+__device__ __forceinline__ StepElem step_elem(long i, int B, int L, int Lp, int dm) {
+  const int b = (int)(i / ((long)L * dm));
+  const int rem = (int)(i % ((long)L * dm));
+  const int t = rem / dm, k = rem % dm;
+  const long stride_e = (long)B * (Lp + L) * dm;
+  const long off = ((long)b * (Lp + L) + Lp + t) * dm + k;
+  return StepElem{b, t, k, off, stride_e};
+}
+static dim3 step_grid(long total) { return dim3((unsigned)min((total + 255) / 256, (long)2048)); }
+
+// CFG combine.  The reference accumulates theta IN PLACE into entry 0's slice (model.py:407-415): `results[0]` IS the
+// running theta, so
 //   incremental: theta += s_e * (r[e+1] - r[e])   with r[0] := running theta when e == 0,
 //   independent: theta += s_e * (r[e+1] - theta)  (later terms see the already-updated entry 0).
+__device__ __forceinline__ float cfg_theta(const float* __restrict__ res, const float* __restrict__ scales,
+                                           const StepElem& s, int n_entries, int mode) {
+  const long stride_e = s.stride_e, off = s.off;
+  float theta = res[off];
+  for (int e = 0; e < n_entries - 1; ++e) {
+    const float hi = res[(e + 1) * stride_e + off];
+    const float lo = (mode == 1 || e == 0) ? theta : res[e * stride_e + off];
+    theta += scales[e] * (hi - lo);
+  }
+  return theta;
+}
+
+// CFG combine + DDPM posterior step, in place on x (B, L, dm).  kDev: (c0, c1, sigma) = coefs[0..2], the triple
+// msmd_sampler_step_select left on the device (a captured step body takes no per-step host scalars).
+struct DdpmCoefs {
+  float c0, c1, sigma;
+};
+
+template <bool kDev>
 __global__ void cfg_ddpm_kernel(float* __restrict__ x, const float* __restrict__ res, const float* __restrict__ z,
-                                const float* __restrict__ scales, int n_entries, int B, int L, int Lp, int dm,
-                                int mode, int target, float c0, float c1, float sigma) {
+                                const float* __restrict__ scales, const float* __restrict__ coefs, DdpmCoefs c,
+                                int n_entries, int B, int L, int Lp, int dm, int mode, int target) {
+  if (kDev) c = DdpmCoefs{coefs[0], coefs[1], coefs[2]};
+  const float c0 = c.c0, c1 = c.c1, sigma = c.sigma;
   const long total = (long)B * L * dm;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const int b = (int)(i / ((long)L * dm));
-    const int rem = (int)(i % ((long)L * dm));
-    const int t = rem / dm, k = rem % dm;
-    const long stride_e = (long)B * (Lp + L) * dm;
-    const long off = ((long)b * (Lp + L) + Lp + t) * dm + k;
-    float theta = res[off];
-    for (int e = 0; e < n_entries - 1; ++e) {
-      const float hi = res[(e + 1) * stride_e + off];
-      const float lo = (mode == 1 || e == 0) ? theta : res[e * stride_e + off];
-      theta += scales[e] * (hi - lo);
-    }
+    const float theta = cfg_theta(res, scales, step_elem(i, B, L, Lp, dm), n_entries, mode);
     const float xt = x[i];
     const float zz = z ? z[i] : 0.f;
     x[i] = (target == 0) ? (c0 * xt + c1 * theta + sigma * zz) : (c0 * (xt - c1 * theta) + sigma * zz);
   }
 }
 
+static int launch_cfg_ddpm(bool dev, float* x, const float* res, const float* z, const float* scales,
+                           const float* coefs, DdpmCoefs c, int n_entries, int B, int L, int Lp, int dm, int mode,
+                           int target, msmd_stream_t stream) {
+  if (B <= 0 || L <= 0 || dm <= 0 || n_entries < 1 || (n_entries > 1 && !scales) || (dev && !coefs)) return 1;
+  const dim3 grid = step_grid((long)B * L * dm), block(256);
+  if (dev)
+    hipLaunchKernelGGL(cfg_ddpm_kernel<true>, grid, block, 0, (hipStream_t)stream, x, res, z, scales, coefs, c,
+                       n_entries, B, L, Lp, dm, mode, target);
+  else
+    hipLaunchKernelGGL(cfg_ddpm_kernel<false>, grid, block, 0, (hipStream_t)stream, x, res, z, scales, coefs, c,
+                       n_entries, B, L, Lp, dm, mode, target);
+  MSMD_RETURN_LAST();
+}
+
 extern "C" int msmd_cfg_ddpm_step(float* x, const float* res, const float* z, const float* scales, int n_entries,
                                   int B, int L, int Lp, int dm, int mode, int target, float c0, float c1, float sigma,
                                   msmd_stream_t stream) {
-  if (B <= 0 || L <= 0 || dm <= 0 || n_entries < 1 || (n_entries > 1 && !scales)) return 1;
-  const long total = (long)B * L * dm;
-  dim3 grid((unsigned)min((total + 255) / 256, (long)2048)), block(256);
-  hipLaunchKernelGGL(cfg_ddpm_kernel, grid, block, 0, (hipStream_t)stream, x, res, z, scales, n_entries, B, L, Lp, dm,
-                     mode, target, c0, c1, sigma);
-  MSMD_RETURN_LAST();
+  return launch_cfg_ddpm(false, x, res, z, scales, nullptr, DdpmCoefs{c0, c1, sigma}, n_entries, B, L, Lp, dm, mode,
+                         target, stream);
+}
+
+extern "C" int msmd_cfg_ddpm_step_dev(float* x, const float* res, const float* z, const float* scales,
+                                      const float* coefs, int n_entries, int B, int L, int Lp, int dm, int mode,
+                                      int target, msmd_stream_t stream) {
+  return launch_cfg_ddpm(true, x, res, z, scales, coefs, DdpmCoefs{}, n_entries, B, L, Lp, dm, mode, target, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------
 // hipGraph support for the sampler: the captured step body must not take per-step host scalars, so the step
 // index lives on the device.  step_select copies row t of the step-embedding table and the (c0, c1, sigma)
-// triple of step t into fixed buffers and then decrements t; cfg_ddpm_dev reads the triple from there.
+// triple of step t into fixed buffers and then decrements t; the kDev step kernels read the triple from there.
 // NC = 3 for the DDPM triple, 6 for a few-step solver row (msmd_sampler_solver_select).
 template <typename T, int NC = 3>
 __global__ void step_select_kernel(const T* __restrict__ emb_all, const float* __restrict__ coef_table,
@@ -270,58 +265,31 @@ __global__ void step_select_kernel(const T* __restrict__ emb_all, const float* _
   if (threadIdx.x == 0) *t_dev = t - 1;
 }
 
+template <int NC>
+static int launch_step_select(const void* emb_all, const float* coef_table, int* t_dev, void* emb_row, float* coefs,
+                              int d, int dtype, msmd_stream_t stream) {
+  if (d <= 0 || !emb_all || !coef_table || !t_dev || !emb_row || !coefs) return 1;
+  return dispatch_dtype<float, f16_t, bf16_t>(dtype, [&](auto tag) {
+    typedef MSMD_TAG_T(tag) T;
+    hipLaunchKernelGGL((step_select_kernel<T, NC>), dim3(1), dim3(256), 0, (hipStream_t)stream, (const T*)emb_all,
+                       coef_table, t_dev, (T*)emb_row, coefs, d);
+    MSMD_RETURN_LAST();
+  });
+}
+
 extern "C" int msmd_sampler_step_select(const void* emb_all, const float* coef_table, int* t_dev, void* emb_row,
                                         float* coefs, int d, int dtype, msmd_stream_t stream) {
-  if (d <= 0 || !emb_all || !coef_table || !t_dev || !emb_row || !coefs) return 1;
-  if (dtype == MSMD_F32)
-    hipLaunchKernelGGL(step_select_kernel<float>, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)emb_all,
-                       coef_table, t_dev, (float*)emb_row, coefs, d);
-  else if (dtype == MSMD_F16)
-    hipLaunchKernelGGL(step_select_kernel<f16_t>, dim3(1), dim3(256), 0, (hipStream_t)stream, (const f16_t*)emb_all,
-                       coef_table, t_dev, (f16_t*)emb_row, coefs, d);
-  else
-    hipLaunchKernelGGL(step_select_kernel<bf16_t>, dim3(1), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)emb_all,
-                       coef_table, t_dev, (bf16_t*)emb_row, coefs, d);
-  MSMD_RETURN_LAST();
+  return launch_step_select<3>(emb_all, coef_table, t_dev, emb_row, coefs, d, dtype, stream);
 }
 
-__global__ void cfg_ddpm_dev_kernel(float* __restrict__ x, const float* __restrict__ res, const float* __restrict__ z,
-                                    const float* __restrict__ scales, const float* __restrict__ coefs, int n_entries,
-                                    int B, int L, int Lp, int dm, int mode, int target) {
-  const float c0 = coefs[0], c1 = coefs[1], sigma = coefs[2];
-  const long total = (long)B * L * dm;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const int b = (int)(i / ((long)L * dm));
-    const int rem = (int)(i % ((long)L * dm));
-    const int t = rem / dm, k = rem % dm;
-    const long stride_e = (long)B * (Lp + L) * dm;
-    const long off = ((long)b * (Lp + L) + Lp + t) * dm + k;
-    float theta = res[off];
-    for (int e = 0; e < n_entries - 1; ++e) {
-      const float hi = res[(e + 1) * stride_e + off];
-      const float lo = (mode == 1 || e == 0) ? theta : res[e * stride_e + off];
-      theta += scales[e] * (hi - lo);
-    }
-    const float xt = x[i];
-    const float zz = z ? z[i] : 0.f;
-    x[i] = (target == 0) ? (c0 * xt + c1 * theta + sigma * zz) : (c0 * (xt - c1 * theta) + sigma * zz);
-  }
-}
-
-extern "C" int msmd_cfg_ddpm_step_dev(float* x, const float* res, const float* z, const float* scales,
-                                      const float* coefs, int n_entries, int B, int L, int Lp, int dm, int mode,
-                                      int target, msmd_stream_t stream) {
-  if (B <= 0 || L <= 0 || dm <= 0 || n_entries < 1 || (n_entries > 1 && !scales) || !coefs) return 1;
-  const long total = (long)B * L * dm;
-  dim3 grid((unsigned)min((total + 255) / 256, (long)2048)), block(256);
-  hipLaunchKernelGGL(cfg_ddpm_dev_kernel, grid, block, 0, (hipStream_t)stream, x, res, z, scales, coefs, n_entries, B,
-                     L, Lp, dm, mode, target);
-  MSMD_RETURN_LAST();
+extern "C" int msmd_sampler_solver_select(const void* emb_tab, const float* coef_tab, int* i_dev, void* emb_row,
+                                          float* coefs, int d, int dtype, msmd_stream_t stream) {
+  return launch_step_select<6>(emb_tab, coef_tab, i_dev, emb_row, coefs, d, dtype, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Few-step solvers (DDIM(eta), DPM-Solver++(2M)) in data-prediction form.  The CFG combine is the arithmetic of
-// cfg_ddpm_kernel in the same order; then, with the six per-step scalars (p0, p1, ax, ath, b1, sigma) folded on the
+// Few-step solvers (DDIM(eta), DPM-Solver++(2M)) in data-prediction form.  The CFG combine is cfg_theta, as in
+// cfg_ddpm_kernel; then, with the six per-step scalars (p0, p1, ax, ath, b1, sigma) folded on the
 // host in float64 (sampler.solver_table):
 //   D = p0 x + p1 theta                       (the x0 prediction: p0 = 0, p1 = 1 for target 'sample')
 //   x <- ax x + ath theta + b1 d_prev + sigma z,   d_prev <- D
@@ -331,6 +299,11 @@ extern "C" int msmd_cfg_ddpm_step_dev(float* x, const float* res, const float* z
 struct SolverCoefs {
   float p0, p1, ax, ath, b1, sigma;
 };
+// -> the new x; D = the x0 prediction (the new d_prev)
+__device__ __forceinline__ float solver_update(const SolverCoefs& c, float xt, float theta, float dp, float zz, float& D) {
+  D = c.p0 * xt + c.p1 * theta;
+  return c.ax * xt + c.ath * theta + c.b1 * dp + c.sigma * zz;
+}
 
 template <bool kDev>
 __global__ void cfg_solver_kernel(float* __restrict__ x, const float* __restrict__ res, const float* __restrict__ z,
@@ -340,22 +313,12 @@ __global__ void cfg_solver_kernel(float* __restrict__ x, const float* __restrict
   if (kDev) c = SolverCoefs{coefs[0], coefs[1], coefs[2], coefs[3], coefs[4], coefs[5]};
   const long total = (long)B * L * dm;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const int b = (int)(i / ((long)L * dm));
-    const int rem = (int)(i % ((long)L * dm));
-    const int t = rem / dm, k = rem % dm;
-    const long stride_e = (long)B * (Lp + L) * dm;
-    const long off = ((long)b * (Lp + L) + Lp + t) * dm + k;
-    float theta = res[off];
-    for (int e = 0; e < n_entries - 1; ++e) {
-      const float hi = res[(e + 1) * stride_e + off];
-      const float lo = (mode == 1 || e == 0) ? theta : res[e * stride_e + off];
-      theta += scales[e] * (hi - lo);
-    }
+    const float theta = cfg_theta(res, scales, step_elem(i, B, L, Lp, dm), n_entries, mode);
     const float xt = x[i];
     const float dp = d_prev[i];
     const float zz = z ? z[i] : 0.f;
-    const float D = c.p0 * xt + c.p1 * theta;
-    x[i] = c.ax * xt + c.ath * theta + c.b1 * dp + c.sigma * zz;
+    float D;
+    x[i] = solver_update(c, xt, theta, dp, zz, D);
     d_prev[i] = D;
   }
 }
@@ -366,8 +329,7 @@ static int launch_cfg_solver(bool dev, float* x, const float* res, const float* 
   if (B <= 0 || L <= 0 || dm <= 0 || Lp < 0 || n_entries < 1 || (n_entries > 1 && !scales) || !x || !res || !d_prev ||
       (dev && !coefs))
     return 1;
-  const long total = (long)B * L * dm;
-  dim3 grid((unsigned)min((total + 255) / 256, (long)2048)), block(256);
+  const dim3 grid = step_grid((long)B * L * dm), block(256);
   if (dev)
     hipLaunchKernelGGL(cfg_solver_kernel<true>, grid, block, 0, (hipStream_t)stream, x, res, z, scales, d_prev, coefs,
                        c, n_entries, B, L, Lp, dm, mode);
@@ -392,12 +354,14 @@ extern "C" int msmd_cfg_solver_step_dev(float* x, const float* res, const float*
 }
 
 // ---------------------------------------------------------------------------------------------------
-// sample_separate on a few-step solver: the CFG combine and solver update of cfg_solver_kernel (the same two lines, so x and
+// sample_separate on a few-step solver: the CFG combine and solver update of cfg_solver_kernel (solver_update itself, so x and
 // d_prev have its bits under the same res) plus, in the same launch, the three diagnostic streams of reference
 // model.py:442-651.  Per element of the last L frames and per CFG entry e (row n = e B + b of dec / res):
 //   dyn_e = dec[n][k],  static_e = sum_b a_{e,b} stat_b[k]  (the loop of heads_mix_kernel: same order, plain sum of the bases
 //   for the last 3 columns without use_head_alpha & 1, sigmoid under use_head_alpha & 2),  alpha_e = a_{e,k} for k < nb;
-// each stream is CFG-combined across entries by the in-place rule of cfg_ddpm_kernel.  res is the output of
+// each stream is CFG-combined across entries by the in-place rule of cfg_theta.  The four streams share ONE pass over the
+// entries and over scales, so theta is combined in that loop too and not by a call (which would read scales twice): its
+// lines there are cfg_theta's, entry for entry.  res is the output of
 // msmd_heads_static_mix (after msmd_dynamic_threshold when that is on), so theta is what the plain solver step sees.
 //   cum_static += ath theta_static   (the step's coefficient on theta stands where the DDPM chain has c1, model.py:590-618)
 //   theta_dyn (B, L, dm) is overwritten;  theta_alpha goes to rows [slot B, (slot + 1) B) of an (n_slots B, L, nb) buffer,
@@ -421,11 +385,7 @@ __global__ void cfg_streams_kernel(float* __restrict__ x, const float* __restric
   if (slot < 0 || slot >= n_slots) slot = n_slots - 1;   // a counter outside the loop's range must not write out of bounds
   const long total = (long)B * L * dm;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const int b = (int)(i / ((long)L * dm));
-    const int rem = (int)(i % ((long)L * dm));
-    const int t = rem / dm, k = rem % dm;
-    const long stride_e = (long)B * (Lp + L) * dm;
-    const long off = ((long)b * (Lp + L) + Lp + t) * dm + k;
+    const auto [b, t, k, off, stride_e] = step_elem(i, B, L, Lp, dm);
     const bool weighted = (use_head_alpha & 1) || (k < dm - 3);
     float theta = 0.f, th_static = 0.f, th_dyn = 0.f, th_alpha = 0.f;
     float lo_static = 0.f, lo_dyn = 0.f, lo_alpha = 0.f;   // entry e's own values while entry e + 1 is combined
@@ -448,7 +408,7 @@ __global__ void cfg_streams_kernel(float* __restrict__ x, const float* __restric
       } else {
         const float sc = scales[e - 1];
         const bool running = (mode == 1 || e == 1);        // lo = the running theta (entry 0's slice, updated in place)
-        const float hi = res[e * stride_e + off];
+        const float hi = res[e * stride_e + off];                          // these three lines: cfg_theta's, at its e + 1
         const float lo = running ? theta : res[(e - 1) * stride_e + off];
         theta += sc * (hi - lo);
         th_static += sc * (st - (running ? th_static : lo_static));
@@ -460,32 +420,13 @@ __global__ void cfg_streams_kernel(float* __restrict__ x, const float* __restric
     const float xt = x[i];
     const float dp = d_prev[i];
     const float zz = z ? z[i] : 0.f;
-    const float D = c.p0 * xt + c.p1 * theta;
-    x[i] = c.ax * xt + c.ath * theta + c.b1 * dp + c.sigma * zz;
+    float D;
+    x[i] = solver_update(c, xt, theta, dp, zz, D);
     d_prev[i] = D;
     cum_static[i] += c.ath * th_static;
     theta_dyn[i] = th_dyn;
     if (k < nb) theta_alpha[(((long)slot * B + b) * L + t) * nb + k] = th_alpha;
   }
-}
-
-template <typename T>
-static int launch_cfg_streams_t(bool dev, float* x, const float* res, const void* dec, long ld_dec, const void* stat,
-                                const float* z, const float* scales, float* d_prev, float* cum_static, float* theta_dyn,
-                                float* theta_alpha, const float* coefs, const int* step_dev, SolverCoefs c, int slot,
-                                int n_slots, int n_entries, int B, int L, int Lp, int dm, int nb, int stat_batch,
-                                int use_head_alpha, int mode, msmd_stream_t stream) {
-  const long total = (long)B * L * dm;
-  dim3 grid((unsigned)min((total + 255) / 256, (long)2048)), block(256);
-  if (dev)
-    hipLaunchKernelGGL((cfg_streams_kernel<T, true>), grid, block, 0, (hipStream_t)stream, x, res, (const T*)dec, ld_dec,
-                       (const T*)stat, z, scales, d_prev, cum_static, theta_dyn, theta_alpha, coefs, step_dev, c, slot,
-                       n_slots, n_entries, B, L, Lp, dm, nb, stat_batch, use_head_alpha, mode);
-  else
-    hipLaunchKernelGGL((cfg_streams_kernel<T, false>), grid, block, 0, (hipStream_t)stream, x, res, (const T*)dec, ld_dec,
-                       (const T*)stat, z, scales, d_prev, cum_static, theta_dyn, theta_alpha, coefs, step_dev, c, slot,
-                       n_slots, n_entries, B, L, Lp, dm, nb, stat_batch, use_head_alpha, mode);
-  MSMD_RETURN_LAST();
 }
 
 static int launch_cfg_streams(bool dev, float* x, const float* res, const void* dec, long ld_dec, const void* stat,
@@ -498,19 +439,19 @@ static int launch_cfg_streams(bool dev, float* x, const float* res, const void* 
       (stat_batch != B && stat_batch != 1 && stat_batch != n_entries * B) || n_slots < 1 ||
       (dev ? (!coefs || !step_dev) : (slot < 0 || slot >= n_slots)))
     return 1;
-  if (dtype == MSMD_F32)
-    return launch_cfg_streams_t<float>(dev, x, res, dec, ld_dec, stat, z, scales, d_prev, cum_static, theta_dyn,
-                                       theta_alpha, coefs, step_dev, c, slot, n_slots, n_entries, B, L, Lp, dm, nb,
-                                       stat_batch, use_head_alpha, mode, stream);
-  if (dtype == MSMD_F16)
-    return launch_cfg_streams_t<f16_t>(dev, x, res, dec, ld_dec, stat, z, scales, d_prev, cum_static, theta_dyn,
-                                       theta_alpha, coefs, step_dev, c, slot, n_slots, n_entries, B, L, Lp, dm, nb,
-                                       stat_batch, use_head_alpha, mode, stream);
-  if (dtype == MSMD_BF16)
-    return launch_cfg_streams_t<bf16_t>(dev, x, res, dec, ld_dec, stat, z, scales, d_prev, cum_static, theta_dyn,
-                                        theta_alpha, coefs, step_dev, c, slot, n_slots, n_entries, B, L, Lp, dm, nb,
-                                        stat_batch, use_head_alpha, mode, stream);
-  return 1;
+  const dim3 grid = step_grid((long)B * L * dm), block(256);
+  return dispatch_dtype<float, f16_t, bf16_t>(dtype, [&](auto tag) {
+    typedef MSMD_TAG_T(tag) T;
+    if (dev)
+      hipLaunchKernelGGL((cfg_streams_kernel<T, true>), grid, block, 0, (hipStream_t)stream, x, res, (const T*)dec, ld_dec,
+                         (const T*)stat, z, scales, d_prev, cum_static, theta_dyn, theta_alpha, coefs, step_dev, c, slot,
+                         n_slots, n_entries, B, L, Lp, dm, nb, stat_batch, use_head_alpha, mode);
+    else
+      hipLaunchKernelGGL((cfg_streams_kernel<T, false>), grid, block, 0, (hipStream_t)stream, x, res, (const T*)dec, ld_dec,
+                         (const T*)stat, z, scales, d_prev, cum_static, theta_dyn, theta_alpha, coefs, step_dev, c, slot,
+                         n_slots, n_entries, B, L, Lp, dm, nb, stat_batch, use_head_alpha, mode);
+    MSMD_RETURN_LAST();
+  });
 }
 
 extern "C" int msmd_cfg_streams_step(float* x, const float* res, const void* dec, long ld_dec, const void* stat,
@@ -535,21 +476,6 @@ extern "C" int msmd_cfg_streams_step_dev(float* x, const float* res, const void*
                             mode, dtype, stream);
 }
 
-extern "C" int msmd_sampler_solver_select(const void* emb_tab, const float* coef_tab, int* i_dev, void* emb_row,
-                                          float* coefs, int d, int dtype, msmd_stream_t stream) {
-  if (d <= 0 || !emb_tab || !coef_tab || !i_dev || !emb_row || !coefs) return 1;
-  if (dtype == MSMD_F32)
-    hipLaunchKernelGGL((step_select_kernel<float, 6>), dim3(1), dim3(256), 0, (hipStream_t)stream,
-                       (const float*)emb_tab, coef_tab, i_dev, (float*)emb_row, coefs, d);
-  else if (dtype == MSMD_F16)
-    hipLaunchKernelGGL((step_select_kernel<f16_t, 6>), dim3(1), dim3(256), 0, (hipStream_t)stream,
-                       (const f16_t*)emb_tab, coef_tab, i_dev, (f16_t*)emb_row, coefs, d);
-  else
-    hipLaunchKernelGGL((step_select_kernel<bf16_t, 6>), dim3(1), dim3(256), 0, (hipStream_t)stream,
-                       (const bf16_t*)emb_tab, coef_tab, i_dev, (bf16_t*)emb_row, coefs, d);
-  MSMD_RETURN_LAST();
-}
-
 // ---------------------------------------------------------------------------------------------------
 template <typename TI, typename TO>
 __global__ void pad_cols_kernel(const TI* __restrict__ x, TO* __restrict__ y, long rows, int ci, int co) {
@@ -566,31 +492,19 @@ extern "C" int msmd_pad_cols(const void* x, void* y, long rows, int cols_in, int
   if (rows <= 0 || cols_in <= 0 || cols_out <= 0) return 1;
   const long total = rows * cols_out;
   dim3 grid((unsigned)min((total + 255) / 256, (long)4096)), block(256);
-  hipStream_t st = (hipStream_t)stream;
-  if (in_dtype == MSMD_F32 && out_dtype == MSMD_F32)
-    hipLaunchKernelGGL((pad_cols_kernel<float, float>), grid, block, 0, st, (const float*)x, (float*)y, rows, cols_in,
-                       cols_out);
-  else if (in_dtype == MSMD_F32 && out_dtype == MSMD_BF16)
-    hipLaunchKernelGGL((pad_cols_kernel<float, bf16_t>), grid, block, 0, st, (const float*)x, (bf16_t*)y, rows,
-                       cols_in, cols_out);
-  else if (in_dtype == MSMD_BF16 && out_dtype == MSMD_F32)
-    hipLaunchKernelGGL((pad_cols_kernel<bf16_t, float>), grid, block, 0, st, (const bf16_t*)x, (float*)y, rows,
-                       cols_in, cols_out);
-  else if (in_dtype == MSMD_F32 && out_dtype == MSMD_F16)
-    hipLaunchKernelGGL((pad_cols_kernel<float, f16_t>), grid, block, 0, st, (const float*)x, (f16_t*)y, rows,
-                       cols_in, cols_out);
-  else if (in_dtype == MSMD_F16 && out_dtype == MSMD_F32)
-    hipLaunchKernelGGL((pad_cols_kernel<f16_t, float>), grid, block, 0, st, (const f16_t*)x, (float*)y, rows,
-                       cols_in, cols_out);
-  else if (in_dtype == MSMD_F16 && out_dtype == MSMD_F16)
-    hipLaunchKernelGGL((pad_cols_kernel<f16_t, f16_t>), grid, block, 0, st, (const f16_t*)x, (f16_t*)y, rows,
-                       cols_in, cols_out);
-  else if (in_dtype == MSMD_BF16 && out_dtype == MSMD_BF16)
-    hipLaunchKernelGGL((pad_cols_kernel<bf16_t, bf16_t>), grid, block, 0, st, (const bf16_t*)x, (bf16_t*)y, rows,
-                       cols_in, cols_out);
-  else
-    return 1;
-  MSMD_RETURN_LAST();
+  return dispatch_dtype<float, f16_t, bf16_t>(in_dtype, [&](auto ti) {
+    return dispatch_dtype<float, f16_t, bf16_t>(out_dtype, [&](auto to) {
+      typedef MSMD_TAG_T(ti) TI;
+      typedef MSMD_TAG_T(to) TO;
+      if constexpr (kStoragePair<TI, TO>) {
+        hipLaunchKernelGGL((pad_cols_kernel<TI, TO>), grid, block, 0, (hipStream_t)stream, (const TI*)x, (TO*)y, rows,
+                           cols_in, cols_out);
+        MSMD_RETURN_LAST();
+      } else {
+        return 1;
+      }
+    });
+  });
 }
 
 extern "C" int msmd_cast(const void* x, void* y, long n, int in_dtype, int out_dtype, msmd_stream_t stream) {

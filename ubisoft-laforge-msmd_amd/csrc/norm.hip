@@ -303,26 +303,20 @@ extern "C" int msmd_layernorm(const void* x, const void* residual, const float* 
                               int out_dtype, msmd_stream_t stream) {
   if (rows <= 0 || cols <= 0 || (cols & 3) || !x || !y || !gamma || !beta) return 1;
   hipStream_t st = (hipStream_t)stream;
-  if (in_dtype == MSMD_F32 && out_dtype == MSMD_F32)
-    return launch_ln<float, float>(x, residual, gamma, beta, post_add, y, rows, cols, eps, act, st);
-  if (in_dtype == out_dtype && (in_dtype == MSMD_BF16 || in_dtype == MSMD_F16) && act == 0 && !post_add) {   // any other code (MSMD_F16X2, junk) falls through to `return 1`
-    const bool took = in_dtype == MSMD_BF16 ? launch_ln16<bf16_t>(x, residual, gamma, beta, y, rows, cols, eps, st, nullptr, nullptr)
-                                            : launch_ln16<f16_t>(x, residual, gamma, beta, y, rows, cols, eps, st, nullptr, nullptr);
-    if (took) MSMD_RETURN_LAST();
-  }
-  if (in_dtype == MSMD_BF16 && out_dtype == MSMD_BF16)
-    return launch_ln<bf16_t, bf16_t>(x, residual, gamma, beta, post_add, y, rows, cols, eps, act, st);
-  if (in_dtype == MSMD_BF16 && out_dtype == MSMD_F32)
-    return launch_ln<bf16_t, float>(x, residual, gamma, beta, post_add, y, rows, cols, eps, act, st);
-  if (in_dtype == MSMD_F32 && out_dtype == MSMD_BF16)
-    return launch_ln<float, bf16_t>(x, residual, gamma, beta, post_add, y, rows, cols, eps, act, st);
-  if (in_dtype == MSMD_F16 && out_dtype == MSMD_F16)
-    return launch_ln<f16_t, f16_t>(x, residual, gamma, beta, post_add, y, rows, cols, eps, act, st);
-  if (in_dtype == MSMD_F16 && out_dtype == MSMD_F32)
-    return launch_ln<f16_t, float>(x, residual, gamma, beta, post_add, y, rows, cols, eps, act, st);
-  if (in_dtype == MSMD_F32 && out_dtype == MSMD_F16)
-    return launch_ln<float, f16_t>(x, residual, gamma, beta, post_add, y, rows, cols, eps, act, st);
-  return 1;
+  return dispatch_dtype<float, bf16_t, f16_t>(in_dtype, [&](auto ti) {
+    return dispatch_dtype<float, bf16_t, f16_t>(out_dtype, [&](auto to) {
+      typedef MSMD_TAG_T(ti) TI;
+      typedef MSMD_TAG_T(to) TO;
+      if constexpr (sizeof(TI) == 2 && __is_same(TI, TO)) {
+        if (act == 0 && !post_add && launch_ln16<TI>(x, residual, gamma, beta, y, rows, cols, eps, st, nullptr, nullptr))
+          MSMD_RETURN_LAST();
+      }
+      if constexpr (kStoragePair<TI, TO>)
+        return launch_ln<TI, TO>(x, residual, gamma, beta, post_add, y, rows, cols, eps, act, st);
+      else
+        return 1;
+    });
+  });
 }
 
 // y = LN_{gamma, beta}( LN_{pre_gamma, pre_beta}(x) + residual ): two consecutive post-LN LayerNorms with a branch added in
@@ -332,16 +326,11 @@ extern "C" int msmd_layernorm_pre(const void* x, const float* pre_gamma, const f
                                   msmd_stream_t stream) {
   if (rows <= 0 || cols <= 0 || (cols & 3) || !x || !y || !gamma || !beta || !pre_gamma || !pre_beta) return 1;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == MSMD_BF16 || dtype == MSMD_F16) {
-    const bool took = dtype == MSMD_BF16 ? launch_ln16<bf16_t>(x, residual, gamma, beta, y, rows, cols, eps, st, pre_gamma, pre_beta)
-                                         : launch_ln16<f16_t>(x, residual, gamma, beta, y, rows, cols, eps, st, pre_gamma, pre_beta);
-    if (took) MSMD_RETURN_LAST();
-  }
-  if (dtype == MSMD_BF16)
-    return launch_ln<bf16_t, bf16_t>(x, residual, gamma, beta, nullptr, y, rows, cols, eps, 0, st, pre_gamma, pre_beta);
-  if (dtype == MSMD_F16)
-    return launch_ln<f16_t, f16_t>(x, residual, gamma, beta, nullptr, y, rows, cols, eps, 0, st, pre_gamma, pre_beta);
-  return 1;
+  return dispatch_dtype<bf16_t, f16_t>(dtype, [&](auto tag) {
+    typedef MSMD_TAG_T(tag) T;
+    if (launch_ln16<T>(x, residual, gamma, beta, y, rows, cols, eps, st, pre_gamma, pre_beta)) MSMD_RETURN_LAST();
+    return launch_ln<T, T>(x, residual, gamma, beta, nullptr, y, rows, cols, eps, 0, st, pre_gamma, pre_beta);
+  });
 }
 
 // mean over time of a channels-last (B, T, C) tensor -> (B, C) fp32
@@ -359,11 +348,9 @@ __global__ void mean_time_kernel(const T* __restrict__ x, float* __restrict__ y,
 extern "C" int msmd_mean_time(const void* x, float* y, int B, int T, int C, int dtype, msmd_stream_t stream) {
   if (B <= 0 || T <= 0 || C <= 0) return 1;
   dim3 grid((C + 255) / 256, B), block(256);
-  if (dtype == MSMD_F32)
-    hipLaunchKernelGGL(mean_time_kernel<float>, grid, block, 0, (hipStream_t)stream, (const float*)x, y, T, C);
-  else if (dtype == MSMD_F16)
-    hipLaunchKernelGGL(mean_time_kernel<f16_t>, grid, block, 0, (hipStream_t)stream, (const f16_t*)x, y, T, C);
-  else
-    hipLaunchKernelGGL(mean_time_kernel<bf16_t>, grid, block, 0, (hipStream_t)stream, (const bf16_t*)x, y, T, C);
-  MSMD_RETURN_LAST();
+  return dispatch_dtype<float, f16_t, bf16_t>(dtype, [&](auto tag) {
+    typedef MSMD_TAG_T(tag) TX;
+    hipLaunchKernelGGL(mean_time_kernel<TX>, grid, block, 0, (hipStream_t)stream, (const TX*)x, y, T, C);
+    MSMD_RETURN_LAST();
+  });
 }
