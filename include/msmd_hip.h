@@ -46,7 +46,7 @@ int msmd_abi_version(void);
  * knobs travels per call -- the GEMM kernel variant and epilogue flags in `act` (msmd_gemm below), the contraction
  * split count of msmd_gemm_tn in its `accumulate` argument.  The kernel families of DESIGN.md section 5 / 5b that
  * lost their measurements are not in the sources any more. */
-#define MSMD_GEMM_VARIANT(v) ((v) << 8)   /* bits 8-15 of `act`: 0 = shape heuristic, 9 / 12 / 13 / 14 / 15 / 17 / 80 (bf16, fp16), 1 / 5 / 14 / 80 (f16x2) */
+#define MSMD_GEMM_VARIANT(v) ((v) << 8)   /* bits 8-15 of `act`: 0 = shape heuristic, 9 / 12 / 13 / 14 / 15 / 17 / 18 / 80 (bf16, fp16), 1 / 5 / 14 / 80 (f16x2) */
 #define MSMD_GEMM_WRITE_THROUGH (1 << 16) /* output stores carry `sc1`: the bytes leave the XCD's L2 as they are stored */
 #define MSMD_GEMM_PAIRED_STORES (1 << 17) /* 16-bit outputs: lane pairs swap a fragment row, one 16-byte store each */
 #define MSMD_GEMM_STAGGER (1 << 18)       /* multi-round launches: the second workgroup of every CU starts half a tile period late */

@@ -693,6 +693,13 @@ template <typename T, int NW, int NF> static int launch_whole(const AttnArgs& p,
 // short sequences: all keys staged once, plain softmax (attn_whole_kernel).  One workgroup per (batch, head) when the
 // queries fit (K / V read once): in the forward step T = 200 runs 16.4 us with 13 waves against 17.5 with 7 (two
 // workgroups per head) and 19.8 for attn_kernel; T = 111 6.6 us with 7 waves against 7.8.
+// Also built and measured, not kept: 7 waves taking TWO query fragments each (one workgroup per (batch, head),
+// K / V staged once, 99 registers, no scratch, two workgroups per CU) for launches of more units than CUs.  Same bits.  us for
+// 13 waves -> that form, median of 30, hot / cold:    B H = 384   16.6 -> 16.2 / 25.3 -> 24.2;  with 4 prefetch ranges 17.9 -> 18.2 / 26.9 -> 27.4
+//                                                      B H = 768   26.4 -> 24.5 / 38.8 -> 36.8;  with 4 prefetch ranges 27.6 -> 25.9 / 40.3 -> 41.0
+// and in the forward step (12 launches, prefetching) 18.11 -> 18.29 us, the step +0.008 ms (slower in 6 of 7 alternating pairs).
+// 384 units on 256 CUs put two units on half of the CUs in either form: the busiest CU does the same work, with half the waves
+// to stage it.
 template <typename T> static int launch_whole_for(const AttnArgs& p, hipStream_t st) {
   if (p.Tk > 16 * ATTN_WHOLE_NF) return launch_whole<T, 9, 17>(p, st);
   if (p.Tq <= 112) return launch_whole<T, 7, ATTN_WHOLE_NF>(p, st);

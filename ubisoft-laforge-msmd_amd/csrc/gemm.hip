@@ -65,7 +65,8 @@ enum : int {
   GV_256x64 = 14,       // narrow outputs (N <= 64): the positional conv; 16-bit and split pairs
   GV_192 = 15,          // 192 x 128, tall grids (M >= 16 k): 80 KB, still 2 workgroups / CU
   GV_128 = 17,          // 128 x 128, 8 waves (4 x 2), 2-stage ring, fragment reads of both k-steps issued first
-  GV_128_AB = 13, GV_128_ONE_AB = 66,      // A/B forms of 17, bf16 only: the compiler's own read / multiply interleave; ONE kernel with every epilogue
+  GV_64x128 = 18,       // 64 x 128, 4 waves (2 x 2) of 17's 32 x 64 wave tile, 4-stage ring (96 KB): one workgroup per CU, twice 17's grid
+  GV_128_AB = 13, GV_128_ONE_AB = 66,     // A/B forms of 17, bf16 only: the compiler's own read / multiply interleave; ONE kernel with every epilogue
   GV_256 = 80,          // 256 x 256, 8-phase schedule, one workgroup per CU (gemm8_kernel); 16-bit and split pairs
 };
 
@@ -376,9 +377,34 @@ __device__ __forceinline__ void ln_finish(const float* stats, int nt, int M, int
 // the statistics of the stored rows written when stats_out is given.  Every load of the epilogue (bias, column sums or
 // gamma / beta, the residual fragments) is issued up front, unconditionally: with run-time "is this pointer set" tests
 // inside the fragment loops the compiler serialises them into one L2 round trip per fragment column (+4 us per launch).
-template <typename TO, int FM, int FN, int MODE, int ACT = -1>
+// EARLY: the MODE 2 operands were requested before the K loop (ln_res_issue, the 4-wave 64 x 128 kernel: 256 registers) and are
+// consumed here from `early` with the same arithmetic; the HBM round trip that otherwise stands between the last MFMA and the
+// first store, for every workgroup of a one-round launch at the same moment, is then behind the K loop.
+template <typename TO, int FM, int FN> struct LnResOps { f32x4 bv[FN], xv[FN], yv[FN]; typename Vec4T<TO>::type rr[FM][FN]; };
+template <typename TO, int FM, int FN>
+__device__ __forceinline__ void ln_res_issue(const GemmArgs& p, int m_base, int n_base, int fr, int fq, LnResOps<TO, FM, FN>& o) {
+  typedef typename Vec4T<TO>::type V4;
+  const int n = n_base + fq * 4;
+#pragma unroll
+  for (int i = 0; i < FN; ++i) o.bv[i] = *(const f32x4*)(p.bias + n + i * 16);
+#pragma unroll
+  for (int j = 0; j < FM; ++j) {
+    const TO* rp = (const TO*)p.R + (long)min(m_base + j * 16 + fr, p.M - 1) * p.ldr + n;
+#pragma unroll
+    for (int i = 0; i < FN; ++i) o.rr[j][i] = *(const V4*)(rp + i * 16);
+  }
+  if (p.r_stats) {
+#pragma unroll
+    for (int i = 0; i < FN; ++i) { o.xv[i] = *(const f32x4*)(p.r_gamma + n + i * 16); o.yv[i] = *(const f32x4*)(p.r_beta + n + i * 16); }
+  } else {
+#pragma unroll
+    for (int i = 0; i < FN; ++i) { o.xv[i] = f32x4{1.f, 1.f, 1.f, 1.f}; o.yv[i] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+  }
+}
+
+template <typename TO, int FM, int FN, int MODE, int ACT = -1, bool EARLY = false>
 __device__ __forceinline__ void gemm_epilogue_ln(const GemmArgs& p, const f32x4 (&acc)[FN][FM], int m_base, int n_base,
-                                                 int fr, int fq, const f32x2 (&raw)[FM][4]) {
+                                                 int fr, int fq, const f32x2 (&raw)[FM][4], const LnResOps<TO, FM, FN>* early = nullptr) {
   static_assert((FN == 4 || FN == 2) && (FM >= 2 && FM <= 4), "one wave = one statistics slab of 16 FN columns, 2 to 4 fragment rows");
   constexpr int SLAB = FN * 16;
   // fragment columns whose operands are requested together: all of them for the two-row tiles; two at a time for the
@@ -405,24 +431,34 @@ __device__ __forceinline__ void gemm_epilogue_ln(const GemmArgs& p, const f32x4 
   for (int i0 = 0; i0 < FN; i0 += IB) {
     f32x4 bv[IB], xv[IB], yv[IB];
     V4 rr[FM][IB];
+    if constexpr (EARLY) {
+      static_assert(MODE == 2 && IB == FN, "the early operands are the LayerNorm-residual form's, all fragment columns at once");
 #pragma unroll
-    for (int ii = 0; ii < IB; ++ii) bv[ii] = *(const f32x4*)(p.bias + n + (i0 + ii) * 16);
-    if constexpr (MODE == 1) {
+      for (int ii = 0; ii < IB; ++ii) {
+        bv[ii] = early->bv[ii]; xv[ii] = early->xv[ii]; yv[ii] = early->yv[ii];
 #pragma unroll
-      for (int ii = 0; ii < IB; ++ii) xv[ii] = *(const f32x4*)(p.w_colsum + n + (i0 + ii) * 16);
+        for (int j = 0; j < FM; ++j) rr[j][ii] = early->rr[j][ii];
+      }
     } else {
 #pragma unroll
-      for (int j = 0; j < FM; ++j) {
-        const TO* rp = (const TO*)p.R + (long)min(m_base + j * 16 + fr, p.M - 1) * p.ldr + n;
+      for (int ii = 0; ii < IB; ++ii) bv[ii] = *(const f32x4*)(p.bias + n + (i0 + ii) * 16);
+      if constexpr (MODE == 1) {
 #pragma unroll
-        for (int ii = 0; ii < IB; ++ii) rr[j][ii] = *(const V4*)(rp + (i0 + ii) * 16);
-      }
-      if (p.r_stats) {
-#pragma unroll
-        for (int ii = 0; ii < IB; ++ii) { xv[ii] = *(const f32x4*)(p.r_gamma + n + (i0 + ii) * 16); yv[ii] = *(const f32x4*)(p.r_beta + n + (i0 + ii) * 16); }
+        for (int ii = 0; ii < IB; ++ii) xv[ii] = *(const f32x4*)(p.w_colsum + n + (i0 + ii) * 16);
       } else {
 #pragma unroll
-        for (int ii = 0; ii < IB; ++ii) { xv[ii] = f32x4{1.f, 1.f, 1.f, 1.f}; yv[ii] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+        for (int j = 0; j < FM; ++j) {
+          const TO* rp = (const TO*)p.R + (long)min(m_base + j * 16 + fr, p.M - 1) * p.ldr + n;
+#pragma unroll
+          for (int ii = 0; ii < IB; ++ii) rr[j][ii] = *(const V4*)(rp + (i0 + ii) * 16);
+        }
+        if (p.r_stats) {
+#pragma unroll
+          for (int ii = 0; ii < IB; ++ii) { xv[ii] = *(const f32x4*)(p.r_gamma + n + (i0 + ii) * 16); yv[ii] = *(const f32x4*)(p.r_beta + n + (i0 + ii) * 16); }
+        } else {
+#pragma unroll
+          for (int ii = 0; ii < IB; ++ii) { xv[ii] = f32x4{1.f, 1.f, 1.f, 1.f}; yv[ii] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+        }
       }
     }
 #pragma unroll
@@ -669,6 +705,21 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8 && NSTAGE * (BM + BN) *
     for (int j = 0; j < FM; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   const int nk = p.K / 64;
+  // The 4-wave 64 x 128 kernel (one workgroup per CU, 256 registers) requests everything its LayerNorm-residual epilogue reads
+  // -- the row statistics, bias, residual fragments, gamma / beta -- in front of the ring's prologue: the counted waits of the
+  // K loop retire them with the first K tile, and the epilogue starts on registers.
+  constexpr bool LNK = (BN == 128 || BN == 64) && WN == 2 && (FM == 2 || FM == 3) && sizeof(TO) == 2;   // slab = BN / 2
+  // the 192-row tile has no registers to spare during the K loop (124 of 128): its statistics are loaded in the epilogue instead
+  // (one batched round trip; with two workgroups per CU and grids of many rounds it hides under the neighbour's K loop)
+  constexpr bool LN_LATE = FM == 3;
+  constexpr bool EARLY_OPS = LNK && EPI == 3 && NW == 4 && BM == 64 && BN == 128;
+  f32x2 lnraw[(LNK && !LN_LATE) ? FM : 1][4];
+  std::conditional_t<EARLY_OPS, LnResOps<TO, FM, FN>, char> early;
+  (void)early;
+  if constexpr (EARLY_OPS) {
+    if (p.r_stats) ln_issue<FM>(p.r_stats, p.r_nt, p.M, m0 + wm, fr, fq, lnraw);
+    ln_res_issue<TO, FM, FN>(p, m0 + wm, n0 + wn, fr, fq, early);
+  }
 #pragma unroll
   for (int s = 0; s < NSTAGE - 1; ++s)
     if (s < nk) issue(s, s);
@@ -681,12 +732,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8 && NSTAGE * (BM + BN) *
     while ((long)(__builtin_amdgcn_s_memrealtime() - t0) < p.stagger_ticks) __builtin_amdgcn_s_sleep(16);
   }
   // LayerNorm-folding mode (msmd_gemm_ln; the 4 x 2-wave 128 x 128 tile only): the row statistics' loads go out now, consumed in the epilogue
-  constexpr bool LNK = (BN == 128 || BN == 64) && WN == 2 && (FM == 2 || FM == 3) && sizeof(TO) == 2;   // slab = BN / 2
-  // the 192-row tile has no registers to spare during the K loop (124 of 128): its statistics are loaded in the epilogue instead
-  // (one batched round trip; with two workgroups per CU and grids of many rounds it hides under the neighbour's K loop)
-  constexpr bool LN_LATE = FM == 3;
-  f32x2 lnraw[(LNK && !LN_LATE) ? FM : 1][4];
-  if constexpr (LNK && !LN_LATE && EPI != 1) {
+  if constexpr (LNK && !LN_LATE && EPI != 1 && !EARLY_OPS) {
     if (EPI == 2 || (EPI == 0 && p.a_stats)) ln_issue<FM>(p.a_stats, p.a_nt, p.M, m0 + wm, fr, fq, lnraw);
     else if (p.r_stats) ln_issue<FM>(p.r_stats, p.r_nt, p.M, m0 + wm, fr, fq, lnraw);
   }
@@ -744,6 +790,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8 && NSTAGE * (BM + BN) *
   auto run_epilogue = [&]() {
     if constexpr (EPI == 1) { gemm_epilogue<TO, FM, FN, false, true, ACTK>(p, acc, z, m0 + wm_e, n0 + wn_e, fr_e, fq_e); return; }
     if constexpr (LNK && !LN_LATE && EPI == 2) { gemm_epilogue_ln<TO, FM, FN, 1, ACTK>(p, acc, m0 + wm_e, n0 + wn_e, fr_e, fq_e, lnraw); return; }
+    if constexpr (EARLY_OPS) { gemm_epilogue_ln<TO, FM, FN, 2, ACTK, true>(p, acc, m0 + wm_e, n0 + wn_e, fr_e, fq_e, lnraw, &early); return; }
     if constexpr (LNK && !LN_LATE && EPI == 3) { gemm_epilogue_ln<TO, FM, FN, 2, ACTK>(p, acc, m0 + wm_e, n0 + wn_e, fr_e, fq_e, lnraw); return; }
     if constexpr (LNK && LN_LATE && (EPI == 2 || EPI == 3)) {      // the 192-row tile: statistics loaded here (no registers to spare in the K loop)
       f32x2 late[FM][4];
@@ -1822,7 +1869,7 @@ static int launch_gemm(GemmArgs& p, int batch, hipStream_t st) {
 // The LDS-DMA variants dispatch_gemm has for bf16 / fp16 operands; gemm16_route asks the same question, so a routed variant always launches.
 static constexpr bool gemm2_has(int variant, bool bf16) {
   if (variant == GV_128_AB || variant == GV_128_ONE_AB) return bf16;
-  return variant == GV_64_DEEP || variant == GV_64 || variant == GV_256x64 || variant == GV_192 || variant == GV_128 || variant == GV_256;
+  return variant == GV_64_DEEP || variant == GV_64 || variant == GV_256x64 || variant == GV_192 || variant == GV_128 || variant == GV_64x128 || variant == GV_256;
 }
 
 // The launcher of a variant for plain (not split-pair) operands TI and output TO
@@ -1841,6 +1888,7 @@ static int dispatch_gemm(GemmArgs& p, int batch, hipStream_t st, int variant) {
       case GV_256x64: return launch_gemm2_epi<TO, 256, 64, 8, 1, 2, true, TI>(p, batch, st);   // 8 waves of 32 x 64
       case GV_192: return launch_gemm2_epi<TO, 192, 128, 4, 2, 2, true, TI>(p, batch, st);
       case GV_128: return launch_gemm2_epi<TO, 128, 128, 4, 2, 2, true, TI>(p, batch, st);
+      case GV_64x128: return launch_gemm2_epi<TO, 64, 128, 2, 2, 4, true, TI>(p, batch, st);
     }
     if constexpr (sizeof(TO) == 2) {      // GV_256
       if (!gemm8_takes(p, batch, 2)) return -1;
@@ -1926,8 +1974,8 @@ static int gemm16_route(const GemmArgs& p, int nz, int osz, bool bf16, int hint,
   const bool takes8 = (cols != 64 || !p.stats_out) && gemm8_takes(p, nz, osz);
   const bool rule8 = hint == 0 && !(flags & GF_NO_256);
   // a hint the call cannot follow leaves the library's own choice: 80 on a call the kernel does not take, and for msmd_gemm_ln
-  // anything but 15 / 17 / 66 inside the 128-column family
-  if (!(hint == GV_256 ? takes8 : !cols || (cols == 128 && (hint == GV_192 || hint == GV_128 || hint == GV_128_ONE_AB)))) hint = 0;
+  // anything but 15 / 17 / 18 / 66 inside the 128-column family
+  if (!(hint == GV_256 ? takes8 : !cols || (cols == 128 && (hint == GV_192 || hint == GV_128 || hint == GV_128_ONE_AB || hint == GV_64x128)))) hint = 0;
   if (hint) return gemm2_has(hint, bf16) ? hint : GV_GENERIC;
   const int M = p.M, N = p.N;
   const long tiles128 = (long)((M + 127) / 128) * ((N + 127) / 128) * nz;
@@ -1942,6 +1990,15 @@ static int gemm16_route(const GemmArgs& p, int nz, int osz, bool bf16, int hint,
   if (wide && osz == 2 && !p.Z && !(p.p_drop > 0.f) && !(p.flags & GF_ACT_BWD) && tall_rounds_favour_192(M, tiles128, tiles192)) return GV_192;
   // the 128 x 128 LDS-DMA kernel (8 waves as 4 x 2, 2-stage ring, fragment reads pipelined) wins once the grid fills the chip at
   // 2 workgroups per CU; below that, 64 x 64 tiles (deep ring for long K) keep more CUs busy
+  // msmd_gemm_ln's 128-column family on a grid that covers half the chip or less with 128 x 128 tiles (the decoder's 3552 x 512:
+  // 112 workgroups on 256 CUs, one 32 KB K tile in flight each): 64 x 128 tiles double the workgroups and keep 72 KB in flight.
+  // Same wave tile, k order and epilogue: the same bits.  It wins while its one-per-CU workgroups fit ONE round of 256 CUs and
+  // loses from the first workgroup of a second round on.  Measured, us hot / cold, 17 -> 18 (tools/bench_small_grid.py bf16 scan):
+  //   x 512 x 512:   32 tiles of 128 x 128  15.4 -> 15.4 / 17.4 -> 12.0;  128 tiles 15.3 -> 15.5 / 18.5 -> 13.4;  160 tiles 15.5 -> 17.2 / 18.8 -> 21.0
+  //   x 512 x 2048:  32 tiles 24.7 -> 19.0 / 38.4 -> 22.0;  128 tiles 27.3 -> 20.4 / 41.4 -> 24.7;  160 tiles 27.5 -> 36.0 / 43.0 -> 42.8
+  // Below 32 tiles nothing was measured: those launches stay on 17.
+  const long tiles64x128 = (long)((M + 63) / 64) * ((N + 127) / 128) * nz;
+  if (cols == 128 && osz == 2 && !p.Z && !(p.p_drop > 0.f) && !(p.flags & GF_ACT_BWD) && tiles128 >= 32 && tiles64x128 <= 256) return GV_64x128;
   if (cols ? wide : wide && tiles128 >= 192) return GV_128;
   if (!cols && N <= 64 && (long)((M + 255) / 256) * nz >= 256) return GV_256x64;   // the positional conv: 256 x 64 tiles, 140 -> 85 us
   return p.K >= 1024 ? GV_64_DEEP : GV_64;
@@ -2077,7 +2134,7 @@ static int gemm_ln_plan(GemmArgs& p, const GemmCall& c) {
   p.a_stats = c.a_stats; p.a_nt = c.a_stats ? K / c.slab_in : 0; p.w_colsum = c.w_colsum;
   p.r_stats = c.r_stats; p.r_nt = c.r_stats ? N / c.slab_in : 0; p.r_gamma = c.r_gamma; p.r_beta = c.r_beta;
   p.stats_out = c.stats_out; p.ln_eps = c.eps;
-  // the caller's tile hint chooses within the 128-column family (15 = 192 x 128, 17 = 128 x 128, 66 = A/B form of 17) or names
+  // the caller's tile hint chooses within the 128-column family (15 = 192 x 128, 17 = 128 x 128, 18 = 64 x 128, 66 = A/B form of 17) or names
   // the 256 x 256 kernel (80), which writes the same 64-column statistics slabs and reads either width
   const int variant = gemm16_route(p, 1, 2, c.in_dtype == MSMD_BF16, u.hint, u.flags & GF_NO_256, cols);
   return variant != GV_GENERIC ? variant : -1;      // no LayerNorm epilogue in gemm_kernel

@@ -182,7 +182,7 @@ GEMM_ONE_TILE_PER_WORKGROUP = 1 << 19      # opt out of the persistent form of m
 GEMM_NO_256_TILE = 1 << 20                 # opt out of the 256 x 256 8-phase kernel where the library would pick it (A/B; plain outputs same bits)
 GEMM_W_BELOW_32 = 1 << 21                  # split operands: |W| < 32 everywhere (set by gemm() from Split.below_32)
 GEMM_LN_FLAGS = 0              # extra `act` bits msmd_gemm_ln calls carry (A/B hook: GEMM_ONE_TILE_PER_WORKGROUP)
-GEMM_LN_ROUTER = None          # optional (M, N, K) -> 15 | 17 | None: tile hint for msmd_gemm_ln's big-tile family
+GEMM_LN_ROUTER = None          # optional (M, N, K) -> 15 | 17 | 18 | None: tile hint for msmd_gemm_ln's big-tile family
 GEMM_LN_ALL_IN_ONE = False     # A/B hook (tools/ab_forward.py): msmd_gemm_ln on the one-kernel-with-every-epilogue form (variant 66)
 
 
@@ -348,7 +348,7 @@ def gemm(a, w, bias=None, residual=None, act=ACT_NONE, out=None, out_dtype=None,
     return out
 
 
-GEMM_LN_TILE = None            # 15 | 17 | None: tile of msmd_gemm_ln's big-tile family for the calls made while it is set (the
+GEMM_LN_TILE = None            # 15 | 17 | 18 | None: tile of msmd_gemm_ln's big-tile family for the calls made while it is set (the
                                # sampler sets 15 -- 192 x 128 -- around the capture of a multi-lane step graph, see sampler.py)
 
 
