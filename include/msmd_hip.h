@@ -56,6 +56,9 @@ int msmd_abi_version(void);
                                              kernel (variant 80) may then scale W's hi plane by 2^11 in registers and keep ONE sum in
                                              units of 2^-11 instead of folding the cross terms once per K tile (11-17 % faster).  Without
                                              the bit nothing is assumed about W.  A W element of 32 or more under this bit overflows fp16. */
+#define MSMD_GEMM_NO_160_ROW_TILE (1 << 22)    /* msmd_gemm_ln: opt out of the 160 x 128 member of variant 17 where the library would launch it (A/B; same bits) */
+#define MSMD_GEMM_FORCE_160_ROW_TILE (1 << 23) /* msmd_gemm_ln: launch the 160 x 128 member of variant 17 wherever the kernel takes the call (residual form, no
+                                                  activation, 64-column slabs, variant 17 by hint or by the library's choice); ignored elsewhere (tests, scans) */
 
 /* Measurement aid: one wavefront that spins for `us` microseconds of the 100 MHz constant clock (s_memrealtime) and
  * optionally stores the ticks it actually spun.  bench.py times it at two lengths to calibrate the overhead of a HIP
@@ -136,6 +139,14 @@ int msmd_gemm_ln_route(const void* A, const void* W, const float* bias, const vo
                        int in_dtype, int out_dtype, long lda, long ldw, long ldc, long ldr, int act, const float* a_stats,
                        const float* w_colsum, const float* r_stats, const float* r_gamma, const float* r_beta,
                        float* stats_out, int slab_in, int slab_out, float eps, msmd_stream_t stream);
+/* The rows of C one workgroup of that launch computes: 64 (variants 9 / 12 / 18), 128 (17 / 66), 160 (17's member for grids that 160-row
+ * tiles put into ONE round of one workgroup per CU: the encoder's out-projection and FFN-2 at 6400 rows), 192 (15) or 256 (80); -1 for
+ * a call msmd_gemm_ln rejects.  The variant number does not change with the member: every tile of the family stores the same bits.
+ * Same arguments and the same guarantees as msmd_gemm_ln_route. */
+int msmd_gemm_ln_rows(const void* A, const void* W, const float* bias, const void* residual, void* C, int M, int N, int K,
+                      int in_dtype, int out_dtype, long lda, long ldw, long ldc, long ldr, int act, const float* a_stats,
+                      const float* w_colsum, const float* r_stats, const float* r_gamma, const float* r_beta,
+                      float* stats_out, int slab_in, int slab_out, float eps, msmd_stream_t stream);
 
 /* Two-level batched GEMM C[zo][zi] = A[zo][zi] . W[zo][zi]^T (no bias / residual / activation): operand z =
  * zo * batch_inner + zi starts at base + zo * stride_o + zi * stride_i.  Used by the explicit (materialised-P)

@@ -42,21 +42,25 @@ struct GemmArgs {
   int stagger_ticks = 0;
 };
 
-// GemmArgs::flags: the MSMD_GEMM_* bits 16-18 of `act` shifted down to bits 0-2, bits 19-21 to bits 4-6 (gemm_unpack_act).
+// GemmArgs::flags: the MSMD_GEMM_* bits 16-18 of `act` shifted down to bits 0-2, bits 19-23 to bits 4-8 (gemm_unpack_act).
 enum : int {
   GF_WRITE_THROUGH = 1, GF_PAIRED_STORES = 2, GF_STAGGER = 4,      // how the output is stored; when a CU's second workgroup starts
   GF_ACT_BWD = 8,      // internal (msmd_gemm_actbwd): Z is an INPUT: C = keep_mask / (1 - p) * act'(Z) * (A W^T), no bias / residual
   GF_ONE_TILE = 16, GF_NO_256 = 32,      // opt out of the persistent form / of the 256 x 256 kernel as the library's own choice (A/B)
   GF_W_BELOW_32 = 64,      // split operands: |W| < 32 everywhere
+  GF_NO_160 = 128, GF_FORCE_160 = 256,      // msmd_gemm_ln: opt out of / force the 160-row member of variant 17 (A/B; tests and scans)
+  GF_ROWS_160 = 512,   // internal (gemm_ln_plan): variant 17 launches its 160 x 128 member; no bit of `act` sets it
 };
 struct GemmActWord { int act, hint, flags; };   // MSMD_ACT_*, the caller's variant (0 = the library's own choice), GF_*
 static constexpr GemmActWord gemm_unpack_act(int act) {
-  return {act & 0xff, (act >> 8) & 0xff, ((act >> 16) & 7) | (((act >> 19) & 7) << 4)};
+  return {act & 0xff, (act >> 8) & 0xff, ((act >> 16) & 7) | (((act >> 19) & 31) << 4)};
 }
 static_assert(gemm_unpack_act(MSMD_GEMM_WRITE_THROUGH).flags == GF_WRITE_THROUGH && gemm_unpack_act(MSMD_GEMM_PAIRED_STORES).flags == GF_PAIRED_STORES &&
               gemm_unpack_act(MSMD_GEMM_STAGGER).flags == GF_STAGGER && gemm_unpack_act(MSMD_GEMM_ONE_TILE_PER_WORKGROUP).flags == GF_ONE_TILE &&
-              gemm_unpack_act(MSMD_GEMM_NO_256_TILE).flags == GF_NO_256 && gemm_unpack_act(MSMD_GEMM_W_BELOW_32).flags == GF_W_BELOW_32 && gemm_unpack_act(~0).flags == (0x7f & ~GF_ACT_BWD),
-              "internal flag bits follow include/msmd_hip.h; no bit of `act` sets the internal one");
+              gemm_unpack_act(MSMD_GEMM_NO_256_TILE).flags == GF_NO_256 && gemm_unpack_act(MSMD_GEMM_W_BELOW_32).flags == GF_W_BELOW_32 &&
+              gemm_unpack_act(MSMD_GEMM_NO_160_ROW_TILE).flags == GF_NO_160 && gemm_unpack_act(MSMD_GEMM_FORCE_160_ROW_TILE).flags == GF_FORCE_160 &&
+              gemm_unpack_act(~0).flags == (0x1ff & ~GF_ACT_BWD),
+              "internal flag bits follow include/msmd_hip.h; no bit of `act` sets the internal ones");
 // Kernel variants: what the plans return, msmd_gemm_route reports and MSMD_GEMM_VARIANT names.
 enum : int {
   GV_GENERIC = 0,       // gemm_kernel: fp32 operands, K % 64 != 0
@@ -64,7 +68,8 @@ enum : int {
   GV_64_DEEP = 9, GV_64 = 12,      // 64 x 64 with a 4- / 2-stage ring: grids that would not fill the chip
   GV_256x64 = 14,       // narrow outputs (N <= 64): the positional conv; 16-bit and split pairs
   GV_192 = 15,          // 192 x 128, tall grids (M >= 16 k): 80 KB, still 2 workgroups / CU
-  GV_128 = 17,          // 128 x 128, 8 waves (4 x 2), 2-stage ring, fragment reads of both k-steps issued first
+  GV_128 = 17,          // 128 x 128, 8 waves (4 x 2), 2-stage ring, fragment reads of both k-steps issued first; msmd_gemm_ln's residual form also
+                        // as 160 x 128, 10 waves (5 x 2), 4-stage ring (144 KB), where that fits the grid into ONE round of one workgroup per CU
   GV_64x128 = 18,       // 64 x 128, 4 waves (2 x 2) of 17's 32 x 64 wave tile, 4-stage ring (96 KB): one workgroup per CU, twice 17's grid
   GV_128_AB = 13, GV_128_ONE_AB = 66,     // A/B forms of 17, bf16 only: the compiler's own read / multiply interleave; ONE kernel with every epilogue
   GV_256 = 80,          // 256 x 256, 8-phase schedule, one workgroup per CU (gemm8_kernel); 16-bit and split pairs
@@ -380,9 +385,11 @@ __device__ __forceinline__ void ln_finish(const float* stats, int nt, int M, int
 // EARLY: the MODE 2 operands were requested before the K loop (ln_res_issue, the 4-wave 64 x 128 kernel: 256 registers) and are
 // consumed here from `early` with the same arithmetic; the HBM round trip that otherwise stands between the last MFMA and the
 // first store, for every workgroup of a one-round launch at the same moment, is then behind the K loop.
-template <typename TO, int FM, int FN> struct LnResOps { f32x4 bv[FN], xv[FN], yv[FN]; typename Vec4T<TO>::type rr[FM][FN]; };
-template <typename TO, int FM, int FN>
-__device__ __forceinline__ void ln_res_issue(const GemmArgs& p, int m_base, int n_base, int fr, int fq, LnResOps<TO, FM, FN>& o) {
+// GB = false (the 10-wave 160 x 128 kernel: 168 registers): bias and residual fragments only; gamma / beta, which every workgroup reads and
+// the L2 holds, are loaded in the epilogue as without EARLY (all four were 68 bytes of scratch there).
+template <typename TO, int FM, int FN, bool GB = true> struct LnResOps { f32x4 bv[FN], xv[GB ? FN : 1], yv[GB ? FN : 1]; typename Vec4T<TO>::type rr[FM][FN]; };
+template <typename TO, int FM, int FN, bool GB>
+__device__ __forceinline__ void ln_res_issue(const GemmArgs& p, int m_base, int n_base, int fr, int fq, LnResOps<TO, FM, FN, GB>& o) {
   typedef typename Vec4T<TO>::type V4;
   const int n = n_base + fq * 4;
 #pragma unroll
@@ -393,18 +400,20 @@ __device__ __forceinline__ void ln_res_issue(const GemmArgs& p, int m_base, int 
 #pragma unroll
     for (int i = 0; i < FN; ++i) o.rr[j][i] = *(const V4*)(rp + i * 16);
   }
-  if (p.r_stats) {
+  if constexpr (GB) {
+    if (p.r_stats) {
 #pragma unroll
-    for (int i = 0; i < FN; ++i) { o.xv[i] = *(const f32x4*)(p.r_gamma + n + i * 16); o.yv[i] = *(const f32x4*)(p.r_beta + n + i * 16); }
-  } else {
+      for (int i = 0; i < FN; ++i) { o.xv[i] = *(const f32x4*)(p.r_gamma + n + i * 16); o.yv[i] = *(const f32x4*)(p.r_beta + n + i * 16); }
+    } else {
 #pragma unroll
-    for (int i = 0; i < FN; ++i) { o.xv[i] = f32x4{1.f, 1.f, 1.f, 1.f}; o.yv[i] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+      for (int i = 0; i < FN; ++i) { o.xv[i] = f32x4{1.f, 1.f, 1.f, 1.f}; o.yv[i] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+    }
   }
 }
 
-template <typename TO, int FM, int FN, int MODE, int ACT = -1, bool EARLY = false>
+template <typename TO, int FM, int FN, int MODE, int ACT = -1, bool EARLY = false, bool EARLY_GB = true>
 __device__ __forceinline__ void gemm_epilogue_ln(const GemmArgs& p, const f32x4 (&acc)[FN][FM], int m_base, int n_base,
-                                                 int fr, int fq, const f32x2 (&raw)[FM][4], const LnResOps<TO, FM, FN>* early = nullptr) {
+                                                 int fr, int fq, const f32x2 (&raw)[FM][4], const LnResOps<TO, FM, FN, EARLY_GB>* early = nullptr) {
   static_assert((FN == 4 || FN == 2) && (FM >= 2 && FM <= 4), "one wave = one statistics slab of 16 FN columns, 2 to 4 fragment rows");
   constexpr int SLAB = FN * 16;
   // fragment columns whose operands are requested together: all of them for the two-row tiles; two at a time for the
@@ -435,9 +444,19 @@ __device__ __forceinline__ void gemm_epilogue_ln(const GemmArgs& p, const f32x4 
       static_assert(MODE == 2 && IB == FN, "the early operands are the LayerNorm-residual form's, all fragment columns at once");
 #pragma unroll
       for (int ii = 0; ii < IB; ++ii) {
-        bv[ii] = early->bv[ii]; xv[ii] = early->xv[ii]; yv[ii] = early->yv[ii];
+        bv[ii] = early->bv[ii];
+        if constexpr (EARLY_GB) { xv[ii] = early->xv[ii]; yv[ii] = early->yv[ii]; }
 #pragma unroll
         for (int j = 0; j < FM; ++j) rr[j][ii] = early->rr[j][ii];
+      }
+      if constexpr (!EARLY_GB) {
+        if (p.r_stats) {
+#pragma unroll
+          for (int ii = 0; ii < IB; ++ii) { xv[ii] = *(const f32x4*)(p.r_gamma + n + ii * 16); yv[ii] = *(const f32x4*)(p.r_beta + n + ii * 16); }
+        } else {
+#pragma unroll
+          for (int ii = 0; ii < IB; ++ii) { xv[ii] = f32x4{1.f, 1.f, 1.f, 1.f}; yv[ii] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+        }
       }
     } else {
 #pragma unroll
@@ -648,6 +667,15 @@ typedef __attribute__((address_space(1))) const void gbl_void_t;
 // epilogue of a 128 x 128 tile at 3.0 us for 32 outputs per lane (bias only), most of it instruction fetch.
 // EPIA = EPI + 10 * (1 + activation) when the activation is compiled in as well (11 / 21 plain with none / GELU, 12 / 22
 // LayerNorm-operand with none / GELU, 13 LayerNorm-residual with none): see act_out_c.
+// The waves that stage a K tile of `slots` LDS-DMA wave-instructions (1 KB each): all `waves` of them where that divides, else the
+// largest count that does (the 160 x 128 tile: 36 slots, 9 of its 10 waves with 4 each; the tenth issues none, so every wave's
+// counted wait stays one compile-time constant that is right for it -- a wave with nothing in flight passes it at once).
+constexpr int gemm2_loader_waves(int slots, int waves) {
+  int w = waves;
+  while (slots % w) --w;
+  return w;
+}
+
 template <typename TO, int BM, int BN, int WM, int WN, int NSTAGE, bool PIPE = false, typename TI = bf16_t, int EPIA = 0>
 // 8-wave workgroups whose ring fits twice into a CU's LDS are MEANT to run two per CU: 4 waves per SIMD = 128 registers
 // (the 192-row tile's LayerNorm epilogues drifted to 145 once, i.e. to one workgroup per CU: HuBERT-large 18.7 -> 21.4 ms).
@@ -655,11 +683,12 @@ template <typename TO, int BM, int BN, int WM, int WN, int NSTAGE, bool PIPE = f
 // fit 128 without spilling and keeps the register count the compiler picks.
 __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8 && NSTAGE * (BM + BN) * 128 <= 80 * 1024 && (epia_family(EPIA) != EPI_ALL || BM * BN <= 128 * 128)) ? 4 : 1) void gemm2_kernel(const GemmArgs p) {
   constexpr int EPI = epia_family(EPIA), ACTK = epia_act(EPIA);
-  constexpr int NW = WM * WN, NT = NW * 64;
+  constexpr int NW = WM * WN;
   constexpr int STAGE = (BM + BN) * 128;
-  constexpr int LPT = (BM + BN) * 8 / NT;  // LDS-DMA instructions per thread per K tile
+  constexpr int NLW = gemm2_loader_waves((BM + BN) / 8, NW);   // waves that issue LDS-DMA
+  constexpr int LPT = (BM + BN) / 8 / NLW;  // LDS-DMA instructions per thread of a loader wave per K tile
   constexpr int FM = BM / WM / 16, FN = BN / WN / 16;
-  static_assert((BM + BN) * 8 % NT == 0, "tile chunks must divide over the threads");
+  static_assert((BM + BN) % 8 == 0 && NLW * LPT * 8 == BM + BN && (NLW == NW || NLW * 2 > NW), "tile chunks must divide over the loader waves");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
   const int pid = blockIdx.x;
@@ -678,7 +707,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8 && NSTAGE * (BM + BN) *
   const bf16_t* src[LPT];
 #pragma unroll
   for (int i = 0; i < LPT; ++i) {
-    const int id = (i * NW + wid) * 64 + lane;  // 16-B slot of the tile image
+    const int id = (i * NLW + wid) * 64 + lane;  // 16-B slot of the tile image (past its end in a wave that loads nothing: clamped, never read)
     const int row = id >> 3, phys = id & 7;
     const int c = phys ^ ((row >> 1) & 7);      // logical chunk stored at this physical slot
     if (row < BM) {
@@ -689,11 +718,13 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8 && NSTAGE * (BM + BN) *
       src[i] = W + (long)n * p.ldw + c * 8;
     }
   }
+  const bool loader = NLW == NW || __builtin_amdgcn_readfirstlane(wid) < NLW;
   auto issue = [&](int kt, int stage) {
+    if constexpr (NLW != NW) { if (!loader) return; }
 #pragma unroll
     for (int i = 0; i < LPT; ++i)
       __builtin_amdgcn_global_load_lds((gbl_void_t*)(src[i] + kt * 64),
-                                       (lds_void_t*)(smem + stage * STAGE + (i * NW + wid) * 1024), 16, 0, 0);
+                                       (lds_void_t*)(smem + stage * STAGE + (i * NLW + wid) * 1024), 16, 0, 0);
   };
 
   const int wm = (wid / WN) * (BM / WM), wn = (wid % WN) * (BN / WN);
@@ -707,18 +738,21 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8 && NSTAGE * (BM + BN) *
   const int nk = p.K / 64;
   // The 4-wave 64 x 128 kernel (one workgroup per CU, 256 registers) requests everything its LayerNorm-residual epilogue reads
   // -- the row statistics, bias, residual fragments, gamma / beta -- in front of the ring's prologue: the counted waits of the
-  // K loop retire them with the first K tile, and the epilogue starts on registers.
+  // K loop retire them with the first K tile, and the epilogue starts on registers.  The 10-wave 160 x 128 kernel (three waves on a
+  // SIMD: 168 registers) does the same without gamma / beta (EARLY_GB; 152 registers, all four: 68 bytes of scratch).  Requested behind
+  // the prologue instead, the first counted wait would take them for ring stages and wait for three K tiles, not one.
   constexpr bool LNK = (BN == 128 || BN == 64) && WN == 2 && (FM == 2 || FM == 3) && sizeof(TO) == 2;   // slab = BN / 2
   // the 192-row tile has no registers to spare during the K loop (124 of 128): its statistics are loaded in the epilogue instead
   // (one batched round trip; with two workgroups per CU and grids of many rounds it hides under the neighbour's K loop)
   constexpr bool LN_LATE = FM == 3;
-  constexpr bool EARLY_OPS = LNK && EPI == 3 && NW == 4 && BM == 64 && BN == 128;
+  constexpr bool EARLY_OPS = LNK && EPI == 3 && ((NW == 4 && BM == 64) || (NW == 10 && BM == 160)) && BN == 128;
   f32x2 lnraw[(LNK && !LN_LATE) ? FM : 1][4];
-  std::conditional_t<EARLY_OPS, LnResOps<TO, FM, FN>, char> early;
+  constexpr bool EARLY_GB = NW == 4;
+  std::conditional_t<EARLY_OPS, LnResOps<TO, FM, FN, EARLY_GB>, char> early;
   (void)early;
   if constexpr (EARLY_OPS) {
     if (p.r_stats) ln_issue<FM>(p.r_stats, p.r_nt, p.M, m0 + wm, fr, fq, lnraw);
-    ln_res_issue<TO, FM, FN>(p, m0 + wm, n0 + wn, fr, fq, early);
+    ln_res_issue<TO, FM, FN, EARLY_GB>(p, m0 + wm, n0 + wn, fr, fq, early);
   }
 #pragma unroll
   for (int s = 0; s < NSTAGE - 1; ++s)
@@ -790,7 +824,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8 && NSTAGE * (BM + BN) *
   auto run_epilogue = [&]() {
     if constexpr (EPI == 1) { gemm_epilogue<TO, FM, FN, false, true, ACTK>(p, acc, z, m0 + wm_e, n0 + wn_e, fr_e, fq_e); return; }
     if constexpr (LNK && !LN_LATE && EPI == 2) { gemm_epilogue_ln<TO, FM, FN, 1, ACTK>(p, acc, m0 + wm_e, n0 + wn_e, fr_e, fq_e, lnraw); return; }
-    if constexpr (EARLY_OPS) { gemm_epilogue_ln<TO, FM, FN, 2, ACTK, true>(p, acc, m0 + wm_e, n0 + wn_e, fr_e, fq_e, lnraw, &early); return; }
+    if constexpr (EARLY_OPS) { gemm_epilogue_ln<TO, FM, FN, 2, ACTK, true, EARLY_GB>(p, acc, m0 + wm_e, n0 + wn_e, fr_e, fq_e, lnraw, &early); return; }
     if constexpr (LNK && !LN_LATE && EPI == 3) { gemm_epilogue_ln<TO, FM, FN, 2, ACTK>(p, acc, m0 + wm_e, n0 + wn_e, fr_e, fq_e, lnraw); return; }
     if constexpr (LNK && LN_LATE && (EPI == 2 || EPI == 3)) {      // the 192-row tile: statistics loaded here (no registers to spare in the K loop)
       f32x2 late[FM][4];
@@ -1697,6 +1731,20 @@ static int gemm2_xcd_grid(GemmArgs& p, int BM, int BN, long lda) {
   return ((p.mt + xm_n - 1) / xm_n) * ((p.nt + p.xn - 1) / p.xn) * 8;
 }
 
+// The XCD grid of the 160 x 128 member of variant 17, which is meant to run ONE round of one workgroup per CU: gemm2_xcd_grid's own xn
+// where its grid, padding included, stays within 256 workgroups (the chip the rule was fitted on), else the first xn whose grid does.
+// Returns that grid's workgroup count, or 0 where none fits (p then holds gemm2_xcd_grid's grid).  6400 x 768: 40 x 6 tiles, 240 workgroups.
+static int gemm160_one_round_grid(GemmArgs& p) {
+  const int wgs = gemm2_xcd_grid(p, 160, 128, p.lda);
+  if (wgs <= 256) return wgs;
+  for (int xn = 1; xn <= 4 && xn <= p.nt; xn *= 2) {
+    const int xm_n = 8 / xn;
+    const int w = ((p.mt + xm_n - 1) / xm_n) * ((p.nt + xn - 1) / xn) * 8;
+    if (w <= 256) { p.xn = xn; return w; }
+  }
+  return 0;
+}
+
 // gemm2_kernel on `wgs` workgroups per batch (gemm2_xcd_grid's)
 template <typename TO, int BM, int BN, int WM, int WN, int NSTAGE, bool PIPE = false, typename TI = bf16_t, int EPIA = 0>
 static int launch_gemm2(GemmArgs& p, int wgs, int batch, hipStream_t st) {
@@ -1724,6 +1772,14 @@ static int launch_gemm2_epi(GemmArgs& p, int batch, hipStream_t st) {
   const int code = gemm_epia(p, LNK), wgs = gemm2_xcd_grid(p, BM, BN, p.lda);
   int r;
   if constexpr (LNK && PIPE && NSTAGE == 2 && WM * WN == 8 && BN == 128 && BM == 128) {
+    // gemm_ln_plan's choice (GF_ROWS_160: residual form, no activation, one batch): the 160 x 128 member, 10 waves of this tile's 32 x 64
+    // wave tile on a 4-stage ring, one workgroup per CU.  Same k order, MFMA sequence and epilogue: the same bits.  Its one epilogue
+    // serves the form with and without statistics on either side.
+    if (p.flags & GF_ROWS_160) {
+      int wgs160 = gemm160_one_round_grid(p);
+      if (!wgs160) wgs160 = gemm2_xcd_grid(p, 160, 128, p.lda);      // forced onto a grid of more than one round
+      return launch_gemm2<TO, 160, 128, 5, 2, 4, true, TI, epia(EPI_LN_RESIDUAL, MSMD_ACT_NONE)>(p, wgs160, batch, st);
+    }
     // more than one round of two workgroups per CU: the persistent form (gemm2p_kernel: 512 workgroups, two per CU); GF_ONE_TILE =
     // the caller opts out (A/B).  The 128 x 128 tile's plain and LayerNorm-operand epilogues: the LayerNorm-residual one (its
     // launches on the path are single-round) and the 192-row tile do not fit 128 registers in this form (20-128 bytes of scratch).
@@ -2105,6 +2161,20 @@ extern "C" int msmd_gemm_route(const void* A, const void* W, const float* bias, 
                                    act, batch, strideA, strideW, strideC, strideBias, strideR, z_out, p_drop, rng_state, site));
 }
 
+// Whether a msmd_gemm_ln call that routes to variant 17 launches its 160 x 128 member (gemm2_kernel<160, 128, 5 x 2 waves, 4-stage ring>).
+// The kernel takes the residual form without an activation in the 128-column family.  The library's own choice (no hint): the
+// 128 x 128 tiles are more than the 256 CUs, so some CU would carry two workgroups and take in twice the operands of the others,
+// while 160-row tiles put the whole grid, XCD padding included, into one round of one workgroup per CU with 108 KB in flight each.
+// MSMD_GEMM_NO_160_ROW_TILE opts out, MSMD_GEMM_FORCE_160_ROW_TILE takes the member wherever the kernel takes the call.
+static bool gemm_ln_takes_160_rows(const GemmArgs& p, int cols, const GemmActWord& u) {
+  if (cols != 128 || p.a_stats || !p.R || p.act != MSMD_ACT_NONE || (u.flags & GF_NO_160)) return false;
+  if (u.flags & GF_FORCE_160) return true;
+  if (u.hint) return false;
+  if ((long)((p.M + 127) / 128) * ((p.N + 127) / 128) <= 256) return false;
+  GemmArgs q = p;
+  return gemm160_one_round_grid(q) > 0;
+}
+
 // C = act(LN_A(A) . W^T + bias) + LN_R(residual), with the LayerNorms folded into this GEMM's epilogue and (optionally)
 // the row statistics of C written for the next consumer: see GemmArgs and include/msmd_hip.h.  Plain row-major operands,
 // no batch, 16-bit operands and output.  The statistics' slab width names the kernel that writes them: 64 = the
@@ -2127,8 +2197,8 @@ static int gemm_ln_plan(GemmArgs& p, const GemmCall& c) {
   const long tiles128 = (long)((M + 127) / 128) * ((N + 127) / 128);
   const int cols = (c.stats_out ? c.slab_out == 64 : (tiles128 >= 192 && (N % 128) == 0)) ? 128 : 64;
   if (cols == 128 && (N % 128)) return -1;
-  // of the word's flags this entry honours MSMD_GEMM_ONE_TILE_PER_WORKGROUP and MSMD_GEMM_NO_256_TILE; paired 16-byte stores
-  // always, where the rows allow them
+  // of the word's flags this entry honours MSMD_GEMM_ONE_TILE_PER_WORKGROUP, MSMD_GEMM_NO_256_TILE and the two 160-row bits; paired
+  // 16-byte stores always, where the rows allow them
   const GemmActWord u = gemm_unpack_act(c.act);
   p = gemm_args(c, u.act, GF_PAIRED_STORES | (u.flags & GF_ONE_TILE), 2);
   p.a_stats = c.a_stats; p.a_nt = c.a_stats ? K / c.slab_in : 0; p.w_colsum = c.w_colsum;
@@ -2137,7 +2207,20 @@ static int gemm_ln_plan(GemmArgs& p, const GemmCall& c) {
   // the caller's tile hint chooses within the 128-column family (15 = 192 x 128, 17 = 128 x 128, 18 = 64 x 128, 66 = A/B form of 17) or names
   // the 256 x 256 kernel (80), which writes the same 64-column statistics slabs and reads either width
   const int variant = gemm16_route(p, 1, 2, c.in_dtype == MSMD_BF16, u.hint, u.flags & GF_NO_256, cols);
+  if (variant == GV_128 && gemm_ln_takes_160_rows(p, cols, u)) p.flags |= GF_ROWS_160;
   return variant != GV_GENERIC ? variant : -1;      // no LayerNorm epilogue in gemm_kernel
+}
+
+// The rows of C per workgroup of the launch a msmd_gemm_ln plan describes
+static int gemm_ln_plan_rows(const GemmArgs& p, int variant) {
+  switch (variant) {
+    case GV_64_DEEP: case GV_64: case GV_64x128: return 64;
+    case GV_128: return (p.flags & GF_ROWS_160) ? 160 : 128;
+    case GV_128_AB: case GV_128_ONE_AB: return 128;
+    case GV_192: return 192;
+    case GV_256: case GV_256x64: return 256;
+  }
+  return -1;
 }
 
 static GemmCall gemm_ln_call(const void* A, const void* W, const float* bias, const void* residual, void* C, int M, int N, int K, int in_dtype,
@@ -2168,6 +2251,17 @@ extern "C" int msmd_gemm_ln_route(const void* A, const void* W, const float* bia
   GemmArgs p;
   return gemm_ln_plan(p, gemm_ln_call(A, W, bias, residual, C, M, N, K, in_dtype, out_dtype, lda, ldw, ldc, ldr, act, a_stats,
                                       w_colsum, r_stats, r_gamma, r_beta, stats_out, slab_in, slab_out, eps));
+}
+
+// The rows of C per workgroup of the launch msmd_gemm_ln would make for the same arguments, or -1 for a call it rejects.  Launches nothing.
+extern "C" int msmd_gemm_ln_rows(const void* A, const void* W, const float* bias, const void* residual, void* C, int M, int N, int K,
+                                 int in_dtype, int out_dtype, long lda, long ldw, long ldc, long ldr, int act, const float* a_stats,
+                                 const float* w_colsum, const float* r_stats, const float* r_gamma, const float* r_beta, float* stats_out,
+                                 int slab_in, int slab_out, float eps, msmd_stream_t) {
+  GemmArgs p;
+  const int variant = gemm_ln_plan(p, gemm_ln_call(A, W, bias, residual, C, M, N, K, in_dtype, out_dtype, lda, ldw, ldc, ldr, act, a_stats,
+                                                   w_colsum, r_stats, r_gamma, r_beta, stats_out, slab_in, slab_out, eps));
+  return variant < 0 ? -1 : gemm_ln_plan_rows(p, variant);
 }
 
 // dZ = keep_mask / (1 - p) * act'(Z) * (A . W^T): the data gradient of a Linear whose INPUT was dropout(act(Z)) -- the product

@@ -181,6 +181,8 @@ GEMM_WRITE_THROUGH, GEMM_PAIRED_STORES, GEMM_STAGGER = 1 << 16, 1 << 17, 1 << 18
 GEMM_ONE_TILE_PER_WORKGROUP = 1 << 19      # opt out of the persistent form of multi-round launches (A/B; same bits)
 GEMM_NO_256_TILE = 1 << 20                 # opt out of the 256 x 256 8-phase kernel where the library would pick it (A/B; plain outputs same bits)
 GEMM_W_BELOW_32 = 1 << 21                  # split operands: |W| < 32 everywhere (set by gemm() from Split.below_32)
+GEMM_NO_160_ROW_TILE = 1 << 22             # gemm_ln: opt out of the 160 x 128 member of variant 17 (A/B; same bits)
+GEMM_FORCE_160_ROW_TILE = 1 << 23          # gemm_ln: the 160 x 128 member wherever its kernel takes the call (tests, scans; same bits)
 GEMM_LN_FLAGS = 0              # extra `act` bits msmd_gemm_ln calls carry (A/B hook: GEMM_ONE_TILE_PER_WORKGROUP)
 GEMM_LN_ROUTER = None          # optional (M, N, K) -> 15 | 17 | 18 | None: tile hint for msmd_gemm_ln's big-tile family
 GEMM_LN_ALL_IN_ONE = False     # A/B hook (tools/ab_forward.py): msmd_gemm_ln on the one-kernel-with-every-epilogue form (variant 66)
