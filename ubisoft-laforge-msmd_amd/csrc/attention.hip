@@ -185,7 +185,7 @@ __global__ __launch_bounds__(64 * NW) void attn_kernel(const AttnArgs p) {
         const int row = c / NCH, ch = c % NCH;
         const bool live = kv0 + row < p.Tk;
         const u32x4 kk = live ? pk[i] : u32x4{0, 0, 0, 0}, vv = live ? pv[i] : u32x4{0, 0, 0, 0};
-        *(u32x4*)(sK + (BF ? k16_off(row, ch) : k256_off(row, ch))) = kk;
+        *(u32x4*)(sK + (BF ? lds_off(row, ch) : k256_off(row, ch))) = kk;
         *(u32x4*)(sV + (BF ? img_off(row, ch) : v32_off(row, ch))) = vv;
       }
     }
@@ -204,7 +204,7 @@ __global__ __launch_bounds__(64 * NW) void attn_kernel(const AttnArgs p) {
       if constexpr (BF) {
 #pragma unroll
         for (int g = 0; g < 2; ++g) {
-          const u32x4 a = *(const u32x4*)(sK + k16_off(row, 4 * g + fq));
+          const u32x4 a = *(const u32x4*)(sK + lds_off(row, 4 * g + fq));
           s[f] = mfma16<T>(a, qf[g], s[f]);
         }
       } else {
@@ -371,7 +371,7 @@ __global__ __launch_bounds__(64 * NW) void attn_whole_kernel(const AttnArgs p) {
     const int c = tid + i * NT, row = c >> 3, ch = c & 7;
     if (row < rows) {
       const bool live = row < p.Tk;
-      *(u32x4*)(sK + k16_off(row, ch)) = live ? pk[i] : u32x4{0, 0, 0, 0};
+      *(u32x4*)(sK + lds_off(row, ch)) = live ? pk[i] : u32x4{0, 0, 0, 0};
       *(u32x4*)(sV + img_off(row, ch)) = live ? pv[i] : u32x4{0, 0, 0, 0};
     }
   }
@@ -411,7 +411,7 @@ __global__ __launch_bounds__(64 * NW) void attn_whole_kernel(const AttnArgs p) {
     const int row = 16 * f + fr;
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
-      const u32x4 a = *(const u32x4*)(sK + k16_off(row, 4 * g + fq));
+      const u32x4 a = *(const u32x4*)(sK + lds_off(row, 4 * g + fq));
       s[f] = mfma16<T>(a, qf[g], s[f]);
     }
   }

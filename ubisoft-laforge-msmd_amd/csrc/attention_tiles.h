@@ -1,14 +1,12 @@
 // LDS tile layouts of the attention kernels (attention.hip, attention_bwd.hip): byte offsets into [rows][64-element] images.
 // Every function returns the offset of something 16-byte aligned unless it says otherwise; `ch` counts 16-byte chunks of a row.
 #pragma once
-#include "common.h"
+#include "gemm_tiles.h"
 
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 // ---- 16-bit elements, 128-byte rows
-// K image (row reads only): chunk ch (0..7) of `row`; chunks XOR (row >> 1) & 7, so the ds_read_b128 of 16 consecutive rows at one
-// logical chunk is conflict-free
-__device__ __forceinline__ int k16_off(int row, int ch) { return row * 128 + ((ch ^ ((row >> 1) & 7)) << 4); }
+// K image (row reads only): lds_off(row, ch) of gemm_tiles.h, the GEMM kernels' operand image
 // V image, and every image of the backward (row reads AND transposed reads): chunk ch (0..7) of `row`; 32-byte blocks XOR
 // (row >> 1) & 3, the two chunks of a block stay together
 __device__ __forceinline__ int img_off(int row, int ch) { return row * 128 + (((((ch >> 1) ^ ((row >> 1) & 3)) << 1) | (ch & 1)) << 4); }

@@ -13,7 +13,7 @@
 // Operands are swapped (D = W_tile . X_tile^T) so each lane ends up with 4 CONSECUTIVE output
 // columns of one row: 16-B (fp32) / 8-B (bf16) epilogue stores and a float4 bias load.
 // bf16: v_mfma_f32_16x16x32_bf16; fp32 parity mode: v_mfma_f32_16x16x4_f32 (exact fp32 FMA chain).
-#include "common.h"
+#include "gemm_tiles.h"
 #include <atomic>
 #include <utility>
 
@@ -107,8 +107,6 @@ template <> struct Mfma<float> {
   }
 };
 
-__device__ __forceinline__ int lds_off(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
-
 // Row m of the (possibly windowed) A operand -> element offset.  Plain GEMMs skip the division; windowed
 // (conv) rows use an fp32 reciprocal with an exact fix-up (m < 2^24), not a 40-instruction integer divide.
 __device__ __forceinline__ long a_row_offset(const GemmArgs& p, int m) {
@@ -118,6 +116,93 @@ __device__ __forceinline__ long a_row_offset(const GemmArgs& p, int m) {
   if (r < 0) { q -= 1; r += p.rows_per_batch; }
   if (r >= p.rows_per_batch) { q += 1; r -= p.rows_per_batch; }
   return (long)q * p.a_batch_stride + (long)r * p.lda;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Shared pieces of the fragment kernels (gemm_kernel, gemm2_kernel, gemm2p_kernel, gemm2s_kernel); layout in gemm_tiles.h.
+
+// Block id -> tile of the XCD grid (8 / xn) x xn over (M, N) tiles (block ids congruent mod 8 share an XCD's L2): an XCD's L2
+// then holds 1 / xn of the weight matrix instead of all of it.  False for the block ids the grid pads with.
+__device__ __forceinline__ bool xcd_tile(const GemmArgs& p, int pid, int& m_tile, int& n_tile) {
+  const int xcd = pid & 7, slot = pid >> 3;
+  const int xm_n = 8 / p.xn, ntx = (p.nt + p.xn - 1) / p.xn;
+  m_tile = (slot / ntx) * xm_n + (xcd % xm_n);
+  n_tile = (slot % ntx) * p.xn + xcd / xm_n;
+  return m_tile < p.mt && n_tile < p.nt;
+}
+// the operands of problem z = outer * batch_inner + inner of a batched launch
+template <typename T> __device__ __forceinline__ const T* batch_a(const GemmArgs& p, int z) {
+  return (const T*)p.A + (z / p.batch_inner) * p.strideA + (z % p.batch_inner) * p.strideA2;
+}
+template <typename T> __device__ __forceinline__ const T* batch_w(const GemmArgs& p, int z) {
+  return (const T*)p.W + (z / p.batch_inner) * p.strideW + (z % p.batch_inner) * p.strideW2;
+}
+
+// Per-lane LDS-DMA sources of one K-contiguous (BM + BN)-row tile image (A rows, then W rows; 16-bit elements) staged by NLW
+// loader waves with LPT wave-instructions (1 KB of the image) each.  The swizzle is applied HERE, to the source address, because
+// an LDS-DMA wave-instruction writes its 1 KB linearly; out-of-range rows are clamped to a valid row (never stored).
+template <typename T, int BM, int BN, int NLW> struct TileSrc {
+  static constexpr int LPT = (BM + BN) / 8 / NLW;
+  static_assert(NLW * LPT * 8 == BM + BN, "tile chunks must divide over the loader waves");
+  const T* src[LPT];
+  __device__ __forceinline__ void set(const GemmArgs& p, const T* A, const T* W, int m0, int n0, int tid) {
+    const int lane = tid & 63, wid = tid >> 6;
+#pragma unroll
+    for (int i = 0; i < LPT; ++i) {
+      const int id = (i * NLW + wid) * 64 + lane;  // 16-B slot of the tile image (past its end in a wave that loads nothing: clamped, never read)
+      const int row = id >> 3, phys = id & 7;
+      const int c = phys ^ ((row >> 1) & 7);      // logical chunk stored at this physical slot
+      if (row < BM) src[i] = A + a_row_offset(p, min(m0 + row, p.M - 1)) + c * 8;
+      else src[i] = W + (long)min(n0 + row - BM, p.N - 1) * p.ldw + c * 8;
+    }
+  }
+  // K tile kt (64 elements per row) into the stage at `stage_base`
+  __device__ __forceinline__ void issue(unsigned char* stage_base, int kt, int tid) const {
+    const int wid = tid >> 6;
+#pragma unroll
+    for (int i = 0; i < LPT; ++i)
+      __builtin_amdgcn_global_load_lds((gbl_void_t*)(src[i] + kt * 64), (lds_void_t*)(stage_base + (i * NLW + wid) * 1024), 16, 0, 0);
+  }
+};
+
+// The K tile of a staged image (A rows at sa, W rows at sw): two 32-deep k-steps of FM + FN fragment reads and FN x FM multiplies.
+template <typename TI, int FM, int FN>
+__device__ __forceinline__ void k_tile_mma(const unsigned char* sa, const unsigned char* sw, const FragLane& l, f32x4 (&acc)[FN][FM]) {
+#pragma unroll
+  for (int g = 0; g < 2; ++g) {
+    u32x4 fx[FM], fw[FN];
+#pragma unroll
+    for (int j = 0; j < FM; ++j) fx[j] = *(const u32x4*)(sa + lds_off(l.wm + j * 16 + l.fr, g * 4 + l.fq));
+#pragma unroll
+    for (int i = 0; i < FN; ++i) fw[i] = *(const u32x4*)(sw + lds_off(l.wn + i * 16 + l.fr, g * 4 + l.fq));
+#pragma unroll
+    for (int i = 0; i < FN; ++i)
+#pragma unroll
+      for (int j = 0; j < FM; ++j) Mfma<TI>::run(fw[i], fx[j], acc[i][j]);
+  }
+}
+// Explicit software pipeline: issue the fragment reads of BOTH 32-deep k-steps, then the MFMAs.  Left to
+// itself hipcc re-uses 16 fragment registers and emits read / lgkmcnt(0) / 4 MFMA groups, exposing the LDS
+// latency four times per K tile; pinned like this the second k-step's reads land behind the first's MFMAs.
+template <typename TI, int FM, int FN>
+__device__ __forceinline__ void k_tile_mma_pipelined(const unsigned char* sa, const unsigned char* sw, const FragLane& l, f32x4 (&acc)[FN][FM]) {
+  u32x4 fx[2][FM], fw[2][FN];
+#pragma unroll
+  for (int g = 0; g < 2; ++g) {
+#pragma unroll
+    for (int j = 0; j < FM; ++j) fx[g][j] = *(const u32x4*)(sa + lds_off(l.wm + j * 16 + l.fr, g * 4 + l.fq));
+#pragma unroll
+    for (int i = 0; i < FN; ++i) fw[g][i] = *(const u32x4*)(sw + lds_off(l.wn + i * 16 + l.fr, g * 4 + l.fq));
+  }
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int g = 0; g < 2; ++g) {
+#pragma unroll
+    for (int i = 0; i < FN; ++i)
+#pragma unroll
+      for (int j = 0; j < FM; ++j) Mfma<TI>::run(fw[g][i], fx[g][j], acc[i][j]);
+    __builtin_amdgcn_sched_barrier(0);
+  }
 }
 
 // Epilogue of the fragment kernels (gemm_kernel, gemm2_kernel, gemm2p_kernel, gemm2s_kernel; gemm8_kernel stores through LDS and
@@ -159,6 +244,28 @@ template <typename TO> __device__ __forceinline__ void store4_out(TO* p, const f
     if (wt) store8_wt(p, __builtin_bit_cast(u32x2, o));
     else *(typename Vec4T<TO>::type*)p = o;
   }
+}
+
+// Dropout of the four values at flat index idx .. idx + 3 of a contiguous (M, N) C: the keep mask is msmd_dropout's.
+__device__ __forceinline__ void dropout4(const GemmArgs& p, long idx, float (&v)[4]) {
+  const Philox4 rb = dropout_bits(p.rng, p.site, (unsigned long)(idx >> 2));
+  const unsigned thr = dropout_threshold(p.p_drop);
+  const float c = 1.0f / (1.0f - p.p_drop);
+  v[0] = rb.x >= thr ? v[0] * c : 0.f;
+  v[1] = rb.y >= thr ? v[1] * c : 0.f;
+  v[2] = rb.z >= thr ? v[2] * c : 0.f;
+  v[3] = rb.w >= thr ? v[3] * c : 0.f;
+}
+// Paired 16-byte stores: lanes l and l ^ 16 hold columns 4 fq .. 4 fq + 3 and the next four of the same rows.
+// They swap one fragment row each (even fq keeps row j0 and takes the partner's half of it, odd fq keeps row
+// j0 + 1), so every lane issues ONE 16-byte store per fragment-row pair instead of two 8-byte ones.
+// a / b: the lane's packed values of rows j0 / j0 + 1.  The result goes to row j0 + odd, 4 columns to the left when odd.
+__device__ __forceinline__ u32x4 pair_swap(const u32x2 a, const u32x2 b, bool odd) {
+  const u32x2 send = odd ? a : b;
+  u32x2 recv;
+  recv[0] = __shfl_xor(send[0], 16, 64);
+  recv[1] = __shfl_xor(send[1], 16, 64);
+  return odd ? u32x4{recv[0], recv[1], b[0], b[1]} : u32x4{a[0], a[1], recv[0], recv[1]};
 }
 
 // Interior tiles (fully inside M x N, vector-aligned): straight-line code, no per-element bounds checks.
@@ -207,14 +314,7 @@ __device__ __forceinline__ void gemm_epilogue_interior(const GemmArgs& p, const 
       for (int e = 0; e < 4; ++e) v[e] = act_out_c<TO, ACT>(v[e], p.act);
     }
     if (!LEAN && p.p_drop > 0.f) {
-      const long idx = (long)(m_base + j * 16 + fr) * p.N + (n_base + i * 16 + fq * 4);
-      const Philox4 rb = dropout_bits(p.rng, p.site, (unsigned long)(idx >> 2));
-      const unsigned thr = dropout_threshold(p.p_drop);
-      const float c = 1.0f / (1.0f - p.p_drop);
-      v[0] = rb.x >= thr ? v[0] * c : 0.f;
-      v[1] = rb.y >= thr ? v[1] * c : 0.f;
-      v[2] = rb.z >= thr ? v[2] * c : 0.f;
-      v[3] = rb.w >= thr ? v[3] * c : 0.f;
+      dropout4(p, (long)(m_base + j * 16 + fr) * p.N + (n_base + i * 16 + fq * 4), v);
     }
     if (R) {
 #pragma unroll
@@ -223,10 +323,7 @@ __device__ __forceinline__ void gemm_epilogue_interior(const GemmArgs& p, const 
   };
   if constexpr (sizeof(TO) == 2 && FM % 2 == 0) {
     if (p.flags & GF_PAIRED_STORES) {
-      // Paired 16-byte stores: lanes l and l ^ 16 hold columns 4 fq .. 4 fq + 3 and the next four of the same rows.
-      // They swap one fragment row each (even fq keeps row j0 and takes the partner's half of it, odd fq keeps row
-      // j0 + 1), so every lane issues ONE 16-byte store per fragment-row pair instead of two 8-byte ones.
-      const bool odd = fq & 1;
+      const bool odd = fq & 1;     // see pair_swap
 #pragma unroll
       for (int jp = 0; jp < FM / 2; ++jp) {
 #pragma unroll
@@ -236,11 +333,7 @@ __device__ __forceinline__ void gemm_epilogue_interior(const GemmArgs& p, const 
           finish(i, 2 * jp + 1, v1);
           const u32x2 a = __builtin_bit_cast(u32x2, pack4<TO>(v0[0], v0[1], v0[2], v0[3]));
           const u32x2 b = __builtin_bit_cast(u32x2, pack4<TO>(v1[0], v1[1], v1[2], v1[3]));
-          const u32x2 send = odd ? a : b;
-          u32x2 recv;
-          recv[0] = __shfl_xor(send[0], 16, 64);
-          recv[1] = __shfl_xor(send[1], 16, 64);
-          const u32x4 o = odd ? u32x4{recv[0], recv[1], b[0], b[1]} : u32x4{a[0], a[1], recv[0], recv[1]};
+          const u32x4 o = pair_swap(a, b, odd);
           TO* dst = C + (long)(2 * jp + (odd ? 1 : 0)) * 16 * p.ldc + i * 16 - (odd ? 4 : 0);
           if (wt) store16_wt(dst, o);
           else *(u32x4*)dst = o;
@@ -303,15 +396,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, const f32x4 (&a
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = act_out_c<TO, ACT>(v[e], p.act);
       }
-      if (!LEAN && p.p_drop > 0.f) {   // launcher guarantees N % 4 == 0 and ldc == N here
-        const Philox4 rb = dropout_bits(p.rng, p.site, (unsigned long)(((long)m * p.N + n) >> 2));
-        const unsigned thr = dropout_threshold(p.p_drop);
-        const float c = 1.0f / (1.0f - p.p_drop);
-        v[0] = rb.x >= thr ? v[0] * c : 0.f;
-        v[1] = rb.y >= thr ? v[1] * c : 0.f;
-        v[2] = rb.z >= thr ? v[2] * c : 0.f;
-        v[3] = rb.w >= thr ? v[3] * c : 0.f;
-      }
+      if (!LEAN && p.p_drop > 0.f) dropout4(p, (long)m * p.N + n, v);   // launcher guarantees N % 4 == 0 and ldc == N here
       if (p.vec_ok && n + 3 < p.N) {
         if (R) {
           const TO* rp = R + (long)m * p.ldr + n;
@@ -387,7 +472,8 @@ __device__ __forceinline__ void ln_finish(const float* stats, int nt, int M, int
 // first store, for every workgroup of a one-round launch at the same moment, is then behind the K loop.
 // GB = false (the 10-wave 160 x 128 kernel: 168 registers): bias and residual fragments only; gamma / beta, which every workgroup reads and
 // the L2 holds, are loaded in the epilogue as without EARLY (all four were 68 bytes of scratch there).
-template <typename TO, int FM, int FN, bool GB = true> struct LnResOps { f32x4 bv[FN], xv[GB ? FN : 1], yv[GB ? FN : 1]; typename Vec4T<TO>::type rr[FM][FN]; };
+template <typename TO, int FM, int FN, bool GB = true> struct LnResOps { static constexpr bool gb = GB; f32x4 bv[FN], xv[GB ? FN : 1], yv[GB ? FN : 1]; typename Vec4T<TO>::type rr[FM][FN]; };
+struct NoEarlyOps {};     // what a kernel without early operands hands to gemm_run_epilogue
 template <typename TO, int FM, int FN, bool GB>
 __device__ __forceinline__ void ln_res_issue(const GemmArgs& p, int m_base, int n_base, int fr, int fq, LnResOps<TO, FM, FN, GB>& o) {
   typedef typename Vec4T<TO>::type V4;
@@ -511,15 +597,10 @@ __device__ __forceinline__ void gemm_epilogue_ln(const GemmArgs& p, const f32x4 
       }
       bool stored = false;
       if constexpr (sizeof(TO) == 2) {
-        if (pair) {     // lanes l and l ^ 16 swap one fragment row: one 16-byte store each (see gemm_epilogue_interior)
+        if (pair) {     // lanes l and l ^ 16 swap one fragment row: one 16-byte store each (see pair_swap)
 #pragma unroll
           for (int jp = 0; jp + 1 < FM; jp += 2) {
-            const u32x2 a = __builtin_bit_cast(u32x2, o[jp]), b = __builtin_bit_cast(u32x2, o[jp + 1]);
-            const u32x2 send = odd ? a : b;
-            u32x2 recv;
-            recv[0] = __shfl_xor(send[0], 16, 64);
-            recv[1] = __shfl_xor(send[1], 16, 64);
-            const u32x4 w = odd ? u32x4{recv[0], recv[1], b[0], b[1]} : u32x4{a[0], a[1], recv[0], recv[1]};
+            const u32x4 w = pair_swap(__builtin_bit_cast(u32x2, o[jp]), __builtin_bit_cast(u32x2, o[jp + 1]), odd);
             const int m = m_base + jp * 16 + (odd ? 16 : 0) + fr;
             if (m < p.M) *(u32x4*)((TO*)p.C + (long)m * p.ldc + n + i * 16 - (odd ? 4 : 0)) = w;
           }
@@ -553,6 +634,30 @@ __device__ __forceinline__ void gemm_epilogue_ln(const GemmArgs& p, const f32x4 
   }
 }
 
+// The 192-row tile: the row statistics are loaded HERE, in the epilogue (no registers to spare in the K loop).
+template <typename TO, int FM, int FN, int MODE, int ACT>
+__device__ __forceinline__ void gemm_epilogue_ln_late(const GemmArgs& p, const f32x4 (&acc)[FN][FM], int m_base, int n_base, int fr, int fq) {
+  f32x2 late[FM][4];
+  if constexpr (MODE == 1) ln_issue<FM>(p.a_stats, p.a_nt, p.M, m_base, fr, fq, late);
+  else if (p.r_stats) ln_issue<FM>(p.r_stats, p.r_nt, p.M, m_base, fr, fq, late);
+  gemm_epilogue_ln<TO, FM, FN, MODE, ACT>(p, acc, m_base, n_base, fr, fq, late);
+}
+
+// The epilogue of a gemm2_kernel / gemm2p_kernel instantiation that carries ONE family (EPI_PLAIN, EPI_LN_OPERAND, EPI_LN_RESIDUAL).
+// LNK: the wave tile is one statistics slab, i.e. the LayerNorm forms exist (else the family falls back to the plain epilogue);
+// LN_LATE: they load the statistics themselves, else `lnraw` holds what ln_issue requested before the K loop; EARLY: the
+// LnResOps requested there too, or NoEarlyOps.
+template <typename TO, int FM, int FN, int EPI, int ACTK, bool LNK, bool LN_LATE, int LR, typename EARLY>
+__device__ __forceinline__ void gemm_run_epilogue(const GemmArgs& p, const f32x4 (&acc)[FN][FM], int z, int m_base, int n_base, int fr, int fq,
+                                                  const f32x2 (&lnraw)[LR][4], const EARLY& early) {
+  static_assert(EPI != EPI_ALL, "the run-time choice among all epilogues is gemm2_kernel's");
+  if constexpr (EPI == EPI_PLAIN) gemm_epilogue<TO, FM, FN, false, true, ACTK>(p, acc, z, m_base, n_base, fr, fq);
+  else if constexpr (!std::is_same_v<EARLY, NoEarlyOps>) gemm_epilogue_ln<TO, FM, FN, 2, ACTK, true, EARLY::gb>(p, acc, m_base, n_base, fr, fq, lnraw, &early);
+  else if constexpr (LNK && LN_LATE) gemm_epilogue_ln_late<TO, FM, FN, EPI - 1, ACTK>(p, acc, m_base, n_base, fr, fq);
+  else if constexpr (LNK) gemm_epilogue_ln<TO, FM, FN, EPI - 1, ACTK>(p, acc, m_base, n_base, fr, fq, lnraw);
+  else gemm_epilogue<TO, FM, FN, sizeof(TO) == 2, false, ACTK>(p, acc, z, m_base, n_base, fr, fq);
+}
+
 template <typename T, typename TO, int BM, int BN>
 __global__ __launch_bounds__(256) void gemm_kernel(const GemmArgs p) {
   constexpr int E = 16 / sizeof(T);     // elements per 16-B chunk
@@ -568,11 +673,10 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmArgs p) {
   const int m_tile = (slot / p.nt) * 8 + xcd, n_tile = slot % p.nt;
   if (m_tile >= p.mt) return;
   const int z = blockIdx.z;
-  const int zo = z / p.batch_inner, zi = z % p.batch_inner;
-  const T* __restrict__ A = (const T*)p.A + zo * p.strideA + zi * p.strideA2;
-  const T* __restrict__ W = (const T*)p.W + zo * p.strideW + zi * p.strideW2;
+  const T* __restrict__ A = batch_a<T>(p, z);
+  const T* __restrict__ W = batch_w<T>(p, z);
   const int m0 = m_tile * BM, n0 = n_tile * BN;
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int tid = threadIdx.x;
 
   // per-thread staging assignments (fixed across K steps)
   const T* a_ptr[LA]; bool a_ok[LA]; int a_lds[LA];
@@ -614,13 +718,9 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmArgs p) {
     for (int i = 0; i < LW; ++i) *(u32x4*)(base + w_lds[i]) = rw[i];
   };
 
-  const int wm = (wid >> 1) * (BM / 2), wn = (wid & 1) * (BN / 2);
-  const int fr = lane & 15, fq = lane >> 4;
+  const FragLane l = frag_lane<BM, BN, 2, 2>(tid);
   f32x4 acc[FN][FM];
-#pragma unroll
-  for (int i = 0; i < FN; ++i)
-#pragma unroll
-    for (int j = 0; j < FM; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
 
   const int nk = (p.K + BKE - 1) / BKE;
   load_global(0);
@@ -630,24 +730,12 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmArgs p) {
     const int cur = kt & 1;
     if (kt + 1 < nk) load_global((kt + 1) * BKE);
     const unsigned char* sa = smem + cur * (BM + BN) * 128;
-    const unsigned char* sw = sa + BM * 128;
-#pragma unroll
-    for (int g = 0; g < 2; ++g) {
-      u32x4 fx[FM], fw[FN];
-#pragma unroll
-      for (int j = 0; j < FM; ++j) fx[j] = *(const u32x4*)(sa + lds_off(wm + j * 16 + fr, g * 4 + fq));
-#pragma unroll
-      for (int i = 0; i < FN; ++i) fw[i] = *(const u32x4*)(sw + lds_off(wn + i * 16 + fr, g * 4 + fq));
-#pragma unroll
-      for (int i = 0; i < FN; ++i)
-#pragma unroll
-        for (int j = 0; j < FM; ++j) Mfma<T>::run(fw[i], fx[j], acc[i][j]);
-    }
+    k_tile_mma<T, FM, FN>(sa, sa + BM * 128, l, acc);
     if (kt + 1 < nk) store_lds(cur ^ 1);
     __syncthreads();
   }
 
-  gemm_epilogue<TO, FM, FN>(p, acc, z, m0 + wm, n0 + wn, fr, fq);
+  gemm_epilogue<TO, FM, FN>(p, acc, z, m0 + l.wm, n0 + l.wn, l.fr, l.fq);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -657,9 +745,6 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmArgs p) {
 // address because an LDS-DMA wave-instruction writes 1 KiB linearly (cdna_hip_programming.md rule 21).
 // Requires K % 64 == 0 (no K tail: LDS-DMA cannot zero-fill); out-of-range rows are clamped to a valid
 // row (their products are never stored).
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void gbl_void_t;
-
 // EPI: which epilogues this instantiation carries.  0 = all of them behind run-time tests (training: pre-activation copy,
 // dropout, activation backward, both LayerNorm forms); 1 = the plain inference epilogue only (bias, activation, residual);
 // 2 / 3 = the LayerNorm-operand / LayerNorm-residual form only.  One instantiation with everything is 127 KB of code of which a
@@ -688,52 +773,28 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8 && NSTAGE * (BM + BN) *
   constexpr int NLW = gemm2_loader_waves((BM + BN) / 8, NW);   // waves that issue LDS-DMA
   constexpr int LPT = (BM + BN) / 8 / NLW;  // LDS-DMA instructions per thread of a loader wave per K tile
   constexpr int FM = BM / WM / 16, FN = BN / WN / 16;
-  static_assert((BM + BN) % 8 == 0 && NLW * LPT * 8 == BM + BN && (NLW == NW || NLW * 2 > NW), "tile chunks must divide over the loader waves");
+  static_assert((BM + BN) % 8 == 0 && (NLW == NW || NLW * 2 > NW), "tile chunks must divide over the loader waves");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
+  int m_tile, n_tile;
   const int pid = blockIdx.x;
-  const int xcd = pid & 7, slot = pid >> 3;
-  // XCD grid (8 / xn) x xn over (M, N) tiles: an XCD's L2 then holds 1 / xn of the weight matrix instead of all of it
-  const int xm_n = 8 / p.xn, ntx = (p.nt + p.xn - 1) / p.xn;
-  const int m_tile = (slot / ntx) * xm_n + (xcd % xm_n), n_tile = (slot % ntx) * p.xn + xcd / xm_n;
-  if (m_tile >= p.mt || n_tile >= p.nt) return;
+  if (!xcd_tile(p, pid, m_tile, n_tile)) return;
   const int z = blockIdx.z;
-  const int zo = z / p.batch_inner, zi = z % p.batch_inner;
-  const bf16_t* __restrict__ A = (const bf16_t*)p.A + zo * p.strideA + zi * p.strideA2;
-  const bf16_t* __restrict__ W = (const bf16_t*)p.W + zo * p.strideW + zi * p.strideW2;
   const int m0 = m_tile * BM, n0 = n_tile * BN;
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int tid = threadIdx.x;
 
-  const bf16_t* src[LPT];
-#pragma unroll
-  for (int i = 0; i < LPT; ++i) {
-    const int id = (i * NLW + wid) * 64 + lane;  // 16-B slot of the tile image (past its end in a wave that loads nothing: clamped, never read)
-    const int row = id >> 3, phys = id & 7;
-    const int c = phys ^ ((row >> 1) & 7);      // logical chunk stored at this physical slot
-    if (row < BM) {
-      const int m = min(m0 + row, p.M - 1);
-      src[i] = A + a_row_offset(p, m) + c * 8;
-    } else {
-      const int n = min(n0 + row - BM, p.N - 1);
-      src[i] = W + (long)n * p.ldw + c * 8;
-    }
-  }
-  const bool loader = NLW == NW || __builtin_amdgcn_readfirstlane(wid) < NLW;
+  TileSrc<bf16_t, BM, BN, NLW> src;
+  src.set(p, batch_a<bf16_t>(p, z), batch_w<bf16_t>(p, z), m0, n0, tid);
+  const bool loader = NLW == NW || __builtin_amdgcn_readfirstlane(tid >> 6) < NLW;
   auto issue = [&](int kt, int stage) {
     if constexpr (NLW != NW) { if (!loader) return; }
-#pragma unroll
-    for (int i = 0; i < LPT; ++i)
-      __builtin_amdgcn_global_load_lds((gbl_void_t*)(src[i] + kt * 64),
-                                       (lds_void_t*)(smem + stage * STAGE + (i * NLW + wid) * 1024), 16, 0, 0);
+    src.issue(smem + stage * STAGE, kt, tid);
   };
 
-  const int wm = (wid / WN) * (BM / WM), wn = (wid % WN) * (BN / WN);
-  const int fr = lane & 15, fq = lane >> 4;
+  const FragLane l = frag_lane<BM, BN, WM, WN>(tid);
+  const int wm = l.wm, wn = l.wn, fr = l.fr, fq = l.fq;
   f32x4 acc[FN][FM];
-#pragma unroll
-  for (int i = 0; i < FN; ++i)
-#pragma unroll
-    for (int j = 0; j < FM; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
 
   const int nk = p.K / 64;
   // The 4-wave 64 x 128 kernel (one workgroup per CU, 256 registers) requests everything its LayerNorm-residual epilogue reads
@@ -748,8 +809,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8 && NSTAGE * (BM + BN) *
   constexpr bool EARLY_OPS = LNK && EPI == 3 && ((NW == 4 && BM == 64) || (NW == 10 && BM == 160)) && BN == 128;
   f32x2 lnraw[(LNK && !LN_LATE) ? FM : 1][4];
   constexpr bool EARLY_GB = NW == 4;
-  std::conditional_t<EARLY_OPS, LnResOps<TO, FM, FN, EARLY_GB>, char> early;
-  (void)early;
+  std::conditional_t<EARLY_OPS, LnResOps<TO, FM, FN, EARLY_GB>, NoEarlyOps> early;
   if constexpr (EARLY_OPS) {
     if (p.r_stats) ln_issue<FM>(p.r_stats, p.r_nt, p.M, m0 + wm, fr, fq, lnraw);
     ln_res_issue<TO, FM, FN, EARLY_GB>(p, m0 + wm, n0 + wn, fr, fq, early);
@@ -772,84 +832,41 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8 && NSTAGE * (BM + BN) *
   }
   int stage = 0;
   for (int kt = 0; kt < nk; ++kt) {
-    if (kt + NSTAGE - 2 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NSTAGE - 2) * LPT) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if (kt + NSTAGE - 1 < nk) issue(kt + NSTAGE - 1, (stage + NSTAGE - 1) % NSTAGE);
+    ring_step<NSTAGE, LPT>(kt, nk, stage, issue);
     const unsigned char* sa = smem + stage * STAGE;
-    const unsigned char* sw = sa + BM * 128;
-    if constexpr (PIPE) {
-      // Explicit software pipeline: issue the fragment reads of BOTH 32-deep k-steps, then the MFMAs.  Left to
-      // itself hipcc re-uses 16 fragment registers and emits read / lgkmcnt(0) / 4 MFMA groups, exposing the LDS
-      // latency four times per K tile; pinned like this the second k-step's reads land behind the first's MFMAs.
-      u32x4 fx[2][FM], fw[2][FN];
-#pragma unroll
-      for (int g = 0; g < 2; ++g) {
-#pragma unroll
-        for (int j = 0; j < FM; ++j) fx[g][j] = *(const u32x4*)(sa + lds_off(wm + j * 16 + fr, g * 4 + fq));
-#pragma unroll
-        for (int i = 0; i < FN; ++i) fw[g][i] = *(const u32x4*)(sw + lds_off(wn + i * 16 + fr, g * 4 + fq));
-      }
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int g = 0; g < 2; ++g) {
-#pragma unroll
-        for (int i = 0; i < FN; ++i)
-#pragma unroll
-          for (int j = 0; j < FM; ++j) Mfma<TI>::run(fw[g][i], fx[g][j], acc[i][j]);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    } else {
-#pragma unroll
-      for (int g = 0; g < 2; ++g) {
-        u32x4 fx[FM], fw[FN];
-#pragma unroll
-        for (int j = 0; j < FM; ++j) fx[j] = *(const u32x4*)(sa + lds_off(wm + j * 16 + fr, g * 4 + fq));
-#pragma unroll
-        for (int i = 0; i < FN; ++i) fw[i] = *(const u32x4*)(sw + lds_off(wn + i * 16 + fr, g * 4 + fq));
-#pragma unroll
-        for (int i = 0; i < FN; ++i)
-#pragma unroll
-          for (int j = 0; j < FM; ++j) Mfma<TI>::run(fw[i], fx[j], acc[i][j]);
-      }
-    }
-    stage = (stage + 1 == NSTAGE) ? 0 : stage + 1;
+    if constexpr (PIPE) k_tile_mma_pipelined<TI, FM, FN>(sa, sa + BM * 128, l, acc);
+    else k_tile_mma<TI, FM, FN>(sa, sa + BM * 128, l, acc);
+    stage = ring_next<NSTAGE>(stage);
   }
   // the 192-row tile has no register to spare: the lane's fragment coordinates are derived again here instead of living
   // through the K loop (one of them went to scratch otherwise)
-  int tid_e = tid;
-  if constexpr (LN_LATE) asm volatile("" : "+v"(tid_e));
-  const int wm_e = ((tid_e >> 6) / WN) * (BM / WM), wn_e = ((tid_e >> 6) % WN) * (BN / WN);
-  const int fr_e = tid_e & 15, fq_e = (tid_e & 63) >> 4;
-  auto run_epilogue = [&]() {
-    if constexpr (EPI == 1) { gemm_epilogue<TO, FM, FN, false, true, ACTK>(p, acc, z, m0 + wm_e, n0 + wn_e, fr_e, fq_e); return; }
-    if constexpr (LNK && !LN_LATE && EPI == 2) { gemm_epilogue_ln<TO, FM, FN, 1, ACTK>(p, acc, m0 + wm_e, n0 + wn_e, fr_e, fq_e, lnraw); return; }
-    if constexpr (EARLY_OPS) { gemm_epilogue_ln<TO, FM, FN, 2, ACTK, true, EARLY_GB>(p, acc, m0 + wm_e, n0 + wn_e, fr_e, fq_e, lnraw, &early); return; }
-    if constexpr (LNK && !LN_LATE && EPI == 3) { gemm_epilogue_ln<TO, FM, FN, 2, ACTK>(p, acc, m0 + wm_e, n0 + wn_e, fr_e, fq_e, lnraw); return; }
-    if constexpr (LNK && LN_LATE && (EPI == 2 || EPI == 3)) {      // the 192-row tile: statistics loaded here (no registers to spare in the K loop)
-      f32x2 late[FM][4];
-      if constexpr (EPI == 2) ln_issue<FM>(p.a_stats, p.a_nt, p.M, m0 + wm_e, fr_e, fq_e, late);
-      else if (p.r_stats) ln_issue<FM>(p.r_stats, p.r_nt, p.M, m0 + wm_e, fr_e, fq_e, late);
-      gemm_epilogue_ln<TO, FM, FN, EPI - 1, ACTK>(p, acc, m0 + wm_e, n0 + wn_e, fr_e, fq_e, late);
-      return;
-    }
-    if constexpr (LNK && !LN_LATE) {
-      if (p.a_stats) { gemm_epilogue_ln<TO, FM, FN, 1, ACTK>(p, acc, m0 + wm_e, n0 + wn_e, fr_e, fq_e, lnraw); return; }
-      if (p.r_stats || p.stats_out) { gemm_epilogue_ln<TO, FM, FN, 2, ACTK>(p, acc, m0 + wm_e, n0 + wn_e, fr_e, fq_e, lnraw); return; }
-    }
-    if constexpr (LNK && LN_LATE) {
-      if (p.a_stats || p.r_stats || p.stats_out) {
-        f32x2 late[FM][4];
-        if (p.a_stats) ln_issue<FM>(p.a_stats, p.a_nt, p.M, m0 + wm_e, fr_e, fq_e, late);
-        else if (p.r_stats) ln_issue<FM>(p.r_stats, p.r_nt, p.M, m0 + wm_e, fr_e, fq_e, late);
-        if (p.a_stats) gemm_epilogue_ln<TO, FM, FN, 1, ACTK>(p, acc, m0 + wm_e, n0 + wn_e, fr_e, fq_e, late);
-        else gemm_epilogue_ln<TO, FM, FN, 2, ACTK>(p, acc, m0 + wm_e, n0 + wn_e, fr_e, fq_e, late);
-        return;
+  const FragLane le = frag_lane<BM, BN, WM, WN>(LN_LATE ? opaque_tid(tid) : tid);
+  if constexpr (EPI != EPI_ALL) {
+    gemm_run_epilogue<TO, FM, FN, EPI, ACTK, LNK, LN_LATE>(p, acc, z, m0 + le.wm, n0 + le.wn, le.fr, le.fq, lnraw, early);
+  } else {
+    // every epilogue behind run-time tests: the form the call's pointers ask for.  (Spelled out in a lambda, the 192-row tile's late
+    // statistics with it: as a function of the arguments, or with gemm_epilogue_ln_late per branch, the compiler emits one more
+    // load of a statistics pair in the 64-row and 192-row tiles, and the 192-row tile takes 128 registers instead of 124.)
+    const int wm_e = le.wm, wn_e = le.wn, fr_e = le.fr, fq_e = le.fq;
+    auto run_epilogue = [&]() {
+      if constexpr (LNK && !LN_LATE) {
+        if (p.a_stats) { gemm_epilogue_ln<TO, FM, FN, 1, ACTK>(p, acc, m0 + wm_e, n0 + wn_e, fr_e, fq_e, lnraw); return; }
+        if (p.r_stats || p.stats_out) { gemm_epilogue_ln<TO, FM, FN, 2, ACTK>(p, acc, m0 + wm_e, n0 + wn_e, fr_e, fq_e, lnraw); return; }
       }
-    }
-    gemm_epilogue<TO, FM, FN, sizeof(TO) == 2, false, ACTK>(p, acc, z, m0 + wm_e, n0 + wn_e, fr_e, fq_e);
-  };
-  run_epilogue();
+      if constexpr (LNK && LN_LATE) {
+        if (p.a_stats || p.r_stats || p.stats_out) {
+          f32x2 late[FM][4];
+          if (p.a_stats) ln_issue<FM>(p.a_stats, p.a_nt, p.M, m0 + wm_e, fr_e, fq_e, late);
+          else if (p.r_stats) ln_issue<FM>(p.r_stats, p.r_nt, p.M, m0 + wm_e, fr_e, fq_e, late);
+          if (p.a_stats) gemm_epilogue_ln<TO, FM, FN, 1, ACTK>(p, acc, m0 + wm_e, n0 + wn_e, fr_e, fq_e, late);
+          else gemm_epilogue_ln<TO, FM, FN, 2, ACTK>(p, acc, m0 + wm_e, n0 + wn_e, fr_e, fq_e, late);
+          return;
+        }
+      }
+      gemm_epilogue<TO, FM, FN, sizeof(TO) == 2, false, ACTK>(p, acc, z, m0 + wm_e, n0 + wn_e, fr_e, fq_e);
+    };
+    run_epilogue();
+  }
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -863,12 +880,10 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8 && NSTAGE * (BM + BN) *
 template <typename TO, int BM, int BN, int WM, int WN, typename TI, int EPIA>
 __global__ __launch_bounds__(WM * WN * 64, 4) void gemm2p_kernel(const GemmArgs p) {
   constexpr int EPI = epia_family(EPIA), ACTK = epia_act(EPIA);
-  constexpr int NW = WM * WN, NT = NW * 64;
+  constexpr int NW = WM * WN;
   constexpr int STAGE = (BM + BN) * 128;
-  constexpr int LPT = (BM + BN) * 8 / NT;
   constexpr int FM = BM / WM / 16, FN = BN / WN / 16;
   static_assert(EPI >= 1 && EPI <= 3 && sizeof(TO) == 2 && NW == 8 && WN == 2 && BN == 128 && (FM == 2 || FM == 3), "the hot 8-wave tiles, inference epilogues");
-  static_assert((BM + BN) * 8 % NT == 0, "tile chunks must divide over the threads");
   constexpr bool LN_LATE = FM == 3;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x;
@@ -879,110 +894,55 @@ __global__ __launch_bounds__(WM * WN * 64, 4) void gemm2p_kernel(const GemmArgs 
   // first block id >= vb of this workgroup's sequence that maps to a tile (the XCD grid pads), or -1
   auto next_tile = [&](int vb, int& m0, int& n0) -> int {
     for (; vb < vgrid; vb += gridDim.x) {
-      const int xcd = vb & 7, slot = vb >> 3;
-      const int m_tile = (slot / ntx) * xm_n + (xcd % xm_n), n_tile = (slot % ntx) * p.xn + xcd / xm_n;
-      if (m_tile < p.mt && n_tile < p.nt) { m0 = m_tile * BM; n0 = n_tile * BN; return vb; }
+      int m_tile, n_tile;
+      if (xcd_tile(p, vb, m_tile, n_tile)) { m0 = m_tile * BM; n0 = n_tile * BN; return vb; }
     }
     return -1;
   };
-  // Everything derived from the lane id is derived AGAIN per tile and per phase (t_k for the K loop, t_e for the epilogue) from
-  // copies the compiler cannot match: kept across the tile loop, the K loop's fragment / staging offsets would be live in
+  // Everything derived from the lane id is derived AGAIN per tile and per phase (t_k for the K loop, another for the epilogue) from
+  // copies the compiler cannot match (opaque_tid): kept across the tile loop, the K loop's fragment / staging offsets would be live in
   // the epilogue and the epilogue's in the K loop (+30 registers: 90-250 bytes of scratch in every LayerNorm form)
-  const TI* src[LPT];
-  auto set_src = [&](int m0, int n0, int t) {
-    const int lane = t & 63, wid = t >> 6;
-#pragma unroll
-    for (int i = 0; i < LPT; ++i) {
-      const int id = (i * NW + wid) * 64 + lane;  // 16-B slot of the tile image
-      const int row = id >> 3, phys = id & 7;
-      const int c = phys ^ ((row >> 1) & 7);      // logical chunk stored at this physical slot
-      if (row < BM) src[i] = A + a_row_offset(p, min(m0 + row, p.M - 1)) + c * 8;
-      else src[i] = W + (long)min(n0 + row - BM, p.N - 1) * p.ldw + c * 8;
-    }
-  };
-  auto issue = [&](int kt, int stage, int t) {
-    const int wid = t >> 6;
-#pragma unroll
-    for (int i = 0; i < LPT; ++i)
-      __builtin_amdgcn_global_load_lds((gbl_void_t*)(src[i] + kt * 64),
-                                       (lds_void_t*)(smem + stage * STAGE + (i * NW + wid) * 1024), 16, 0, 0);
-  };
+  TileSrc<TI, BM, BN, NW> src;
   int m0 = 0, n0 = 0;
   int vb = next_tile(blockIdx.x, m0, n0);
   if (vb < 0) return;
   const int nk = p.K / 64;
-  set_src(m0, n0, tid);
+  src.set(p, A, W, m0, n0, tid);
   int stage = 0;
-  issue(0, 0, tid);
+  src.issue(smem, 0, tid);
   for (;;) {
-    int t_k = tid;
-    asm volatile("" : "+v"(t_k));
-    const int wm = ((t_k >> 6) / WN) * (BM / WM), wn = ((t_k >> 6) % WN) * (BN / WN);
-    const int fr = t_k & 15, fq = (t_k & 63) >> 4;
+    const int t_k = opaque_tid(tid);
+    const FragLane l = frag_lane<BM, BN, WM, WN>(t_k);
     f32x2 lnraw[LN_LATE ? 1 : FM][4];
     if constexpr (!LN_LATE && EPI != 1) {
-      if constexpr (EPI == 2) ln_issue<FM>(p.a_stats, p.a_nt, p.M, m0 + wm, fr, fq, lnraw);
-      else if (p.r_stats) ln_issue<FM>(p.r_stats, p.r_nt, p.M, m0 + wm, fr, fq, lnraw);
+      if constexpr (EPI == 2) ln_issue<FM>(p.a_stats, p.a_nt, p.M, m0 + l.wm, l.fr, l.fq, lnraw);
+      else if (p.r_stats) ln_issue<FM>(p.r_stats, p.r_nt, p.M, m0 + l.wm, l.fr, l.fq, lnraw);
     }
     f32x4 acc[FN][FM];
-#pragma unroll
-    for (int i = 0; i < FN; ++i)
-#pragma unroll
-      for (int j = 0; j < FM; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    zero_acc(acc);
     int m0n = 0, n0n = 0, vbn = -1;
     for (int kt = 0; kt < nk; ++kt) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
       if (kt + 1 < nk) {
-        issue(kt + 1, stage ^ 1, t_k);
+        src.issue(smem + (stage ^ 1) * STAGE, kt + 1, t_k);
       } else {
         // the other stage is free (every wave is past this barrier, i.e. done reading it): the next tile's first stage
         vbn = next_tile(vb + (int)gridDim.x, m0n, n0n);
-        if (vbn >= 0) { set_src(m0n, n0n, t_k); issue(0, stage ^ 1, t_k); }
+        if (vbn >= 0) { src.set(p, A, W, m0n, n0n, t_k); src.issue(smem + (stage ^ 1) * STAGE, 0, t_k); }
       }
       const unsigned char* sa = smem + stage * STAGE;
-      const unsigned char* sw = sa + BM * 128;
-      u32x4 fx[2][FM], fw[2][FN];
-#pragma unroll
-      for (int g = 0; g < 2; ++g) {
-#pragma unroll
-        for (int j = 0; j < FM; ++j) fx[g][j] = *(const u32x4*)(sa + lds_off(wm + j * 16 + fr, g * 4 + fq));
-#pragma unroll
-        for (int i = 0; i < FN; ++i) fw[g][i] = *(const u32x4*)(sw + lds_off(wn + i * 16 + fr, g * 4 + fq));
-      }
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int g = 0; g < 2; ++g) {
-#pragma unroll
-        for (int i = 0; i < FN; ++i)
-#pragma unroll
-          for (int j = 0; j < FM; ++j) Mfma<TI>::run(fw[g][i], fx[g][j], acc[i][j]);
-        __builtin_amdgcn_sched_barrier(0);
-      }
+      k_tile_mma_pipelined<TI, FM, FN>(sa, sa + BM * 128, l, acc);
       stage ^= 1;
     }
-    int t_e = tid;
-    asm volatile("" : "+v"(t_e));
-    const int wm_e = ((t_e >> 6) / WN) * (BM / WM), wn_e = ((t_e >> 6) % WN) * (BN / WN);
-    const int fr_e = t_e & 15, fq_e = (t_e & 63) >> 4;
-    if constexpr (EPI == 1) {
-      gemm_epilogue<TO, FM, FN, false, true, ACTK>(p, acc, 0, m0 + wm_e, n0 + wn_e, fr_e, fq_e);
-    } else if constexpr (!LN_LATE) {
-      gemm_epilogue_ln<TO, FM, FN, EPI - 1, ACTK>(p, acc, m0 + wm_e, n0 + wn_e, fr_e, fq_e, lnraw);
-    } else {      // the 192-row tile: statistics loaded here (no registers to spare in the K loop)
-      f32x2 late[FM][4];
-      if constexpr (EPI == 2) ln_issue<FM>(p.a_stats, p.a_nt, p.M, m0 + wm_e, fr_e, fq_e, late);
-      else if (p.r_stats) ln_issue<FM>(p.r_stats, p.r_nt, p.M, m0 + wm_e, fr_e, fq_e, late);
-      gemm_epilogue_ln<TO, FM, FN, EPI - 1, ACTK>(p, acc, m0 + wm_e, n0 + wn_e, fr_e, fq_e, late);
-    }
+    const FragLane le = frag_lane<BM, BN, WM, WN>(opaque_tid(tid));
+    gemm_run_epilogue<TO, FM, FN, EPI, ACTK, true, LN_LATE>(p, acc, 0, m0 + le.wm, n0 + le.wn, le.fr, le.fq, lnraw, NoEarlyOps{});
     if (vbn < 0) break;
     vb = vbn; m0 = m0n; n0 = n0n;
     // the operand addresses again, from values the compiler cannot match with the ones above: they are NOT kept in
     // registers across the epilogue (8 registers the LayerNorm epilogues do not have)
     asm volatile("" : "+s"(m0), "+s"(n0));
-    int t_s = tid;
-    asm volatile("" : "+v"(t_s));
-    set_src(m0, n0, t_s);
+    src.set(p, A, W, m0, n0, opaque_tid(tid));
   }
 }
 
@@ -1073,48 +1033,27 @@ __device__ __forceinline__ void gemm_epilogue_split(const GemmArgs& p, const f32
 // this order -- so that a launch returns the same bits whether its row count routes it to this kernel or to the 256 x 256 one.
 template <typename TO, int BM, int BN, int WM, int WN, int NSTAGE, int ACTK = -1, bool WS = false>
 __global__ __launch_bounds__(WM * WN * 64) void gemm2s_kernel(const GemmArgs p) {
-  constexpr int NW = WM * WN, NT = NW * 64;
+  constexpr int NW = WM * WN;
   constexpr int STAGE = (BM + BN) * 128;
-  constexpr int LPT = (BM + BN) * 8 / NT;
   constexpr int FM = BM / WM / 16, FN = BN / WN / 16;
-  static_assert((BM + BN) * 8 % NT == 0, "tile chunks must divide over the threads");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
-  const int pid = blockIdx.x;
-  const int xcd = pid & 7, slot = pid >> 3;
-  const int xm_n = 8 / p.xn, ntx = (p.nt + p.xn - 1) / p.xn;
-  const int m_tile = (slot / ntx) * xm_n + (xcd % xm_n), n_tile = (slot % ntx) * p.xn + xcd / xm_n;
-  if (m_tile >= p.mt || n_tile >= p.nt) return;
+  int m_tile, n_tile;
+  if (!xcd_tile(p, blockIdx.x, m_tile, n_tile)) return;
   const int z = blockIdx.z;
-  const int zo = z / p.batch_inner, zi = z % p.batch_inner;
-  const f16_t* __restrict__ A = (const f16_t*)p.A + zo * p.strideA + zi * p.strideA2;
-  const f16_t* __restrict__ W = (const f16_t*)p.W + zo * p.strideW + zi * p.strideW2;
   const int m0 = m_tile * BM, n0 = n_tile * BN;
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int tid = threadIdx.x;
 
-  const f16_t* src[LPT];
-#pragma unroll
-  for (int i = 0; i < LPT; ++i) {
-    const int id = (i * NW + wid) * 64 + lane;
-    const int row = id >> 3, phys = id & 7;
-    const int c = phys ^ ((row >> 1) & 7);
-    if (row < BM) src[i] = A + a_row_offset(p, min(m0 + row, p.M - 1)) + c * 8;
-    else src[i] = W + (long)min(n0 + row - BM, p.N - 1) * p.ldw + c * 8;
-  }
-  auto issue = [&](int kt, int stage) {
-#pragma unroll
-    for (int i = 0; i < LPT; ++i)
-      __builtin_amdgcn_global_load_lds((gbl_void_t*)(src[i] + kt * 64),
-                                       (lds_void_t*)(smem + stage * STAGE + (i * NW + wid) * 1024), 16, 0, 0);
-  };
+  TileSrc<f16_t, BM, BN, NW> src;
+  constexpr int LPT = decltype(src)::LPT;
+  src.set(p, batch_a<f16_t>(p, z), batch_w<f16_t>(p, z), m0, n0, tid);
+  auto issue = [&](int kt, int stage) { src.issue(smem + stage * STAGE, kt, tid); };
 
-  const int wm = (wid / WN) * (BM / WM), wn = (wid % WN) * (BN / WN);
-  const int fr = lane & 15, fq = lane >> 4;
+  const FragLane l = frag_lane<BM, BN, WM, WN>(tid);
+  const int wm = l.wm, wn = l.wn, fr = l.fr, fq = l.fq;
   f32x4 acc0[FN][FM], acc1[FN][FM];
-#pragma unroll
-  for (int i = 0; i < FN; ++i)
-#pragma unroll
-    for (int j = 0; j < FM; ++j) acc0[i][j] = acc1[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc0);
+  zero_acc(acc1);
 
   const int nk = p.K / 32;
 #pragma unroll
@@ -1122,10 +1061,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm2s_kernel(const GemmArgs p) 
     if (s < nk) issue(s, s);
   int stage = 0;
   for (int kt = 0; kt < nk; ++kt) {
-    if (kt + NSTAGE - 2 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NSTAGE - 2) * LPT) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if (kt + NSTAGE - 1 < nk) issue(kt + NSTAGE - 1, (stage + NSTAGE - 1) % NSTAGE);
+    ring_step<NSTAGE, LPT>(kt, nk, stage, issue);
     const unsigned char* sa = smem + stage * STAGE;
     const unsigned char* sw = sa + BM * 128;
     u32x4 ah[FM], al[FM], wh[FN], wl[FN];
@@ -1169,7 +1105,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm2s_kernel(const GemmArgs p) 
           Mfma<f16_t>::run(wl[i], ah[j], acc1[i][j]);
         }
     }
-    stage = (stage + 1 == NSTAGE) ? 0 : stage + 1;
+    stage = ring_next<NSTAGE>(stage);
   }
 #pragma unroll
   for (int i = 0; i < FN; ++i)

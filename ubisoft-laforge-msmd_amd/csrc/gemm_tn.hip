@@ -14,14 +14,12 @@
 //
 // Reference semantics: the weight / bias gradients autograd produces for nn.Linear / F.linear in the reference's
 // training step (training_script.py:163-201 -> loss.backward()).
-#include "common.h"
+#include "gemm_tiles.h"
 #include <type_traits>
 #include <utility>
 
 namespace {
 
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) void gbl_void_t;
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 

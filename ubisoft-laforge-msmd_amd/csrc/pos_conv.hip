@@ -16,10 +16,7 @@
 // the 16 lanes of every ds_read_b128 lane group fall on 16 different 16-byte slots of the 256-byte bank row (128 B would be
 // 4-way).  W tile: 256-byte rows, 16-byte chunk c of row n stored at slot c ^ (n & 15), conflict-free the same way; the
 // permutation is applied to the per-lane SOURCE address because an LDS-DMA instruction writes its 1 KiB linearly.
-#include "common.h"
-
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void gbl_void_t;
+#include "gemm_tiles.h"
 
 #define PC_TAPS 128
 #define PC_BM 256      // frames per workgroup at most (16 fragment rows over 4 waves)
@@ -119,10 +116,7 @@ __global__ __launch_bounds__(256) void pos_conv_kernel(const PosConvArgs p) {
 
   int stage = 0;
   for (int kt = 0; kt < NK; ++kt) {
-    if (kt + PC_NSTAGE - 2 < NK) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((PC_NSTAGE - 2) * LPT) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if (kt + PC_NSTAGE - 1 < NK) issue(kt + PC_NSTAGE - 1, (stage + PC_NSTAGE - 1) % PC_NSTAGE);
+    ring_step<PC_NSTAGE, LPT>(kt, NK, stage, issue);
     const unsigned char* sw = smem + stage * STAGE;
     u32x4 fx[2][FM], fw[2][FN];
     auto read = [&](int g, int s) {
@@ -145,7 +139,7 @@ __global__ __launch_bounds__(256) void pos_conv_kernel(const PosConvArgs p) {
         for (int i = 0; i < FN; ++i) acc[i][FM - 1] = mfma16<T>(fw[g & 1][i], fx[g & 1][FM - 1], acc[i][FM - 1]);
       }
     }
-    stage = (stage + 1 == PC_NSTAGE) ? 0 : stage + 1;
+    stage = ring_next<PC_NSTAGE>(stage);
   }
 
   // epilogue: lane holds row fr, columns 4 fq .. 4 fq + 3 of each 16 x 16 fragment
