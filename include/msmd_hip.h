@@ -586,6 +586,48 @@ int msmd_rotation_convert_bwd(int op, const float* in, const float* in2, const f
                               float* grad_in2, long n, int conv, msmd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Head pose from tracked face landmarks (reference dataset_processing/Step2_preprocess_head_pose_mediapipe.py).
+ *
+ * msmd_headpose_fit, one workgroup per frame of a ragged batch of clips laid end to end (n_frames frames in all):
+ *   landmarks (n_frames, P, 3) fp32.  Frame f is (1 - plan_w[f]) landmarks[plan_a[f]] + plan_w[f] landmarks[plan_b[f]]:
+ *   a tracked frame names itself with weight 0 (plan_b is then not read), a missing one its two tracked neighbours.
+ *   plan_a, plan_b (n_frames) int32 frame indices into the whole batch, plan_w (n_frames) fp32.
+ *   neutral (P, 3) fp32, read at static_idx only; static_idx (S) int32 in [0, P), 3 <= S <= 64.  plan_a / plan_b / static_idx
+ *   outside their ranges are the caller's error; the kernel clamps them, so nothing is read out of bounds.
+ *   With X the S static points of the frame and Y those of the neutral shape (Umeyama's similarity fit, the reference's
+ *   procrustes_analysis): cov = (1/S) (Y - mu_y)(X - mu_x)^T = U D V^T, Sg = diag(1, 1, det(U) det(V^T) < 0 ? -1 : 1),
+ *   R = U Sg V^T, c = sum(D diag Sg) / rho2_x (rho2_x the summed per-axis population variance of X), t = mu_y - c R mu_x.
+ *   Means and second moments are summed in double after the mean is subtracted, the 3 x 3 stage (one-sided Jacobi) runs in double.
+ *   Outputs: R (n_frames, 9) row-major, c (n_frames), t (n_frames, 3), and, unless `aligned` is NULL, aligned (n_frames, P, 3) =
+ *   c R x + t for every blended landmark x of the frame -- all fp32.
+ *   OUTSIDE THE CONTRACT: a covariance of rank < 3 (collinear or coplanar static points).  Collinear points have no unique fit
+ *   and the outputs are unspecified (possibly NaN).  Coplanar points (S = 3 always) still determine R: U's third column is
+ *   completed as u0 x u1 and the sign rule above applies as it stands -- which is the reference's rule for a rank-deficient
+ *   covariance, but the reference chooses between that rule and det(cov) < 0 by a numerical rank test, so agreement with it
+ *   on (nearly) coplanar points is not promised.  Returns 1 for S outside [3, 64], S > P or a NULL pointer other than `aligned`.
+ *
+ * msmd_headpose_smooth, one workgroup per clip: R (n_frames, 9) fp32 as msmd_headpose_fit wrote it; clip_offsets (n_clips + 1)
+ *   int64 on the device, clip k owns frames [clip_offsets[k], clip_offsets[k + 1]); a clip shorter than `window` is left unwritten.
+ *   Per clip: unit quaternions of R; signs made continuous (s_0 = 1, s_i = s_{i-1} (q_i . q_{i-1} < 0 ? -1 : 1) on the raw
+ *   quaternions: a prefix product scanned MSMD_HEADPOSE_CHUNK frames at a time with a carried sign); a Savitzky-Golay filter over each
+ *   component; renormalisation; the matrix, premultiplied by diag(1, -1, -1); its intrinsic Y-X-Z angles pitch = asin(-M[1][2]),
+ *   yaw = atan2(M[0][2], M[2][2]), roll = atan2(M[1][0], M[1][1]).  ypr_deg (n_frames, 3) fp32 = (yaw, pitch, -roll) in degrees;
+ *   R_out (n_frames, 9) fp32 or NULL = Ry(yaw) Rx(pitch) Rz(-roll) of those angles before their rounding to fp32 (the reference's
+ *   R_modified).
+ *   coeffs: window * window doubles on the device = the `window` symmetric interior coefficients, then the edge table
+ *   (2 (window / 2), window): row r < window / 2 gives frame r from the clip's first `window` frames, row window / 2 + r gives
+ *   frame F - window / 2 + r from its last `window` (scipy's mode='interp').  window odd, 3 <= window <= MSMD_HEADPOSE_MAX_WINDOW.
+ *   The arithmetic is double; the quaternion's sign convention is free (the result depends on it only at a dot product of exactly 0).
+ *   OUTSIDE THE CONTRACT: gimbal lock, |pitch| within 1e-3 degrees of 90 (yaw and roll are then not separately defined). */
+#define MSMD_HEADPOSE_MAX_WINDOW 33
+#define MSMD_HEADPOSE_CHUNK 256
+int msmd_headpose_fit(const float* landmarks, const int* plan_a, const int* plan_b, const float* plan_w, const float* neutral,
+                      const int* static_idx, float* R, float* c, float* t, float* aligned, int n_frames, int P, int S,
+                      msmd_stream_t stream);
+int msmd_headpose_smooth(const float* R, const long* clip_offsets, int n_clips, const double* coeffs, int window, float* ypr_deg,
+                         float* R_out, msmd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Losses / training-step pieces (reference utils/common.py:198-620, 443-454, 769-832; training_script.py:548-551).
  */
 /* out[0] = scale * mean over valid (n, t) of mean_{c in [c_lo, c_hi)} crit(D^order gt, D^order pred)

@@ -1705,3 +1705,65 @@ def znorm_audio(out, desc, desc_host, partials):
     _lib.check(_lib.load().msmd_audio_znorm(_p(out), out.numel(), _p(desc), h.shape[0], max_out, _p(partials), _p(stats),
                                             _stream()), "msmd_audio_znorm")
     return out
+
+
+# ----------------------------------------------------------------------------- head pose from landmarks (csrc/headpose.hip)
+HEADPOSE_MAX_WINDOW = 33   # MSMD_HEADPOSE_MAX_WINDOW
+HEADPOSE_CHUNK = 256       # MSMD_HEADPOSE_CHUNK: frames per step of the smoothing kernel's sign scan
+HEADPOSE_MAX_STATIC = 64   # one static landmark per lane of a wave
+
+
+def headpose_fit(landmarks, plan_a, plan_b, plan_w, neutral, static_idx, want_aligned=True):
+    """-> (R (n, 3, 3), c (n), t (n, 3), aligned (n, P, 3) or None) fp32: msmd_headpose_fit, the per-frame similarity fit of
+    the static landmarks onto `neutral` and the fitted transform applied to every landmark.  landmarks (n, P, 3) fp32, the
+    clips of a batch end to end; plan_a / plan_b (n) int32 and plan_w (n) fp32: frame f is (1 - w) L[a] + w L[b]
+    (utils/head_pose.gap_plan); neutral (P, 3) fp32, read at static_idx (S) int32 in [0, P), 3 <= S <= 64.  The index
+    arrays live on the device and are not read back here: the kernel clamps them into range."""
+    _need_cuda(landmarks, plan_a, plan_b, plan_w, neutral, static_idx)
+    _render_arg("landmarks", landmarks, torch.float32)
+    if landmarks.dim() != 3 or landmarks.shape[2] != 3 or landmarks.shape[0] == 0:
+        raise TypeError(f"landmarks must have shape (n_frames, P, 3), got {tuple(landmarks.shape)}")
+    n, P, _ = landmarks.shape
+    _render_arg("plan_a", plan_a, torch.int32, (n,))
+    _render_arg("plan_b", plan_b, torch.int32, (n,))
+    _render_arg("plan_w", plan_w, torch.float32, (n,))
+    _render_arg("neutral", neutral, torch.float32, (P, 3))
+    _render_arg("static_idx", static_idx, torch.int32)
+    S = static_idx.numel()
+    if static_idx.dim() != 1 or not 3 <= S <= min(HEADPOSE_MAX_STATIC, P):
+        raise ValueError(f"static_idx must hold 3 .. min({HEADPOSE_MAX_STATIC}, P) indices, got shape {tuple(static_idx.shape)}")
+    dev = landmarks.device
+    R = torch.empty(n, 3, 3, device=dev, dtype=torch.float32)
+    c = torch.empty(n, device=dev, dtype=torch.float32)
+    t = torch.empty(n, 3, device=dev, dtype=torch.float32)
+    aligned = torch.empty(n, P, 3, device=dev, dtype=torch.float32) if want_aligned else None
+    _lib.check(_lib.load().msmd_headpose_fit(_p(landmarks), _p(plan_a), _p(plan_b), _p(plan_w), _p(neutral), _p(static_idx),
+                                             _p(R), _p(c), _p(t), _p(aligned), n, P, S, _stream()), "msmd_headpose_fit")
+    return R, c, t, aligned
+
+
+def headpose_smooth(R, clip_offsets, table, window, want_matrix=False):
+    """-> (ypr (n, 3) fp32 yaw / pitch / -roll in degrees, R_modified (n, 3, 3) fp32 or None): msmd_headpose_smooth over
+    the clips [clip_offsets[k], clip_offsets[k + 1]) of R (n, 3, 3) fp32.  clip_offsets: the (n_clips + 1) offsets on the
+    HOST (checked here: ascending from 0 to n, every clip at least `window` frames; copied to the device as int64);
+    table (window * window) float64 on the device (utils/head_pose.savgol_table)."""
+    _need_cuda(R, table)
+    _render_arg("R", R, torch.float32)
+    if R.dim() != 3 or tuple(R.shape[1:]) != (3, 3) or R.shape[0] == 0:
+        raise TypeError(f"R must have shape (n_frames, 3, 3), got {tuple(R.shape)}")
+    window = int(window)
+    if window < 3 or window > HEADPOSE_MAX_WINDOW or window % 2 == 0:
+        raise ValueError(f"window must be odd and in [3, {HEADPOSE_MAX_WINDOW}], got {window}")
+    _render_arg("table", table, torch.float64, (window * window,))
+    off = [int(o) for o in clip_offsets]
+    if len(off) < 2 or off[0] != 0 or off[-1] != R.shape[0]:
+        raise ValueError(f"clip_offsets must run from 0 to {R.shape[0]}, got {off[:1]} .. {off[-1:]}")
+    for a, b in zip(off[:-1], off[1:]):
+        if b - a < window:
+            raise ValueError(f"a clip of {b - a} frames is shorter than the window of {window}")
+    off_dev = torch.tensor(off, dtype=torch.int64).to(R.device)
+    ypr = torch.empty(R.shape[0], 3, device=R.device, dtype=torch.float32)
+    R_mod = torch.empty_like(R) if want_matrix else None
+    _lib.check(_lib.load().msmd_headpose_smooth(_p(R), _p(off_dev), len(off) - 1, _p(table), window, _p(ypr), _p(R_mod),
+                                                _stream()), "msmd_headpose_smooth")
+    return ypr, R_mod
