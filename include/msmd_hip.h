@@ -486,7 +486,8 @@ int msmd_lbs_skin_bf16x3(const void* coef_hl, const float* A, const float* v_tem
  * into fp16 hi + lo: 15 of the 32 K slots), its accumulator landing where the blendshape product puts p(vertex,
  * frame).
  * skin_tiles: ceil(B / 16) records of 18 432 bytes, one per 16 frames, written by msmd_lbs_prepare (its at_tiles
- *   argument) or msmd_lbs_pack and read by 18 contiguous one-KiB LDS-DMA pieces:
+ *   argument) or msmd_lbs_pack and read by 18 contiguous one-KiB LDS-DMA pieces.  csrc/lbs_tiles.h DEFINES the record
+ *   (sizes, offsets, the writers); in words:
  *     [0, 12 288)       coefficients as bf16 hi then lo, [chunk = (hi|lo) * 24 + k / 8][frame % 16][k % 8]
  *     [12 288, 18 432)  blend rows, fp16, [component m of the 3x4][slot / 8][frame % 16][slot % 8] with the 16 K slots
  *                       [Ah_0..4 | Al_0..4 | Ah_0..4 | 0];
@@ -512,7 +513,7 @@ int msmd_lbs_skin_v2_f16(const void* skin_tiles, const float* v_template, const 
                          void* verts16, int B, int J, int V, int V_ld, int Vp, int Kp, const int* shape_varies,
                          const float* v_template_folded, int single_plane, msmd_stream_t stream);
 /* msmd_lbs_skin_v2's tile records (18 432 bytes per 16 frames) -> the single-plane form's (12 288 bytes: coefficients hi + lo
- * as one fp16 number [k / 8][frame % 16][k % 8], then the blend rows). */
+ * as one fp16 number [k / 8][frame % 16][k % 8], then the blend rows; csrc/lbs_tiles.h defines both). */
 int msmd_lbs_tiles_f16(const void* skin_tiles, void* tiles16, int B, msmd_stream_t stream);
 
 /* Training through FLAME (the reference's use_vertex_space branch: training_script.py:167-176 -> utils/common.py:486-513

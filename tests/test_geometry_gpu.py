@@ -1,4 +1,4 @@
-"""Geometry kernels (csrc/flame.hip, csrc/rotations.hip) against float64 restatements written here from the formulas, at the
+"""Geometry kernels (csrc/flame.hip, csrc/lbs_skin.hip, csrc/rotations.hip) against float64 restatements written here from the formulas, at the
 shapes where these kernels go wrong: vertex counts around the 64 / 128-vertex tiles and the fp16 lane pairs (odd and even V),
 frame counts around the 16-frame tile, every coefficient width the 192-wide K row admits, item counts around the 256-item
 workgroup of the rotation kernel and unaligned input views.  Every output element is compared; each tolerance is a stated

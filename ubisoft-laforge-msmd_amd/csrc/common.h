@@ -19,6 +19,10 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
+// 12-byte vertex / index triples, 4-byte aligned: ONE dwordx3 load or store
+struct __attribute__((packed, aligned(4))) F3 { float x, y, z; };
+struct __attribute__((packed, aligned(4))) I3 { int a, b, c; };
+
 #define MSMD_WAVE 64
 
 // Launch-error plumbing: every extern "C" launcher returns a hipError_t-compatible int.

@@ -7,9 +7,6 @@
 
 namespace {
 
-struct __attribute__((packed, aligned(4))) F3 { float x, y, z; };
-struct __attribute__((packed, aligned(4))) I3 { int a, b, c; };
-
 __device__ __forceinline__ F3 cross3(const F3 a, const F3 b) {
   return F3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
 }

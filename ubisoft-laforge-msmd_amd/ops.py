@@ -830,7 +830,23 @@ def mean_time(x):
 
 
 # ----------------------------------------------------------------------------- FLAME
-SKIN_TILE_BYTES = 18432   # msmd_lbs_skin_v2's input record per 16 frames (include/msmd_hip.h)
+# msmd_lbs_skin_v2's input record per 16 frames, and the record of its single-fp16-plane form: csrc/lbs_tiles.h defines both
+SKIN_TILE_BYTES, SKIN_TILE16_BYTES = 18432, 12288
+
+
+def _skin_tiles(B, device, tile_bytes=SKIN_TILE_BYTES):
+    """An unwritten tile buffer for B frames: one record per 16 frames."""
+    return torch.empty((B + 15) // 16, tile_bytes // 2, device=device, dtype=torch.float16)
+
+
+def _tile_fed(skin_tiles, B, weight_planes, dirs_hl):
+    """-> (J, Vp) of a skinning call that reads tile records, after checking that `skin_tiles` holds B frames' worth."""
+    assert skin_tiles.numel() * skin_tiles.element_size() == ((B + 15) // 16) * SKIN_TILE_BYTES
+    return weight_planes.shape[0], dirs_hl.shape[-2]
+
+
+def _verts32(B, V, device):
+    return torch.empty(B, V, 3, device=device, dtype=torch.float32)
 
 
 def lbs_prepare(betas, pose, JS, parents, Kp=192, pose_is_matrix=False, want_joints=True, want_split=False,
@@ -844,7 +860,7 @@ def lbs_prepare(betas, pose, JS, parents, Kp=192, pose_is_matrix=False, want_joi
     coef_hl = torch.empty(B, 2, Kp, device=betas.device, dtype=torch.bfloat16) if want_split else None
     A = torch.empty(B, J, 12, device=betas.device, dtype=torch.float32)
     joints = torch.empty(B, J, 3, device=betas.device, dtype=torch.float32) if want_joints else None
-    at = torch.empty((B + 15) // 16, SKIN_TILE_BYTES // 2, device=betas.device, dtype=torch.float16) if want_blend_tiles else None
+    at = _skin_tiles(B, betas.device) if want_blend_tiles else None
     _lib.check(lib.msmd_lbs_prepare(_p(betas), _p(pose), _p(JS), _p(parents), _p(coef), _p(coef_hl), _p(A), _p(joints),
                                     _p(at), B, NB, J, Kp, int(pose_is_matrix), _stream()), "msmd_lbs_prepare")
     return (coef, coef_hl, A, joints, at) if want_blend_tiles else (coef, coef_hl, A, joints)
@@ -859,7 +875,7 @@ def flame_prepare(shape, expr, pose6, eye, JS, parents, ignore_global_rot=False,
     lib = _lib.load()
     _need_cuda(shape, expr, pose6)
     B = shape.shape[0]
-    tiles = torch.empty((B + 15) // 16, SKIN_TILE_BYTES // 2, device=shape.device, dtype=torch.float16)
+    tiles = _skin_tiles(B, shape.device)
     flag = folded = None
     Vp = 0
     if dirs is not None and v_template_planes is not None:
@@ -875,22 +891,18 @@ def flame_prepare(shape, expr, pose6, eye, JS, parents, ignore_global_rot=False,
 def lbs_skin(coef, A, v_template_planes, dirs, weight_planes, V):
     lib = _lib.load()
     B, Kp = coef.shape
-    J = A.shape[1]
-    Vp = dirs.shape[-1]
-    verts = torch.empty(B, V, 3, device=coef.device, dtype=torch.float32)
-    _lib.check(lib.msmd_lbs_skin(_p(coef), _p(A), _p(v_template_planes), _p(dirs), _p(weight_planes), _p(verts), B, J,
-                                 V, Vp, Kp, _stream()), "msmd_lbs_skin")
+    verts = _verts32(B, V, coef.device)
+    _lib.check(lib.msmd_lbs_skin(_p(coef), _p(A), _p(v_template_planes), _p(dirs), _p(weight_planes), _p(verts), B,
+                                 A.shape[1], V, dirs.shape[-1], Kp, _stream()), "msmd_lbs_skin")
     return verts
 
 
 def lbs_skin_bf16x3(coef_hl, A, v_template_planes, dirs_hl, weight_planes, V):
     lib = _lib.load()
     B, _, Kp = coef_hl.shape
-    J = A.shape[1]
-    Vp = dirs_hl.shape[-2]
-    verts = torch.empty(B, V, 3, device=A.device, dtype=torch.float32)
+    verts = _verts32(B, V, A.device)
     _lib.check(lib.msmd_lbs_skin_bf16x3(_p(coef_hl), _p(A), _p(v_template_planes), _p(dirs_hl), _p(weight_planes),
-                                        _p(verts), B, J, V, Vp, Kp, _stream()), "msmd_lbs_skin_bf16x3")
+                                        _p(verts), B, A.shape[1], V, dirs_hl.shape[-2], Kp, _stream()), "msmd_lbs_skin_bf16x3")
     return verts
 
 
@@ -902,15 +914,13 @@ def lbs_skin_v2(skin_tiles, B, v_template_planes, dirs_hl, weight_planes, V, Kp=
     records are converted by msmd_lbs_tiles_f16 first): |error| <= 2^-11 |v| + 2^-10 sum_k |coef_k| |dirs_k|; without it the fp32 kernel's arithmetic,
     rounded once at the store."""
     lib = _lib.load()
-    assert skin_tiles.numel() * skin_tiles.element_size() == ((B + 15) // 16) * SKIN_TILE_BYTES
-    J = weight_planes.shape[0]
-    Vp = dirs_hl.shape[-2]
+    J, Vp = _tile_fed(skin_tiles, B, weight_planes, dirs_hl)
     if out_dtype == torch.float16:
         V_ld = V + (V & 1)
         v16 = torch.empty(B, V_ld, 3, device=skin_tiles.device, dtype=torch.float16)
         tiles, dirs, single = skin_tiles, dirs_hl, 0
         if dirs_f16 is not None:
-            tiles = torch.empty((B + 15) // 16, 12288 // 2, device=skin_tiles.device, dtype=torch.float16)
+            tiles = _skin_tiles(B, skin_tiles.device, SKIN_TILE16_BYTES)
             _lib.check(lib.msmd_lbs_tiles_f16(_p(skin_tiles), _p(tiles), B, _stream()), "msmd_lbs_tiles_f16")
             dirs, single = dirs_f16, 1
         _lib.check(lib.msmd_lbs_skin_v2_f16(_p(tiles), _p(v_template_planes), _p(dirs), _p(weight_planes), _p(v16), B, J, V,
@@ -918,7 +928,7 @@ def lbs_skin_v2(skin_tiles, B, v_template_planes, dirs_hl, weight_planes, V, Kp=
         return v16[:, :V]
     if out_dtype != torch.float32:
         raise TypeError("lbs_skin_v2: fp32 or fp16 vertices")
-    verts = torch.empty(B, V, 3, device=skin_tiles.device, dtype=torch.float32)
+    verts = _verts32(B, V, skin_tiles.device)
     _lib.check(lib.msmd_lbs_skin_v2(_p(skin_tiles), _p(v_template_planes), _p(dirs_hl), _p(weight_planes),
                                     _p(verts), B, J, V, Vp, Kp, _p(shape_varies), _p(folded), _stream()),
                "msmd_lbs_skin_v2")
@@ -930,7 +940,7 @@ def lbs_pack(coef, A, want_split=False):
     lib = _lib.load()
     B, Kp = coef.shape
     coef_hl = torch.empty(B, 2, Kp, device=coef.device, dtype=torch.bfloat16) if want_split else None
-    at = torch.empty((B + 15) // 16, SKIN_TILE_BYTES // 2, device=coef.device, dtype=torch.float16)
+    at = _skin_tiles(B, coef.device)
     _lib.check(lib.msmd_lbs_pack(_p(coef), _p(A), _p(coef_hl), _p(at), B, Kp, _stream()), "msmd_lbs_pack")
     return (at, coef_hl) if want_split else at
 
@@ -938,11 +948,8 @@ def lbs_pack(coef, A, want_split=False):
 def lbs_skin_v2_train(skin_tiles, B, v_template_planes, dirs_hl, weight_planes, V, Kp=192):
     """-> (verts, v_posed): msmd_lbs_skin_v2 that also stores the un-skinned vertices (needed by lbs_skin_bwd)."""
     lib = _lib.load()
-    assert skin_tiles.numel() * skin_tiles.element_size() == ((B + 15) // 16) * SKIN_TILE_BYTES
-    J = weight_planes.shape[0]
-    Vp = dirs_hl.shape[-2]
-    verts = torch.empty(B, V, 3, device=skin_tiles.device, dtype=torch.float32)
-    vposed = torch.empty(B, V, 3, device=skin_tiles.device, dtype=torch.float32)
+    J, Vp = _tile_fed(skin_tiles, B, weight_planes, dirs_hl)
+    verts, vposed = _verts32(B, V, skin_tiles.device), _verts32(B, V, skin_tiles.device)
     _lib.check(lib.msmd_lbs_skin_v2_train(_p(skin_tiles), _p(v_template_planes), _p(dirs_hl),
                                           _p(weight_planes), _p(verts), _p(vposed), B, J, V, Vp, Kp, _stream()),
                "msmd_lbs_skin_v2_train")

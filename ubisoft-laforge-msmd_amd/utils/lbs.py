@@ -1,7 +1,7 @@
 """Linear blend skinning on the MI355X (drop-in surface of reference utils/lbs.py).
 
 ``lbs(...)`` keeps the reference signature (utils/lbs.py:141) but runs as two HIP launches
-(csrc/flame.hip): a per-frame kinematics kernel and one fused blendshape+skinning kernel; the
+(csrc/flame.hip, csrc/lbs_skin.hip): a per-frame kinematics kernel and one fused blendshape+skinning kernel; the
 reference's (B, V, 4, 4) transforms and homogeneous coordinates are never materialised.
 """
 from __future__ import annotations
