@@ -949,6 +949,59 @@ int msmd_jpeg_measure(const short* coef, int B, int H, int W, int header_len, in
 int msmd_jpeg_write(const short* coef, int B, int H, int W, const void* header, int header_len, const long* interval_rel,
                     const long* offsets, void* out, long out_bytes, msmd_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Style losses (reference utils/common.py:29-91 StyleAdherenceLoss, 835-875 nt_xent_loss).  fp32, contiguous,
+ * no allocation, no host synchronisation, no floating-point atomics: every sum has one owner and an order that is a function
+ * of the shape alone, so the same inputs give the same bits on every run and a batch row's bits do not depend on its batch.
+ *
+ * Style adherence, X (B, T, F) against S (B, K, F), lambda >= 0:
+ *   d[b, t, k] = (1 / F) sum_f (X[b, t, f] - S[b, k, f])^2, from the differences, ascending f by fma, one division by F;
+ *   soft != 0: w = softmax_k(-lambda d), L[b, t] = sum_k w_k d_k; stat (B, T, 2) fp32 = (m, log sum_k exp(-lambda (d_k - m))),
+ *     m = min_k d_k: the soft minimum's log-sum-exp -lambda m + log(.) kept as its two parts, so that a recomputed weight
+ *     exp(-lambda (d_k - m) - log(.)) does not carry the lambda m 2^-24 of a sum rounded to one fp32 number;
+ *   soft == 0: L[b, t] = min_k d_k; stat (B, T) int32 = the lowest index that attains it.
+ *   The running (min, sum e, sum e d), e = exp(-lambda (d - min)), is kept per lane over k = j, j + 16, ... and rescaled when
+ *   the minimum moves; a row's 16 lanes are joined by the xor butterfly 8, 4, 2, 1.
+ * msmd_style_adherence_forward: one launch, a workgroup per MSMD_STYLE_ROWS rows of one b; S[b] passes through LDS in tiles of
+ *   MSMD_STYLE_KTILE frames, MSMD_STYLE_FCHUNK features at a time (any F).  Writes L (B, T) and stat; no workspace.
+ * msmd_style_adherence_backward: g = the gradient of L's rows, read at g[(b T + t) g_stride] * g_scale (g_stride 0: one
+ *   device scalar for every row, e.g. the upstream of a mean with g_scale = 1 / (B T); g_stride 1: per row).  With
+ *   c[t, k] = w_k (1 - lambda (d_k - L[t])) (soft) or [k = stat[t]] (hard), recomputed from L and stat:
+ *     dX[b, t] = (2 / F) g sum_k c[t, k] (X[b, t] - S[b, k])       (= (2 / F) g (X[b, t] - sum_k c S[b, k]), as sum_k c = 1)
+ *     dS[b, k] = -(2 / F) sum_t g[b, t] c[t, k] (X[b, t] - S[b, k])
+ *   dX: a workgroup per row tile, S streamed in ascending k; dS: a workgroup per tile of k, X[b] streamed in ascending t; each
+ *   keeps its running sums in its own rows of the output.  dX or dS may be NULL (not both): that launch is skipped.  One or
+ *   two launches, no workspace.
+ * msmd_ordered_mean: out[0] = (sum of in[0 .. n)) / n; one workgroup, thread i adds elements i, i + 256, ... in double, then a
+ *   halving tree over the 256 partial sums.
+ *
+ * NT-Xent, rows f = cat(a, b) (N = 2 B rows of D), fhat = f / max(|f|, 1e-12), s_ij = fhat_i . fhat_j / temperature,
+ * p(i) = (i + B) mod N:  loss = (1 / N) sum_i [ log sum_{j != i} exp(s_ij) - s_{i p(i)} ].
+ * msmd_nt_xent_forward: two launches, a workgroup per row: writes fhat (N, D), norm (N) = |f_i|, lse (N, 2) = the row's
+ *   log-sum-exp as (max_j s_ij, log sum_j exp(s_ij - max)) and row_loss (N); the caller takes msmd_ordered_mean of row_loss.
+ *   fhat, norm and lse are what the backward reads (N D + 3 N floats).
+ * msmd_nt_xent_backward: upstream = the loss's 0-dim gradient on the device.  G_ij = upstream (exp((s_ij - max_i) - log_i) - [j = p(i)])
+ *   / (N temperature) for j != i;  h_i = sum_j (G_ij + G_ji) fhat_j in ascending j;  grad[i] = (h_i - fhat_i (fhat_i . h_i)) /
+ *   |f_i|, or h_i / 1e-12 where |f_i| < 1e-12 (the clamp passes no gradient to the norm).  grad (N, D): rows [0, B) belong to a,
+ *   [B, N) to b.  One launch, a workgroup per row, no workspace.  B = 1 gives loss 0 and a zero gradient.
+ *
+ * Return codes: 0, a hipError_t of a failed launch, or 1 (hipErrorInvalidValue) before any launch for B, T, K, F or D < 1, a
+ * grid beyond 2^31 - 1 workgroups, lambda < 0 or not finite, temperature <= 0 or not finite, g_stride outside {0, 1}, or a
+ * NULL operand. */
+#define MSMD_STYLE_ROWS 16
+#define MSMD_STYLE_KTILE 64
+#define MSMD_STYLE_FCHUNK 64
+int msmd_style_adherence_forward(const float* X, const float* S, float* L, void* stat, int B, int T, int K, int F, float lambda,
+                                 int soft, msmd_stream_t stream);
+int msmd_style_adherence_backward(const float* X, const float* S, const float* L, const void* stat, const float* g,
+                                  int g_stride, float g_scale, float* dX, float* dS, int B, int T, int K, int F, float lambda,
+                                  int soft, msmd_stream_t stream);
+int msmd_ordered_mean(const float* in, long n, float* out, msmd_stream_t stream);
+int msmd_nt_xent_forward(const float* a, const float* b, float* fhat, float* norm, float* row_loss, float* lse, int B, int D,
+                         float temperature, msmd_stream_t stream);
+int msmd_nt_xent_backward(const float* fhat, const float* norm, const float* lse, const float* upstream, float* grad, int B,
+                          int D, float temperature, msmd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -747,3 +747,44 @@ def flametex(texcode, mean, basis, src_hw=(512, 512), dst_hw=(256, 256)):
     dtype) -> (bs, 3, Hd, Wd) fp32, differentiable once with respect to texcode."""
     ops._need_cuda(texcode)
     return FlameTexFn.apply(texcode.float(), mean, basis, src_hw, dst_hw)
+
+
+class StyleAdherenceFn(torch.autograd.Function):
+    """utils/common.StyleAdherenceLoss.forward on msmd_style_adherence_forward / _backward.  X (B, T, F) and
+    S (B, K, F) contiguous fp32 -> the rows' loss (B, T), or its ordered mean (0-dim) with `reduce`.  What is kept for the
+    backward is the inputs, the rows' loss and one statistic per row; S gets a gradient only where it asks for one."""
+
+    @staticmethod
+    def forward(ctx, X, S, lambda_softmin, soft, reduce):
+        L, stat = ops.style_adherence_forward(X, S, lambda_softmin, soft)
+        ctx.save_for_backward(X, S, L, stat)
+        ctx.cfg = (float(lambda_softmin), bool(soft), bool(reduce))
+        return ops.ordered_mean(L) if reduce else L
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        X, S, L, stat = ctx.saved_tensors
+        lam, soft, reduce = ctx.cfg
+        dX, dS = ops.style_adherence_backward(X, S, L, stat, g.float().contiguous(), lam, soft, need_dS=ctx.needs_input_grad[1],
+                                              g_scale=1.0 / L.numel() if reduce else 1.0, need_dX=ctx.needs_input_grad[0])
+        return dX, dS, None, None, None
+
+
+class NtXentFn(torch.autograd.Function):
+    """utils/common.nt_xent_loss on msmd_nt_xent_forward / _backward: feature_a, feature_b (B, D) contiguous
+    fp32 -> the 0-dim loss.  The normalised rows, their norms and the rows' log-sum-exps are kept for the backward."""
+
+    @staticmethod
+    def forward(ctx, feature_a, feature_b, temperature):
+        loss, _, saved = ops.nt_xent_forward(feature_a, feature_b, temperature)
+        ctx.save_for_backward(*saved)
+        ctx.temperature = float(temperature)
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        grad = ops.nt_xent_backward(ctx.saved_tensors, g.float().contiguous(), ctx.temperature)
+        B = grad.shape[0] // 2
+        return grad[:B], grad[B:], None

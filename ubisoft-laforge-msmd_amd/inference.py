@@ -20,6 +20,8 @@ SURVEY.md section 8(f) n3, the callers either side of the sampler:
   * ``--texture`` -- an `.npz` with `tex_img`, `vt`, `ft`: the frames are drawn with that texture.
   * ``--flame_tex`` -- an albedo `.npz` (BFM or FLAME texture space, plus `vt`, `ft`): the texture is evaluated by
     utils/flame.FLAMETex from ``--tex_code`` (default: the mean face) and the frames are drawn with it.
+  * ``--style_adherence`` -- every generated frame's soft-min distance to the whole normalised style clip
+    (utils/common.StyleAdherenceLoss), written beside the pickles.
 The rest of the reference script's media IO (compressed audio codecs, cv2, H.264) stays outside.
 """
 from __future__ import annotations
@@ -182,6 +184,14 @@ def denormalize_coeffs(overall_coef, coef_stats):
 
 
 @torch.no_grad()
+def style_adherence_per_frame(coef, style_clip, lambda_softmin=10.0):
+    """(1, T, C) generated coefficients against (1, K, C) style-clip coefficients, both normalised -> (T,) fp32: every frame's
+    soft-min mean squared distance to the clip's frames (utils/common.StyleAdherenceLoss, reduce=False)."""
+    from .utils.common import StyleAdherenceLoss
+    return StyleAdherenceLoss(True, lambda_softmin)(coef, style_clip, reduce=False)[0]
+
+
+@torch.no_grad()
 def render_coeffs_chunks(coef, shape_coef, flame, coef_stats, renderer, chunk=512, *, with_global_pose=True, tex_img=None,
                          tex_uv=None):
     """`render_coeffs` as a generator: yields the frames of `chunk` coefficients at a time, (n, H, W, 3) uint8 views of the
@@ -316,6 +326,9 @@ def build_parser():
     ap.add_argument("--video", action="store_true", help="write video_<clip>_seed_<s>.avi instead of the raw frames "
                                                          "(needs --render_size > 0)")
     ap.add_argument("--video_quality", type=int, default=90, help="JPEG quality of the video's frames, 1 .. 100")
+    # metric (not in the reference script; the loss is its utils/common.StyleAdherenceLoss)
+    ap.add_argument("--style_adherence", action="store_true", help="write style_adherence_<clip>_seed_<s>.npy: every generated "
+                                                                   "frame's soft-min distance to the whole style clip")
     return ap
 
 
@@ -394,7 +407,9 @@ def main(argv=None):
     frames are JPEG-compressed on the device chunk by chunk as they are rendered (so one chunk of raw pixels is alive at a
     time), at model_args.fps, with --audio_clip as the sound track when it is a `.wav` and silent otherwise.  --texture PATH
     (an `.npz` with tex_img, vt, ft) draws the frames textured, in either form; --flame_tex PATH (an albedo `.npz` with vt, ft)
-    does so with the FLAMETex texture of --tex_code."""
+    does so with the FLAMETex texture of --tex_code.  --style_adherence also writes `style_adherence_<clip>_seed_<s>.npy`, (T,)
+    float32: the soft adherence (lambda 10) of repetition 0's normalised coefficients to the whole normalised style clip, and
+    prints its mean; it needs the style clip's coefficients to be as wide as the model's."""
     import os
     args = parse_args(argv)
     device = torch.device("cuda")
@@ -445,6 +460,14 @@ def main(argv=None):
             with open(out, "wb") as f:
                 pkl.dump(val.cpu().numpy(), f)
             written.append(out)
+        if args.style_adherence:
+            # the normalised coefficients of repetition 0 against the WHOLE normalised style clip, not only the 100 frames
+            # the style encoder saw
+            per_frame = style_adherence_per_frame(coef[0:1], motion_coeff)
+            out = os.path.join(temp, f"style_adherence_{clip}_seed_{seed}.npy")
+            np.save(out, per_frame.cpu().numpy())
+            written.append(out)
+            print(f"style adherence (seed {seed}): mean {float(per_frame.mean()):.6f} over {per_frame.numel()} frames")
         if renderer is not None and args.video:
             from .utils import media
             jpegs = []

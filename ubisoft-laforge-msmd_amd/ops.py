@@ -1774,3 +1774,120 @@ def headpose_smooth(R, clip_offsets, table, window, want_matrix=False):
     _lib.check(_lib.load().msmd_headpose_smooth(_p(R), _p(off_dev), len(off) - 1, _p(table), window, _p(ypr), _p(R_mod),
                                                 _stream()), "msmd_headpose_smooth")
     return ypr, R_mod
+
+
+# ----------------------------------------------------------------------------- style losses (csrc/style_loss.hip)
+STYLE_ROWS = 16      # MSMD_STYLE_ROWS: rows of X per workgroup
+STYLE_KTILE = 64     # MSMD_STYLE_KTILE: style frames per LDS tile
+STYLE_FCHUNK = 64    # MSMD_STYLE_FCHUNK: features per pass over a tile
+NT_XENT_CHUNK = 256  # rows j per step of the NT-Xent backward's coefficient table
+
+
+def _style_shapes(X, S, lambda_softmin):
+    """(B, T, K, F) of X (B, T, F) against S (B, K, F); ValueError before anything touches the device or the library."""
+    if X.dim() != 3 or S.dim() != 3:
+        raise ValueError(f"style adherence takes X (B, T, F) and S (B, K, F), got {tuple(X.shape)} and {tuple(S.shape)}")
+    (B, T, F), (Bs, K, Fs) = X.shape, S.shape
+    if B != Bs or F != Fs:
+        raise ValueError(f"style adherence: X {tuple(X.shape)} and S {tuple(S.shape)} differ in batch or feature size")
+    if min(B, T, K, F) < 1:
+        raise ValueError(f"style adherence: empty operand, X {tuple(X.shape)}, S {tuple(S.shape)} (K = 0 has no minimum)")
+    lam = float(lambda_softmin)
+    if not 0.0 <= lam < float("inf"):
+        raise ValueError(f"style adherence: lambda_softmin = {lambda_softmin!r} must be finite and >= 0")
+    return B, T, K, F, lam
+
+
+def style_adherence_forward(X, S, lambda_softmin=10.0, soft=True):
+    """-> (L (B, T) fp32, stat (B, T)): msmd_style_adherence_forward.  X (B, T, F), S (B, K, F) contiguous fp32.  soft: L =
+    sum_k softmax_k(-lambda d) d over d[t, k] = mean_f (X[t] - S[k])^2, stat (B, T, 2) fp32 = (min_k d, log sum_k exp(-lambda (d -
+    min))); hard: L = min_k d, stat (B, T) int32 = the lowest index that attains it.  stat is what style_adherence_backward
+    reads."""
+    B, T, K, F, lam = _style_shapes(X, S, lambda_softmin)
+    _need_cuda(X, S)
+    _render_arg("X", X, torch.float32)
+    _render_arg("S", S, torch.float32)
+    L = torch.empty(B, T, device=X.device, dtype=torch.float32)
+    stat = torch.empty((B, T, 2) if soft else (B, T), device=X.device, dtype=torch.float32 if soft else torch.int32)
+    _lib.check(_lib.load().msmd_style_adherence_forward(_p(X), _p(S), _p(L), _p(stat), B, T, K, F, lam, int(bool(soft)),
+                                                        _stream()), "msmd_style_adherence_forward")
+    return L, stat
+
+
+def style_adherence_backward(X, S, L, stat, g, lambda_softmin=10.0, soft=True, need_dS=True, g_scale=1.0, need_dX=True):
+    """-> (dX (B, T, F) or None, dS (B, K, F) or None): msmd_style_adherence_backward from the forward's L and stat.  g: the
+    rows' gradient, (B, T) fp32, or one element (the upstream of a mean; pass g_scale = 1 / (B T)) that every row reads.  A
+    gradient that is not needed is not computed (its launch is skipped)."""
+    if not (need_dX or need_dS):
+        return None, None
+    B, T, K, F, lam = _style_shapes(X, S, lambda_softmin)
+    _need_cuda(X, S, L, stat, g)
+    _render_arg("X", X, torch.float32)
+    _render_arg("S", S, torch.float32)
+    _render_arg("L", L, torch.float32, (B, T))
+    _render_arg("stat", stat, torch.float32 if soft else torch.int32, (B, T, 2) if soft else (B, T))
+    _render_arg("g", g, torch.float32)
+    if g.numel() != 1 and tuple(g.shape) != (B, T):
+        raise TypeError(f"g must have one element or shape {(B, T)}, got {tuple(g.shape)}")
+    dX = torch.empty_like(X) if need_dX else None
+    dS = torch.empty_like(S) if need_dS else None
+    _lib.check(_lib.load().msmd_style_adherence_backward(_p(X), _p(S), _p(L), _p(stat), _p(g), 0 if g.numel() == 1 else 1,
+                                                         float(g_scale), _p(dX), _p(dS), B, T, K, F, lam, int(bool(soft)),
+                                                         _stream()), "msmd_style_adherence_backward")
+    return dX, dS
+
+
+def ordered_mean(x):
+    """0-dim fp32 mean of a contiguous fp32 tensor, summed in an order that depends on its size alone: msmd_ordered_mean."""
+    _need_cuda(x)
+    _render_arg("x", x, torch.float32)
+    if x.numel() < 1:
+        raise ValueError("ordered_mean of an empty tensor")
+    out = torch.empty((), device=x.device, dtype=torch.float32)
+    _lib.check(_lib.load().msmd_ordered_mean(_p(x), x.numel(), _p(out), _stream()), "msmd_ordered_mean")
+    return out
+
+
+def _nt_xent_shapes(a, b, temperature):
+    if a.dim() != 2 or b.dim() != 2 or a.shape != b.shape:
+        raise ValueError(f"nt_xent takes two (batch, feature) tensors of one shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+    if a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError(f"nt_xent: empty features {tuple(a.shape)}")
+    tau = float(temperature)
+    if not 0.0 < tau < float("inf"):
+        raise ValueError(f"nt_xent: temperature = {temperature!r} must be finite and > 0")
+    return a.shape[0], a.shape[1], tau
+
+
+def nt_xent_forward(a, b, temperature):
+    """-> (loss 0-dim fp32, row_loss (2 B), (fhat (2 B, D), norm (2 B), lse (2 B, 2))): msmd_nt_xent_forward and the ordered mean of
+    its row losses.  a, b (B, D) contiguous fp32; the last tuple is what nt_xent_backward reads."""
+    B, D, tau = _nt_xent_shapes(a, b, temperature)
+    _need_cuda(a, b)
+    _render_arg("feature_a", a, torch.float32)
+    _render_arg("feature_b", b, torch.float32)
+    fhat = torch.empty(2 * B, D, device=a.device, dtype=torch.float32)
+    norm, row_loss = (torch.empty(2 * B, device=a.device, dtype=torch.float32) for _ in range(2))
+    lse = torch.empty(2 * B, 2, device=a.device, dtype=torch.float32)
+    _lib.check(_lib.load().msmd_nt_xent_forward(_p(a), _p(b), _p(fhat), _p(norm), _p(row_loss), _p(lse), B, D, tau, _stream()),
+               "msmd_nt_xent_forward")
+    return ordered_mean(row_loss), row_loss, (fhat, norm, lse)
+
+
+def nt_xent_backward(saved, upstream, temperature):
+    """-> grad (2 B, D) fp32, rows [0, B) for feature_a and [B, 2 B) for feature_b: msmd_nt_xent_backward.  saved: the forward's
+    (fhat, norm, lse); upstream: the loss's gradient, one fp32 element on the device."""
+    fhat, norm, lse = saved
+    _need_cuda(fhat, norm, lse, upstream)
+    _render_arg("fhat", fhat, torch.float32)
+    N, D = fhat.shape
+    _render_arg("norm", norm, torch.float32, (N,))
+    _render_arg("lse", lse, torch.float32, (N, 2))
+    _render_arg("upstream", upstream, torch.float32)
+    tau = float(temperature)
+    if upstream.numel() != 1 or N % 2 or not 0.0 < tau < float("inf"):
+        raise ValueError("nt_xent_backward: upstream has one element, fhat an even number of rows, temperature > 0")
+    grad = torch.empty_like(fhat)
+    _lib.check(_lib.load().msmd_nt_xent_backward(_p(fhat), _p(norm), _p(lse), _p(upstream), _p(grad), N // 2, D, tau, _stream()),
+               "msmd_nt_xent_backward")
+    return grad

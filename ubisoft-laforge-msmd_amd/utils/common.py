@@ -1,9 +1,10 @@
 """Coefficient glue, losses and truncation augmentation on the MI355X
-(drop-in surface of reference utils/common.py:118-196, 198-620, 769-832).
+(drop-in surface of reference utils/common.py:29-91, 118-196, 198-620, 769-832, 835-875).
 
 Losses are evaluated by one generic masked-reduction HIP kernel (csrc/losses.hip); they return 0-dim fp32
 tensors (or None where the reference returns None).  These are the FORWARD values (validation `test()` path,
 reference training_script.py:245-403); the autograd path is the next build row.
+The two style losses (`StyleAdherenceLoss`, `nt_xent_loss`; csrc/style_loss.hip) carry their own HIP backward.
 """
 from __future__ import annotations
 
@@ -31,6 +32,61 @@ class NullableArgs:
     def __getattr__(self, key):            # reached only when normal lookup fails
         rule = NullableArgs._DERIVED.get(key)
         return rule(self.__dict__) if rule is not None else None
+
+
+# ----------------------------------------------------------------------------- style losses (csrc/style_loss.hip)
+def _check_style_operands(X_pred, S, lambda_softmin):
+    """ValueError for what has no answer, before the device or the library is touched."""
+    if not (torch.is_tensor(X_pred) and torch.is_tensor(S)) or X_pred.dim() != 3 or S.dim() != 3:
+        raise ValueError("StyleAdherenceLoss takes X_pred (B, T, F) and S (B, K, F)")
+    if X_pred.shape[0] != S.shape[0] or X_pred.shape[2] != S.shape[2]:
+        raise ValueError(f"StyleAdherenceLoss: X_pred {tuple(X_pred.shape)} and S {tuple(S.shape)} differ in batch or "
+                         "feature size")
+    if S.shape[1] == 0:
+        raise ValueError("StyleAdherenceLoss: the style clip has no frames (K = 0)")
+    if min(X_pred.shape) == 0:
+        raise ValueError(f"StyleAdherenceLoss: X_pred {tuple(X_pred.shape)} is empty")
+    if not 0.0 <= float(lambda_softmin) < float("inf"):
+        raise ValueError(f"StyleAdherenceLoss: lambda_softmin = {lambda_softmin!r} must be finite and >= 0")
+
+
+class StyleAdherenceLoss(torch.nn.Module):
+    """How close every generated frame is to SOME frame of the style clip (reference utils/common.py:29-91, same constructor
+    and call): d[b, t, k] = mean_f (X_pred[b, t, f] - S[b, k, f])^2; soft: sum_k softmax_k(-lambda d) d, hard: min_k d.  One
+    fused HIP kernel streams the style clip with a running soft minimum, so nothing of size T x K is ever stored, forward or
+    backward; differentiable once with respect to both operands."""
+
+    def __init__(self, use_soft_min=True, lambda_softmin=10.0):
+        super().__init__()
+        self.use_soft_min = use_soft_min
+        self.lambda_softmin = lambda_softmin
+
+    def forward(self, X_pred, S, reduce=True):
+        """X_pred (B, T, F), S (B, K, F), any floating dtype (cast to fp32 like the reference's) -> the 0-dim mean over (B, T),
+        or with reduce=False in the soft form the rows' (B, T).  The hard form returns the mean whatever `reduce` says, as the
+        reference does."""
+        from ..autograd import StyleAdherenceFn
+        _check_style_operands(X_pred, S, self.lambda_softmin)
+        ops._need_cuda(X_pred, S)
+        soft = bool(self.use_soft_min)
+        return StyleAdherenceFn.apply(X_pred.float().contiguous(), S.float().contiguous(), float(self.lambda_softmin), soft,
+                                      bool(reduce) or not soft)
+
+
+def nt_xent_loss(feature_a, feature_b, temperature):
+    """Normalised temperature-scaled cross entropy of SimCLR (reference utils/common.py:835-875, same call): rows i of
+    feature_a and feature_b (B, D) are each other's positives, every other row of the 2 B a negative.  HIP forward and
+    backward; -> 0-dim fp32, differentiable once."""
+    from ..autograd import NtXentFn
+    if not (torch.is_tensor(feature_a) and torch.is_tensor(feature_b)) or feature_a.dim() != 2 or feature_b.dim() != 2:
+        raise ValueError("nt_xent_loss takes feature_a and feature_b of shape (batch_size, feature_dim)")
+    if feature_a.shape != feature_b.shape or min(feature_a.shape) == 0:
+        raise ValueError(f"nt_xent_loss: feature_a {tuple(feature_a.shape)} and feature_b {tuple(feature_b.shape)} must have "
+                         "one non-empty shape")
+    if not 0.0 < float(temperature) < float("inf"):
+        raise ValueError(f"nt_xent_loss: temperature = {temperature!r} must be finite and > 0")
+    ops._need_cuda(feature_a, feature_b)
+    return NtXentFn.apply(feature_a.float().contiguous(), feature_b.float().contiguous(), float(temperature))
 
 
 def count_parameters(model):
