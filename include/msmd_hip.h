@@ -367,6 +367,28 @@ int msmd_denoiser_pack_input_guided(const float* motion, const float* eps, const
                                     const float* guide_values, void* feats, int N, int L, int Lp, int dm, int Kpad,
                                     int motion_batch, int out_dtype, msmd_stream_t stream);
 
+/* Everything the eval forward of the denoiser lays out before its first GEMM, in ONE launch (16-bit storage types only:
+ * dtype MSMD_BF16 / MSMD_F16, anything else returns 1).  The caller allocates every output; all are written in whole
+ * 16-byte units, so Kpad, d, kp_person and mem_stride are multiples of 8 and the 16-bit buffers 16-byte aligned.
+ *   feats (N, 1+Lp+L, Kpad)  exactly msmd_denoiser_pack_input's (motion_batch = N), with c0 = t0[ts[n]], c1 = t1[ts[n]] read
+ *                            inside from the two fp32 schedule tables (n_steps rows) and the device int64 ts (N); eps NULL =
+ *                            no q-sample (t0 / t1 unused); indicator NULL = no indicator column.  prev_motion_stride =
+ *                            elements between two sequences' (Lp, dm) blocks, 0 = one block for all.
+ *   pf (N, kp_person)        [person_a (N, cols_a) | person_b (N, cols_b) or NULL | zeros]: msmd_pad_cols' conversion.
+ *   style_out (style_n)      style (style_n fp32 values, flat) in the storage type: msmd_cast's conversion; style NULL
+ *                            with style_n = 0 = no style.
+ *   emb (N, d)               row ts[n] of emb_table (n_steps, d), storage type.
+ *   mem[n, :Lpa, :]          prev_audio (fp32; prev_audio_stride elements between sequences, 0 = one block for all) into
+ *                            the first Lpa rows of each sequence of mem (row length d, mem_stride elements per sequence).
+ * A ts entry outside [0, n_steps) reads the nearest end of the tables. */
+int msmd_denoiser_prepare(const float* motion, const float* eps, const float* t0, const float* t1, const long* ts,
+                          int n_steps, const float* prev_motion, long prev_motion_stride, const float* indicator,
+                          void* feats, int N, int L, int Lp, int dm, int Kpad, const float* person_a, int cols_a,
+                          const float* person_b, int cols_b, void* pf, int kp_person, const float* style,
+                          long style_n, void* style_out, const void* emb_table, void* emb, int d,
+                          const float* prev_audio, long prev_audio_stride, int Lpa, void* mem, long mem_stride,
+                          int dtype, msmd_stream_t stream);
+
 /* x (N, T, d) += pe (T, d) (learned PE, model.py:949); row 0 is REPLACED by tok0[n] + row0_add + pe[0]
  * (tok0 (N, d) = person projection (+ step embedding); row0_add (d) optional shared step embedding). */
 int msmd_add_pe_token(void* x, const float* pe, const void* tok0, const void* row0_add, int N, int T, int d,

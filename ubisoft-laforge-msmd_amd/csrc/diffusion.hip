@@ -8,32 +8,45 @@
 // motion.  The mask / value pair is dense, (motion_batch, L) uint8 / (motion_batch, L, dm) fp32, so a captured launch does not
 // depend on which frames are pinned or how many; the overwrite is per clip and every CFG entry of a clip reads the same
 // overwritten input.  eps (nullable): the q-sample form of the training path (no keyframes there: the entry rejects both).
-template <typename TO>
-__global__ void pack_input_kernel(const float* __restrict__ motion, const float* __restrict__ eps,
-                                  const float* __restrict__ c0, const float* __restrict__ c1,
-                                  const float* __restrict__ prev, const float* __restrict__ ind,
-                                  const unsigned char* __restrict__ guide_mask, const float* __restrict__ guide_values,
-                                  TO* __restrict__ feats, int L, int Lp, int dm, int Kpad, int motion_batch) {
-  const int n = blockIdx.y;
-  const int Tn = 1 + Lp + L;
-  const int nm = n % motion_batch;  // CFG entries share one x_t (reference model.py:389)
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < Tn * Kpad; i += gridDim.x * blockDim.x) {
-    const int r = i / Kpad - 1, k = i % Kpad;  // r == -1: person-token row, zero-filled here
-    float v = 0.f;
-    if (r >= 0 && r < Lp) {
-      if (k < dm) v = prev[((long)n * Lp + r) * dm + k];
-    } else if (r >= Lp) {
-      const int t = r - Lp;
-      if (k < dm) {
-        const long at = ((long)nm * L + t) * dm + k;
-        v = (guide_mask && guide_mask[(long)nm * L + t]) ? guide_values[at] : motion[at];
-        if (eps) v = c0[nm] * v + c1[nm] * eps[at];
-      } else if (k == dm && ind) {
-        v = ind[(long)n * L + t];
-      }
+// The operands of one packing, shared by pack_input_kernel and denoiser_prepare_kernel.  prev_stride: elements between the prev
+// rows of two sequences (Lp * dm for a contiguous (N, Lp, dm); 0 = every sequence reads the one start row block).
+struct PackInput {
+  const float* motion; const float* eps; const float* prev; const float* ind;
+  const unsigned char* guide_mask; const float* guide_values;
+  int L, Lp, dm, Kpad, motion_batch; long prev_stride;
+};
+
+// Element i (row i / Kpad, column i % Kpad) of sequence n's (1 + Lp + L, Kpad) block, before the cast to the storage type.
+// c0 / c1: the q-sample coefficients of clip n % motion_batch, read only where eps is set.
+__device__ __forceinline__ float pack_input_value(const PackInput& a, int n, int i, float c0, float c1) {
+  const int nm = n % a.motion_batch;  // CFG entries share one x_t (reference model.py:389)
+  const int r = i / a.Kpad - 1, k = i % a.Kpad;  // r == -1: person-token row, zero-filled here
+  float v = 0.f;
+  if (r >= 0 && r < a.Lp) {
+    if (k < a.dm) v = a.prev[(long)n * a.prev_stride + (long)r * a.dm + k];
+  } else if (r >= a.Lp) {
+    const int t = r - a.Lp;
+    if (k < a.dm) {
+      const long at = ((long)nm * a.L + t) * a.dm + k;
+      v = a.motion[at];
+      if (a.guide_mask && a.guide_mask[(long)nm * a.L + t]) v = a.guide_values[at];
+      if (a.eps) v = __fmaf_rn(c0, v, c1 * a.eps[at]);   // one rounding of c1 eps, then one fused multiply-add
+    } else if (k == a.dm && a.ind) {
+      v = a.ind[(long)n * a.L + t];
     }
-    feats[(long)n * Tn * Kpad + i] = from_f32<TO>(v);
   }
+  return v;
+}
+
+template <typename TO>
+__global__ void pack_input_kernel(PackInput a, const float* __restrict__ c0, const float* __restrict__ c1,
+                                  TO* __restrict__ feats) {
+  const int n = blockIdx.y;
+  const int Tn = 1 + a.Lp + a.L;
+  const int nm = n % a.motion_batch;
+  const float c0n = a.eps ? c0[nm] : 0.f, c1n = a.eps ? c1[nm] : 0.f;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < Tn * a.Kpad; i += gridDim.x * blockDim.x)
+    feats[(long)n * Tn * a.Kpad + i] = from_f32<TO>(pack_input_value(a, n, i, c0n, c1n));
 }
 
 extern "C" int msmd_denoiser_pack_input_guided(const float* motion, const float* eps, const float* c0, const float* c1,
@@ -44,10 +57,10 @@ extern "C" int msmd_denoiser_pack_input_guided(const float* motion, const float*
   if (guide_mask && (eps || !guide_values)) return 1;  // the q-sample form is the training path: no keyframes there
   if (N <= 0 || L <= 0 || Lp < 0 || dm <= 0 || Kpad < dm + (indicator ? 1 : 0) || motion_batch <= 0) return 1;
   dim3 grid(((1 + Lp + L) * Kpad + 255) / 256, N), block(256);
+  const PackInput a{motion, eps, prev_motion, indicator, guide_mask, guide_values, L, Lp, dm, Kpad, motion_batch, (long)Lp * dm};
   return dispatch_dtype<float, f16_t, bf16_t>(out_dtype, [&](auto tag) {
     typedef MSMD_TAG_T(tag) TO;
-    hipLaunchKernelGGL(pack_input_kernel<TO>, grid, block, 0, (hipStream_t)stream, motion, eps, c0, c1, prev_motion,
-                       indicator, guide_mask, guide_values, (TO*)feats, L, Lp, dm, Kpad, motion_batch);
+    hipLaunchKernelGGL(pack_input_kernel<TO>, grid, block, 0, (hipStream_t)stream, a, c0, c1, (TO*)feats);
     MSMD_RETURN_LAST();
   });
 }
@@ -510,6 +523,153 @@ extern "C" int msmd_pad_cols(const void* x, void* y, long rows, int cols_in, int
 extern "C" int msmd_cast(const void* x, void* y, long n, int in_dtype, int out_dtype, msmd_stream_t stream) {
   if (n <= 0 || n > 0x7fffffffL) return 1;
   return msmd_pad_cols(x, y, 1, (int)n, (int)n, in_dtype, out_dtype, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// msmd_denoiser_prepare: everything the denoiser's forward lays out before its first GEMM, in ONE launch.  The five outputs
+// are independent of each other, so the grid is cut into five block ranges ("roles"), each a grid-stride loop over units of 8
+// output elements (one 16-byte store) of its own buffer:
+//   feats  pack_input_value, with c0 / c1 gathered from the schedule tables at ts[clip]
+//   mem    rows [0, Lpa) of every sequence <- prev_audio (fp32), batch stride 0 = the broadcast start rows
+//   emb    row ts[n] of the step-embedding table, 16-byte copies
+//   pf     [person_a | person_b | zeros] per row: msmd_pad_cols' conversion
+//   style  flat fp32 -> storage type: msmd_cast's conversion (the last unit may be short)
+// The roles' first-past-the-end blocks are cumulative in `end`; a role with nothing to do has an empty range.
+struct PrepareArgs {
+  PackInput pack;
+  const float* t0; const float* t1; const long* ts; int n_steps;
+  const float* prev_audio; long prev_audio_stride, mem_stride; int Lpa, d;
+  const void* emb_table;
+  const float* person_a; const float* person_b; int cols_a, cols_b, kp_person;
+  const float* style; long style_n;
+  void* feats; void* mem; void* emb; void* pf; void* style_out;
+  int N, end[5];
+};
+
+// a time step as a row of a (n_steps, ...) table: an index outside the table reads its nearest end, never past it
+__device__ __forceinline__ int prepare_step(const PrepareArgs& p, int n) {
+  const long t = p.ts[n];
+  return (int)(t < 0 ? 0 : (t >= p.n_steps ? p.n_steps - 1 : t));
+}
+
+template <typename TO>
+__global__ __launch_bounds__(256) void denoiser_prepare_kernel(PrepareArgs p) {
+  typedef typename Vec8T<TO>::type V8;
+  const int b = blockIdx.x;
+  if (b < p.end[0]) {
+    const int per_seq = (1 + p.pack.Lp + p.pack.L) * p.pack.Kpad;
+    const long units = (long)p.N * (per_seq >> 3);
+    for (long u = b * 256L + threadIdx.x; u < units; u += p.end[0] * 256L) {
+      const int n = (int)(u / (per_seq >> 3)), i = (int)(u % (per_seq >> 3)) << 3;
+      float c0 = 0.f, c1 = 0.f;
+      if (p.pack.eps) {
+        const int step = prepare_step(p, n % p.pack.motion_batch);
+        c0 = p.t0[step];
+        c1 = p.t1[step];
+      }
+      V8 o;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o[e] = from_f32<TO>(pack_input_value(p.pack, n, i + e, c0, c1));
+      *(V8*)((TO*)p.feats + (long)n * per_seq + i) = o;
+    }
+  } else if (b < p.end[1]) {
+    const int per_seq = p.Lpa * p.d;
+    const long units = (long)p.N * (per_seq >> 3);
+    const int nb = p.end[1] - p.end[0];
+    for (long u = (b - p.end[0]) * 256L + threadIdx.x; u < units; u += nb * 256L) {
+      const int n = (int)(u / (per_seq >> 3)), i = (int)(u % (per_seq >> 3)) << 3;
+      const float* src = p.prev_audio + (long)n * p.prev_audio_stride + i;
+      const f32x4 lo = *(const f32x4*)src, hi = *(const f32x4*)(src + 4);
+      V8 o;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { o[e] = from_f32<TO>(lo[e]); o[4 + e] = from_f32<TO>(hi[e]); }
+      *(V8*)((TO*)p.mem + (long)n * p.mem_stride + i) = o;
+    }
+  } else if (b < p.end[2]) {
+    const int per_row = p.d >> 3;
+    const long units = (long)p.N * per_row;
+    const int nb = p.end[2] - p.end[1];
+    for (long u = (b - p.end[1]) * 256L + threadIdx.x; u < units; u += nb * 256L) {
+      const int n = (int)(u / per_row), c = (int)(u % per_row) << 3;
+      *(V8*)((TO*)p.emb + (long)n * p.d + c) = *(const V8*)((const TO*)p.emb_table + (long)prepare_step(p, n) * p.d + c);
+    }
+  } else if (b < p.end[3]) {
+    const int per_row = p.kp_person >> 3;
+    const long units = (long)p.N * per_row;
+    const int nb = p.end[3] - p.end[2];
+    for (long u = (b - p.end[2]) * 256L + threadIdx.x; u < units; u += nb * 256L) {
+      const int n = (int)(u / per_row), c0 = (int)(u % per_row) << 3;
+      V8 o;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const int c = c0 + e;
+        float v = 0.f;
+        if (c < p.cols_a) v = p.person_a[(long)n * p.cols_a + c];
+        else if (c < p.cols_a + p.cols_b) v = p.person_b[(long)n * p.cols_b + (c - p.cols_a)];
+        o[e] = from_f32<TO>(v);
+      }
+      *(V8*)((TO*)p.pf + (long)n * p.kp_person + c0) = o;
+    }
+  } else {
+    const long units = (p.style_n + 7) >> 3;
+    const int nb = p.end[4] - p.end[3];
+    for (long u = (b - p.end[3]) * 256L + threadIdx.x; u < units; u += nb * 256L) {
+      const long i = u << 3;
+      if (i + 8 <= p.style_n) {
+        V8 o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = from_f32<TO>(p.style[i + e]);
+        *(V8*)((TO*)p.style_out + i) = o;
+      } else {
+        for (long j = i; j < p.style_n; ++j) ((TO*)p.style_out)[j] = from_f32<TO>(p.style[j]);
+      }
+    }
+  }
+}
+
+extern "C" int msmd_denoiser_prepare(const float* motion, const float* eps, const float* t0, const float* t1, const long* ts,
+                                     int n_steps, const float* prev_motion, long prev_motion_stride, const float* indicator,
+                                     void* feats, int N, int L, int Lp, int dm, int Kpad, const float* person_a, int cols_a,
+                                     const float* person_b, int cols_b, void* pf, int kp_person, const float* style,
+                                     long style_n, void* style_out, const void* emb_table, void* emb, int d,
+                                     const float* prev_audio, long prev_audio_stride, int Lpa, void* mem, long mem_stride,
+                                     int dtype, msmd_stream_t stream) {
+  if (N <= 0 || L <= 0 || Lp < 0 || Lpa < 0 || dm <= 0 || Kpad < dm + (indicator ? 1 : 0) || n_steps <= 0 || d <= 0) return 1;
+  if (!motion || !feats || !ts || !emb_table || !emb || !person_a || !pf || (Lp && !prev_motion)) return 1;
+  if (eps && (!t0 || !t1)) return 1;
+  if (Lpa && (!prev_audio || !mem)) return 1;
+  if (cols_a <= 0 || cols_b < 0 || (cols_b && !person_b) || kp_person < cols_a + cols_b || style_n < 0) return 1;
+  if (style_n && (!style || !style_out)) return 1;
+  // whole 16-byte units: 8 storage elements out, 2 x 4 fp32 in
+  if ((Kpad & 7) || (d & 7) || (kp_person & 7) || (mem_stride & 7) || (prev_audio_stride & 3) || mem_stride < (long)Lpa * d) return 1;
+  if (prev_motion_stride != 0 && prev_motion_stride < (long)Lp * dm) return 1;
+  if (prev_audio_stride != 0 && prev_audio_stride < (long)Lpa * d) return 1;
+  if (((uintptr_t)feats | (uintptr_t)mem | (uintptr_t)emb | (uintptr_t)emb_table | (uintptr_t)pf | (uintptr_t)style_out |
+       (uintptr_t)prev_audio) & 15)
+    return 1;
+  PrepareArgs p{};
+  p.pack = PackInput{motion, eps, prev_motion, indicator, nullptr, nullptr, L, Lp, dm, Kpad, N, prev_motion_stride};
+  p.t0 = t0; p.t1 = t1; p.ts = ts; p.n_steps = n_steps;
+  p.prev_audio = prev_audio; p.prev_audio_stride = prev_audio_stride; p.mem_stride = mem_stride; p.Lpa = Lpa; p.d = d;
+  p.emb_table = emb_table;
+  p.person_a = person_a; p.person_b = person_b; p.cols_a = cols_a; p.cols_b = cols_b; p.kp_person = kp_person;
+  p.style = style; p.style_n = style_n;
+  p.feats = feats; p.mem = mem; p.emb = emb; p.pf = pf; p.style_out = style_out;
+  p.N = N;
+  // blocks by the bytes of a role (one 16-byte unit per thread and trip), at most 256 for the largest: launch-bound work
+  const long units[5] = {(long)N * (1 + Lp + L) * (Kpad >> 3), (long)N * Lpa * (d >> 3), (long)N * (d >> 3),
+                         (long)N * (kp_person >> 3), (style_n + 7) >> 3};
+  const int cap[5] = {256, 128, 16, 16, 16};
+  int at = 0;
+  for (int r = 0; r < 5; ++r) {
+    at += (int)min((units[r] + 255) / 256, (long)cap[r]);
+    p.end[r] = at;
+  }
+  return dispatch_dtype<f16_t, bf16_t>(dtype, [&](auto tag) {
+    typedef MSMD_TAG_T(tag) TO;
+    hipLaunchKernelGGL(denoiser_prepare_kernel<TO>, dim3(at), dim3(256), 0, (hipStream_t)stream, p);
+    MSMD_RETURN_LAST();
+  });
 }
 
 extern "C" int msmd_abi_version(void) { return 2; }   // 2: + msmd_comm_* / msmd_allreduce_bucket (round 4), msmd_comm_version

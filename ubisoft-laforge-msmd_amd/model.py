@@ -231,6 +231,7 @@ class DenoisingNetwork_MSMD(nn.Module):
         P.split = split
         P.te = f32(sd["TE.pe"][0])
         P.te_cd = P.te if split else P.te.to(dtype)
+        P.emb_table = None     # step_embeddings(): built by the first eval forward, lives and dies with this pack
         if self.use_learnable_pe:
             P.pe = f32(sd["PE"][0])
         else:
@@ -238,11 +239,13 @@ class DenoisingNetwork_MSMD(nn.Module):
             P.pe = f32(sd["PE.pe"][0, T]).expand(T, -1).contiguous()
         P.ds0 = (cd(sd["diff_step_map.0.weight"]), f32(sd["diff_step_map.0.bias"]))
         P.ds2 = (cd(sd["diff_step_map.2.weight"]), f32(sd["diff_step_map.2.bias"]))
-        P.pp = (padk(sd["person_proj.weight"]), f32(sd["person_proj.bias"]))
         # feature_proj's K = 68 is padded to a whole 64-element K tile in the 16-bit modes (zeros: the packed input rows are
         # zero-filled to the same width), so it runs on the LDS-DMA GEMM like every other projection (K = 72 took the
-        # register-staged kernel: 29.8 us per sampler step for 1.6 GFLOP)
-        P.fp = (padk(sd["feature_proj.weight"], 32 if split else (64 if dtype != torch.float32 else 8)), f32(sd["feature_proj.bias"]))
+        # register-staged kernel: 29.8 us per sampler step for 1.6 GFLOP).  person_proj's K = 356 likewise (384: the bits of
+        # the register-staged kernel at K = 360)
+        k_tile = 32 if split else (64 if dtype != torch.float32 else 8)
+        P.pp = (padk(sd["person_proj.weight"], k_tile), f32(sd["person_proj.bias"]))
+        P.fp = (padk(sd["feature_proj.weight"], k_tile), f32(sd["feature_proj.bias"]))
         P.kp_person, P.kp_feat = P.pp[0].shape[1], P.fp[0].shape[1]
         P.mask = self.alignment_mask.to(torch.uint8).contiguous() if self.alignment_mask is not None else None
         # align_mask_width == 1 (the default): motion token t >= 1 sees exactly audio frame t - 1 and the person token
@@ -291,11 +294,12 @@ class DenoisingNetwork_MSMD(nn.Module):
         return P
 
     # ------------------------------------------------------------------ pieces (shared with the sampler)
-    def static_bases(self, static_style_feat, dtype, out_dtype=None):
-        """(Ns, 1, d_style) -> (Ns, nb, dm): the 4 style->static-pose MLPs (model.py:964-971); step-invariant."""
+    def static_bases(self, static_style_feat, dtype, out_dtype=None, _rows=None):
+        """(Ns, 1, d_style) -> (Ns, nb, dm): the 4 style->static-pose MLPs (model.py:964-971); step-invariant.
+        _rows: the (Ns, d_style) style rows already in the compute dtype (forward's prepare launch wrote them)."""
         P = self.pack(dtype)
         nb, dm, d = self.num_of_basis, self.motion_feat_dim, self.feature_dim
-        s = ops.cast(static_style_feat.reshape(-1, static_style_feat.shape[-1]).contiguous(), dtype)
+        s = _rows if _rows is not None else ops.cast(static_style_feat.reshape(-1, static_style_feat.shape[-1]).contiguous(), dtype)
         Ns = s.shape[0]
         h = ops.gemm(s, *P.st0, act=ops.ACT_GELU)  # (Ns, nb*d)
         stat = torch.empty(Ns, nb, dm, device=s.device, dtype=out_dtype or dtype)
@@ -310,6 +314,23 @@ class DenoisingNetwork_MSMD(nn.Module):
         emb = ops.gemm(ops.gemm(te, *P.ds0, act=ops.ACT_GELU), *P.ds2)
         pf = ops.pad_cols(person_feat.reshape(person_feat.shape[0], -1).float().contiguous(), P.kp_person, dtype)
         return ops.gemm(pf, *P.pp, residual=emb)
+
+    def prepares_fused(self, dtype):
+        """Does forward lay its inputs out with the one msmd_denoiser_prepare launch?  Eval, 16-bit storage, and the
+        `fused_prepare` switch (default on; False = the separate launches every other mode keeps)."""
+        return bool(getattr(self, "fused_prepare", True)) and not self.training and dtype in (torch.bfloat16, torch.float16)
+
+    def step_embeddings(self, dtype):
+        """diff_step_map(TE.pe[0, t]) for every step t at once: (n_diff_steps + 1, d) in the compute dtype.  A function of the
+        packed weights alone, so it is computed once per pack -- by the same two GEMMs person_token runs on the gathered rows,
+        and a GEMM row does not depend on the rows around it: row t carries person_token's bits.  Eval only
+        (the weights move between training calls), and never built inside a stream capture."""
+        P = self.pack(dtype)
+        if P.emb_table is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("step_embeddings: run one eager forward before capturing (the table is built once per pack)")
+            P.emb_table = ops.gemm(ops.gemm(P.te_cd, *P.ds0, act=ops.ACT_GELU), *P.ds2)
+        return P.emb_table
 
     def memory_kv(self, mem, dtype, stacked=False):
         """Cross-attention K/V projections of the audio memory for every layer: step-invariant in the
@@ -446,27 +467,52 @@ class DenoisingNetwork_MSMD(nn.Module):
         return ops.gemm(h, *P.md2, out_dtype=torch.float32)
 
     def forward(self, motion_feat, audio_feat, person_feat, static_style_feat, prev_motion_feat, prev_audio_feat, step,
-                indicator=None, keep_separate=False, dtype=None, _qsample=None, _audio_cd=None):
-        """reference model.py:914-996.  Returns (N, L_p + L, d_motion) fp32."""
+                indicator=None, keep_separate=False, dtype=None, _qsample=None, _audio_cd=None, _prepared=None):
+        """reference model.py:914-996.  Returns (N, L_p + L, d_motion) fp32.
+
+        Eval forward in the 16-bit modes (`fused_prepare`, default on; False = the launches of the other modes): ONE
+        msmd_denoiser_prepare launch lays out the packed input, the padded person rows, the style rows, the gathered step
+        embedding and the previous window's audio rows.  `_prepared` is MSMD.forward's hand-over for that path:
+        (shape rows, style rows, (eps, t0, t1) or None, mem with this window's rows already written or None)."""
         dtype = dtype or getattr(self, "compute_dtype", torch.float32)
         if self.use_indicator and indicator is None:
             raise TypeError("expected Tensor as element 1 in argument 0, but got NoneType")  # reference model.py:944
         P = self.pack(dtype)
-        N = person_feat.shape[0]
+        N = motion_feat.shape[0] if person_feat is None else person_feat.shape[0]
         L, Lp, dm, nb = motion_feat.shape[1], prev_motion_feat.shape[1], self.motion_feat_dim, self.num_of_basis
         step = torch.as_tensor(step, device=self.device, dtype=torch.long)
-        tok0 = self.person_token(person_feat, step, dtype)
-        feats = torch.empty(N, 1 + Lp + L, P.kp_feat, device=self.device, dtype=dtype)
-        eps, c0, c1 = _qsample if _qsample is not None else (None, None, None)
-        ops.denoiser_pack_input(motion_feat.float().contiguous(), prev_motion_feat.float().contiguous(),
-                                indicator.float().contiguous() if self.use_indicator else None, feats, eps, c0, c1)
-        # audio memory [previous window | this window] in the compute dtype: two casting copies into one buffer
         La, Lpa = audio_feat.shape[1], prev_audio_feat.shape[1]
-        mem = torch.empty(N, Lpa + La, audio_feat.shape[2], device=self.device, dtype=dtype)
-        mem[:, :Lpa].copy_(prev_audio_feat)
-        mem[:, Lpa:].copy_(_audio_cd if _audio_cd is not None else audio_feat)
+        feats = torch.empty(N, 1 + Lp + L, P.kp_feat, device=self.device, dtype=dtype)
+        ind = indicator.float().contiguous() if self.use_indicator else None
+        if _prepared is not None or (self.prepares_fused(dtype) and _qsample is None and step.numel() == N
+                                     and motion_feat.shape[0] == N):
+            shape_rows, style_rows, tables, mem = _prepared or (person_feat, None, None, None)
+            eps, t0, t1 = tables or (None, None, None)
+            d = self.feature_dim
+            if mem is None:   # this window's features arrive as a tensor: one casting copy into its rows
+                mem = torch.empty(N, Lpa + La, d, device=self.device, dtype=dtype)
+                mem[:, Lpa:].copy_(audio_feat)
+            emb = torch.empty(N, d, device=self.device, dtype=dtype)
+            pf = torch.empty(N, P.kp_person, device=self.device, dtype=dtype)
+            s_in = static_style_feat.reshape(-1, static_style_feat.shape[-1]).contiguous()
+            s = s_in if s_in.dtype == dtype else torch.empty_like(s_in, dtype=dtype)
+            f32 = lambda t: None if t is None else t.reshape(N, -1).float().contiguous()
+            ops.denoiser_prepare(motion_feat.float().contiguous(), prev_motion_feat, ind, feats, step.reshape(-1).contiguous(),
+                                 self.step_embeddings(dtype), emb, f32(shape_rows), f32(style_rows), pf, prev_audio_feat, mem,
+                                 style=None if s is s_in else s_in.float(), style_out=None if s is s_in else s,
+                                 eps=eps, t0=t0, t1=t1)
+            tok0 = ops.gemm(pf, *P.pp, residual=emb)
+        else:
+            tok0 = self.person_token(person_feat, step, dtype)
+            eps, c0, c1 = _qsample if _qsample is not None else (None, None, None)
+            ops.denoiser_pack_input(motion_feat.float().contiguous(), prev_motion_feat.float().contiguous(), ind, feats, eps, c0, c1)
+            # audio memory [previous window | this window] in the compute dtype: two casting copies into one buffer
+            mem = torch.empty(N, Lpa + La, audio_feat.shape[2], device=self.device, dtype=dtype)
+            mem[:, :Lpa].copy_(prev_audio_feat)
+            mem[:, Lpa:].copy_(_audio_cd if _audio_cd is not None else audio_feat)
+            s = None
         dec = self.trunk(feats, tok0, mem, dtype)
-        stat = self.static_bases(static_style_feat, dtype, out_dtype=torch.float32)   # the head mixes in fp32
+        stat = self.static_bases(static_style_feat, dtype, out_dtype=torch.float32, _rows=s)   # the head mixes in fp32
         if keep_separate:
             dynamic = dec[:, :, :dm]
             alphas = dec[:, :, dm:]
@@ -629,10 +675,26 @@ class MSMD(nn.Module):
         if self.use_style:
             assert style_feat is not None, "Missing style features!"
         batch_size = motion_feat.shape[0]
+        net = self.denoising_net
+        fused = net.prepares_fused(dtype) and not self.training
+        if prev_audio_feat is None:
+            prev_audio_feat = self.start_audio_feat.expand(batch_size, -1, -1)
+        mem = None
         if audio_or_feat.ndim == 2:
             assert audio_or_feat.shape[1] == 16000 * self.n_motions / self.fps, \
                 f"Incorrect audio length {audio_or_feat.shape[1]}"
-            audio_cd = self._audio_feat(audio_or_feat, self.n_motions, dtype)      # compute dtype: what the denoiser reads
+            if fused:
+                # the audio-feature GEMM writes this window's rows of the denoiser's memory in place (one batch entry per
+                # clip: the rows of a clip are not evenly spaced behind the previous window's); the fp32 copy that is
+                # returned is cast from there
+                La, Lpa, d = self.n_motions, prev_audio_feat.shape[1], net.feature_dim
+                h = self._audio_768(audio_or_feat, La, dtype)
+                mem = torch.empty(batch_size, Lpa + La, d, device=self.device, dtype=dtype)
+                audio_cd = mem[:, Lpa:]
+                ops.gemm(h, *self._afm_packed(dtype), out=audio_cd, M=La, N=d, K=h.shape[-1], lda=h.shape[-1], ldc=d,
+                         batch=batch_size, strideA=La * h.shape[-1], strideW=0, strideC=(Lpa + La) * d)
+            else:
+                audio_cd = self._audio_feat(audio_or_feat, self.n_motions, dtype)  # compute dtype: what the denoiser reads
             audio_feat_saved = audio_cd.float()
         elif audio_or_feat.ndim == 3:
             assert audio_or_feat.shape[1] == self.n_motions, f"Incorrect audio feature length {audio_or_feat.shape[1]}"
@@ -648,8 +710,6 @@ class MSMD(nn.Module):
             style_feat = style_feat.unsqueeze(1)
         if prev_motion_feat is None:
             prev_motion_feat = self.start_motion_feat.expand(batch_size, -1, -1)
-        if prev_audio_feat is None:
-            prev_audio_feat = self.start_audio_feat.expand(batch_size, -1, -1)
         # classifier-free guidance masking (model.py:190-218)
         if len(self.guiding_conditions) > 0 and train_with_CFG:
             assert len(self.guiding_conditions) <= 2, "Only support 1 or 2 CFG conditions!"
@@ -671,19 +731,26 @@ class MSMD(nn.Module):
                 if "audio" in self.guiding_conditions:
                     audio_feat = torch.where((mask_flag > 0.9).view(-1, 1, 1),
                                              self.null_audio_feat.expand(batch_size, self.n_motions, -1), audio_feat)
-        person_feat = shape_feat if style_feat is None else torch.cat([shape_feat, style_feat], dim=-1)
         if time_step is None:
             time_step = self.diffusion_sched.uniform_sample_t(batch_size)
         ts = torch.as_tensor(time_step, device=self.device, dtype=torch.long)
-        t0, t1 = self.diffusion_sched.qsample_tables()
-        c0, c1 = t0[ts], t1[ts]                                     # sqrt(alpha_bar_t), sqrt(1 - alpha_bar_t)
+        t0, t1 = self.diffusion_sched.qsample_tables()              # sqrt(alpha_bar_t), sqrt(1 - alpha_bar_t)
         if eps is None:
             eps = torch.randn_like(motion_feat)
         eps = eps.float().contiguous()
         # q-sample is fused into the denoiser's input packing kernel (model.py:231-236)
-        out = self.denoising_net(motion_feat, audio_feat, person_feat, style_feat, prev_motion_feat, prev_audio_feat,
-                                 ts, indicator, keep_separate=keep_separate, dtype=dtype, _qsample=(eps, c0, c1),
-                                 _audio_cd=audio_cd if audio_feat is audio_feat_saved else None)
+        if fused and ts.numel() == batch_size:
+            # the prepare launch gathers the q-sample coefficients and joins the person rows itself; it keeps the memory
+            # rows the audio GEMM wrote unless CFG masking replaced this window's features
+            if mem is not None and audio_feat is not audio_feat_saved:
+                mem[:, prev_audio_feat.shape[1]:].copy_(audio_feat)
+            out = net(motion_feat, audio_feat, None, style_feat, prev_motion_feat, prev_audio_feat, ts, indicator,
+                      keep_separate=keep_separate, dtype=dtype, _prepared=(shape_feat, style_feat, (eps, t0, t1), mem))
+        else:
+            person_feat = shape_feat if style_feat is None else torch.cat([shape_feat, style_feat], dim=-1)
+            out = net(motion_feat, audio_feat, person_feat, style_feat, prev_motion_feat, prev_audio_feat, ts, indicator,
+                      keep_separate=keep_separate, dtype=dtype, _qsample=(eps, t0[ts], t1[ts]),
+                      _audio_cd=audio_cd if audio_feat is audio_feat_saved else None)
         if keep_separate:
             dyn, stat, alpha_t = out
             if self.use_head_alpha:

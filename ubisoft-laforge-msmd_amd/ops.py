@@ -694,6 +694,65 @@ def denoiser_pack_input_guided(motion, prev_motion, indicator, feats, guide_mask
     return feats
 
 
+def denoiser_prepare(motion, prev_motion, indicator, feats, ts, emb_table, emb, person_a, person_b, pf, prev_audio, mem,
+                     style=None, style_out=None, eps=None, t0=None, t1=None):
+    """The denoiser's input layout in one launch (msmd_denoiser_prepare): `feats` as denoiser_pack_input writes it with
+    c0 = t0[ts], c1 = t1[ts]; `pf` = [person_a | person_b | zeros] as pad_cols; `style_out` = cast(style); `emb` =
+    emb_table[ts]; mem[:, :Lpa] = prev_audio.  Every output is the caller's.  prev_motion (1 | N, Lp, dm) and prev_audio
+    (1 | N, Lpa, d) may be expanded views (batch stride 0).  16-bit storage types only."""
+    lib = _lib.load()
+    N, Tn, Kpad = feats.shape
+    L, dm = motion.shape[1], motion.shape[2]
+    Lp, Lpa, d = prev_motion.shape[1], prev_audio.shape[1], emb.shape[-1]
+    _need_cuda(motion, prev_motion, indicator, feats, ts, emb_table, emb, person_a, person_b, pf, prev_audio, mem, style,
+               style_out, eps, t0, t1)
+
+    def rows(t, inner, vec):
+        """fp32 (1 | N, ...) whose sequences are contiguous blocks of `inner` elements -> (tensor, batch stride); vec: the
+        blocks are read 16 bytes at a time."""
+        if t.dtype != torch.float32:
+            t = t.float()
+        if t.shape[0] != 1 and t.stride(0) == 0:
+            t = t[:1]
+        if (not t[0].is_contiguous() or (t.shape[0] > 1 and t.stride(0) < inner)
+                or (vec and (t.data_ptr() % 16 or t.stride(0) % 4))):
+            t = t.contiguous()
+        if t.shape[0] not in (1, N):
+            raise ValueError("denoiser_prepare: prev_motion / prev_audio hold 1 or N sequences")
+        return t, (0 if t.shape[0] == 1 else t.stride(0))
+    prev_motion, pm_stride = rows(prev_motion, Lp * dm, False)
+    prev_audio, pa_stride = rows(prev_audio, Lpa * d, True)
+    for t in (motion, indicator, eps, t0, t1, person_a, person_b, style):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise TypeError("denoiser_prepare: motion, indicator, eps, the schedule tables, person and style rows are contiguous fp32")
+    if ts.dtype != torch.long or ts.numel() != N or not ts.is_contiguous():
+        raise TypeError("denoiser_prepare: ts is a contiguous int64 tensor of N steps")
+    if (Tn != 1 + Lp + L or motion.shape[0] != N or (eps is not None and (eps.shape != motion.shape or t0 is None or t1 is None
+                                                                            or t0.numel() != emb_table.shape[0] or t1.numel() != t0.numel()))
+            or (indicator is not None and indicator.numel() != N * L)):
+        raise ValueError("denoiser_prepare: feats (N, 1 + Lp + L, Kpad), motion / eps (N, L, dm), indicator (N, L), tables of one length")
+    for t in (feats, emb_table, emb, pf, mem, style_out):
+        if t is not None and t.dtype != feats.dtype:
+            raise TypeError("denoiser_prepare: feats, emb_table, emb, pf, mem and style_out share one storage type")
+    if (not (feats.is_contiguous() and emb.is_contiguous() and emb_table.is_contiguous() and pf.is_contiguous())
+            or tuple(emb.shape) != (N, d) or emb_table.shape[-1] != d or emb_table.dim() != 2 or pf.shape[0] != N
+            or mem.shape[0] != N or mem.shape[1] < Lpa or mem.shape[2] != d or mem.stride(2) != 1 or mem.stride(1) != d
+            or prev_audio.shape[2] != d):
+        raise ValueError("denoiser_prepare: emb (N, d), emb_table (steps, d), pf (N, kp), mem (N, >= Lpa, d) with contiguous sequences")
+    cols_a = person_a.numel() // N
+    cols_b = 0 if person_b is None else person_b.numel() // N
+    if person_a.numel() != N * cols_a or (person_b is not None and person_b.numel() != N * cols_b):
+        raise ValueError("denoiser_prepare: person rows are (N, cols)")
+    if (style is None) != (style_out is None) or (style is not None and (style_out.numel() != style.numel() or not style_out.is_contiguous())):
+        raise ValueError("denoiser_prepare: style and style_out come together, with one element count")
+    _lib.check(lib.msmd_denoiser_prepare(_p(motion), _p(eps), _p(t0), _p(t1), _p(ts), emb_table.shape[0], _p(prev_motion),
+                                         pm_stride, _p(indicator), _p(feats), N, L, Lp, dm, Kpad, _p(person_a), cols_a,
+                                         _p(person_b), cols_b, _p(pf), pf.shape[-1], _p(style),
+                                         0 if style is None else style.numel(), _p(style_out), _p(emb_table), _p(emb), d,
+                                         _p(prev_audio), pa_stride, Lpa, _p(mem), mem.stride(0), _dt(feats), _stream()),
+               "msmd_denoiser_prepare")
+
+
 def add_pe_token(x, pe, tok0, row0_add=None):
     lib = _lib.load()
     N, T, d = x.shape
