@@ -1024,6 +1024,43 @@ int msmd_nt_xent_forward(const float* a, const float* b, float* fhat, float* nor
 int msmd_nt_xent_backward(const float* fhat, const float* norm, const float* lse, const float* upstream, float* grad, int B,
                           int D, float temperature, msmd_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Fourier resampling of motion tracks to the goal frame rate (reference dataset_processing/Step5_resample_and_assemble.py:
+ * scipy.signal.resample per track; Step3_preprocess_expression_code.py: savgol_filter(code, 5, 2, axis=0)).
+ *
+ * msmd_track_resample: x (total_in, C) fp32, a ragged batch of clips laid end to end; y (total_out, C) fp32.
+ *   in_offsets, out_offsets: (n_clips + 1) int32 prefix sums ON THE HOST, both starting at 0: clip i owns input frames
+ *   [in_offsets[i], in_offsets[i + 1]) and output frames [out_offsets[i], out_offsets[i + 1]).  They are checked here and
+ *   copied into the head of `ws` on the stream; the kernels read that copy.
+ *   Per clip, with Nx input frames, num output frames, N = min(Nx, num), K = N / 2:
+ *     X[k] = sum_n x[n] e^{-2 pi i k n / Nx}, k = 0 .. K;
+ *     N even: X[K] is doubled for num < Nx, halved for num > Nx;
+ *     y[m] = (1 / Nx) Re(X[0] + 2 sum_{k = 1 .. K} X[k] e^{+2 pi i k m / num}), where bin K enters once and by its real
+ *     part alone when it is the output's own Nyquist bin (num even, K == num / 2): scipy.signal.resample on a real track.
+ *   window != 0: x is read through a Savitzky-Golay filter along the frames, `savgol` = window * window doubles on the device
+ *   laid out as msmd_headpose_smooth's `coeffs` (interior row, then the 2 (window / 2) edge rows, scipy's mode='interp');
+ *   window odd, 3 <= window <= MSMD_HEADPOSE_MAX_WINDOW, every clip at least `window` frames.  window == 0: no filter, savgol
+ *   may be NULL.
+ *   Arithmetic: inputs widened to double, the twiddles cos / sin(2 pi r / P) tabulated per workgroup in double for the
+ *   integer residue r = k n mod Nx (m k mod num) stepped exactly, sums in double in ascending n (k); the only fp32 rounding
+ *   is the store of y.  A clip's bits depend on (Nx, num, window) and its own samples alone: no atomics, no cross-clip state.
+ *   Two launches behind the copy of the offsets, whatever n_clips is: the analysis, a workgroup per (clip, MSMD_TRACK_ROWS
+ *   bins, MSMD_TRACK_CH_TILE channels) with the (filtered) frames staged MSMD_TRACK_STAGE at a time, writes the scaled
+ *   spectrum to `ws`; the synthesis, a workgroup per (clip, MSMD_TRACK_ROWS output frames, MSMD_TRACK_CH_TILE channels) with
+ *   the bins staged MSMD_TRACK_STAGE at a time.
+ *   ws: msmd_track_resample_ws_bytes(total_in, n_clips, C) bytes on the device, 16-byte aligned.
+ * Returns 1 (hipErrorInvalidValue) before any launch for a NULL pointer, n_clips or C < 1, C > 65535 MSMD_TRACK_CH_TILE, a
+ * window outside the above, offsets that do not start at 0, a clip of fewer than 1 (or `window`) or more than
+ * MSMD_TRACK_MAX_FRAMES input or output frames; otherwise 0 or the hipError_t of the copy or a launch.
+ * msmd_track_resample_ws_bytes returns 0 for arguments out of range. */
+#define MSMD_TRACK_MAX_FRAMES 4096
+#define MSMD_TRACK_ROWS 16
+#define MSMD_TRACK_CH_TILE 16
+#define MSMD_TRACK_STAGE 64
+long msmd_track_resample_ws_bytes(long total_in, int n_clips, int C);
+int msmd_track_resample(const float* x, const int* in_offsets, const int* out_offsets, int n_clips, int C, const double* savgol,
+                        int window, void* ws, float* y, msmd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

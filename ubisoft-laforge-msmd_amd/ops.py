@@ -1835,6 +1835,59 @@ def headpose_smooth(R, clip_offsets, table, window, want_matrix=False):
     return ypr, R_mod
 
 
+# ----------------------------------------------------------------------------- track resampling (csrc/track_resample.hip)
+TRACK_MAX_FRAMES = 4096    # MSMD_TRACK_MAX_FRAMES: frames of one clip, in or out
+TRACK_ROWS = 16            # MSMD_TRACK_ROWS: bins / output frames per workgroup
+TRACK_CH_TILE = 16         # MSMD_TRACK_CH_TILE: channels per workgroup
+TRACK_STAGE = 64           # MSMD_TRACK_STAGE: frames / bins staged in LDS per pass
+
+
+def _track_offsets(name, offsets, total, window=0):
+    off = [int(o) for o in offsets]
+    if len(off) < 2 or off[0] != 0 or off[-1] != total:
+        raise ValueError(f"{name} must run from 0 to {total}, got {off[:1]} .. {off[-1:]}")
+    for a, b in zip(off[:-1], off[1:]):
+        if not 1 <= b - a <= TRACK_MAX_FRAMES:
+            raise ValueError(f"{name}: a clip must have 1 .. {TRACK_MAX_FRAMES} frames, got {b - a}")
+        if b - a < window:
+            raise ValueError(f"a clip of {b - a} frames is shorter than the window of {window}")
+    return off
+
+
+def track_resample(x, in_offsets, out_offsets, savgol_table=None, window=0):
+    """-> y (out_offsets[-1], C) fp32: msmd_track_resample, scipy.signal.resample along the frames of every clip
+    [in_offsets[k], in_offsets[k + 1]) of x (n, C) fp32 to out_offsets[k + 1] - out_offsets[k] frames, one call for the whole
+    list.  The offsets are on the HOST (checked here: ascending from 0, 1 .. TRACK_MAX_FRAMES frames a clip).
+    window != 0: the track is read through the Savitzky-Golay filter of `savgol_table` (window * window) float64 on the
+    device (utils/head_pose.savgol_table), window odd in [3, HEADPOSE_MAX_WINDOW], every clip at least `window` frames."""
+    _need_cuda(x, savgol_table)
+    _render_arg("x", x, torch.float32)
+    if x.dim() != 2 or x.shape[0] == 0 or x.shape[1] == 0:
+        raise TypeError(f"x must have shape (n_frames, C) and not be empty, got {tuple(x.shape)}")
+    window = int(window)
+    if window != 0:
+        if window < 3 or window > HEADPOSE_MAX_WINDOW or window % 2 == 0:
+            raise ValueError(f"window must be 0 or odd and in [3, {HEADPOSE_MAX_WINDOW}], got {window}")
+        _render_arg("savgol_table", savgol_table, torch.float64, (window * window,))
+    elif savgol_table is not None:
+        raise ValueError("savgol_table given with window = 0")
+    n, C = x.shape
+    if C > 65535 * TRACK_CH_TILE:
+        raise ValueError(f"x has {C} channels; the kernel takes up to {65535 * TRACK_CH_TILE}")
+    off_in = _track_offsets("in_offsets", in_offsets, n, window)
+    if len(out_offsets) != len(off_in):
+        raise ValueError(f"{len(off_in) - 1} input clips but {len(out_offsets) - 1} output clips")
+    off_out = _track_offsets("out_offsets", out_offsets, int(out_offsets[-1]))
+    n_clips = len(off_in) - 1
+    lib = _lib.load()
+    host_in, host_out = torch.tensor(off_in, dtype=torch.int32), torch.tensor(off_out, dtype=torch.int32)
+    ws = torch.empty(lib.msmd_track_resample_ws_bytes(n, n_clips, C), device=x.device, dtype=torch.uint8)
+    y = torch.empty(off_out[-1], C, device=x.device, dtype=torch.float32)
+    _lib.check(lib.msmd_track_resample(_p(x), _p(host_in), _p(host_out), n_clips, C, _p(savgol_table), window, _p(ws), _p(y),
+                                       _stream()), "msmd_track_resample")
+    return y
+
+
 # ----------------------------------------------------------------------------- style losses (csrc/style_loss.hip, DESIGN.md 5.19)
 STYLE_ROWS = 16      # MSMD_STYLE_ROWS: rows of X per workgroup
 STYLE_KTILE = 64     # MSMD_STYLE_KTILE: style frames per LDS tile
