@@ -562,8 +562,9 @@ int msmd_landmarks(const float* verts, const int* faces, const int* lmk_faces_id
 /* Backward of msmd_landmarks: grad_lmk (B, L, 3) scattered to grad_verts (B, V, 3); faces / lmk_faces_idx / bary and their
  * batch strides exactly as the forward takes them.  Landmarks that share a vertex are summed without atomics, in
  * (landmark, corner) order: the result is bit-identical from run to run.  accumulate == 0: every vertex of grad_verts is
- * written (untouched ones with 0, in the same launch); accumulate != 0: the sums are added into grad_verts.  L <= 1024.
- * No gradient goes to the tables. */
+ * written (untouched ones with 0, in the same launch); accumulate != 0: the sums are added into grad_verts.
+ * L <= MSMD_LANDMARKS_BWD_MAX_L (a frame's 3 L contributions are kept in LDS).  No gradient goes to the tables. */
+#define MSMD_LANDMARKS_BWD_MAX_L 1024
 int msmd_landmarks_bwd(const float* grad_lmk, const int* faces, const int* lmk_faces_idx, long idx_bstride,
                        const float* bary, long bary_bstride, float* grad_verts, int B, int V, int L, int accumulate,
                        msmd_stream_t stream);
@@ -615,7 +616,7 @@ int msmd_rotation_convert_bwd(int op, const float* in, const float* in2, const f
  *   landmarks (n_frames, P, 3) fp32.  Frame f is (1 - plan_w[f]) landmarks[plan_a[f]] + plan_w[f] landmarks[plan_b[f]]:
  *   a tracked frame names itself with weight 0 (plan_b is then not read), a missing one its two tracked neighbours.
  *   plan_a, plan_b (n_frames) int32 frame indices into the whole batch, plan_w (n_frames) fp32.
- *   neutral (P, 3) fp32, read at static_idx only; static_idx (S) int32 in [0, P), 3 <= S <= 64.  plan_a / plan_b / static_idx
+ *   neutral (P, 3) fp32, read at static_idx only; static_idx (S) int32 in [0, P), 3 <= S <= MSMD_HEADPOSE_MAX_STATIC.  plan_a / plan_b / static_idx
  *   outside their ranges are the caller's error; the kernel clamps them, so nothing is read out of bounds.
  *   With X the S static points of the frame and Y those of the neutral shape (Umeyama's similarity fit, the reference's
  *   procrustes_analysis): cov = (1/S) (Y - mu_y)(X - mu_x)^T = U D V^T, Sg = diag(1, 1, det(U) det(V^T) < 0 ? -1 : 1),
@@ -627,7 +628,7 @@ int msmd_rotation_convert_bwd(int op, const float* in, const float* in2, const f
  *   and the outputs are unspecified (possibly NaN).  Coplanar points (S = 3 always) still determine R: U's third column is
  *   completed as u0 x u1 and the sign rule above applies as it stands -- which is the reference's rule for a rank-deficient
  *   covariance, but the reference chooses between that rule and det(cov) < 0 by a numerical rank test, so agreement with it
- *   on (nearly) coplanar points is not promised.  Returns 1 for S outside [3, 64], S > P or a NULL pointer other than `aligned`.
+ *   on (nearly) coplanar points is not promised.  Returns 1 for S outside [3, MSMD_HEADPOSE_MAX_STATIC], S > P or a NULL pointer other than `aligned`.
  *
  * msmd_headpose_smooth, one workgroup per clip: R (n_frames, 9) fp32 as msmd_headpose_fit wrote it; clip_offsets (n_clips + 1)
  *   int64 on the device, clip k owns frames [clip_offsets[k], clip_offsets[k + 1]); a clip shorter than `window` is left unwritten.
@@ -644,6 +645,7 @@ int msmd_rotation_convert_bwd(int op, const float* in, const float* in2, const f
  *   OUTSIDE THE CONTRACT: gimbal lock, |pitch| within 1e-3 degrees of 90 (yaw and roll are then not separately defined). */
 #define MSMD_HEADPOSE_MAX_WINDOW 33
 #define MSMD_HEADPOSE_CHUNK 256
+#define MSMD_HEADPOSE_MAX_STATIC 64 /* msmd_headpose_fit: one static landmark per lane of a wave */
 int msmd_headpose_fit(const float* landmarks, const int* plan_a, const int* plan_b, const float* plan_w, const float* neutral,
                       const int* static_idx, float* R, float* c, float* t, float* aligned, int n_frames, int P, int S,
                       msmd_stream_t stream);
@@ -826,7 +828,7 @@ int msmd_render_raster(const float* screen, const float* normals, const int* fac
  * the ordinary OpenGL / OBJ ones (GL_REPEAT, GL_LINEAR magnification, GL_LINEAR_MIPMAP_LINEAR minification, v up, no sRGB
  * conversion), stated here because they are this project's: there is no pixel parity with pyrender.
  *
- * Pyramid of a (Ht, Wt, 3 | 4) uint8 image (alpha ignored), 1 <= Ht, Wt <= 4096, any size: L = 1 + floor(log2(max(Ht, Wt)))
+ * Pyramid of a (Ht, Wt, 3 | 4) uint8 image (alpha ignored), 1 <= Ht, Wt <= MSMD_TEXTURE_MAX_SIDE, any size: L = 1 + floor(log2(max(Ht, Wt)))
  *   levels, level l + 1 of size max(1, H_l >> 1) x max(1, W_l >> 1), stored one after the other as fp32 RGBA texels (16
  *   bytes, values 0 .. 255, the fourth component 0).  Level 0 is the image's bytes converted; texel (y, x) of level l + 1 is
  *   ((a + b) + (c + d)) * 0.25f in fp32 with a = (2y, 2x), b = (2y, min(2x + 1, W_l - 1)), c = (min(2y + 1, H_l - 1), 2x),
@@ -851,6 +853,7 @@ int msmd_render_raster(const float* screen, const float* normals, const int* fac
  *   - uvl (B, H, W, 3) fp32 or NULL: (u, v, lambda) as sampled (u and v after the not-finite rule, unwrapped; lambda
  *     clamped), zeros where face_id is outside [0, F).
  *   Depth and face_id are not written and pixels outside the mesh are left as they are. */
+#define MSMD_TEXTURE_MAX_SIDE 4096
 long msmd_texture_texels(int Ht, int Wt);
 int msmd_texture_mips(const void* img, int Ht, int Wt, int channels, float* pyramid, msmd_stream_t stream);
 int msmd_render_shade_textured(const float* screen, const float* normals, const int* faces, const float* vt, const int* ft,
@@ -862,8 +865,8 @@ int msmd_render_shade_textured(const float* screen, const float* normals, const 
  * FLAMETex albedo model (reference utils/flame.py:247-301): a linear texture space over an (Hs, Ws, 3)
  * image (the reference's is 512 x 512), evaluated for ONE code, nearest-resized to (Hd, Wd) and channel-reversed.
  *   mean (Hs Ws 3) fp32, basis (Hs Ws 3, n_tex) fp32 row-major and contiguous, code (n_tex) fp32 (reference l.292: row 0 of
- *   texcode; every copy is the same image, l.300).  1 <= Hs, Ws, Hd, Wd <= 4096, 1 <= n_tex <= 256, else hipErrorInvalidValue
- *   without a launch.  Row offsets are 64-bit.
+ *   texcode; every copy is the same image, l.300).  1 <= Hs, Ws, Hd, Wd <= MSMD_FLAMETEX_MAX_SIDE,
+ *   1 <= n_tex <= MSMD_FLAMETEX_MAX_TEX, else hipErrorInvalidValue without a launch.  Row offsets are 64-bit.
  *   - source index of destination index d (F.interpolate's nearest rule, l.299): min((int)floorf(d * scale), S - 1) in fp32
  *     with scale = (float)S / (float)D; at 512 -> 256 the even rows and columns;
  *   - value of channel c at (y, x) (l.296-300): mean[r] + sum_k basis[r, k] code[k], r = (sy(y) Ws + sx(x)) 3 + (2 - c).  The
@@ -882,6 +885,8 @@ int msmd_render_shade_textured(const float* screen, const float* normals, const 
  *   inputs give the same bits on every run. */
 #define MSMD_TEX_PLANAR_F32 0
 #define MSMD_TEX_IMAGE_U8 1
+#define MSMD_FLAMETEX_MAX_SIDE 4096
+#define MSMD_FLAMETEX_MAX_TEX 256
 int msmd_flametex_forward(const float* mean, const float* basis, const float* code, void* out, int out_format, int n_copies,
                           int Hs, int Ws, int Hd, int Wd, int n_tex, msmd_stream_t stream);
 long msmd_flametex_backward_workspace(int Hd, int Wd, int n_tex);
@@ -918,8 +923,9 @@ int msmd_flametex_backward(const float* basis, const float* grad_out, int n_copi
  *   Reads and writes the descriptors would place outside pcm_elems / out_elems are dropped.
  * msmd_audio_znorm: two launches.  One wave per clip adds the clip's partial pairs in run order and leaves stats (n_clips, 2)
  *   double = (mean, 1 / (std + 1e-5)); then out is normalised in place from stats.  Linear in the clips' lengths.
- * n_clips <= 65535 per call (the clip is the grid's y index). */
+ * n_clips <= MSMD_AUDIO_MAX_CLIPS per call (the clip is the grid's y index). */
 #define MSMD_AUDIO_RUN 256
+#define MSMD_AUDIO_MAX_CLIPS 65535
 int msmd_audio_resample(const void* pcm, long pcm_elems, int is_int16, const long* desc, int n_clips, long max_out_len,
                         int L, int M, int taps, const float* bank, float* out, long out_elems, double* partials,
                         msmd_stream_t stream);
@@ -1013,6 +1019,7 @@ int msmd_jpeg_write(const short* coef, int B, int H, int W, const void* header, 
 #define MSMD_STYLE_ROWS 16
 #define MSMD_STYLE_KTILE 64
 #define MSMD_STYLE_FCHUNK 64
+#define MSMD_NT_XENT_CHUNK 256 /* rows j per step of msmd_nt_xent_backward's coefficient table */
 int msmd_style_adherence_forward(const float* X, const float* S, float* L, void* stat, int B, int T, int K, int F, float lambda,
                                  int soft, msmd_stream_t stream);
 int msmd_style_adherence_backward(const float* X, const float* S, const float* L, const void* stat, const float* g,
@@ -1049,7 +1056,7 @@ int msmd_nt_xent_backward(const float* fhat, const float* norm, const float* lse
  *   spectrum to `ws`; the synthesis, a workgroup per (clip, MSMD_TRACK_ROWS output frames, MSMD_TRACK_CH_TILE channels) with
  *   the bins staged MSMD_TRACK_STAGE at a time.
  *   ws: msmd_track_resample_ws_bytes(total_in, n_clips, C) bytes on the device, 16-byte aligned.
- * Returns 1 (hipErrorInvalidValue) before any launch for a NULL pointer, n_clips or C < 1, C > 65535 MSMD_TRACK_CH_TILE, a
+ * Returns 1 (hipErrorInvalidValue) before any launch for a NULL pointer, n_clips or C < 1, C > MSMD_TRACK_MAX_CHANNELS, a
  * window outside the above, offsets that do not start at 0, a clip of fewer than 1 (or `window`) or more than
  * MSMD_TRACK_MAX_FRAMES input or output frames; otherwise 0 or the hipError_t of the copy or a launch.
  * msmd_track_resample_ws_bytes returns 0 for arguments out of range. */
@@ -1057,6 +1064,7 @@ int msmd_nt_xent_backward(const float* fhat, const float* norm, const float* lse
 #define MSMD_TRACK_ROWS 16
 #define MSMD_TRACK_CH_TILE 16
 #define MSMD_TRACK_STAGE 64
+#define MSMD_TRACK_MAX_CHANNELS 1048560 /* 65535 tiles of MSMD_TRACK_CH_TILE: the channel tile is the grid's z index */
 long msmd_track_resample_ws_bytes(long total_in, int n_clips, int C);
 int msmd_track_resample(const float* x, const int* in_offsets, const int* out_offsets, int n_clips, int C, const double* savgol,
                         int window, void* ws, float* y, msmd_stream_t stream);

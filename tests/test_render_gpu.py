@@ -213,6 +213,53 @@ def test_surface():
             ops.render_raster(*args)
 
 
+def test_argument_spec():
+    """ops._arg, the one check between a caller of the data-prep and media wrappers and a kernel that indexes raw pointers."""
+    from msmd_amd import ops
+    f32, i32 = torch.float32, torch.int32
+    z = lambda *shape, dtype=f32: torch.zeros(*shape, dtype=dtype, device=DEV)
+    d = {}
+    ops._arg("verts", z(2, 5, 3), f32, "B V 3", d)
+    ops._arg("faces", z(7, 3, dtype=i32), i32, "F 3", d)
+    assert d == {"B": 2, "V": 5, "F": 7}
+    ops._arg("csr_offsets", z(6, dtype=i32), i32, (d["V"] + 1,))
+    # a name bound by one argument and violated by a later one: the later argument, the bound size and the offending one
+    with pytest.raises(TypeError, match=r"normals must have shape \(2, 5, 3\), got \(2, 4, 3\)"):
+        ops._arg("normals", z(2, 4, 3), f32, "B V 3", d)
+    with pytest.raises(TypeError, match=r"ft must have shape \(7, 3\), got \(6, 3\)"):
+        ops._arg("ft", z(6, 3, dtype=i32), i32, "F 3", d)
+    assert d == {"B": 2, "V": 5, "F": 7}                                   # a refused argument binds nothing
+    with pytest.raises(TypeError, match=r"lights must have shape \(L, 4\), got \(4,\)"):
+        ops._arg("lights", z(4), f32, "L 4", d)
+    with pytest.raises(TypeError, match=r"view must have shape \(3, 4\), got \(4, 3\)"):
+        ops._arg("view", z(4, 3), f32, "3 4")
+    with pytest.raises(TypeError, match=r"m must have shape \(n, n\), got \(2, 3\)"):
+        ops._arg("m", z(2, 3), f32, "n n")
+    # a set entry
+    for c in (3, 4):
+        ops._arg("img", z(8, 9, c, dtype=torch.uint8), torch.uint8, ("Ht", "Wt", (3, 4)))
+    with pytest.raises(TypeError, match=r"img must have shape \(Ht, Wt, 3 \| 4\), got \(8, 9, 2\)"):
+        ops._arg("img", z(8, 9, 2, dtype=torch.uint8), torch.uint8, ("Ht", "Wt", (3, 4)))
+    # "+": at least one
+    ops._arg("vt", z(1, 2), f32, "Nt+ 2")
+    ops._arg("faces", z(0, 3, dtype=i32), i32, "F 3")
+    with pytest.raises(TypeError, match=r"vt must have shape \(Nt, 2\), got \(0, 2\)"):
+        ops._arg("vt", z(0, 2), f32, "Nt+ 2")
+    # None passes only where it may; a tensor is contiguous, on the device and of the stated dtype
+    ops._arg("rot", None, f32, "B 3", d, optional=True)
+    for bad in (None, np.zeros((2, 3), np.float32), z(2, 3).cpu(), z(2, 3).double(), z(2, 3, dtype=i32), z(3, 2).t(), z(2, 6)[:, ::2]):
+        with pytest.raises(TypeError, match="rot must be a contiguous torch.float32 CUDA tensor"):
+            ops._arg("rot", bad, f32, "B 3", d)
+    # the Savitzky-Golay table of the smoothing wrappers goes through the same check
+    assert ops._savgol_window(5, ("table", z(25, dtype=torch.float64))) == 5
+    with pytest.raises(TypeError, match=r"table must have shape \(25,\), got \(24,\)"):
+        ops._savgol_window(5, ("table", z(24, dtype=torch.float64)))
+    with pytest.raises(TypeError, match="table must be a contiguous torch.float64"):
+        ops._savgol_window(5, ("table", z(25)))
+    with pytest.raises(TypeError, match="table must be a contiguous torch.float64"):
+        ops._savgol_window(5, ("table", None))
+
+
 def test_render_coeffs_equals_the_chain():
     from types import SimpleNamespace
     from msmd_amd.inference import render_coeffs

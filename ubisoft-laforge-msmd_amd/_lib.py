@@ -50,6 +50,14 @@ def parse_header(path: str = HEADER):
 RESTYPE = {}
 
 
+def parse_constants(path: str = HEADER):
+    """Return {"MSMD_<NAME>": int} for every ``#define MSMD_<NAME> <value>`` of the header whose value is a decimal integer
+    or ``(1 << n)``; comments are stripped first.  Reads the header alone: the library need not exist."""
+    src = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
+    found = re.findall(r"^[ \t]*#[ \t]*define[ \t]+(MSMD_\w+)[ \t]+(?:(\d+)|\(1 << (\d+)\))[ \t]*$", src, flags=re.M)
+    return {name: int(dec) if dec else 1 << int(shift) for name, dec, shift in found}
+
+
 class MsmdLibraryError(RuntimeError):
     pass
 

@@ -37,8 +37,7 @@ __device__ __forceinline__ float downmix_at(const S* __restrict__ pcm, const Cli
 
 // Fixed-order sum over the workgroup's 256 lanes in double: xor tree inside a wave, then the four waves in wave order.
 __device__ __forceinline__ double block_sum_f64(double v, double* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  v = wave_sum_f64(v);
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   if (lane == 0) red[wid] = v;
   __syncthreads();
@@ -150,7 +149,7 @@ __global__ __launch_bounds__(AR_THREADS) void audio_znorm_kernel(float* __restri
 extern "C" int msmd_audio_resample(const void* pcm, long pcm_elems, int is_int16, const long* desc, int n_clips,
                                    long max_out_len, int L, int M, int taps, const float* bank, float* out, long out_elems,
                                    double* partials, msmd_stream_t stream) {
-  if (n_clips <= 0 || n_clips > 65535 || max_out_len <= 0 || pcm_elems <= 0 || out_elems <= 0 || L <= 0 || M <= 0) return 1;
+  if (n_clips <= 0 || n_clips > MSMD_AUDIO_MAX_CLIPS || max_out_len <= 0 || pcm_elems <= 0 || out_elems <= 0 || L <= 0 || M <= 0) return 1;
   if (taps == 0 ? (L != 1 || M != 1) : (taps < 4 || (taps & 1) || bank == nullptr)) return 1;
   const long runs = (max_out_len + AR_RUN - 1) / AR_RUN;
   if (runs > 2147483647L) return 1;
@@ -169,7 +168,7 @@ extern "C" int msmd_audio_resample(const void* pcm, long pcm_elems, int is_int16
 
 extern "C" int msmd_audio_znorm(float* out, long out_elems, const long* desc, int n_clips, long max_out_len,
                                 const double* partials, double* stats, msmd_stream_t stream) {
-  if (n_clips <= 0 || n_clips > 65535 || max_out_len <= 0 || out_elems <= 0 || stats == nullptr) return 1;
+  if (n_clips <= 0 || n_clips > MSMD_AUDIO_MAX_CLIPS || max_out_len <= 0 || out_elems <= 0 || stats == nullptr) return 1;
   const long runs = (max_out_len + AR_RUN - 1) / AR_RUN, blocks = (max_out_len + AZ_RUN - 1) / AZ_RUN;
   if (blocks > 2147483647L) return 1;
   hipLaunchKernelGGL(audio_stats_kernel, dim3((unsigned)n_clips), dim3(64), 0, (hipStream_t)stream, desc, partials, stats, runs);

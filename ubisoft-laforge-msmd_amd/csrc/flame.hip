@@ -333,7 +333,7 @@ extern "C" int msmd_landmarks(const float* verts, const int* faces, const int* l
 // the FIRST contribution of each vertex id owns that vertex and adds up all contributions of the same id in list order,
 // then stores (accumulate = 0) or adds into (accumulate != 0) the vertex gradient.  With accumulate = 0 the same launch
 // zero-fills the frame's other vertices first (a barrier orders the fill before the owners' stores).
-#define LMK_BWD_MAXL 1024
+#define LMK_BWD_MAXL MSMD_LANDMARKS_BWD_MAX_L
 __global__ __launch_bounds__(256) void landmarks_bwd_kernel(const float* __restrict__ glmk, const int* __restrict__ faces,
                                                             const int* __restrict__ idx, long idx_bs,
                                                             const float* __restrict__ bary, long bary_bs,

@@ -4,8 +4,8 @@
 // rows only.  A destination pixel's three rows are one contiguous run of 3 n_tex floats of the module's own buffer.
 #include "common.h"
 
-#define FT_MAX_SIDE 4096
-#define FT_MAX_TEX 256
+#define FT_MAX_SIDE MSMD_FLAMETEX_MAX_SIDE
+#define FT_MAX_TEX MSMD_FLAMETEX_MAX_TEX
 #define FT_GROUP 16                 // lanes per destination pixel in the forward kernel (4 pixels per wave)
 #define FT_FWD_THREADS 256
 #define FT_BWD_THREADS 256

@@ -3,18 +3,12 @@
 // quaternion sign continuity, a Savitzky-Golay filter with polynomial edge rows and the intrinsic Y-X-Z angles.
 // Outside the contract (include/msmd_hip.h): agreement with the reference on a covariance of rank < 3 (collinear points have no
 // fit at all), and |pitch| within 1e-3 degrees of 90.
-#include "common.h"
+#include "savgol.h"
 
 constexpr int HP_WG = 256;
 constexpr int HP_TILE = 1024;          // landmarks staged per pass of the transform
-constexpr int HP_MAX_WINDOW = 33;      // MSMD_HEADPOSE_MAX_WINDOW
-static_assert(HP_MAX_WINDOW == MSMD_HEADPOSE_MAX_WINDOW && HP_WG == MSMD_HEADPOSE_CHUNK, "header and kernel disagree");
+static_assert(HP_WG == MSMD_HEADPOSE_CHUNK && MSMD_WAVE == MSMD_HEADPOSE_MAX_STATIC, "header and kernel disagree");
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 __device__ __forceinline__ int clamp_index(int i, int n) { return i < 0 ? 0 : (i >= n ? n - 1 : i); }
 
 // One-sided Jacobi on the columns a0, a1, a2 of a 3 x 3 matrix with V accumulated in v0, v1, v2: one rotation of the pair
@@ -180,7 +174,7 @@ extern "C" int msmd_headpose_fit(const float* landmarks, const int* plan_a, cons
                                  const float* neutral, const int* static_idx, float* R, float* c, float* t, float* aligned,
                                  int n_frames, int P, int S, msmd_stream_t stream) {
   if (!landmarks || !plan_a || !plan_b || !plan_w || !neutral || !static_idx || !R || !c || !t) return 1;
-  if (n_frames <= 0 || P <= 0 || S < 3 || S > MSMD_WAVE || S > P || (long)P * 3 > 0x7fffffffL) return 1;
+  if (n_frames <= 0 || P <= 0 || S < 3 || S > MSMD_HEADPOSE_MAX_STATIC || S > P || (long)P * 3 > 0x7fffffffL) return 1;
   hipLaunchKernelGGL(headpose_fit_kernel, dim3((unsigned)n_frames), dim3(HP_WG), 0, (hipStream_t)stream, landmarks, plan_a, plan_b,
                      plan_w, neutral, static_idx, R, c, t, aligned, n_frames, P, S);
   MSMD_RETURN_LAST();
@@ -215,18 +209,17 @@ __host__ __device__ __forceinline__ Quat quat_of(const float* __restrict__ m) {
 __global__ __launch_bounds__(HP_WG) void headpose_smooth_kernel(const float* __restrict__ R, const long* __restrict__ clip_offsets,
                                                                 const double* __restrict__ coeffs, int window,
                                                                 float* __restrict__ ypr_deg, float* __restrict__ R_out) {
-  constexpr int HALO = HP_MAX_WINDOW - 1;
+  constexpr int HALO = SAVGOL_MAX_WINDOW - 1;
   __shared__ Quat s_q[HALO + HP_WG];
   __shared__ Quat s_raw[HP_WG];
-  __shared__ double s_coef[HP_MAX_WINDOW * HP_MAX_WINDOW];
+  __shared__ double s_coef[SAVGOL_TABLE];
   __shared__ int s_par[HP_WG / MSMD_WAVE];
   const long begin = clip_offsets[blockIdx.x];
   const int F = (int)(clip_offsets[blockIdx.x + 1] - begin);
   const int h = window >> 1, halo = window - 1;
   if (F < window) return;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  for (int i = tid; i < window * window; i += HP_WG) s_coef[i] = coeffs[i];
-  const double* __restrict__ edges = s_coef + window;
+  savgol_stage<HP_WG>(s_coef, coeffs, window);
   Quat carry_q = Quat{0, 0, 0, 0};           // raw quaternion of the frame before this chunk (uniform across the workgroup)
   int carry_par = 0;                         // parity of the flips up to and including that frame
   for (int c0 = 0; c0 < F; c0 += HP_WG) {
@@ -253,11 +246,8 @@ __global__ __launch_bounds__(HP_WG) void headpose_smooth_kernel(const float* __r
     // frames [c0 - halo, c0 + n) of the clip are s_q[0 .. halo + n): write those whose window is complete
     const int lo = max(c0 - h, 0), hi = (c0 + n == F) ? F : c0 + n - h;
     for (int j = lo + tid; j < hi; j += HP_WG) {
-      const double* __restrict__ row;
-      int first;                              // clip frame of the window's first sample
-      if (j < h) { row = edges + j * window; first = 0; }
-      else if (j >= F - h) { row = edges + (h + j - (F - h)) * window; first = F - window; }
-      else { row = s_coef; first = j - h; }
+      int first;
+      const double* __restrict__ row = savgol_row(s_coef, window, j, F, first);
       const Quat* __restrict__ src = s_q + (first - (c0 - halo));
       double x = 0, y = 0, z = 0, ww = 0;
       for (int m = 0; m < window; ++m) {
@@ -299,7 +289,7 @@ __global__ __launch_bounds__(HP_WG) void headpose_smooth_kernel(const float* __r
 extern "C" int msmd_headpose_smooth(const float* R, const long* clip_offsets, int n_clips, const double* coeffs, int window,
                                     float* ypr_deg, float* R_out, msmd_stream_t stream) {
   if (!R || !clip_offsets || !coeffs || !ypr_deg || n_clips <= 0) return 1;
-  if (window < 3 || window > HP_MAX_WINDOW || !(window & 1)) return 1;
+  if (!savgol_window_ok(window)) return 1;
   hipLaunchKernelGGL(headpose_smooth_kernel, dim3((unsigned)n_clips), dim3(HP_WG), 0, (hipStream_t)stream, R, clip_offsets, coeffs,
                      window, ypr_deg, R_out);
   MSMD_RETURN_LAST();

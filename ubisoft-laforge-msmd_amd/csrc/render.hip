@@ -304,7 +304,7 @@ __global__ __launch_bounds__(RT_THREADS) void render_raster_kernel(const float* 
 }
 
 // ------------------------------------------------------------------------------------------------ texture
-#define TX_MAX_SIDE 4096
+#define TX_MAX_SIDE MSMD_TEXTURE_MAX_SIDE
 #define TX_MAX_LEVELS 13           // 1 + log2(4096)
 #define TX_ROWS 16                 // rows of a 64-pixel-wide strip per workgroup: a wave stores one row segment per step
 #define TX_THREADS 256

@@ -326,7 +326,7 @@ extern "C" int msmd_ordered_mean(const float* in, long n, float* out, msmd_strea
 
 // ------------------------------------------------------------------------------------------------ NT-Xent
 #define NTX_EPS 1e-12f            // F.normalize's eps
-#define NTX_CHUNK 256
+#define NTX_CHUNK MSMD_NT_XENT_CHUNK
 
 // row i of cat(a, b) -> fhat[i] = f / max(|f|, eps), norm[i] = |f|: one workgroup per row
 __global__ __launch_bounds__(256) void nt_xent_normalize_kernel(const float* __restrict__ a, const float* __restrict__ b,

@@ -4,16 +4,15 @@
 // arbitrary length in two stages, each a workgroup tile of TR_ROWS outputs x TR_CH channels that loops over the other index
 // with the twiddle e^{2 pi i r / P} read from a table at the integer residue r = (row * j) mod P.  Everything is double; the
 // residue is stepped in integers, so no phase is ever formed in floating point.
-#include "common.h"
+#include "savgol.h"
 
 constexpr int TR_WG = 256;
 constexpr int TR_ROWS = 16;            // bins (analysis) / output frames (synthesis) per workgroup
 constexpr int TR_CH = 16;              // channels per workgroup
 constexpr int TR_STAGE = 64;           // frames (analysis) / bins (synthesis) staged in LDS per pass
 constexpr int TR_MAX = 4096;           // frames of one clip, in or out
-constexpr int TR_MAX_WINDOW = 33;
 static_assert(TR_ROWS == MSMD_TRACK_ROWS && TR_CH == MSMD_TRACK_CH_TILE && TR_STAGE == MSMD_TRACK_STAGE &&
-              TR_MAX == MSMD_TRACK_MAX_FRAMES && TR_MAX_WINDOW == MSMD_HEADPOSE_MAX_WINDOW, "header and kernel disagree");
+              TR_MAX == MSMD_TRACK_MAX_FRAMES && 65535 * TR_CH == MSMD_TRACK_MAX_CHANNELS, "header and kernel disagree");
 static_assert(TR_ROWS * TR_CH == TR_WG && TR_STAGE % TR_ROWS == 0, "one thread per (row, channel) of the tile");
 
 struct Cplx { double re, im; };
@@ -55,7 +54,7 @@ __global__ __launch_bounds__(TR_WG) void track_analysis_kernel(const float* __re
                                                                Cplx* __restrict__ spec) {
   __shared__ Cplx s_tab[TR_MAX / 2 + 1];
   __shared__ double s_x[TR_STAGE * TR_CH];
-  __shared__ double s_coef[TR_MAX_WINDOW * TR_MAX_WINDOW];
+  __shared__ double s_coef[SAVGOL_TABLE];
   const Clip cl = clip_of(offs, n_clips, blockIdx.x);
   const int k0 = blockIdx.y * TR_ROWS;
   if (!cl.ok || k0 > cl.K || cl.Nx < window) return;
@@ -63,8 +62,7 @@ __global__ __launch_bounds__(TR_WG) void track_analysis_kernel(const float* __re
   const int c = blockIdx.z * TR_CH + lc, k = k0 + lr;
   const bool live_c = c < C;
   fill_twiddles(s_tab, Nx);
-  for (int i = tid; i < window * window; i += TR_WG) s_coef[i] = savgol[i];
-  const int h = window >> 1;
+  savgol_stage<TR_WG>(s_coef, savgol, window);
   const float* __restrict__ xc = x + cl.in0 * C + (live_c ? c : 0);
   double re = 0.0, im = 0.0;
   for (int n0 = 0; n0 < Nx; n0 += TR_STAGE) {
@@ -77,11 +75,8 @@ __global__ __launch_bounds__(TR_WG) void track_analysis_kernel(const float* __re
         if (window == 0) {
           v = (double)xc[(long)n * C];
         } else {
-          const double* __restrict__ row;
           int first;
-          if (n < h) { row = s_coef + window + n * window; first = 0; }
-          else if (n >= Nx - h) { row = s_coef + window + (h + n - (Nx - h)) * window; first = Nx - window; }
-          else { row = s_coef; first = n - h; }
+          const double* __restrict__ row = savgol_row(s_coef, window, n, Nx, first);
           for (int m = 0; m < window; ++m) v = fma(row[m], (double)xc[(long)(first + m) * C], v);
         }
       }
@@ -158,8 +153,8 @@ extern "C" long msmd_track_resample_ws_bytes(long total_in, int n_clips, int C) 
 
 extern "C" int msmd_track_resample(const float* x, const int* in_offsets, const int* out_offsets, int n_clips, int C,
                                    const double* savgol, int window, void* ws, float* y, msmd_stream_t stream) {
-  if (!x || !in_offsets || !out_offsets || !ws || !y || n_clips < 1 || C < 1 || C > 65535 * TR_CH) return 1;
-  if (window != 0 && (window < 3 || window > TR_MAX_WINDOW || !(window & 1) || !savgol)) return 1;
+  if (!x || !in_offsets || !out_offsets || !ws || !y || n_clips < 1 || C < 1 || C > MSMD_TRACK_MAX_CHANNELS) return 1;
+  if (window != 0 && !(savgol_window_ok(window) && savgol)) return 1;
   if (in_offsets[0] != 0 || out_offsets[0] != 0) return 1;
   int max_k = 0, max_m = 0;
   for (int i = 0; i < n_clips; ++i) {

@@ -16,7 +16,16 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 
-F32, BF16, F16, F16X2 = 0, 1, 2, 3
+_HEADER = _lib.parse_constants()   # the #define MSMD_<NAME> lines of include/msmd_hip.h: no constant of the C ABI is typed again here
+
+
+def _h(*names):
+    """The header's MSMD_<name> values: one int for one name, a tuple for several."""
+    vals = tuple(_HEADER["MSMD_" + n] for n in names)
+    return vals if len(vals) > 1 else vals[0]
+
+
+F32, BF16, F16, F16X2 = _h("F32", "BF16", "F16", "F16X2")
 SPLIT = "f16x2"   # dtype token of the parity-grade speed mode (MSMD_F16X2 split storage, include/msmd_hip.h)
 
 
@@ -128,8 +137,8 @@ def unsplit(s, cols=None):
     out = torch.empty(*s.shape[:-1], cols, device=t.device, dtype=torch.float32)
     _lib.check(_lib.load().msmd_unsplit_f16x2(_p(t), _p(out), rows, cols, C, cols, _stream()), "msmd_unsplit_f16x2")
     return out
-ACT_NONE, ACT_GELU, ACT_ELU = 0, 1, 2
-CONV0_SPLITS = 16
+ACT_NONE, ACT_GELU, ACT_ELU = _h("ACT_NONE", "ACT_GELU", "ACT_ELU")
+CONV0_SPLITS = _h("CONV0_SPLITS")
 
 # Optional per-launch timing of the dominant kernel (bench.py roofline leg): when a list is installed
 # here, every msmd_gemm launch is bracketed by HIP events recorded on the launch stream.
@@ -177,12 +186,12 @@ _TUNED = {}
 # Per-call GEMM knobs (include/msmd_hip.h: MSMD_GEMM_VARIANT / _WRITE_THROUGH / _PAIRED_STORES).  The C library has no
 # global state; these module-level defaults are what `gemm()` passes when the caller gives none (`gemm_defaults`
 # scopes a change, e.g. while a hipGraph is captured -- the choice is then baked into that graph).
-GEMM_WRITE_THROUGH, GEMM_PAIRED_STORES, GEMM_STAGGER = 1 << 16, 1 << 17, 1 << 18
-GEMM_ONE_TILE_PER_WORKGROUP = 1 << 19      # opt out of the persistent form of multi-round launches (A/B; same bits)
-GEMM_NO_256_TILE = 1 << 20                 # opt out of the 256 x 256 8-phase kernel where the library would pick it (A/B; plain outputs same bits)
-GEMM_W_BELOW_32 = 1 << 21                  # split operands: |W| < 32 everywhere (set by gemm() from Split.below_32)
-GEMM_NO_160_ROW_TILE = 1 << 22             # gemm_ln: opt out of the 160 x 128 member of variant 17 (A/B; same bits)
-GEMM_FORCE_160_ROW_TILE = 1 << 23          # gemm_ln: the 160 x 128 member wherever its kernel takes the call (tests, scans; same bits)
+GEMM_WRITE_THROUGH, GEMM_PAIRED_STORES, GEMM_STAGGER = _h("GEMM_WRITE_THROUGH", "GEMM_PAIRED_STORES", "GEMM_STAGGER")
+GEMM_ONE_TILE_PER_WORKGROUP = _h("GEMM_ONE_TILE_PER_WORKGROUP")      # opt out of the persistent form of multi-round launches (A/B; same bits)
+GEMM_NO_256_TILE = _h("GEMM_NO_256_TILE")     # opt out of the 256 x 256 8-phase kernel where the library would pick it (A/B; plain outputs same bits)
+GEMM_W_BELOW_32 = _h("GEMM_W_BELOW_32")       # split operands: |W| < 32 everywhere (set by gemm() from Split.below_32)
+GEMM_NO_160_ROW_TILE = _h("GEMM_NO_160_ROW_TILE")           # gemm_ln: opt out of the 160 x 128 member of variant 17 (A/B; same bits)
+GEMM_FORCE_160_ROW_TILE = _h("GEMM_FORCE_160_ROW_TILE")     # gemm_ln: the 160 x 128 member wherever its kernel takes the call (tests, scans; same bits)
 GEMM_LN_FLAGS = 0              # extra `act` bits msmd_gemm_ln calls carry (A/B hook: GEMM_ONE_TILE_PER_WORKGROUP)
 GEMM_LN_ROUTER = None          # optional (M, N, K) -> 15 | 17 | 18 | None: tile hint for msmd_gemm_ln's big-tile family
 GEMM_LN_ALL_IN_ONE = False     # A/B hook (tools/ab_forward.py): msmd_gemm_ln on the one-kernel-with-every-epilogue form (variant 66)
@@ -1069,7 +1078,7 @@ class _LandmarksFn(torch.autograd.Function):
         return landmarks_bwd(g.float().contiguous(), *ctx.saved_tensors, ctx.V), None, None, None
 
 
-LANDMARKS_BWD_MAX_L = 1024   # msmd_landmarks_bwd keeps a frame's 3 L contributions in LDS (include/msmd_hip.h)
+LANDMARKS_BWD_MAX_L = _h("LANDMARKS_BWD_MAX_L")   # msmd_landmarks_bwd keeps a frame's 3 L contributions in LDS (include/msmd_hip.h)
 
 
 def landmarks(verts, faces_i32, lmk_faces_idx_i32, bary):
@@ -1380,35 +1389,48 @@ def unfold_t(xp, T, Kk):
 
 
 # ----------------------------------------------------------------------------- mesh renderer (csrc/render.hip)
-def _render_arg(name, t, dtype, shape=None, optional=False):
-    """The renderer's entry points index raw pointers from the stated sizes: contiguous device tensors of one dtype only."""
+def _arg(name, t, dtype, shape=None, sizes=None, optional=False):
+    """The entry points from here on index raw pointers from the stated sizes: t is a contiguous device tensor of one dtype whose
+    shape fits `shape` ("B V 3" or a tuple of such entries), TypeError otherwise.  An integer is exact; a name binds in `sizes` (a dict
+    the wrapper's calls share) where first seen and must agree afterwards, "n+" is at least 1; a tuple such as (3, 4) is a set."""
     if t is None and optional:
         return
     if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
         raise TypeError(f"{name} must be a contiguous {dtype} CUDA tensor")
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise TypeError(f"{name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
+    if shape is None:
+        return
+    entries = [e if isinstance(e, tuple) else str(e) for e in (shape.split() if isinstance(shape, str) else shape)]
+    known = {} if sizes is None else sizes
+    bound = dict(known)
+    ok = t.dim() == len(entries)
+    for e, n in zip(entries, t.shape):
+        if isinstance(e, tuple):
+            ok &= n in e
+        elif e.isdigit():
+            ok &= n == int(e)
+        else:
+            ok &= n == bound.setdefault(e.rstrip("+"), n) and n >= e.count("+")
+    if not ok:
+        want = (" | ".join(map(str, e)) if isinstance(e, tuple) else str(known.get(e.rstrip("+"), e.rstrip("+"))) for e in entries)
+        raise TypeError(f"{name} must have shape ({', '.join(want)}{',' * (len(entries) == 1)}), got {tuple(t.shape)}")
+    known.update(bound)
 
 
 def render_vertices(verts, faces_i32, csr_offsets, csr_faces, view, focal, height, width, t_center=None, rot=None):
     """-> (screen (B, V, 3) = (x_s, y_s, eye depth), normals (B, V, 3) eye-space unit vertex normals): msmd_render_vertices.
     verts (B, V, 3) fp32; faces (F, 3), csr_offsets (V + 1), csr_faces (3 F) int32 (utils/renderer.vertex_face_csr);
     view (3, 4) fp32 world -> eye; rot (B, 3) axis-angle about t_center (3), both or neither."""
-    _render_arg("verts", verts, torch.float32)
-    if verts.dim() != 3 or verts.shape[2] != 3:
-        raise TypeError(f"verts must have shape (B, V, 3), got {tuple(verts.shape)}")
-    B, V, _ = verts.shape
-    _render_arg("faces", faces_i32, torch.int32)
-    if faces_i32.dim() != 2 or faces_i32.shape[1] != 3:
-        raise TypeError(f"faces must have shape (F, 3), got {tuple(faces_i32.shape)}")
-    Fc = faces_i32.shape[0]
-    _render_arg("csr_offsets", csr_offsets, torch.int32, (V + 1,))
-    _render_arg("csr_faces", csr_faces, torch.int32, (3 * Fc,))
-    _render_arg("view", view, torch.float32, (3, 4))
+    d = {}
+    _arg("verts", verts, torch.float32, "B V 3", d)
+    _arg("faces", faces_i32, torch.int32, "F 3", d)
+    B, V, Fc = d["B"], d["V"], d["F"]
+    _arg("csr_offsets", csr_offsets, torch.int32, (V + 1,))
+    _arg("csr_faces", csr_faces, torch.int32, (3 * Fc,))
+    _arg("view", view, torch.float32, "3 4")
     if (rot is None) != (t_center is None):
         raise TypeError("rot and t_center are given together")
-    _render_arg("rot", rot, torch.float32, (B, 3), optional=True)
-    _render_arg("t_center", t_center, torch.float32, (3,), optional=True)
+    _arg("rot", rot, torch.float32, "B 3", d, optional=True)
+    _arg("t_center", t_center, torch.float32, "3", optional=True)
     lib = _lib.load()
     screen = torch.empty(B, V, 3, device=verts.device, dtype=torch.float32)
     normals = torch.empty(B, V, 3, device=verts.device, dtype=torch.float32)
@@ -1422,19 +1444,13 @@ def render_raster(screen, normals, faces_i32, shade, lights, height, width, near
     """-> (rgba (B, H, W, 4) uint8, depth (B, H, W) fp32, face_id (B, H, W) int32 or None): msmd_render_raster.
     screen / normals (B, V, 3) fp32 as render_vertices returns them; shade (6) = base rgb, ambient rgb; lights (L, 4) =
     eye-space unit direction towards the light, intensity; background = R | G << 8 | B << 16 | A << 24."""
-    _render_arg("screen", screen, torch.float32)
-    if screen.dim() != 3 or screen.shape[2] != 3:
-        raise TypeError(f"screen must have shape (B, V, 3), got {tuple(screen.shape)}")
-    B, V, _ = screen.shape
-    _render_arg("normals", normals, torch.float32, (B, V, 3))
-    _render_arg("faces", faces_i32, torch.int32)
-    if faces_i32.dim() != 2 or faces_i32.shape[1] != 3:
-        raise TypeError(f"faces must have shape (F, 3), got {tuple(faces_i32.shape)}")
-    _render_arg("shade", shade, torch.float32, (6,))
-    _render_arg("lights", lights, torch.float32)
-    if lights.dim() != 2 or lights.shape[1] != 4:
-        raise TypeError(f"lights must have shape (L, 4), got {tuple(lights.shape)}")
-    H, W = int(height), int(width)
+    d = {}
+    _arg("screen", screen, torch.float32, "B V 3", d)
+    _arg("normals", normals, torch.float32, "B V 3", d)
+    _arg("faces", faces_i32, torch.int32, "F 3", d)
+    _arg("shade", shade, torch.float32, "6")
+    _arg("lights", lights, torch.float32, "L 4", d)
+    B, V, H, W = d["B"], d["V"], int(height), int(width)
     lib = _lib.load()
     rgba = torch.empty(B, H, W, 4, device=screen.device, dtype=torch.uint8)
     depth = torch.empty(B, H, W, device=screen.device, dtype=torch.float32)
@@ -1445,15 +1461,13 @@ def render_raster(screen, normals, faces_i32, shade, lights, height, width, near
     return rgba, depth, face_id
 
 
-TEXTURE_MAX_SIDE = 4096         # TX_MAX_SIDE in csrc/render.hip
+TEXTURE_MAX_SIDE = _h("TEXTURE_MAX_SIDE")
 
 
 def texture_pyramid(img_u8):
     """(Ht, Wt, 3 | 4) uint8 image on the device (alpha ignored) -> its mip pyramid, (n_texels, 4) fp32 RGBA texels with the
     levels one after the other (level l + 1 is max(1, H_l >> 1) x max(1, W_l >> 1)): msmd_texture_mips."""
-    _render_arg("img", img_u8, torch.uint8)
-    if img_u8.dim() != 3 or img_u8.shape[2] not in (3, 4):
-        raise TypeError(f"img must have shape (Ht, Wt, 3) or (Ht, Wt, 4), got {tuple(img_u8.shape)}")
+    _arg("img", img_u8, torch.uint8, ("Ht", "Wt", (3, 4)))
     Ht, Wt, C = img_u8.shape
     lib = _lib.load()
     n = lib.msmd_texture_texels(Ht, Wt)
@@ -1471,34 +1485,23 @@ def render_shade_textured(screen, normals, faces_i32, vt, ft, pyramid, tex_heigh
     lights as render_raster takes them; vt (Nt, 2) fp32, ft (F, 3) int32 per-corner indices into vt; pyramid as
     texture_pyramid returns it for a tex_height x tex_width image.  -> uvl (B, H, W, 3) fp32 = (u, v, lambda) per pixel (zeros
     on the background) if want_uvl, else None."""
-    _render_arg("screen", screen, torch.float32)
-    if screen.dim() != 3 or screen.shape[2] != 3:
-        raise TypeError(f"screen must have shape (B, V, 3), got {tuple(screen.shape)}")
-    B, V, _ = screen.shape
-    _render_arg("normals", normals, torch.float32, (B, V, 3))
-    _render_arg("faces", faces_i32, torch.int32)
-    if faces_i32.dim() != 2 or faces_i32.shape[1] != 3:
-        raise TypeError(f"faces must have shape (F, 3), got {tuple(faces_i32.shape)}")
-    Fc = faces_i32.shape[0]
-    _render_arg("vt", vt, torch.float32)
-    if vt.dim() != 2 or vt.shape[1] != 2 or vt.shape[0] == 0:
-        raise TypeError(f"vt must have shape (Nt, 2), got {tuple(vt.shape)}")
-    _render_arg("ft", ft, torch.int32, (Fc, 3))
-    _render_arg("shade", shade, torch.float32, (6,))
-    _render_arg("lights", lights, torch.float32)
-    if lights.dim() != 2 or lights.shape[1] != 4:
-        raise TypeError(f"lights must have shape (L, 4), got {tuple(lights.shape)}")
-    _render_arg("face_id", face_id, torch.int32)
-    if face_id.dim() != 3 or face_id.shape[0] != B:
-        raise TypeError(f"face_id must have shape ({B}, H, W), got {tuple(face_id.shape)}")
-    H, W = face_id.shape[1:]
-    _render_arg("rgba", rgba, torch.uint8, (B, H, W, 4))
+    d = {}
+    _arg("screen", screen, torch.float32, "B V 3", d)
+    _arg("normals", normals, torch.float32, "B V 3", d)
+    _arg("faces", faces_i32, torch.int32, "F 3", d)
+    _arg("vt", vt, torch.float32, "Nt+ 2", d)
+    _arg("ft", ft, torch.int32, "F 3", d)
+    _arg("shade", shade, torch.float32, "6")
+    _arg("lights", lights, torch.float32, "L 4", d)
+    _arg("face_id", face_id, torch.int32, "B H W", d)
+    _arg("rgba", rgba, torch.uint8, "B H W 4", d)
+    B, V, Fc, H, W = (d[k] for k in "BVFHW")
     lib = _lib.load()
     Ht, Wt = int(tex_height), int(tex_width)
     n = lib.msmd_texture_texels(Ht, Wt)
     if n < 0:
         raise ValueError(f"a {Ht} x {Wt} texture is outside [1, {TEXTURE_MAX_SIDE}]")
-    _render_arg("pyramid", pyramid, torch.float32, (n, 4))
+    _arg("pyramid", pyramid, torch.float32, (n, 4))
     uvl = torch.empty(B, H, W, 3, device=screen.device, dtype=torch.float32) if want_uvl else None
     _lib.check(lib.msmd_render_shade_textured(_p(screen), _p(normals), _p(faces_i32), _p(vt), _p(ft), _p(pyramid), Ht, Wt,
                                               _p(shade), _p(lights), lights.shape[0], _p(face_id), _p(rgba), _p(uvl), B, V, Fc,
@@ -1507,15 +1510,13 @@ def render_shade_textured(screen, normals, faces_i32, vt, ft, pyramid, tex_heigh
 
 
 # ----------------------------------------------------------------------------- FLAMETex albedo model (csrc/flametex.hip)
-TEX_PLANAR_F32, TEX_IMAGE_U8 = 0, 1     # MSMD_TEX_PLANAR_F32 / MSMD_TEX_IMAGE_U8
-FLAMETEX_MAX_SIDE, FLAMETEX_MAX_TEX = 4096, 256
+TEX_PLANAR_F32, TEX_IMAGE_U8 = _h("TEX_PLANAR_F32", "TEX_IMAGE_U8")
+FLAMETEX_MAX_SIDE, FLAMETEX_MAX_TEX = _h("FLAMETEX_MAX_SIDE", "FLAMETEX_MAX_TEX")
 
 
 def _flametex_sizes(basis, src_hw, dst_hw):
     (Hs, Ws), (Hd, Wd) = (int(v) for v in src_hw), (int(v) for v in dst_hw)
-    _render_arg("basis", basis, torch.float32)
-    if basis.dim() != 2:
-        raise TypeError(f"basis must have shape (Hs Ws 3, n_tex), got {tuple(basis.shape)}")
+    _arg("basis", basis, torch.float32, "rows n_tex")
     n_tex = basis.shape[1]
     if not all(1 <= v <= FLAMETEX_MAX_SIDE for v in (Hs, Ws, Hd, Wd)) or not 1 <= n_tex <= FLAMETEX_MAX_TEX:
         raise ValueError(f"flametex: sides {(Hs, Ws, Hd, Wd)} outside [1, {FLAMETEX_MAX_SIDE}] or n_tex = {n_tex} outside "
@@ -1530,8 +1531,8 @@ def flametex_forward(mean, basis, code, n_copies=1, src_hw=(512, 512), dst_hw=(2
     the rows the resize keeps: msmd_flametex_forward.  -> (n_copies, 3, Hd, Wd) fp32 (TEX_PLANAR_F32) or (Hd, Wd, 3) uint8 RGB
     (TEX_IMAGE_U8, n_copies = 1).  All operands contiguous fp32 on the device."""
     Hs, Ws, Hd, Wd, n_tex = _flametex_sizes(basis, src_hw, dst_hw)
-    _render_arg("mean", mean, torch.float32, (Hs * Ws * 3,))
-    _render_arg("code", code, torch.float32, (n_tex,))
+    _arg("mean", mean, torch.float32, (Hs * Ws * 3,))
+    _arg("code", code, torch.float32, (n_tex,))
     n_copies = int(n_copies)
     if out_format == TEX_IMAGE_U8:
         if n_copies != 1:
@@ -1552,14 +1553,11 @@ def flametex_backward(basis, grad_out, src_hw=(512, 512), out=None):
     """grad_out (n_copies, 3, Hd, Wd) fp32 -> the gradient of flametex_forward's code, (n_tex,) fp32, summed over the copies:
     msmd_flametex_backward (per-workgroup partial sums in a workspace, then one ordered reduction; the same bits every run).
     out: a contiguous (n_tex,) fp32 tensor to write instead of a new one."""
-    _render_arg("grad_out", grad_out, torch.float32)
-    if grad_out.dim() != 4 or grad_out.shape[1] != 3:
-        raise TypeError(f"grad_out must have shape (n_copies, 3, Hd, Wd), got {tuple(grad_out.shape)}")
+    _arg("grad_out", grad_out, torch.float32, "n_copies 3 Hd Wd")
     Hs, Ws, Hd, Wd, n_tex = _flametex_sizes(basis, src_hw, grad_out.shape[2:])
     lib = _lib.load()
     workspace = torch.empty(lib.msmd_flametex_backward_workspace(Hd, Wd, n_tex), device=basis.device, dtype=torch.float32)
-    if out is not None:
-        _render_arg("out", out, torch.float32, (n_tex,))
+    _arg("out", out, torch.float32, (n_tex,), optional=True)
     grad_code = out if out is not None else torch.empty(n_tex, device=basis.device, dtype=torch.float32)
     _lib.check(lib.msmd_flametex_backward(_p(basis), _p(grad_out), grad_out.shape[0], _p(grad_code), _p(workspace), Hs, Ws, Hd,
                                           Wd, n_tex, _stream()), "msmd_flametex_backward")
@@ -1567,8 +1565,7 @@ def flametex_backward(basis, grad_out, src_hw=(512, 512), out=None):
 
 
 # ----------------------------------------------------------------------------- JPEG encoder (csrc/jpeg.hip)
-JPEG_RESTART_INTERVAL = 32      # MSMD_JPEG_RESTART_INTERVAL
-JPEG_MAX_SIDE = 16384           # MSMD_JPEG_MAX_SIDE
+JPEG_RESTART_INTERVAL, JPEG_MAX_SIDE = _h("JPEG_RESTART_INTERVAL", "JPEG_MAX_SIDE")
 # ITU-T T.81 Annex K.1 quantisation tables (natural order) and Annex K.3 typical Huffman tables (BITS, HUFFVAL): the header's
 # copy; the kernels carry their own in csrc/jpeg.hip and tests/test_video_gpu.py holds the two together through the decoder.
 JPEG_BASE_LUMA = (
@@ -1699,14 +1696,13 @@ def jpeg_encode(frames, quality=90):
 
 
 # ----------------------------------------------------------------------------- audio front end (csrc/audio_io.hip)
-AUDIO_RUN = 256         # MSMD_AUDIO_RUN: outputs per workgroup of msmd_audio_resample = outputs per partial-sum pair
-AUDIO_MAX_CLIPS = 65535  # clips per call of the audio entry points
+AUDIO_RUN, AUDIO_MAX_CLIPS = _h("AUDIO_RUN", "AUDIO_MAX_CLIPS")     # outputs per partial-sum pair; clips per call
 
 
 def _audio_desc(desc, desc_host, pcm_elems=None):
     """desc (n, 5) int64 on the device and the host array it was copied from.  The kernels index raw pointers from these
     numbers, so the host copy is checked here: every clip inside the PCM buffer, output ranges disjoint and in order."""
-    _render_arg("desc", desc, torch.int64)
+    _arg("desc", desc, torch.int64)
     h = desc_host.numpy() if torch.is_tensor(desc_host) else desc_host
     if h.ndim != 2 or h.shape[1] != 5 or h.shape[0] == 0 or str(h.dtype) != "int64" or tuple(desc.shape) != tuple(h.shape):
         raise TypeError("desc_host must be the (n_clips, 5) int64 array desc was copied from")
@@ -1741,9 +1737,7 @@ def resample_audio(pcm, desc, desc_host, bank, L, M):
             raise ValueError("resample_audio: no filter bank is the same-rate bypass, L = M = 1")
         taps = 0
     else:
-        _render_arg("bank", bank, torch.float32)
-        if bank.dim() != 2 or bank.shape[1] != L:
-            raise TypeError(f"bank must have shape (taps, {L}), got {tuple(bank.shape)}")
+        _arg("bank", bank, torch.float32, ("taps", L))
         taps = bank.shape[0]
     lib = _lib.load()
     max_out = int(h[:, 4].max())
@@ -1761,10 +1755,10 @@ def resample_audio(pcm, desc, desc_host, bank, L, M):
 def znorm_audio(out, desc, desc_host, partials):
     """In place (y - mean) / (std + 1e-5) per clip, population std: msmd_audio_znorm on what resample_audio returned (one
     wave per clip adds its partial sums in run order, then the samples are normalised)."""
-    _render_arg("out", out, torch.float32)
+    _arg("out", out, torch.float32)
     h, total = _audio_desc(desc, desc_host)
     max_out = int(h[:, 4].max())
-    _render_arg("partials", partials, torch.float64, (h.shape[0], (max_out + AUDIO_RUN - 1) // AUDIO_RUN, 2))
+    _arg("partials", partials, torch.float64, (h.shape[0], (max_out + AUDIO_RUN - 1) // AUDIO_RUN, 2))
     if out.dim() != 1 or out.numel() < total:
         raise TypeError(f"out must be 1-D with at least {total} samples")
     stats = torch.empty(h.shape[0], 2, device=out.device, dtype=torch.float64)
@@ -1774,28 +1768,52 @@ def znorm_audio(out, desc, desc_host, partials):
 
 
 # ----------------------------------------------------------------------------- head pose from landmarks (csrc/headpose.hip)
-HEADPOSE_MAX_WINDOW = 33   # MSMD_HEADPOSE_MAX_WINDOW
-HEADPOSE_CHUNK = 256       # MSMD_HEADPOSE_CHUNK: frames per step of the smoothing kernel's sign scan
-HEADPOSE_MAX_STATIC = 64   # one static landmark per lane of a wave
+HEADPOSE_MAX_WINDOW, HEADPOSE_CHUNK, HEADPOSE_MAX_STATIC = _h("HEADPOSE_MAX_WINDOW", "HEADPOSE_CHUNK", "HEADPOSE_MAX_STATIC")
+
+
+def _clip_offsets(name, offsets, total, window=0, max_frames=None):
+    """The HOST offsets of a ragged batch of clips laid end to end -> a list of ints: ascending from 0 to `total`, every clip
+    of max(1, window) .. max_frames frames (None: no cap, and the window rule alone speaks); ValueError otherwise."""
+    off = [int(o) for o in offsets]
+    if len(off) < 2 or off[0] != 0 or off[-1] != total:
+        raise ValueError(f"{name} must run from 0 to {total}, got {off[:1]} .. {off[-1:]}")
+    for a, b in zip(off[:-1], off[1:]):
+        if max_frames is not None and not 1 <= b - a <= max_frames:
+            raise ValueError(f"{name}: a clip must have 1 .. {max_frames} frames, got {b - a}")
+        if b - a < max(window, 1):
+            raise ValueError(f"a clip of {b - a} frames is shorter than the window of {window}")
+    return off
+
+
+def _savgol_window(window, table=None, allow_zero=False, name="window"):
+    """-> int(window): odd and in [3, HEADPOSE_MAX_WINDOW], or 0 (no filter, and then no table) if allow_zero; ValueError
+    otherwise.  table = (its name, tensor): the (window * window,) float64 device tensor of utils/head_pose.savgol_table (TypeError)."""
+    window = int(window)
+    if window == 0 and allow_zero:
+        if table is not None and table[1] is not None:
+            raise ValueError(f"{table[0]} given with {name} = 0")
+    elif window < 3 or window > HEADPOSE_MAX_WINDOW or window % 2 == 0:
+        raise ValueError(f"{name} must be {'0 or ' if allow_zero else ''}odd and in [3, {HEADPOSE_MAX_WINDOW}], got {window}")
+    elif table is not None:
+        _arg(*table, torch.float64, (window * window,))
+    return window
 
 
 def headpose_fit(landmarks, plan_a, plan_b, plan_w, neutral, static_idx, want_aligned=True):
     """-> (R (n, 3, 3), c (n), t (n, 3), aligned (n, P, 3) or None) fp32: msmd_headpose_fit, the per-frame similarity fit of
     the static landmarks onto `neutral` and the fitted transform applied to every landmark.  landmarks (n, P, 3) fp32, the
     clips of a batch end to end; plan_a / plan_b (n) int32 and plan_w (n) fp32: frame f is (1 - w) L[a] + w L[b]
-    (utils/head_pose.gap_plan); neutral (P, 3) fp32, read at static_idx (S) int32 in [0, P), 3 <= S <= 64.  The index
+    (utils/head_pose.gap_plan); neutral (P, 3) fp32, read at static_idx (S) int32 in [0, P), 3 <= S <= HEADPOSE_MAX_STATIC.  The index
     arrays live on the device and are not read back here: the kernel clamps them into range."""
     _need_cuda(landmarks, plan_a, plan_b, plan_w, neutral, static_idx)
-    _render_arg("landmarks", landmarks, torch.float32)
-    if landmarks.dim() != 3 or landmarks.shape[2] != 3 or landmarks.shape[0] == 0:
-        raise TypeError(f"landmarks must have shape (n_frames, P, 3), got {tuple(landmarks.shape)}")
-    n, P, _ = landmarks.shape
-    _render_arg("plan_a", plan_a, torch.int32, (n,))
-    _render_arg("plan_b", plan_b, torch.int32, (n,))
-    _render_arg("plan_w", plan_w, torch.float32, (n,))
-    _render_arg("neutral", neutral, torch.float32, (P, 3))
-    _render_arg("static_idx", static_idx, torch.int32)
-    S = static_idx.numel()
+    d = {}
+    _arg("landmarks", landmarks, torch.float32, "n+ P 3", d)
+    _arg("plan_a", plan_a, torch.int32, "n", d)
+    _arg("plan_b", plan_b, torch.int32, "n", d)
+    _arg("plan_w", plan_w, torch.float32, "n", d)
+    _arg("neutral", neutral, torch.float32, "P 3", d)
+    _arg("static_idx", static_idx, torch.int32)
+    n, P, S = d["n"], d["P"], static_idx.numel()
     if static_idx.dim() != 1 or not 3 <= S <= min(HEADPOSE_MAX_STATIC, P):
         raise ValueError(f"static_idx must hold 3 .. min({HEADPOSE_MAX_STATIC}, P) indices, got shape {tuple(static_idx.shape)}")
     dev = landmarks.device
@@ -1814,19 +1832,9 @@ def headpose_smooth(R, clip_offsets, table, window, want_matrix=False):
     HOST (checked here: ascending from 0 to n, every clip at least `window` frames; copied to the device as int64);
     table (window * window) float64 on the device (utils/head_pose.savgol_table)."""
     _need_cuda(R, table)
-    _render_arg("R", R, torch.float32)
-    if R.dim() != 3 or tuple(R.shape[1:]) != (3, 3) or R.shape[0] == 0:
-        raise TypeError(f"R must have shape (n_frames, 3, 3), got {tuple(R.shape)}")
-    window = int(window)
-    if window < 3 or window > HEADPOSE_MAX_WINDOW or window % 2 == 0:
-        raise ValueError(f"window must be odd and in [3, {HEADPOSE_MAX_WINDOW}], got {window}")
-    _render_arg("table", table, torch.float64, (window * window,))
-    off = [int(o) for o in clip_offsets]
-    if len(off) < 2 or off[0] != 0 or off[-1] != R.shape[0]:
-        raise ValueError(f"clip_offsets must run from 0 to {R.shape[0]}, got {off[:1]} .. {off[-1:]}")
-    for a, b in zip(off[:-1], off[1:]):
-        if b - a < window:
-            raise ValueError(f"a clip of {b - a} frames is shorter than the window of {window}")
+    _arg("R", R, torch.float32, "n+ 3 3")
+    window = _savgol_window(window, ("table", table))
+    off = _clip_offsets("clip_offsets", clip_offsets, R.shape[0], window)
     off_dev = torch.tensor(off, dtype=torch.int64).to(R.device)
     ypr = torch.empty(R.shape[0], 3, device=R.device, dtype=torch.float32)
     R_mod = torch.empty_like(R) if want_matrix else None
@@ -1836,22 +1844,8 @@ def headpose_smooth(R, clip_offsets, table, window, want_matrix=False):
 
 
 # ----------------------------------------------------------------------------- track resampling (csrc/track_resample.hip)
-TRACK_MAX_FRAMES = 4096    # MSMD_TRACK_MAX_FRAMES: frames of one clip, in or out
-TRACK_ROWS = 16            # MSMD_TRACK_ROWS: bins / output frames per workgroup
-TRACK_CH_TILE = 16         # MSMD_TRACK_CH_TILE: channels per workgroup
-TRACK_STAGE = 64           # MSMD_TRACK_STAGE: frames / bins staged in LDS per pass
-
-
-def _track_offsets(name, offsets, total, window=0):
-    off = [int(o) for o in offsets]
-    if len(off) < 2 or off[0] != 0 or off[-1] != total:
-        raise ValueError(f"{name} must run from 0 to {total}, got {off[:1]} .. {off[-1:]}")
-    for a, b in zip(off[:-1], off[1:]):
-        if not 1 <= b - a <= TRACK_MAX_FRAMES:
-            raise ValueError(f"{name}: a clip must have 1 .. {TRACK_MAX_FRAMES} frames, got {b - a}")
-        if b - a < window:
-            raise ValueError(f"a clip of {b - a} frames is shorter than the window of {window}")
-    return off
+TRACK_MAX_FRAMES, TRACK_MAX_CHANNELS, TRACK_ROWS, TRACK_CH_TILE, TRACK_STAGE = _h(
+    "TRACK_MAX_FRAMES", "TRACK_MAX_CHANNELS", "TRACK_ROWS", "TRACK_CH_TILE", "TRACK_STAGE")    # limits and the kernels' tile
 
 
 def track_resample(x, in_offsets, out_offsets, savgol_table=None, window=0):
@@ -1861,23 +1855,15 @@ def track_resample(x, in_offsets, out_offsets, savgol_table=None, window=0):
     window != 0: the track is read through the Savitzky-Golay filter of `savgol_table` (window * window) float64 on the
     device (utils/head_pose.savgol_table), window odd in [3, HEADPOSE_MAX_WINDOW], every clip at least `window` frames."""
     _need_cuda(x, savgol_table)
-    _render_arg("x", x, torch.float32)
-    if x.dim() != 2 or x.shape[0] == 0 or x.shape[1] == 0:
-        raise TypeError(f"x must have shape (n_frames, C) and not be empty, got {tuple(x.shape)}")
-    window = int(window)
-    if window != 0:
-        if window < 3 or window > HEADPOSE_MAX_WINDOW or window % 2 == 0:
-            raise ValueError(f"window must be 0 or odd and in [3, {HEADPOSE_MAX_WINDOW}], got {window}")
-        _render_arg("savgol_table", savgol_table, torch.float64, (window * window,))
-    elif savgol_table is not None:
-        raise ValueError("savgol_table given with window = 0")
+    _arg("x", x, torch.float32, "n+ C+")
+    window = _savgol_window(window, ("savgol_table", savgol_table), allow_zero=True)
     n, C = x.shape
-    if C > 65535 * TRACK_CH_TILE:
-        raise ValueError(f"x has {C} channels; the kernel takes up to {65535 * TRACK_CH_TILE}")
-    off_in = _track_offsets("in_offsets", in_offsets, n, window)
+    if C > TRACK_MAX_CHANNELS:
+        raise ValueError(f"x has {C} channels; the kernel takes up to {TRACK_MAX_CHANNELS}")
+    off_in = _clip_offsets("in_offsets", in_offsets, n, window, TRACK_MAX_FRAMES)
     if len(out_offsets) != len(off_in):
         raise ValueError(f"{len(off_in) - 1} input clips but {len(out_offsets) - 1} output clips")
-    off_out = _track_offsets("out_offsets", out_offsets, int(out_offsets[-1]))
+    off_out = _clip_offsets("out_offsets", out_offsets, int(out_offsets[-1]), 0, TRACK_MAX_FRAMES)
     n_clips = len(off_in) - 1
     lib = _lib.load()
     host_in, host_out = torch.tensor(off_in, dtype=torch.int32), torch.tensor(off_out, dtype=torch.int32)
@@ -1889,10 +1875,8 @@ def track_resample(x, in_offsets, out_offsets, savgol_table=None, window=0):
 
 
 # ----------------------------------------------------------------------------- style losses (csrc/style_loss.hip)
-STYLE_ROWS = 16      # MSMD_STYLE_ROWS: rows of X per workgroup
-STYLE_KTILE = 64     # MSMD_STYLE_KTILE: style frames per LDS tile
-STYLE_FCHUNK = 64    # MSMD_STYLE_FCHUNK: features per pass over a tile
-NT_XENT_CHUNK = 256  # rows j per step of the NT-Xent backward's coefficient table
+STYLE_ROWS, STYLE_KTILE, STYLE_FCHUNK = _h("STYLE_ROWS", "STYLE_KTILE", "STYLE_FCHUNK")    # the kernels' tile (include/msmd_hip.h)
+NT_XENT_CHUNK = _h("NT_XENT_CHUNK")  # rows j per step of the NT-Xent backward's coefficient table
 
 
 def _style_shapes(X, S, lambda_softmin):
@@ -1917,8 +1901,8 @@ def style_adherence_forward(X, S, lambda_softmin=10.0, soft=True):
     reads."""
     B, T, K, F, lam = _style_shapes(X, S, lambda_softmin)
     _need_cuda(X, S)
-    _render_arg("X", X, torch.float32)
-    _render_arg("S", S, torch.float32)
+    _arg("X", X, torch.float32)
+    _arg("S", S, torch.float32)
     L = torch.empty(B, T, device=X.device, dtype=torch.float32)
     stat = torch.empty((B, T, 2) if soft else (B, T), device=X.device, dtype=torch.float32 if soft else torch.int32)
     _lib.check(_lib.load().msmd_style_adherence_forward(_p(X), _p(S), _p(L), _p(stat), B, T, K, F, lam, int(bool(soft)),
@@ -1934,11 +1918,11 @@ def style_adherence_backward(X, S, L, stat, g, lambda_softmin=10.0, soft=True, n
         return None, None
     B, T, K, F, lam = _style_shapes(X, S, lambda_softmin)
     _need_cuda(X, S, L, stat, g)
-    _render_arg("X", X, torch.float32)
-    _render_arg("S", S, torch.float32)
-    _render_arg("L", L, torch.float32, (B, T))
-    _render_arg("stat", stat, torch.float32 if soft else torch.int32, (B, T, 2) if soft else (B, T))
-    _render_arg("g", g, torch.float32)
+    _arg("X", X, torch.float32)
+    _arg("S", S, torch.float32)
+    _arg("L", L, torch.float32, (B, T))
+    _arg("stat", stat, torch.float32 if soft else torch.int32, (B, T, 2) if soft else (B, T))
+    _arg("g", g, torch.float32)
     if g.numel() != 1 and tuple(g.shape) != (B, T):
         raise TypeError(f"g must have one element or shape {(B, T)}, got {tuple(g.shape)}")
     dX = torch.empty_like(X) if need_dX else None
@@ -1952,7 +1936,7 @@ def style_adherence_backward(X, S, L, stat, g, lambda_softmin=10.0, soft=True, n
 def ordered_mean(x):
     """0-dim fp32 mean of a contiguous fp32 tensor, summed in an order that depends on its size alone: msmd_ordered_mean."""
     _need_cuda(x)
-    _render_arg("x", x, torch.float32)
+    _arg("x", x, torch.float32)
     if x.numel() < 1:
         raise ValueError("ordered_mean of an empty tensor")
     out = torch.empty((), device=x.device, dtype=torch.float32)
@@ -1976,8 +1960,8 @@ def nt_xent_forward(a, b, temperature):
     its row losses.  a, b (B, D) contiguous fp32; the last tuple is what nt_xent_backward reads."""
     B, D, tau = _nt_xent_shapes(a, b, temperature)
     _need_cuda(a, b)
-    _render_arg("feature_a", a, torch.float32)
-    _render_arg("feature_b", b, torch.float32)
+    _arg("feature_a", a, torch.float32)
+    _arg("feature_b", b, torch.float32)
     fhat = torch.empty(2 * B, D, device=a.device, dtype=torch.float32)
     norm, row_loss = (torch.empty(2 * B, device=a.device, dtype=torch.float32) for _ in range(2))
     lse = torch.empty(2 * B, 2, device=a.device, dtype=torch.float32)
@@ -1991,11 +1975,11 @@ def nt_xent_backward(saved, upstream, temperature):
     (fhat, norm, lse); upstream: the loss's gradient, one fp32 element on the device."""
     fhat, norm, lse = saved
     _need_cuda(fhat, norm, lse, upstream)
-    _render_arg("fhat", fhat, torch.float32)
+    _arg("fhat", fhat, torch.float32, "N D")
     N, D = fhat.shape
-    _render_arg("norm", norm, torch.float32, (N,))
-    _render_arg("lse", lse, torch.float32, (N, 2))
-    _render_arg("upstream", upstream, torch.float32)
+    _arg("norm", norm, torch.float32, (N,))
+    _arg("lse", lse, torch.float32, (N, 2))
+    _arg("upstream", upstream, torch.float32)
     tau = float(temperature)
     if upstream.numel() != 1 or N % 2 or not 0.0 < tau < float("inf"):
         raise ValueError("nt_xent_backward: upstream has one element, fhat an even number of rows, temperature > 0")

@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from .. import ops
+from .common import clip_list, cut_clips, flatten_clips
 from .head_pose import savgol_table
 
 KEY_FILES = ("keys.txt", "keys_train.txt", "keys_valid.txt", "keys_test.txt")
@@ -40,29 +41,16 @@ def resample_track(x, n_out, smooth=None):
     (one C, any F in 1 .. ops.TRACK_MAX_FRAMES) resampled in ONE call; n_out: an int, or a list of ints.  smooth =
     (window, polyorder): the track is read through scipy's savgol_filter(x, window, polyorder, axis=0) first.
     -> a tensor (n_out, C), or a list of them for a list."""
-    single = torch.is_tensor(x)
-    clips = [x] if single else list(x)
+    clips, single = clip_list(x)
     n_outs = [n_out] * len(clips) if isinstance(n_out, (int, np.integer)) else [int(n) for n in n_out]
-    if not clips:
-        raise ValueError("no clip given")
     if len(n_outs) != len(clips):
         raise ValueError(f"{len(clips)} clips but {len(n_outs)} output lengths")
     ops._need_cuda(*clips)
-    C = clips[0].shape[1] if clips[0].dim() == 2 else -1
-    in_off, out_off = [0], [0]
-    for t, n in zip(clips, n_outs):
-        if t.dim() != 2 or t.shape[1] != C:
-            raise TypeError(f"every clip must have shape (F, {C}), got {tuple(t.shape)}")
-        in_off.append(in_off[-1] + t.shape[0])
-        out_off.append(out_off[-1] + int(n))
-    table, window = None, 0
-    if smooth is not None:
-        window = int(smooth[0])
-        table = torch.from_numpy(savgol_table(window, smooth[1])).to(clips[0].device)
-    flat = (clips[0] if len(clips) == 1 else torch.cat(clips, 0)).float().contiguous()
-    y = ops.track_resample(flat, in_off, out_off, table, window)
-    out = [y[a:b] for a, b in zip(out_off[:-1], out_off[1:])]
-    return out[0] if single else out
+    flat, in_off, _ = flatten_clips(clips, (None,))
+    out_off = [0] + np.cumsum(n_outs).tolist()
+    window = 0 if smooth is None else int(smooth[0])
+    table = None if smooth is None else torch.from_numpy(savgol_table(window, smooth[1])).to(flat.device)
+    return cut_clips(ops.track_resample(flat, in_off, out_off, table, window), out_off, single)
 
 
 def _track(a, width, name, device):

@@ -211,7 +211,7 @@ def load_clips(sources, device="cuda", normalize=True, rates=None):
         groups.setdefault((rate, pcm.dtype == np.int16), []).append(i)
     result = [None] * len(clips)
     pieces = [(key, members[a:a + ops.AUDIO_MAX_CLIPS]) for key, members in groups.items()
-              for a in range(0, len(members), ops.AUDIO_MAX_CLIPS)]           # an entry point takes 65 535 clips per call
+              for a in range(0, len(members), ops.AUDIO_MAX_CLIPS)]           # an entry point takes that many clips per call
     for (rate, is_int16), members in pieces:
         fb = filter_bank(rate)
         width = 2 if is_int16 else 4

@@ -34,6 +34,36 @@ class NullableArgs:
         return rule(self.__dict__) if rule is not None else None
 
 
+# ----------------------------------------------------------------------------- ragged batches of clips (host only)
+def clip_list(clips):
+    """One tensor or a list of tensors -> (the list, whether a bare tensor came in); ValueError for no clip."""
+    single = torch.is_tensor(clips)
+    clips = [clips] if single else list(clips)
+    if not clips:
+        raise ValueError("no clip given")
+    return clips, single
+
+
+def flatten_clips(clips, trailing):
+    """One tensor (F, ...) or a list of them -> (flat, offsets, single): the clips end to end as one contiguous fp32 tensor, the
+    (n_clips + 1) host offsets, and `clip_list`'s flag (`cut_clips` undoes it).  trailing: the shape behind F, None where every
+    clip must agree with the first, e.g. (None, 3).  TypeError for another shape.  Nothing is launched."""
+    clips, single = clip_list(clips)
+    first = tuple(clips[0].shape[1:]) if clips[0].dim() == 1 + len(trailing) else (-1,) * len(trailing)
+    want = tuple(f if t is None else t for f, t in zip(first, trailing))
+    offsets = [0]
+    for c in clips:
+        if c.dim() == 0 or tuple(c.shape[1:]) != want:
+            raise TypeError(f"every clip must have shape (F, {', '.join(map(str, want))}), got {tuple(c.shape)}")
+        offsets.append(offsets[-1] + c.shape[0])
+    return (clips[0] if len(clips) == 1 else torch.cat(clips, 0)).float().contiguous(), offsets, single
+
+
+def cut_clips(x, offsets, single=False):
+    """The clips [offsets[k], offsets[k + 1]) of x as a list of views, or the first one alone if `single`."""
+    return x[:offsets[1]] if single else [x[a:b] for a, b in zip(offsets[:-1], offsets[1:])]
+
+
 # ----------------------------------------------------------------------------- style losses (csrc/style_loss.hip, DESIGN.md 5.19)
 def _check_style_operands(X_pred, S, lambda_softmin):
     """ValueError for what has no answer, before the device or the library is touched."""

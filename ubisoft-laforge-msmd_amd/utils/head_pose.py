@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from .. import ops
+from .common import clip_list, cut_clips, flatten_clips
 
 
 def gap_plan(valid):
@@ -57,9 +58,7 @@ def savgol_table(window, polyorder):
     From the definition: A the Vandermonde matrix of the window's positions (centred, scaled to [-1, 1]), A = Q R, and
     H = Q Q^T takes the samples to their least-squares polynomial at every position.
     ValueError for an even window, a window outside [3, 33], or polyorder >= window."""
-    window, polyorder = int(window), int(polyorder)
-    if window % 2 == 0 or window < 3 or window > ops.HEADPOSE_MAX_WINDOW:
-        raise ValueError(f"window_length must be odd and in [3, {ops.HEADPOSE_MAX_WINDOW}], got {window}")
+    window, polyorder = ops._savgol_window(window, name="window_length"), int(polyorder)
     if polyorder >= window or polyorder < 0:
         raise ValueError(f"polyorder must be in [0, window_length), got {polyorder} for a window of {window}")
     h = window // 2
@@ -75,7 +74,7 @@ def head_pose_from_landmarks(landmarks, neutral, static_idx, valid=None, window_
 
     landmarks: one (F, P, 3) fp32 device tensor, or a list of them (clips of different lengths, one P): they are
     concatenated once and each kernel is launched once for the whole list; a list comes back as a list.
-    neutral (N, 3): the canonical face; static_idx (S), 3 <= S <= 64, each below min(N, P): the rigid landmarks the fit uses.
+    neutral (N, 3): the canonical face; static_idx (S), 3 <= S <= ops.HEADPOSE_MAX_STATIC, each below min(N, P): the rigid landmarks the fit uses.
     valid: per clip a bool array (F), False where the tracker found no face (None: every frame is valid).  Missing frames are
     filled as `gap_plan` says; what the landmark array holds at those frames is never read.
     The reference also lets a frame whose landmarks are all zero hold its predecessor; after its own gap filling no such
@@ -87,31 +86,26 @@ def head_pose_from_landmarks(landmarks, neutral, static_idx, valid=None, window_
 
     Outside the contract: agreement with the reference on static landmarks that are collinear or coplanar (collinear ones
     have no fit; three points still get the rotation they determine), and |pitch| within 1e-3 degrees of 90."""
-    single = torch.is_tensor(landmarks)
-    clips = [landmarks] if single else list(landmarks)
-    if not clips:
-        raise ValueError("no clip given")
+    clips, single = clip_list(landmarks)
     valids = [valid] if single else (list(valid) if valid is not None else [None] * len(clips))
     if len(valids) != len(clips):
         raise ValueError(f"{len(clips)} clips but {len(valids)} valid arrays")
     ops._need_cuda(*clips)
     table = savgol_table(window_length, polyorder)
-    P = clips[0].shape[1] if clips[0].dim() == 3 else -1
-    plan_a, plan_b, plan_w, offsets = [], [], [], [0]
-    for L, v in zip(clips, valids):
-        if L.dim() != 3 or L.shape[1] != P or L.shape[2] != 3:
-            raise TypeError(f"every clip must have shape (F, {P}, 3), got {tuple(L.shape)}")
-        F = L.shape[0]
+    L, offsets, _ = flatten_clips(clips, (None, 3))
+    P, dev = L.shape[1], L.device
+    plan_a, plan_b, plan_w = [], [], []
+    for begin, end, v in zip(offsets[:-1], offsets[1:], valids):
+        F = end - begin
         if F < window_length:
             raise ValueError(f"a clip of {F} frames is shorter than window_length = {window_length}")
         v = np.ones(F, bool) if v is None else np.asarray(v)
         if v.shape != (F,):
             raise ValueError(f"valid has shape {v.shape} for a clip of {F} frames")
         a, b, w = gap_plan(v)
-        plan_a.append(a + offsets[-1])
-        plan_b.append(b + offsets[-1])
+        plan_a.append(a + begin)
+        plan_b.append(b + begin)
         plan_w.append(w)
-        offsets.append(offsets[-1] + F)
     neutral = np.asarray(neutral.detach().cpu() if torch.is_tensor(neutral) else neutral, dtype=np.float32)
     sidx = np.asarray(static_idx.detach().cpu() if torch.is_tensor(static_idx) else static_idx).astype(np.int64).reshape(-1)
     if neutral.ndim != 2 or neutral.shape[1] != 3:
@@ -122,15 +116,12 @@ def head_pose_from_landmarks(landmarks, neutral, static_idx, valid=None, window_
         raise ValueError(f"static_idx must lie in [0, {min(P, neutral.shape[0])}): the landmarks have {P} points, neutral {neutral.shape[0]}")
     rows = np.zeros((P, 3), np.float32)                 # the kernel takes (P, 3) and reads it at static_idx only
     rows[:min(P, neutral.shape[0])] = neutral[:P]
-    dev = clips[0].device
     up = lambda x, dt: torch.from_numpy(np.ascontiguousarray(x)).to(dt).to(dev)
-    L = clips[0] if len(clips) == 1 else torch.cat(clips, 0)
-    L = L.float().contiguous()
     R, c, t, aligned = ops.headpose_fit(L, up(np.concatenate(plan_a), torch.int32), up(np.concatenate(plan_b), torch.int32),
                                         up(np.concatenate(plan_w), torch.float32), up(rows, torch.float32),
                                         up(sidx, torch.int32), want_aligned=return_details)
     ypr, R_mod = ops.headpose_smooth(R, offsets, up(table, torch.float64), window_length, want_matrix=return_details)
-    cut = lambda x: [x[a:b] for a, b in zip(offsets[:-1], offsets[1:])]
+    cut = lambda x: cut_clips(x, offsets)
     out = cut(ypr)
     if not return_details:
         return out[0] if single else out
