@@ -1069,6 +1069,32 @@ long msmd_track_resample_ws_bytes(long total_in, int n_clips, int C);
 int msmd_track_resample(const float* x, const int* in_offsets, const int* out_offsets, int n_clips, int C, const double* savgol,
                         int window, void* ws, float* y, msmd_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Face crops for an expression encoder (reference dataset_processing/transform.py: crop_v2's cv2.warpAffine(INTER_LINEAR),
+ * Step3_preprocess_expression_code.py: cvtColor(RGB2BGR), ToTensor + Normalize).
+ *
+ * msmd_face_crop, one launch for the batch: frames (F, H, W, 3 | 4) uint8 addressed as msmd_jpeg_coefficients addresses them
+ *   (frame_stride / row_stride in bytes, pixel_stride 3 or 4; a 4th byte is never read); inverse (F, 2, 3) float64 on the
+ *   device, the map from an OUTPUT pixel (column j, row i) to source coordinates; table (3, 256) fp32 on the device.
+ *   Per output pixel, in float64 with every operation rounded on its own (no fused multiply-add):
+ *     sx = ((a00 * j) + (a01 * i)) + a02, sy = ((a10 * j) + (a11 * i)) + a12;
+ *     x0 = floor(sx), fx = sx - x0, y0 = floor(sy), fy = sy - y0;
+ *     p(y, x) = the source byte for 0 <= x < W and 0 <= y < H, else 0 (a neighbour outside the frame is not clamped);
+ *     v = ((p00 * (1 - fx) + p01 * fx) * (1 - fy)) + ((p10 * (1 - fx) + p11 * fx) * fy);   u8 = min(255, floor(v + 0.5));
+ *     (sx, sy) outside (-1, W) x (-1, H), or not finite: u8 = 0, and no integer is formed from the coordinate.
+ *   Output channel c reads source channel 2 - c when swap_rb is set, else c.
+ *   out (F, 3, out_h, out_w) of out_dtype (MSMD_F32 / MSMD_BF16 / MSMD_F16), or NULL: table[c][u8], for the 16-bit types rounded to
+ *   nearest even; crop_u8 (F, out_h, out_w, 3) uint8, or NULL: u8.  A lane owns four consecutive pixels of an output row
+ *   and stores them as 16 (8) bytes per plane and 12 bytes of crop_u8 where out_w % 4 == 0 and the buffers are 16- (8-, 4-)
+ *   byte aligned, element by element otherwise: the same bits.  A frame's bits depend on its own pixels and map alone.
+ * Returns 1 (hipErrorInvalidValue) before the launch for a NULL frames / inverse / table, both outputs NULL, F < 1, H or W
+ * outside [1, MSMD_JPEG_MAX_SIDE], out_h or out_w outside [1, MSMD_CROP_MAX_SIDE], pixel_stride not 3 or 4, strides under
+ * which rows or frames would overlap, or an out_dtype other than the three; otherwise 0 or the launch's hipError_t. */
+#define MSMD_CROP_MAX_SIDE 1024
+int msmd_face_crop(const void* frames, long frame_stride, long row_stride, int pixel_stride, int F, int H, int W,
+                   const double* inverse, const float* table, int out_h, int out_w, int swap_rb, void* out, int out_dtype,
+                   void* crop_u8, msmd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1874,6 +1874,35 @@ def track_resample(x, in_offsets, out_offsets, savgol_table=None, window=0):
     return y
 
 
+# ----------------------------------------------------------------------------- face crops (csrc/face_crop.hip)
+CROP_MAX_SIDE = _h("CROP_MAX_SIDE")     # largest output side of msmd_face_crop
+_CROP_DTYPES = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
+
+
+def face_crop(frames, inverse, table, out_size, dtype=torch.float32, swap_rb=True, want_normalised=True, want_uint8=False):
+    """-> (out (F, 3, S_h, S_w) of `dtype` or None, crop (F, S_h, S_w, 3) uint8 or None): msmd_face_crop, the float64 bilinear
+    affine warp with a zero border of include/msmd_hip.h, one launch for the batch.  frames (F, H, W, 3 | 4) uint8 on the
+    device, laid out as `jpeg_encode` takes them (alpha ignored); inverse (F, 2, 3) float64 on the device, output pixel ->
+    source coordinates; table (3, 256) fp32 on the device, out[f, c] = table[c][byte]; out_size = S or (S_h, S_w), each in
+    [1, CROP_MAX_SIDE].  swap_rb: output channel c reads source channel 2 - c."""
+    F, H, W, sb, sh, sw = _jpeg_frames(frames, 90)
+    d = {"F": F}
+    _arg("inverse", inverse, torch.float64, "F 2 3", d)
+    _arg("table", table, torch.float32, "3 256")
+    S_h, S_w = (int(out_size),) * 2 if isinstance(out_size, int) else (int(s) for s in out_size)
+    if not (1 <= S_h <= CROP_MAX_SIDE and 1 <= S_w <= CROP_MAX_SIDE):
+        raise ValueError(f"out_size {out_size!r} is outside [1, {CROP_MAX_SIDE}]")
+    if dtype not in _CROP_DTYPES:
+        raise TypeError(f"dtype must be torch.float32, torch.bfloat16 or torch.float16, got {dtype}")
+    if not (want_normalised or want_uint8):
+        raise ValueError("face_crop: neither output is asked for")
+    out = torch.empty(F, 3, S_h, S_w, device=frames.device, dtype=dtype) if want_normalised else None
+    crop = torch.empty(F, S_h, S_w, 3, device=frames.device, dtype=torch.uint8) if want_uint8 else None
+    _lib.check(_lib.load().msmd_face_crop(_p(frames), sb, sh, sw, F, H, W, _p(inverse), _p(table), S_h, S_w, int(bool(swap_rb)),
+                                          _p(out), _CROP_DTYPES[dtype], _p(crop), _stream()), "msmd_face_crop")
+    return out, crop
+
+
 # ----------------------------------------------------------------------------- style losses (csrc/style_loss.hip, DESIGN.md 5.19)
 STYLE_ROWS, STYLE_KTILE, STYLE_FCHUNK = _h("STYLE_ROWS", "STYLE_KTILE", "STYLE_FCHUNK")    # the kernels' tile (include/msmd_hip.h)
 NT_XENT_CHUNK = _h("NT_XENT_CHUNK")  # rows j per step of the NT-Xent backward's coefficient table
