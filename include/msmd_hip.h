@@ -978,6 +978,75 @@ int msmd_jpeg_write(const short* coef, int B, int H, int W, const void* header, 
                     const long* offsets, void* out, long out_bytes, msmd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Baseline JPEG decoder, the inverse of the encoder above: B files of one size and sampling, back to back in
+ * one byte stream on the device -> pixels (B, H, W, 3 | 4) uint8.  The host (ops.jpeg_parse) reads the marker segments, finds
+ * the restart intervals and builds the tables below; the three entries are the entropy decode, the inverse DCT and the colour
+ * pass.  Integer arithmetic throughout: the pixels are a pure function of the file's bytes.
+ *
+ * Accepted (everything else is refused by the host with ValueError before a launch): SOF0, 8 bit, 1 <= H, W <=
+ *   MSMD_JPEG_MAX_SIDE; one scan with all components, Ss = 0, Se = 63, Ah = Al = 0; one component (MSMD_JPEG_GREY; its
+ *   sampling factors are ignored, as T.81 A.2.2 has it for a scan of one component) or three with luminance (1,1), (2,1) or
+ *   (2,2) and both chrominance components (1,1): MSMD_JPEG_444 / _422 / _420; DQT with 8-bit entries, ids 0-3; DHT classes 0 / 1,
+ *   ids 0 / 1, any valid lengths up to 16; no DHT at all: the Annex K.3 tables; DRI any or none (then the scan is one interval).
+ * Geometry (`layout` fixes hs, vs = 1,1 / 1,1 / 2,1 / 2,2): an MCU is 8 hs x 8 vs pixels, mcux = ceil(W / 8 hs), mcuy =
+ *   ceil(H / 8 vs), n_mcu = mcux mcuy; component c has h_c x v_c blocks per MCU ((hs, vs) for c = 0, else (1, 1)), in the scan row
+ *   by row inside the MCU, Y then Cb then Cr.  Its plane is bh_c = mcuy v_c by bw_c = mcux h_c blocks; the planes of a frame
+ *   follow one another, msmd_jpeg_decode_blocks(H, W, layout) = sum_c bh_c bw_c blocks in all (-1 if out of range).
+ * Table set (MSMD_JPEG_TABLE_SET_BYTES = 192 + 8 + 4 x 384 bytes, built by the host, de-duplicated by its bytes): Q of
+ *   component 0, 1, 2 (64 bytes each, zig-zag order as in DQT); the bytes Td0 Ta0 Td1 Ta1 Td2 Ta2 0 0; the Huffman tables DC 0,
+ *   DC 1, AC 0, AC 1 in canonical form (T.81 F.2.2.3), each int32 maxcode[16] (-1: no code of that length), int32 delta[16] =
+ *   valptr - mincode, then HUFFVAL padded to 256 bytes.
+ * Interval table: n_entries rows of three int64, n_entries a multiple of MSMD_JPEG_DECODE_LANES (a workgroup): [0] byte offset
+ *   of the interval in the stream, [1] = length | frame << 32, [2] = first MCU | table set << 32.  All rows of one workgroup
+ *   name one table set (its first row's); a row with frame = -1 is padding.  A row that points outside the stream, the frame
+ *   range or the MCU range is skipped.
+ * Entropy decode (T.81 F.2.2) of one interval = MCUs [first, min(first + Ri, n_mcu)) (Ri = 0: to n_mcu), predictors 0 at its
+ *   start.  The bits are the interval's bytes with every 0x00 that follows a 0xFF dropped; past the end the reader supplies
+ *   zero bits; no byte outside [offset, offset + length) is read.  A unit is a Huffman code and its extra bits.  DC: code ->
+ *   category s <= 16, diff = EXTEND(RECEIVE(s), s), pred = sat16(pred + diff), coefficient 0 = pred.  AC from k = 1: code ->
+ *   (r, s); s = 0: r = 15 adds 16 to k, any other r ends the block; else k += r, coefficient k = sat16(EXTEND(RECEIVE(s), s)),
+ *   k += 1.  Decode errors, checked per unit in this order: no code within 16 bits, or a DC category above 16
+ *   (MSMD_JPEG_ERR_CODE); bits consumed past the interval's end (MSMD_JPEG_ERR_OVERRUN); k past 63 after adding a run, ZRL
+ *   included (MSMD_JPEG_ERR_RUN).  The lane ORs the bit into status[frame] and stops its interval without storing the unit's
+ *   coefficient; what it has not written stays zero.  MSMD_JPEG_ERR_RESTART is set by the host in the initial status where
+ *   the number of intervals is not ceil(n_mcu / Ri) or the RSTn do not count mod 8; interval k of the file is then decoded as
+ *   interval k of the frame for k below both counts.
+ * Inverse DCT: F = coefficient x Q in natural order, x = M^T F M with the encoder's M (S = 15) and no intermediate rounding,
+ *   |F| < 2^23, every absolute column sum of M is 86 567 < 2^17: pass 1 < 2^40, pass 2 < 2^57, both int64;
+ *   sample = clamp(((x + 2^29) >> 30) + 128, 0, 255).
+ * Upsampling (libjpeg's triangle filters) of a chrominance plane of true size cw = ceil(W / hs), ch = ceil(H / vs), p = a row:
+ *   (2,1): out[2i] = (3 p[i] + p[i-1] + 1) >> 2, out[2i+1] = (3 p[i] + p[i+1] + 2) >> 2, out[0] = p[0], out[2cw-1] = p[cw-1].
+ *   (2,2): output row 2j: r = 3 p[j] + p[j-1], row 2j+1: r = 3 p[j] + p[j+1] (row -1 is row 0, row ch is row ch - 1); out[2i] =
+ *   (3 r[i] + r[i-1] + 8) >> 4, out[2i+1] = (3 r[i] + r[i+1] + 7) >> 4, out[0] = (4 r[0] + 8) >> 4, out[2cw-1] = (4 r[cw-1] + 7) >> 4.
+ * Colour, cb = Cb - 128, cr = Cr - 128: R = clamp(Y + ((91881 cr + 32768) >> 16)), G = clamp(Y + ((-22554 cb - 46802 cr +
+ *   32768) >> 16)), B = clamp(Y + ((116130 cb + 32768) >> 16)); grey: R = G = B = Y; a fourth channel is 255.
+ *
+ * msmd_jpeg_decode_coefficients: zeroes coef (B, blocks, 64) int16 (zig-zag order, block-raster order per component plane),
+ *   then one lane per interval-table row.  status (B) int32 is ORed into, never cleared: the host uploads its initial value.
+ * msmd_jpeg_decode_planes: frame_set (B) int32 = the table set of each frame; planes (B, 64 blocks) uint8, each component's
+ *   plane padded to whole blocks, row pitch 8 bw_c.
+ * msmd_jpeg_decode_pixels: pixels (B, H, W, channels) uint8 contiguous, 4-byte aligned; channels 3 or 4.
+ * Each returns 1 for sizes out of range, a null pointer, n_entries not a positive multiple of the lanes or n_sets < 1. */
+#define MSMD_JPEG_GREY 0
+#define MSMD_JPEG_444 1
+#define MSMD_JPEG_422 2
+#define MSMD_JPEG_420 3
+#define MSMD_JPEG_ERR_CODE (1 << 0)
+#define MSMD_JPEG_ERR_RUN (1 << 1)
+#define MSMD_JPEG_ERR_OVERRUN (1 << 2)
+#define MSMD_JPEG_ERR_RESTART (1 << 3)
+#define MSMD_JPEG_TABLE_SET_BYTES 1736
+#define MSMD_JPEG_DECODE_LANES 64
+long msmd_jpeg_decode_blocks(int H, int W, int layout);
+int msmd_jpeg_decode_coefficients(const void* stream_bytes, long n_bytes, const long* intervals, int n_entries,
+                                  const void* table_sets, int n_sets, int B, int H, int W, int layout, int restart_interval,
+                                  short* coef, int* status, msmd_stream_t stream);
+int msmd_jpeg_decode_planes(const short* coef, const void* table_sets, int n_sets, const int* frame_set, int B, int H, int W,
+                            int layout, void* planes, msmd_stream_t stream);
+int msmd_jpeg_decode_pixels(const void* planes, int B, int H, int W, int layout, int channels, void* pixels,
+                            msmd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Style losses (reference utils/common.py:29-91 StyleAdherenceLoss, 835-875 nt_xent_loss).  fp32, contiguous,
  * no allocation, no host synchronisation, no floating-point atomics: every sum has one owner and an order that is a function
  * of the shape alone, so the same inputs give the same bits on every run and a batch row's bits do not depend on its batch.

@@ -14,6 +14,8 @@ tracked ends, and `smooth_boxes` counts a smoothed value within 1e-6 below an in
 The warp is not cv2's fixed-point one.
 
     python -m msmd_amd.utils.face_crop --frames clip.npy --boxes clip.pickle --out crops.npy [--size 224] [--video crops.avi --fps 25]
+
+`--frames` also takes a Motion-JPEG `.avi` (`utils/media.read_video` decodes it on the device).
 """
 from __future__ import annotations
 
@@ -276,21 +278,27 @@ def crop_clip(frames, boxes, out_size=256, smoothing="savgol", batch_size=32, K=
 
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description="normalised face crops of a clip from its frames and Step 1's box pickle")
-    p.add_argument("--frames", required=True, help=".npy, (F, H, W, 3) uint8")
+    p.add_argument("--frames", required=True, help=".npy, (F, H, W, 3) uint8, or a Motion-JPEG .avi (decoded on the device)")
     p.add_argument("--boxes", required=True, help="Step 1's .pickle: processed_bbox_frames if present, else raw_bbox_frames")
     p.add_argument("--out", required=True, help=".npy to write, (F, 3, S, S) float32")
     p.add_argument("--size", type=int, default=256, help="224 for the reference's SPECTRE flag")
     p.add_argument("--smoothing", default="savgol", choices=SMOOTHINGS)
     p.add_argument("--batch_size", type=int, default=32)
     p.add_argument("--video", default=None, help="also write the uint8 crops as a Motion-JPEG .avi")
-    p.add_argument("--fps", type=float, default=None, help="frame rate of --video (default: the pickle's fps, else 30)")
+    p.add_argument("--fps", type=float, default=None,
+                   help="frame rate of --video (default: the pickle's fps, else the rate of an .avi given as --frames, else 30)")
     p.add_argument("--device", default="cuda")
     return p.parse_args(argv)
 
 
 def main(argv=None):
     args = parse_args(argv)
-    frames = torch.from_numpy(np.load(args.frames)).to(args.device)
+    file_fps = None
+    if args.frames.lower().endswith(".avi"):
+        from .media import read_avi, read_video
+        frames, file_fps = read_video(args.frames, device=args.device), read_avi(args.frames).fps
+    else:
+        frames = torch.from_numpy(np.load(args.frames)).to(args.device)
     with open(args.boxes, "rb") as f:
         meta = pkl.load(f)
     boxes = meta["processed_bbox_frames"] if "processed_bbox_frames" in meta else meta["raw_bbox_frames"]
@@ -306,7 +314,7 @@ def main(argv=None):
     print(f"wrote {args.out}: {out.shape}")
     if args.video is not None:
         from .media import write_avi
-        fps = args.fps if args.fps is not None else meta.get("fps", 30)
+        fps = args.fps if args.fps is not None else meta.get("fps", 30 if file_fps is None else file_fps)
         n = write_avi(args.video, jpegs, fps, (args.size, args.size))
         print(f"wrote {args.video}: {len(jpegs)} frames, {n} bytes")
 

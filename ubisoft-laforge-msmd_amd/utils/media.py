@@ -4,12 +4,17 @@ pipes PNG files and the audio through ffmpeg to H.264; there is no ffmpeg here, 
 Each frame is compressed on the device by the baseline JPEG encoder of csrc/jpeg.hip (`ops.jpeg_encode`) and
 leaves it at its compressed size; this module only lays the bytes out as RIFF `AVI ` on the host.  The file is AVI 1.0 with an
 `idx1` index, at most 2^31 - 1 bytes: OpenDML (AVI 2.0), H.264 and 4:2:0 stay outside.
+
+Frames in: `read_avi` finds the JPEG files inside a Motion-JPEG AVI, this project's or another writer's,
+`read_video` decodes them on the device with `ops.jpeg_decode` (baseline, grey / 4:4:4 / 4:2:2 / 4:2:0), and `extract_frames`
+writes them out as `.jpg` files, which is what the reference's helper of that name does through ffmpeg.
 """
 from __future__ import annotations
 
 import os
 import struct
 from fractions import Fraction
+from typing import NamedTuple, Optional
 
 import numpy as np
 
@@ -144,3 +149,186 @@ def combine_frames_and_audio(frames, audio_file, fps, output, quality=90, chunk=
     for i in range(0, frames.shape[0], chunk):
         jpegs += encode_jpeg(frames[i:i + chunk], quality)
     return write_avi(output, jpegs, fps, (frames.shape[2], frames.shape[1]), audio)
+
+
+# ----------------------------------------------------------------------------- frames in
+def decode_jpeg(files, channels=3):
+    """JFIF files (a list of bytes, or what `ops.jpeg_encode` returns, copied to the host) -> (B, H, W, channels) uint8 on the
+    device: `ops.jpeg_decode`, strict."""
+    return ops.jpeg_decode(files, channels=channels)
+
+
+class AviClip(NamedTuple):
+    """What `read_avi` returns.  data: the file as a uint8 array; frames: [(first, end)] byte ranges of the JPEG files in it, one
+    per frame in display order; fps: Fraction; size: (width, height); audio: (pcm int16 (n, channels), rate) or None."""
+    data: np.ndarray
+    frames: list
+    fps: Fraction
+    size: tuple
+    audio: Optional[tuple]
+
+    def jpeg(self, k):
+        return self.data[self.frames[k][0]:self.frames[k][1]]
+
+
+def _riff_chunks(blob, pos, end):
+    """(fourcc, body offset, size) of the chunks in blob[pos:end]; a size that runs past `end` (a cut file) is clipped."""
+    while pos + 8 <= end:
+        cid, size = bytes(blob[pos:pos + 4]), struct.unpack_from("<I", blob, pos + 4)[0]
+        size = min(size, end - pos - 8)
+        yield cid, pos + 8, size
+        pos += 8 + size + (size & 1)
+
+
+def read_avi(path):
+    """A Motion-JPEG AVI 1.0 file -> AviClip.  Reads `avih`, the `vids` stream (handler or compression `MJPG` / `mjpg`; any other
+    raises ValueError naming the fourcc), an optional 16-bit PCM `auds` stream, and the `movi` chunks through `idx1` where the
+    file has one, else by walking `movi` (`LIST rec ` groups included; so a file cut short behind `movi` still reads).  Chunks
+    are padded to even lengths.  A video chunk of length zero (a dropped frame) repeats the frame before it.  OpenDML (AVI
+    2.0: `RIFF AVIX`, an `odml` list, `indx`) raises ValueError.  Nothing is decoded here."""
+    data = np.fromfile(os.fspath(path), dtype=np.uint8)
+    n = data.size
+    if n < 12 or bytes(data[:4]) != b"RIFF" or bytes(data[8:12]) != b"AVI ":
+        raise ValueError(f"{path}: not a RIFF AVI file")
+    riff_end = min(n, 8 + struct.unpack_from("<I", data, 4)[0])
+    if riff_end + 12 <= n and bytes(data[riff_end:riff_end + 4]) == b"RIFF" and bytes(data[riff_end + 8:riff_end + 12]) == b"AVIX":
+        raise ValueError(f"{path}: OpenDML file (RIFF AVIX): only AVI 1.0 is read")
+    streams, movi, index = [], None, None
+    for cid, body, size in _riff_chunks(data, 12, riff_end):
+        kind = bytes(data[body:body + 4]) if cid == b"LIST" else None
+        if kind == b"hdrl":
+            for c2, b2, s2 in _riff_chunks(data, body + 4, body + size):
+                k2 = bytes(data[b2:b2 + 4]) if c2 == b"LIST" else None
+                if k2 == b"odml":
+                    raise ValueError(f"{path}: OpenDML file (LIST odml): only AVI 1.0 is read")
+                if k2 != b"strl":
+                    continue
+                st = {}
+                for c3, b3, s3 in _riff_chunks(data, b2 + 4, b2 + s2):
+                    if c3 == b"strh" and s3 >= 36:
+                        st["type"], st["handler"] = bytes(data[b3:b3 + 4]), bytes(data[b3 + 4:b3 + 8])
+                        st["scale"], st["rate"] = struct.unpack_from("<II", data, b3 + 20)
+                    elif c3 == b"strf":
+                        st["strf"] = bytes(data[b3:b3 + s3])
+                    elif c3 == b"indx":
+                        raise ValueError(f"{path}: OpenDML file (indx): only AVI 1.0 is read")
+                streams.append(st)
+        elif kind == b"movi":
+            movi = (body, body + size)
+        elif cid == b"idx1":
+            index = (body, size // 16)
+    if movi is None:
+        raise ValueError(f"{path}: no movi list")
+    video = [k for k, st in enumerate(streams) if st.get("type") == b"vids"]
+    if not video:
+        raise ValueError(f"{path}: no video stream")
+    v = video[0]
+    vs = streams[v]
+    strf = vs.get("strf", b"")
+    compression = strf[16:20] if len(strf) >= 20 else b""
+    if vs["handler"] not in (b"MJPG", b"mjpg") and compression not in (b"MJPG", b"mjpg"):
+        raise ValueError(f"{path}: video stream {vs['handler']!r} / {compression!r} is not Motion-JPEG (MJPG)")
+    if vs["scale"] == 0 or vs["rate"] == 0:
+        raise ValueError(f"{path}: the video stream has dwRate / dwScale = {vs['rate']} / {vs['scale']}")
+    width, height = struct.unpack_from("<ii", strf, 4) if len(strf) >= 12 else (0, 0)
+    audio = [k for k, st in enumerate(streams) if st.get("type") == b"auds"]
+    wave = None
+    if audio:
+        a = audio[0]
+        fmt = streams[a].get("strf", b"")
+        if len(fmt) < 16:
+            raise ValueError(f"{path}: the audio stream has no WAVEFORMAT")
+        tag, channels, arate, _, _, bits = struct.unpack_from("<HHIIHH", fmt)
+        if tag != 1 or bits != 16 or channels < 1:
+            raise ValueError(f"{path}: audio format tag {tag}, {bits} bits: only 16-bit PCM is read")
+        wave = (a, channels, arate)
+    vid_ids = (b"%02ddc" % v, b"%02ddb" % v)
+    aud_id = b"%02dwb" % wave[0] if wave else None
+    chunks = []                                         # (fourcc, body offset, size) in file order
+    if index is not None and index[1] > 0:
+        entries = np.frombuffer(data[index[0]:index[0] + 16 * index[1]].tobytes(), dtype=[("id", "S4"), ("flags", "<u4"), ("off", "<u4"), ("size", "<u4")])
+        # offsets count from the `movi` fourcc; some writers count from the start of the file
+        first_off = int(entries["off"][0])
+        rel = movi[0] if bytes(data[movi[0] + first_off:movi[0] + first_off + 4]) == bytes(entries["id"][0]).ljust(4, b"\x00") else 0
+        for cid, off, size in zip(entries["id"].tolist(), entries["off"].tolist(), entries["size"].tolist()):
+            at = rel + off + 8
+            if at + size > n:
+                raise ValueError(f"{path}: idx1 names bytes {at} .. {at + size} of a file of {n}")
+            chunks.append((cid.ljust(4, b"\x00"), at, size))
+    else:
+        def walk(pos, end):
+            for cid, body, size in _riff_chunks(data, pos, end):
+                if cid == b"LIST":
+                    if bytes(data[body:body + 4]) == b"rec ":
+                        walk(body + 4, body + size)
+                else:
+                    chunks.append((cid, body, size))
+        walk(movi[0] + 4, movi[1])
+    frames, pcm = [], []
+    for cid, body, size in chunks:
+        if cid in vid_ids:
+            if size == 0:
+                if not frames:
+                    raise ValueError(f"{path}: the first video chunk is empty")
+                frames.append(frames[-1])
+            else:
+                frames.append((body, body + size))
+        elif cid == aud_id:
+            pcm.append(data[body:body + size])
+    if not frames:
+        raise ValueError(f"{path}: no video frames")
+    track = None
+    if wave:
+        raw = np.concatenate(pcm) if pcm else np.zeros(0, np.uint8)
+        align = 2 * wave[1]
+        track = (np.frombuffer(raw[:raw.size // align * align].tobytes(), "<i2").reshape(-1, wave[1]).astype(np.int16), wave[2])
+    return AviClip(data, frames, Fraction(vs["rate"], vs["scale"]), (int(width), abs(int(height))), track)
+
+
+def read_video(path, channels=3, chunk=256, device="cuda"):
+    """A Motion-JPEG AVI -> its frames as one (F, H, W, channels) uint8 tensor on the device, `chunk` frames decoded per call of
+    `ops.jpeg_decode`.  A frame whose size or sampling differs from the first raises ValueError; so does a damaged one."""
+    import torch
+    clip = read_avi(path)
+    first = ops.jpeg_parse(clip.jpeg(0))[0]
+    shape = (first["height"], first["width"], first["layout"])
+    out = torch.empty(len(clip.frames), shape[0], shape[1], channels, device=device, dtype=torch.uint8)
+    for i in range(0, len(clip.frames), int(chunk)):
+        j = min(i + int(chunk), len(clip.frames))
+        h = ops.jpeg_parse(clip.jpeg(i))[0]
+        if (h["height"], h["width"], h["layout"]) != shape:
+            raise ValueError(f"{path}: frame {i} is {h['height']} x {h['width']} layout {h['layout']}, frame 0 is "
+                             f"{shape[0]} x {shape[1]} layout {shape[2]}")
+        files = [clip.jpeg(k) for k in range(i, j)]
+        if out[i:j].data_ptr() % 4 == 0:
+            ops.jpeg_decode(files, channels=channels, out=out[i:j])
+        else:
+            out[i:j] = ops.jpeg_decode(files, channels=channels, device=out.device)
+    return out
+
+
+def _default_dht():
+    return b"".join(b"\xff\xc4" + struct.pack(">H", 19 + len(vals)) + bytes((cls << 4 | tid,)) + bits + vals
+                    for cls, tid, bits, vals in ops.JPEG_HUFFMAN)
+
+
+def extract_frames(filename, output_dir, quality=1):
+    """The reference helper's name and argument order (utils/media.py: ffmpeg writes `%06d.jpg` from 0): the frames of a
+    Motion-JPEG AVI as JPEG files in `output_dir`.  Nothing is decoded or re-encoded: a file is the frame's chunk as it stands in
+    the AVI, with the Annex K.3 `DHT` segments inserted in front of `SOS` where the frame carries none (the AVI `MJPG`
+    convention, which stand-alone readers do not know).  `quality` is accepted for the reference's callers and ignored.  Only
+    Motion-JPEG is read: an H.264 file raises ValueError in `read_avi`.  -> the paths written."""
+    clip = read_avi(filename)
+    os.makedirs(os.fspath(output_dir), exist_ok=True)
+    paths = []
+    for k in range(len(clip.frames)):
+        raw = clip.jpeg(k).tobytes()
+        header = ops.jpeg_parse(raw)[0]
+        if header["default_huffman"]:
+            sos = header["scan"][0] - 8 - 2 * header["components"]
+            raw = raw[:sos] + _default_dht() + raw[sos:]
+        p = os.path.join(os.fspath(output_dir), "%06d.jpg" % k)
+        with open(p, "wb") as fh:
+            fh.write(raw)
+        paths.append(p)
+    return paths
