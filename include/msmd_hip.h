@@ -979,7 +979,7 @@ int msmd_jpeg_write(const short* coef, int B, int H, int W, const void* header, 
 
 /* ------------------------------------------------------------------------------------------------
  * Baseline JPEG decoder, the inverse of the encoder above: B files of one size and sampling, back to back in
- * one byte stream on the device -> pixels (B, H, W, 3 | 4) uint8.  The host (ops.jpeg_parse) reads the marker segments, finds
+ * one byte stream on the device -> pixels (B, H, W, 3 | 4) uint8.  The host (jpeg_format.jpeg_parse) reads the marker segments, finds
  * the restart intervals and builds the tables below; the three entries are the entropy decode, the inverse DCT and the colour
  * pass.  Integer arithmetic throughout: the pixels are a pure function of the file's bytes.
  *

@@ -11,7 +11,7 @@ from PIL import Image
 
 import jpeg_decode_ref as dr
 import jpeg_ref as jr
-from msmd_amd import ops
+from msmd_amd import jpeg_format, ops
 from msmd_amd.utils import media
 
 # The restatement against Pillow 12.2 (libjpeg-turbo's islow inverse DCT, its triangle upsampling and its colour tables) on the
@@ -260,7 +260,7 @@ def test_damaged_streams_are_defined_by_the_restatement():
 def test_decode_plan_groups_rows_by_table_set():
     img = images()["smooth"]
     files = [pillow_jpeg(img, q, 0, 1) for q in (50, 50, 90, 100, 100)]
-    plan = ops._jpeg_plan(files)
+    plan = jpeg_format._jpeg_plan(files)
     n_int = ops.jpeg_parse(files[0])[1].shape[0]
     assert plan.n_sets == 3 and plan.frame_set.tolist() == [0, 0, 1, 2, 2] and (plan.B, plan.H, plan.W, plan.layout) == (5, 40, 56, ops.JPEG_444)
     rows = plan.intervals
@@ -284,14 +284,49 @@ def test_decode_plan_groups_rows_by_table_set():
         assert plan.headers[b]["table_set"] == ops.jpeg_parse(f)[0]["table_set"] and plan.headers[b]["scan"] == ops.jpeg_parse(f)[0]["scan"]
     # the second input form: one array and offsets
     offsets = np.cumsum([0] + [len(f) for f in files])
-    again = ops._jpeg_plan((blob, offsets))
+    again = jpeg_format._jpeg_plan((blob, offsets))
     assert np.array_equal(again.intervals, rows) and again.sets.tobytes() == plan.sets.tobytes()
     with pytest.raises(ValueError, match="share size"):
-        ops._jpeg_plan([files[0], pillow_jpeg(img[:24], 90, 0, 1)])
+        jpeg_format._jpeg_plan([files[0], pillow_jpeg(img[:24], 90, 0, 1)])
     with pytest.raises(ValueError, match="share size"):
-        ops._jpeg_plan([files[0], pillow_jpeg(img, 90, 2, 1)])
+        jpeg_format._jpeg_plan([files[0], pillow_jpeg(img, 90, 2, 1)])
     with pytest.raises(ValueError, match="channels"):
         ops.jpeg_decode(files, channels=2)
+
+
+def test_format_module_never_loads_the_library(monkeypatch):
+    """msmd_amd.jpeg_format is host code: it parses, plans and writes a header with `_lib.load` made to raise."""
+    from msmd_amd import _lib
+
+    def no_library(*args, **kwargs):
+        raise AssertionError("jpeg_format reached _lib.load")
+    monkeypatch.setattr(_lib, "load", no_library)
+    jf = jpeg_format
+    img = images()["smooth"][:24, :40]
+    files = [pillow_jpeg(img, q, 2, 1) for q in (50, 90)]
+    h, iv = jf.jpeg_parse(files[0])
+    assert (h["height"], h["width"], h["layout"], h["restart_interval"], h["n_mcu"], h["status"]) == (24, 40, jf.JPEG_420, 1, 6, 0)
+    assert h["sampling"] == ((2, 2), (1, 1), (1, 1)) and iv.tolist() == [list(t) for t in dr.walk(files[0])["intervals"]] and len(iv) == 6
+    plan = jf._jpeg_plan(files)
+    assert (plan.B, plan.H, plan.W, plan.layout, plan.ri, plan.n_sets) == (2, 24, 40, jf.JPEG_420, 1, 2)
+    assert plan.frame_set.tolist() == [0, 1] and plan.sets.size == 2 * jf.JPEG_TABLE_SET_BYTES and plan.blocks == 6 * 6
+    rows = plan.intervals
+    assert rows.shape == (2 * jf.JPEG_DECODE_LANES, 3)                          # the set changes: frame 1 begins a workgroup
+    for b in (0, 1):
+        mine = rows[b * 64:b * 64 + 6]
+        assert (mine[:, 1] >> 32).tolist() == [b] * 6 and (mine[:, 2] >> 32).tolist() == [b] * 6
+        assert (mine[:, 2] & 0xFFFFFFFF).tolist() == list(range(6)) and (rows[b * 64 + 6:(b + 1) * 64, 1] >> 32 == -1).all()
+        assert plan.sets[b * jf.JPEG_TABLE_SET_BYTES:(b + 1) * jf.JPEG_TABLE_SET_BYTES].tobytes() == jf.jpeg_parse(files[b])[0]["table_set"]
+    # what the encoder's header says is what the parser reads back
+    head = jf.jpeg_header(40, 56, 90)
+    h, iv = jf.jpeg_parse(head + b"\xff\xd9")
+    assert (h["height"], h["width"], h["layout"], h["restart_interval"]) == (40, 56, jf.JPEG_444, jf.JPEG_RESTART_INTERVAL)
+    assert h["scan"] == (len(head), len(head)) and iv.tolist() == [[len(head), len(head)]]
+    zz = list(jf.JPEG_ZIGZAG)
+    luma, chroma = (np.array(jf.jpeg_quant_table(base, 90))[zz] for base in (jf.JPEG_BASE_LUMA, jf.JPEG_BASE_CHROMA))
+    assert np.array_equal(h["quant"], np.stack([luma, chroma, chroma]))
+    assert h["huffman"] == {(cls, tid): (bits, vals) for cls, tid, bits, vals in jf.JPEG_HUFFMAN} and not h["default_huffman"]
+    assert h["selectors"] == ((0, 0), (1, 1), (1, 1)) and head.count(jf.jpeg_dht()) == 1
 
 
 # ----------------------------------------------------------------------------- AVI

@@ -3,16 +3,14 @@
 // is integer arithmetic, so the file is a pure function of the frames.  Four kernels, no global atomics, no host
 // synchronisation: coefficients; pack (run twice: once for the stuffed length of every interval, once to write the bytes at
 // their final place); the two scans in between that turn lengths into offsets.
-#include "common.h"
+#include "jpeg_common.h"
 
 namespace {
 
 #define JP_RI MSMD_JPEG_RESTART_INTERVAL   // MCUs per restart interval = per workgroup
 #define JP_BLOCKS (3 * JP_RI)              // 8 x 8 blocks of an interval: Y, Cb, Cr of each MCU
 #define JP_THREADS 256
-#define JP_S 15                            // DCT matrix scale
-#define JP_ROW 9                           // LDS row pitch of a staged block (ints): rows and columns both conflict-free
-#define JP_BLK (8 * JP_ROW)
+#define JP_BLK (8 * JPEG_ROW)
 #define JP_BLOCK_BYTES 208                 // worst case of one block: 22 bits of DC + 63 x 26 bits of AC = 1660 bits
 #define JP_WORDS (JP_BLOCKS * JP_BLOCK_BYTES / 4)
 
@@ -23,10 +21,7 @@ __constant__ unsigned char c_base[2][64] = {
      100, 103, 99},
     {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
      99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99}};
-// natural index -> position in the zig-zag scan
-__constant__ unsigned char c_nat2zz[64] = {0,  1,  5,  6,  14, 15, 27, 28, 2,  4,  7,  13, 16, 26, 29, 42, 3,  8,  12, 17, 25, 30,
-                                           41, 43, 9,  11, 18, 24, 31, 40, 44, 53, 10, 19, 23, 32, 39, 45, 52, 54, 20, 22, 33, 38,
-                                           46, 51, 55, 60, 21, 34, 37, 47, 50, 56, 59, 61, 35, 36, 48, 49, 57, 58, 62, 63};
+__constant__ Perm64 c_nat2zz = inverse(kZz2Nat);   // natural index -> position in the zig-zag scan
 
 // T.81 Annex K.3: BITS and HUFFVAL of the four typical tables; the codes are derived at compile time (Annex C).
 struct HuffSpec { unsigned char bits[16]; unsigned char vals[162]; int n; };
@@ -71,27 +66,6 @@ constexpr HuffSpec kAcChroma = {
 // [0] luminance, [1] chrominance
 __constant__ HuffTab c_dc[2] = {make_huff(kDcLuma), make_huff(kDcChroma)};
 __constant__ HuffTab c_ac[2] = {make_huff(kAcLuma), make_huff(kAcChroma)};
-
-// M[k][n] = rint(2^15 c_k cos((2 n + 1) k pi / 16)) for n < 4; M[k][7 - n] = (-1)^k M[k][n] holds for the rounded integers too.
-// |M| <= 16069 and a row's absolute sum is <= 92680.
-#define JP_M0 11585
-__device__ constexpr int kM[8][4] = {{JP_M0, JP_M0, JP_M0, JP_M0},   {16069, 13623, 9102, 3196},   {15137, 6270, -6270, -15137},
-                                     {13623, -3196, -16069, -9102}, {JP_M0, -JP_M0, -JP_M0, JP_M0}, {9102, -16069, 3196, 13623},
-                                     {6270, -15137, 15137, -6270},  {3196, -9102, 13623, -16069}};
-
-// One 8-point pass with the even / odd split (the same integers as the plain matrix product: integer sums re-associate).
-template <typename Acc> __device__ __forceinline__ void dct8(const int* x, Acc* out) {
-  int s[4], d[4];
-#pragma unroll
-  for (int n = 0; n < 4; ++n) { s[n] = x[n] + x[7 - n]; d[n] = x[n] - x[7 - n]; }
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    Acc a = 0;
-#pragma unroll
-    for (int n = 0; n < 4; ++n) a += (Acc)kM[k][n] * (Acc)((k & 1) ? d[n] : s[n]);
-    out[k] = a;
-  }
-}
 
 // interval geometry shared by the kernels
 struct Geo { int mcu_x, n_mcu, n_int; };
@@ -142,12 +116,12 @@ __global__ __launch_bounds__(JP_THREADS) void jpeg_coef_kernel(const unsigned ch
       cb = min(max(((-11059 * R - 21709 * G + 32768 * Bv + 32768) >> 16) + 128, 0), 255) - 128;
       cr = min(max(((32768 * R - 27439 * G - 5329 * Bv + 32768) >> 16) + 128, 0), 255) - 128;
     }
-    int* o = s_px + (m * 3) * JP_BLK + r * JP_ROW + px;
+    int* o = s_px + (m * 3) * JP_BLK + r * JPEG_ROW + px;
     o[0] = yy; o[JP_BLK] = cb; o[2 * JP_BLK] = cr;
   }
   __syncthreads();
   for (int task = tid; task < JP_BLOCKS * 8; task += JP_THREADS) {      // pass 1: (block, row), in place
-    int* row = s_px + (task >> 3) * JP_BLK + (task & 7) * JP_ROW;
+    int* row = s_px + (task >> 3) * JP_BLK + (task & 7) * JPEG_ROW;
     int x[8], t[8];
 #pragma unroll
     for (int n = 0; n < 8; ++n) x[n] = row[n];
@@ -162,7 +136,7 @@ __global__ __launch_bounds__(JP_THREADS) void jpeg_coef_kernel(const unsigned ch
     int t[8];
     long c[8];
 #pragma unroll
-    for (int m = 0; m < 8; ++m) t[m] = col[m * JP_ROW];
+    for (int m = 0; m < 8; ++m) t[m] = col[m * JPEG_ROW];
     dct8<long>(t, c);
     const unsigned short* qt = s_q[(blk % 3) != 0];
 #pragma unroll
@@ -171,10 +145,10 @@ __global__ __launch_bounds__(JP_THREADS) void jpeg_coef_kernel(const unsigned ch
       const unsigned Q = qt[nat];
       const unsigned long a = (unsigned long)(c[k] < 0 ? -c[k] : c[k]);
       // (2 a + d) div (2 d) with d = Q 2^30 is ((2 a + d) >> 31) div Q: nested floor divisions compose; the shifted value is < 2^12
-      const unsigned u = (unsigned)((2 * a + ((unsigned long)Q << (2 * JP_S))) >> (2 * JP_S + 1));
+      const unsigned u = (unsigned)((2 * a + ((unsigned long)Q << (2 * JPEG_DCT_S))) >> (2 * JPEG_DCT_S + 1));
       int q = (int)(u / Q);
       if (nat != 0) q = min(q, 1023);
-      s_zz[blk * 64 + c_nat2zz[nat]] = (short)(c[k] < 0 ? -q : q);
+      s_zz[blk * 64 + c_nat2zz.v[nat]] = (short)(c[k] < 0 ? -q : q);
     }
   }
   __syncthreads();
@@ -362,7 +336,7 @@ __global__ __launch_bounds__(JP_THREADS) void jpeg_offsets_kernel(const long* __
 }
 
 bool jpeg_sizes_ok(int B, int H, int W, long* grid) {
-  if (B <= 0 || H <= 0 || W <= 0 || H > MSMD_JPEG_MAX_SIDE || W > MSMD_JPEG_MAX_SIDE) return false;
+  if (B <= 0 || jpeg_sides_bad(H, W)) return false;
   *grid = (long)B * geo_of(H, W).n_int;
   return *grid <= 2147483647L;
 }
@@ -370,8 +344,7 @@ bool jpeg_sizes_ok(int B, int H, int W, long* grid) {
 }  // namespace
 
 extern "C" int msmd_jpeg_intervals(int H, int W) {
-  if (H <= 0 || W <= 0 || H > MSMD_JPEG_MAX_SIDE || W > MSMD_JPEG_MAX_SIDE) return -1;
-  return geo_of(H, W).n_int;
+  return jpeg_sides_bad(H, W) ? -1 : geo_of(H, W).n_int;
 }
 
 extern "C" int msmd_jpeg_coefficients(const void* frames, long frame_stride, long row_stride, int pixel_stride, int B, int H,

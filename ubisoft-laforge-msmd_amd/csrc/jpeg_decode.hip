@@ -1,9 +1,9 @@
 // Baseline JPEG decoder, the inverse of jpeg.hip: B files of one size and sampling in one byte stream on the
-// device -> (B, H, W, 3 | 4) uint8.  The host has read the marker segments and found the restart intervals (ops.jpeg_parse);
+// device -> (B, H, W, 3 | 4) uint8.  The host has read the marker segments and found the restart intervals (jpeg_format.py);
 // here: (A) the entropy decode, one lane per (frame, interval), int16 coefficients per component plane in block-raster order;
 // (B) dequantise + inverse DCT per block, uint8 planes padded to whole blocks; (C) chroma upsampling and colour per output
 // pixel.  Integer arithmetic throughout, no global atomics but the OR into status[frame], nothing the host waits for.
-#include "common.h"
+#include "jpeg_common.h"
 
 namespace {
 
@@ -13,20 +13,10 @@ namespace {
 #define JD_HUFF_WORDS 96                                         // maxcode[16], delta[16], HUFFVAL[256]
 #define JD_IDCT_BLOCKS 32                                        // blocks per workgroup of (B): 8 lanes per block
 #define JD_THREADS 256
-#define JD_ROW 9                                                 // LDS row pitch of a staged block, as in the encoder
 static_assert(JD_TAB_WORDS == 2 + 4 * JD_HUFF_WORDS, "table set layout");
 static_assert(JD_LANES == 64, "one wave per workgroup of the entropy decode");
 
-// zig-zag position -> natural index (row * 8 + column)
-__constant__ unsigned char c_zz2nat[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                           41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                           30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
-// The encoder's table: M[k][n] = rint(2^15 c_k cos((2 n + 1) k pi / 16)) for n < 4; M[k][7 - n] = (-1)^k M[k][n].
-#define JD_M0 11585
-__device__ constexpr int kM[8][4] = {{JD_M0, JD_M0, JD_M0, JD_M0},   {16069, 13623, 9102, 3196},   {15137, 6270, -6270, -15137},
-                                     {13623, -3196, -16069, -9102}, {JD_M0, -JD_M0, -JD_M0, JD_M0}, {9102, -16069, 3196, 13623},
-                                     {6270, -15137, 15137, -6270},  {3196, -9102, 13623, -16069}};
+__constant__ Perm64 c_zz2nat = kZz2Nat;   // zig-zag position -> natural index (row * 8 + column)
 
 // Geometry of a frame.  Component 0 has hs x vs blocks per MCU, the others one; every index below is a compile-time constant
 // after unrolling, so the record lives in registers.
@@ -37,7 +27,7 @@ struct DecGeo {
   long base1, base2, blocks;   // first block of planes 1 and 2, blocks of a frame
 };
 __device__ __host__ __forceinline__ bool dec_geo(int H, int W, int layout, DecGeo* g) {
-  if (H < 1 || W < 1 || H > MSMD_JPEG_MAX_SIDE || W > MSMD_JPEG_MAX_SIDE || layout < MSMD_JPEG_GREY || layout > MSMD_JPEG_420) return false;
+  if (jpeg_sides_bad(H, W) || layout < MSMD_JPEG_GREY || layout > MSMD_JPEG_420) return false;
   g->ncomp = layout == MSMD_JPEG_GREY ? 1 : 3;
   g->hs = layout >= MSMD_JPEG_422 ? 2 : 1;
   g->vs = layout == MSMD_JPEG_420 ? 2 : 1;
@@ -184,30 +174,14 @@ __global__ __launch_bounds__(JD_LANES) void jpeg_entropy_kernel(const unsigned c
 }
 
 // ------------------------------------------------------------------------------------------------ (B) dequantise, inverse DCT
-// One 8-point pass of x = M^T F with the even / odd split: out[n] = e[n] + o[n], out[7 - n] = e[n] - o[n], e over the even k, o
-// over the odd ones (the same integers as the plain product: integer sums re-associate).
-template <typename In> __device__ __forceinline__ void idct8(const In* f, long* out) {
-#pragma unroll
-  for (int n = 0; n < 4; ++n) {
-    long e = 0, o = 0;
-#pragma unroll
-    for (int k = 0; k < 8; k += 2) {
-      e += (long)kM[k][n] * (long)f[k];
-      o += (long)kM[k + 1][n] * (long)f[k + 1];
-    }
-    out[n] = e + o;
-    out[7 - n] = e - o;
-  }
-}
-
 // 256 lanes = 32 blocks x 8.  Lane (block, r) loads zig-zag coefficients 8 r .. 8 r + 7 with one 16-byte load, multiplies by
 // Q and scatters F into the LDS block in natural order; pass 1 per (block, column) in int64 (< 2^40) into a second LDS block;
 // pass 2 per (block, row) in int64 (< 2^57); round, level shift, clamp; one 8-byte store of the row into the plane.
 __global__ __launch_bounds__(JD_THREADS) void jpeg_idct_kernel(const short* __restrict__ coef, const unsigned char* __restrict__ sets,
                                                                int n_sets, const int* __restrict__ frame_set, int B, int H, int W,
                                                                int layout, unsigned char* __restrict__ planes) {
-  __shared__ int s_f[JD_IDCT_BLOCKS * 8 * JD_ROW];
-  __shared__ long s_t[JD_IDCT_BLOCKS * 8 * JD_ROW];
+  __shared__ int s_f[JD_IDCT_BLOCKS * 8 * JPEG_ROW];
+  __shared__ long s_t[JD_IDCT_BLOCKS * 8 * JPEG_ROW];
   const int tid = threadIdx.x, blk = tid >> 3, r = tid & 7;
   DecGeo g;
   dec_geo(H, W, layout, &g);
@@ -217,8 +191,8 @@ __global__ __launch_bounds__(JD_THREADS) void jpeg_idct_kernel(const short* __re
   if (frame < B) set = frame_set[frame];
   const bool live = set >= 0 && set < n_sets;
   const int comp = g.ncomp == 1 ? 0 : (in_frame >= g.base1) + (in_frame >= g.base2);
-  int* f = s_f + blk * 8 * JD_ROW;
-  long* t = s_t + blk * 8 * JD_ROW;
+  int* f = s_f + blk * 8 * JPEG_ROW;
+  long* t = s_t + blk * 8 * JPEG_ROW;
   if (live) {
     const u32x4 c = *(const u32x4*)(coef + gb * 64 + r * 8);
     const u32x2 q = *(const u32x2*)(sets + (long)set * MSMD_JPEG_TABLE_SET_BYTES + comp * 64 + r * 8);
@@ -226,8 +200,8 @@ __global__ __launch_bounds__(JD_THREADS) void jpeg_idct_kernel(const short* __re
     for (int e = 0; e < 8; ++e) {
       const int cv = (int)(short)(c[e >> 1] >> (16 * (e & 1)));
       const int qv = (int)((q[e >> 2] >> (8 * (e & 3))) & 255u);
-      const int nat = c_zz2nat[r * 8 + e];
-      f[(nat >> 3) * JD_ROW + (nat & 7)] = cv * qv;
+      const int nat = c_zz2nat.v[r * 8 + e];
+      f[(nat >> 3) * JPEG_ROW + (nat & 7)] = cv * qv;
     }
   }
   __syncthreads();
@@ -235,16 +209,16 @@ __global__ __launch_bounds__(JD_THREADS) void jpeg_idct_kernel(const short* __re
     int col[8];
     long o[8];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) col[k] = f[k * JD_ROW + r];
+    for (int k = 0; k < 8; ++k) col[k] = f[k * JPEG_ROW + r];
     idct8<int>(col, o);
 #pragma unroll
-    for (int n = 0; n < 8; ++n) t[n * JD_ROW + r] = o[n];
+    for (int n = 0; n < 8; ++n) t[n * JPEG_ROW + r] = o[n];
   }
   __syncthreads();
   if (live) {                                                     // pass 2: row r, x[r][m] = sum_l t[r][l] M[l][m]
     long in[8], o[8];
 #pragma unroll
-    for (int l = 0; l < 8; ++l) in[l] = t[r * JD_ROW + l];
+    for (int l = 0; l < 8; ++l) in[l] = t[r * JPEG_ROW + l];
     idct8<long>(in, o);
     unsigned w[2] = {0u, 0u};
 #pragma unroll

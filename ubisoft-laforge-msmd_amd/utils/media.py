@@ -19,6 +19,7 @@ from typing import NamedTuple, Optional
 import numpy as np
 
 from .. import ops
+from ..jpeg_format import jpeg_dht
 
 AVI_MAX_BYTES = 2 ** 31 - 1
 _AVIF_HASINDEX, _AVIF_ISINTERLEAVED, _AVIIF_KEYFRAME = 0x10, 0x100, 0x10
@@ -307,11 +308,6 @@ def read_video(path, channels=3, chunk=256, device="cuda"):
     return out
 
 
-def _default_dht():
-    return b"".join(b"\xff\xc4" + struct.pack(">H", 19 + len(vals)) + bytes((cls << 4 | tid,)) + bits + vals
-                    for cls, tid, bits, vals in ops.JPEG_HUFFMAN)
-
-
 def extract_frames(filename, output_dir, quality=1):
     """The reference helper's name and argument order (utils/media.py: ffmpeg writes `%06d.jpg` from 0): the frames of a
     Motion-JPEG AVI as JPEG files in `output_dir`.  Nothing is decoded or re-encoded: a file is the frame's chunk as it stands in
@@ -326,7 +322,7 @@ def extract_frames(filename, output_dir, quality=1):
         header = ops.jpeg_parse(raw)[0]
         if header["default_huffman"]:
             sos = header["scan"][0] - 8 - 2 * header["components"]
-            raw = raw[:sos] + _default_dht() + raw[sos:]
+            raw = raw[:sos] + jpeg_dht() + raw[sos:]
         p = os.path.join(os.fspath(output_dir), "%06d.jpg" % k)
         with open(p, "wb") as fh:
             fh.write(raw)
