@@ -308,10 +308,12 @@ int msmd_pad_audio(const float* audio, float* out, int B, int L, int reflect_len
 /* conv0 (1->C, k=10, s=5, no bias) statistics for GroupNorm(C groups): stats (B, C, 2) = {mean, rstd}
  * over the T0 = (Lp - 10)/5 + 1 output frames, reading the UNPADDED audio through the pad map.
  * w0: (C, 10) fp32.  Replaces HF Wav2Vec2GroupNormConvLayer (called at utils/wav2vec2.py:79). */
-#define MSMD_CONV0_SPLITS 16 /* ws: (B, MSMD_CONV0_SPLITS, 66) fp32 partial signal moments (sum, S[10], R[55]); at least
-                              * B*16*66 floats.  The conv response is linear in the signal, so per-channel mean / variance
+#define MSMD_CONV0_SPLITS 16 /* ws: (B, MSMD_CONV0_SPLITS, 66) fp64 partial signal moments (shift, S[10], R[55]); at least
+                              * B*16*66 doubles.  The conv response is linear in the signal, so per-channel mean / variance
                               * follow from these 66 numbers per clip. */
-int msmd_conv0_stats(const float* audio, const float* w0, float* stats, float* ws, int B, int L, int reflect_len,
+/* Returns 1 (nothing launched) for reflect_len < 0, replicate_len < 0, reflect_len >= L or no output frame, as
+ * msmd_pad_audio does; so do msmd_conv0_gn_gelu and msmd_conv0_ln_gelu. */
+int msmd_conv0_stats(const float* audio, const float* w0, float* stats, double* ws, int B, int L, int reflect_len,
                      int replicate_len, int C, float eps, msmd_stream_t stream);
 
 /* out (B, T0, C) = GELU(GroupNorm(conv0(pad(audio)))) with the statistics above. */

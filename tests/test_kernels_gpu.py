@@ -1143,6 +1143,26 @@ def _unknown_dtype_cases():
         y = out(1, 7, 512)
         return lib.msmd_conv0_ln_gelu(P(inp(1, 40)), P(inp(512, 10)), None, P(inp(512)), P(inp(512)), P(y), 1, 40, 0, 0, 512, 1e-5, *c, st), [y]
 
+    # The conv0 entries fuse pad_audio into their loads and refuse what msmd_pad_audio refuses.  Here the "codes" are
+    # (L, reflect_len, replicate_len) with a valid storage type: negative lengths, reflect_len >= L (the pad map would
+    # index outside the clip), and a padded clip shorter than one 10-sample window (no output frame).
+    geometry = [(40, -1, 0), (40, 0, -1), (40, 40, 0), (40, 45, 0), (9, 0, 0), (3, 1, 1)]
+
+    @case("msmd_conv0_stats[geometry]", geometry)
+    def _(lib, st, c):
+        stats, ws = out(1, 8, 2), out(1, 16, 132)
+        return lib.msmd_conv0_stats(P(inp(1, 40)), P(inp(8, 10)), P(stats), P(ws), 1, *c, 8, 1e-5, st), [stats, ws]
+
+    @case("msmd_conv0_gn_gelu[geometry]", geometry)
+    def _(lib, st, c):
+        y = out(1, 64, 8)
+        return lib.msmd_conv0_gn_gelu(P(inp(1, 40)), P(inp(8, 10)), P(inp(1, 8, 2)), P(inp(8)), P(inp(8)), P(y), 1, *c, 8, 0, st), [y]
+
+    @case("msmd_conv0_ln_gelu[geometry]", geometry)
+    def _(lib, st, c):
+        y = out(1, 64, 512)
+        return lib.msmd_conv0_ln_gelu(P(inp(1, 40)), P(inp(512, 10)), None, P(inp(512)), P(inp(512)), P(y), 1, *c, 512, 1e-5, 0, st), [y]
+
     @case("msmd_interp_linear", one)
     def _(lib, st, c):
         y = out(1, 6, 8)
@@ -1223,7 +1243,8 @@ _UNKNOWN_DTYPE_EXEMPT = {}
 def test_unknown_dtype_codes_are_refused_and_nothing_is_written():
     """A storage-type code outside an entry's type list (7: no type; 3: MSMD_F16X2 where the entry has no split form; for the
     converting entries one 16-bit type into the other) returns non-zero and launches nothing: every output keeps its
-    sentinel.  Called on the library directly: ops._dt() would not produce most of these codes."""
+    sentinel.  Called on the library directly: ops._dt() would not produce most of these codes.  The [geometry] rows do the
+    same for the pad lengths the conv0 entries must refuse."""
     from msmd_amd import _lib
     lib = _lib.load()
     st = torch.cuda.current_stream().cuda_stream

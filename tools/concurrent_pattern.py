@@ -25,7 +25,7 @@ def fn(i):
     if which == "stats":
         from msmd_amd import ops
         B, L = bs[i]["audio"].shape
-        st = torch.empty(B, 512, 2, device="cuda"); ws = torch.empty(B, ops.CONV0_SPLITS, 66, device="cuda")
+        st = torch.empty(B, 512, 2, device="cuda"); ws = ops.conv0_workspace(B, "cuda")
         from msmd_amd import _lib
         _lib.check(_lib.load().msmd_conv0_stats(bs[i]["audio"].data_ptr(), FE["w0"].data_ptr(), st.data_ptr(), ws.data_ptr(), B, L, r_, rep_, 512, 1e-5,
                                                 torch.cuda.current_stream().cuda_stream), "stats")

@@ -34,6 +34,18 @@ extern "C" int msmd_pad_audio(const float* audio, float* out, int B, int L, int 
   MSMD_RETURN_LAST();
 }
 
+#define C0_K 10
+#define C0_S 5
+#define C0_SPLITS 16
+#define C0_NMOM 66  // 1 (sum x) + 10 (S) + 55 (upper triangle of R)
+
+// The conv0 entries fuse pad_audio into their signal loads: the same argument check as msmd_pad_audio (pad_src reflects
+// once per stage, so reflect_len >= L would index outside the clip), and at least one output frame.
+static bool conv0_geometry_ok(int B, int L, int reflect_len, int replicate_len) {
+  if (B <= 0 || L <= 0 || reflect_len < 0 || replicate_len < 0 || reflect_len >= L) return false;
+  return (long)L + 4L * reflect_len + 2L * replicate_len >= C0_K;
+}
+
 // ---------------------------------------------------------------------------------------------------
 // conv0 statistics for GroupNorm(C groups, C channels) WITHOUT evaluating the conv per channel:
 // y_c[t] = sum_k w_c[k] x[5t+k] is linear in x, so over the T0 frames of a clip
@@ -41,34 +53,35 @@ extern "C" int msmd_pad_audio(const float* audio, float* out, int B, int L, int 
 //   sum_t y_c^2   = w_c^T R w_c      R[k][k'] = sum_t xc[5t+k] xc[5t+k']      (10 + 55 numbers per clip)
 // with xc = x - mu the clip-centred signal (a constant shift leaves the variance unchanged and removes the
 // E[y^2] - mean^2 cancellation for signals with a DC offset).  190x fewer FLOPs than the direct form; the
-// partial sums are fp32 per thread over <= 64 frames, then fp64 across threads/splits.
-#define C0_K 10
-#define C0_S 5
-#define C0_SPLITS 16
-#define C0_NMOM 66  // 1 (sum x) + 10 (S) + 55 (upper triangle of R)
+// partial sums are fp32 per thread over <= 64 frames, then fp64 across threads and splits: the workspace holds doubles.
+// w_c^T R w_c cancels on its own for a channel whose taps sum to about zero over a clip with a step in it (R is then
+// nearly rank one and large, the channel's variance the small remainder), so a split total rounded to fp32 costs that
+// channel 2^-24 x the condition number: 8.6e-5 on a normalised value for a clip of 400 zeros, then DC 0.5 + noise 0.01.
 
-__global__ __launch_bounds__(256) void conv0_moments_partial(const float* __restrict__ audio, float* __restrict__ ws,
+__global__ __launch_bounds__(256) void conv0_moments_partial(const float* __restrict__ audio, double* __restrict__ ws,
                                                              int L, int r, int rep, int T0, int pass) {
   // ws[b][split][0] = the shift mu; [1..] = S and R of the shifted signal over this split's frames.
   __shared__ double red[4][C0_NMOM];
   const int b = blockIdx.y, split = blockIdx.x;
   const int per = (T0 + C0_SPLITS - 1) / C0_SPLITS;
   const int t_begin = split * per, t_end = min(T0, t_begin + per);
-  float* out = ws + ((long)b * C0_SPLITS + split) * C0_NMOM;
+  double* out = ws + ((long)b * C0_SPLITS + split) * C0_NMOM;
   const float* xa = audio + (long)b * L;
-  // Centre of the moments: the mean of the clip's first min(256, n) padded samples, computed by EVERY block in the same
-  // order (all splits of a clip must shift by the same constant; any constant near the mean removes the
-  // E[y^2] - mean^2 cancellation, the finish kernel's algebra is exact for whatever shift was used).  One launch instead
-  // of the former mean pass + moments pass.
+  // Centre of the moments: the mean of min(256, n) padded samples spread evenly over the n the frames use (a clip that
+  // starts with silence has its mean elsewhere), computed by EVERY block in the same order (all splits of a clip must
+  // shift by the same constant; any constant near the mean removes the E[y^2] - mean^2 cancellation, the finish kernel's
+  // algebra is exact for whatever shift was used).  One launch instead of the former mean pass + moments pass.
   const int n_used = T0 * C0_S + C0_K - C0_S;
+  const int n_mu = min(256, n_used);
   {
-    double v = threadIdx.x < min(256, n_used) ? (double)xa[pad_src(threadIdx.x, L, r, rep)] : 0.0;
+    const int j = (int)(((long)threadIdx.x * n_used) / n_mu);      // < n_used for threadIdx.x < n_mu
+    double v = threadIdx.x < n_mu ? (double)xa[pad_src(j, L, r, rep)] : 0.0;
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][0] = v;
     __syncthreads();
   }
-  const float mu = (float)((red[0][0] + red[1][0] + red[2][0] + red[3][0]) / (double)min(256, n_used));
-  if (threadIdx.x == 0) out[0] = mu;
+  const float mu = (float)((red[0][0] + red[1][0] + red[2][0] + red[3][0]) / (double)n_mu);
+  if (threadIdx.x == 0) out[0] = (double)mu;
   float m[C0_NMOM];
 #pragma unroll
   for (int i = 0; i < C0_NMOM; ++i) m[i] = 0.f;
@@ -94,22 +107,22 @@ __global__ __launch_bounds__(256) void conv0_moments_partial(const float* __rest
   }
   __syncthreads();
   if (threadIdx.x >= 1 && threadIdx.x < C0_NMOM)
-    out[threadIdx.x] = (float)(red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x]);
+    out[threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
 }
 
-__global__ void conv0_stats_finish(const float* __restrict__ ws, const float* __restrict__ w0,
+__global__ void conv0_stats_finish(const double* __restrict__ ws, const float* __restrict__ w0,
                                    float* __restrict__ stats, int C, int T0, float eps) {
   __shared__ double mom[C0_NMOM];
   const int b = blockIdx.y;
   if (threadIdx.x < C0_NMOM) {
     double v = 0.0;
-    for (int s = 0; s < C0_SPLITS; ++s) v += (double)ws[((long)b * C0_SPLITS + s) * C0_NMOM + threadIdx.x];
+    for (int s = 0; s < C0_SPLITS; ++s) v += ws[((long)b * C0_SPLITS + s) * C0_NMOM + threadIdx.x];
     mom[threadIdx.x] = v;
   }
   __syncthreads();
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
-  const double mu = (double)ws[(long)b * C0_SPLITS * C0_NMOM];      // the shift every split used
+  const double mu = ws[(long)b * C0_SPLITS * C0_NMOM];              // the shift every split used
   double w[C0_K], wsum = 0.0, ws1 = 0.0, q = 0.0;
   for (int k = 0; k < C0_K; ++k) { w[k] = (double)w0[c * C0_K + k]; wsum += w[k]; ws1 += w[k] * mom[1 + k]; }
   int idx = 1 + C0_K;
@@ -121,12 +134,11 @@ __global__ void conv0_stats_finish(const float* __restrict__ ws, const float* __
   stats[((long)b * C + c) * 2 + 1] = (float)(1.0 / sqrt(fmax(var, 0.0) + (double)eps));
 }
 
-extern "C" int msmd_conv0_stats(const float* audio, const float* w0, float* stats, float* ws, int B, int L,
+extern "C" int msmd_conv0_stats(const float* audio, const float* w0, float* stats, double* ws, int B, int L,
                                 int reflect_len, int replicate_len, int C, float eps, msmd_stream_t stream) {
-  if (B <= 0 || L <= 0 || C <= 0 || !ws) return 1;
+  if (!conv0_geometry_ok(B, L, reflect_len, replicate_len) || C <= 0 || !ws) return 1;
   const int Lp = L + 4 * reflect_len + 2 * replicate_len;
   const int T0 = (Lp - C0_K) / C0_S + 1;
-  if (T0 <= 0) return 1;
   hipStream_t st = (hipStream_t)stream;
   dim3 grid(C0_SPLITS, B);
   hipLaunchKernelGGL(conv0_moments_partial, grid, dim3(256), 0, st, audio, ws, L, reflect_len, replicate_len, T0, 1);
@@ -215,8 +227,24 @@ __global__ __launch_bounds__(256) void conv0_mfma_kernel(const float* __restrict
   const int nt = min(FR, T0 - t0);
   const int ns = nt * C0_S + (C0_K - C0_S);
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  for (int i = tid; i < ns; i += 256) xs[i] = audio[(long)b * L + pad_src(t0 * C0_S + i, L, r, rep)];
+  float amax = 0.f;
+  for (int i = tid; i < ns; i += 256) {
+    const float x = audio[(long)b * L + pad_src(t0 * C0_S + i, L, r, rep)];
+    xs[i] = x;
+    amax = fmaxf(amax, fabsf(x));
+  }
   for (int i = ns + tid; i < FR * C0_S + C0_K; i += 256) xs[i] = 0.f;
+  // The signal is split after an exact power-of-two scale that puts this block's largest sample in [2^10, 2^11), and the
+  // per-channel scale carries the inverse: the fp16 halves of a quiet recording (one LSB of 16-bit noise is 3e-5: xh and
+  // xl both subnormal, 1e-3 relative on every sample) keep their bits, and every other clip's result keeps its bits.
+  __shared__ float amax_w[4];
+  amax = wave_max(amax);
+  if (lane == 0) amax_w[wid] = amax;
+  __syncthreads();
+  amax = fmaxf(fmaxf(amax_w[0], amax_w[1]), fmaxf(amax_w[2], amax_w[3]));
+  const int aexp = (__float_as_int(amax) >> 23) & 0xff;          // biased exponent: 0 for silence, 255 for inf
+  const int shift = (aexp == 0 || aexp == 255) ? 0 : max(-100, min(100, 10 - (aexp - 127)));
+  const float xscale = __int_as_float((127 + shift) << 23), xinv = __int_as_float((127 - shift) << 23);
   // weight image: image row R = 16 j + rho (fragment j, operand row rho = 4 q + e) holds channel
   //   32 (j / 2) + 8 q + 4 (j & 1) + e
   for (int R = tid; R < C; R += 256) {
@@ -238,7 +266,7 @@ __global__ __launch_bounds__(256) void conv0_mfma_kernel(const float* __restrict
   for (int c = tid; c < C; c += 256) {
     const float mean = stats[((long)b * C + c) * 2], rstd = stats[((long)b * C + c) * 2 + 1];
     const float sc = rstd * gamma[c];
-    ssc[c] = sc;
+    ssc[c] = sc * xinv;
     ssh[c] = beta[c] - mean * sc;
   }
   __syncthreads();
@@ -252,7 +280,7 @@ __global__ __launch_bounds__(256) void conv0_mfma_kernel(const float* __restrict
     TO xh[C0_K], xl[C0_K];
 #pragma unroll
     for (int k = 0; k < C0_K; ++k) {
-      const float x = xp[k];
+      const float x = xp[k] * xscale;
       xh[k] = (TO)x;
       xl[k] = (TO)(x - (float)xh[k]);
     }
@@ -290,7 +318,7 @@ __global__ __launch_bounds__(256) void conv0_mfma_kernel(const float* __restrict
 extern "C" int msmd_conv0_gn_gelu(const float* audio, const float* w0, const float* stats, const float* gamma,
                                   const float* beta, void* out, int B, int L, int reflect_len, int replicate_len,
                                   int C, int out_dtype, msmd_stream_t stream) {
-  if (B <= 0 || L <= 0 || C <= 0 || (C & 7)) return 1;
+  if (!conv0_geometry_ok(B, L, reflect_len, replicate_len) || C <= 0 || (C & 7)) return 1;
   const int Lp = L + 4 * reflect_len + 2 * replicate_len;
   const int T0 = (Lp - C0_K) / C0_S + 1;
   dim3 grid((T0 + 63) / 64, B), block(256);
@@ -384,7 +412,7 @@ __global__ __launch_bounds__(256) void conv0_ln_gelu_kernel(const float* __restr
 extern "C" int msmd_conv0_ln_gelu(const float* audio, const float* w0, const float* bias, const float* gamma,
                                   const float* beta, void* out, int B, int L, int reflect_len, int replicate_len,
                                   int C, float eps, int out_dtype, msmd_stream_t stream) {
-  if (B <= 0 || L <= 0 || C != 512) return 1;
+  if (!conv0_geometry_ok(B, L, reflect_len, replicate_len) || C != 512) return 1;
   const int Lp = L + 4 * reflect_len + 2 * replicate_len;
   const int T0 = (Lp - C0_K) / C0_S + 1;
   dim3 grid((T0 + 63) / 64, B), block(256);
@@ -413,8 +441,13 @@ __global__ void interp_linear_kernel(const T* __restrict__ x, T* __restrict__ y,
   const T* p0 = x + ((long)b * T_in + i0) * C;
   const T* p1 = x + ((long)b * T_in + i1) * C;
   T* q = y + ((long)b * T_out + j) * C;
-  for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < C; c += gridDim.x * blockDim.x)
-    q[c] = from_f32<T>(w0 * to_f32(p0[c]) + w1 * to_f32(p1[c]));
+  // each product and the sum rounded on their own, as oracle/nn.py:interp_linear_cl computes them: left to the compiler
+  // this contracts to mul + fma, one ulp away from the oracle wherever the weights are not 0 / 0.5 / 1
+  for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < C; c += gridDim.x * blockDim.x) {
+#pragma clang fp contract(off)
+    const float a0 = w0 * to_f32(p0[c]), a1 = w1 * to_f32(p1[c]);
+    q[c] = from_f32<T>(a0 + a1);
+  }
 }
 
 extern "C" int msmd_interp_linear(const void* x, void* y, int B, int T_in, int T_crop, int T_out, int C, int dtype,

@@ -605,6 +605,11 @@ def pad_audio(audio, reflect_len, replicate_len):
     return out
 
 
+def conv0_workspace(B, device):
+    """the moment workspace of msmd_conv0_stats: (B, CONV0_SPLITS, 66) doubles"""
+    return torch.empty(B, CONV0_SPLITS, 66, device=device, dtype=torch.float64)
+
+
 def conv0_gn_gelu(audio, w0, gamma, beta, reflect_len, replicate_len, out_dtype, eps=1e-5):
     """GELU(GroupNorm(conv0(pad_audio(audio)))) -> (B, T0, C) channels-last."""
     lib = _lib.load()
@@ -613,7 +618,7 @@ def conv0_gn_gelu(audio, w0, gamma, beta, reflect_len, replicate_len, out_dtype,
     Lp = L + 4 * reflect_len + 2 * replicate_len
     T0 = (Lp - 10) // 5 + 1
     stats = torch.empty(B, C, 2, device=audio.device, dtype=torch.float32)
-    ws = torch.empty(B, CONV0_SPLITS, 66, device=audio.device, dtype=torch.float32)
+    ws = conv0_workspace(B, audio.device)
     _lib.check(lib.msmd_conv0_stats(_p(audio), _p(w0), _p(stats), _p(ws), B, L, reflect_len, replicate_len, C, eps,
                                     _stream()), "msmd_conv0_stats")
     out = empty((B, T0, C), audio.device, out_dtype)
