@@ -148,6 +148,41 @@ int msmd_gemm_ln_rows(const void* A, const void* W, const float* bias, const voi
                       const float* w_colsum, const float* r_stats, const float* r_gamma, const float* r_beta,
                       float* stats_out, int slab_in, int slab_out, float eps, msmd_stream_t stream);
 
+/* A stack of 2 to 4 strided Conv1d layers (+ bias + activation) over a channels-last 16-bit signal as ONE launch of the 256 x 256
+ * kernel (variant 80's K loop and epilogue): layer l is the windowed GEMM msmd_gemm would run for it -- M = B * T_l rows, N outputs,
+ * K = kernel[l] * channels in -- and reads layer l - 1's output while other workgroups are still writing later rows of it.  Tiles
+ * are handed out by one ticket counter, layer after layer and row block after row block, so a tile only ever waits for tiles with
+ * a lower ticket; row-block counters say when a tile's input rows are complete.  Every layer's output holds the
+ * bits msmd_gemm stores for the same layer.
+ *   x (B, T0, C); layer l: w[l] (N, kernel[l] * C_l) with C_0 = C, C_l = N; bias[l] fp32 (N) or NULL; out[l] (B, T_l, N),
+ *   T_l = (T_{l-1} - kernel[l]) / stride[l] + 1.  w / bias / out / kernel / stride are HOST arrays of n_layers entries (the only
+ *   host pointers of this header); what they point to is device memory.  act: MSMD_ACT_NONE or MSMD_ACT_GELU, every layer's.
+ *   workspace: msmd_conv_chain_workspace() bytes of device memory, 16-byte aligned, zeroed by a launch this call puts on the
+ *   stream ahead of the kernel.  max_workgroups: 0 = one workgroup per CU, else a smaller grid (tests).
+ *   flags: MSMD_CONV_CHAIN_RELEASE = rows that a later layer reads are stored plainly and published by one agent-scope release
+ *   per tile, instead of write-through stores; MSMD_CONV_CHAIN_ROW_BLOCK_TICKETS = a ticket is a row block with all its column
+ *   tiles, instead of one tile.  Neither changes what is stored.
+ * Returns 1, having launched nothing, for what the kernel does not take: N % 256 != 0, a K % 64 != 0 or K < 128, a dtype other
+ * than MSMD_BF16 / MSMD_F16, operand offsets past 4 GB, fewer than 2 or more than 4 layers, 2^24 rows or more in a layer; the
+ * caller then runs the layers as msmd_gemm calls.
+ * msmd_conv_chain_plan: the kernel's own ticket arithmetic on the host (no HIP call): out6 = (layer, row block, first column tile,
+ *   column tiles, first and last row block of layer - 1 that must be complete; the last two 0, -1 for layer 0); returns 0, the
+ *   ticket count for a ticket past the last one, -1 for shapes the kernel does not take.
+ * msmd_conv_chain_status: a BLOCKING read of the launch's status word, 0 or MSMD_CONV_CHAIN_TIMEOUT (a wait for a producer took
+ *   longer than 20 ms of wall clock: the workgroup stopped taking tickets and returned); -1 where the copy failed.  For tests
+ *   and tools, never on a timed path.
+ * Replaces conv_layers[1..4] of HF Wav2Vec2FeatureEncoder (reference utils/wav2vec2.py:79, the nn.Conv1d + GELU modules). */
+#define MSMD_CONV_CHAIN_RELEASE 1
+#define MSMD_CONV_CHAIN_ROW_BLOCK_TICKETS 2
+#define MSMD_CONV_CHAIN_TIMEOUT 1
+int msmd_conv_chain(const void* x, int B, int T0, int C, int N, int n_layers, const void* const* w, const float* const* bias,
+                    void* const* out, const int* kernel, const int* stride, int act, int dtype, void* workspace,
+                    long workspace_bytes, int max_workgroups, int flags, msmd_stream_t stream);
+long msmd_conv_chain_workspace(int B, int T0, int C, int N, int n_layers, const int* kernel, const int* stride);
+int msmd_conv_chain_plan(int B, int T0, int C, int N, int n_layers, const int* kernel, const int* stride, int flags, int ticket,
+                         int* out6);
+int msmd_conv_chain_status(const void* workspace);
+
 /* Two-level batched GEMM C[zo][zi] = A[zo][zi] . W[zo][zi]^T (no bias / residual / activation): operand z =
  * zo * batch_inner + zi starts at base + zo * stride_o + zi * stride_i.  Used by the explicit (materialised-P)
  * training attention, where zo = batch and zi = head index into packed (B, T, H*64) tensors. */

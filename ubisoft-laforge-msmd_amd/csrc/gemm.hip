@@ -1158,8 +1158,62 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm2s_kernel(const GemmArgs p) 
 // ONE sum in units of 2^-11 (AL / WL = the stored lo planes, already x 2^11), scaled back in the epilogue: 16 vector
 // instructions per K tile instead of 128, one accumulator set, the matrix pipe 11-17 % busier (conv1 875 -> 779 us, QKV 81 ->
 // 68, same box).  LayerNorm forms are not built for it (the split path runs LayerNorm as its own kernel): EPI = 1 only.
-template <typename TI, int EPIA, int SPLIT = 0>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void gemm8_kernel(const GemmArgs p) {
+//
+// CHAIN (msmd_conv_chain): the same K loop and epilogue walk the tiles of 2 to 4 problems, problem l's A being problem
+// l - 1's C, in ONE launch.  Tiles are taken by TICKET from one global counter, problem-major and row-block ascending, so a
+// workgroup only ever waits for tiles with a lower ticket, which a running workgroup already holds: the launch makes progress
+// with any number of resident workgroups.  A finished tile adds one to its row block's counter (the hand-over of
+// cdna_hip_programming.md Guideline 16: every storing wave drains, barrier, one lane signals); a consumer tile needs the
+// counters of the producer row blocks its windows read at `nt`.  The next ticket is claimed in K tile nk - 2 and its counters are
+// read under the last K tile: when they are already full (the producers ran rounds earlier) wave 0 acquires before the barrier
+// that ends the K loop and the next tile's first K tile is staged under this tile's epilogue as in the plain kernel; else the
+// workgroup waits behind its epilogue, W staged, A not.  Every wait is bounded by CHAIN_WAIT_TICKS of the 100 MHz clock.
+struct ChainProblem {
+  const void* A; const void* W; const float* bias; void* C;
+  long lda, a_batch_stride;      // elements, as GemmArgs
+  int M, rows_per_batch, K, mt;
+  int t_in, stride, taps;        // rows per clip of A (= the producer's C), window step and length in rows
+  int ticket0, cnt0;             // the problem's first ticket; its first row-block counter in the state block
+  float inv_rpb;
+};
+struct ChainTable {
+  ChainProblem pr[4];
+  unsigned* state;               // [0] ticket counter, [1] status, [CHAIN_STATE_HEAD + cnt0 + row block] finished column tiles
+  int n, nt, per_block, total;   // problems; column tiles; 1 = a ticket is a row block (all its column tiles), 0 = one tile; tickets
+  int release;                   // 1 = plain stores + one agent-scope release per tile, 0 = write-through stores
+};
+struct NoChain : ChainTable {};      // the plain kernel: an empty table nothing reads (the chain statements are discarded there)
+struct ChainTile { int l, rb, ct, nct, pb0, pb1; };      // problem, row block, first column tile and their number, producer row blocks
+constexpr int CHAIN_STATE_HEAD = 4;
+constexpr long CHAIN_WAIT_TICKS = 2000000;      // 20 ms per wait (more than 10 x the whole launch at the bench shape)
+
+// ticket -> tile and the producer row blocks it reads (host and device: msmd_conv_chain_plan is this function)
+__host__ __device__ inline bool chain_decode(const ChainTable& t, int ticket, ChainTile& o) {
+  if (ticket < 0 || ticket >= t.total) return false;
+  int l = 0;
+  for (int i = 1; i < t.n; ++i)
+    if (ticket >= t.pr[i].ticket0) l = i;
+  const ChainProblem& q = t.pr[l];
+  const int local = ticket - q.ticket0;
+  o.l = l; o.pb0 = 0; o.pb1 = -1;
+  if (t.per_block) { o.rb = local; o.ct = 0; o.nct = t.nt; }
+  else { o.rb = local / t.nt; o.ct = local - o.rb * t.nt; o.nct = 1; }
+  if (l > 0) {
+    // rows r0 .. r1 of this problem read the rows [first row of r0's window, last tap of r1's window] of the producer's output,
+    // clip after clip: every row block in between, whole clips included
+    const int r0 = o.rb * 256, r1 = (r0 + 255 < q.M ? r0 + 255 : q.M - 1);
+    const int q0 = r0 / q.rows_per_batch, q1 = r1 / q.rows_per_batch;
+    const int first = q0 * q.t_in + (r0 - q0 * q.rows_per_batch) * q.stride;
+    const int last = q1 * q.t_in + (r1 - q1 * q.rows_per_batch) * q.stride + q.taps - 1;
+    o.pb0 = first >> 8; o.pb1 = last >> 8;
+  }
+  return true;
+}
+
+template <typename TI, int EPIA, int SPLIT, typename PA, typename CH>
+__device__ __forceinline__ void gemm8_body(PA& p, const CH& ch) {
+  constexpr bool CHAIN = !std::is_same_v<CH, NoChain>;
+  static_assert(!CHAIN || (SPLIT == 0 && epia_family(EPIA) == EPI_PLAIN), "the chained form: 16-bit operands, plain epilogue");
   typedef typename std::conditional<(SPLIT & 3) == 2, float, TI>::type TO;
   constexpr bool WS = (SPLIT & 4) != 0;   // W's hi plane scaled in registers, single accumulator
   constexpr int EPI = epia_family(EPIA), ACTK = epia_act(EPIA);
@@ -1178,11 +1232,60 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   const int run_n = (ntiles >> 3) + (xcd < (ntiles & 7) ? 1 : 0);
   const int stride = (nwg >> 3) + (xcd < (nwg & 7) ? 1 : 0);
   int tl = pid >> 3;                     // position in the XCD's run
-  const bf16_t* __restrict__ A = (const bf16_t*)p.A;
-  const bf16_t* __restrict__ W = (const bf16_t*)p.W;
+  const bf16_t* A = (const bf16_t*)p.A;
+  const bf16_t* W = (const bf16_t*)p.W;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wid >> 2, wc = wid & 3;
+
+  // CHAIN: the tile this workgroup takes next (cz), what is left of its ticket, and the mailbox behind the ring through which wave 0
+  // tells the workgroup the ticket it claimed ([0], -1 = none left or a wait expired) and whether its producers are done ([1])
+  ChainTile cz{};
+  int c_left = 0;
+  volatile int* mbox = (volatile int*)(smem + 2 * BUF);
+  unsigned c_claim = 0, c_cnt = 0;       // wave 0: the claimed ticket (lane 0), the counters of its producer row blocks (one per lane)
+  // the problem of tile cz: the operands the staging reads (the epilogue of the tile before keeps its own copies)
+  auto chain_problem = [&]() {
+    if constexpr (CHAIN) {
+      const ChainProblem& q = ch.pr[cz.l];
+      p.A = q.A; p.W = q.W; p.bias = q.bias; p.C = q.C; p.M = q.M; p.K = q.K; p.ldw = q.K;
+      p.lda = q.lda; p.a_batch_stride = q.a_batch_stride; p.rows_per_batch = q.rows_per_batch; p.inv_rpb = q.inv_rpb;
+      A = (const bf16_t*)q.A; W = (const bf16_t*)q.W;
+    }
+  };
+  // all of wave 0: are the producer row blocks of cz finished (counters at nt)?  Relaxed loads, one counter per lane.
+  auto chain_counters = [&](const ChainTile& z) -> unsigned {
+    unsigned c = ~0u;
+    if constexpr (CHAIN) {
+      if (z.l > 0) {
+        const unsigned* cnt = ch.state + CHAIN_STATE_HEAD + ch.pr[z.l - 1].cnt0;
+        c = (unsigned)ch.nt;
+        for (int b = z.pb0 + lane; b <= z.pb1; b += 64) {
+          const unsigned v = __hip_atomic_load(cnt + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          c = v < c ? v : c;
+        }
+      }
+    }
+    return c;
+  };
+  // all of wave 0, behind the epilogue: poll until they are, bounded by wall clock; then ONE agent-scope acquire, drained, ahead of the
+  // workgroup's barrier.  False: the wait expired (status word set).
+  auto chain_wait = [&](const ChainTile& z) -> bool {
+    if constexpr (CHAIN) {
+      if (z.l == 0) return true;
+      const long t0 = (long)__builtin_amdgcn_s_memrealtime();
+      while (!__all(chain_counters(z) >= (unsigned)ch.nt)) {
+        if ((long)__builtin_amdgcn_s_memrealtime() - t0 > CHAIN_WAIT_TICKS) {
+          if (lane == 0) __hip_atomic_store(ch.state + 1, (unsigned)MSMD_CONV_CHAIN_TIMEOUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          return false;
+        }
+        __builtin_amdgcn_s_sleep(8);
+      }
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    return true;
+  };
 
   // LDS-DMA sources: piece i (0, 1) of this wave inside a half-tile is its 1 KB chunk i * 8 + wid = rows 8 chunk .. + 7
   unsigned src[4][2];        // [X0 X1 W0 W1][piece]: byte offsets from A / W (the launcher refuses operands past 4 GB)
@@ -1191,8 +1294,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   // lane id the compiler cannot match, so that the eight pointers are not kept across the epilogue: with the 128 accumulators
   // and the epilogue's rows live they were the spill)
   auto set_tile = [&](int t) {
-    const int m_tile = (run0 + t) / p.nt, n_tile = (run0 + t) - m_tile * p.nt;
-    m0 = m_tile * 256; n0 = n_tile * 256;
+    if constexpr (CHAIN) { m0 = cz.rb * 256; n0 = cz.ct * 256; }
+    else {
+      const int m_tile = (run0 + t) / p.nt, n_tile = (run0 + t) - m_tile * p.nt;
+      m0 = m_tile * 256; n0 = n_tile * 256;
+    }
     int ln = lane;
     asm volatile("" : "+v"(ln));
 #pragma unroll
@@ -1337,11 +1443,27 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
   };
 
-  const int nk = p.K / (SPLIT ? 32 : 64);       // K tiles of 128 bytes per operand row
+  int nk = p.K / (SPLIT ? 32 : 64);       // K tiles of 128 bytes per operand row (CHAIN: of the problem of the tile in the K loop)
   typedef typename Vec4T<TO>::type V4;
   const bool has_r = p.R != nullptr;
   const bool wt = p.flags & GF_WRITE_THROUGH;     // write-through stores (MSMD_GEMM_WRITE_THROUGH): the rows leave the L2 as they are stored
 
+  if constexpr (CHAIN) {
+    // the first ticket: claimed, and waited for where it has producers (a grid larger than the first problem), before anything is staged
+    if (wid == 0) {
+      if (lane == 0) c_claim = __hip_atomic_fetch_add(ch.state, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const int tk = __builtin_amdgcn_readfirstlane((int)c_claim);
+      const bool ok = chain_decode(ch, tk, cz) && chain_wait(cz);
+      if (lane == 0) mbox[0] = ok ? tk : -1;
+    }
+    __syncthreads();
+    const int tk = __builtin_amdgcn_readfirstlane(mbox[0]);
+    if (tk < 0) return;
+    chain_decode(ch, tk, cz);
+    c_left = cz.nct - 1;
+    chain_problem();
+    nk = p.K / 64;
+  }
   // prologue of the first tile: K tile 0 whole, K tile 1 except X1 (which phase 1 of tile 0 stages)
   set_tile(tl);
   ln_request();
@@ -1364,6 +1486,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // MODE 0: steady state; 1: K tile nk - 2 (only X1 of the last tile is left to stage); 2: the last K tile
     auto ktile = [&](int t, auto MODE_) {
       constexpr int MODE = decltype(MODE_)::value;
+      if constexpr (CHAIN && MODE == 1) {
+        // the next ticket: asked for here, three phases ahead of this K tile's vmcnt(0)
+        if (wid == 0 && c_left == 0 && lane == 0) c_claim = __hip_atomic_fetch_add(ch.state, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
       // ---- phase 1
       read_w(0, fw0);
       __builtin_amdgcn_sched_barrier(0);
@@ -1394,6 +1520,16 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       if (MODE == 0) stage(3, t + 2, cur);
       if (MODE == 0) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");   // all but the three youngest half-tiles: tile t + 1 is in
       if (MODE == 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if constexpr (CHAIN && MODE == 1) {
+        // the ticket is in: wave 0 posts it and asks for the counters of its producer row blocks, which the last K tile covers
+        if (wid == 0 && c_left == 0) {
+          const int tk = __builtin_amdgcn_readfirstlane((int)c_claim);
+          ChainTile nz;
+          const bool ok = chain_decode(ch, tk, nz);
+          c_cnt = ok ? chain_counters(nz) : ~0u;
+          if (lane == 0) mbox[0] = ok ? tk : -1;
+        }
+      }
       G8_BAR();
       quadrant(acc[1][0], fw0, fs0);
       G8_BAR();
@@ -1402,6 +1538,19 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     for (int t = 0; t < nk - 2; ++t) ktile(t, std::integral_constant<int, 0>{});
     ktile(nk - 2, std::integral_constant<int, 1>{});
     ktile(nk - 1, std::integral_constant<int, 2>{});
+    if constexpr (CHAIN) {
+      // producers done already (the usual case: they ran rounds ago)?  Then the acquire goes here, drained ahead of the barrier
+      // below, behind which every wave may load the next tile's A rows.  A first-problem or absent tile has no counters (~0).
+      if (wid == 0 && c_left == 0) {
+        const bool ready = __all(c_cnt >= (unsigned)ch.nt);
+        if (ready && __builtin_amdgcn_readfirstlane((int)c_cnt) != -1) {
+          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        if (lane == 0) mbox[1] = ready;
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      }
+    }
     if (wr == 0) __builtin_amdgcn_s_barrier();   // row 0 pays back the stagger: every wave has read its last fragments
     if (nk & 1) { xa0 ^= BUF; xa1 ^= BUF; wa0 ^= BUF; wa1 ^= BUF; }   // the next tile starts in buffer 0 again
 
@@ -1410,6 +1559,19 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // half h as fp32 (16-byte chunk c of row r at r * 1024 + ((c ^ (r & 15)) << 4): conflict-free for the fragment writes and
     // the row reads), then wave w finishes rows 8 w .. 8 w + 7 of the block.
     const int em0 = m0, en0 = n0;                    // this tile (m0 / n0 move on to the next one below)
+    // CHAIN: p moves on to the next tile's problem below as well: the epilogue's own copies, whether this tile has consumers in the
+    // launch (e_pub: then its row block's counter e_cnt), and how it stores (consumed rows in the form the table names; the last
+    // problem's write-through, as launch_gemm8 stores a launch that ends in one burst)
+    const int eM = p.M;
+    void* const eC = p.C;
+    const float* const ebias = p.bias;
+    bool e_pub = false, ewt = wt;
+    unsigned* e_cnt = nullptr;
+    if constexpr (CHAIN) {
+      e_pub = cz.l + 1 < ch.n;
+      ewt = e_pub ? !ch.release : true;
+      e_cnt = ch.state + CHAIN_STATE_HEAD + ch.pr[cz.l].cnt0 + cz.rb;
+    }
     // everything the epilogue derives from the lane id comes from a copy the compiler cannot match with the K loop's: hoisted
     // out of the tile loop those values lived across the K loop and pushed its staging pointers into scratch
     int el = lane;
@@ -1417,7 +1579,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int efr = el & 15, efq = el >> 4;
     const int ncol = en0 + el * 4;                   // this lane's four columns in every row it finishes
     f32x4 cbias = f32x4{0.f, 0.f, 0.f, 0.f}, cx = f32x4{1.f, 1.f, 1.f, 1.f}, cy = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (p.bias) cbias = *(const f32x4*)(p.bias + ncol);
+    if (ebias) cbias = *(const f32x4*)(ebias + ncol);
     if constexpr (EPI == 2) cx = *(const f32x4*)(p.w_colsum + ncol);
     if constexpr (EPI == 3) {
       if (p.r_stats) { cx = *(const f32x4*)(p.r_gamma + ncol); cy = *(const f32x4*)(p.r_beta + ncol); }
@@ -1457,11 +1619,30 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       }
     }
     // the next tile of this workgroup: its first K tile goes out now and lands under the epilogue
-    tl += stride;
-    const bool more = tl < run_n;
+    bool more, ready = true;
+    if constexpr (CHAIN) {
+      // the rest of a row-block ticket reads the rows this workgroup has acquired already; else what wave 0 posted
+      if (c_left > 0) { --c_left; ++cz.ct; more = true; }
+      else {
+        const int tk = __builtin_amdgcn_readfirstlane(mbox[0]);
+        ready = __builtin_amdgcn_readfirstlane(mbox[1]) != 0;
+        more = tk >= 0;
+        if (more) {
+          chain_decode(ch, tk, cz);
+          c_left = cz.nct - 1;
+          chain_problem();
+          nk = p.K / 64;
+        }
+      }
+    } else {
+      tl += stride;
+      more = tl < run_n;
+    }
     if (more) {
       set_tile(tl);
-      stage(2, 0, 0); stage(0, 0, 0); stage(3, 0, 0); stage(1, 0, 0);
+      // (CHAIN, producers not done: W, which nobody writes in the launch, goes out now; A behind the wait below)
+      stage(2, 0, 0); if (ready) stage(0, 0, 0);
+      stage(3, 0, 0); if (ready) stage(1, 0, 0);
       ln_request();
     }
     auto write_block = [&](const f32x4 (&q0)[2][4], const f32x4 (&q1)[2][4]) {
@@ -1482,7 +1663,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         if (has_r) {
 #pragma unroll
           for (int it = 0; it < 8; ++it) {
-            const int m = min(em0 + ps * 64 + wid * 8 + it, p.M - 1);
+            const int m = min(em0 + ps * 64 + wid * 8 + it, eM - 1);
             rr[it] = *(const f32x4*)((const float*)p.R + (long)m * p.ldr + ncol);
           }
         }
@@ -1496,9 +1677,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             o[e] = act_out_c<float, ACTK>(WS ? fmaf(a[e], MSMD_SPLIT_INV, cbias[e]) : a[e] + cbias[e], p.act);   // gemm2s_kernel's fp32 epilogue
             if (has_r) o[e] += rr[it][e];
           }
-          if (m < p.M) {
-            if (wt) store16_wt((float*)p.C + (long)m * p.ldc + ncol, __builtin_bit_cast(u32x4, o));
-            else *(f32x4*)((float*)p.C + (long)m * p.ldc + ncol) = o;
+          if (m < eM) {
+            if (ewt) store16_wt((float*)eC + (long)m * p.ldc + ncol, __builtin_bit_cast(u32x4, o));
+            else *(f32x4*)((float*)eC + (long)m * p.ldc + ncol) = o;
           }
         }
       } else if constexpr ((SPLIT & 3) == 1) {
@@ -1513,7 +1694,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         if (has_r) {
 #pragma unroll
           for (int it = 0; it < 8; ++it) {
-            const int m = min(em0 + ps * 64 + wid * 8 + it, p.M - 1);
+            const int m = min(em0 + ps * 64 + wid * 8 + it, eM - 1);
             rr[it] = *(const u32x4*)((const f16_t*)p.R + (long)m * 2 * p.ldr + coff);
           }
         }
@@ -1539,9 +1720,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
           const unsigned lp0 = __builtin_bit_cast(unsigned, f16x2{l[0], l[1]}), lp1 = __builtin_bit_cast(unsigned, f16x2{l[2], l[3]});
           const unsigned g0 = swap1(odd ? hp0 : lp0), g1 = swap1(odd ? hp1 : lp1);
           const u32x4 o = odd ? u32x4{g0, g1, lp0, lp1} : u32x4{hp0, hp1, g0, g1};
-          if (m < p.M) {
-            if (wt) store16_wt((f16_t*)p.C + (long)m * 2 * p.ldc + coff, o);
-            else *(u32x4*)((f16_t*)p.C + (long)m * 2 * p.ldc + coff) = o;
+          if (m < eM) {
+            if (ewt) store16_wt((f16_t*)eC + (long)m * 2 * p.ldc + coff, o);
+            else *(u32x4*)((f16_t*)eC + (long)m * 2 * p.ldc + coff) = o;
           }
         }
       } else {
@@ -1550,7 +1731,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       if (EPI != 2 && has_r) {
 #pragma unroll
         for (int it = 0; it < 8; ++it) {
-          const int m = min(em0 + ps * 64 + wid * 8 + it, p.M - 1);
+          const int m = min(em0 + ps * 64 + wid * 8 + it, eM - 1);
           rr[it] = *(const V4*)((const TO*)p.R + (long)m * p.ldr + ncol);
         }
       }
@@ -1573,9 +1754,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
           else if (has_r) v[e] += (float)rr[it][e];
         }
         const V4 o = pack4<TO>(v[0], v[1], v[2], v[3]);
-        if (m < p.M) {
-          if (wt) store8_wt((TO*)p.C + (long)m * p.ldc + ncol, __builtin_bit_cast(u32x2, o));
-          else *(V4*)((TO*)p.C + (long)m * p.ldc + ncol) = o;
+        if (m < eM) {
+          if (ewt) store8_wt((TO*)eC + (long)m * p.ldc + ncol, __builtin_bit_cast(u32x2, o));
+          else *(V4*)((TO*)eC + (long)m * p.ldc + ncol) = o;
         }
         if constexpr (EPI == 3) {
           if (p.stats_out) {      // sums of what the consumer will read, per 64-column slab = 16 lanes
@@ -1606,10 +1787,43 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     if (wr == 1) write_block(acc[1][0], acc[1][1]);
     G8_EBAR();
     finish_block(3);
-    if (!more) break;
-    // the upper half of the ring is free again once every wave has read its rows of the last block; the first K tile has
-    // been in flight since before the epilogue: K tile 1 except X1 follows, and the loop's own counted waits take over
-    G8_EBAR();
+    if constexpr (CHAIN) {
+      if (e_pub) {
+        // hand the tile over: every storing wave drains its stores, the workgroup meets, ONE lane signals (plain stores: behind one
+        // agent-scope release, its own wait written out -- cdna_hip_programming.md Guideline 16, Pitfall 12)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        G8_EBAR();
+        if (tid == 0) {
+          if (ch.release) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          }
+          __hip_atomic_fetch_add(e_cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+      }
+      if (!more) break;
+      if (!e_pub) G8_EBAR();
+      if (!ready) {
+        // the producers of the next tile were not done when its ticket came in: wave 0 waits for them (bounded), acquires, and only
+        // behind the barrier do the A rows of its first K tile go out
+        if (wid == 0) {
+          const bool ok = chain_wait(cz);
+          if (lane == 0) mbox[2] = ok;
+        }
+        __syncthreads();
+        if (!__builtin_amdgcn_readfirstlane(mbox[2])) {      // a wait expired: no more tickets, a normal return
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          break;
+        }
+        set_tile(tl);
+        stage(0, 0, 0); stage(1, 0, 0);
+      }
+    } else {
+      if (!more) break;
+      // the upper half of the ring is free again once every wave has read its rows of the last block; the first K tile has
+      // been in flight since before the epilogue: K tile 1 except X1 follows, and the loop's own counted waits take over
+      G8_EBAR();
+    }
     set_tile(tl);
     stage(2, 1, BUF); stage(0, 1, BUF); stage(3, 1, BUF);
     asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
@@ -1617,6 +1831,17 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   }
 #undef G8_BAR
 #undef G8_EBAR
+}
+
+template <typename TI, int EPIA, int SPLIT = 0>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void gemm8_kernel(const GemmArgs p) {
+  gemm8_body<TI, EPIA, SPLIT>(p, NoChain{});
+}
+// p: what the problems share (N, ldc, act); the rest of it follows the table's problem of the tile at hand
+template <typename TI, int EPIA>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void gemm8_chain_kernel(const GemmArgs p0, const ChainTable ch) {
+  GemmArgs p = p0;
+  gemm8_body<TI, EPIA, 0>(p, ch);
 }
 
 // f(std::integral_constant<int, C>) for the C of the compile-time list that equals the run-time `code`: its result (a launcher's:
@@ -1630,8 +1855,8 @@ static int dispatch_code(int code, F&& f) {
 
 // Launches KFN on the current device and returns the last error.  More than 64 KB of dynamic LDS has to be allowed per kernel
 // and per DEVICE (hipFuncSetAttribute acts on the current one): once for each, remembered in a bit per device ordinal.
-template <auto KFN>
-static int gemm_launch_kernel(dim3 grid, int threads, int lds, hipStream_t st, const GemmArgs& p) {
+template <auto KFN, typename... ARGS>
+static int gemm_launch_kernel(dim3 grid, int threads, int lds, hipStream_t st, const ARGS&... p) {
   if (lds > 0) {
     static std::atomic<unsigned long> allowed{0};
     int dev = 0;
@@ -1642,7 +1867,7 @@ static int gemm_launch_kernel(dim3 grid, int threads, int lds, hipStream_t st, c
       allowed.fetch_or(bit, std::memory_order_relaxed);
     }
   }
-  hipLaunchKernelGGL(KFN, grid, dim3(threads), lds, st, p);
+  hipLaunchKernelGGL(KFN, grid, dim3(threads), lds, st, p...);
   MSMD_RETURN_LAST();
 }
 
@@ -2223,4 +2448,94 @@ extern "C" int msmd_gemm_batched2(const void* A, const void* W, void* C, int M, 
   c.batch = batch_outer; c.strideA = strideA_o; c.strideW = strideW_o; c.strideC = strideC_o;
   c.batch_inner = batch_inner; c.strideA2 = strideA_i; c.strideW2 = strideW_i; c.strideC2 = strideC_i;
   return gemm_run(gemm_plan, c, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// msmd_conv_chain: 2 to 4 strided Conv1d layers over a channels-last signal as ONE launch of gemm8_chain_kernel (see CHAIN at
+// gemm8_body).  The table of the shapes alone (no pointers): what msmd_conv_chain_plan and msmd_conv_chain_workspace answer from.
+// False for what the kernel does not take.
+static bool conv_chain_table(ChainTable& t, int B, int T0, int C, int N, int n, const int* kernel, const int* stride, int flags) {
+  if (B <= 0 || T0 <= 0 || C <= 0 || N <= 0 || n < 2 || n > 4 || !kernel || !stride || (N % 256)) return false;
+  t = ChainTable{};
+  t.n = n; t.nt = N / 256;
+  t.per_block = (flags & MSMD_CONV_CHAIN_ROW_BLOCK_TICKETS) != 0;
+  t.release = (flags & MSMD_CONV_CHAIN_RELEASE) != 0;
+  long t_in = T0, c_in = C;
+  int tickets = 0, counters = 0;
+  for (int l = 0; l < n; ++l) {
+    ChainProblem& q = t.pr[l];
+    if (kernel[l] <= 0 || stride[l] <= 0 || t_in < kernel[l]) return false;
+    const long t_out = (t_in - kernel[l]) / stride[l] + 1, M = (long)B * t_out, K = kernel[l] * c_in;
+    if ((K % 64) || K < 128 || M >= (1L << 24)) return false;      // whole 128-byte K tiles, two of them; a_row_offset's fp32 reciprocal
+    q.M = (int)M; q.K = (int)K; q.rows_per_batch = (int)t_out; q.inv_rpb = 1.0f / (float)t_out;
+    q.lda = stride[l] * c_in; q.a_batch_stride = t_in * c_in;
+    q.t_in = (int)t_in; q.stride = stride[l]; q.taps = kernel[l];
+    q.mt = (int)((M + 255) / 256);
+    q.ticket0 = tickets; q.cnt0 = counters;
+    tickets += t.per_block ? q.mt : q.mt * t.nt;
+    counters += q.mt;
+    // 32-bit staging offsets from A / W
+    if (((long)(B - 1) * q.a_batch_stride + (t_out - 1) * q.lda + K) * 2 >= (1L << 32) || (long)N * K * 2 >= (1L << 32)) return false;
+    t_in = t_out; c_in = N;
+  }
+  t.total = tickets;
+  return true;
+}
+static long conv_chain_state_bytes(const ChainTable& t) {
+  const long words = CHAIN_STATE_HEAD + t.pr[t.n - 1].cnt0 + t.pr[t.n - 1].mt;
+  return (words * 4 + 15) / 16 * 16;
+}
+
+extern "C" long msmd_conv_chain_workspace(int B, int T0, int C, int N, int n_layers, const int* kernel, const int* stride) {
+  ChainTable t;
+  return conv_chain_table(t, B, T0, C, N, n_layers, kernel, stride, 0) ? conv_chain_state_bytes(t) : 0;
+}
+
+extern "C" int msmd_conv_chain_plan(int B, int T0, int C, int N, int n_layers, const int* kernel, const int* stride, int flags, int ticket,
+                                    int* out6) {
+  ChainTable t;
+  if (!out6 || !conv_chain_table(t, B, T0, C, N, n_layers, kernel, stride, flags)) return -1;
+  ChainTile z;
+  if (!chain_decode(t, ticket, z)) return t.total;      // past the last ticket: the ticket count (>= 1), nothing written
+  out6[0] = z.l; out6[1] = z.rb; out6[2] = z.ct; out6[3] = z.nct; out6[4] = z.pb0; out6[5] = z.pb1;
+  return 0;
+}
+
+extern "C" int msmd_conv_chain(const void* x, int B, int T0, int C, int N, int n_layers, const void* const* w, const float* const* bias,
+                               void* const* out, const int* kernel, const int* stride, int act, int dtype, void* workspace,
+                               long workspace_bytes, int max_workgroups, int flags, msmd_stream_t stream) {
+  ChainTable t;
+  if ((dtype != MSMD_BF16 && dtype != MSMD_F16) || (act != MSMD_ACT_NONE && act != MSMD_ACT_GELU) || !x || !w || !bias || !out || !workspace) return 1;
+  if (!conv_chain_table(t, B, T0, C, N, n_layers, kernel, stride, flags)) return 1;
+  const long state_bytes = conv_chain_state_bytes(t);
+  if (workspace_bytes < state_bytes || ((uintptr_t)workspace & 15) || max_workgroups < 0) return 1;
+  for (int l = 0; l < n_layers; ++l) {
+    ChainProblem& q = t.pr[l];
+    q.A = l ? out[l - 1] : x; q.W = w[l]; q.bias = bias[l]; q.C = out[l];
+    if (!q.W || !q.C || ((uintptr_t)q.A & 15) || ((uintptr_t)q.W & 15) || ((uintptr_t)q.bias & 15) || ((uintptr_t)q.C & 15)) return 1;
+  }
+  t.state = (unsigned*)workspace;
+  GemmArgs p{};      // what the problems share; gemm8_body's chain_problem fills in the rest per tile
+  p.N = N; p.ldc = N; p.act = act; p.vec_ok = 1; p.batch_inner = 1; p.xn = 1; p.nt = t.nt;
+  p.A = t.pr[0].A; p.W = t.pr[0].W; p.C = t.pr[0].C; p.M = t.pr[0].M; p.K = t.pr[0].K;
+  const int cap = gemm8_workgroup_cap();
+  int grid = t.total < cap ? t.total : cap;
+  if (max_workgroups > 0 && max_workgroups < grid) grid = max_workgroups;
+  hipStream_t st = (hipStream_t)stream;
+  // the polled words start from zero in every call: the library's zeroing launch (common.h), under capture a kernel node that is
+  // replayed ahead of the chain.  (A hipMemsetAsync here was captured as a memset node that zeroed the block in the first replay
+  // and filled it with a 32-byte pattern of other data from the second replay on: DESIGN.md 5.26.)
+  if (const hipError_t e = msmd_zero_async(workspace, (size_t)state_bytes, st); e != hipSuccess) return (int)e;
+  constexpr int LDS = GEMM8_RING + 16;      // + the workgroup's mailbox
+  const int code = epia(EPI_PLAIN, act);
+  if (dtype == MSMD_BF16)
+    return dispatch_code<11, 21>(code, [&](auto c) { return gemm_launch_kernel<gemm8_chain_kernel<bf16_t, decltype(c)::value>>(dim3(grid), 512, LDS, st, p, t); });
+  return dispatch_code<11, 21>(code, [&](auto c) { return gemm_launch_kernel<gemm8_chain_kernel<f16_t, decltype(c)::value>>(dim3(grid), 512, LDS, st, p, t); });
+}
+
+// The status word of a finished launch (0, or MSMD_CONV_CHAIN_TIMEOUT where a wait expired): a blocking copy, for tests and tools.
+extern "C" int msmd_conv_chain_status(const void* workspace) {
+  unsigned s = 0;
+  if (!workspace || hipMemcpy(&s, (const unsigned*)workspace + 1, sizeof(s), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  return (int)s;
 }

@@ -481,6 +481,68 @@ def conv1d_cl(x, w_packed, bias=None, *, kernel, stride, act=ACT_NONE, out_dtype
     return out
 
 
+CONV_CHAIN_RELEASE, CONV_CHAIN_ROW_BLOCK_TICKETS = _h("CONV_CHAIN_RELEASE", "CONV_CHAIN_ROW_BLOCK_TICKETS")
+CONV_CHAIN_FLAGS = 0      # the forms conv_chain() asks for when the caller names none: write-through hand-over, one tile per ticket
+
+
+def _int_array(vals):
+    return (ctypes.c_int * len(vals))(*[int(v) for v in vals])
+
+
+def conv_chain_plan(B, T0, C, N, kernels, strides, flags, ticket):
+    """msmd_conv_chain_plan (host only, no GPU): (layer, row block, first column tile, column tiles, first, last producer row
+    block) of `ticket`; the ticket count (an int) for a ticket past the last; None for shapes the kernel does not take."""
+    out = (ctypes.c_int * 6)()
+    r = _lib.load().msmd_conv_chain_plan(B, T0, C, N, len(kernels), _int_array(kernels), _int_array(strides), flags, ticket, out)
+    return None if r < 0 else (tuple(out) if r == 0 else r)
+
+
+def conv_chain_status(workspace):
+    """The status word of the conv_chain launch that used `workspace` (blocks; 0 = no wait expired)."""
+    return _lib.load().msmd_conv_chain_status(_p(workspace))
+
+
+def conv_chain(x, ws_packed, biases, *, kernels, strides, act=ACT_NONE, flags=None, max_workgroups=0, outs=None, workspace=None):
+    """2 to 4 strided Conv1d layers over a channels-last 16-bit (B, T, C) signal as ONE launch (msmd_conv_chain): layer l is
+    conv1d_cl(., ws_packed[l], biases[l], kernel=kernels[l], stride=strides[l], act=act) of layer l - 1's output, same bits.
+    Returns the list of every layer's output, or None -- nothing launched -- where the library declines the shapes (the caller
+    then runs the layers one by one).  outs / workspace: buffers to reuse (tests, tools)."""
+    _need_cuda(x, *ws_packed, *biases)
+    lib = _lib.load()
+    B, T0, C = x.shape
+    n, N = len(ws_packed), ws_packed[0].shape[0]
+    if x.dtype not in (torch.bfloat16, torch.float16) or not x.is_contiguous() or any(w.dtype != x.dtype or not w.is_contiguous() for w in ws_packed):
+        return None
+    ks, ss = _int_array(kernels), _int_array(strides)
+    nbytes = lib.msmd_conv_chain_workspace(B, T0, C, N, n, ks, ss)
+    if nbytes <= 0:
+        return None
+    if outs is None:
+        outs, T = [], T0
+        for k, s in zip(kernels, strides):
+            T = (T - k) // s + 1
+            outs.append(torch.empty((B, T, N), device=x.device, dtype=x.dtype))
+    if workspace is None:
+        workspace = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
+    Ms = [o.shape[0] * o.shape[1] for o in outs]
+    ptrs = lambda ts: (ctypes.c_void_p * n)(*[_p(t) for t in ts])
+    flags = CONV_CHAIN_FLAGS if flags is None else flags
+    # one bracket for the launch: N is shared and so is K past the first layer, so 2 N sum(M_l K_l) is booked as the first
+    # layer's own product plus the rest on the shared K; marked as a 256 x 256-tile launch
+    Ks = [k * (C if l == 0 else N) for l, k in enumerate(kernels)]
+    if len(set(Ks)) == 1:
+        trace = _trace_begin(sum(Ms), N, Ks[0], 1, _dt(x))
+    else:
+        if GEMM_FLOPS is not None:
+            GEMM_FLOPS[0] += 2.0 * N * (sum(m * k for m, k in zip(Ms, Ks)) - sum(Ms[1:]) * Ks[1])
+        trace = _trace_begin(sum(Ms[1:]), N, Ks[1], 1, _dt(x))
+    r = lib.msmd_conv_chain(_p(x), B, T0, C, N, n, ptrs(ws_packed), ptrs(biases), ptrs(outs), ks, ss, act, _dt(x), _p(workspace),
+                            workspace.numel(), max_workgroups, flags, _stream())
+    _lib.check(r, "msmd_conv_chain")
+    _trace_end(trace, lambda: 80, ())
+    return outs
+
+
 def layernorm(x, gamma, beta, residual=None, post_add=None, act=ACT_NONE, eps=1e-5, out_dtype=None, post_act=ACT_NONE,
               split=None):
     """y = post_act(LayerNorm(act(x + residual)) * gamma + beta) + post_add.

@@ -296,7 +296,7 @@ def audio_encoder_train(enc, audio, output_fps, frame_num, dtype, groups=1):
     c = enc.config
     with torch.no_grad():
         r, rep = pad_audio_plan(audio.shape[1])
-        x = enc.feature_extractor_cl(audio, dtype, r, rep)
+        x = enc.feature_extractor_cl(audio, dtype, r, rep, chain=False)
         T50 = x.shape[1]
         crop = min(round(frame_num * 50 / output_fps), T50)
         if not (crop == T50 and frame_num == T50):

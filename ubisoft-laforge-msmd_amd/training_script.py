@@ -410,7 +410,13 @@ class Trainer:
             if ag.TrainNoise.active:   # the reference's extra pass also runs under model.train()
                 prev_audio = tg.audio_feat_train(model, audio, model.n_motions, dtype).float()[:, -n_prev:]
             else:
-                prev_audio = model.extract_audio_feature(audio)[:, -n_prev:]
+                # the training iteration keeps conv1-4 as per-layer launches on this pass too (its launch sequence is recorded)
+                enc = model.audio_encoder
+                chain, enc.conv_chain = enc.conv_chain, False
+                try:
+                    prev_audio = model.extract_audio_feature(audio)[:, -n_prev:]
+                finally:
+                    enc.conv_chain = chain
         return batch[1][0][:, -n_prev:], prev_audio
 
     def _loss_terms(self, i, W, target, prev_motion, shape, mu, logvar, terms, lw):

@@ -158,6 +158,7 @@ class Wav2Vec2Model(nn.Module):
     """HF-key-compatible parameter tree + HIP forward.  ``config`` carries num_hidden_layers etc."""
 
     model_type = "wav2vec2"
+    conv_chain = True      # feature_extractor_cl: conv1-4 of the group-norm 16-bit path as one chained launch (ops.conv_chain)
 
     def __init__(self, config=None):
         super().__init__()
@@ -350,9 +351,10 @@ class Wav2Vec2Model(nn.Module):
         return P
 
     # ------------------------------------------------------------------ forward pieces
-    def feature_extractor_cl(self, audio, dtype, reflect_len=None, replicate_len=None):
+    def feature_extractor_cl(self, audio, dtype, reflect_len=None, replicate_len=None, chain=True):
         """HF Wav2Vec2FeatureEncoder on UNPADDED audio (B, L) with pad_audio fused into conv0's loads.
-        Returns (B, T50, 512) channels-last."""
+        Returns (B, T50, 512) channels-last.  chain=False (the training step) keeps conv1-4 as per-layer launches whatever
+        the `conv_chain` attribute says."""
         P = self.pack_fe(dtype)
         if reflect_len is None:
             reflect_len, replicate_len = 0, 0
@@ -376,7 +378,17 @@ class Wav2Vec2Model(nn.Module):
                                   act=ops.ACT_GELU, out_dtype=torch.float32 if last else ops.SPLIT)
             return x
         x = ops.conv0_gn_gelu(audio.float().contiguous(), P.w0, P.gn_g, P.gn_b, reflect_len, replicate_len, dtype, eps)
+        first = 0
+        if self.conv_chain and chain and len(P.conv_w) >= 4:
+            # conv1-4 as one chained launch (ops.conv_chain: the same bits); conv5 / conv6, 100 and 50 tiles with K = 1 024, would
+            # each add a dependent sub-round to its end and stay per-layer launches, as does everything the library declines
+            outs = ops.conv_chain(x, P.conv_w[:4], P.conv_b[1:5], kernels=CONV_KERNEL[1:5], strides=CONV_STRIDE[1:5],
+                                  act=ops.ACT_GELU)
+            if outs is not None:
+                x, first = outs[-1], 4
         for i, w in enumerate(P.conv_w):
+            if i < first:
+                continue
             x = ops.conv1d_cl(x, w, P.conv_b[i + 1], kernel=CONV_KERNEL[i + 1], stride=CONV_STRIDE[i + 1],
                               act=ops.ACT_GELU)
         return x
