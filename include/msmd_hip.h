@@ -860,6 +860,43 @@ int msmd_render_raster(const float* screen, const float* normals, const int* fac
                        int H, int W, float near, float far, unsigned background, msmd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Anti-aliased rendering: four samples per pixel.  Opt-in; one sample per pixel is the entry points above
+ * and their bits.  The convention is this project's own (no parity with pyrender's sample positions):
+ *   - sample points of pixel (i, j), in 1/256 pixel units from the pixel's top-left corner (256 j, 256 i):
+ *     s0 = (96, 32), s1 = (224, 96), s2 = (32, 160), s3 = (160, 224): the rotated-grid 4x pattern (0.375, 0.125),
+ *     (0.875, 0.375), (0.125, 0.625), (0.625, 0.875).  Integers on the snap grid, so the edge functions at a sample stay
+ *     exact in int64 and the 2^30 snap limit holds;
+ *   - every sample is rasterised exactly as the pixel centre is at one sample: the same snapped coordinates, orientation
+ *     swap and top-left rule, evaluated at the sample point; depth 1/d interpolated at the sample with the same
+ *     [near, far] discard; the nearest fragment wins per sample and the lower face id wins a tie; the same faces are
+ *     dropped whole;
+ *   - a face's pixel box is the pixels that have some sample inside the snapped bounding box: jmin = (xmin + 31) >> 8,
+ *     jmax = (xmax - 32) >> 8, likewise for i, clipped to the tile and the image;
+ *   - shading runs per sample at the sample's own position (sparse supersampling: no attribute is extrapolated outside
+ *     its triangle) with msmd_render_raster's formulas, quantised per sample by floor(255 c + 0.5);
+ *   - resolve: each of the four RGBA bytes of a pixel is (b0 + b1 + b2 + b3 + 2) >> 2 over the four samples' bytes; a
+ *     covered sample contributes its quantised colour with alpha 255, an uncovered one the four bytes of `background`
+ *     (so with a background alpha of 0 the stored alpha is the coverage).
+ * msmd_render_raster_ms, samples = 4, one workgroup per (frame, 32 x 32 tile): rgba (B, H, W, 4) uint8 resolved; depth
+ *   (B, H, W) the least depth over the pixel's covered samples, 0 if none; sample_face_id (B, H, W, 4) int32 or NULL, -1
+ *   for an uncovered sample; sample_depth (B, H, W, 4) fp32 or NULL, 0 for an uncovered sample.  Both sample buffers are
+ *   16-byte aligned.  samples = 1 forwards to msmd_render_raster with the sample buffers of shape (B, H, W, 1)
+ *   (sample_depth is then a copy of depth).  Any other `samples` returns 1 before anything is launched.
+ * msmd_render_shade_textured_ms, samples = 4: the deferred pass of msmd_render_shade_textured over sample_face_id
+ *   (B, H, W, 4): every sample with 0 <= id < F is shaded at its own position with that pass's formulas (uv, the analytic
+ *   level of detail from the exact per-PIXEL steps, the trilinear fetch), any other sample contributes `background`, and
+ *   every pixel with at least one shaded sample is overwritten with the resolve of its four; other pixels are left as they
+ *   are.  (u, v, lambda) is not offered.  samples = 1 forwards to msmd_render_shade_textured without uvl. */
+int msmd_render_raster_ms(const float* screen, const float* normals, const int* faces, const float* shade,
+                          const float* lights, int n_lights, void* rgba, float* depth, int* sample_face_id,
+                          float* sample_depth, int B, int V, int F, int H, int W, float near, float far,
+                          unsigned background, int samples, msmd_stream_t stream);
+int msmd_render_shade_textured_ms(const float* screen, const float* normals, const int* faces, const float* vt, const int* ft,
+                                  const float* pyramid, int Ht, int Wt, const float* shade, const float* lights,
+                                  int n_lights, const int* sample_face_id, void* rgba, int B, int V, int F, int Nt, int H,
+                                  int W, float near, unsigned background, int samples, msmd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Textured shading (the reference's render_mesh(tex_img, tex_uv)).  A deferred, pixel-parallel pass behind
  * msmd_render_raster: it reads that launch's face_id buffer and overwrites rgba at the covered pixels.  The conventions are
  * the ordinary OpenGL / OBJ ones (GL_REPEAT, GL_LINEAR magnification, GL_LINEAR_MIPMAP_LINEAR minification, v up, no sRGB

@@ -14,6 +14,11 @@ stage (C) of the raster launch also does for every covered pixel, which is waste
 its msmd_render_raster is timed in the same rounds, which is the only untextured time of the parent there is to compare with.
 
     python tools/bench_render.py --texture 1024 [--parent_lib /path/to/parent/libmsmd_hip.so] [--out profiles/r11_texture.txt]
+
+--samples 4 times the four-sample raster launch instead: per size, the one-sample launch, the four-sample launch
+and, with --parent_lib, the parent build's one-sample launch, in turn within every round.
+
+    python tools/bench_render.py --samples 4 [--parent_lib /path/to/parent/libmsmd_hip.so] [--out profiles/5_27_msaa.txt]
 """
 import argparse
 import ctypes
@@ -110,11 +115,52 @@ def bench_texture(args, dev, v, f, verts, rot, tc, lines):
                      f"untextured shading of those pixels inside the raster launch is wasted work under a texture")
 
 
+def bench_samples(args, dev, f, verts, rot, tc, lines):
+    """One- and four-sample raster launches (and the parent build's) as raw calls of the C entry points on the same preallocated
+    buffers, so that every launch carries the same host work between its two events."""
+    from msmd_amd import _lib
+    B, V = verts.shape[:2]
+    lib = _lib.load()
+    parent = None
+    if args.parent_lib:
+        parent = ctypes.CDLL(args.parent_lib).msmd_render_raster
+        parent.argtypes, parent.restype = _lib.PROTOS["msmd_render_raster"], ctypes.c_int
+    for size in (512, 256):
+        r = MeshRenderer((size, size))
+        faces, off, ids = r._tables(torch.from_numpy(f).to(dev), V, dev)
+        view, shade, lights = r._device_consts(dev)
+        near, far = r.frustum["near"], r.frustum["far"]
+        screen, normals = ops.render_vertices(verts, faces, off, ids, view, 1.0 / np.tan(r.fov / 2.0), size, size, tc, rot)
+        rgba, depth, _ = ops.render_raster(screen, normals, faces, shade, lights, size, size, near, far, 0xffffffff)
+        stream = torch.cuda.current_stream().cuda_stream
+        head = (screen.data_ptr(), normals.data_ptr(), faces.data_ptr(), shade.data_ptr(), lights.data_ptr(), lights.shape[0],
+                rgba.data_ptr(), depth.data_ptr())
+        tail = (B, V, faces.shape[0], size, size, near, far, 0xffffffff)
+        one = lambda: lib.msmd_render_raster(*head, None, *tail, stream)
+        ms = lambda: lib.msmd_render_raster_ms(*head, None, None, *tail, args.samples, stream)
+        fns, names = [one, ms], ["msmd_render_raster", f"msmd_render_raster_ms samples={args.samples}"]
+        if parent is not None:
+            fns.append(lambda: parent(*head, None, *tail, stream))
+            names.append("parent build's msmd_render_raster")
+        n = (ops.render_raster(screen, normals, faces, shade, lights, size, size, near, far, 0xffffffff, want_face_id=True,
+                               samples=args.samples)[2] >= 0).sum(-1)
+        res = timed_in_turn(fns)
+        for name, (med, lo, hi) in zip(names, res):
+            lines.append(f"{name} B={B} V={V} F={faces.shape[0]} {size}x{size}: median {med:.4f} ms (min {lo:.4f}, max {hi:.4f}, 9 rounds "
+                         f"in turn), {B / med * 1e3:.0f} frames/s")
+        lines.append(f"{args.samples} samples / 1 sample {size}x{size}: {res[1][0] / res[0][0]:.3f}"
+                     + (f"; this build's one-sample raster / the parent's: {res[0][0] / res[2][0]:.3f}" if parent is not None else "")
+                     + f"; {100 * float((n > 0).float().mean()):.1f} % of the pixels have a covered sample, "
+                     f"{100 * float(((n > 0) & (n < args.samples)).float().mean()):.2f} % are partly covered")
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=100)
     ap.add_argument("--out", type=str, default=None)
     ap.add_argument("--texture", type=int, default=0, help="side of a noise texture: time the textured pass too (0: do not)")
+    ap.add_argument("--samples", type=int, default=1, choices=ops.RENDER_SAMPLES,
+                    help="4: time the four-sample raster launch beside the one-sample launch instead")
     ap.add_argument("--parent_lib", type=str, default=None, help="another build of the library whose raster launch is timed in turn")
     args = ap.parse_args(argv)
     assert torch.cuda.is_available(), "bench_render needs an MI355X"
@@ -126,7 +172,9 @@ def main(argv=None):
     rot = torch.from_numpy(0.3 * synth.normalish("bench_render/rot", (B, 3))).float().to(dev)
     tc = torch.zeros(3, device=dev)
     lines = []
-    for size in (512, 256):
+    if args.samples != 1:
+        bench_samples(args, dev, f, verts, rot, tc, lines)
+    for size in (512, 256) if args.samples == 1 else ():
         r = MeshRenderer((size, size))
         faces, off, ids = r._tables(torch.from_numpy(f).to(dev), V, dev)
         view, shade, lights = r._device_consts(dev)

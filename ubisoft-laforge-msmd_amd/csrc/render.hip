@@ -2,7 +2,8 @@
 // An Instinct card has no graphics pipe; this turns the (B, V, 3) vertices msmd_lbs_skin_v2 leaves on the device into images
 // there.  Two launches per batch of frames, no host synchronisation, no global atomics, bit-identical from run to run.
 // A texture adds a mip pyramid (built once per image) and a third, deferred launch that shades the covered pixels from it
-// (DESIGN.md 5.14).
+// (DESIGN.md 5.14).  The raster and the textured kernel are templates on the samples per pixel: one, or four for anti-aliased
+// frames.
 #include "common.h"
 
 namespace {
@@ -80,12 +81,27 @@ __global__ __launch_bounds__(256) void render_vertices_kernel(const float* __res
 }
 
 // ------------------------------------------------------------------------------------------------ raster stage
-#define RT_TILE 64                 // pixels per tile side
+#define RT_TILE 64                 // pixels per tile side at one sample per pixel; the strip width of the textured pass
+#define RT_TILE_MS 32              // pixels per tile side at four samples per pixel: the same 4096 keys
 #define RT_THREADS 256
 #define RT_CAP 2048                // compacted face ids held in LDS between two coverage passes
-#define RT_WAVE_WALK 256           // an in-tile bounding box of more pixels than this is walked by a whole wave
+#define RT_WAVE_WALK 256           // an in-tile bounding box of more fragments than this is walked by a whole wave
 #define RT_SNAP_LIMIT 1073741824.f // 2^30: |snapped coordinate| below it, so every edge function fits 64 bits (see below)
 #define RT_EMPTY 0xffffffffffffffffull
+
+// The sample points of a pixel, in 1 / 256 pixel units from its top-left corner (256 j, 256 i).  S = 1: the centre.  S = 4: the
+// rotated grid s0 = (96, 32), s1 = (224, 96), s2 = (32, 160), s3 = (160, 224).  Integers on the snap grid, so an edge function
+// at a sample is as exact as at the centre and the 2^30 limit below holds unchanged.
+template <int S> struct Rt {
+  static_assert(S == 1 || S == 4, "one or four samples per pixel");
+  static constexpr int tile = S == 1 ? RT_TILE : RT_TILE_MS;
+  static constexpr int keys = tile * tile * S;
+  static constexpr int walk = RT_WAVE_WALK / S;          // in pixels
+  static constexpr int lo = S == 1 ? 128 : 32;           // the least and the greatest sample offset (the same in x and in y)
+  static constexpr int hi = S == 1 ? 128 : 224;
+  __device__ static constexpr int sx(int k) { return S == 1 ? 128 : k == 0 ? 96 : k == 1 ? 224 : k == 2 ? 32 : 160; }
+  __device__ static constexpr int sy(int k) { return S == 1 ? 128 : 32 + 64 * k; }
+};
 
 // A face as the coverage and the shading passes see it, from ONE routine, so both compute the same bits.
 // Coordinates are snapped to 8 sub-pixel bits (round half even).  With |X|, |Y| < 2^30 a difference is below 2^31, a product
@@ -108,6 +124,7 @@ __device__ __forceinline__ long edge_bias(int ax, int ay, int bx, int by) {
   return (dy > 0 || (dy == 0 && dx > 0)) ? 0L : -1L;
 }
 
+template <int S>
 __device__ __forceinline__ FaceSetup face_setup(const int* __restrict__ faces, const float* __restrict__ scr, int f, int V,
                                                 float near, int tx0, int ty0, int tx1, int ty1) {
   FaceSetup s;
@@ -132,21 +149,29 @@ __device__ __forceinline__ FaceSetup face_setup(const int* __restrict__ faces, c
     const float q = s.q1; s.q1 = s.q2; s.q2 = q;
     s.area = -s.area;
   }
-  // pixels whose centre (256 j + 128) lies inside the snapped bounding box
+  // pixels that have some sample point inside the snapped bounding box: the centre (256 j + 128) at one sample, so + 127 and
+  // - 128; offsets 32 .. 224 at four, so + 31 and - 32 (a sliver that covers no centre can cover a sample)
   const int xmin = min(s.x0, min(s.x1, s.x2)), xmax = max(s.x0, max(s.x1, s.x2));
   const int ymin = min(s.y0, min(s.y1, s.y2)), ymax = max(s.y0, max(s.y1, s.y2));
-  s.jmin = max((xmin + 127) >> 8, tx0); s.jmax = min((xmax - 128) >> 8, tx1);
-  s.imin = max((ymin + 127) >> 8, ty0); s.imax = min((ymax - 128) >> 8, ty1);
+  s.jmin = max((xmin + 255 - Rt<S>::hi) >> 8, tx0); s.jmax = min((xmax - Rt<S>::lo) >> 8, tx1);
+  s.imin = max((ymin + 255 - Rt<S>::hi) >> 8, ty0); s.imax = min((ymax - Rt<S>::lo) >> 8, ty1);
   s.ok = s.jmin <= s.jmax && s.imin <= s.imax;
   return s;
 }
 
-// the three edge functions at pixel centre (j, i): e0 is opposite vertex 0, and so on
-__device__ __forceinline__ void edges_at(const FaceSetup& s, int j, int i, long& e0, long& e1, long& e2) {
-  const long px = 256L * j + 128, py = 256L * i + 128;
+// the three edge functions at sample k of pixel (j, i): e0 is opposite vertex 0, and so on
+template <int S>
+__device__ __forceinline__ void edges_at(const FaceSetup& s, int j, int i, int k, long& e0, long& e1, long& e2) {
+  const long px = 256L * j + Rt<S>::sx(k), py = 256L * i + Rt<S>::sy(k);
   e0 = edge_fn(s.x1, s.y1, s.x2, s.y2, px, py);
   e1 = edge_fn(s.x2, s.y2, s.x0, s.y0, px, py);
   e2 = edge_fn(s.x0, s.y0, s.x1, s.y1, px, py);
+}
+// what the edge function of (a -> b) at sample k of a pixel adds to its value at sample 0 of that pixel: d e / d x = -(by - ay),
+// d e / d y = bx - ax per 1 / 256 pixel, exact integers (0 for k = 0, so nothing at one sample)
+template <int S>
+__device__ __forceinline__ long sample_step(int ax, int ay, int bx, int by, int k) {
+  return -(long)(by - ay) * (Rt<S>::sx(k) - Rt<S>::sx(0)) + (long)(bx - ax) * (Rt<S>::sy(k) - Rt<S>::sy(0));
 }
 // 1 / depth by the integer barycentrics, one fixed order of operations; w_k are returned for the shading pass
 __device__ __forceinline__ float inv_depth(const FaceSetup& s, long e0, long e1, long e2, float& w0, float& w1, float& w2) {
@@ -169,28 +194,70 @@ __device__ __forceinline__ float lambert_diffuse(const float* __restrict__ nrm, 
   return diff * 0.318309886183790672f;
 }
 
-__device__ __forceinline__ void fragment(const FaceSetup& s, int f, int j, int i, long e0, long e1, long e2, long b0, long b1,
+template <int S>
+__device__ __forceinline__ void fragment(const FaceSetup& s, int f, int j, int i, int k, long e0, long e1, long e2, long b0, long b1,
                                          long b2, float near, float far, int tx0, int ty0, unsigned long long* s_key) {
   if ((e0 + b0) < 0 || (e1 + b1) < 0 || (e2 + b2) < 0) return;
   float w0, w1, w2;
   const float d = 1.f / inv_depth(s, e0, e1, e2, w0, w1, w2);
   if (!(d >= near && d <= far)) return;
   const unsigned long long key = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)f;
-  atomicMin(&s_key[(i - ty0) * RT_TILE + (j - tx0)], key);     // LDS; min of (depth, face id): independent of arrival order
+  atomicMin(&s_key[((i - ty0) * Rt<S>::tile + (j - tx0)) * S + k], key);     // LDS; min of (depth, face id): independent of arrival order
 }
 
-// One workgroup per (frame, 64 x 64 tile).  (A) the frame's faces are streamed 256 at a time and those whose snapped box
-// meets the tile are compacted, in face order, into an LDS list; (B) whenever the list could overflow, and at the end, the
-// listed faces are rasterised into the tile's 64-bit (depth bits, face id) keys with one LDS atomicMin per fragment: a lane
-// owns a face and walks its box, a face with a large box is queued and walked by a whole wave; (C) the tile is resolved
-// and shaded pixel-parallel.
+// every sample of pixel (j, i) from the edge values at its sample 0
+template <int S>
+__device__ __forceinline__ void fragments(const FaceSetup& s, int f, int j, int i, long e0, long e1, long e2, long b0, long b1, long b2,
+                                          float near, float far, int tx0, int ty0, unsigned long long* s_key) {
+  fragment<S>(s, f, j, i, 0, e0, e1, e2, b0, b1, b2, near, far, tx0, ty0, s_key);
+#pragma unroll
+  for (int k = 1; k < S; ++k)
+    fragment<S>(s, f, j, i, k, e0 + sample_step<S>(s.x1, s.y1, s.x2, s.y2, k), e1 + sample_step<S>(s.x2, s.y2, s.x0, s.y0, k),
+                e2 + sample_step<S>(s.x0, s.y0, s.x1, s.y1, k), b0, b1, b2, near, far, tx0, ty0, s_key);
+}
+
+// the untextured colour of face `s` at the point whose edge values are e0, e1, e2: R | G << 8 | B << 16 | 255 << 24
+__device__ __forceinline__ unsigned shade_flat(const FaceSetup& s, const float* __restrict__ nrm, long e0, long e1, long e2,
+                                               const float* __restrict__ lights, int n_lights, float base_r, float base_g,
+                                               float base_b, float amb_r, float amb_g, float amb_b) {
+  float w0, w1, w2;
+  const float iz = inv_depth(s, e0, e1, e2, w0, w1, w2);
+  // perspective-correct weights w_k q_k / (sum), then the interpolated normal
+  const float p0 = w0 * s.q0 / iz, p1 = w1 * s.q1 / iz, p2 = w2 * s.q2 / iz;
+  const float diff = lambert_diffuse(nrm, s, p0, p1, p2, lights, n_lights);
+  const float cr = fminf(fmaxf(base_r * (amb_r + diff), 0.f), 1.f), cg = fminf(fmaxf(base_g * (amb_g + diff), 0.f), 1.f),
+              cb = fminf(fmaxf(base_b * (amb_b + diff), 0.f), 1.f);
+  const unsigned ur = (unsigned)floorf(255.f * cr + 0.5f), ug = (unsigned)floorf(255.f * cg + 0.5f),
+                 ub = (unsigned)floorf(255.f * cb + 0.5f);
+  return ur | (ug << 8) | (ub << 16) | 0xff000000u;
+}
+
+// The resolve of four RGBA words, (b0 + b1 + b2 + b3 + 2) >> 2 in every byte: the even and the odd bytes are summed in 16-bit
+// lanes (a sum is at most 4 * 255 + 2), which start at the rounding term.
+struct Resolve4 {
+  unsigned even = 0x00020002u, odd = 0x00020002u;
+  __device__ __forceinline__ void add(unsigned c) { even += c & 0x00ff00ffu; odd += (c >> 8) & 0x00ff00ffu; }
+  __device__ __forceinline__ unsigned word() const { return ((even >> 2) & 0x00ff00ffu) | (((odd >> 2) & 0x00ff00ffu) << 8); }
+};
+
+// One workgroup per (frame, tile): 64 x 64 pixels at one sample per pixel, 32 x 32 at four, 4096 keys either way.  (A) the
+// frame's faces are streamed 256 at a time and those whose snapped box meets the tile are compacted, in face order, into an
+// LDS list; (B) whenever the list could overflow, and at the end, the listed faces are rasterised into the tile's 64-bit
+// (depth bits, face id) keys, one per sample at [pixel][sample], with one LDS atomicMin per fragment: a lane owns a face and
+// walks its box, a face with a large box is queued and walked by a whole wave; the samples of a pixel take their edge values
+// from sample 0's by sample_step; (C) the tile is resolved and shaded pixel-parallel: every covered sample at its own
+// position, and at four samples the mean of the four (Resolve4), an uncovered sample counting as the background's bytes.
+// sample_depth is written at four samples only (at one it is `depth`).
+template <int S>
 __global__ __launch_bounds__(RT_THREADS) void render_raster_kernel(const float* __restrict__ screen, const float* __restrict__ normals,
                                                                    const int* __restrict__ faces, const float* __restrict__ shade,
                                                                    const float* __restrict__ lights, int n_lights,
                                                                    unsigned* __restrict__ rgba, float* __restrict__ depth,
-                                                                   int* __restrict__ face_id, int V, int F, int H, int W,
-                                                                   int tiles_x, int tiles_y, float near, float far, unsigned bg) {
-  __shared__ unsigned long long s_key[RT_TILE * RT_TILE];   // 32 KB
+                                                                   int* __restrict__ face_id, float* __restrict__ sample_depth, int V,
+                                                                   int F, int H, int W, int tiles_x, int tiles_y, float near, float far,
+                                                                   unsigned bg) {
+  constexpr int TILE = Rt<S>::tile;
+  __shared__ unsigned long long s_key[Rt<S>::keys];   // 32 KB
   __shared__ int s_list[RT_CAP];
   __shared__ int s_big[RT_CAP];
   __shared__ int s_wcnt[2][RT_THREADS / 64];
@@ -199,12 +266,12 @@ __global__ __launch_bounds__(RT_THREADS) void render_raster_kernel(const float* 
   const int tiles = tiles_x * tiles_y;
   const int b = blockIdx.x / tiles, tile = blockIdx.x - b * tiles;
   const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
-  const int tx0 = tx * RT_TILE, ty0 = ty * RT_TILE;
-  const int tx1 = min(tx0 + RT_TILE, W) - 1, ty1 = min(ty0 + RT_TILE, H) - 1;
+  const int tx0 = tx * TILE, ty0 = ty * TILE;
+  const int tx1 = min(tx0 + TILE, W) - 1, ty1 = min(ty0 + TILE, H) - 1;
   const float* scr = screen + (long)b * V * 3;
   const float* nrm = normals + (long)b * V * 3;
 
-  for (int p = tid; p < RT_TILE * RT_TILE; p += RT_THREADS) s_key[p] = RT_EMPTY;
+  for (int p = tid; p < Rt<S>::keys; p += RT_THREADS) s_key[p] = RT_EMPTY;
   if (tid == 0) s_nbig = 0;
   int count = 0;   // uniform: entries of s_list
   int it = 0;
@@ -212,7 +279,7 @@ __global__ __launch_bounds__(RT_THREADS) void render_raster_kernel(const float* 
     // (A) compaction of faces [base, base + 256) behind the `count` entries already listed
     const int f = base + tid;
     bool keep = false;
-    if (f < F) keep = face_setup(faces, scr, f, V, near, tx0, ty0, tx1, ty1).ok;
+    if (f < F) keep = face_setup<S>(faces, scr, f, V, near, tx0, ty0, tx1, ty1).ok;
     const unsigned long long m = __ballot(keep);
     if (lane == 0) s_wcnt[it & 1][wid] = __popcll(m);
     __syncthreads();     // also orders the key initialisation / the previous pass before what follows
@@ -230,22 +297,22 @@ __global__ __launch_bounds__(RT_THREADS) void render_raster_kernel(const float* 
     // (B) coverage, face-parallel
     for (int e = tid; e < count; e += RT_THREADS) {
       const int g = s_list[e];
-      const FaceSetup s = face_setup(faces, scr, g, V, near, tx0, ty0, tx1, ty1);
+      const FaceSetup s = face_setup<S>(faces, scr, g, V, near, tx0, ty0, tx1, ty1);
       const int bw = s.jmax - s.jmin + 1, bh = s.imax - s.imin + 1;
-      if (bw * bh > RT_WAVE_WALK) {
+      if (bw * bh > Rt<S>::walk) {
         s_big[atomicAdd(&s_nbig, 1)] = g;       // the order of this queue does not reach the result (min of keys)
         continue;
       }
       const long b0 = edge_bias(s.x1, s.y1, s.x2, s.y2), b1 = edge_bias(s.x2, s.y2, s.x0, s.y0), b2 = edge_bias(s.x0, s.y0, s.x1, s.y1);
       long r0, r1, r2;
-      edges_at(s, s.jmin, s.imin, r0, r1, r2);
+      edges_at<S>(s, s.jmin, s.imin, 0, r0, r1, r2);
       // d e / d j = -256 (by - ay), d e / d i = 256 (bx - ax): exact integer steps
       const long a0 = -256L * (s.y2 - s.y1), a1 = -256L * (s.y0 - s.y2), a2 = -256L * (s.y1 - s.y0);
       const long c0 = 256L * (s.x2 - s.x1), c1 = 256L * (s.x0 - s.x2), c2 = 256L * (s.x1 - s.x0);
       for (int i = s.imin; i <= s.imax; ++i) {
         long e0 = r0, e1 = r1, e2 = r2;
         for (int j = s.jmin; j <= s.jmax; ++j) {
-          fragment(s, g, j, i, e0, e1, e2, b0, b1, b2, near, far, tx0, ty0, s_key);
+          fragments<S>(s, g, j, i, e0, e1, e2, b0, b1, b2, near, far, tx0, ty0, s_key);
           e0 += a0; e1 += a1; e2 += a2;
         }
         r0 += c0; r1 += c1; r2 += c2;
@@ -255,14 +322,14 @@ __global__ __launch_bounds__(RT_THREADS) void render_raster_kernel(const float* 
     const int nbig = s_nbig;
     for (int e = wid; e < nbig; e += RT_THREADS / 64) {
       const int g = s_big[e];
-      const FaceSetup s = face_setup(faces, scr, g, V, near, tx0, ty0, tx1, ty1);
+      const FaceSetup s = face_setup<S>(faces, scr, g, V, near, tx0, ty0, tx1, ty1);
       const long b0 = edge_bias(s.x1, s.y1, s.x2, s.y2), b1 = edge_bias(s.x2, s.y2, s.x0, s.y0), b2 = edge_bias(s.x0, s.y0, s.x1, s.y1);
       const int bw = s.jmax - s.jmin + 1, n = bw * (s.imax - s.imin + 1);
       for (int p = lane; p < n; p += 64) {
         const int i = s.imin + p / bw, j = s.jmin + p % bw;
         long e0, e1, e2;
-        edges_at(s, j, i, e0, e1, e2);
-        fragment(s, g, j, i, e0, e1, e2, b0, b1, b2, near, far, tx0, ty0, s_key);
+        edges_at<S>(s, j, i, 0, e0, e1, e2);
+        fragments<S>(s, g, j, i, e0, e1, e2, b0, b1, b2, near, far, tx0, ty0, s_key);
       }
     }
     __syncthreads();     // before the lists are refilled
@@ -271,35 +338,61 @@ __global__ __launch_bounds__(RT_THREADS) void render_raster_kernel(const float* 
   }
   __syncthreads();
 
-  // (C) resolve and shade: a wave stores one 64-pixel row segment (256 contiguous bytes of RGBA) per step
+  // (C) resolve and shade: a wave stores row segments of the tile's width (256 contiguous bytes of RGBA at one sample per
+  // pixel, two of 128 at four) per step
   const float base_r = shade[0], base_g = shade[1], base_b = shade[2], amb_r = shade[3], amb_g = shade[4], amb_b = shade[5];
-  for (int p = tid; p < RT_TILE * RT_TILE; p += RT_THREADS) {
-    const int i = ty0 + p / RT_TILE, j = tx0 + p % RT_TILE;
+  for (int p = tid; p < TILE * TILE; p += RT_THREADS) {
+    const int i = ty0 + p / TILE, j = tx0 + p % TILE;
     if (i > ty1 || j > tx1) continue;
-    const unsigned long long key = s_key[p];
     const long o = ((long)b * H + i) * W + j;
-    if (key == RT_EMPTY) {
-      rgba[o] = bg;
-      depth[o] = 0.f;
-      if (face_id != nullptr) face_id[o] = -1;
-      continue;
+    if constexpr (S == 1) {
+      const unsigned long long key = s_key[p];
+      if (key == RT_EMPTY) {
+        rgba[o] = bg;
+        depth[o] = 0.f;
+        if (face_id != nullptr) face_id[o] = -1;
+        continue;
+      }
+      const int g = (int)(unsigned)(key & 0xffffffffull);
+      const FaceSetup s = face_setup<S>(faces, scr, g, V, near, tx0, ty0, tx1, ty1);
+      long e0, e1, e2;
+      edges_at<S>(s, j, i, 0, e0, e1, e2);
+      rgba[o] = shade_flat(s, nrm, e0, e1, e2, lights, n_lights, base_r, base_g, base_b, amb_r, amb_g, amb_b);
+      depth[o] = __uint_as_float((unsigned)(key >> 32));
+      if (face_id != nullptr) face_id[o] = g;
+    } else {
+      Resolve4 sum;
+      unsigned dmin = 0xffffffffu;      // depths are positive, so their bits order as they do
+      int ids[S];
+      float ds[S];
+      int last = -1;                    // the set-up is kept while consecutive samples show the same face
+      FaceSetup s;
+#pragma unroll
+      for (int k = 0; k < S; ++k) {
+        const unsigned long long key = s_key[p * S + k];
+        unsigned c = bg;
+        ids[k] = -1;
+        ds[k] = 0.f;
+        if (key != RT_EMPTY) {
+          const int g = (int)(unsigned)(key & 0xffffffffull);
+          if (g != last) {
+            s = face_setup<S>(faces, scr, g, V, near, tx0, ty0, tx1, ty1);
+            last = g;
+          }
+          long e0, e1, e2;
+          edges_at<S>(s, j, i, k, e0, e1, e2);
+          c = shade_flat(s, nrm, e0, e1, e2, lights, n_lights, base_r, base_g, base_b, amb_r, amb_g, amb_b);
+          ids[k] = g;
+          ds[k] = __uint_as_float((unsigned)(key >> 32));
+          dmin = min(dmin, (unsigned)(key >> 32));
+        }
+        sum.add(c);
+      }
+      rgba[o] = sum.word();
+      depth[o] = dmin == 0xffffffffu ? 0.f : __uint_as_float(dmin);
+      if (face_id != nullptr) *(int4*)(face_id + o * 4) = make_int4(ids[0], ids[1], ids[2], ids[3]);
+      if (sample_depth != nullptr) *(float4*)(sample_depth + o * 4) = make_float4(ds[0], ds[1], ds[2], ds[3]);
     }
-    const int g = (int)(unsigned)(key & 0xffffffffull);
-    const FaceSetup s = face_setup(faces, scr, g, V, near, tx0, ty0, tx1, ty1);
-    long e0, e1, e2;
-    edges_at(s, j, i, e0, e1, e2);
-    float w0, w1, w2;
-    const float iz = inv_depth(s, e0, e1, e2, w0, w1, w2);
-    // perspective-correct weights w_k q_k / (sum), then the interpolated normal
-    const float p0 = w0 * s.q0 / iz, p1 = w1 * s.q1 / iz, p2 = w2 * s.q2 / iz;
-    const float diff = lambert_diffuse(nrm, s, p0, p1, p2, lights, n_lights);
-    const float cr = fminf(fmaxf(base_r * (amb_r + diff), 0.f), 1.f), cg = fminf(fmaxf(base_g * (amb_g + diff), 0.f), 1.f),
-                cb = fminf(fmaxf(base_b * (amb_b + diff), 0.f), 1.f);
-    const unsigned ur = (unsigned)floorf(255.f * cr + 0.5f), ug = (unsigned)floorf(255.f * cg + 0.5f),
-                   ub = (unsigned)floorf(255.f * cb + 0.5f);
-    rgba[o] = ur | (ug << 8) | (ub << 16) | 0xff000000u;
-    depth[o] = __uint_as_float((unsigned)(key >> 32));
-    if (face_id != nullptr) face_id[o] = g;
   }
 }
 
@@ -350,14 +443,69 @@ __device__ __forceinline__ F3 texture_bilinear(const float4* __restrict__ lvl, i
             gy * (gx * t00.z + fx * t10.z) + fy * (gx * t01.z + fx * t11.z)};
 }
 
-// One workgroup per (frame, 64 x 16 strip); pixel-parallel in stage (C)'s mapping, so a wave reads 64 contiguous face ids and
-// stores 256 contiguous bytes of RGBA per step.  The face's set-up, the barycentrics and the lighting are the routines of the
-// raster pass; the level table (offset, width, height of every level) is built once per workgroup in LDS.
+// The textured colour of face g (set-up `s`) at the point whose edge values are e0, e1, e2: R | G << 8 | B << 16 | 255 << 24, and
+// (u, v, lambda) as sampled.  The level table lvl_off / lvl_w / lvl_h holds the offset, width and height of every level.
+struct TexturedArgs {
+  const float* nrm; const int* faces; const float* vt; const int* ft; const float4* pyramid; const float* lights;
+  const int *lvl_off, *lvl_w, *lvl_h;
+  int n_lights, Nt, L;
+  float amb_r, amb_g, amb_b, Wtf, Htf, top;
+};
+__device__ __forceinline__ unsigned shade_textured(const FaceSetup& s, int g, long e0, long e1, long e2, const TexturedArgs& t, F3& uvl) {
+  float w0, w1, w2;
+  const float iz = inv_depth(s, e0, e1, e2, w0, w1, w2);
+  const float p0 = w0 * s.q0 / iz, p1 = w1 * s.q1 / iz, p2 = w2 * s.q2 / iz;
+  // per-corner texture coordinates in the face's oriented order: face_setup swapped corners 1 and 2 iff it swapped the ids
+  const I3 ti = *(const I3*)(t.ft + (long)g * 3);
+  const bool swapped = s.i1 != t.faces[(long)g * 3 + 1];
+  const int k0 = ti.a, k1 = swapped ? ti.c : ti.b, k2 = swapped ? ti.b : ti.c;
+  float2 t0 = make_float2(0.f, 0.f), t1 = t0, t2 = t0;
+  if ((unsigned)k0 < (unsigned)t.Nt) t0 = *(const float2*)(t.vt + (long)k0 * 2);
+  if ((unsigned)k1 < (unsigned)t.Nt) t1 = *(const float2*)(t.vt + (long)k1 * 2);
+  if ((unsigned)k2 < (unsigned)t.Nt) t2 = *(const float2*)(t.vt + (long)k2 * 2);
+  const float u = (p0 * t0.x + p1 * t1.x) + p2 * t2.x, v = (p0 * t0.y + p1 * t1.y) + p2 * t2.y;
+  // analytic level of detail: d w_k / d j = a_k / A, d w_k / d i = c_k / A with stage (B)'s integer edge steps
+  const float A = (float)s.area;
+  const float g0 = s.q0 * ((float)(-256L * (s.y2 - s.y1)) / A), g1 = s.q1 * ((float)(-256L * (s.y0 - s.y2)) / A),
+              g2 = s.q2 * ((float)(-256L * (s.y1 - s.y0)) / A);
+  const float h0 = s.q0 * ((float)(256L * (s.x2 - s.x1)) / A), h1 = s.q1 * ((float)(256L * (s.x0 - s.x2)) / A),
+              h2 = s.q2 * ((float)(256L * (s.x1 - s.x0)) / A);
+  const float dDj = (g0 + g1) + g2, dDi = (h0 + h1) + h2;
+  const float duj = (((g0 * t0.x + g1 * t1.x) + g2 * t2.x) - u * dDj) / iz, dvj = (((g0 * t0.y + g1 * t1.y) + g2 * t2.y) - v * dDj) / iz;
+  const float dui = (((h0 * t0.x + h1 * t1.x) + h2 * t2.x) - u * dDi) / iz, dvi = (((h0 * t0.y + h1 * t1.y) + h2 * t2.y) - v * dDi) / iz;
+  const float rj2 = (t.Wtf * duj) * (t.Wtf * duj) + (t.Htf * dvj) * (t.Htf * dvj),
+              ri2 = (t.Wtf * dui) * (t.Wtf * dui) + (t.Htf * dvi) * (t.Htf * dvi);
+  float lam = 0.5f * log2f(fmaxf(rj2, ri2));
+  if (!(finite_f(rj2) && finite_f(ri2) && finite_f(lam))) lam = 0.f;
+  lam = fminf(fmaxf(lam, 0.f), t.top);
+  const float us = finite_f(u) ? u : 0.f, vs = finite_f(v) ? v : 0.f;
+  const float U = us - floorf(us), Vv = vs - floorf(vs);
+  const int l0 = min((int)floorf(lam), t.L - 1), l1 = min(l0 + 1, t.L - 1);
+  const float fl = lam - (float)l0;
+  const F3 c0 = texture_bilinear(t.pyramid + t.lvl_off[l0], t.lvl_w[l0], t.lvl_h[l0], U, Vv);
+  const F3 c1 = texture_bilinear(t.pyramid + t.lvl_off[l1], t.lvl_w[l1], t.lvl_h[l1], U, Vv);
+  const float gl = 1.f - fl;
+  const float Tr = gl * c0.x + fl * c1.x, Tg = gl * c0.y + fl * c1.y, Tb = gl * c0.z + fl * c1.z;
+  const float diff = lambert_diffuse(t.nrm, s, p0, p1, p2, t.lights, t.n_lights);
+  const float cr = fminf(fmaxf((Tr / 255.f) * (t.amb_r + diff), 0.f), 1.f), cg = fminf(fmaxf((Tg / 255.f) * (t.amb_g + diff), 0.f), 1.f),
+              cb = fminf(fmaxf((Tb / 255.f) * (t.amb_b + diff), 0.f), 1.f);
+  const unsigned ur = (unsigned)floorf(255.f * cr + 0.5f), ug = (unsigned)floorf(255.f * cg + 0.5f),
+                 ub = (unsigned)floorf(255.f * cb + 0.5f);
+  uvl = F3{us, vs, lam};
+  return ur | (ug << 8) | (ub << 16) | 0xff000000u;
+}
+
+// One workgroup per (frame, 64 x 16 strip); pixel-parallel in stage (C)'s mapping, so a wave reads 64 contiguous face ids (at
+// four samples per pixel 64 contiguous int4) and stores 256 contiguous bytes of RGBA per step.  The face's set-up, the
+// barycentrics and the lighting are the routines of the raster pass; the level table is built once per workgroup in LDS.
+// At four samples face_id is (B, H, W, 4): every sample with 0 <= id < F is shaded at its own position, any other counts as
+// `bg`, and a pixel with a shaded sample receives the mean of the four (Resolve4); uvl is not offered.
+template <int S>
 __global__ __launch_bounds__(TX_THREADS) void render_shade_textured_kernel(
     const float* __restrict__ screen, const float* __restrict__ normals, const int* __restrict__ faces, const float* __restrict__ vt,
     const int* __restrict__ ft, const float4* __restrict__ pyramid, const float* __restrict__ shade, const float* __restrict__ lights,
     int n_lights, const int* __restrict__ face_id, unsigned* __restrict__ rgba, float* __restrict__ uvl, int V, int F, int Nt,
-    int Ht, int Wt, int L, int H, int W, int tiles_x, int strips_y, float near) {
+    int Ht, int Wt, int L, int H, int W, int tiles_x, int strips_y, float near, unsigned bg) {
   __shared__ int s_off[TX_MAX_LEVELS], s_w[TX_MAX_LEVELS], s_h[TX_MAX_LEVELS];
   const int tid = threadIdx.x;
   if (tid < L) {
@@ -375,63 +523,59 @@ __global__ __launch_bounds__(TX_THREADS) void render_shade_textured_kernel(
   const int sy = rest / tiles_x, tx = rest - sy * tiles_x;
   const int tx0 = tx * RT_TILE, ty0 = sy * TX_ROWS;
   const float* scr = screen + (long)b * V * 3;
-  const float* nrm = normals + (long)b * V * 3;
-  const float amb_r = shade[3], amb_g = shade[4], amb_b = shade[5];
-  const float Wtf = (float)Wt, Htf = (float)Ht, top = (float)(L - 1);
+  TexturedArgs t;
+  t.nrm = normals + (long)b * V * 3; t.faces = faces; t.vt = vt; t.ft = ft; t.pyramid = pyramid; t.lights = lights;
+  t.lvl_off = s_off; t.lvl_w = s_w; t.lvl_h = s_h;
+  t.n_lights = n_lights; t.Nt = Nt; t.L = L;
+  t.amb_r = shade[3]; t.amb_g = shade[4]; t.amb_b = shade[5];
+  t.Wtf = (float)Wt; t.Htf = (float)Ht; t.top = (float)(L - 1);
   for (int p = tid; p < RT_TILE * TX_ROWS; p += TX_THREADS) {
     const int i = ty0 + p / RT_TILE, j = tx0 + p % RT_TILE;
     if (i >= H || j >= W) continue;
     const long o = ((long)b * H + i) * W + j;
-    const int g = face_id[o];
-    FaceSetup s;
-    s.ok = false;
-    if ((unsigned)g < (unsigned)F) s = face_setup(faces, scr, g, V, near, 0, 0, W - 1, H - 1);
-    if (!s.ok) {                      // background, or a face id the raster pass cannot have written
-      if (uvl != nullptr) *(F3*)(uvl + o * 3) = F3{0.f, 0.f, 0.f};
-      continue;
+    if constexpr (S == 1) {
+      const int g = face_id[o];
+      FaceSetup s;
+      s.ok = false;
+      if ((unsigned)g < (unsigned)F) s = face_setup<S>(faces, scr, g, V, near, 0, 0, W - 1, H - 1);
+      if (!s.ok) {                      // background, or a face id the raster pass cannot have written
+        if (uvl != nullptr) *(F3*)(uvl + o * 3) = F3{0.f, 0.f, 0.f};
+        continue;
+      }
+      long e0, e1, e2;
+      edges_at<S>(s, j, i, 0, e0, e1, e2);
+      F3 sampled;
+      rgba[o] = shade_textured(s, g, e0, e1, e2, t, sampled);
+      if (uvl != nullptr) *(F3*)(uvl + o * 3) = sampled;
+    } else {
+      const int4 id4 = *(const int4*)(face_id + o * 4);
+      const int ids[4] = {id4.x, id4.y, id4.z, id4.w};
+      Resolve4 sum;
+      bool any = false;
+      int last = -1;                    // the set-up is kept while consecutive samples show the same face
+      FaceSetup s;
+      s.ok = false;
+#pragma unroll
+      for (int k = 0; k < S; ++k) {
+        const int g = ids[k];
+        unsigned c = bg;
+        if ((unsigned)g < (unsigned)F) {
+          if (g != last) {
+            s = face_setup<S>(faces, scr, g, V, near, 0, 0, W - 1, H - 1);
+            last = g;
+          }
+          if (s.ok) {
+            long e0, e1, e2;
+            edges_at<S>(s, j, i, k, e0, e1, e2);
+            F3 sampled;
+            c = shade_textured(s, g, e0, e1, e2, t, sampled);
+            any = true;
+          }
+        }
+        sum.add(c);
+      }
+      if (any) rgba[o] = sum.word();
     }
-    long e0, e1, e2;
-    edges_at(s, j, i, e0, e1, e2);
-    float w0, w1, w2;
-    const float iz = inv_depth(s, e0, e1, e2, w0, w1, w2);
-    const float p0 = w0 * s.q0 / iz, p1 = w1 * s.q1 / iz, p2 = w2 * s.q2 / iz;
-    // per-corner texture coordinates in the face's oriented order: face_setup swapped corners 1 and 2 iff it swapped the ids
-    const I3 ti = *(const I3*)(ft + (long)g * 3);
-    const bool swapped = s.i1 != faces[(long)g * 3 + 1];
-    const int k0 = ti.a, k1 = swapped ? ti.c : ti.b, k2 = swapped ? ti.b : ti.c;
-    float2 t0 = make_float2(0.f, 0.f), t1 = t0, t2 = t0;
-    if ((unsigned)k0 < (unsigned)Nt) t0 = *(const float2*)(vt + (long)k0 * 2);
-    if ((unsigned)k1 < (unsigned)Nt) t1 = *(const float2*)(vt + (long)k1 * 2);
-    if ((unsigned)k2 < (unsigned)Nt) t2 = *(const float2*)(vt + (long)k2 * 2);
-    const float u = (p0 * t0.x + p1 * t1.x) + p2 * t2.x, v = (p0 * t0.y + p1 * t1.y) + p2 * t2.y;
-    // analytic level of detail: d w_k / d j = a_k / A, d w_k / d i = c_k / A with stage (B)'s integer edge steps
-    const float A = (float)s.area;
-    const float g0 = s.q0 * ((float)(-256L * (s.y2 - s.y1)) / A), g1 = s.q1 * ((float)(-256L * (s.y0 - s.y2)) / A),
-                g2 = s.q2 * ((float)(-256L * (s.y1 - s.y0)) / A);
-    const float h0 = s.q0 * ((float)(256L * (s.x2 - s.x1)) / A), h1 = s.q1 * ((float)(256L * (s.x0 - s.x2)) / A),
-                h2 = s.q2 * ((float)(256L * (s.x1 - s.x0)) / A);
-    const float dDj = (g0 + g1) + g2, dDi = (h0 + h1) + h2;
-    const float duj = (((g0 * t0.x + g1 * t1.x) + g2 * t2.x) - u * dDj) / iz, dvj = (((g0 * t0.y + g1 * t1.y) + g2 * t2.y) - v * dDj) / iz;
-    const float dui = (((h0 * t0.x + h1 * t1.x) + h2 * t2.x) - u * dDi) / iz, dvi = (((h0 * t0.y + h1 * t1.y) + h2 * t2.y) - v * dDi) / iz;
-    const float rj2 = (Wtf * duj) * (Wtf * duj) + (Htf * dvj) * (Htf * dvj), ri2 = (Wtf * dui) * (Wtf * dui) + (Htf * dvi) * (Htf * dvi);
-    float lam = 0.5f * log2f(fmaxf(rj2, ri2));
-    if (!(finite_f(rj2) && finite_f(ri2) && finite_f(lam))) lam = 0.f;
-    lam = fminf(fmaxf(lam, 0.f), top);
-    const float us = finite_f(u) ? u : 0.f, vs = finite_f(v) ? v : 0.f;
-    const float U = us - floorf(us), Vv = vs - floorf(vs);
-    const int l0 = min((int)floorf(lam), L - 1), l1 = min(l0 + 1, L - 1);
-    const float fl = lam - (float)l0;
-    const F3 c0 = texture_bilinear(pyramid + s_off[l0], s_w[l0], s_h[l0], U, Vv);
-    const F3 c1 = texture_bilinear(pyramid + s_off[l1], s_w[l1], s_h[l1], U, Vv);
-    const float gl = 1.f - fl;
-    const float Tr = gl * c0.x + fl * c1.x, Tg = gl * c0.y + fl * c1.y, Tb = gl * c0.z + fl * c1.z;
-    const float diff = lambert_diffuse(nrm, s, p0, p1, p2, lights, n_lights);
-    const float cr = fminf(fmaxf((Tr / 255.f) * (amb_r + diff), 0.f), 1.f), cg = fminf(fmaxf((Tg / 255.f) * (amb_g + diff), 0.f), 1.f),
-                cb = fminf(fmaxf((Tb / 255.f) * (amb_b + diff), 0.f), 1.f);
-    const unsigned ur = (unsigned)floorf(255.f * cr + 0.5f), ug = (unsigned)floorf(255.f * cg + 0.5f),
-                   ub = (unsigned)floorf(255.f * cb + 0.5f);
-    rgba[o] = ur | (ug << 8) | (ub << 16) | 0xff000000u;
-    if (uvl != nullptr) *(F3*)(uvl + o * 3) = F3{us, vs, lam};
   }
 }
 
@@ -463,21 +607,46 @@ extern "C" int msmd_texture_mips(const void* img, int Ht, int Wt, int channels, 
   MSMD_RETURN_LAST();
 }
 
-extern "C" int msmd_render_shade_textured(const float* screen, const float* normals, const int* faces, const float* vt, const int* ft,
-                                          const float* pyramid, int Ht, int Wt, const float* shade, const float* lights,
-                                          int n_lights, const int* face_id, void* rgba, float* uvl, int B, int V, int F, int Nt,
-                                          int H, int W, float near, msmd_stream_t stream) {
+namespace {
+template <int S>
+int launch_shade_textured(const float* screen, const float* normals, const int* faces, const float* vt, const int* ft,
+                          const float* pyramid, int Ht, int Wt, const float* shade, const float* lights, int n_lights,
+                          const int* face_id, void* rgba, float* uvl, int B, int V, int F, int Nt, int H, int W, float near,
+                          unsigned background, msmd_stream_t stream) {
   if (B <= 0 || V <= 0 || F <= 0 || Nt <= 0 || H <= 0 || W <= 0 || n_lights < 0 || !(near > 0.f) || face_id == nullptr ||
       msmd_texture_texels(Ht, Wt) < 0) return 1;
+  if (S == 4 && ((size_t)face_id & 15) != 0) return 1;      // read as int4
   int L = 1;
   for (int m = Ht > Wt ? Ht : Wt; m > 1; m >>= 1) ++L;
   const int tiles_x = (W + RT_TILE - 1) / RT_TILE, strips_y = (H + TX_ROWS - 1) / TX_ROWS;
   const long grid = (long)B * tiles_x * strips_y;
   if (grid > 2147483647L) return 1;
-  hipLaunchKernelGGL(render_shade_textured_kernel, dim3((unsigned)grid), dim3(TX_THREADS), 0, (hipStream_t)stream, screen, normals,
+  hipLaunchKernelGGL(render_shade_textured_kernel<S>, dim3((unsigned)grid), dim3(TX_THREADS), 0, (hipStream_t)stream, screen, normals,
                      faces, vt, ft, (const float4*)pyramid, shade, lights, n_lights, face_id, (unsigned*)rgba, uvl, V, F, Nt, Ht, Wt, L,
-                     H, W, tiles_x, strips_y, near);
+                     H, W, tiles_x, strips_y, near, background);
   MSMD_RETURN_LAST();
+}
+}  // namespace
+
+extern "C" int msmd_render_shade_textured(const float* screen, const float* normals, const int* faces, const float* vt, const int* ft,
+                                          const float* pyramid, int Ht, int Wt, const float* shade, const float* lights,
+                                          int n_lights, const int* face_id, void* rgba, float* uvl, int B, int V, int F, int Nt,
+                                          int H, int W, float near, msmd_stream_t stream) {
+  return launch_shade_textured<1>(screen, normals, faces, vt, ft, pyramid, Ht, Wt, shade, lights, n_lights, face_id, rgba, uvl, B, V, F,
+                                  Nt, H, W, near, 0u, stream);
+}
+
+extern "C" int msmd_render_shade_textured_ms(const float* screen, const float* normals, const int* faces, const float* vt,
+                                             const int* ft, const float* pyramid, int Ht, int Wt, const float* shade,
+                                             const float* lights, int n_lights, const int* sample_face_id, void* rgba, int B, int V,
+                                             int F, int Nt, int H, int W, float near, unsigned background, int samples,
+                                             msmd_stream_t stream) {
+  if (samples == 1)
+    return launch_shade_textured<1>(screen, normals, faces, vt, ft, pyramid, Ht, Wt, shade, lights, n_lights, sample_face_id, rgba,
+                                    nullptr, B, V, F, Nt, H, W, near, background, stream);
+  if (samples != 4) return 1;
+  return launch_shade_textured<4>(screen, normals, faces, vt, ft, pyramid, Ht, Wt, shade, lights, n_lights, sample_face_id, rgba,
+                                  nullptr, B, V, F, Nt, H, W, near, background, stream);
 }
 
 extern "C" int msmd_render_vertices(const float* verts, const int* faces, const int* csr_offsets, const int* csr_faces,
@@ -491,14 +660,41 @@ extern "C" int msmd_render_vertices(const float* verts, const int* faces, const 
   MSMD_RETURN_LAST();
 }
 
+namespace {
+template <int S>
+int launch_raster(const float* screen, const float* normals, const int* faces, const float* shade, const float* lights, int n_lights,
+                  void* rgba, float* depth, int* face_id, float* sample_depth, int B, int V, int F, int H, int W, float near, float far,
+                  unsigned background, msmd_stream_t stream) {
+  if (B <= 0 || V <= 0 || F <= 0 || H <= 0 || W <= 0 || n_lights < 0 || !(near > 0.f) || !(far >= near)) return 1;
+  if (S == 4 && ((((size_t)face_id) | ((size_t)sample_depth)) & 15) != 0) return 1;      // stored as int4 / float4
+  const int tiles_x = (W + Rt<S>::tile - 1) / Rt<S>::tile, tiles_y = (H + Rt<S>::tile - 1) / Rt<S>::tile;
+  const long grid = (long)B * tiles_x * tiles_y;
+  if (grid > 2147483647L) return 1;
+  hipLaunchKernelGGL(render_raster_kernel<S>, dim3((unsigned)grid), dim3(RT_THREADS), 0, (hipStream_t)stream, screen, normals, faces,
+                     shade, lights, n_lights, (unsigned*)rgba, depth, face_id, sample_depth, V, F, H, W, tiles_x, tiles_y, near, far,
+                     background);
+  MSMD_RETURN_LAST();
+}
+}  // namespace
+
 extern "C" int msmd_render_raster(const float* screen, const float* normals, const int* faces, const float* shade,
                                   const float* lights, int n_lights, void* rgba, float* depth, int* face_id, int B, int V,
                                   int F, int H, int W, float near, float far, unsigned background, msmd_stream_t stream) {
-  if (B <= 0 || V <= 0 || F <= 0 || H <= 0 || W <= 0 || n_lights < 0 || !(near > 0.f) || !(far >= near)) return 1;
-  const int tiles_x = (W + RT_TILE - 1) / RT_TILE, tiles_y = (H + RT_TILE - 1) / RT_TILE;
-  const long grid = (long)B * tiles_x * tiles_y;
-  if (grid > 2147483647L) return 1;
-  hipLaunchKernelGGL(render_raster_kernel, dim3((unsigned)grid), dim3(RT_THREADS), 0, (hipStream_t)stream, screen, normals, faces,
-                     shade, lights, n_lights, (unsigned*)rgba, depth, face_id, V, F, H, W, tiles_x, tiles_y, near, far, background);
-  MSMD_RETURN_LAST();
+  return launch_raster<1>(screen, normals, faces, shade, lights, n_lights, rgba, depth, face_id, nullptr, B, V, F, H, W, near, far,
+                          background, stream);
+}
+
+extern "C" int msmd_render_raster_ms(const float* screen, const float* normals, const int* faces, const float* shade,
+                                     const float* lights, int n_lights, void* rgba, float* depth, int* sample_face_id,
+                                     float* sample_depth, int B, int V, int F, int H, int W, float near, float far,
+                                     unsigned background, int samples, msmd_stream_t stream) {
+  if (samples != 1 && samples != 4) return 1;
+  if (samples == 4)
+    return launch_raster<4>(screen, normals, faces, shade, lights, n_lights, rgba, depth, sample_face_id, sample_depth, B, V, F, H, W,
+                            near, far, background, stream);
+  const int rc = msmd_render_raster(screen, normals, faces, shade, lights, n_lights, rgba, depth, sample_face_id, B, V, F, H, W, near,
+                                    far, background, stream);
+  if (rc != 0 || sample_depth == nullptr) return rc;
+  // one sample per pixel: the sample's depth is the pixel's
+  return (int)hipMemcpyAsync(sample_depth, depth, (size_t)B * H * W * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream);
 }

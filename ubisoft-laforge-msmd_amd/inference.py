@@ -311,6 +311,8 @@ def build_parser():
     ap.add_argument("--eta", type=float, default=0.0, help="DDIM noise scale: 0 deterministic, 1 ancestral")
     # rendering (the reference script stops before it; 0 = off: the files written are then exactly the two pickles)
     ap.add_argument("--render_size", type=int, default=0, help="side of the square frames rendered from the result (0: none)")
+    ap.add_argument("--render_samples", type=int, default=1, choices=(1, 4),
+                    help="sample points per pixel of the rendered frames: 4 draws them anti-aliased (needs --render_size > 0)")
     ap.add_argument("--flame_model_path", type=str, default=None, help="FLAME generic_model.pkl (with --render_size)")
     ap.add_argument("--flame_lmk_embedding_path", type=str, default=None, help="FLAME landmark embedding (with --render_size)")
     ap.add_argument("--texture", type=str, default=None, help=".npz with tex_img (Ht, Wt, 3 | 4) uint8, vt (Nt, 2) and ft (F, 3) "
@@ -333,12 +335,14 @@ def build_parser():
 
 
 def parse_args(argv=None):
-    """build_parser().parse_args with the checks that span flags: --video, --texture and --flame_tex need --render_size > 0,
+    """build_parser().parse_args with the checks that span flags: --video, --render_samples 4, --texture and --flame_tex need --render_size > 0,
     --flame_tex and --texture exclude each other, --tex_code needs --flame_tex, and the quality lies in [1, 100]."""
     ap = build_parser()
     args = ap.parse_args(argv)
     if args.video and args.render_size <= 0:
         ap.error("--video needs --render_size > 0: there are no frames to encode")
+    if args.render_samples != 1 and args.render_size <= 0:
+        ap.error("--render_samples needs --render_size > 0: there are no frames to draw")
     if args.texture is not None and args.render_size <= 0:
         ap.error("--texture needs --render_size > 0: there are no frames to draw it on")
     if args.flame_tex is not None and args.render_size <= 0:
@@ -407,7 +411,8 @@ def main(argv=None):
     frames are JPEG-compressed on the device chunk by chunk as they are rendered (so one chunk of raw pixels is alive at a
     time), at model_args.fps, with --audio_clip as the sound track when it is a `.wav` and silent otherwise.  --texture PATH
     (an `.npz` with tex_img, vt, ft) draws the frames textured, in either form; --flame_tex PATH (an albedo `.npz` with vt, ft)
-    does so with the FLAMETex texture of --tex_code.  --style_adherence also writes `style_adherence_<clip>_seed_<s>.npy`, (T,)
+    does so with the FLAMETex texture of --tex_code.  --render_samples 4 draws the frames anti-aliased, four samples per pixel
+    (MeshRenderer(samples=4)), in every one of these forms.  --style_adherence also writes `style_adherence_<clip>_seed_<s>.npy`, (T,)
     float32: the soft adherence (lambda 10) of repetition 0's normalised coefficients to the whole normalised style clip, and
     prints its mean; it needs the style clip's coefficients to be as wide as the model's."""
     import os
@@ -448,7 +453,7 @@ def main(argv=None):
         if args.flame_lmk_embedding_path is not None:
             cfg.flame_lmk_embedding_path = args.flame_lmk_embedding_path
         flame = FLAME(cfg).to(device)
-        renderer = MeshRenderer((args.render_size, args.render_size))
+        renderer = MeshRenderer((args.render_size, args.render_size), samples=args.render_samples)
     for seed in range(args.versions_of_render):
         np.random.seed(seed)
         torch.manual_seed(seed)

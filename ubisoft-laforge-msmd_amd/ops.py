@@ -1509,25 +1509,42 @@ def render_vertices(verts, faces_i32, csr_offsets, csr_faces, view, focal, heigh
     return screen, normals
 
 
-def render_raster(screen, normals, faces_i32, shade, lights, height, width, near, far, background, want_face_id=False):
+RENDER_SAMPLES = (1, 4)
+
+
+def render_raster(screen, normals, faces_i32, shade, lights, height, width, near, far, background, want_face_id=False, samples=1,
+                  want_sample_depth=False):
     """-> (rgba (B, H, W, 4) uint8, depth (B, H, W) fp32, face_id (B, H, W) int32 or None): msmd_render_raster.
     screen / normals (B, V, 3) fp32 as render_vertices returns them; shade (6) = base rgb, ambient rgb; lights (L, 4) =
-    eye-space unit direction towards the light, intensity; background = R | G << 8 | B << 16 | A << 24."""
+    eye-space unit direction towards the light, intensity; background = R | G << 8 | B << 16 | A << 24.
+    samples = 4 (msmd_render_raster_ms) rasterises and shades four sample points per pixel: rgba is their
+    resolve, depth the least depth over the pixel's covered samples, face_id (B, H, W, 4) per sample.  want_sample_depth
+    appends sample_depth to the result: (B, H, W, 4) fp32 at four samples, 0 on an uncovered sample; (B, H, W), a copy of
+    depth, at one (that call goes through msmd_render_raster_ms as well)."""
     d = {}
     _arg("screen", screen, torch.float32, "B V 3", d)
     _arg("normals", normals, torch.float32, "B V 3", d)
     _arg("faces", faces_i32, torch.int32, "F 3", d)
     _arg("shade", shade, torch.float32, "6")
     _arg("lights", lights, torch.float32, "L 4", d)
+    if samples not in RENDER_SAMPLES:
+        raise ValueError(f"samples must be one of {RENDER_SAMPLES}, got {samples!r}")
     B, V, H, W = d["B"], d["V"], int(height), int(width)
     lib = _lib.load()
+    per_sample = (B, H, W) if samples == 1 else (B, H, W, samples)
     rgba = torch.empty(B, H, W, 4, device=screen.device, dtype=torch.uint8)
     depth = torch.empty(B, H, W, device=screen.device, dtype=torch.float32)
-    face_id = torch.empty(B, H, W, device=screen.device, dtype=torch.int32) if want_face_id else None
-    _lib.check(lib.msmd_render_raster(_p(screen), _p(normals), _p(faces_i32), _p(shade), _p(lights), lights.shape[0], _p(rgba),
-                                      _p(depth), _p(face_id), B, V, faces_i32.shape[0], H, W, float(near), float(far),
-                                      int(background) & 0xffffffff, _stream()), "msmd_render_raster")
-    return rgba, depth, face_id
+    face_id = torch.empty(per_sample, device=screen.device, dtype=torch.int32) if want_face_id else None
+    if samples == 1 and not want_sample_depth:
+        _lib.check(lib.msmd_render_raster(_p(screen), _p(normals), _p(faces_i32), _p(shade), _p(lights), lights.shape[0], _p(rgba),
+                                          _p(depth), _p(face_id), B, V, faces_i32.shape[0], H, W, float(near), float(far),
+                                          int(background) & 0xffffffff, _stream()), "msmd_render_raster")
+        return rgba, depth, face_id
+    sample_depth = torch.empty(per_sample, device=screen.device, dtype=torch.float32) if want_sample_depth else None
+    _lib.check(lib.msmd_render_raster_ms(_p(screen), _p(normals), _p(faces_i32), _p(shade), _p(lights), lights.shape[0], _p(rgba),
+                                         _p(depth), _p(face_id), _p(sample_depth), B, V, faces_i32.shape[0], H, W, float(near),
+                                         float(far), int(background) & 0xffffffff, int(samples), _stream()), "msmd_render_raster_ms")
+    return (rgba, depth, face_id, sample_depth) if want_sample_depth else (rgba, depth, face_id)
 
 
 TEXTURE_MAX_SIDE = _h("TEXTURE_MAX_SIDE")
@@ -1548,12 +1565,22 @@ def texture_pyramid(img_u8):
 
 
 def render_shade_textured(screen, normals, faces_i32, vt, ft, pyramid, tex_height, tex_width, shade, lights, face_id, rgba, near,
-                          want_uvl=False):
+                          want_uvl=False, samples=1, background=None):
     """Overwrites rgba (B, H, W, 4) uint8 at the pixels face_id (B, H, W) int32 marks as covered with the mip-mapped,
     trilinearly sampled texture under render_raster's lighting: msmd_render_shade_textured.  screen / normals / faces / shade /
     lights as render_raster takes them; vt (Nt, 2) fp32, ft (F, 3) int32 per-corner indices into vt; pyramid as
     texture_pyramid returns it for a tex_height x tex_width image.  -> uvl (B, H, W, 3) fp32 = (u, v, lambda) per pixel (zeros
-    on the background) if want_uvl, else None."""
+    on the background) if want_uvl, else None.
+    samples = 4 (msmd_render_shade_textured_ms): face_id is render_raster's (B, H, W, 4) at four samples, every
+    covered sample is shaded at its own position and every pixel with a covered sample receives the resolve of its four, an
+    uncovered sample counting as `background` (R | G << 8 | B << 16 | A << 24, the one render_raster was given: required).
+    There is no uvl at four samples: want_uvl is a ValueError."""
+    if samples not in RENDER_SAMPLES:
+        raise ValueError(f"samples must be one of {RENDER_SAMPLES}, got {samples!r}")
+    if samples != 1 and want_uvl:
+        raise ValueError("(u, v, level of detail) is per pixel: it is not offered at four samples per pixel")
+    if samples != 1 and background is None:
+        raise ValueError("samples=4 needs the background the raster pass was given: its uncovered samples take part in the resolve")
     d = {}
     _arg("screen", screen, torch.float32, "B V 3", d)
     _arg("normals", normals, torch.float32, "B V 3", d)
@@ -1562,7 +1589,7 @@ def render_shade_textured(screen, normals, faces_i32, vt, ft, pyramid, tex_heigh
     _arg("ft", ft, torch.int32, "F 3", d)
     _arg("shade", shade, torch.float32, "6")
     _arg("lights", lights, torch.float32, "L 4", d)
-    _arg("face_id", face_id, torch.int32, "B H W", d)
+    _arg("face_id", face_id, torch.int32, "B H W" if samples == 1 else f"B H W {samples}", d)
     _arg("rgba", rgba, torch.uint8, "B H W 4", d)
     B, V, Fc, H, W = (d[k] for k in "BVFHW")
     lib = _lib.load()
@@ -1571,6 +1598,12 @@ def render_shade_textured(screen, normals, faces_i32, vt, ft, pyramid, tex_heigh
     if n < 0:
         raise ValueError(f"a {Ht} x {Wt} texture is outside [1, {TEXTURE_MAX_SIDE}]")
     _arg("pyramid", pyramid, torch.float32, (n, 4))
+    if samples != 1:
+        _lib.check(lib.msmd_render_shade_textured_ms(_p(screen), _p(normals), _p(faces_i32), _p(vt), _p(ft), _p(pyramid), Ht, Wt,
+                                                     _p(shade), _p(lights), lights.shape[0], _p(face_id), _p(rgba), B, V, Fc,
+                                                     vt.shape[0], H, W, float(near), int(background) & 0xffffffff, int(samples),
+                                                     _stream()), "msmd_render_shade_textured_ms")
+        return None
     uvl = torch.empty(B, H, W, 3, device=screen.device, dtype=torch.float32) if want_uvl else None
     _lib.check(lib.msmd_render_shade_textured(_p(screen), _p(normals), _p(faces_i32), _p(vt), _p(ft), _p(pyramid), Ht, Wt,
                                               _p(shade), _p(lights), lights.shape[0], _p(face_id), _p(rgba), _p(uvl), B, V, Fc,

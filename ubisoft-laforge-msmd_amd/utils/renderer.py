@@ -13,6 +13,11 @@ magnification, GL_LINEAR_MIPMAP_LINEAR minification with an analytic per-pixel l
 texel replaces the base colour of the shading model above.  `vt` is indexed per corner through `ft`, so a seam needs no
 duplicated vertex (the reference writes an OBJ file and reloads it for that), and normals stay those of the topology `f`.
 
+``samples=4`` draws anti-aliased: coverage, depth and shading at four sample points per pixel (the rotated grid (96, 32),
+(224, 96), (32, 160), (160, 224) in 1/256 pixel units from the pixel's top-left corner), each exactly as the pixel centre is
+treated at one sample, resolved by the rounded mean of the four samples' bytes, an uncovered sample counting as the
+background.  ``samples=1``, the default, is the pixel-centre renderer and its bits.
+
 ``render_mesh`` keeps the reference's signature and returns numpy arrays; ``render_vertices`` takes the (B, V, 3) device
 tensor FLAME produces and leaves colour and depth on the device.
 """
@@ -95,10 +100,13 @@ def rodrigues(r):
 
 
 class MeshRenderer:
-    def __init__(self, size, fov=16 / 180 * np.pi, camera_pose=None, light_pose=None, black_bg=False):
+    def __init__(self, size, fov=16 / 180 * np.pi, camera_pose=None, light_pose=None, black_bg=False, samples=1):
         self.width, self.height = int(size[0]), int(size[1])       # the reference hands `size` on as (width, height)
         if not (0 < self.width <= 16384 and 0 < self.height <= 16384):
             raise ValueError(f"size {size} is outside (0, 16384]")
+        if samples not in ops.RENDER_SAMPLES:
+            raise ValueError(f"samples must be one of {ops.RENDER_SAMPLES}, got {samples!r}")
+        self.samples = int(samples)
         self.fov = float(fov)
         self.frustum = {"near": 0.01, "far": 3.0}
         self.base_color = np.array([0.3, 0.3, 0.3])
@@ -204,7 +212,9 @@ class MeshRenderer:
         t_center (3,) per frame.  return_face_id appends the winning face id per pixel (int32, -1 = background);
         return_screen appends the vertex stage's screen (B, V, 3) = (x_s, y_s, depth) and eye-space normals (B, V, 3).
         tex_img (Ht, Wt, 3 | 4) uint8 with tex_uv = {'vt': (Nt, 2), 'ft': (F, 3)} (validate_texture) draws the mesh textured;
-        return_uv (textured only) appends (u, v, level of detail) per pixel, (B, H, W, 3) fp32 with zeros on the background."""
+        return_uv (textured only) appends (u, v, level of detail) per pixel, (B, H, W, 3) fp32 with zeros on the background.
+        With samples=4 colour is the resolve of the four samples, depth the least depth over the pixel's covered samples, the
+        face id is per sample, (B, H, W, 4), and return_uv is a ValueError."""
         if (tex_img is None) != (tex_uv is None):
             if tex_uv is None:
                 raise NotImplementedError("a texture needs a uv table: tex_uv = {'vt', 'ft'} (there are no default per-vertex "
@@ -212,6 +222,8 @@ class MeshRenderer:
             raise TypeError("tex_uv is given without tex_img")
         if return_uv and tex_img is None:
             raise TypeError("return_uv needs tex_img and tex_uv")
+        if return_uv and self.samples != 1:
+            raise ValueError("return_uv is per pixel: it is not offered at four samples per pixel")
         if not torch.is_tensor(vertices) or not vertices.is_cuda or vertices.dim() != 3 or vertices.shape[2] != 3:
             raise TypeError("vertices must be a (B, V, 3) CUDA tensor")
         device = vertices.device
@@ -227,14 +239,15 @@ class MeshRenderer:
         focal = 1.0 / np.tan(self.fov / 2.0)
         screen, normals = ops.render_vertices(verts, faces_d, off, ids, view, focal, self.height, self.width, tc_d, rot_d)
         r, g, b = self.bg_color
+        background = r | g << 8 | b << 16 | 255 << 24
         rgba, depth, face_id = ops.render_raster(screen, normals, faces_d, shade, lights, self.height, self.width,
-                                                 self.frustum["near"], self.frustum["far"], r | g << 8 | b << 16 | 255 << 24,
-                                                 want_face_id=return_face_id or tex_img is not None)
+                                                 self.frustum["near"], self.frustum["far"], background,
+                                                 want_face_id=return_face_id or tex_img is not None, samples=self.samples)
         uvl = None
         if tex_img is not None:
             pyramid, vt, ft, tex_h, tex_w = self._texture(tex_img, tex_uv, faces_d.shape[0], device)
             uvl = ops.render_shade_textured(screen, normals, faces_d, vt, ft, pyramid, tex_h, tex_w, shade, lights, face_id, rgba,
-                                            self.frustum["near"], want_uvl=return_uv)
+                                            self.frustum["near"], want_uvl=return_uv, samples=self.samples, background=background)
         out = (rgba[..., :3], depth)
         if return_face_id:
             out += (face_id,)
