@@ -1238,6 +1238,40 @@ int msmd_face_crop(const void* frames, long frame_stride, long row_stride, int p
                    const double* inverse, const float* table, int out_h, int out_w, int swap_rb, void* out, int out_dtype,
                    void* crop_u8, msmd_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Expression code and jaw pose from model-space landmarks: a per-frame geometric fit of FLAME.
+ *
+ * The model.  Global, neck and eye rotations at identity, shape fixed per subject; expression e (NE), jaw axis-angle theta.
+ *   R = Rodrigues(theta) in utils/lbs.py's convention (angle = |theta + 1e-8|, direction = theta / angle), M = R - I.
+ *   Landmark k is l_k = X_k + M Y_k with X_k and Y_k (3 each) affine in [e | vec(M)]: six rows per landmark (X's three
+ *   coordinates, then Y's) of NC = NE + 9 coefficients in `tab` (K, 6, NC) float64, and their constants in `tab0` (S, K, 6)
+ *   float64, one set per subject (utils/expression_fit.reduce_flame builds both).
+ * The objective, per frame: f(p) = sum_k w_k |l_k(p) - y_k|^2 + lambda_exp |e|^2 + lambda_jaw |theta|^2, p = [e | free theta];
+ *   y = landmarks (n, K, 3) fp32, w (K) float64 >= 0, shared by the frames.  jaw_dof 0: theta = 0; 1: theta_x free; 3: all free.
+ * The solver, Levenberg-Marquardt with fixed work:
+ *   1. p = 0, mu = 1e-3.
+ *   2. exactly `iterations` times: r and the analytic Jacobian Jm at p; H = Jm^T W Jm + D, g = Jm^T W r + D p (D the diagonal of
+ *      the lambdas); solve (H + mu diag H) delta = -g over the free parameters by Cholesky; if f(p + delta) <= f(p): p += delta,
+ *      mu = max(mu / 10, 1e-9); otherwise mu = 10 mu and p stays -- a rejected step uses up its iteration.  A pivot that is not
+ *      positive counts as a rejection and sets status bit 1.
+ *   3. no data-dependent exit; 4. a frame's result depends on nothing outside that frame.
+ *   All of it in float64; the products with W are formed as (sqrt(w) Jm)^T (sqrt(w) Jm).
+ * subject (n) int32 selects tab0's set per frame; the kernel clamps it into [0, S).
+ * Outputs, fp32: code (n, NE) = e; jaw (n, 3) = theta (locked components 0); rms (n) = sqrt(sum_k w_k |r_k|^2 / sum_k w_k) at the
+ *   returned p; status (n) int32: bit 0 = a non-finite landmark in the frame (its code, jaw and rms are NaN, status exactly 1, and
+ *   no other frame is touched), bit 1 = a factorisation was refused, the rest zero.
+ * One wave per frame, MSMD_EXPFIT_FRAMES frames per workgroup; no atomics, no host synchronisation.
+ * Returns 1 before the launch for a NULL pointer, n < 1, K outside [1, MSMD_EXPFIT_MAX_LANDMARKS], NE outside
+ * [1, MSMD_EXPFIT_MAX_EXP], S < 1, jaw_dof not 0 / 1 / 3, iterations outside [0, MSMD_EXPFIT_MAX_ITERATIONS], a lambda that is
+ * negative or NaN; otherwise 0 or the launch's hipError_t. */
+#define MSMD_EXPFIT_MAX_LANDMARKS 128
+#define MSMD_EXPFIT_MAX_EXP 61 /* NE + 3 jaw parameters <= 64: one parameter per lane of a wave */
+#define MSMD_EXPFIT_MAX_ITERATIONS 64
+#define MSMD_EXPFIT_FRAMES 4
+int msmd_expression_fit(const float* landmarks, const int* subject, const double* tab, const double* tab0, const double* w,
+                        float* code, float* jaw, float* rms, int* status, int n, int K, int NE, int S, int jaw_dof,
+                        int iterations, double lambda_exp, double lambda_jaw, msmd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1967,6 +1967,52 @@ def headpose_smooth(R, clip_offsets, table, window, want_matrix=False):
     return ypr, R_mod
 
 
+# ----------------------------------------------------------------------------- expression fit (csrc/expression_fit.hip)
+EXPFIT_MAX_LANDMARKS, EXPFIT_MAX_EXP, EXPFIT_MAX_ITERATIONS, EXPFIT_FRAMES = _h(
+    "EXPFIT_MAX_LANDMARKS", "EXPFIT_MAX_EXP", "EXPFIT_MAX_ITERATIONS", "EXPFIT_FRAMES")
+
+
+def expression_fit(landmarks, subject, tab, tab0, weights, jaw_dof=1, lambda_exp=1e-6, lambda_jaw=0.0, iterations=12):
+    """-> (code (n, NE), jaw (n, 3), rms (n)) fp32 and status (n) int32: msmd_expression_fit, the per-frame Levenberg-Marquardt
+    fit of FLAME's expression and jaw pose to landmarks (n, K, 3) fp32 in model space, the clips of a batch end to end.
+    tab (K, 6, NE + 9) and tab0 (S, K, 6) float64: the reduced model (utils/expression_fit.reduce_flame); subject (n) int32 picks
+    tab0's set per frame -- it lives on the device and is not read back here: the kernel clamps it into [0, S).
+    weights (K) float64 >= 0 (checked by utils/expression_fit.fit_expression, which has them on the host).
+    jaw_dof 0 / 1 / 3 free jaw components; `iterations` in [0, EXPFIT_MAX_ITERATIONS] of fixed work; the include file states the
+    solver and the status bits.  ValueError for a size or option outside the kernel's limits."""
+    _need_cuda(landmarks, subject, tab, tab0, weights)
+    d = {}
+    _arg("landmarks", landmarks, torch.float32, "n+ K+ 3", d)
+    _arg("subject", subject, torch.int32, "n", d)
+    _arg("tab0", tab0, torch.float64, "S+ K 6", d)
+    _arg("tab", tab, torch.float64, "K 6 NC+", d)
+    _arg("weights", weights, torch.float64, "K", d)
+    n, K, NE = d["n"], d["K"], d["NC"] - 9
+    if K > EXPFIT_MAX_LANDMARKS:
+        raise ValueError(f"{K} landmarks; the kernel takes up to {EXPFIT_MAX_LANDMARKS}")
+    if not 1 <= NE <= EXPFIT_MAX_EXP:
+        raise ValueError(f"tab has {NE} expression columns; the kernel takes 1 .. {EXPFIT_MAX_EXP}")
+    if jaw_dof not in (0, 1, 3):
+        raise ValueError(f"jaw_dof must be 0, 1 or 3, got {jaw_dof!r}")
+    iterations = int(iterations)
+    if not 0 <= iterations <= EXPFIT_MAX_ITERATIONS:
+        raise ValueError(f"iterations must be in [0, {EXPFIT_MAX_ITERATIONS}], got {iterations}")
+    lambda_exp, lambda_jaw = float(lambda_exp), float(lambda_jaw)
+    if not (0.0 <= lambda_exp < float("inf") and 0.0 <= lambda_jaw < float("inf")):
+        raise ValueError(f"lambda_exp and lambda_jaw must be finite and >= 0, got {lambda_exp!r}, {lambda_jaw!r}")
+    if n * K * 3 > 0x7fffffff:
+        raise ValueError(f"{n} frames of {K} landmarks are more than one call addresses")
+    dev = landmarks.device
+    code = torch.empty(n, NE, device=dev, dtype=torch.float32)
+    jaw = torch.empty(n, 3, device=dev, dtype=torch.float32)
+    rms = torch.empty(n, device=dev, dtype=torch.float32)
+    status = torch.empty(n, device=dev, dtype=torch.int32)
+    _lib.check(_lib.load().msmd_expression_fit(_p(landmarks), _p(subject), _p(tab), _p(tab0), _p(weights), _p(code), _p(jaw),
+                                               _p(rms), _p(status), n, K, NE, d["S"], int(jaw_dof), iterations, lambda_exp,
+                                               lambda_jaw, _stream()), "msmd_expression_fit")
+    return code, jaw, rms, status
+
+
 # ----------------------------------------------------------------------------- track resampling (csrc/track_resample.hip, DESIGN.md 5.21)
 TRACK_MAX_FRAMES, TRACK_MAX_CHANNELS, TRACK_ROWS, TRACK_CH_TILE, TRACK_STAGE = _h(
     "TRACK_MAX_FRAMES", "TRACK_MAX_CHANNELS", "TRACK_ROWS", "TRACK_CH_TILE", "TRACK_STAGE")    # limits and the kernels' tile
