@@ -1272,6 +1272,40 @@ int msmd_expression_fit(const float* landmarks, const int* subject, const double
                         float* code, float* jaw, float* rms, int* status, int n, int K, int NE, int S, int jaw_dof,
                         int iterations, double lambda_exp, double lambda_jaw, msmd_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Vertex-space evaluation of a predicted mesh sequence against the ground truth: what the lip vertex error,
+ * the upper-face dynamics deviation and the mean / maximum / RMS vertex error are reduced from (utils/metrics.py).
+ * pred, gt (n, V, 3) contiguous, both MSMD_F32 or both MSMD_F16; a stored value enters as its exact float64 image and every
+ * operation after that is a float64 one rounded on its own (no fused multiply-add).  No floating-point atomics.
+ *
+ * msmd_vertex_frame_errors: region (V) bytes, bit 0 = lip vertex (bit 1 = upper-face vertex, not read here); out (n, 4) float64.
+ *   Per vertex d2 = ((dx dx + dy dy) + dz dz) of the differences pred - gt.  Row f of out:
+ *     [0] max over the lip vertices of d2 (0 when region marks none)   [1] sum over all vertices of sqrt(d2)
+ *     [2] max over all vertices of sqrt(d2)                            [3] sum over all vertices of d2
+ *   The maxima are numpy's: a NaN operand is the result.  So a column is NaN exactly when a vertex that contributes to it has
+ *   a NaN difference (inf - inf is one), and a NaN at a vertex off the lips leaves column 0 finite.
+ *   One workgroup of 256 per frame; thread t folds vertices t, t + 256, ... in ascending order, the lanes of a wave are joined by
+ *   the xor butterfly 32 .. 1 and the four waves in wave order: an order that depends on V alone, never on n.
+ *
+ * msmd_vertex_motion_moments: the running moments over a clip's frames of m = |v - template|^2 (same parenthesisation) at every
+ *   upper-face vertex, for pred and for gt.  pred, gt: the n_chunk frames [frame0, frame0 + n_chunk) of a sequence of clips laid
+ *   end to end; clip_offsets (n_clips + 1) int64 on the device, over the WHOLE sequence; upper_idx (U) int32, ascending, clamped
+ *   into [0, V) by the kernel; tmpl (V, 3) fp32, or (n_clips, V, 3) with template_per_clip != 0.
+ *   state (n_clips, U, 2, 3) float64, [track: 0 pred, 1 gt][count, mean, M2]; the caller zeroes it before the first chunk.
+ *   Welford's recurrence per frame:  count += 1;  delta = m - mean;  mean += delta / count;  M2 += delta * (m - mean).
+ *   One thread owns one (clip, u, track): it reads the state, walks the clip's frames that fall inside the chunk in frame order, and
+ *   writes the state back (the other threads of its workgroup only load vertices and leave m in LDS for it); a clip with no frame
+ *   in the chunk is not touched.  The order is the frame order however the sequence is cut, so the state after the last chunk
+ *   holds the same bits for every cut.  A frame is counted once if the chunks of
+ *   successive calls tile the sequence; that is the caller's to keep.
+ * Both return 1 (hipErrorInvalidValue) before the launch for n or n_chunk < 0, frame0 < 0, V < 1, U < 1, n_clips < 1, a dtype
+ * other than the two, or a NULL pointer with work to do; n = 0 / n_chunk = 0 returns 0 and launches nothing. */
+int msmd_vertex_frame_errors(const void* pred, const void* gt, const unsigned char* region, double* out, int n, int V, int dtype,
+                             msmd_stream_t stream);
+int msmd_vertex_motion_moments(const void* pred, const void* gt, long frame0, int n_chunk, const long* clip_offsets, int n_clips,
+                               const int* upper_idx, int U, const float* tmpl, int template_per_clip, double* state, int V,
+                               int dtype, msmd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2186,3 +2186,59 @@ def nt_xent_backward(saved, upstream, temperature):
     _lib.check(_lib.load().msmd_nt_xent_backward(_p(fhat), _p(norm), _p(lse), _p(upstream), _p(grad), N // 2, D, tau, _stream()),
                "msmd_nt_xent_backward")
     return grad
+
+
+# ----------------------------------------------------------------------------- vertex-space metrics (csrc/vertex_metrics.hip)
+def _vertex_pair(pred, gt, d):
+    """pred and gt (n, V, 3) contiguous on the device, one dtype, fp32 or fp16 -> the MSMD_* code of that dtype."""
+    _need_cuda(pred, gt)
+    if not (torch.is_tensor(pred) and torch.is_tensor(gt)) or pred.dtype != gt.dtype:
+        raise TypeError(f"pred and gt must be tensors of one dtype, got {getattr(pred, 'dtype', type(pred))} and {getattr(gt, 'dtype', type(gt))}")
+    if pred.dtype not in (torch.float32, torch.float16):
+        raise TypeError(f"pred and gt must be torch.float32 or torch.float16, got {pred.dtype}")
+    _arg("pred", pred, pred.dtype, "n V+ 3", d)
+    _arg("gt", gt, pred.dtype, "n V 3", d)
+    return _dt(pred)
+
+
+def vertex_frame_errors(pred, gt, region):
+    """-> (n, 4) float64: msmd_vertex_frame_errors.  Row f = (max over the lip vertices of d2, sum of sqrt(d2), max of sqrt(d2), sum of
+    d2) over the vertices of frame f, d2 the squared distance pred - gt in float64.  pred, gt (n, V, 3) contiguous, both fp32 or
+    both fp16; region (V) uint8 on the device, bit 0 = lip vertex (utils/metrics.regions).  n = 0 gives an empty table."""
+    d = {}
+    dt = _vertex_pair(pred, gt, d)
+    _need_cuda(region)
+    _arg("region", region, torch.uint8, "V", d)
+    n, V = d["n"], d["V"]
+    out = torch.empty(n, 4, device=pred.device, dtype=torch.float64)
+    _lib.check(_lib.load().msmd_vertex_frame_errors(_p(pred), _p(gt), _p(region), _p(out), n, V, dt, _stream()),
+               "msmd_vertex_frame_errors")
+    return out
+
+
+def vertex_motion_moments_(state, pred, gt, frame0, clip_offsets_dev, upper_idx, template):
+    """msmd_vertex_motion_moments, in place on state (n_clips, U, 2, 3) float64 = [pred | gt][count, mean, M2] of m = |v - template|^2
+    over each clip's frames (zero it before the first chunk).  pred, gt (n_chunk, V, 3): the frames [frame0, frame0 + n_chunk) of
+    the sequence; clip_offsets_dev (n_clips + 1) int64 on the device, over the whole sequence (its values are not read back
+    here: the kernel clamps the frame range into the chunk); upper_idx (U) int32 ascending (clamped into [0, V) by the kernel);
+    template (V, 3) or (n_clips, V, 3) fp32.  Returns state."""
+    d = {}
+    dt = _vertex_pair(pred, gt, d)
+    _need_cuda(state, clip_offsets_dev, upper_idx, template)
+    _arg("clip_offsets_dev", clip_offsets_dev, torch.int64, "C1+")
+    d["C"] = clip_offsets_dev.numel() - 1
+    if d["C"] < 1:
+        raise TypeError("clip_offsets_dev must hold at least two offsets")
+    _arg("upper_idx", upper_idx, torch.int32, "U+", d)
+    _arg("state", state, torch.float64, "C U 2 3", d)
+    if torch.is_tensor(template) and template.dim() == 2:
+        _arg("template", template, torch.float32, "V 3", d)
+    else:
+        _arg("template", template, torch.float32, "C V 3", d)
+    frame0 = int(frame0)
+    if frame0 < 0:
+        raise ValueError(f"frame0 = {frame0} is negative")
+    _lib.check(_lib.load().msmd_vertex_motion_moments(_p(pred), _p(gt), frame0, d["n"], _p(clip_offsets_dev), d["C"], _p(upper_idx),
+                                                      d["U"], _p(template), int(template.dim() == 3), _p(state), d["V"], dt,
+                                                      _stream()), "msmd_vertex_motion_moments")
+    return state
