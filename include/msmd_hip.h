@@ -936,6 +936,28 @@ int msmd_render_shade_textured(const float* screen, const float* normals, const 
                                int H, int W, float near, msmd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Per-vertex colours: a deferred, pixel-parallel pass behind msmd_render_raster[_ms], the sibling of the textured
+ * pass with its launch shape (one workgroup per (frame, 64 x 16 strip)).  It reads that launch's face_id / sample_face_id buffer
+ * and overwrites rgba; depth and face ids are not written.
+ * msmd_render_shade_vertex_color: vcol (V, 4) uint8 RGBA per vertex, or (B, V, 4) with color_per_frame != 0; 4-byte aligned; alpha
+ *   is not read.  At a shaded point of face f
+ *   - corner colours c_k are the bytes at the face's vertex ids in the order face_setup oriented them (the face and its colours
+ *     swap together);
+ *   - per channel C = (p0 c0 + p1 c1) + p2 c2 in fp32 with the perspective-correct weights p_k = w_k q_k / iz of the textured pass;
+ *   - lit != 0: colour = clamp((C / 255)(ambient + diffuse), 0, 1) with msmd_render_raster's lighting (the same device function);
+ *     lit == 0: colour = clamp(C / 255, 0, 1), the interpolated colour itself; floor(255 c + 0.5), alpha 255.
+ *   samples == 1: face_id (B, H, W); a pixel with 0 <= face_id < F whose face the set-up accepts is overwritten, every other is left
+ *   as it is (`background` is not read).  samples == 4: sample_face_id (B, H, W, 4), 16-byte aligned; every covered sample is shaded
+ *   at its own position, an uncovered one contributes the four bytes of `background`, and a pixel with a shaded sample receives the
+ *   rounded mean of its four ((b0 + b1 + b2 + b3 + 2) >> 2 per byte); other pixels are left as they are.
+ *   Returns 1 (hipErrorInvalidValue) before a launch for any other `samples`, a size below 1, n_lights < 0, near <= 0, a NULL
+ *   sample_face_id or vcol, or a misaligned vcol / sample_face_id. */
+int msmd_render_shade_vertex_color(const float* screen, const float* normals, const int* faces, const unsigned char* vcol,
+                                   int color_per_frame, int lit, const float* shade, const float* lights, int n_lights,
+                                   const int* sample_face_id, void* rgba, int B, int V, int F, int H, int W, float near,
+                                   unsigned background, int samples, msmd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * FLAMETex albedo model (reference utils/flame.py:247-301): a linear texture space over an (Hs, Ws, 3)
  * image (the reference's is 512 x 512), evaluated for ONE code, nearest-resized to (Hd, Wd) and channel-reversed.
  *   mean (Hs Ws 3) fp32, basis (Hs Ws 3, n_tex) fp32 row-major and contiguous, code (n_tex) fp32 (reference l.292: row 0 of
@@ -1305,6 +1327,28 @@ int msmd_vertex_frame_errors(const void* pred, const void* gt, const unsigned ch
 int msmd_vertex_motion_moments(const void* pred, const void* gt, long frame0, int n_chunk, const long* clip_offsets, int n_clips,
                                const int* upper_idx, int U, const float* tmpl, int template_per_clip, double* state, int V,
                                int dtype, msmd_stream_t stream);
+
+/* The error FIELD of the same pair of sequences, and its colours.  Same loads and float64 conventions: per vertex
+ * d = sqrt(d2), d2 as above.  A colour table `lut` is (256, 4) uint8 RGBA, 4-byte aligned, as is every colour output.
+ * The colour rule, ONE device function for both colour entry points: t = x / vmax; a NaN t stores the four bytes of nan_color
+ *   (R | G << 8 | B << 16 | A << 24); otherwise idx = (t >= 1.0) ? 255 : (int)floor(t * 255.0 + 0.5) (so +inf maps to 255; a t <= 0,
+ *   which a distance never gives, to 0) and the four bytes of lut[idx] are stored.
+ * msmd_vertex_error_colors: out (n, V, 4) uint8 = the rule at x = d.  The distance is never stored.
+ * msmd_colormap_f64: x (N) float64 -> out (N, 4) uint8 = the rule at x; it colours the time-mean map sum / F.
+ * msmd_vertex_error_sums: the running per-clip, per-vertex sum of d.  state (n_clips, V) float64, zeroed by the caller; pred, gt,
+ *   frame0, n_chunk and clip_offsets as msmd_vertex_motion_moments takes them.  One thread owns one (clip, vertex): it reads its sum,
+ *   adds the d of the clip's frames that fall inside the chunk in frame order, and writes it back; a clip with no frame in the chunk
+ *   is not touched.  So the state after the last chunk holds the same bits however the sequence is cut and whatever the other
+ *   clips hold.  NaN propagates.
+ * All three return 1 (hipErrorInvalidValue) before the launch for a vmax that is not finite or not > 0, for the arguments the two
+ * entry points above refuse (n, n_chunk or N < 0, frame0 < 0, V < 1, n_clips < 1, a dtype other than the two, a NULL pointer with
+ * work to do) and for a misaligned lut / out; n = 0 / n_chunk = 0 / N = 0 returns 0 and launches nothing. */
+int msmd_vertex_error_colors(const void* pred, const void* gt, const unsigned char* lut, unsigned char* out, int n, int V, int dtype,
+                             double vmax, unsigned nan_color, msmd_stream_t stream);
+int msmd_vertex_error_sums(const void* pred, const void* gt, long frame0, int n_chunk, const long* clip_offsets, int n_clips,
+                           double* state, int V, int dtype, msmd_stream_t stream);
+int msmd_colormap_f64(const double* x, const unsigned char* lut, unsigned char* out, long N, double vmax, unsigned nan_color,
+                      msmd_stream_t stream);
 
 #ifdef __cplusplus
 }

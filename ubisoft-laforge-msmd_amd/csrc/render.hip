@@ -3,7 +3,7 @@
 // there.  Two launches per batch of frames, no host synchronisation, no global atomics, bit-identical from run to run.
 // A texture adds a mip pyramid (built once per image) and a third, deferred launch that shades the covered pixels from it
 // (DESIGN.md 5.14).  The raster and the textured kernel are templates on the samples per pixel: one, or four for anti-aliased
-// frames.
+// frames.  Per-vertex colours are a second deferred pass of the textured pass's shape, lit or unlit.
 #include "common.h"
 
 namespace {
@@ -579,6 +579,97 @@ __global__ __launch_bounds__(TX_THREADS) void render_shade_textured_kernel(
   }
 }
 
+// ------------------------------------------------------------------------------------------------ vertex colours
+// The colour of face `s` at the point whose edge values are e0, e1, e2 from the RGBA bytes at its three vertices (alpha not read):
+// per channel C = (p0 c0 + p1 c1) + p2 c2 with the perspective-correct weights of the textured pass, the corners in the order
+// face_setup left them in (s.i0, s.i1, s.i2: the face and its colours swap together); then clamp((C / 255)(ambient + diffuse), 0, 1)
+// under the raster pass's lighting, or clamp(C / 255, 0, 1) unlit; floor(255 c + 0.5), alpha 255.
+struct VertexColorArgs {
+  const float* nrm; const unsigned* vcol; const float* lights;
+  int n_lights, lit;
+  float amb_r, amb_g, amb_b;
+};
+__device__ __forceinline__ unsigned shade_vertex_color(const FaceSetup& s, long e0, long e1, long e2, const VertexColorArgs& t) {
+  float w0, w1, w2;
+  const float iz = inv_depth(s, e0, e1, e2, w0, w1, w2);
+  const float p0 = w0 * s.q0 / iz, p1 = w1 * s.q1 / iz, p2 = w2 * s.q2 / iz;
+  const unsigned c0 = t.vcol[s.i0], c1 = t.vcol[s.i1], c2 = t.vcol[s.i2];
+  const float Cr = (p0 * (float)(c0 & 255u) + p1 * (float)(c1 & 255u)) + p2 * (float)(c2 & 255u);
+  const float Cg = (p0 * (float)((c0 >> 8) & 255u) + p1 * (float)((c1 >> 8) & 255u)) + p2 * (float)((c2 >> 8) & 255u);
+  const float Cb = (p0 * (float)((c0 >> 16) & 255u) + p1 * (float)((c1 >> 16) & 255u)) + p2 * (float)((c2 >> 16) & 255u);
+  float cr = Cr / 255.f, cg = Cg / 255.f, cb = Cb / 255.f;
+  if (t.lit) {
+    const float diff = lambert_diffuse(t.nrm, s, p0, p1, p2, t.lights, t.n_lights);
+    cr *= t.amb_r + diff; cg *= t.amb_g + diff; cb *= t.amb_b + diff;
+  }
+  cr = fminf(fmaxf(cr, 0.f), 1.f); cg = fminf(fmaxf(cg, 0.f), 1.f); cb = fminf(fmaxf(cb, 0.f), 1.f);
+  const unsigned ur = (unsigned)floorf(255.f * cr + 0.5f), ug = (unsigned)floorf(255.f * cg + 0.5f),
+                 ub = (unsigned)floorf(255.f * cb + 0.5f);
+  return ur | (ug << 8) | (ub << 16) | 0xff000000u;
+}
+
+// The textured pass's launch shape and mapping: one workgroup per (frame, 64 x 16 strip), pixel-parallel, a wave reads 64 contiguous
+// face ids (int4 at four samples) and stores 256 contiguous bytes per step; the three colour gathers per shaded point are 4-byte
+// loads from a (V, 4) table that stays in L2.  vcol is the frame's table, or the one shared table (col_stride = 0).
+template <int S>
+__global__ __launch_bounds__(TX_THREADS) void render_shade_vertex_color_kernel(
+    const float* __restrict__ screen, const float* __restrict__ normals, const int* __restrict__ faces, const unsigned* __restrict__ vcol,
+    long col_stride, int lit, const float* __restrict__ shade, const float* __restrict__ lights, int n_lights,
+    const int* __restrict__ face_id, unsigned* __restrict__ rgba, int V, int F, int H, int W, int tiles_x, int strips_y, float near,
+    unsigned bg) {
+  const int tid = threadIdx.x;
+  const int per_frame = tiles_x * strips_y;
+  const int b = blockIdx.x / per_frame, rest = blockIdx.x - b * per_frame;
+  const int sy = rest / tiles_x, tx = rest - sy * tiles_x;
+  const int tx0 = tx * RT_TILE, ty0 = sy * TX_ROWS;
+  const float* scr = screen + (long)b * V * 3;
+  VertexColorArgs t;
+  t.nrm = normals + (long)b * V * 3; t.vcol = vcol + (long)b * col_stride; t.lights = lights;
+  t.n_lights = n_lights; t.lit = lit;
+  t.amb_r = shade[3]; t.amb_g = shade[4]; t.amb_b = shade[5];
+  for (int p = tid; p < RT_TILE * TX_ROWS; p += TX_THREADS) {
+    const int i = ty0 + p / RT_TILE, j = tx0 + p % RT_TILE;
+    if (i >= H || j >= W) continue;
+    const long o = ((long)b * H + i) * W + j;
+    if constexpr (S == 1) {
+      const int g = face_id[o];
+      if ((unsigned)g >= (unsigned)F) continue;          // background, or a face id the raster pass cannot have written
+      const FaceSetup s = face_setup<S>(faces, scr, g, V, near, 0, 0, W - 1, H - 1);
+      if (!s.ok) continue;
+      long e0, e1, e2;
+      edges_at<S>(s, j, i, 0, e0, e1, e2);
+      rgba[o] = shade_vertex_color(s, e0, e1, e2, t);
+    } else {
+      const int4 id4 = *(const int4*)(face_id + o * 4);
+      const int ids[4] = {id4.x, id4.y, id4.z, id4.w};
+      Resolve4 sum;
+      bool any = false;
+      int last = -1;                    // the set-up is kept while consecutive samples show the same face
+      FaceSetup s;
+      s.ok = false;
+#pragma unroll
+      for (int k = 0; k < S; ++k) {
+        const int g = ids[k];
+        unsigned c = bg;
+        if ((unsigned)g < (unsigned)F) {
+          if (g != last) {
+            s = face_setup<S>(faces, scr, g, V, near, 0, 0, W - 1, H - 1);
+            last = g;
+          }
+          if (s.ok) {
+            long e0, e1, e2;
+            edges_at<S>(s, j, i, k, e0, e1, e2);
+            c = shade_vertex_color(s, e0, e1, e2, t);
+            any = true;
+          }
+        }
+        sum.add(c);
+      }
+      if (any) rgba[o] = sum.word();
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" long msmd_texture_texels(int Ht, int Wt) {
@@ -647,6 +738,36 @@ extern "C" int msmd_render_shade_textured_ms(const float* screen, const float* n
   if (samples != 4) return 1;
   return launch_shade_textured<4>(screen, normals, faces, vt, ft, pyramid, Ht, Wt, shade, lights, n_lights, sample_face_id, rgba,
                                   nullptr, B, V, F, Nt, H, W, near, background, stream);
+}
+
+namespace {
+template <int S>
+int launch_shade_vertex_color(const float* screen, const float* normals, const int* faces, const unsigned char* vcol, int color_per_frame,
+                              int lit, const float* shade, const float* lights, int n_lights, const int* face_id, void* rgba, int B,
+                              int V, int F, int H, int W, float near, unsigned background, msmd_stream_t stream) {
+  if (B <= 0 || V <= 0 || F <= 0 || H <= 0 || W <= 0 || n_lights < 0 || !(near > 0.f) || face_id == nullptr || vcol == nullptr ||
+      ((size_t)vcol & 3) != 0) return 1;                    // a vertex's four bytes are read as one word
+  if (S == 4 && ((size_t)face_id & 15) != 0) return 1;      // read as int4
+  const int tiles_x = (W + RT_TILE - 1) / RT_TILE, strips_y = (H + TX_ROWS - 1) / TX_ROWS;
+  const long grid = (long)B * tiles_x * strips_y;
+  if (grid > 2147483647L) return 1;
+  hipLaunchKernelGGL(render_shade_vertex_color_kernel<S>, dim3((unsigned)grid), dim3(TX_THREADS), 0, (hipStream_t)stream, screen,
+                     normals, faces, (const unsigned*)vcol, color_per_frame ? (long)V : 0L, lit != 0, shade, lights, n_lights, face_id,
+                     (unsigned*)rgba, V, F, H, W, tiles_x, strips_y, near, background);
+  MSMD_RETURN_LAST();
+}
+}  // namespace
+
+extern "C" int msmd_render_shade_vertex_color(const float* screen, const float* normals, const int* faces, const unsigned char* vcol,
+                                              int color_per_frame, int lit, const float* shade, const float* lights, int n_lights,
+                                              const int* sample_face_id, void* rgba, int B, int V, int F, int H, int W, float near,
+                                              unsigned background, int samples, msmd_stream_t stream) {
+  if (samples == 1)
+    return launch_shade_vertex_color<1>(screen, normals, faces, vcol, color_per_frame, lit, shade, lights, n_lights, sample_face_id, rgba,
+                                        B, V, F, H, W, near, background, stream);
+  if (samples != 4) return 1;
+  return launch_shade_vertex_color<4>(screen, normals, faces, vcol, color_per_frame, lit, shade, lights, n_lights, sample_face_id, rgba,
+                                      B, V, F, H, W, near, background, stream);
 }
 
 extern "C" int msmd_render_vertices(const float* verts, const int* faces, const int* csr_offsets, const int* csr_faces,

@@ -3,7 +3,8 @@
 // dynamics deviation.  Both stream the two vertex tensors once.  Everything after the loads is float64 with every operation
 // rounded on its own (no fused multiply-add), so a numpy transcription of the lines below holds the same numbers.  No
 // floating-point atomics: a frame's row has one workgroup, a (clip, vertex, track) state has one thread, and each is reduced in an
-// order that depends on V (on the frame order) alone.
+// order that depends on V (on the frame order) alone.  The error FIELD behind those numbers is kept too: the per-vertex
+// distance through a colour table, and its running per-clip sum, under the same conventions.
 #include "common.h"
 
 #define VM_THREADS 256
@@ -163,6 +164,102 @@ __global__ __launch_bounds__(VM_THREADS) void vertex_motion_moments_kernel(const
   if (owner) { st[0] = s.count; st[1] = s.mean; st[2] = s.m2; }
 }
 
+// ------------------------------------------------------------------------------------------------ the error field
+#define VM_COLOR_BATCH 4          // vertices (elements) a thread of the colour kernels loads before it consumes the first
+
+// x -> t = x / vmax -> a table row, ONE routine for the distance field and for any float64 array: NaN gives nan_color; t >= 1
+// (+inf too) row 255; otherwise floor(t * 255 + 0.5), which is at most 255; t <= 0 (-inf too; a distance is never negative) row 0
+__device__ __forceinline__ unsigned colormap_word(double x, double vmax, const unsigned* lut, unsigned nan_color) {
+#pragma clang fp contract(off)
+  const double t = x / vmax;
+  if (t != t) return nan_color;
+  const int idx = t >= 1.0 ? 255 : t > 0.0 ? (int)floor(t * 255.0 + 0.5) : 0;
+  return lut[idx];
+}
+
+// the 256 table rows, one 4-byte word each, into LDS: one load per thread of the workgroup
+__device__ __forceinline__ void stage_lut(const unsigned* __restrict__ lut, unsigned* s_lut) {
+  static_assert(VM_THREADS == 256, "one table row per thread");
+  s_lut[threadIdx.x] = lut[threadIdx.x];
+  __syncthreads();
+}
+
+// The n V vertices as one flat run: a workgroup takes VM_COLOR_BATCH * 256 consecutive vertices, thread t the vertices t, t + 256,
+// ... of them, so a wave's load covers 768 (384) contiguous bytes per tensor and its store 256 contiguous bytes.  The distance is
+// never stored.  The slots past the end re-read the last vertex and store nothing.
+template <typename T>
+__global__ __launch_bounds__(VM_THREADS) void vertex_error_colors_kernel(const T* __restrict__ pred, const T* __restrict__ gt,
+                                                                         const unsigned* __restrict__ lut, unsigned* __restrict__ out,
+                                                                         long N, double vmax, unsigned nan_color) {
+  typedef typename Vertex<T>::type Vtx;
+  __shared__ unsigned s_lut[256];
+  stage_lut(lut, s_lut);
+  const Vtx* p = (const Vtx*)pred;
+  const Vtx* g = (const Vtx*)gt;
+  const long v0 = (long)blockIdx.x * (VM_COLOR_BATCH * VM_THREADS) + threadIdx.x;
+  Vtx pv[VM_COLOR_BATCH], gv[VM_COLOR_BATCH];
+#pragma unroll
+  for (int j = 0; j < VM_COLOR_BATCH; ++j) {
+    const long v = v0 + j * VM_THREADS < N ? v0 + j * VM_THREADS : N - 1;
+    pv[j] = p[v];
+    gv[j] = g[v];
+  }
+#pragma unroll
+  for (int j = 0; j < VM_COLOR_BATCH; ++j) {
+    const long v = v0 + j * VM_THREADS;
+    if (v < N) out[v] = colormap_word(sqrt(dist2(pv[j], gv[j])), vmax, s_lut, nan_color);
+  }
+}
+
+__global__ __launch_bounds__(VM_THREADS) void colormap_f64_kernel(const double* __restrict__ x, const unsigned* __restrict__ lut,
+                                                                  unsigned* __restrict__ out, long N, double vmax,
+                                                                  unsigned nan_color) {
+  __shared__ unsigned s_lut[256];
+  stage_lut(lut, s_lut);
+  const long i0 = (long)blockIdx.x * (VM_COLOR_BATCH * VM_THREADS) + threadIdx.x;
+  double xv[VM_COLOR_BATCH];
+#pragma unroll
+  for (int j = 0; j < VM_COLOR_BATCH; ++j) xv[j] = x[i0 + j * VM_THREADS < N ? i0 + j * VM_THREADS : N - 1];
+#pragma unroll
+  for (int j = 0; j < VM_COLOR_BATCH; ++j) {
+    const long i = i0 + j * VM_THREADS;
+    if (i < N) out[i] = colormap_word(xv[j], vmax, s_lut, nan_color);
+  }
+}
+
+// One thread OWNS one (clip, vertex): it alone reads, updates and writes that sum, adding the distance of the clip's frames that lie
+// in [frame0, frame0 + n_chunk) in frame order (VM_BATCH frames' loads in flight; the slots past the end re-read the last frame and
+// are not added).  Consecutive threads own consecutive vertices: a frame's reads are contiguous 12- (6-) byte triples.  The sum goes
+// through memory between chunks, a float64 round trip is exact, and so the final sum does not know where the chunks were cut.
+template <typename T>
+__global__ __launch_bounds__(VM_THREADS) void vertex_error_sums_kernel(const T* __restrict__ pred, const T* __restrict__ gt, long frame0,
+                                                                       int n_chunk, const long* __restrict__ clip_offsets,
+                                                                       double* __restrict__ state, int V, int tiles) {
+  typedef typename Vertex<T>::type Vtx;
+  const int clip = blockIdx.x / tiles, v = (blockIdx.x % tiles) * VM_THREADS + threadIdx.x;
+  const long c0 = clip_offsets[clip], c1 = clip_offsets[clip + 1], end = frame0 + (long)n_chunk;
+  const long lo = c0 > frame0 ? c0 : frame0, hi = c1 < end ? c1 : end;
+  if (lo >= hi || v >= V) return;                    // the clip has no frame in this chunk: its sums are not touched
+  double* st = state + (long)clip * V + v;
+  double s = *st;
+  const Vtx* p = (const Vtx*)pred + v;
+  const Vtx* g = (const Vtx*)gt + v;
+  const long nf = hi - frame0;                       // the clip's frames in this chunk are [lo - frame0, nf) of pred / gt
+  for (long f0 = lo - frame0; f0 < nf; f0 += VM_BATCH) {
+    Vtx pv[VM_BATCH], gv[VM_BATCH];
+#pragma unroll
+    for (int j = 0; j < VM_BATCH; ++j) {
+      const long ff = f0 + j < nf ? f0 + j : nf - 1;
+      pv[j] = p[ff * V];
+      gv[j] = g[ff * V];
+    }
+#pragma unroll
+    for (int j = 0; j < VM_BATCH; ++j)
+      if (f0 + j < nf) s += sqrt(dist2(pv[j], gv[j]));
+  }
+  *st = s;
+}
+
 extern "C" int msmd_vertex_frame_errors(const void* pred, const void* gt, const unsigned char* region, double* out, int n, int V,
                                         int dtype, msmd_stream_t stream) {
   if (n < 0 || V < 1 || (dtype != MSMD_F32 && dtype != MSMD_F16)) return 1;
@@ -189,6 +286,56 @@ extern "C" int msmd_vertex_motion_moments(const void* pred, const void* gt, long
     hipLaunchKernelGGL(vertex_motion_moments_kernel<T>, dim3((unsigned)(n_clips * tiles)), dim3(VM_THREADS), 0, (hipStream_t)stream,
                        (const T*)pred, (const T*)gt, frame0, n_chunk, clip_offsets, upper_idx, U, tmpl, template_per_clip != 0,
                        state, V, (int)tiles);
+    return (int)hipGetLastError();
+  });
+}
+
+namespace {
+// the colour kernels read the table and write the colours as 4-byte words; a workgroup takes VM_COLOR_BATCH * 256 elements
+bool color_args_ok(const void* lut, const void* out, long N, double vmax) {
+  const bool finite = vmax - vmax == 0.0;            // false for NaN and +-inf
+  return finite && vmax > 0.0 && lut && out && ((((size_t)lut) | ((size_t)out)) & 3) == 0 &&
+         (N + VM_COLOR_BATCH * VM_THREADS - 1) / (VM_COLOR_BATCH * VM_THREADS) <= 0x7fffffffL;
+}
+}  // namespace
+
+extern "C" int msmd_vertex_error_colors(const void* pred, const void* gt, const unsigned char* lut, unsigned char* out, int n, int V,
+                                        int dtype, double vmax, unsigned nan_color, msmd_stream_t stream) {
+  if (n < 0 || V < 1 || (dtype != MSMD_F32 && dtype != MSMD_F16) || !(vmax - vmax == 0.0) || !(vmax > 0.0)) return 1;
+  if (n == 0) return 0;
+  const long N = (long)n * V;
+  if (!pred || !gt || !color_args_ok(lut, out, N, vmax)) return 1;
+  const unsigned grid = (unsigned)((N + VM_COLOR_BATCH * VM_THREADS - 1) / (VM_COLOR_BATCH * VM_THREADS));
+  return dispatch_dtype<float, f16_t>(dtype, [&](auto tag) {
+    typedef MSMD_TAG_T(tag) T;
+    hipLaunchKernelGGL(vertex_error_colors_kernel<T>, dim3(grid), dim3(VM_THREADS), 0, (hipStream_t)stream, (const T*)pred,
+                       (const T*)gt, (const unsigned*)lut, (unsigned*)out, N, vmax, nan_color);
+    return (int)hipGetLastError();
+  });
+}
+
+extern "C" int msmd_colormap_f64(const double* x, const unsigned char* lut, unsigned char* out, long N, double vmax,
+                                 unsigned nan_color, msmd_stream_t stream) {
+  if (N < 0 || !(vmax - vmax == 0.0) || !(vmax > 0.0)) return 1;
+  if (N == 0) return 0;
+  if (!x || !color_args_ok(lut, out, N, vmax)) return 1;
+  const unsigned grid = (unsigned)((N + VM_COLOR_BATCH * VM_THREADS - 1) / (VM_COLOR_BATCH * VM_THREADS));
+  hipLaunchKernelGGL(colormap_f64_kernel, dim3(grid), dim3(VM_THREADS), 0, (hipStream_t)stream, x, (const unsigned*)lut,
+                     (unsigned*)out, N, vmax, nan_color);
+  return (int)hipGetLastError();
+}
+
+extern "C" int msmd_vertex_error_sums(const void* pred, const void* gt, long frame0, int n_chunk, const long* clip_offsets,
+                                      int n_clips, double* state, int V, int dtype, msmd_stream_t stream) {
+  if (n_chunk < 0 || frame0 < 0 || n_clips < 1 || V < 1 || (dtype != MSMD_F32 && dtype != MSMD_F16)) return 1;
+  const long tiles = ((long)V + VM_THREADS - 1) / VM_THREADS;
+  if ((long)n_clips * tiles > 0x7fffffffL) return 1;
+  if (n_chunk == 0) return 0;
+  if (!pred || !gt || !clip_offsets || !state) return 1;
+  return dispatch_dtype<float, f16_t>(dtype, [&](auto tag) {
+    typedef MSMD_TAG_T(tag) T;
+    hipLaunchKernelGGL(vertex_error_sums_kernel<T>, dim3((unsigned)(n_clips * tiles)), dim3(VM_THREADS), 0, (hipStream_t)stream,
+                       (const T*)pred, (const T*)gt, frame0, n_chunk, clip_offsets, state, V, (int)tiles);
     return (int)hipGetLastError();
   });
 }

@@ -1611,6 +1611,35 @@ def render_shade_textured(screen, normals, faces_i32, vt, ft, pyramid, tex_heigh
     return uvl
 
 
+def render_shade_vertex_color(screen, normals, faces_i32, vcol, shade, lights, face_id, rgba, near, lit=True, samples=1,
+                              background=None):
+    """Overwrites rgba (B, H, W, 4) uint8 at the pixels face_id marks as covered with the colour interpolated from the vertices:
+    msmd_render_shade_vertex_color.  screen / normals / faces / shade / lights / face_id as render_shade_textured
+    takes them; vcol (V, 4) uint8 RGBA per vertex (alpha ignored), shared by the frames, or (B, V, 4) per frame.  lit=True
+    multiplies the colour by render_raster's lighting as a texel is; lit=False stores the interpolated colour itself.  samples = 4:
+    face_id is (B, H, W, 4), every covered sample is shaded at its own position and `background` (the one render_raster was
+    given: required) stands for the uncovered samples of a pixel that has a covered one."""
+    if samples not in RENDER_SAMPLES:
+        raise ValueError(f"samples must be one of {RENDER_SAMPLES}, got {samples!r}")
+    if samples != 1 and background is None:
+        raise ValueError("samples=4 needs the background the raster pass was given: its uncovered samples take part in the resolve")
+    d = {}
+    _arg("screen", screen, torch.float32, "B V 3", d)
+    _arg("normals", normals, torch.float32, "B V 3", d)
+    _arg("faces", faces_i32, torch.int32, "F 3", d)
+    per_frame = torch.is_tensor(vcol) and vcol.dim() == 3
+    _arg("vcol", vcol, torch.uint8, "B V 4" if per_frame else "V 4", d)
+    _arg("shade", shade, torch.float32, "6")
+    _arg("lights", lights, torch.float32, "L 4", d)
+    _arg("face_id", face_id, torch.int32, "B H W" if samples == 1 else f"B H W {samples}", d)
+    _arg("rgba", rgba, torch.uint8, "B H W 4", d)
+    B, V, Fc, H, W = (d[k] for k in "BVFHW")
+    _lib.check(_lib.load().msmd_render_shade_vertex_color(_p(screen), _p(normals), _p(faces_i32), _p(vcol), int(per_frame), int(bool(lit)),
+                                                          _p(shade), _p(lights), lights.shape[0], _p(face_id), _p(rgba), B, V, Fc, H, W,
+                                                          float(near), 0 if background is None else int(background) & 0xffffffff,
+                                                          int(samples), _stream()), "msmd_render_shade_vertex_color")
+
+
 # ----------------------------------------------------------------------------- FLAMETex albedo model (csrc/flametex.hip, DESIGN.md 5.15)
 TEX_PLANAR_F32, TEX_IMAGE_U8 = _h("TEX_PLANAR_F32", "TEX_IMAGE_U8")
 FLAMETEX_MAX_SIDE, FLAMETEX_MAX_TEX = _h("FLAMETEX_MAX_SIDE", "FLAMETEX_MAX_TEX")
@@ -2241,4 +2270,62 @@ def vertex_motion_moments_(state, pred, gt, frame0, clip_offsets_dev, upper_idx,
     _lib.check(_lib.load().msmd_vertex_motion_moments(_p(pred), _p(gt), frame0, d["n"], _p(clip_offsets_dev), d["C"], _p(upper_idx),
                                                       d["U"], _p(template), int(template.dim() == 3), _p(state), d["V"], dt,
                                                       _stream()), "msmd_vertex_motion_moments")
+    return state
+
+
+# the error field and its colours
+def _color_table(lut, vmax, nan_color):
+    """lut (256, 4) uint8 contiguous on the device, vmax finite and > 0, nan_color (R, G, B[, A]) bytes -> (vmax, nan_color word)."""
+    _need_cuda(lut)
+    _arg("lut", lut, torch.uint8, "256 4")
+    vmax = float(vmax)
+    if not 0.0 < vmax < float("inf"):
+        raise ValueError(f"vmax = {vmax} must be finite and greater than 0")
+    c = tuple(int(x) for x in nan_color)
+    if len(c) not in (3, 4) or any(not 0 <= x <= 255 for x in c):
+        raise ValueError(f"nan_color must be 3 or 4 bytes, got {nan_color!r}")
+    r, g, b, a = c if len(c) == 4 else c + (255,)
+    return vmax, r | g << 8 | b << 16 | a << 24
+
+
+def vertex_error_colors(pred, gt, vmax, lut, nan_color=(255, 0, 255)):
+    """-> (n, V, 4) uint8: msmd_vertex_error_colors.  The distance |pred - gt| of every vertex, in float64, through the colour table:
+    t = d / vmax, row 255 at t >= 1 (+inf too), else row floor(t * 255 + 0.5); a NaN distance gives nan_color.  pred, gt (n, V, 3)
+    contiguous, both fp32 or both fp16; lut (256, 4) uint8 on the device (utils/metrics.colormap_table); vmax finite and > 0."""
+    d = {}
+    dt = _vertex_pair(pred, gt, d)
+    vmax, word = _color_table(lut, vmax, nan_color)
+    n, V = d["n"], d["V"]
+    out = torch.empty(n, V, 4, device=pred.device, dtype=torch.uint8)
+    _lib.check(_lib.load().msmd_vertex_error_colors(_p(pred), _p(gt), _p(lut), _p(out), n, V, dt, vmax, word, _stream()),
+               "msmd_vertex_error_colors")
+    return out
+
+
+def colormap(x, vmax, lut, nan_color=(255, 0, 255)):
+    """-> x.shape + (4,) uint8: msmd_colormap_f64, vertex_error_colors' rule applied to any contiguous float64 device tensor."""
+    _need_cuda(x)
+    _arg("x", x, torch.float64)
+    vmax, word = _color_table(lut, vmax, nan_color)
+    out = torch.empty(tuple(x.shape) + (4,), device=x.device, dtype=torch.uint8)
+    _lib.check(_lib.load().msmd_colormap_f64(_p(x), _p(lut), _p(out), x.numel(), vmax, word, _stream()), "msmd_colormap_f64")
+    return out
+
+
+def vertex_error_sums_(state, pred, gt, frame0, clip_offsets_dev):
+    """msmd_vertex_error_sums, in place on state (n_clips, V) float64 = the sum over each clip's frames of the per-vertex distance
+    (zero it before the first chunk).  pred, gt, frame0 and clip_offsets_dev as vertex_motion_moments_ takes them.  Returns state."""
+    d = {}
+    dt = _vertex_pair(pred, gt, d)
+    _need_cuda(state, clip_offsets_dev)
+    _arg("clip_offsets_dev", clip_offsets_dev, torch.int64, "C1+")
+    d["C"] = clip_offsets_dev.numel() - 1
+    if d["C"] < 1:
+        raise TypeError("clip_offsets_dev must hold at least two offsets")
+    _arg("state", state, torch.float64, "C V", d)
+    frame0 = int(frame0)
+    if frame0 < 0:
+        raise ValueError(f"frame0 = {frame0} is negative")
+    _lib.check(_lib.load().msmd_vertex_error_sums(_p(pred), _p(gt), frame0, d["n"], _p(clip_offsets_dev), d["C"], _p(state), d["V"], dt,
+                                                  _stream()), "msmd_vertex_error_sums")
     return state

@@ -13,6 +13,10 @@ magnification, GL_LINEAR_MIPMAP_LINEAR minification with an analytic per-pixel l
 texel replaces the base colour of the shading model above.  `vt` is indexed per corner through `ft`, so a seam needs no
 duplicated vertex (the reference writes an OBJ file and reloads it for that), and normals stay those of the topology `f`.
 
+Per-vertex colours (vertex_colors, (V, 3 | 4) or per frame (B, V, 3 | 4) uint8) replace the base colour with the colour
+interpolated from the face's corners with the perspective-correct weights: lit like a texel, or with ``lit=False`` stored as it
+is, which is how a heat map of a scalar on the vertices is drawn (utils/metrics.render_comparison).
+
 ``samples=4`` draws anti-aliased: coverage, depth and shading at four sample points per pixel (the rotated grid (96, 32),
 (224, 96), (32, 160), (160, 224) in 1/256 pixel units from the pixel's top-left corner), each exactly as the pixel centre is
 treated at one sample, resolved by the rounded mean of the four samples' bytes, an uncovered sample counting as the
@@ -78,6 +82,23 @@ def validate_texture(tex_img, tex_uv, n_faces):
     if ft.min() < 0 or ft.max() >= vt.shape[0]:
         raise ValueError(f"tex_uv['ft'] refers to texture coordinates outside [0, {vt.shape[0]})")
     return np.ascontiguousarray(img), np.ascontiguousarray(vt, np.float32), np.ascontiguousarray(ft.astype(np.int32))
+
+
+def vertex_color_table(vertex_colors, n_frames, n_vertices, device):
+    """vertex_colors (V, 3 | 4) or (B, V, 3 | 4) uint8, a tensor or anything numpy reads -> the contiguous (V, 4) / (B, V, 4) uint8
+    table on `device` (three channels padded once with alpha 255).  TypeError for a dtype other than uint8, ValueError for a shape
+    that is neither; both name the expected shape."""
+    B, V = int(n_frames), int(n_vertices)
+    want = f"({V}, 3 | 4) or ({B}, {V}, 3 | 4) uint8"
+    c = vertex_colors if torch.is_tensor(vertex_colors) else torch.from_numpy(np.ascontiguousarray(vertex_colors))
+    if c.dtype != torch.uint8:
+        raise TypeError(f"vertex_colors must be {want}, got dtype {c.dtype}")
+    if c.dim() not in (2, 3) or c.shape[-1] not in (3, 4) or c.shape[-2] != V or (c.dim() == 3 and c.shape[0] != B):
+        raise ValueError(f"vertex_colors must be {want}, got shape {tuple(c.shape)}")
+    c = c.detach().to(device)
+    if c.shape[-1] == 3:
+        c = torch.cat([c, torch.full_like(c[..., :1], 255)], dim=-1)
+    return c.contiguous()
 
 
 def _content_key(x):
@@ -206,7 +227,7 @@ class MeshRenderer:
 
     # ------------------------------------------------------------------ rendering
     def render_vertices(self, vertices, faces, t_center=None, rot=None, return_face_id=False, return_screen=False, tex_img=None,
-                        tex_uv=None, return_uv=False):
+                        tex_uv=None, return_uv=False, vertex_colors=None, lit=True):
         """vertices (B, V, 3) CUDA tensor (fp32, or fp16 / bf16: cast) -> colour (B, H, W, 3) uint8 (a view of the RGBA
         buffer) and eye depth (B, H, W) fp32 (0 = background), both on the device.  rot: (3,) or (B, 3) axis-angle about
         t_center (3,) per frame.  return_face_id appends the winning face id per pixel (int32, -1 = background);
@@ -214,7 +235,12 @@ class MeshRenderer:
         tex_img (Ht, Wt, 3 | 4) uint8 with tex_uv = {'vt': (Nt, 2), 'ft': (F, 3)} (validate_texture) draws the mesh textured;
         return_uv (textured only) appends (u, v, level of detail) per pixel, (B, H, W, 3) fp32 with zeros on the background.
         With samples=4 colour is the resolve of the four samples, depth the least depth over the pixel's covered samples, the
-        face id is per sample, (B, H, W, 4), and return_uv is a ValueError."""
+        face id is per sample, (B, H, W, 4), and return_uv is a ValueError.
+        vertex_colors (V, 3 | 4) uint8 shared by the frames, or (B, V, 3 | 4) per frame, a device tensor or a numpy array (alpha
+        ignored), draws the mesh in the colours interpolated from its vertices: under the lighting as a texel
+        is, or with lit=False as they are, the same everywhere on the face.  Together with tex_img it is a TypeError."""
+        if vertex_colors is not None and (tex_img is not None or tex_uv is not None):
+            raise TypeError("vertex_colors and a texture are not drawn together: give one of them")
         if (tex_img is None) != (tex_uv is None):
             if tex_uv is None:
                 raise NotImplementedError("a texture needs a uv table: tex_uv = {'vt', 'ft'} (there are no default per-vertex "
@@ -229,6 +255,7 @@ class MeshRenderer:
         device = vertices.device
         verts = vertices.detach().float().contiguous()
         B, V, _ = verts.shape
+        vcol = None if vertex_colors is None else vertex_color_table(vertex_colors, B, V, device)      # refused before a launch
         faces_d, off, ids = self._tables(faces, V, device)
         view, shade, lights = self._device_consts(device)
         rot_d = tc_d = None
@@ -242,7 +269,11 @@ class MeshRenderer:
         background = r | g << 8 | b << 16 | 255 << 24
         rgba, depth, face_id = ops.render_raster(screen, normals, faces_d, shade, lights, self.height, self.width,
                                                  self.frustum["near"], self.frustum["far"], background,
-                                                 want_face_id=return_face_id or tex_img is not None, samples=self.samples)
+                                                 want_face_id=return_face_id or tex_img is not None or vcol is not None,
+                                                 samples=self.samples)
+        if vcol is not None:
+            ops.render_shade_vertex_color(screen, normals, faces_d, vcol, shade, lights, face_id, rgba, self.frustum["near"],
+                                          lit=lit, samples=self.samples, background=background)
         uvl = None
         if tex_img is not None:
             pyramid, vt, ft, tex_h, tex_w = self._texture(tex_img, tex_uv, faces_d.shape[0], device)
