@@ -1350,6 +1350,59 @@ int msmd_vertex_error_sums(const void* pred, const void* gt, long frame0, int n_
 int msmd_colormap_f64(const double* x, const unsigned char* lut, unsigned char* out, long N, double vmax, unsigned nan_color,
                       msmd_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Frame resizing: separable fixed-point resampling of 8-bit frames.  The operator is Pillow's
+ * Image.resize for 8-bit images: integer arithmetic on the device, coefficient tables built in float64 on the host
+ * (ops.resize_tables).  No floating point in the kernels; the bytes are a pure function of the source bytes and the tables.
+ *
+ * One axis is described by `bounds` (T, n_out, 2) int32 = (first source sample, number of taps) and `coef` (T, n_out, ksize)
+ * int32, the weights in units of 2^-22; T tables, and table_of_frame (N) int32 names the table of each frame for BOTH axes'
+ * table sets (so Tx == Ty is the caller's to keep; the kernels clamp the index into each set).  One 1-D pass:
+ *   out = clip((2^21 + sum_{i < taps} in[first + i] * coef[i]) >> 22, 0, 255), int32 accumulator, arithmetic shift.
+ * A frame is the horizontal pass over every source row, rounded to uint8 as above, then the vertical pass over that result.
+ * A pass that changes nothing is an identity table (first = o, taps = 1, coef = 2^22): the same bytes as no pass.
+ * Every index read from a table is clamped before use: first into [0, n_in - 1], taps into [0, min(ksize, n_in - first)],
+ * table_of_frame into [0, T - 1].  So no table can take a load outside the source, and the result for such a table is the
+ * operator on the clamped table.
+ *
+ * msmd_resize_u8: src (N, Hs, Ws, C) uint8, C in {1, 3, 4}, addressed by frame_stride / row_stride in bytes and pixel_stride
+ *   (1 for C = 1; 3 or 4 for C = 3, a 4th byte is never read; 4 for C = 4), any byte alignment.  dst (N, Hd, Wd, C) contiguous.
+ *   form MSMD_RESIZE_TWO_PASS: a horizontal launch into workspace (N, Hs, Wd, C) uint8, then a vertical launch; any sizes.
+ *   form MSMD_RESIZE_FUSED: one launch.  A workgroup owns MSMD_RESIZE_TILE_H output rows by MSMD_RESIZE_TILE_W output columns,
+ *     runs the horizontal pass for the source rows its vertical taps touch into LDS (uint8, rows padded by one word), then
+ *     the vertical pass from LDS.  rows_span is the caller's bound on the source rows one tile touches (the largest, over
+ *     the tiles of MSMD_RESIZE_TILE_H consecutive output rows and over the tables, of max(first + taps) - min(first)); the
+ *     kernel keeps that many rows and clamps a row index beyond them, so a wrong bound gives wrong bytes, never a wild access.
+ *   form MSMD_RESIZE_AUTO: msmd_resize_route chooses.
+ *   Output words are stored four bytes at a time where Wd * C % 4 == 0 and the buffer is 4-byte aligned, byte by byte
+ *   otherwise; 4-byte source pixels of a 4-channel frame are loaded as words where src and its strides allow: the same bytes.
+ * msmd_resize_fits: 1 when C is in {1, 3, 4}, 1 <= rows_span and rows_span * (MSMD_RESIZE_TILE_W * C + 4) <= MSMD_RESIZE_LDS_BYTES: the
+ *   fused form can run; else 0.
+ * msmd_resize_route: the form MSMD_RESIZE_AUTO takes.  MSMD_RESIZE_TWO_PASS where the fused form does not fit, and also where both
+ *   of these hold (measured): the tiles' overlap makes the fused form repeat more than one horizontal
+ *   multiply-add per intermediate byte, (rows_span * ceil(Hd / MSMD_RESIZE_TILE_H) - Hs) * kx > Hs, and the two-pass form's
+ *   intermediate stays in the last-level cache, N * Hs * Wd * C <= MSMD_RESIZE_CACHE_BYTES.  Else MSMD_RESIZE_FUSED.
+ *   Both are host functions: nothing is launched.
+ * msmd_resize_u8 returns 1 (hipErrorInvalidValue) before any launch for N < 0, a C outside {1, 3, 4}, a pixel_stride that
+ * does not go with C, Hs / Ws / Hd / Wd outside [1, MSMD_JPEG_MAX_SIDE], kx / ky / Tx / Ty < 1, strides under which rows or frames
+ * would overlap, a form outside the three, the fused form asked for where msmd_resize_fits refuses it, or, with work to
+ * do, a NULL pointer or the two-pass form without a workspace; N = 0 passes those checks, returns 0, looks at no pointer (the
+ * workspace included) and writes nothing; otherwise 0 or the launch's hipError_t. */
+#define MSMD_RESIZE_AUTO 0
+#define MSMD_RESIZE_FUSED 1
+#define MSMD_RESIZE_TWO_PASS 2
+#define MSMD_RESIZE_TILE_H 32
+#define MSMD_RESIZE_TILE_W 64
+#define MSMD_RESIZE_LDS_BYTES 65536
+#define MSMD_RESIZE_PRECISION_BITS 22
+#define MSMD_RESIZE_CACHE_BYTES 134217728
+int msmd_resize_fits(int C, int rows_span);
+int msmd_resize_route(int C, int rows_span, int N, int Hs, int Hd, int Wd, int kx);
+int msmd_resize_u8(const void* src, long frame_stride, long row_stride, int pixel_stride, int N, int Hs, int Ws, int C,
+                   const int* xbounds, const int* xcoef, int kx, int Tx, const int* ybounds, const int* ycoef, int ky, int Ty,
+                   const int* table_of_frame, void* dst, int Hd, int Wd, void* workspace, int rows_span, int form,
+                   msmd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

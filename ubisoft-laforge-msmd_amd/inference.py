@@ -17,6 +17,8 @@ SURVEY.md section 8(f) n3, the callers either side of the sampler:
   * ``load_audio_16k`` -- a `.wav` of any rate and channel count -> 16 kHz mono on the device (utils/audio.py, csrc/audio_io.hip).
   * ``--video`` -- the frames, JPEG-compressed on the device chunk by chunk (csrc/jpeg.hip), and the input WAV as one
     Motion-JPEG AVI (utils/media.py), where the reference calls ffmpeg (utils/media.py:combine_frames_and_audio).
+  * ``--source_video`` -- a Motion-JPEG AVI shown left of the render in that video, sampled to the render's frame rate and resized
+    to its height on the device (csrc/resize.hip).
   * ``--texture`` -- an `.npz` with `tex_img`, `vt`, `ft`: the frames are drawn with that texture.
   * ``--flame_tex`` -- an albedo `.npz` (BFM or FLAME texture space, plus `vt`, `ft`): the texture is evaluated by
     utils/flame.FLAMETex from ``--tex_code`` (default: the mean face) and the frames are drawn with it.
@@ -328,6 +330,8 @@ def build_parser():
     ap.add_argument("--video", action="store_true", help="write video_<clip>_seed_<s>.avi instead of the raw frames "
                                                          "(needs --render_size > 0)")
     ap.add_argument("--video_quality", type=int, default=90, help="JPEG quality of the video's frames, 1 .. 100")
+    ap.add_argument("--source_video", type=str, default=None, help="Motion-JPEG AVI shown left of the render in the video, sampled "
+                                                                   "to the render's frame rate and scaled to its height (needs --video)")
     # metric (not in the reference script; the loss is its utils/common.StyleAdherenceLoss)
     ap.add_argument("--style_adherence", action="store_true", help="write style_adherence_<clip>_seed_<s>.npy: every generated "
                                                                    "frame's soft-min distance to the whole style clip")
@@ -353,7 +357,34 @@ def parse_args(argv=None):
         ap.error("--tex_code needs --flame_tex: there is no texture space to evaluate it in")
     if not 1 <= args.video_quality <= 100:
         ap.error(f"--video_quality {args.video_quality} is outside [1, 100]")
+    if args.source_video is not None and not args.video:
+        ap.error("--source_video needs --video: it is a panel of the video")
     return args
+
+
+def load_source_panel(path, height, device="cuda"):
+    """--source_video's clip as the left panel of the video -> (frames (F, height, W', 3) uint8 on the device, fps as a Fraction):
+    decoded and scaled chunk by chunk (utils/media.read_video(size=)) to the render's height, the width keeping the aspect as
+    `media.side_by_side` rounds it."""
+    from . import ops
+    from .utils import media
+    clip = media.read_avi(path)
+    w, h = clip.size
+    if w < 1 or h < 1:
+        head = ops.jpeg_parse(clip.jpeg(0))[0]
+        w, h = head["width"], head["height"]
+    width = max(1, (2 * w * height + h) // (2 * h))
+    return media.read_video(path, device=device, size=(width, height)), clip.fps
+
+
+def beside_source(part, first, source, source_fps, fps):
+    """The frames [first, first + n) of the render, `part` (n, H, W, 3 | 4) uint8, with the source panel left of them: the source
+    frame of every output frame is `media.frames_at`'s, the one nearest in time."""
+    from .utils import media
+    n = part.shape[0]
+    idx = media.frames_at(first + n, fps, source.shape[0], source_fps)[first:]
+    left = source[torch.tensor(idx, device=source.device)]
+    return media.side_by_side([left, part[..., :3]], height=part.shape[1])
 
 
 def load_texture(path):
@@ -409,7 +440,8 @@ def main(argv=None):
     coefficients are also decoded by FLAME and rendered on the device (render_coeffs), and `frames_<clip>_seed_<s>.npy`
     ((T, N, N, 3) uint8) is written beside them.  With --video as well, `video_<clip>_seed_<s>.avi` is written in its place: the
     frames are JPEG-compressed on the device chunk by chunk as they are rendered (so one chunk of raw pixels is alive at a
-    time), at model_args.fps, with --audio_clip as the sound track when it is a `.wav` and silent otherwise.  --texture PATH
+    time), at model_args.fps, with --audio_clip as the sound track when it is a `.wav` and silent otherwise.  --source_video
+    CLIP.avi puts that clip left of the render (`load_source_panel`, `beside_source`); the sound stays --audio_clip.  --texture PATH
     (an `.npz` with tex_img, vt, ft) draws the frames textured, in either form; --flame_tex PATH (an albedo `.npz` with vt, ft)
     does so with the FLAMETex texture of --tex_code.  --render_samples 4 draws the frames anti-aliased, four samples per pixel
     (MeshRenderer(samples=4)), in every one of these forms.  --style_adherence also writes `style_adherence_<clip>_seed_<s>.npy`, (T,)
@@ -439,7 +471,7 @@ def main(argv=None):
     temp = os.path.join(args.output_dir, f"{args.model_name}_iter_{args.model_iter}", "temp")
     os.makedirs(temp, exist_ok=True)
     written = []
-    flame = renderer = None
+    flame = renderer = source = source_fps = None
     tex_img, tex_uv = load_texture(args.texture) if args.texture is not None else (None, None)
     if args.flame_tex is not None:
         tex_img, tex_uv = load_flame_texture(args.flame_tex, args.tex_type, args.tex_code, device)
@@ -475,16 +507,22 @@ def main(argv=None):
             print(f"style adherence (seed {seed}): mean {float(per_frame.mean()):.6f} over {per_frame.numel()} frames")
         if renderer is not None and args.video:
             from .utils import media
-            jpegs = []
+            jpegs, first, width = [], 0, args.render_size
+            if args.source_video is not None and source is None:
+                source, source_fps = load_source_panel(args.source_video, args.render_size, device)
             for part in render_coeffs_chunks(torch.cat([exp_code, head_rot], dim=-1), shape_coef.reshape(1, -1), flame, None,
                                              renderer, chunk=256, tex_img=tex_img, tex_uv=tex_uv):
+                if source is not None:
+                    n = part.shape[0]
+                    part = beside_source(part, first, source, source_fps, model_args.fps)
+                    first, width = first + n, part.shape[2]
                 jpegs += media.encode_jpeg(part, args.video_quality)
             sound = None
             if args.audio_clip.lower().endswith(".wav"):
                 from .utils.audio import read_wav
                 sound = read_wav(args.audio_clip)
             out = os.path.join(temp, f"video_{clip}_seed_{seed}.avi")
-            media.write_avi(out, jpegs, model_args.fps, (args.render_size, args.render_size), sound)
+            media.write_avi(out, jpegs, model_args.fps, (width, args.render_size), sound)
             written.append(out)
         elif renderer is not None:
             frames = render_coeffs(torch.cat([exp_code, head_rot], dim=-1), shape_coef.reshape(1, -1), flame, None, renderer,

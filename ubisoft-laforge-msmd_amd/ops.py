@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import ctypes
 import functools
+import math
 import os
 
 import numpy as np
@@ -2100,6 +2101,253 @@ def face_crop(frames, inverse, table, out_size, dtype=torch.float32, swap_rb=Tru
     _lib.check(_lib.load().msmd_face_crop(_p(frames), sb, sh, sw, F, H, W, _p(inverse), _p(table), S_h, S_w, int(bool(swap_rb)),
                                           _p(out), _CROP_DTYPES[dtype], _p(crop), _stream()), "msmd_face_crop")
     return out, crop
+
+
+# ----------------------------------------------------------------------------- frame resizing (csrc/resize.hip)
+RESIZE_AUTO, RESIZE_FUSED, RESIZE_TWO_PASS = _h("RESIZE_AUTO", "RESIZE_FUSED", "RESIZE_TWO_PASS")
+RESIZE_TILE_H, RESIZE_TILE_W, RESIZE_LDS_BYTES = _h("RESIZE_TILE_H", "RESIZE_TILE_W", "RESIZE_LDS_BYTES")
+RESIZE_PRECISION_BITS, RESIZE_CACHE_BYTES = _h("RESIZE_PRECISION_BITS", "RESIZE_CACHE_BYTES")
+RESIZE_FORMS = {None: RESIZE_AUTO, "fused": RESIZE_FUSED, "two_pass": RESIZE_TWO_PASS}
+_RESIZE_FORM_NAMES = {RESIZE_FUSED: "fused", RESIZE_TWO_PASS: "two_pass"}
+
+
+def _resize_box(x):
+    return 1.0 if -0.5 < x <= 0.5 else 0.0
+
+
+def _resize_bilinear(x):
+    x = -x if x < 0.0 else x
+    return 1.0 - x if x < 1.0 else 0.0
+
+
+def _resize_bicubic(x):
+    a = -0.5
+    x = -x if x < 0.0 else x
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    if x < 2.0:
+        return (((x - 5) * x + 8) * x - 4) * a
+    return 0.0
+
+
+def _resize_sinc(x):
+    if x == 0.0:
+        return 1.0
+    x = x * math.pi
+    return math.sin(x) / x
+
+
+def _resize_lanczos(x):
+    return _resize_sinc(x) * _resize_sinc(x / 3) if -3.0 <= x < 3.0 else 0.0
+
+
+RESIZE_FILTERS = {"box": (_resize_box, 0.5), "bilinear": (_resize_bilinear, 1.0), "bicubic": (_resize_bicubic, 2.0),
+                  "lanczos": (_resize_lanczos, 3.0)}
+
+
+@functools.lru_cache(maxsize=256)
+def resize_tables(n_in, n_out, filter, in0=None, in1=None):
+    """One axis of Pillow's 8-bit `Image.resize`: n_in samples -> n_out over the source interval [in0, in1) (the whole axis by
+    default) -> (bounds (n_out, 2) int32 = (first tap, taps), coef (n_out, ksize) int32 in units of 2^-22, zero behind the
+    taps).  Python floats in Pillow's order of operations; the arrays are cached and read-only.  Raises
+    ValueError for an unknown filter, a size below 1, an interval that is empty or leaves the axis, and a table under which
+    the int32 accumulator could overflow."""
+    if filter not in RESIZE_FILTERS:
+        raise ValueError(f"filter must be one of {sorted(RESIZE_FILTERS)}, got {filter!r}")
+    n_in, n_out = int(n_in), int(n_out)
+    if n_in < 1 or n_out < 1:
+        raise ValueError(f"resize_tables: sizes {n_in} -> {n_out} must be at least 1")
+    in0, in1 = float(0 if in0 is None else in0), float(n_in if in1 is None else in1)
+    if not 0.0 <= in0 < in1 <= n_in:
+        raise ValueError(f"resize_tables: the interval [{in0}, {in1}) is empty or leaves [0, {n_in}]")
+    f, support = RESIZE_FILTERS[filter]
+    scale = (in1 - in0) / n_out
+    fs = max(scale, 1.0)
+    sup = support * fs
+    ksize = int(math.ceil(sup)) * 2 + 1
+    ss = 1.0 / fs
+    one = float(1 << RESIZE_PRECISION_BITS)
+    bounds = np.zeros((n_out, 2), np.int32)
+    coef = np.zeros((n_out, ksize), np.int32)
+    for xx in range(n_out):
+        center = in0 + (xx + 0.5) * scale
+        xmin = max(0, int(center - sup + 0.5))
+        xmax = min(n_in, int(center + sup + 0.5)) - xmin
+        w = [f((i + xmin - center + 0.5) * ss) for i in range(xmax)]
+        ww = 0.0
+        for v in w:
+            ww += v
+        if ww != 0.0:
+            w = [v / ww for v in w]
+        k = [int(0.5 + v * one) if v >= 0 else int(-0.5 + v * one) for v in w]
+        if sum(abs(v) for v in k) * 255 + (1 << (RESIZE_PRECISION_BITS - 1)) >= 1 << 31:
+            raise ValueError(f"resize_tables: {n_in} -> {n_out} ({filter}): output {xx} could overflow the int32 accumulator")
+        bounds[xx] = (xmin, xmax)
+        coef[xx, :xmax] = k
+    bounds.setflags(write=False)
+    coef.setflags(write=False)
+    return bounds, coef
+
+
+def _resize_identity(n):
+    """The table of a pass that is skipped: one tap of weight 1 at the output's own position."""
+    bounds = np.stack([np.arange(n, dtype=np.int32), np.ones(n, np.int32)], 1)
+    return bounds, np.full((n, 1), 1 << RESIZE_PRECISION_BITS, np.int32)
+
+
+def _resize_axis(n_in, n_out, filter, in0, in1):
+    """`resize_tables`, or the identity where the pass is skipped: the axis keeps its size over the whole-axis interval."""
+    if n_in == n_out and in0 == 0.0 and in1 == float(n_in):
+        if filter not in RESIZE_FILTERS:
+            raise ValueError(f"filter must be one of {sorted(RESIZE_FILTERS)}, got {filter!r}")
+        return _resize_identity(n_in)
+    return resize_tables(n_in, n_out, filter, in0, in1)
+
+
+def _resize_stack(tables):
+    """[(bounds, coef)] of one axis -> (bounds (T, n_out, 2), coef (T, n_out, ksize)), the weights padded with zeros to one ksize."""
+    ksize = max(c.shape[1] for _, c in tables)
+    coef = np.zeros((len(tables), tables[0][1].shape[0], ksize), np.int32)
+    for t, (_, c) in enumerate(tables):
+        coef[t, :, :c.shape[1]] = c
+    return np.ascontiguousarray(np.stack([b for b, _ in tables])), coef
+
+
+def resize_rows_span(ybounds, n_in, ksize):
+    """The source rows one tile of RESIZE_TILE_H output rows touches, at most, over the tables of ybounds (T, n_out, 2): what
+    msmd_resize_u8 takes as rows_span.  The bounds are clamped as the kernel clamps them."""
+    b = np.asarray(ybounds).reshape(-1, np.asarray(ybounds).shape[-2], 2).astype(np.int64)
+    first = np.clip(b[..., 0], 0, n_in - 1)
+    end = first + np.clip(b[..., 1], 0, np.minimum(ksize, n_in - first))
+    span = 0
+    for y0 in range(0, b.shape[1], RESIZE_TILE_H):
+        span = max(span, int((end[:, y0:y0 + RESIZE_TILE_H].max(1) - first[:, y0:y0 + RESIZE_TILE_H].min(1)).max()))
+    return span
+
+
+def resize_fits(C, rows_span):
+    """-> bool: msmd_resize_fits, whether the fused form can run: the tile's rows_span intermediate rows of RESIZE_TILE_W * C + 4
+    bytes fit RESIZE_LDS_BYTES."""
+    return bool(_lib.load().msmd_resize_fits(int(C), int(rows_span)))
+
+
+def resize_route(C, rows_span, N, Hs, Hd, Wd, kx):
+    """-> "fused" | "two_pass": msmd_resize_route, the rule msmd_resize_u8 follows when no form is forced.  Fused where it fits,
+    except where the tiles' overlap repeats more than one horizontal multiply-add per intermediate byte
+    ((rows_span * ceil(Hd / RESIZE_TILE_H) - Hs) * kx > Hs) while the two-pass intermediate of N * Hs * Wd * C bytes stays within
+    RESIZE_CACHE_BYTES: there the two launches were measured faster."""
+    return _RESIZE_FORM_NAMES[_lib.load().msmd_resize_route(int(C), int(rows_span), int(N), int(Hs), int(Hd), int(Wd), int(kx))]
+
+
+def _resize_source(frames):
+    """Checks of (N, H, W, 1 | 3 | 4) uint8 device frames, laid out as `_u8_frames` accepts them (one byte per pixel for one
+    channel) -> (N, H, W, C, frame stride, row stride, pixel stride).  N = 0 is allowed."""
+    if not torch.is_tensor(frames) or frames.dtype != torch.uint8:
+        raise TypeError("frames must be a uint8 tensor")
+    if not frames.is_cuda:
+        raise TypeError("frames must be on the MI355X (cuda) device; there is no CPU resampler")
+    if frames.dim() != 4 or frames.shape[3] not in (1, 3, 4):
+        raise TypeError(f"frames must have shape (N, H, W, 1 | 3 | 4), got {tuple(frames.shape)}")
+    N, H, W, C = frames.shape
+    if not (1 <= H <= JPEG_MAX_SIDE and 1 <= W <= JPEG_MAX_SIDE):
+        raise ValueError(f"frames of shape {tuple(frames.shape)}: 1 <= H, W <= {JPEG_MAX_SIDE} is required")
+    sb, sh, sw, sc = frames.stride()
+    if C == 1:
+        sc = 1                                          # the stride of a dimension of size 1 is arbitrary
+    if sc != 1 or not (sw == C or (C == 3 and sw == 4)) or sh < (W - 1) * sw + C or (N > 1 and sb < (H - 1) * sh + (W - 1) * sw + C):
+        raise TypeError(f"frames with strides {frames.stride()}: channels must be adjacent bytes, pixels {C} bytes apart (3 or 4 "
+                        "for 3 channels), rows and frames must not overlap (call .contiguous())")
+    return N, H, W, C, sb, sh, sw
+
+
+def resize_u8(frames, xbounds, xcoef, ybounds, ycoef, table_of_frame, size, out=None, form=None, rows_span=None):
+    """msmd_resize_u8 on tables that are already on the device: frames (N, Hs, Ws, C) -> (N, Hd, Wd, C), size = (Hd, Wd).
+    xbounds (T, Wd, 2), xcoef (T, Wd, kx), ybounds (T, Hd, 2), ycoef (T, Hd, ky), table_of_frame (N), all int32.  rows_span as
+    `resize_rows_span` gives it for ybounds (required for the fused form; the route without it is two_pass).  form: None for
+    `resize_route`'s choice.  The two-pass
+    workspace is allocated here."""
+    N, Hs, Ws, C, sb, sh, sw = _resize_source(frames)
+    Hd, Wd = int(size[0]), int(size[1])
+    if form not in RESIZE_FORMS:
+        raise ValueError(f"form must be None, 'fused' or 'two_pass', got {form!r}")
+    d = {"N": N, "Hd": Hd, "Wd": Wd}
+    _arg("xbounds", xbounds, torch.int32, "T+ Wd 2", d)
+    _arg("xcoef", xcoef, torch.int32, "T Wd kx+", d)
+    _arg("ybounds", ybounds, torch.int32, "T Hd 2", d)
+    _arg("ycoef", ycoef, torch.int32, "T Hd ky+", d)
+    _arg("table_of_frame", table_of_frame, torch.int32, "N", d)
+    _arg("out", out, torch.uint8, (N, Hd, Wd, C), optional=True)
+    rows_span = 0 if rows_span is None else int(rows_span)
+    lib = _lib.load()
+    route = lib.msmd_resize_route(C, rows_span, N, Hs, Hd, Wd, d["kx"])
+    if form == "fused" and not lib.msmd_resize_fits(C, rows_span):
+        raise ValueError(f"resize: the fused form does not fit: {rows_span} intermediate rows of {RESIZE_TILE_W * C + 4} bytes "
+                         f"against {RESIZE_LDS_BYTES} bytes of LDS")
+    code = RESIZE_FORMS[form] or route
+    dst = out if out is not None else torch.empty(N, Hd, Wd, C, device=frames.device, dtype=torch.uint8)
+    ws = torch.empty(N * Hs * Wd * C, device=frames.device, dtype=torch.uint8) if code == RESIZE_TWO_PASS else None
+    _lib.check(lib.msmd_resize_u8(_p(frames), sb, sh, sw, N, Hs, Ws, C, _p(xbounds), _p(xcoef), d["kx"], d["T"], _p(ybounds),
+                                  _p(ycoef), d["ky"], d["T"], _p(table_of_frame), _p(dst), Hd, Wd, _p(ws), rows_span, code,
+                                  _stream()), "msmd_resize_u8")
+    return dst
+
+
+def _resize_plan(Hs, Ws, Hd, Wd, filter, boxes, device):
+    """The tables of the distinct boxes of a call, on the device of that name -> (xbounds, xcoef, ybounds, ycoef, rows_span).
+    boxes: a tuple of (x0, y0, x1, y1), already rounded to float32.  Nothing on the device is kept: a set of boxes per frame
+    is unlikely to come again (the 1-D host tables behind it are cached by `resize_tables`)."""
+    xs = [_resize_axis(Ws, Wd, filter, b[0], b[2]) for b in boxes]
+    ys = [_resize_axis(Hs, Hd, filter, b[1], b[3]) for b in boxes]
+    (xb, xc), (yb, yc) = _resize_stack(xs), _resize_stack(ys)
+    up = lambda a: torch.from_numpy(a).to(device)
+    return up(xb), up(xc), up(yb), up(yc), resize_rows_span(yb, Hs, yc.shape[2])
+
+
+@functools.lru_cache(maxsize=32)
+def _resize_plan_shared(Hs, Ws, Hd, Wd, filter, box, device):
+    """`_resize_plan` for one box shared by every frame, uploaded once for the calls of a video (a few hundred KB at most)."""
+    return _resize_plan(Hs, Ws, Hd, Wd, filter, (box,), device)
+
+
+def resize_frames(frames, size, filter="bilinear", box=None, out=None, form=None):
+    """frames (N, Hs, Ws, 1 | 3 | 4) uint8 on the device -> (N, Hd, Wd, C) uint8, size = (Wd, Hd) as Pillow orders it: the bytes
+    of `PIL.Image.resize(size, filter, box=, reducing_gap=None)` on every frame (four channels are four plain channels, Pillow's
+    CMYK).  filter: "box", "bilinear", "bicubic" or "lanczos".  box: None, one (x0, y0, x1, y1) for all frames
+    or (N, 4) with one per frame, in source pixels, rounded to float32, 0 <= x0 < x1 <= Ws and the same in y; frames with equal
+    boxes share a table.  out: a contiguous (N, Hd, Wd, C) uint8 device tensor to write.  form: None (the route's choice,
+    `resize_route`), "fused" or "two_pass"; a forced fused form that does not fit raises ValueError.  A row stride above the row,
+    the renderer's RGB view of RGBA and any byte alignment are taken as they are."""
+    N, Hs, Ws, C, _, _, _ = _resize_source(frames)
+    if filter not in RESIZE_FILTERS:
+        raise ValueError(f"filter must be one of {sorted(RESIZE_FILTERS)}, got {filter!r}")
+    try:
+        Wd, Hd = (int(s) for s in size)
+    except (TypeError, ValueError):
+        raise ValueError(f"size must be (width, height), got {size!r}") from None
+    if not (1 <= Hd <= JPEG_MAX_SIDE and 1 <= Wd <= JPEG_MAX_SIDE):
+        raise ValueError(f"size {size!r}: 1 <= width, height <= {JPEG_MAX_SIDE} is required")
+    if box is None:
+        boxes = np.array([[0, 0, Ws, Hs]], np.float64)
+    else:
+        boxes = np.asarray(box.cpu() if torch.is_tensor(box) else box, dtype=np.float64)
+        if boxes.shape != (4,) and boxes.shape != (N, 4):
+            raise ValueError(f"box must be None, (x0, y0, x1, y1) or ({N}, 4), got shape {boxes.shape}")
+        boxes = boxes.reshape(-1, 4).astype(np.float32).astype(np.float64)      # Pillow's C code stores a box as float32
+        if not (np.isfinite(boxes).all() and (0 <= boxes[:, :2]).all() and (boxes[:, :2] < boxes[:, 2:]).all()
+                and (boxes[:, 2] <= Ws).all() and (boxes[:, 3] <= Hs).all()):
+            raise ValueError(f"box {box!r}: 0 <= x0 < x1 <= {Ws} and 0 <= y0 < y1 <= {Hs} are required")
+    keys = [tuple(b) for b in boxes.tolist()] or [(0.0, 0.0, float(Ws), float(Hs))]     # an empty batch with an empty (0, 4) box
+    distinct = tuple(dict.fromkeys(keys))
+    if len(distinct) == 1:
+        xb, xc, yb, yc, span = _resize_plan_shared(Hs, Ws, Hd, Wd, filter, distinct[0], str(frames.device))
+    else:
+        xb, xc, yb, yc, span = _resize_plan(Hs, Ws, Hd, Wd, filter, distinct, str(frames.device))
+    if len(keys) == 1:
+        tof = torch.zeros(N, device=frames.device, dtype=torch.int32)
+    else:
+        at = {k: t for t, k in enumerate(distinct)}
+        tof = torch.tensor([at[k] for k in keys], dtype=torch.int32).to(frames.device)
+    return resize_u8(frames, xb, xc, yb, yc, tof, (Hd, Wd), out=out, form=form, rows_span=span)
 
 
 # ----------------------------------------------------------------------------- style losses (csrc/style_loss.hip, DESIGN.md 5.19)

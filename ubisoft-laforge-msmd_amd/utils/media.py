@@ -8,6 +8,10 @@ leaves it at its compressed size; this module only lays the bytes out as RIFF `A
 Frames in: `read_avi` finds the JPEG files inside a Motion-JPEG AVI, this project's or another writer's,
 `read_video` decodes them on the device with `ops.jpeg_decode` (baseline, grey / 4:4:4 / 4:2:2 / 4:2:0), and `extract_frames`
 writes them out as `.jpg` files, which is what the reference's helper of that name does through ffmpeg.
+
+Frames of another size: `read_video(size=)` stores a clip at the size it is wanted, `side_by_side` joins panels of
+different sizes at one height, `frames_at` picks the source frame nearest in time, and `python -m msmd_amd.utils.media --resize
+IN.avi OUT.avi --size WxH` re-encodes a clip; all of them resize with `ops.resize_frames` (csrc/resize.hip).
 """
 from __future__ import annotations
 
@@ -286,14 +290,17 @@ def read_avi(path):
     return AviClip(data, frames, Fraction(vs["rate"], vs["scale"]), (int(width), abs(int(height))), track)
 
 
-def read_video(path, channels=3, chunk=256, device="cuda"):
+def read_video(path, channels=3, chunk=256, device="cuda", size=None, resample="bilinear"):
     """A Motion-JPEG AVI -> its frames as one (F, H, W, channels) uint8 tensor on the device, `chunk` frames decoded per call of
-    `ops.jpeg_decode`.  A frame whose size or sampling differs from the first raises ValueError; so does a damaged one."""
+    `ops.jpeg_decode`.  A frame whose size or sampling differs from the first raises ValueError; so does a damaged one.
+    size = (width, height): every decoded chunk is resized with `ops.resize_frames(chunk, size, resample)` before it is stored,
+    so the clip never lives on the device at its full size; the result is `resize_frames` of what `size=None` returns."""
     import torch
     clip = read_avi(path)
     first = ops.jpeg_parse(clip.jpeg(0))[0]
     shape = (first["height"], first["width"], first["layout"])
-    out = torch.empty(len(clip.frames), shape[0], shape[1], channels, device=device, dtype=torch.uint8)
+    width, height = (shape[1], shape[0]) if size is None else (int(s) for s in size)
+    out = torch.empty(len(clip.frames), height, width, channels, device=device, dtype=torch.uint8)
     for i in range(0, len(clip.frames), int(chunk)):
         j = min(i + int(chunk), len(clip.frames))
         h = ops.jpeg_parse(clip.jpeg(i))[0]
@@ -301,7 +308,9 @@ def read_video(path, channels=3, chunk=256, device="cuda"):
             raise ValueError(f"{path}: frame {i} is {h['height']} x {h['width']} layout {h['layout']}, frame 0 is "
                              f"{shape[0]} x {shape[1]} layout {shape[2]}")
         files = [clip.jpeg(k) for k in range(i, j)]
-        if out[i:j].data_ptr() % 4 == 0:
+        if size is not None:
+            ops.resize_frames(ops.jpeg_decode(files, channels=channels, device=out.device), (width, height), resample, out=out[i:j])
+        elif out[i:j].data_ptr() % 4 == 0:
             ops.jpeg_decode(files, channels=channels, out=out[i:j])
         else:
             out[i:j] = ops.jpeg_decode(files, channels=channels, device=out.device)
@@ -328,3 +337,76 @@ def extract_frames(filename, output_dir, quality=1):
             fh.write(raw)
         paths.append(p)
     return paths
+
+
+# ----------------------------------------------------------------------------- frames of another size
+def frames_at(n_out, fps_out, n_src, fps_src):
+    """-> list of n_out source frame numbers: for output frame k, shown at k / fps_out, the source frame nearest in time,
+    min(n_src - 1, (2 k a + b) // (2 b)) with a / b = fps_src / fps_out in lowest terms.  Integer arithmetic on `fps_fraction`'s
+    numerators and denominators: a tie goes to the later frame, and no float decides a frame."""
+    if n_src < 1:
+        raise ValueError(f"frames_at: n_src = {n_src} must be at least 1")
+    (rs, ss), (ro, so) = fps_fraction(fps_src), fps_fraction(fps_out)
+    ratio = Fraction(rs * so, ss * ro)
+    a, b = ratio.numerator, ratio.denominator
+    return [min(n_src - 1, (2 * k * a + b) // (2 * b)) for k in range(int(n_out))]
+
+
+def side_by_side(panels, height=None, resample="bilinear"):
+    """panels: a list of (F, H_i, W_i, 3) uint8 device tensors with one F -> (F, height, sum W_i', 3): every panel scaled to the
+    common height (the first panel's by default) with `ops.resize_frames`, its width W_i' = max(1, (2 W_i height + H_i) //
+    (2 H_i)), the nearest integer that keeps its aspect, and the panels laid left to right.  A panel that already has the
+    height is copied as it is."""
+    import torch
+    panels = list(panels)
+    if not panels:
+        raise ValueError("side_by_side: no panels")
+    F = panels[0].shape[0]
+    for p in panels:
+        if not torch.is_tensor(p) or p.dim() != 4 or p.shape[3] != 3 or p.shape[0] != F or p.dtype != torch.uint8:
+            raise TypeError(f"side_by_side: every panel must be a ({F}, H, W, 3) uint8 tensor, got {getattr(p, 'shape', type(p))}")
+    height = int(panels[0].shape[1] if height is None else height)
+    if height < 1:
+        raise ValueError(f"side_by_side: height = {height} must be at least 1")
+    widths = [max(1, (2 * p.shape[2] * height + p.shape[1]) // (2 * p.shape[1])) for p in panels]
+    out = torch.empty(F, height, sum(widths), 3, device=panels[0].device, dtype=torch.uint8)
+    at = 0
+    for p, w in zip(panels, widths):
+        if (p.shape[1], p.shape[2]) == (height, w):
+            out[:, :, at:at + w] = p
+        else:
+            out[:, :, at:at + w] = ops.resize_frames(p, (w, height), resample)
+        at += w
+    return out
+
+
+def resize_video(src, dst, size, resample="bilinear", quality=90, chunk=64):
+    """Re-encode the Motion-JPEG AVI `src` at size = (width, height) into `dst`: decode, `ops.resize_frames`, encode, `chunk`
+    frames at a time; the frame rate and the audio track are carried over.  -> bytes written."""
+    clip = read_avi(src)
+    width, height = (int(s) for s in size)
+    jpegs = []
+    for i in range(0, len(clip.frames), int(chunk)):
+        files = [clip.jpeg(k) for k in range(i, min(i + int(chunk), len(clip.frames)))]
+        jpegs += encode_jpeg(ops.resize_frames(ops.jpeg_decode(files), (width, height), resample), quality)
+    return write_avi(dst, jpegs, clip.fps, (width, height), clip.audio)
+
+
+def main(argv=None):
+    import argparse
+    ap = argparse.ArgumentParser(prog="python -m msmd_amd.utils.media", description="Re-encode a Motion-JPEG AVI at a new size.")
+    ap.add_argument("--resize", nargs=2, metavar=("IN.avi", "OUT.avi"), required=True)
+    ap.add_argument("--size", required=True, metavar="WxH")
+    ap.add_argument("--filter", default="bilinear", choices=sorted(ops.RESIZE_FILTERS))
+    ap.add_argument("--quality", type=int, default=90)
+    a = ap.parse_args(argv)
+    try:
+        width, height = (int(v) for v in a.size.lower().split("x"))
+    except ValueError:
+        ap.error(f"--size must be WxH, got {a.size!r}")
+    n = resize_video(a.resize[0], a.resize[1], (width, height), a.filter, a.quality)
+    print(f"{a.resize[1]}: {width} x {height}, {n} bytes")
+
+
+if __name__ == "__main__":
+    main()
