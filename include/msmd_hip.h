@@ -1403,6 +1403,66 @@ int msmd_resize_u8(const void* src, long frame_stride, long row_stride, int pixe
                    const int* table_of_frame, void* dst, int Hd, int Wd, void* workspace, int rows_span, int form,
                    msmd_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Overlays: 2-D primitives drawn onto 8-bit frames that are already on the device.  Integer arithmetic
+ * throughout; the bytes are a pure function of the source bytes, the records and the font table.
+ *
+ * Coordinates are int32 in units of 1/16 pixel: pixel (column j, row i) covers [16 j, 16 j + 16) x [16 i, 16 i + 16).  The sample
+ * points of a pixel are its corner (16 j, 16 i) plus the offset (8, 8) for samples = 1, and plus the 4 x 4 grid of offsets
+ * {2, 6, 10, 14} in each axis for samples = 16.
+ *
+ * prims (P, 8) int32, one record = [kind, x0, y0, x1, y1, r, aux, colour], colour = R | G << 8 | B << 16 | A << 24.
+ * prim_offsets (N + 1) int32: frame f draws the records [off[f], off[f + 1]) in that order; the kernel clamps both ends into
+ * [0, P] and makes the end no less than the begin, so a bad table gives wrong pictures, never a load outside prims.
+ * With p a sample point and q = p - (x0, y0), p is inside a record of
+ *   MSMD_OVERLAY_NONE (0)     never: padding;
+ *   MSMD_OVERLAY_DISC (1)     iff aux^2 <= |q|^2 <= r^2: a filled disc for aux = 0, else a ring of inner radius aux;
+ *   MSMD_OVERLAY_CAPSULE (2)  the segment a = (x0, y0) -> b = (x1, y1) of half-width r with round caps, decided without a
+ *                             division: d = b - a, L = d.d, s = q.d; s <= 0: iff |q|^2 <= r^2; s >= L: iff |p - b|^2 <= r^2;
+ *                             otherwise iff (qx dy - qy dx)^2 <= r^2 L, compared on 128-bit products (the left side reaches 2^86
+ *                             at the coordinate limits); a = b is the disc;
+ *   MSMD_OVERLAY_BOX (3)      iff x0 <= px <= x1 and y0 <= py <= y1 and, for aux > 0, NOT (x0 + aux <= px <= x1 - aux and
+ *                             y0 + aux <= py <= y1 - aux): an outline of thickness aux drawn inwards, filled for aux = 0;
+ *   MSMD_OVERLAY_GLYPH (4)    one character: font (n_glyphs, 8) uint8, row v of a glyph is one byte, bit 7 - u set = font pixel
+ *                             (u, v) is ink; x1 is the side of a font pixel in 1/16 px, y1 the glyph index; u = (px - x0) div x1,
+ *                             v = (py - y0) div x1 (floor division); iff 0 <= u, v < 8 and the bit is set.
+ * A record draws nothing if its kind is outside 0 .. 4; if x0 or y0, or for the kinds 1 .. 3 x1 or y1, lies outside
+ * +-MSMD_OVERLAY_MAX_COORD; if r or aux lies outside [0, MSMD_OVERLAY_MAX_RADIUS]; or if it is a glyph with y1 outside
+ * [0, n_glyphs) or x1 outside [1, MSMD_OVERLAY_MAX_RADIUS].
+ *
+ * Blend: for each record in list order and each pixel, cov = the number of the pixel's sample points inside the record,
+ * w = cov * (16 / samples) * A, and every written channel with destination byte d and colour byte c becomes
+ *   d <- (d * (4080 - w) + c * w + 2040) div 4080.
+ * C = 1 takes colour byte 0; C = 3 and C = 4 take colour bytes 0 .. 2 into channels 0 .. 2 in memory order (RGB or BGR is the
+ * caller's business); the fourth byte of a 4-channel pixel is never read or written.
+ *
+ * msmd_draw_overlay: src, dst (N, H, W, C) uint8, C in {1, 3, 4}, both addressed by frame_stride / row_stride in bytes and
+ *   pixel_stride (1 for C = 1; 3 or 4 for C = 3; 4 for C = 4), any byte alignment.  src == dst draws in place; otherwise the two
+ *   must not overlap (the caller's to keep) and dst receives every pixel, drawn on or not.  One launch: a workgroup of 256
+ *   threads owns MSMD_OVERLAY_TILE_W x MSMD_OVERLAY_TILE_H pixels of one frame, four horizontally adjacent pixels per thread;
+ *   per MSMD_OVERLAY_CHUNK records it tests each record's bounding box against the tile, compacts the hits in order into LDS
+ *   and every pixel walks that list.  Pixels are loaded once and stored once; a tile no record touches writes nothing in place
+ *   and copies otherwise.  Pixels go as whole words where C = pixel_stride is 1 or 3 and both buffers and both strides are
+ *   4-byte aligned, byte by byte otherwise: the same bytes.  No allocation, no host synchronisation.
+ * Returns 1 (hipErrorInvalidValue) before any launch for N < 0 or n_prims < 0, a C outside {1, 3, 4}, a pixel_stride that does
+ * not go with C, H or W outside [1, MSMD_JPEG_MAX_SIDE], strides under which rows or frames would overlap, samples outside
+ * {1, 16}, n_glyphs < 0, or, with work to do, a NULL src, dst or prim_offsets, NULL prims with n_prims > 0 or NULL font with
+ * n_glyphs > 0; N = 0 passes those checks, returns 0, looks at no pointer and writes nothing; otherwise 0 or the launch's
+ * hipError_t. */
+#define MSMD_OVERLAY_NONE 0
+#define MSMD_OVERLAY_DISC 1
+#define MSMD_OVERLAY_CAPSULE 2
+#define MSMD_OVERLAY_BOX 3
+#define MSMD_OVERLAY_GLYPH 4
+#define MSMD_OVERLAY_TILE_W 64
+#define MSMD_OVERLAY_TILE_H 16
+#define MSMD_OVERLAY_CHUNK 256
+#define MSMD_OVERLAY_MAX_COORD (1 << 20)
+#define MSMD_OVERLAY_MAX_RADIUS (1 << 16)
+int msmd_draw_overlay(const void* src, void* dst, long frame_stride, long row_stride, int pixel_stride, int N, int H, int W, int C,
+                      const int* prims, long n_prims, const int* prim_offsets, const unsigned char* font, int n_glyphs,
+                      int samples, msmd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

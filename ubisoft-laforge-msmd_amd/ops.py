@@ -2254,7 +2254,9 @@ def _resize_source(frames):
     sb, sh, sw, sc = frames.stride()
     if C == 1:
         sc = 1                                          # the stride of a dimension of size 1 is arbitrary
-    if sc != 1 or not (sw == C or (C == 3 and sw == 4)) or sh < (W - 1) * sw + C or (N > 1 and sb < (H - 1) * sh + (W - 1) * sw + C):
+    if N == 0:
+        sb, sh, sw = H * W * C, W * C, C                 # an empty batch has no addresses: whatever strides it carries are not used
+    elif sc != 1 or not (sw == C or (C == 3 and sw == 4)) or sh < (W - 1) * sw + C or (N > 1 and sb < (H - 1) * sh + (W - 1) * sw + C):
         raise TypeError(f"frames with strides {frames.stride()}: channels must be adjacent bytes, pixels {C} bytes apart (3 or 4 "
                         "for 3 channels), rows and frames must not overlap (call .contiguous())")
     return N, H, W, C, sb, sh, sw
@@ -2348,6 +2350,41 @@ def resize_frames(frames, size, filter="bilinear", box=None, out=None, form=None
         at = {k: t for t, k in enumerate(distinct)}
         tof = torch.tensor([at[k] for k in keys], dtype=torch.int32).to(frames.device)
     return resize_u8(frames, xb, xc, yb, yc, tof, (Hd, Wd), out=out, form=form, rows_span=span)
+
+
+# ----------------------------------------------------------------------------- overlays (csrc/overlay.hip)
+OVERLAY_NONE, OVERLAY_DISC, OVERLAY_CAPSULE, OVERLAY_BOX, OVERLAY_GLYPH = _h("OVERLAY_NONE", "OVERLAY_DISC", "OVERLAY_CAPSULE",
+                                                                             "OVERLAY_BOX", "OVERLAY_GLYPH")
+OVERLAY_TILE_W, OVERLAY_TILE_H, OVERLAY_CHUNK = _h("OVERLAY_TILE_W", "OVERLAY_TILE_H", "OVERLAY_CHUNK")
+OVERLAY_MAX_COORD, OVERLAY_MAX_RADIUS = _h("OVERLAY_MAX_COORD", "OVERLAY_MAX_RADIUS")
+OVERLAY_SAMPLES = (1, 16)
+
+
+def draw_overlay(frames, prims, prim_offsets, font=None, samples=16, out=None):
+    """msmd_draw_overlay: the records of prims (P, 8) int32 = [kind, x0, y0, x1, y1, r, aux, colour] drawn onto frames (N, H, W,
+    1 | 3 | 4) uint8 on the device, frame f taking the records [prim_offsets[f], prim_offsets[f + 1]) in that order (prim_offsets
+    (N + 1) int32); coordinates in 1/16 pixel, the rule in include/msmd_hip.h.  font (n_glyphs, 8) uint8 serves the glyph records
+    (None: no glyph draws).  samples: 1 or 16 sample points per pixel.  frames may be a strided view (a panel of a wider frame, a
+    4-byte pixel stride under 3 channels, any byte alignment) whose channels are adjacent bytes.  out=None draws in place and
+    returns frames; otherwise out is a uint8 device tensor of the same shape and strides that does not overlap frames, receives
+    every pixel and is returned."""
+    _need_cuda(frames, prims, prim_offsets, font, out)
+    N, H, W, C, sb, sh, sw = _resize_source(frames)
+    if samples not in OVERLAY_SAMPLES:
+        raise ValueError(f"samples must be one of {OVERLAY_SAMPLES}, got {samples!r}")
+    d = {}
+    _arg("prims", prims, torch.int32, "P 8", d)
+    _arg("prim_offsets", prim_offsets, torch.int32, (N + 1,))
+    _arg("font", font, torch.uint8, "G 8", d, optional=True)
+    if out is not None:
+        if not torch.is_tensor(out) or out.dtype != torch.uint8 or not out.is_cuda or out.shape != frames.shape:
+            raise TypeError(f"out must be a uint8 CUDA tensor of shape {tuple(frames.shape)}")
+        if _resize_source(out)[4 if N > 1 else 5:] != ((sb, sh, sw) if N > 1 else (sh, sw)):      # one frame has no frame stride
+            raise TypeError(f"out with strides {out.stride()} must share the strides of frames, {frames.stride()}")
+    dst = frames if out is None else out
+    _lib.check(_lib.load().msmd_draw_overlay(_p(frames), _p(dst), sb, sh, sw, N, H, W, C, _p(prims), d["P"], _p(prim_offsets), _p(font),
+                                             d.get("G", 0), int(samples), _stream()), "msmd_draw_overlay")
+    return dst
 
 
 # ----------------------------------------------------------------------------- style losses (csrc/style_loss.hip, DESIGN.md 5.19)

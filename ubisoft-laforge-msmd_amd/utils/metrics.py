@@ -24,7 +24,7 @@ error heat map side by side through `MeshRenderer.render_vertices(vertex_colors=
 
 Command line:  python -m msmd_amd.utils.metrics --pred_exp P.pkl --pred_rot P_rot.pkl --gt_exp G.pkl --gt_rot G_rot.pkl
                    --regions masks.pkl --out metrics.json [--flame_model_path ... --flame_lmk_embedding_path ...]
-                   [--comparison_video OUT.avi --error_map OUT.jpg --error_max METRES --colormap jet --render_size 256
+                   [--comparison_video OUT.avi --error_map OUT.jpg --error_max METRES --colormap jet --legend_labels --render_size 256
                     --render_samples 1 --fps 25 --audio A.wav --video_quality 90]
 The four pickles are the (T, 50) expression codes and (T, 3) head rotations `inference.py` writes and `utils/assemble.py` reads."""
 from __future__ import annotations
@@ -230,16 +230,51 @@ def paint_legend(frames, table):
     return frames
 
 
+def legend_label_layout(H, W, labels):
+    """Where `paint_legend_labels` prints labels = (bottom, top) on an (H, W) panel -> [(text, (x, y), scale)] with (x, y) the
+    bottom-left pixel of the line as `Overlay.text` takes it: right-aligned two pixels left of `paint_legend`'s bar, the top
+    label's ink from row 2 down, the bottom label's down to row H - 3; a font pixel is max(1, H // 128) pixels."""
+    from .overlay import FONT_ADVANCE, FONT_ROWS
+    try:
+        bottom, top = (str(s) for s in labels)
+    except (TypeError, ValueError):
+        raise ValueError(f"legend_labels must be (bottom, top) strings, got {labels!r}") from None
+    scale = max(1, H // 128)
+    right = W - max(4, W // 32) - 2                             # the first column the labels leave free
+    x = lambda s: right - (FONT_ADVANCE * len(s) - 1) * scale
+    return [(top, (x(top), 2 + FONT_ROWS * scale - 1), scale), (bottom, (x(bottom), H - 3), scale)]
+
+
+def legend_label_boxes(H, W, labels):
+    """The pixels the labels may touch -> [(x0, y0, x1, y1)], ends excluded, clipped to the panel."""
+    from .overlay import FONT_ADVANCE, FONT_ROWS
+    return [(max(x, 0), max(y - FONT_ROWS * scale + 1, 0), min(x + (FONT_ADVANCE * len(s) - 1) * scale, W), min(y + 1, H))
+            for s, (x, y), scale in legend_label_layout(H, W, labels)]
+
+
+def paint_legend_labels(frames, labels, colour=(0, 0, 0)):
+    """The ends of the scale in words, in place on frames (n, H, W, 3) uint8 on the device: labels = (bottom, top) in `colour` at
+    `legend_label_layout`'s places, the same on every frame, drawn by ops.draw_overlay."""
+    from .overlay import Overlay
+    n, H, W, _ = frames.shape
+    ov = Overlay(n)
+    for s, at, scale in legend_label_layout(H, W, labels):
+        ov.text([s] * n, np.tile(np.asarray(at, np.float64), (n, 1)), colour, scale=scale)
+    return ov.draw(frames)
+
+
 PANELS = ("gt", "pred", "error")
 
 
 @torch.no_grad()
-def render_comparison(pred, gt, faces, renderer, vmax, table="jet", panels=PANELS, legend=True, t_center=None, rot=None):
+def render_comparison(pred, gt, faces, renderer, vmax, table="jet", panels=PANELS, legend=True, t_center=None, rot=None,
+                      legend_labels=None):
     """pred, gt (n, V, 3) on the device, both fp32 or both fp16 -> (n, H, len(panels) * W, 3) uint8 on the device, the panels side by
     side: "gt" and "pred" the plain render of each track, "error" the prediction's geometry drawn UNLIT in the colours
     ops.vertex_error_colors gives its vertices (distance / vmax through `table`: a name of COLORMAPS or a (256, 3 | 4) uint8
-    array), with the colour bar of `paint_legend` at its right edge if `legend`.  t_center, rot as `renderer.render_vertices`
-    takes them."""
+    array), with the colour bar of `paint_legend` at its right edge if `legend`, and with legend_labels = (bottom, top) strings
+    printed left of the bar's two ends, black on the renderer's white background and white on its black one (`paint_legend_labels`; None: no text, the bytes of the bar alone).  t_center, rot as
+    `renderer.render_vertices` takes them."""
     panels = tuple(panels)
     if not panels or any(p not in PANELS for p in panels):
         raise ValueError(f"panels must be taken from {PANELS}, got {panels!r}")
@@ -251,6 +286,9 @@ def render_comparison(pred, gt, faces, renderer, vmax, table="jet", panels=PANEL
             frames = renderer.render_vertices(pred, faces, t_center=t_center, rot=rot, vertex_colors=colours, lit=False)[0]
             if legend:
                 frames = paint_legend(frames.contiguous(), lut)
+                if legend_labels is not None:
+                    dark = sum(getattr(renderer, "bg_color", (255, 255, 255))) < 384       # white ink on a dark background
+                    frames = paint_legend_labels(frames, legend_labels, (255, 255, 255) if dark else (0, 0, 0))
         else:
             frames = renderer.render_vertices(gt if p == "gt" else pred, faces, t_center=t_center, rot=rot)[0]
         out.append(frames)
@@ -372,6 +410,8 @@ def build_parser():
                     help="the error drawn in the top colour (default: the clip's max_ve for the video, which costs a second pass "
                          "over the chunks, and the map's own maximum for the still)")
     ap.add_argument("--colormap", type=str, default="jet", choices=sorted(COLORMAPS))
+    ap.add_argument("--legend_labels", action="store_true", help="print the ends of the scale, 0 and the maximum in mm, beside the "
+                                                                 "colour bar of --comparison_video")
     ap.add_argument("--render_size", type=int, default=None, help="side of a panel in pixels (default 256)")
     ap.add_argument("--render_samples", type=int, default=1, choices=ops.RENDER_SAMPLES, help="samples per pixel")
     ap.add_argument("--fps", type=float, default=None, help="frame rate of the video (default 25)")
@@ -399,6 +439,8 @@ def parse_args(argv=None):
         for flag in ("fps", "audio"):
             if getattr(args, flag) is not None:
                 ap.error(f"--{flag} is read only with --comparison_video")
+        if args.legend_labels:
+            ap.error("--legend_labels is read only with --comparison_video")
     if args.error_max is not None and not 0.0 < args.error_max < float("inf"):
         ap.error(f"--error_max {args.error_max} must be finite and greater than 0")
     if args.render_size is not None and not 1 <= args.render_size <= 16384:
@@ -444,7 +486,8 @@ class _Drawing:
 
     def video_chunk(self, pv, gv):
         from . import media
-        frames = render_comparison(pv, gv, self.faces, self.renderer, self.video_max, self.args.colormap)
+        labels = ("0", f"{self.video_max * 1000:.1f} mm") if self.args.legend_labels else None
+        frames = render_comparison(pv, gv, self.faces, self.renderer, self.video_max, self.args.colormap, legend_labels=labels)
         self.jpegs += media.encode_jpeg(frames, self.args.video_quality)
 
     def on_chunk(self, pv, gv, i, j):
