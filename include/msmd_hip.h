@@ -1463,6 +1463,67 @@ int msmd_draw_overlay(const void* src, void* dst, long frame_stride, long row_st
                       const int* prims, long n_prims, const int* prim_offsets, const unsigned char* font, int n_glyphs,
                       int samples, msmd_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Retargeting: FLAME motion onto a blendshape rig, a bounded least-squares fit per frame.
+ *
+ * The rig: neutral (V, 3) fp32; deltas (K, V, 3) fp32, 1 <= K <= MSMD_RETARGET_MAX_SHAPES; vertex_weight (V) fp32 >= 0 (absent: 1);
+ * lo < hi (K) float64 (absent: 0 and 1); ridge (K) float64 >= 0 (absent: 0).  Every sum below reads these stored arrays.
+ *   A[k, v, c] = fl32(vertex_weight[v] * deltas[k, v, c])      (utils/retarget.prepare_rig forms it, once per rig)
+ *   G = A A^T over the 3 V coordinates, float64;  H = G + diag(ridge), which must be positive definite (prepare_rig checks it).
+ * Per frame n with vertices x (V, 3) fp32:
+ *   b[n, k] = sum_{v, c} A[k, v, c] * fl32(x[n, v, c] - neutral[v, c]): the difference is rounded to fp32 first; products and
+ *     sums are fp32.  A vertex with vertex_weight == 0 is not part of the sum and is never read: a NaN there does not reach b.
+ *   w[n] = argmin 1/2 w^T H w - b[n]^T w  subject to lo <= w <= hi, solved in float64 and rounded once to fp32.
+ *
+ * msmd_retarget_gram: G and H (K, K) float64 from A (K, V, 3).  ridge is a HOST array of K doubles or NULL.  One workgroup of 256
+ *   per pair (k, l <= k): thread t adds the exact products of coordinates t, t + 256, ... in ascending order, then the 256 sums
+ *   fold in halves (t += t + 128, 64, ... 1).  The order depends on V alone.
+ * msmd_retarget_rhs: b (N, K) fp32.  A workgroup owns MSMD_RETARGET_FRAME_TILE frames and one contraction split of
+ *   MSMD_RETARGET_SPLIT_VERTICES vertices, which it walks MSMD_RETARGET_VERTEX_TILE vertices at a time on v_mfma_f32_16x16x4_f32; its
+ *   sums go to partial (msmd_retarget_splits(V), N, K) fp32, the caller's workspace, and a second launch adds a frame's splits in
+ *   ascending order.  The split is a constant, so a frame's bits depend on V, K and the frame alone: not on N, not on the
+ *   frame's place in the batch, not on the run.  vertex_weight (V) or NULL (every vertex is read).
+ * msmd_retarget_solve: block principal pivoting for a box, float64, one wave per frame, MSMD_RETARGET_SOLVE_FRAMES frames per
+ *   workgroup, frames independent.  lo, hi are HOST arrays of K doubles or NULL (0 and 1).  Every weight is at lo (L), free (F) or
+ *   at hi (U); all start in L.  One iteration:
+ *     1. the L and U weights take their bounds;  2. H_FF w_F = b_F - H_F,L lo_L - H_F,U hi_U by Cholesky (the rows and columns
+ *     of the bound weights pinned to the identity);  3. g = H w - b;  4. a weight is infeasible if it is F with w < lo (-> L), F
+ *     with w > hi (-> U), L with g < 0 (-> F) or U with g > 0 (-> F);  5. none infeasible: done;  6. otherwise, if the
+ *     infeasible count is below every count seen so far, the budget p is reset to 3 and all infeasible weights are exchanged;
+ *     else if p > 0, p -= 1 and all are exchanged; else only the infeasible weight of the largest index is exchanged.
+ *   Outputs: w (N, K) fp32; iterations (N) int32; status (N) int32: MSMD_RETARGET_CONVERGED; MSMD_RETARGET_CAP_REACHED (the
+ *   output is the iterate of iteration max_iterations clipped to the box); MSMD_RETARGET_BAD_INPUT (b not finite: the frame's
+ *   weights are NaN, 0 iterations); MSMD_RETARGET_NOT_POSITIVE (a pivot was not positive, which a positive definite H never
+ *   gives: weights NaN).
+ * msmd_blendshape_apply: out[n, v, c] = neutral[v, c] + sum_k w[n, k] * deltas[k, v, c], (N, V, 3) fp32: an fmaf chain that starts at
+ *   neutral and takes k in ascending order.  A thread owns one coordinate of MSMD_RETARGET_APPLY_FRAMES frames.
+ * All four return 1 (hipErrorInvalidValue) before any launch for N < 0, K outside [1, MSMD_RETARGET_MAX_SHAPES], V outside
+ * [1, MSMD_RETARGET_MAX_VERTICES], a ridge that is negative or NaN, lo >= hi or a bound that is not finite, max_iterations outside
+ * [1, MSMD_RETARGET_MAX_ITERATIONS], N above 65535 * MSMD_RETARGET_APPLY_FRAMES for the apply, or, with work to do, a NULL pointer
+ * other than the optional ones; N = 0 passes those checks, returns 0 and launches nothing; otherwise 0 or the launch's
+ * hipError_t.  msmd_retarget_splits is a host function: ceil(V / MSMD_RETARGET_SPLIT_VERTICES), 0 for V < 1. */
+#define MSMD_RETARGET_MAX_SHAPES 64
+#define MSMD_RETARGET_MAX_VERTICES (1 << 24)
+#define MSMD_RETARGET_FRAME_TILE 128
+#define MSMD_RETARGET_VERTEX_TILE 32
+#define MSMD_RETARGET_SPLIT_VERTICES 1024
+#define MSMD_RETARGET_SOLVE_FRAMES 4
+#define MSMD_RETARGET_APPLY_FRAMES 32
+#define MSMD_RETARGET_ITERATIONS 256 /* the default cap */
+#define MSMD_RETARGET_MAX_ITERATIONS 65536
+#define MSMD_RETARGET_CONVERGED 0
+#define MSMD_RETARGET_CAP_REACHED 1
+#define MSMD_RETARGET_BAD_INPUT 2
+#define MSMD_RETARGET_NOT_POSITIVE 3
+int msmd_retarget_splits(int V);
+int msmd_retarget_gram(const float* A, const double* ridge, double* G, double* H, int K, int V, msmd_stream_t stream);
+int msmd_retarget_rhs(const float* x, const float* neutral, const float* A, const float* vertex_weight, float* partial, float* b,
+                      int N, int V, int K, msmd_stream_t stream);
+int msmd_retarget_solve(const double* H, const float* b, const double* lo, const double* hi, float* w, int* status,
+                        int* iterations, int N, int K, int max_iterations, msmd_stream_t stream);
+int msmd_blendshape_apply(const float* w, const float* neutral, const float* deltas, float* out, int N, int V, int K,
+                          msmd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

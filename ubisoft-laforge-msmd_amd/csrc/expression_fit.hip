@@ -9,11 +9,12 @@
 //   r  lane = (landmark, coordinate): l = X + (R - I) Y, the residual, sqrt(w) r into LDS, w r^2 summed
 //   B  lane = parameter: its column of sqrt(w) Jm for the slice's 3 EF_KS rows into LDS, and g += column . sqrt(w) r
 //   C  lane (ti, tj) of an 8 x 8 grid holds H[8 a + ti][8 b + tj], a, b < 8, in registers: rank-(3 EF_KS) update from LDS
-// The Cholesky factorisation stays in that cyclic register layout (right-looking: one column through LDS per step, 64 FMAs
-// per lane per step); the factor goes to LDS packed by columns, over the dead Jm slice, for the two triangular solves with
-// one row per lane.  A wave's LDS traffic is ordered by the hardware, so inside a wave a fence suffices; the workgroup
-// barriers are those of the staging alone, and every wave passes the same number of them whatever its frame does.
+// The Cholesky factorisation stays in that cyclic register layout and the factor goes to LDS packed by columns, over the dead
+// Jm slice, for the two triangular solves with one row per lane (wave_chol.h, shared with retarget.hip).  A wave's LDS traffic
+// is ordered by the hardware, so inside a wave a fence suffices; the workgroup barriers are those of the staging alone, and
+// every wave passes the same number of them whatever its frame does.
 #include "common.h"
+#include "wave_chol.h"
 
 constexpr int EF_WG = 256;
 constexpr int EF_FRAMES = EF_WG / MSMD_WAVE;       // frames per workgroup
@@ -45,16 +46,10 @@ constexpr int EF_OFF_VAL = EF_OFF_ROT + 36;        // table rows' values (EF_TRO
 constexpr int EF_OFF_DVAL = EF_OFF_VAL + EF_TROWS; // their products with d vec(R) / d theta_a (3 x EF_TROWS)
 constexpr int EF_OFF_RS = EF_OFF_DVAL + 3 * EF_TROWS;
 constexpr int EF_OFF_COL = EF_OFF_RS + EF_ROWS;    // Cholesky: the step's column (64) and pivot (1)
-constexpr int EF_OFF_BIG = EF_OFF_COL + 72;        // the Jm slice (EF_ROWS x 64), later the packed factor
+constexpr int EF_OFF_BIG = EF_OFF_COL + WCHOL_COL;       // the Jm slice (EF_ROWS x 64), later the packed factor
 __host__ __device__ constexpr int ef_big(int NP) { return NP * (NP + 1) / 2 > EF_ROWS * 64 ? NP * (NP + 1) / 2 : EF_ROWS * 64; }
 __host__ __device__ constexpr int ef_ncs(int NC) { return NC | 1; }            // odd row pitch: one row per lane meets no bank twice
 __host__ __device__ constexpr int ef_shared(int NC) { return EF_TROWS * ef_ncs(NC) + MSMD_EXPFIT_MAX_LANDMARKS + 8; }
-
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // R - I and d R / d theta_a of utils/lbs.py's Rodrigues formula: angle = |theta + 1e-8|, direction = theta / angle.
 __device__ __forceinline__ void rodrigues_jet(const double* th, double* out) {
@@ -226,65 +221,6 @@ __device__ __forceinline__ double ef_pass(const ExpFitArgs& p, const ExpFitWave&
   return wave_sum_f64(fsum);
 }
 
-// acc (cyclic) = L L^T for its leading NP x NP part; L packed by columns into `sL`, its diagonal inverted.  -> false at the first pivot that is not
-// positive (a NaN included); the factor is then not to be used.
-__device__ __forceinline__ bool ef_cholesky(const ExpFitWave& W, double (&acc)[8][8]) {
-  const int lane = W.lane, NP = W.NP, ti = lane >> 3, tj = lane & 7;
-  double* __restrict__ col = W.wv + EF_OFF_COL;
-  double* __restrict__ sL = W.wv + EF_OFF_BIG;
-  bool ok = true;
-#pragma unroll
-  for (int jb = 0; jb < 8; ++jb) {
-    for (int jj = 0; jj < 8; ++jj) {
-      const int j = jb * 8 + jj;
-      if (j >= NP || !ok) break;
-      if (ti == jj && tj == jj) col[64] = acc[jb][jb];
-      wave_sync();
-      const double d = col[64];
-      if (!(d > 0.0)) { ok = false; break; }
-      const double inv = 1.0 / sqrt(d);
-      if (tj == jj) {
-        const int off = j * NP - (j * (j - 1)) / 2 - j;
-#pragma unroll
-        for (int a = 0; a < 8; ++a) {
-          const int i = a * 8 + ti;
-          const double v = i >= j ? acc[a][jb] * inv : 0.0;
-          col[i] = v;
-          if (i >= j && i < NP) sL[off + i] = i == j ? inv : v;      // the diagonal holds 1 / L_jj
-        }
-      }
-      wave_sync();
-      double la[8], lb[8];
-#pragma unroll
-      for (int a = 0; a < 8; ++a) { la[a] = col[a * 8 + ti]; lb[a] = col[a * 8 + tj]; }
-#pragma unroll
-      for (int a = 0; a < 8; ++a)
-#pragma unroll
-        for (int b = 0; b < 8; ++b) acc[a][b] = fma(-la[a], lb[b], acc[a][b]);
-    }
-  }
-  wave_sync();
-  return ok;
-}
-
-// L L^T x = b with one row per lane: -> x (lanes from NP on keep b).
-__device__ __forceinline__ double ef_solve(const ExpFitWave& W, double b) {
-  const int lane = W.lane, NP = W.NP;
-  const double* __restrict__ sL = W.wv + EF_OFF_BIG;
-  for (int j = 0; j < NP; ++j) {
-    const int off = j * NP - (j * (j - 1)) / 2;
-    const double z = __shfl(b, j, 64) * sL[off];
-    if (lane == j) b = z;
-    if (lane > j && lane < NP) b = fma(-sL[off + lane - j], z, b);
-  }
-  for (int j = NP - 1; j >= 0; --j) {
-    const double z = __shfl(b, j, 64) * sL[j * NP - (j * (j - 1)) / 2];
-    if (lane == j) b = z;
-    if (lane < j) b = fma(-sL[lane * NP - (lane * (lane - 1)) / 2 + j - lane], z, b);
-  }
-  return b;
-}
-
 __global__ __launch_bounds__(EF_WG) void expression_fit_kernel(const ExpFitArgs p) {
   extern __shared__ __attribute__((aligned(16))) double ef_smem[];
   const int tid = threadIdx.x;
@@ -339,9 +275,9 @@ __global__ __launch_bounds__(EF_WG) void expression_fit_kernel(const ExpFitArgs 
         acc[a][a] = (acc[a][a] + di) * (1.0 + mu);
       }
     }
-    const bool ok = ef_cholesky(W, acc);
+    const bool ok = wave_cholesky(lane, NP, W.wv + EF_OFF_COL, W.wv + EF_OFF_BIG, acc);
     double delta = 0.0;
-    if (ok) delta = ef_solve(W, -g);
+    if (ok) delta = wave_chol_solve(lane, NP, W.wv + EF_OFF_BIG, -g);
     else st |= 2;
     const double pt = lane < NP && ok ? pv + delta : pv;
     ef_set_point(p, W, pt);

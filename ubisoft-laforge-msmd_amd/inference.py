@@ -335,6 +335,13 @@ def build_parser():
     # metric (not in the reference script; the loss is its utils/common.StyleAdherenceLoss)
     ap.add_argument("--style_adherence", action="store_true", help="write style_adherence_<clip>_seed_<s>.npy: every generated "
                                                                    "frame's soft-min distance to the whole style clip")
+    # retargeting (not in the reference: DESIGN.md 5.33)
+    ap.add_argument("--retarget", type=str, default=None, metavar="RIG.npz",
+                    help="blendshape rig on FLAME's topology (utils/retarget.load_rig): write retarget_<clip>_seed_<s>.csv, one "
+                         "weight curve per slider (needs --flame_model_path)")
+    ap.add_argument("--comparison_video", action="store_true",
+                    help="with --retarget: also write retarget_<clip>_seed_<s>.avi, FLAME | the rig's reconstruction | its error "
+                         "heat map (needs --render_size > 0)")
     return ap
 
 
@@ -359,7 +366,43 @@ def parse_args(argv=None):
         ap.error(f"--video_quality {args.video_quality} is outside [1, 100]")
     if args.source_video is not None and not args.video:
         ap.error("--source_video needs --video: it is a panel of the video")
+    if args.retarget is not None and args.flame_model_path is None:
+        ap.error("--retarget needs --flame_model_path: the rig is fitted to FLAME's vertices")
+    if args.comparison_video and (args.retarget is None or args.render_size <= 0):
+        ap.error("--comparison_video needs --retarget and --render_size > 0: it draws the rig's reconstruction")
     return args
+
+
+@torch.no_grad()
+def write_retarget(coef, shape_coef, flame, rig, fps, csv_path, video_path=None, renderer=None, quality=90, chunk=256,
+                   with_global_pose=False):
+    """Motion coefficients (T, 53 | 54) in the data's units -> FLAME vertices -> blendshape weights (utils/retarget.py), written to
+    `csv_path` (or .json) as one curve per slider.  The head is held still unless with_global_pose: a rig's neutral does not
+    turn.  video_path: also a Motion-JPEG AVI of FLAME (as ground truth) | the rig's reconstruction | its error heat map through
+    utils/metrics.render_comparison, the colour scale topped at the clip's largest error (a second pass over the chunks).
+    -> {'frames', 'mean', 'max', 'rms' (vertex error of the reconstruction), 'flagged' (frames whose status is not 0)}."""
+    from .utils import retarget as RT
+    from .utils.metrics import VertexMetrics, _scale_or_one, _track
+    coef = _track(coef)
+    T = coef.shape[0]
+    if T < 1:
+        raise ValueError("no frames to retarget")
+    rig = RT.prepare_rig(rig, coef.device)
+    shape = shape_coef.reshape(-1, shape_coef.shape[-1]).float().expand(T, -1)
+    cd = get_coef_dict(coef, shape, None, with_global_pose=with_global_pose)
+    vm = VertexMetrics([0, T], rig.V, [0], [0], rig.neutral, coef.device)
+    weights, status = RT.retarget_coeffs(cd, flame, rig, chunk, on_chunk=lambda v, w, i: vm.update(RT.rig_vertices(w, rig), v))
+    RT.write_curves(csv_path, weights, rig.names, fps)
+    r = vm.result()["all"]
+    rep = dict(frames=T, mean=r["mve"], max=r["max_ve"], rms=r["rmse"], flagged=int((status != 0).sum()))
+    if video_path is not None:
+        from .utils import media
+        vmax, jpegs = _scale_or_one(r["max_ve"]), []
+        for v, i in RT._flame_chunks(cd, flame, chunk):
+            jpegs += media.encode_jpeg(RT.comparison_frames(v, weights[i:i + v.shape[0]], rig, flame.faces_tensor, renderer, vmax).contiguous(),
+                                       quality)
+        media.write_avi(video_path, jpegs, fps, (3 * renderer.width, renderer.height))
+    return rep
 
 
 def load_source_panel(path, height, device="cuda"):
@@ -475,7 +518,7 @@ def main(argv=None):
     tex_img, tex_uv = load_texture(args.texture) if args.texture is not None else (None, None)
     if args.flame_tex is not None:
         tex_img, tex_uv = load_flame_texture(args.flame_tex, args.tex_type, args.tex_code, device)
-    if args.render_size > 0:
+    if args.render_size > 0 or args.retarget is not None:
         from .utils.flame import FLAME, FLAMEConfig
         from .utils.renderer import MeshRenderer
         from types import SimpleNamespace
@@ -485,7 +528,11 @@ def main(argv=None):
         if args.flame_lmk_embedding_path is not None:
             cfg.flame_lmk_embedding_path = args.flame_lmk_embedding_path
         flame = FLAME(cfg).to(device)
-        renderer = MeshRenderer((args.render_size, args.render_size), samples=args.render_samples)
+        renderer = MeshRenderer((args.render_size, args.render_size), samples=args.render_samples) if args.render_size > 0 else None
+    rig = None
+    if args.retarget is not None:
+        from .utils.retarget import load_rig, prepare_rig
+        rig = prepare_rig(load_rig(args.retarget), device)
     for seed in range(args.versions_of_render):
         np.random.seed(seed)
         torch.manual_seed(seed)
@@ -505,6 +552,13 @@ def main(argv=None):
             np.save(out, per_frame.cpu().numpy())
             written.append(out)
             print(f"style adherence (seed {seed}): mean {float(per_frame.mean()):.6f} over {per_frame.numel()} frames")
+        if rig is not None:
+            out = os.path.join(temp, f"retarget_{clip}_seed_{seed}.csv")
+            video = os.path.join(temp, f"retarget_{clip}_seed_{seed}.avi") if args.comparison_video else None
+            rep = write_retarget(torch.cat([exp_code, head_rot], dim=-1), shape_coef.reshape(1, -1), flame, rig, model_args.fps, out,
+                                 video, renderer, args.video_quality)
+            written += [out] + ([video] if video else [])
+            print(f"retarget (seed {seed}): {rep}")
         if renderer is not None and args.video:
             from .utils import media
             jpegs, first, width = [], 0, args.render_size

@@ -2614,3 +2614,114 @@ def vertex_error_sums_(state, pred, gt, frame0, clip_offsets_dev):
     _lib.check(_lib.load().msmd_vertex_error_sums(_p(pred), _p(gt), frame0, d["n"], _p(clip_offsets_dev), d["C"], _p(state), d["V"], dt,
                                                   _stream()), "msmd_vertex_error_sums")
     return state
+
+
+# ----------------------------------------------------------------------------- retargeting (csrc/retarget.hip)
+RETARGET_MAX_SHAPES, RETARGET_MAX_VERTICES, RETARGET_ITERATIONS, RETARGET_MAX_ITERATIONS = _h(
+    "RETARGET_MAX_SHAPES", "RETARGET_MAX_VERTICES", "RETARGET_ITERATIONS", "RETARGET_MAX_ITERATIONS")
+RETARGET_FRAME_TILE, RETARGET_VERTEX_TILE, RETARGET_SPLIT_VERTICES, RETARGET_SOLVE_FRAMES, RETARGET_APPLY_FRAMES = _h(
+    "RETARGET_FRAME_TILE", "RETARGET_VERTEX_TILE", "RETARGET_SPLIT_VERTICES", "RETARGET_SOLVE_FRAMES", "RETARGET_APPLY_FRAMES")
+RETARGET_CONVERGED, RETARGET_CAP_REACHED, RETARGET_BAD_INPUT, RETARGET_NOT_POSITIVE = _h(
+    "RETARGET_CONVERGED", "RETARGET_CAP_REACHED", "RETARGET_BAD_INPUT", "RETARGET_NOT_POSITIVE")
+
+
+def _retarget_sizes(K, V):
+    if not 1 <= K <= RETARGET_MAX_SHAPES:
+        raise ValueError(f"{K} blendshapes; the kernels take 1 .. {RETARGET_MAX_SHAPES}")
+    if not 1 <= V <= RETARGET_MAX_VERTICES:
+        raise ValueError(f"{V} vertices; the kernels take 1 .. {RETARGET_MAX_VERTICES}")
+
+
+def _host_f64(name, v, K):
+    """An optional per-shape host array -> contiguous float64 numpy (K) or None."""
+    if v is None:
+        return None
+    if torch.is_tensor(v):
+        v = v.detach().cpu().numpy()
+    a = np.ascontiguousarray(np.asarray(v, dtype=np.float64))
+    if a.shape != (K,):
+        raise ValueError(f"{name} must hold {K} values, got shape {a.shape}")
+    return a
+
+
+def retarget_gram(A, ridge=None):
+    """-> (G, H) (K, K) float64: msmd_retarget_gram, G = A A^T over the 3 V coordinates of A (K, V, 3) fp32 in float64 and a fixed
+    order, H = G + diag(ridge).  ridge: K values >= 0 on the HOST, or None."""
+    _need_cuda(A)
+    d = {}
+    _arg("A", A, torch.float32, "K+ V+ 3", d)
+    K, V = d["K"], d["V"]
+    _retarget_sizes(K, V)
+    ridge = _host_f64("ridge", ridge, K)
+    if ridge is not None and not (ridge >= 0.0).all():
+        raise ValueError("ridge must be >= 0")
+    G = torch.empty(K, K, device=A.device, dtype=torch.float64)
+    H = torch.empty(K, K, device=A.device, dtype=torch.float64)
+    _lib.check(_lib.load().msmd_retarget_gram(_p(A), None if ridge is None else ridge.ctypes.data, _p(G), _p(H), K, V, _stream()),
+               "msmd_retarget_gram")
+    return G, H
+
+
+def retarget_rhs(x, neutral, A, vertex_weight=None):
+    """-> b (N, K) fp32: msmd_retarget_rhs, b[n, k] = sum A[k, v, c] * fl32(x[n, v, c] - neutral[v, c]) in fp32 on the exact-fp32
+    MFMA.  x (N, V, 3), neutral (V, 3), A (K, V, 3) fp32; vertex_weight (V) fp32 or None: a vertex whose weight is 0 is never read.
+    A frame's bits do not depend on N or on where the frame sits.  N = 0 gives an empty table."""
+    _need_cuda(x, neutral, A, vertex_weight)
+    d = {}
+    _arg("A", A, torch.float32, "K+ V+ 3", d)
+    _arg("x", x, torch.float32, "N V 3", d)
+    _arg("neutral", neutral, torch.float32, "V 3", d)
+    _arg("vertex_weight", vertex_weight, torch.float32, "V", d, optional=True)
+    N, K, V = d["N"], d["K"], d["V"]
+    _retarget_sizes(K, V)
+    lib = _lib.load()
+    b = torch.empty(N, K, device=x.device, dtype=torch.float32)
+    partial = torch.empty(lib.msmd_retarget_splits(V), N, K, device=x.device, dtype=torch.float32)
+    _lib.check(lib.msmd_retarget_rhs(_p(x), _p(neutral), _p(A), _p(vertex_weight), _p(partial), _p(b), N, V, K, _stream()),
+               "msmd_retarget_rhs")
+    return b
+
+
+def retarget_solve(H, b, lo=None, hi=None, max_iterations=RETARGET_ITERATIONS):
+    """-> (w (N, K) fp32, status (N) int32, iterations (N) int32): msmd_retarget_solve, per frame the minimiser of
+    1/2 w^T H w - b^T w in the box lo <= w <= hi by block principal pivoting in float64 (the include file states the rule).
+    H (K, K) float64 positive definite, b (N, K) fp32 on the device; lo, hi K values on the HOST (None: 0 and 1).
+    status: RETARGET_CONVERGED / _CAP_REACHED / _BAD_INPUT / _NOT_POSITIVE."""
+    _need_cuda(H, b)
+    d = {}
+    _arg("H", H, torch.float64, "K+ K", d)
+    _arg("b", b, torch.float32, "N K", d)
+    N, K = d["N"], d["K"]
+    _retarget_sizes(K, 1)
+    lo, hi = _host_f64("lo", lo, K), _host_f64("hi", hi, K)
+    lo_v, hi_v = np.zeros(K) if lo is None else lo, np.ones(K) if hi is None else hi
+    if not (np.isfinite(lo_v).all() and np.isfinite(hi_v).all() and (lo_v < hi_v).all()):
+        raise ValueError("the bounds must be finite with lo < hi")
+    max_iterations = int(max_iterations)
+    if not 1 <= max_iterations <= RETARGET_MAX_ITERATIONS:
+        raise ValueError(f"max_iterations must be in [1, {RETARGET_MAX_ITERATIONS}], got {max_iterations}")
+    w = torch.empty(N, K, device=b.device, dtype=torch.float32)
+    status = torch.empty(N, device=b.device, dtype=torch.int32)
+    its = torch.empty(N, device=b.device, dtype=torch.int32)
+    _lib.check(_lib.load().msmd_retarget_solve(_p(H), _p(b), None if lo is None else lo.ctypes.data,
+                                               None if hi is None else hi.ctypes.data, _p(w), _p(status), _p(its), N, K,
+                                               max_iterations, _stream()), "msmd_retarget_solve")
+    return w, status, its
+
+
+def blendshape_apply(w, neutral, deltas):
+    """-> (N, V, 3) fp32: msmd_blendshape_apply, neutral + sum_k w[n, k] * deltas[k], an fp32 fmaf chain in ascending k.
+    w (N, K), neutral (V, 3), deltas (K, V, 3) fp32."""
+    _need_cuda(w, neutral, deltas)
+    d = {}
+    _arg("deltas", deltas, torch.float32, "K+ V+ 3", d)
+    _arg("w", w, torch.float32, "N K", d)
+    _arg("neutral", neutral, torch.float32, "V 3", d)
+    N, K, V = d["N"], d["K"], d["V"]
+    _retarget_sizes(K, V)
+    if N > 65535 * RETARGET_APPLY_FRAMES:
+        raise ValueError(f"{N} frames are more than one call takes ({65535 * RETARGET_APPLY_FRAMES}); cut the sequence")
+    out = torch.empty(N, V, 3, device=w.device, dtype=torch.float32)
+    _lib.check(_lib.load().msmd_blendshape_apply(_p(w), _p(neutral), _p(deltas), _p(out), N, V, K, _stream()),
+               "msmd_blendshape_apply")
+    return out
