@@ -10,13 +10,14 @@ frames/s.  Needs an MI355X; there is no CPU path.
 --texture N adds the textured shading pass with an N x N noise texture in longitude / latitude coordinates:
 per size, the untextured raster launch, the textured pass alone and the two together, timed in turn within every round (so
 the three share the clock state), per frame, and the textured pass with a 1 x 1 texture: the set-up, lighting and stores that
-stage (C) of the raster launch also does for every covered pixel, which is wasted work under a texture.  --parent_lib PATH names another build of the library (the parent commit's):
-its msmd_render_raster is timed in the same rounds, which is the only untextured time of the parent there is to compare with.
+stage (C) of the raster launch also does for every covered pixel, which is wasted work under a texture.  --parent_lib PATH names another build of the library (the parent commit's,
+the same C ABI): its msmd_render_raster and msmd_render_shade_textured are timed in the same rounds beside raw calls of this build's,
+and each pair is reported as this build's median over the parent's with the parent's own spread over the rounds.
 
     python tools/bench_render.py --texture 1024 [--parent_lib /path/to/parent/libmsmd_hip.so] [--out profiles/r11_texture.txt]
 
 --samples 4 times the four-sample raster launch instead: per size, the one-sample launch, the four-sample launch
-and, with --parent_lib, the parent build's one-sample launch, in turn within every round.
+and, with --parent_lib, the parent build's two launches, in turn within every round.
 
     python tools/bench_render.py --samples 4 [--parent_lib /path/to/parent/libmsmd_hip.so] [--out profiles/5_27_msaa.txt]
 """
@@ -64,6 +65,21 @@ def timed_in_turn(fns, reps=9, warmup=3):
     return [(float(np.median(m)), float(min(m)), float(max(m))) for m in ms]
 
 
+def parent_entry(path, name):
+    """Entry point `name` of another build of the library: the same C ABI, so this build's prototypes."""
+    from msmd_amd import _lib
+    _lib.load()
+    fn = getattr(ctypes.CDLL(path), name)
+    fn.argtypes, fn.restype = _lib.PROTOS[name], ctypes.c_int
+    return fn
+
+
+def against_parent(what, mine, parent):
+    """This build's median over the parent build's in the same rounds, beside the parent's own spread (max - min) / median."""
+    return (f"{what}: this build / the parent's {mine[0] / parent[0]:.4f} (the parent's spread over its rounds "
+            f"{(parent[2] - parent[1]) / parent[0]:.4f})")
+
+
 def bench_texture(args, dev, v, f, verts, rot, tc, lines):
     from msmd_amd import _lib
     B, V = verts.shape[:2]
@@ -74,11 +90,11 @@ def bench_texture(args, dev, v, f, verts, rot, tc, lines):
     pyramid1 = ops.texture_pyramid(img[:1, :1].contiguous())      # one texel: the pass without its texture traffic
     vt = np.stack([np.arctan2(v[:, 0], v[:, 2]) / (2 * np.pi) + 0.5, np.arcsin(np.clip(v[:, 1] / 0.09, -1, 1)) / np.pi + 0.5], axis=1)
     vt_d, ft_d = torch.from_numpy(vt.astype(np.float32)).to(dev), torch.from_numpy(f).to(dev)
-    parent = None
+    lib = _lib.load()
+    parent = parent_tex = None
     if args.parent_lib:
-        _lib.load()
-        parent = ctypes.CDLL(args.parent_lib).msmd_render_raster
-        parent.argtypes, parent.restype = _lib.PROTOS["msmd_render_raster"], ctypes.c_int
+        parent = parent_entry(args.parent_lib, "msmd_render_raster")
+        parent_tex = parent_entry(args.parent_lib, "msmd_render_shade_textured")
     for size in (512, 256):
         r = MeshRenderer((size, size))
         faces, off, ids = r._tables(torch.from_numpy(f).to(dev), V, dev)
@@ -92,11 +108,14 @@ def bench_texture(args, dev, v, f, verts, rot, tc, lines):
         shade_1 = lambda: ops.render_shade_textured(screen, normals, faces, vt_d, ft_d, pyramid1, 1, 1, shade, lights, fid, rgba, near)
         fns, names = [raster, shade_t, both], ["msmd_render_raster (untextured, with face ids)", "msmd_render_shade_textured",
                                                "raster + textured pass"]
+        stream = torch.cuda.current_stream().cuda_stream
+        raster_args = (screen.data_ptr(), normals.data_ptr(), faces.data_ptr(), shade.data_ptr(), lights.data_ptr(), lights.shape[0],
+                       rgba.data_ptr(), depth.data_ptr(), fid.data_ptr(), B, V, faces.shape[0], size, size, near, far, 0xffffffff, stream)
+        tex_args = (screen.data_ptr(), normals.data_ptr(), faces.data_ptr(), vt_d.data_ptr(), ft_d.data_ptr(), pyramid.data_ptr(), N, N,
+                    shade.data_ptr(), lights.data_ptr(), lights.shape[0], fid.data_ptr(), rgba.data_ptr(), None, B, V, faces.shape[0],
+                    vt_d.shape[0], size, size, near, stream)
         if parent is not None:
-            stream = torch.cuda.current_stream().cuda_stream
-            fns.append(lambda: parent(screen.data_ptr(), normals.data_ptr(), faces.data_ptr(), shade.data_ptr(), lights.data_ptr(),
-                                      lights.shape[0], rgba.data_ptr(), depth.data_ptr(), fid.data_ptr(), B, V, faces.shape[0], size, size,
-                                      near, far, 0xffffffff, stream))
+            fns.append(lambda: parent(*raster_args))
             names.append("parent build's msmd_render_raster")
         uvl = ops.render_shade_textured(screen, normals, faces, vt_d, ft_d, pyramid, N, N, shade, lights, fid, rgba, near, want_uvl=True)
         cov = fid >= 0
@@ -104,6 +123,11 @@ def bench_texture(args, dev, v, f, verts, rot, tc, lines):
         fns.append(shade_1)
         names.append("msmd_render_shade_textured with a 1 x 1 texture (set-up, lighting and stores: what stage (C) of the raster "
                      "launch repeats)")
+        if parent is not None:        # raw calls of both builds on the same buffers: the same host work between the two events
+            fns += [lambda: lib.msmd_render_raster(*raster_args), lambda: lib.msmd_render_shade_textured(*tex_args),
+                    lambda: parent_tex(*tex_args)]
+            names += ["msmd_render_raster, raw call", "msmd_render_shade_textured, raw call",
+                      "parent build's msmd_render_shade_textured, raw call"]
         res = timed_in_turn(fns)
         for name, (med, lo, hi) in zip(names, res):
             lines.append(f"{name} B={B} {size}x{size} texture {N}x{N}: median {med:.4f} ms (min {lo:.4f}, max {hi:.4f}, 9 rounds in "
@@ -113,6 +137,9 @@ def bench_texture(args, dev, v, f, verts, rot, tc, lines):
                         f"the parent's: {res[0][0] / res[3][0]:.3f})" if parent is not None else "")
                      + f"; {100 * float(cov.float().mean()):.1f} % of the pixels covered, mean level of detail {float(lam.mean()):.2f}; the "
                      f"untextured shading of those pixels inside the raster launch is wasted work under a texture")
+        if parent is not None:
+            lines.append(against_parent(f"msmd_render_raster {size}x{size}", res[-3], res[3]))
+            lines.append(against_parent(f"msmd_render_shade_textured {size}x{size}", res[-2], res[-1]))
 
 
 def bench_samples(args, dev, f, verts, rot, tc, lines):
@@ -121,10 +148,10 @@ def bench_samples(args, dev, f, verts, rot, tc, lines):
     from msmd_amd import _lib
     B, V = verts.shape[:2]
     lib = _lib.load()
-    parent = None
+    parent = parent_ms = None
     if args.parent_lib:
-        parent = ctypes.CDLL(args.parent_lib).msmd_render_raster
-        parent.argtypes, parent.restype = _lib.PROTOS["msmd_render_raster"], ctypes.c_int
+        parent = parent_entry(args.parent_lib, "msmd_render_raster")
+        parent_ms = parent_entry(args.parent_lib, "msmd_render_raster_ms")
     for size in (512, 256):
         r = MeshRenderer((size, size))
         faces, off, ids = r._tables(torch.from_numpy(f).to(dev), V, dev)
@@ -140,8 +167,8 @@ def bench_samples(args, dev, f, verts, rot, tc, lines):
         ms = lambda: lib.msmd_render_raster_ms(*head, None, None, *tail, args.samples, stream)
         fns, names = [one, ms], ["msmd_render_raster", f"msmd_render_raster_ms samples={args.samples}"]
         if parent is not None:
-            fns.append(lambda: parent(*head, None, *tail, stream))
-            names.append("parent build's msmd_render_raster")
+            fns += [lambda: parent(*head, None, *tail, stream), lambda: parent_ms(*head, None, None, *tail, args.samples, stream)]
+            names += ["parent build's msmd_render_raster", f"parent build's msmd_render_raster_ms samples={args.samples}"]
         n = (ops.render_raster(screen, normals, faces, shade, lights, size, size, near, far, 0xffffffff, want_face_id=True,
                                samples=args.samples)[2] >= 0).sum(-1)
         res = timed_in_turn(fns)
@@ -152,6 +179,9 @@ def bench_samples(args, dev, f, verts, rot, tc, lines):
                      + (f"; this build's one-sample raster / the parent's: {res[0][0] / res[2][0]:.3f}" if parent is not None else "")
                      + f"; {100 * float((n > 0).float().mean()):.1f} % of the pixels have a covered sample, "
                      f"{100 * float(((n > 0) & (n < args.samples)).float().mean()):.2f} % are partly covered")
+        if parent is not None:
+            lines.append(against_parent(f"msmd_render_raster {size}x{size}", res[0], res[2]))
+            lines.append(against_parent(f"msmd_render_raster_ms samples={args.samples} {size}x{size}", res[1], res[3]))
 
 
 def main(argv=None):
@@ -161,7 +191,7 @@ def main(argv=None):
     ap.add_argument("--texture", type=int, default=0, help="side of a noise texture: time the textured pass too (0: do not)")
     ap.add_argument("--samples", type=int, default=1, choices=ops.RENDER_SAMPLES,
                     help="4: time the four-sample raster launch beside the one-sample launch instead")
-    ap.add_argument("--parent_lib", type=str, default=None, help="another build of the library whose raster launch is timed in turn")
+    ap.add_argument("--parent_lib", type=str, default=None, help="another build of the library whose launches are timed in turn")
     args = ap.parse_args(argv)
     assert torch.cuda.is_available(), "bench_render needs an MI355X"
     dev = torch.device("cuda:0")

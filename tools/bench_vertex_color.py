@@ -10,8 +10,12 @@ The launches of a group are timed in turn within every round (so they share the 
 of one kernel, 9 rounds after 3 warm-up rounds, the median per launch with the least and the greatest.  Needs an MI355X.
 
     python tools/bench_vertex_color.py [--out profiles/5_30_vertex_color.txt]
+
+--parent_lib PATH names another build of the library (the parent commit's, the same C ABI): its shading passes are timed in the same
+rounds, and each is reported as this build's median over the parent's with the parent's own spread (max - min) / median.
 """
 import argparse
+import ctypes
 import os
 import sys
 
@@ -71,15 +75,22 @@ def bench_shading(args, dev, lines):
         screen, normals = ops.render_vertices(verts, faces, off, ids, view, 1.0 / np.tan(r.fov / 2.0), size, size, tc, rot)
         rgba, _, fid = ops.render_raster(screen, normals, faces, shade, lights, size, size, near, far, 0xffffffff, want_face_id=True, samples=S)
         p = lambda t: t.data_ptr()
-        tex = lambda: lib.msmd_render_shade_textured_ms(p(screen), p(normals), p(faces), p(vt), p(ft), p(pyramid), N, N, p(shade), p(lights),
-                                                        lights.shape[0], p(fid), p(rgba), B, V, faces.shape[0], V, size, size, near,
-                                                        0xffffffff, S, st)
-        col = lambda table, per_frame, lit: (lambda: lib.msmd_render_shade_vertex_color(
+        tex = lambda L: (lambda: L.msmd_render_shade_textured_ms(p(screen), p(normals), p(faces), p(vt), p(ft), p(pyramid), N, N, p(shade),
+                                                                 p(lights), lights.shape[0], p(fid), p(rgba), B, V, faces.shape[0], V, size,
+                                                                 size, near, 0xffffffff, S, st))
+        col = lambda L, table, per_frame, lit: (lambda: L.msmd_render_shade_vertex_color(
             p(screen), p(normals), p(faces), p(table), per_frame, lit, p(shade), p(lights), lights.shape[0], p(fid), p(rgba), B, V,
             faces.shape[0], size, size, near, 0xffffffff, S, st))
-        fns = [tex, col(shared[0], 0, 1), col(shared[0], 0, 0), col(shared, 1, 1), col(shared, 1, 0)]
+        passes = lambda L: [tex(L), col(L, shared[0], 0, 1), col(L, shared[0], 0, 0), col(L, shared, 1, 1), col(L, shared, 1, 0)]
+        fns = passes(lib)
         names = [f"msmd_render_shade_textured{'_ms' if S == 4 else ''} ({N} x {N} texture)", "vertex colours, shared table, lit",
                  "vertex colours, shared table, unlit", "vertex colours, per-frame tables, lit", "vertex colours, per-frame tables, unlit"]
+        if args.parent_lib:
+            parent = ctypes.CDLL(args.parent_lib)
+            for name in ("msmd_render_shade_textured_ms", "msmd_render_shade_vertex_color"):
+                getattr(parent, name).argtypes, getattr(parent, name).restype = _lib.PROTOS[name], ctypes.c_int
+            fns += passes(parent)
+            names += [f"parent build's {name}" for name in names]
         assert all(fn() == 0 for fn in fns)
         res = timed_in_turn(fns, args.launches)
         cov = float((fid >= 0).float().mean())
@@ -88,6 +99,10 @@ def bench_shading(args, dev, lines):
         report(lines, names, res)
         lines.append(f"  vertex colours (shared, lit) / textured: {res[1][0] / res[0][0]:.3f}; unlit / lit: {res[2][0] / res[1][0]:.3f}; "
                      f"per-frame / shared (lit): {res[3][0] / res[1][0]:.3f}")
+        for k in range(5 if args.parent_lib else 0):
+            mine, theirs = res[k], res[5 + k]
+            lines.append(f"  {names[k]}: this build / the parent's {mine[0] / theirs[0]:.4f} (the parent's spread over its rounds "
+                         f"{(theirs[2] - theirs[1]) / theirs[0]:.4f})")
 
 
 def bench_colours(args, dev, lines):
@@ -127,6 +142,7 @@ def main():
     ap.add_argument("--n", type=int, default=512)
     ap.add_argument("--launches", type=int, default=20, help="launches of one kernel between two events")
     ap.add_argument("--out", type=str, default=None)
+    ap.add_argument("--parent_lib", type=str, default=None, help="another build of the library whose shading passes are timed in turn")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs an MI355X"
     dev = torch.device("cuda:0")

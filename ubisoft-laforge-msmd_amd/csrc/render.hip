@@ -2,8 +2,10 @@
 // An Instinct card has no graphics pipe; this turns the (B, V, 3) vertices msmd_lbs_skin_v2 leaves on the device into images
 // there.  Two launches per batch of frames, no host synchronisation, no global atomics, bit-identical from run to run.
 // A texture adds a mip pyramid (built once per image) and a third, deferred launch that shades the covered pixels from it
-// (DESIGN.md 5.14).  The raster and the textured kernel are templates on the samples per pixel: one, or four for anti-aliased
-// frames.  Per-vertex colours are a second deferred pass of the textured pass's shape, lit or unlit.
+// (DESIGN.md 5.14); per-vertex colours, lit or unlit, are that deferred launch with another shader.  The raster
+// and the deferred kernel are templates on the samples per pixel: one, or four for anti-aliased frames.
+// What the passes must agree on bit for bit is written once: the face's set-up with its edge steps and biases,
+// the barycentrics at a point, the lighting, the colour's bytes and the per-pixel resolve; a pass adds its shader.
 #include "common.h"
 
 namespace {
@@ -103,18 +105,6 @@ template <int S> struct Rt {
   __device__ static constexpr int sy(int k) { return S == 1 ? 128 : 32 + 64 * k; }
 };
 
-// A face as the coverage and the shading passes see it, from ONE routine, so both compute the same bits.
-// Coordinates are snapped to 8 sub-pixel bits (round half even).  With |X|, |Y| < 2^30 a difference is below 2^31, a product
-// below 2^62 and an edge function (a difference of two products) below 2^63: exact in int64 for any image size.
-struct FaceSetup {
-  int x0, y0, x1, y1, x2, y2;   // oriented so that the doubled area is positive (vertices 1 and 2 swapped if it was not)
-  int i0, i1, i2;               // vertex ids in that order
-  float q0, q1, q2;             // 1 / eye depth
-  long area;                    // e0 + e1 + e2 at any point
-  int jmin, jmax, imin, imax;   // pixel box inside the tile and the image (empty if min > max)
-  bool ok;
-};
-
 __device__ __forceinline__ long edge_fn(int ax, int ay, int bx, int by, long px, long py) {
   return (long)(bx - ax) * (py - ay) - (long)(by - ay) * (px - ax);
 }
@@ -123,6 +113,29 @@ __device__ __forceinline__ long edge_bias(int ax, int ay, int bx, int by) {
   const int dx = bx - ax, dy = by - ay;
   return (dy > 0 || (dy == 0 && dx > 0)) ? 0L : -1L;
 }
+
+// A face as the coverage and the shading passes see it, from ONE routine, so both compute the same bits.
+// Coordinates are snapped to 8 sub-pixel bits (round half even).  With |X|, |Y| < 2^30 a difference is below 2^31, a product
+// below 2^62 and an edge function (a difference of two products) below 2^63: exact in int64 for any image size.
+struct EdgeSteps { long a0, a1, a2, c0, c1, c2; };
+struct EdgeBias { long b0, b1, b2; };
+struct FaceSetup {
+  int x0, y0, x1, y1, x2, y2;   // oriented so that the doubled area is positive (vertices 1 and 2 swapped if it was not)
+  int i0, i1, i2;               // vertex ids in that order
+  float q0, q1, q2;             // 1 / eye depth
+  long area;                    // e0 + e1 + e2 at any point
+  int jmin, jmax, imin, imax;   // pixel box inside the given bounds (empty if min > max)
+  bool ok;
+  // what one pixel to the right (a_k) and one pixel down (c_k) add to edge function k, the one opposite vertex k:
+  // d e / d j = -256 (by - ay), d e / d i = 256 (bx - ax), exact integers.  The coverage walk steps by them and the level of
+  // detail differentiates the barycentrics with them.
+  __device__ __forceinline__ EdgeSteps steps() const {
+    return EdgeSteps{-256L * (y2 - y1), -256L * (y0 - y2), -256L * (y1 - y0), 256L * (x2 - x1), 256L * (x0 - x2), 256L * (x1 - x0)};
+  }
+  __device__ __forceinline__ EdgeBias biases() const {
+    return EdgeBias{edge_bias(x1, y1, x2, y2), edge_bias(x2, y2, x0, y0), edge_bias(x0, y0, x1, y1)};
+  }
+};
 
 template <int S>
 __device__ __forceinline__ FaceSetup face_setup(const int* __restrict__ faces, const float* __restrict__ scr, int f, int V,
@@ -180,10 +193,21 @@ __device__ __forceinline__ float inv_depth(const FaceSetup& s, long e0, long e1,
   return fmaf(w2, s.q2, fmaf(w1, s.q1, __fmul_rn(w0, s.q0)));
 }
 
+// The barycentrics of face `s` at the point whose edge values are e0, e1, e2, as every shader takes them: the screen-space
+// weights w_k, iz = 1 / depth and the perspective-correct weights p_k = w_k q_k / iz.  (Coverage needs the depth alone: inv_depth.)
+struct Bary { float w0, w1, w2, iz, p0, p1, p2; };
+__device__ __forceinline__ Bary barycentrics(const FaceSetup& s, long e0, long e1, long e2) {
+  Bary b;
+  b.iz = inv_depth(s, e0, e1, e2, b.w0, b.w1, b.w2);
+  b.p0 = b.w0 * s.q0 / b.iz; b.p1 = b.w1 * s.q1 / b.iz; b.p2 = b.w2 * s.q2 / b.iz;
+  return b;
+}
+
 // (1 / pi) sum_k I_k max(0, n . l_k) with n the perspective-correct interpolated vertex normal, renormalised: the lighting of
-// the untextured and the textured pass, from ONE routine
-__device__ __forceinline__ float lambert_diffuse(const float* __restrict__ nrm, const FaceSetup& s, float p0, float p1, float p2,
+// every pass
+__device__ __forceinline__ float lambert_diffuse(const float* __restrict__ nrm, const FaceSetup& s, const Bary& b,
                                                  const float* __restrict__ lights, int n_lights) {
+  const float p0 = b.p0, p1 = b.p1, p2 = b.p2;
   const F3 n0 = *(const F3*)(nrm + (long)s.i0 * 3), n1 = *(const F3*)(nrm + (long)s.i1 * 3), n2 = *(const F3*)(nrm + (long)s.i2 * 3);
   const F3 n = unit_or_z(F3{p0 * n0.x + p1 * n1.x + p2 * n2.x, p0 * n0.y + p1 * n1.y + p2 * n2.y, p0 * n0.z + p1 * n1.z + p2 * n2.z});
   float diff = 0.f;
@@ -195,9 +219,9 @@ __device__ __forceinline__ float lambert_diffuse(const float* __restrict__ nrm, 
 }
 
 template <int S>
-__device__ __forceinline__ void fragment(const FaceSetup& s, int f, int j, int i, int k, long e0, long e1, long e2, long b0, long b1,
-                                         long b2, float near, float far, int tx0, int ty0, unsigned long long* s_key) {
-  if ((e0 + b0) < 0 || (e1 + b1) < 0 || (e2 + b2) < 0) return;
+__device__ __forceinline__ void fragment(const FaceSetup& s, int f, int j, int i, int k, long e0, long e1, long e2, const EdgeBias& bias,
+                                         float near, float far, int tx0, int ty0, unsigned long long* s_key) {
+  if ((e0 + bias.b0) < 0 || (e1 + bias.b1) < 0 || (e2 + bias.b2) < 0) return;
   float w0, w1, w2;
   const float d = 1.f / inv_depth(s, e0, e1, e2, w0, w1, w2);
   if (!(d >= near && d <= far)) return;
@@ -207,30 +231,39 @@ __device__ __forceinline__ void fragment(const FaceSetup& s, int f, int j, int i
 
 // every sample of pixel (j, i) from the edge values at its sample 0
 template <int S>
-__device__ __forceinline__ void fragments(const FaceSetup& s, int f, int j, int i, long e0, long e1, long e2, long b0, long b1, long b2,
+__device__ __forceinline__ void fragments(const FaceSetup& s, int f, int j, int i, long e0, long e1, long e2, const EdgeBias& bias,
                                           float near, float far, int tx0, int ty0, unsigned long long* s_key) {
-  fragment<S>(s, f, j, i, 0, e0, e1, e2, b0, b1, b2, near, far, tx0, ty0, s_key);
+  fragment<S>(s, f, j, i, 0, e0, e1, e2, bias, near, far, tx0, ty0, s_key);
 #pragma unroll
   for (int k = 1; k < S; ++k)
     fragment<S>(s, f, j, i, k, e0 + sample_step<S>(s.x1, s.y1, s.x2, s.y2, k), e1 + sample_step<S>(s.x2, s.y2, s.x0, s.y0, k),
-                e2 + sample_step<S>(s.x0, s.y0, s.x1, s.y1, k), b0, b1, b2, near, far, tx0, ty0, s_key);
+                e2 + sample_step<S>(s.x0, s.y0, s.x1, s.y1, k), bias, near, far, tx0, ty0, s_key);
 }
 
-// the untextured colour of face `s` at the point whose edge values are e0, e1, e2: R | G << 8 | B << 16 | 255 << 24
-__device__ __forceinline__ unsigned shade_flat(const FaceSetup& s, const float* __restrict__ nrm, long e0, long e1, long e2,
-                                               const float* __restrict__ lights, int n_lights, float base_r, float base_g,
-                                               float base_b, float amb_r, float amb_g, float amb_b) {
-  float w0, w1, w2;
-  const float iz = inv_depth(s, e0, e1, e2, w0, w1, w2);
-  // perspective-correct weights w_k q_k / (sum), then the interpolated normal
-  const float p0 = w0 * s.q0 / iz, p1 = w1 * s.q1 / iz, p2 = w2 * s.q2 / iz;
-  const float diff = lambert_diffuse(nrm, s, p0, p1, p2, lights, n_lights);
-  const float cr = fminf(fmaxf(base_r * (amb_r + diff), 0.f), 1.f), cg = fminf(fmaxf(base_g * (amb_g + diff), 0.f), 1.f),
-              cb = fminf(fmaxf(base_b * (amb_b + diff), 0.f), 1.f);
-  const unsigned ur = (unsigned)floorf(255.f * cr + 0.5f), ug = (unsigned)floorf(255.f * cg + 0.5f),
-                 ub = (unsigned)floorf(255.f * cb + 0.5f);
-  return ur | (ug << 8) | (ub << 16) | 0xff000000u;
+// The bytes of a colour, R | G << 8 | B << 16 | 255 << 24: clamp(albedo (ambient + diffuse), 0, 1) per channel under the lighting,
+// clamp(albedo, 0, 1) unlit, then floor(255 c + 0.5).  The albedo is the base colour, a texel / 255 or a vertex colour / 255;
+// diffuse() is called for the diffuse term under the lighting only.
+template <class Diffuse>
+__device__ __forceinline__ unsigned color_bytes(F3 c, bool lit, const F3 amb, Diffuse diffuse) {
+  if (lit) {
+    const float diff = diffuse();
+    c.x *= amb.x + diff; c.y *= amb.y + diff; c.z *= amb.z + diff;
+  }
+  const auto byte = [](float x) { return (unsigned)floorf(255.f * fminf(fmaxf(x, 0.f), 1.f) + 0.5f); };
+  return byte(c.x) | (byte(c.y) << 8) | (byte(c.z) << 16) | 0xff000000u;
 }
+
+// A shader is called with a face's set-up, its id and the barycentrics at a point and returns the colour word there; `sampled` is
+// what it looked up on the way, (u, v, lambda) for the textured one, and is left alone by the others.
+// The untextured one: the base colour under the lighting.
+struct FlatShade {
+  const float* nrm; const float* lights;
+  int n_lights;
+  F3 base, amb;
+  __device__ __forceinline__ unsigned operator()(const FaceSetup& s, int, const Bary& b, F3&) const {
+    return color_bytes(base, true, amb, [&] { return lambert_diffuse(nrm, s, b, lights, n_lights); });
+  }
+};
 
 // The resolve of four RGBA words, (b0 + b1 + b2 + b3 + 2) >> 2 in every byte: the even and the odd bytes are summed in 16-bit
 // lanes (a sum is at most 4 * 255 + 2), which start at the rounding term.
@@ -239,6 +272,42 @@ struct Resolve4 {
   __device__ __forceinline__ void add(unsigned c) { even += c & 0x00ff00ffu; odd += (c >> 8) & 0x00ff00ffu; }
   __device__ __forceinline__ unsigned word() const { return ((even >> 2) & 0x00ff00ffu) | (((odd >> 2) & 0x00ff00ffu) << 8); }
 };
+
+// Pixel (j, i) from the face ids of its S samples: a sample with 0 <= id < F whose face the set-up accepts is shaded at its own
+// position, any other counts as `bg`; `word` is the one colour at one sample and the mean of the four (Resolve4) at four.
+// -> whether a sample was shaded.  (bx0, by0, bx1, by1) go to the set-up, the tile in the raster pass and the image in a deferred
+// one: they bound its pixel box and decide `ok`; nothing else of them reaches the colour.  Own: the ids are this launch's own
+// coverage (stage (C)), -1 or a face whose set-up was accepted in these bounds, so neither is tested again.
+template <int S, bool Own, class Shade>
+__device__ __forceinline__ bool resolve_pixel(const Shade& shade, const int (&ids)[S], const int* __restrict__ faces,
+                                              const float* __restrict__ scr, int V, int F, float near, int bx0, int by0, int bx1,
+                                              int by1, int j, int i, unsigned bg, unsigned& word, F3& sampled) {
+  Resolve4 sum;
+  bool any = false;
+  int last = -1;                    // the set-up is kept while consecutive samples show the same face
+  FaceSetup s;
+  s.ok = false;
+#pragma unroll
+  for (int k = 0; k < S; ++k) {
+    const int g = ids[k];
+    unsigned c = bg;
+    const bool valid = Own ? g >= 0 : (unsigned)g < (unsigned)F;
+    if (valid && g != last) {
+      s = face_setup<S>(faces, scr, g, V, near, bx0, by0, bx1, by1);
+      last = g;
+    }
+    if (valid && (Own || s.ok)) {
+      long e0, e1, e2;
+      edges_at<S>(s, j, i, k, e0, e1, e2);
+      c = shade(s, g, barycentrics(s, e0, e1, e2), sampled);
+      any = true;
+    }
+    sum.add(c);
+    word = c;
+  }
+  if (S == 4) word = sum.word();
+  return any;
+}
 
 // One workgroup per (frame, tile): 64 x 64 pixels at one sample per pixel, 32 x 32 at four, 4096 keys either way.  (A) the
 // frame's faces are streamed 256 at a time and those whose snapped box meets the tile are compacted, in face order, into an
@@ -303,19 +372,17 @@ __global__ __launch_bounds__(RT_THREADS) void render_raster_kernel(const float* 
         s_big[atomicAdd(&s_nbig, 1)] = g;       // the order of this queue does not reach the result (min of keys)
         continue;
       }
-      const long b0 = edge_bias(s.x1, s.y1, s.x2, s.y2), b1 = edge_bias(s.x2, s.y2, s.x0, s.y0), b2 = edge_bias(s.x0, s.y0, s.x1, s.y1);
+      const EdgeBias bias = s.biases();
+      const EdgeSteps d = s.steps();
       long r0, r1, r2;
       edges_at<S>(s, s.jmin, s.imin, 0, r0, r1, r2);
-      // d e / d j = -256 (by - ay), d e / d i = 256 (bx - ax): exact integer steps
-      const long a0 = -256L * (s.y2 - s.y1), a1 = -256L * (s.y0 - s.y2), a2 = -256L * (s.y1 - s.y0);
-      const long c0 = 256L * (s.x2 - s.x1), c1 = 256L * (s.x0 - s.x2), c2 = 256L * (s.x1 - s.x0);
       for (int i = s.imin; i <= s.imax; ++i) {
         long e0 = r0, e1 = r1, e2 = r2;
         for (int j = s.jmin; j <= s.jmax; ++j) {
-          fragments<S>(s, g, j, i, e0, e1, e2, b0, b1, b2, near, far, tx0, ty0, s_key);
-          e0 += a0; e1 += a1; e2 += a2;
+          fragments<S>(s, g, j, i, e0, e1, e2, bias, near, far, tx0, ty0, s_key);
+          e0 += d.a0; e1 += d.a1; e2 += d.a2;
         }
-        r0 += c0; r1 += c1; r2 += c2;
+        r0 += d.c0; r1 += d.c1; r2 += d.c2;
       }
     }
     __syncthreads();
@@ -323,13 +390,13 @@ __global__ __launch_bounds__(RT_THREADS) void render_raster_kernel(const float* 
     for (int e = wid; e < nbig; e += RT_THREADS / 64) {
       const int g = s_big[e];
       const FaceSetup s = face_setup<S>(faces, scr, g, V, near, tx0, ty0, tx1, ty1);
-      const long b0 = edge_bias(s.x1, s.y1, s.x2, s.y2), b1 = edge_bias(s.x2, s.y2, s.x0, s.y0), b2 = edge_bias(s.x0, s.y0, s.x1, s.y1);
+      const EdgeBias bias = s.biases();
       const int bw = s.jmax - s.jmin + 1, n = bw * (s.imax - s.imin + 1);
       for (int p = lane; p < n; p += 64) {
         const int i = s.imin + p / bw, j = s.jmin + p % bw;
         long e0, e1, e2;
         edges_at<S>(s, j, i, 0, e0, e1, e2);
-        fragments<S>(s, g, j, i, e0, e1, e2, b0, b1, b2, near, far, tx0, ty0, s_key);
+        fragments<S>(s, g, j, i, e0, e1, e2, bias, near, far, tx0, ty0, s_key);
       }
     }
     __syncthreads();     // before the lists are refilled
@@ -340,56 +407,30 @@ __global__ __launch_bounds__(RT_THREADS) void render_raster_kernel(const float* 
 
   // (C) resolve and shade: a wave stores row segments of the tile's width (256 contiguous bytes of RGBA at one sample per
   // pixel, two of 128 at four) per step
-  const float base_r = shade[0], base_g = shade[1], base_b = shade[2], amb_r = shade[3], amb_g = shade[4], amb_b = shade[5];
+  const FlatShade flat{nrm, lights, n_lights, F3{shade[0], shade[1], shade[2]}, F3{shade[3], shade[4], shade[5]}};
   for (int p = tid; p < TILE * TILE; p += RT_THREADS) {
     const int i = ty0 + p / TILE, j = tx0 + p % TILE;
     if (i > ty1 || j > tx1) continue;
     const long o = ((long)b * H + i) * W + j;
-    if constexpr (S == 1) {
-      const unsigned long long key = s_key[p];
-      if (key == RT_EMPTY) {
-        rgba[o] = bg;
-        depth[o] = 0.f;
-        if (face_id != nullptr) face_id[o] = -1;
-        continue;
-      }
-      const int g = (int)(unsigned)(key & 0xffffffffull);
-      const FaceSetup s = face_setup<S>(faces, scr, g, V, near, tx0, ty0, tx1, ty1);
-      long e0, e1, e2;
-      edges_at<S>(s, j, i, 0, e0, e1, e2);
-      rgba[o] = shade_flat(s, nrm, e0, e1, e2, lights, n_lights, base_r, base_g, base_b, amb_r, amb_g, amb_b);
-      depth[o] = __uint_as_float((unsigned)(key >> 32));
-      if (face_id != nullptr) face_id[o] = g;
-    } else {
-      Resolve4 sum;
-      unsigned dmin = 0xffffffffu;      // depths are positive, so their bits order as they do
-      int ids[S];
-      float ds[S];
-      int last = -1;                    // the set-up is kept while consecutive samples show the same face
-      FaceSetup s;
+    unsigned dmin = 0xffffffffu;      // depths are positive, so their bits order as they do
+    int ids[S];
+    float ds[S];
 #pragma unroll
-      for (int k = 0; k < S; ++k) {
-        const unsigned long long key = s_key[p * S + k];
-        unsigned c = bg;
-        ids[k] = -1;
-        ds[k] = 0.f;
-        if (key != RT_EMPTY) {
-          const int g = (int)(unsigned)(key & 0xffffffffull);
-          if (g != last) {
-            s = face_setup<S>(faces, scr, g, V, near, tx0, ty0, tx1, ty1);
-            last = g;
-          }
-          long e0, e1, e2;
-          edges_at<S>(s, j, i, k, e0, e1, e2);
-          c = shade_flat(s, nrm, e0, e1, e2, lights, n_lights, base_r, base_g, base_b, amb_r, amb_g, amb_b);
-          ids[k] = g;
-          ds[k] = __uint_as_float((unsigned)(key >> 32));
-          dmin = min(dmin, (unsigned)(key >> 32));
-        }
-        sum.add(c);
-      }
-      rgba[o] = sum.word();
-      depth[o] = dmin == 0xffffffffu ? 0.f : __uint_as_float(dmin);
+    for (int k = 0; k < S; ++k) {
+      const unsigned long long key = s_key[p * S + k];
+      const bool covered = key != RT_EMPTY;
+      ids[k] = covered ? (int)(unsigned)(key & 0xffffffffull) : -1;
+      ds[k] = covered ? __uint_as_float((unsigned)(key >> 32)) : 0.f;
+      if (covered) dmin = min(dmin, (unsigned)(key >> 32));
+    }
+    unsigned word;
+    F3 unused;
+    resolve_pixel<S, true>(flat, ids, faces, scr, V, F, near, tx0, ty0, tx1, ty1, j, i, bg, word, unused);
+    rgba[o] = word;
+    depth[o] = dmin == 0xffffffffu ? 0.f : __uint_as_float(dmin);
+    if constexpr (S == 1) {
+      if (face_id != nullptr) face_id[o] = ids[0];
+    } else {
       if (face_id != nullptr) *(int4*)(face_id + o * 4) = make_int4(ids[0], ids[1], ids[2], ids[3]);
       if (sample_depth != nullptr) *(float4*)(sample_depth + o * 4) = make_float4(ds[0], ds[1], ds[2], ds[3]);
     }
@@ -443,230 +484,128 @@ __device__ __forceinline__ F3 texture_bilinear(const float4* __restrict__ lvl, i
             gy * (gx * t00.z + fx * t10.z) + fy * (gx * t01.z + fx * t11.z)};
 }
 
-// The textured colour of face g (set-up `s`) at the point whose edge values are e0, e1, e2: R | G << 8 | B << 16 | 255 << 24, and
-// (u, v, lambda) as sampled.  The level table lvl_off / lvl_w / lvl_h holds the offset, width and height of every level.
-struct TexturedArgs {
-  const float* nrm; const int* faces; const float* vt; const int* ft; const float4* pyramid; const float* lights;
+// The textured shader: the trilinearly sampled texel / 255 under the lighting, and (u, v, lambda) as sampled.  The launcher fills
+// the first two rows; prepare(), once per workgroup, moves nrm to frame b, loads the ambient colour and builds the level table
+// lvl_off / lvl_w / lvl_h (the offset, width and height of every level) in LDS.
+struct TexturedShade {
+  const float* nrm; const int* faces; const float* vt; const int* ft; const float4* pyramid; const float* shade; const float* lights;
+  int n_lights, Nt, Ht, Wt, L;
   const int *lvl_off, *lvl_w, *lvl_h;
-  int n_lights, Nt, L;
-  float amb_r, amb_g, amb_b, Wtf, Htf, top;
+  F3 amb;
+  float Wtf, Htf, top;
+  __device__ __forceinline__ void prepare(int b, int V) {
+    __shared__ int s_off[TX_MAX_LEVELS], s_w[TX_MAX_LEVELS], s_h[TX_MAX_LEVELS];
+    const int tid = threadIdx.x;
+    if (tid < L) {
+      int off = 0, w = Wt, h = Ht;
+      for (int l = 0; l < tid; ++l) {
+        off += w * h;
+        w = max(1, w >> 1);
+        h = max(1, h >> 1);
+      }
+      s_off[tid] = off; s_w[tid] = w; s_h[tid] = h;
+    }
+    __syncthreads();
+    nrm += (long)b * V * 3;
+    lvl_off = s_off; lvl_w = s_w; lvl_h = s_h;
+    amb = F3{shade[3], shade[4], shade[5]};
+    Wtf = (float)Wt; Htf = (float)Ht; top = (float)(L - 1);
+  }
+  __device__ __forceinline__ unsigned operator()(const FaceSetup& s, int g, const Bary& b, F3& uvl) const {
+    const float iz = b.iz, p0 = b.p0, p1 = b.p1, p2 = b.p2;
+    // per-corner texture coordinates in the face's oriented order: face_setup swapped corners 1 and 2 iff it swapped the ids
+    const I3 ti = *(const I3*)(ft + (long)g * 3);
+    const bool swapped = s.i1 != faces[(long)g * 3 + 1];
+    const int k0 = ti.a, k1 = swapped ? ti.c : ti.b, k2 = swapped ? ti.b : ti.c;
+    float2 t0 = make_float2(0.f, 0.f), t1 = t0, t2 = t0;
+    if ((unsigned)k0 < (unsigned)Nt) t0 = *(const float2*)(vt + (long)k0 * 2);
+    if ((unsigned)k1 < (unsigned)Nt) t1 = *(const float2*)(vt + (long)k1 * 2);
+    if ((unsigned)k2 < (unsigned)Nt) t2 = *(const float2*)(vt + (long)k2 * 2);
+    const float u = (p0 * t0.x + p1 * t1.x) + p2 * t2.x, v = (p0 * t0.y + p1 * t1.y) + p2 * t2.y;
+    // analytic level of detail: d w_k / d j = a_k / A, d w_k / d i = c_k / A with the set-up's integer edge steps
+    const float A = (float)s.area;
+    const EdgeSteps d = s.steps();
+    const float g0 = s.q0 * ((float)d.a0 / A), g1 = s.q1 * ((float)d.a1 / A), g2 = s.q2 * ((float)d.a2 / A);
+    const float h0 = s.q0 * ((float)d.c0 / A), h1 = s.q1 * ((float)d.c1 / A), h2 = s.q2 * ((float)d.c2 / A);
+    const float dDj = (g0 + g1) + g2, dDi = (h0 + h1) + h2;
+    const float duj = (((g0 * t0.x + g1 * t1.x) + g2 * t2.x) - u * dDj) / iz, dvj = (((g0 * t0.y + g1 * t1.y) + g2 * t2.y) - v * dDj) / iz;
+    const float dui = (((h0 * t0.x + h1 * t1.x) + h2 * t2.x) - u * dDi) / iz, dvi = (((h0 * t0.y + h1 * t1.y) + h2 * t2.y) - v * dDi) / iz;
+    const float rj2 = (Wtf * duj) * (Wtf * duj) + (Htf * dvj) * (Htf * dvj),
+                ri2 = (Wtf * dui) * (Wtf * dui) + (Htf * dvi) * (Htf * dvi);
+    float lam = 0.5f * log2f(fmaxf(rj2, ri2));
+    if (!(finite_f(rj2) && finite_f(ri2) && finite_f(lam))) lam = 0.f;
+    lam = fminf(fmaxf(lam, 0.f), top);
+    const float us = finite_f(u) ? u : 0.f, vs = finite_f(v) ? v : 0.f;
+    const float U = us - floorf(us), Vv = vs - floorf(vs);
+    const int l0 = min((int)floorf(lam), L - 1), l1 = min(l0 + 1, L - 1);
+    const float fl = lam - (float)l0;
+    const F3 c0 = texture_bilinear(pyramid + lvl_off[l0], lvl_w[l0], lvl_h[l0], U, Vv);
+    const F3 c1 = texture_bilinear(pyramid + lvl_off[l1], lvl_w[l1], lvl_h[l1], U, Vv);
+    const float gl = 1.f - fl;
+    const float Tr = gl * c0.x + fl * c1.x, Tg = gl * c0.y + fl * c1.y, Tb = gl * c0.z + fl * c1.z;
+    uvl = F3{us, vs, lam};
+    return color_bytes(F3{Tr / 255.f, Tg / 255.f, Tb / 255.f}, true, amb, [&] { return lambert_diffuse(nrm, s, b, lights, n_lights); });
+  }
 };
-__device__ __forceinline__ unsigned shade_textured(const FaceSetup& s, int g, long e0, long e1, long e2, const TexturedArgs& t, F3& uvl) {
-  float w0, w1, w2;
-  const float iz = inv_depth(s, e0, e1, e2, w0, w1, w2);
-  const float p0 = w0 * s.q0 / iz, p1 = w1 * s.q1 / iz, p2 = w2 * s.q2 / iz;
-  // per-corner texture coordinates in the face's oriented order: face_setup swapped corners 1 and 2 iff it swapped the ids
-  const I3 ti = *(const I3*)(t.ft + (long)g * 3);
-  const bool swapped = s.i1 != t.faces[(long)g * 3 + 1];
-  const int k0 = ti.a, k1 = swapped ? ti.c : ti.b, k2 = swapped ? ti.b : ti.c;
-  float2 t0 = make_float2(0.f, 0.f), t1 = t0, t2 = t0;
-  if ((unsigned)k0 < (unsigned)t.Nt) t0 = *(const float2*)(t.vt + (long)k0 * 2);
-  if ((unsigned)k1 < (unsigned)t.Nt) t1 = *(const float2*)(t.vt + (long)k1 * 2);
-  if ((unsigned)k2 < (unsigned)t.Nt) t2 = *(const float2*)(t.vt + (long)k2 * 2);
-  const float u = (p0 * t0.x + p1 * t1.x) + p2 * t2.x, v = (p0 * t0.y + p1 * t1.y) + p2 * t2.y;
-  // analytic level of detail: d w_k / d j = a_k / A, d w_k / d i = c_k / A with stage (B)'s integer edge steps
-  const float A = (float)s.area;
-  const float g0 = s.q0 * ((float)(-256L * (s.y2 - s.y1)) / A), g1 = s.q1 * ((float)(-256L * (s.y0 - s.y2)) / A),
-              g2 = s.q2 * ((float)(-256L * (s.y1 - s.y0)) / A);
-  const float h0 = s.q0 * ((float)(256L * (s.x2 - s.x1)) / A), h1 = s.q1 * ((float)(256L * (s.x0 - s.x2)) / A),
-              h2 = s.q2 * ((float)(256L * (s.x1 - s.x0)) / A);
-  const float dDj = (g0 + g1) + g2, dDi = (h0 + h1) + h2;
-  const float duj = (((g0 * t0.x + g1 * t1.x) + g2 * t2.x) - u * dDj) / iz, dvj = (((g0 * t0.y + g1 * t1.y) + g2 * t2.y) - v * dDj) / iz;
-  const float dui = (((h0 * t0.x + h1 * t1.x) + h2 * t2.x) - u * dDi) / iz, dvi = (((h0 * t0.y + h1 * t1.y) + h2 * t2.y) - v * dDi) / iz;
-  const float rj2 = (t.Wtf * duj) * (t.Wtf * duj) + (t.Htf * dvj) * (t.Htf * dvj),
-              ri2 = (t.Wtf * dui) * (t.Wtf * dui) + (t.Htf * dvi) * (t.Htf * dvi);
-  float lam = 0.5f * log2f(fmaxf(rj2, ri2));
-  if (!(finite_f(rj2) && finite_f(ri2) && finite_f(lam))) lam = 0.f;
-  lam = fminf(fmaxf(lam, 0.f), t.top);
-  const float us = finite_f(u) ? u : 0.f, vs = finite_f(v) ? v : 0.f;
-  const float U = us - floorf(us), Vv = vs - floorf(vs);
-  const int l0 = min((int)floorf(lam), t.L - 1), l1 = min(l0 + 1, t.L - 1);
-  const float fl = lam - (float)l0;
-  const F3 c0 = texture_bilinear(t.pyramid + t.lvl_off[l0], t.lvl_w[l0], t.lvl_h[l0], U, Vv);
-  const F3 c1 = texture_bilinear(t.pyramid + t.lvl_off[l1], t.lvl_w[l1], t.lvl_h[l1], U, Vv);
-  const float gl = 1.f - fl;
-  const float Tr = gl * c0.x + fl * c1.x, Tg = gl * c0.y + fl * c1.y, Tb = gl * c0.z + fl * c1.z;
-  const float diff = lambert_diffuse(t.nrm, s, p0, p1, p2, t.lights, t.n_lights);
-  const float cr = fminf(fmaxf((Tr / 255.f) * (t.amb_r + diff), 0.f), 1.f), cg = fminf(fmaxf((Tg / 255.f) * (t.amb_g + diff), 0.f), 1.f),
-              cb = fminf(fmaxf((Tb / 255.f) * (t.amb_b + diff), 0.f), 1.f);
-  const unsigned ur = (unsigned)floorf(255.f * cr + 0.5f), ug = (unsigned)floorf(255.f * cg + 0.5f),
-                 ub = (unsigned)floorf(255.f * cb + 0.5f);
-  uvl = F3{us, vs, lam};
-  return ur | (ug << 8) | (ub << 16) | 0xff000000u;
-}
-
-// One workgroup per (frame, 64 x 16 strip); pixel-parallel in stage (C)'s mapping, so a wave reads 64 contiguous face ids (at
-// four samples per pixel 64 contiguous int4) and stores 256 contiguous bytes of RGBA per step.  The face's set-up, the
-// barycentrics and the lighting are the routines of the raster pass; the level table is built once per workgroup in LDS.
-// At four samples face_id is (B, H, W, 4): every sample with 0 <= id < F is shaded at its own position, any other counts as
-// `bg`, and a pixel with a shaded sample receives the mean of the four (Resolve4); uvl is not offered.
-template <int S>
-__global__ __launch_bounds__(TX_THREADS) void render_shade_textured_kernel(
-    const float* __restrict__ screen, const float* __restrict__ normals, const int* __restrict__ faces, const float* __restrict__ vt,
-    const int* __restrict__ ft, const float4* __restrict__ pyramid, const float* __restrict__ shade, const float* __restrict__ lights,
-    int n_lights, const int* __restrict__ face_id, unsigned* __restrict__ rgba, float* __restrict__ uvl, int V, int F, int Nt,
-    int Ht, int Wt, int L, int H, int W, int tiles_x, int strips_y, float near, unsigned bg) {
-  __shared__ int s_off[TX_MAX_LEVELS], s_w[TX_MAX_LEVELS], s_h[TX_MAX_LEVELS];
-  const int tid = threadIdx.x;
-  if (tid < L) {
-    int off = 0, w = Wt, h = Ht;
-    for (int l = 0; l < tid; ++l) {
-      off += w * h;
-      w = max(1, w >> 1);
-      h = max(1, h >> 1);
-    }
-    s_off[tid] = off; s_w[tid] = w; s_h[tid] = h;
-  }
-  __syncthreads();
-  const int per_frame = tiles_x * strips_y;
-  const int b = blockIdx.x / per_frame, rest = blockIdx.x - b * per_frame;
-  const int sy = rest / tiles_x, tx = rest - sy * tiles_x;
-  const int tx0 = tx * RT_TILE, ty0 = sy * TX_ROWS;
-  const float* scr = screen + (long)b * V * 3;
-  TexturedArgs t;
-  t.nrm = normals + (long)b * V * 3; t.faces = faces; t.vt = vt; t.ft = ft; t.pyramid = pyramid; t.lights = lights;
-  t.lvl_off = s_off; t.lvl_w = s_w; t.lvl_h = s_h;
-  t.n_lights = n_lights; t.Nt = Nt; t.L = L;
-  t.amb_r = shade[3]; t.amb_g = shade[4]; t.amb_b = shade[5];
-  t.Wtf = (float)Wt; t.Htf = (float)Ht; t.top = (float)(L - 1);
-  for (int p = tid; p < RT_TILE * TX_ROWS; p += TX_THREADS) {
-    const int i = ty0 + p / RT_TILE, j = tx0 + p % RT_TILE;
-    if (i >= H || j >= W) continue;
-    const long o = ((long)b * H + i) * W + j;
-    if constexpr (S == 1) {
-      const int g = face_id[o];
-      FaceSetup s;
-      s.ok = false;
-      if ((unsigned)g < (unsigned)F) s = face_setup<S>(faces, scr, g, V, near, 0, 0, W - 1, H - 1);
-      if (!s.ok) {                      // background, or a face id the raster pass cannot have written
-        if (uvl != nullptr) *(F3*)(uvl + o * 3) = F3{0.f, 0.f, 0.f};
-        continue;
-      }
-      long e0, e1, e2;
-      edges_at<S>(s, j, i, 0, e0, e1, e2);
-      F3 sampled;
-      rgba[o] = shade_textured(s, g, e0, e1, e2, t, sampled);
-      if (uvl != nullptr) *(F3*)(uvl + o * 3) = sampled;
-    } else {
-      const int4 id4 = *(const int4*)(face_id + o * 4);
-      const int ids[4] = {id4.x, id4.y, id4.z, id4.w};
-      Resolve4 sum;
-      bool any = false;
-      int last = -1;                    // the set-up is kept while consecutive samples show the same face
-      FaceSetup s;
-      s.ok = false;
-#pragma unroll
-      for (int k = 0; k < S; ++k) {
-        const int g = ids[k];
-        unsigned c = bg;
-        if ((unsigned)g < (unsigned)F) {
-          if (g != last) {
-            s = face_setup<S>(faces, scr, g, V, near, 0, 0, W - 1, H - 1);
-            last = g;
-          }
-          if (s.ok) {
-            long e0, e1, e2;
-            edges_at<S>(s, j, i, k, e0, e1, e2);
-            F3 sampled;
-            c = shade_textured(s, g, e0, e1, e2, t, sampled);
-            any = true;
-          }
-        }
-        sum.add(c);
-      }
-      if (any) rgba[o] = sum.word();
-    }
-  }
-}
 
 // ------------------------------------------------------------------------------------------------ vertex colours
-// The colour of face `s` at the point whose edge values are e0, e1, e2 from the RGBA bytes at its three vertices (alpha not read):
-// per channel C = (p0 c0 + p1 c1) + p2 c2 with the perspective-correct weights of the textured pass, the corners in the order
-// face_setup left them in (s.i0, s.i1, s.i2: the face and its colours swap together); then clamp((C / 255)(ambient + diffuse), 0, 1)
-// under the raster pass's lighting, or clamp(C / 255, 0, 1) unlit; floor(255 c + 0.5), alpha 255.
-struct VertexColorArgs {
-  const float* nrm; const unsigned* vcol; const float* lights;
-  int n_lights, lit;
-  float amb_r, amb_g, amb_b;
-};
-__device__ __forceinline__ unsigned shade_vertex_color(const FaceSetup& s, long e0, long e1, long e2, const VertexColorArgs& t) {
-  float w0, w1, w2;
-  const float iz = inv_depth(s, e0, e1, e2, w0, w1, w2);
-  const float p0 = w0 * s.q0 / iz, p1 = w1 * s.q1 / iz, p2 = w2 * s.q2 / iz;
-  const unsigned c0 = t.vcol[s.i0], c1 = t.vcol[s.i1], c2 = t.vcol[s.i2];
-  const float Cr = (p0 * (float)(c0 & 255u) + p1 * (float)(c1 & 255u)) + p2 * (float)(c2 & 255u);
-  const float Cg = (p0 * (float)((c0 >> 8) & 255u) + p1 * (float)((c1 >> 8) & 255u)) + p2 * (float)((c2 >> 8) & 255u);
-  const float Cb = (p0 * (float)((c0 >> 16) & 255u) + p1 * (float)((c1 >> 16) & 255u)) + p2 * (float)((c2 >> 16) & 255u);
-  float cr = Cr / 255.f, cg = Cg / 255.f, cb = Cb / 255.f;
-  if (t.lit) {
-    const float diff = lambert_diffuse(t.nrm, s, p0, p1, p2, t.lights, t.n_lights);
-    cr *= t.amb_r + diff; cg *= t.amb_g + diff; cb *= t.amb_b + diff;
+// The vertex-colour shader: from the RGBA bytes at the face's three vertices (alpha not read), per channel C = (p0 c0 + p1 c1) +
+// p2 c2 with the perspective-correct weights, the corners in the order face_setup left them in (s.i0, s.i1, s.i2: the face and its
+// colours swap together); then C / 255 under the lighting, or as it is unlit.  The three gathers per shaded point are 4-byte loads
+// from a (V, 4) table that stays in L2.  The launcher fills the first two rows; prepare() moves nrm and vcol to frame b
+// (col_stride = 0: the one shared table) and loads the ambient colour.
+struct VertexColorShade {
+  const float* nrm; const unsigned* vcol; const float* shade; const float* lights;
+  long col_stride; int n_lights, lit;
+  F3 amb;
+  __device__ __forceinline__ void prepare(int b, int V) {
+    nrm += (long)b * V * 3;
+    vcol += (long)b * col_stride;
+    amb = F3{shade[3], shade[4], shade[5]};
   }
-  cr = fminf(fmaxf(cr, 0.f), 1.f); cg = fminf(fmaxf(cg, 0.f), 1.f); cb = fminf(fmaxf(cb, 0.f), 1.f);
-  const unsigned ur = (unsigned)floorf(255.f * cr + 0.5f), ug = (unsigned)floorf(255.f * cg + 0.5f),
-                 ub = (unsigned)floorf(255.f * cb + 0.5f);
-  return ur | (ug << 8) | (ub << 16) | 0xff000000u;
-}
+  __device__ __forceinline__ unsigned operator()(const FaceSetup& s, int, const Bary& b, F3&) const {
+    const float p0 = b.p0, p1 = b.p1, p2 = b.p2;
+    const unsigned c0 = vcol[s.i0], c1 = vcol[s.i1], c2 = vcol[s.i2];
+    const float Cr = (p0 * (float)(c0 & 255u) + p1 * (float)(c1 & 255u)) + p2 * (float)(c2 & 255u);
+    const float Cg = (p0 * (float)((c0 >> 8) & 255u) + p1 * (float)((c1 >> 8) & 255u)) + p2 * (float)((c2 >> 8) & 255u);
+    const float Cb = (p0 * (float)((c0 >> 16) & 255u) + p1 * (float)((c1 >> 16) & 255u)) + p2 * (float)((c2 >> 16) & 255u);
+    return color_bytes(F3{Cr / 255.f, Cg / 255.f, Cb / 255.f}, lit, amb, [&] { return lambert_diffuse(nrm, s, b, lights, n_lights); });
+  }
+};
 
-// The textured pass's launch shape and mapping: one workgroup per (frame, 64 x 16 strip), pixel-parallel, a wave reads 64 contiguous
-// face ids (int4 at four samples) and stores 256 contiguous bytes per step; the three colour gathers per shaded point are 4-byte
-// loads from a (V, 4) table that stays in L2.  vcol is the frame's table, or the one shared table (col_stride = 0).
-template <int S>
-__global__ __launch_bounds__(TX_THREADS) void render_shade_vertex_color_kernel(
-    const float* __restrict__ screen, const float* __restrict__ normals, const int* __restrict__ faces, const unsigned* __restrict__ vcol,
-    long col_stride, int lit, const float* __restrict__ shade, const float* __restrict__ lights, int n_lights,
-    const int* __restrict__ face_id, unsigned* __restrict__ rgba, int V, int F, int H, int W, int tiles_x, int strips_y, float near,
-    unsigned bg) {
-  const int tid = threadIdx.x;
+// ------------------------------------------------------------------------------------------------ the deferred pass
+// One workgroup per (frame, 64 x 16 strip); pixel-parallel in stage (C)'s mapping, so a wave reads 64 contiguous face ids (at
+// four samples per pixel, where face_id is (B, H, W, 4), 64 contiguous int4) and stores 256 contiguous bytes of RGBA per step.
+// A pixel is resolved as the raster pass resolves it (resolve_pixel) with the pass's shader in place of the untextured one, and
+// stored only if a sample was shaded: the others keep what the raster pass wrote.  uvl, one sample per pixel only, receives what the
+// shader sampled, zeros at a pixel without a shaded sample.
+template <int S, class Shade>
+__global__ __launch_bounds__(TX_THREADS) void render_shade_kernel(Shade shade, const float* __restrict__ screen,
+                                                                  const int* __restrict__ faces, const int* __restrict__ face_id,
+                                                                  unsigned* __restrict__ rgba, float* __restrict__ uvl, int V, int F,
+                                                                  int H, int W, int tiles_x, int strips_y, float near, unsigned bg) {
   const int per_frame = tiles_x * strips_y;
   const int b = blockIdx.x / per_frame, rest = blockIdx.x - b * per_frame;
   const int sy = rest / tiles_x, tx = rest - sy * tiles_x;
   const int tx0 = tx * RT_TILE, ty0 = sy * TX_ROWS;
   const float* scr = screen + (long)b * V * 3;
-  VertexColorArgs t;
-  t.nrm = normals + (long)b * V * 3; t.vcol = vcol + (long)b * col_stride; t.lights = lights;
-  t.n_lights = n_lights; t.lit = lit;
-  t.amb_r = shade[3]; t.amb_g = shade[4]; t.amb_b = shade[5];
-  for (int p = tid; p < RT_TILE * TX_ROWS; p += TX_THREADS) {
+  shade.prepare(b, V);
+  for (int p = threadIdx.x; p < RT_TILE * TX_ROWS; p += TX_THREADS) {
     const int i = ty0 + p / RT_TILE, j = tx0 + p % RT_TILE;
     if (i >= H || j >= W) continue;
     const long o = ((long)b * H + i) * W + j;
+    int ids[S];
     if constexpr (S == 1) {
-      const int g = face_id[o];
-      if ((unsigned)g >= (unsigned)F) continue;          // background, or a face id the raster pass cannot have written
-      const FaceSetup s = face_setup<S>(faces, scr, g, V, near, 0, 0, W - 1, H - 1);
-      if (!s.ok) continue;
-      long e0, e1, e2;
-      edges_at<S>(s, j, i, 0, e0, e1, e2);
-      rgba[o] = shade_vertex_color(s, e0, e1, e2, t);
+      ids[0] = face_id[o];
     } else {
       const int4 id4 = *(const int4*)(face_id + o * 4);
-      const int ids[4] = {id4.x, id4.y, id4.z, id4.w};
-      Resolve4 sum;
-      bool any = false;
-      int last = -1;                    // the set-up is kept while consecutive samples show the same face
-      FaceSetup s;
-      s.ok = false;
-#pragma unroll
-      for (int k = 0; k < S; ++k) {
-        const int g = ids[k];
-        unsigned c = bg;
-        if ((unsigned)g < (unsigned)F) {
-          if (g != last) {
-            s = face_setup<S>(faces, scr, g, V, near, 0, 0, W - 1, H - 1);
-            last = g;
-          }
-          if (s.ok) {
-            long e0, e1, e2;
-            edges_at<S>(s, j, i, k, e0, e1, e2);
-            c = shade_vertex_color(s, e0, e1, e2, t);
-            any = true;
-          }
-        }
-        sum.add(c);
-      }
-      if (any) rgba[o] = sum.word();
+      ids[0] = id4.x; ids[1] = id4.y; ids[2] = id4.z; ids[3] = id4.w;
     }
+    unsigned word;
+    F3 sampled{0.f, 0.f, 0.f};
+    const bool any = resolve_pixel<S, false>(shade, ids, faces, scr, V, F, near, 0, 0, W - 1, H - 1, j, i, bg, word, sampled);
+    if (S == 1 && uvl != nullptr) *(F3*)(uvl + o * 3) = sampled;
+    if (any) rgba[o] = word;
   }
 }
 
@@ -699,23 +638,31 @@ extern "C" int msmd_texture_mips(const void* img, int Ht, int Wt, int channels, 
 }
 
 namespace {
-template <int S>
-int launch_shade_textured(const float* screen, const float* normals, const int* faces, const float* vt, const int* ft,
-                          const float* pyramid, int Ht, int Wt, const float* shade, const float* lights, int n_lights,
-                          const int* face_id, void* rgba, float* uvl, int B, int V, int F, int Nt, int H, int W, float near,
-                          unsigned background, msmd_stream_t stream) {
-  if (B <= 0 || V <= 0 || F <= 0 || Nt <= 0 || H <= 0 || W <= 0 || n_lights < 0 || !(near > 0.f) || face_id == nullptr ||
-      msmd_texture_texels(Ht, Wt) < 0) return 1;
-  if (S == 4 && ((size_t)face_id & 15) != 0) return 1;      // read as int4
-  int L = 1;
-  for (int m = Ht > Wt ? Ht : Wt; m > 1; m >>= 1) ++L;
+// The launch of a deferred pass with its shader: what every such pass checks, the sample count, the 64 x 16 strip grid.
+template <class Shade>
+int launch_shade(const Shade& shade, const float* screen, const int* faces, const int* face_id, void* rgba, float* uvl, int B, int V,
+                 int F, int H, int W, float near, unsigned background, int samples, msmd_stream_t stream) {
+  if (B <= 0 || V <= 0 || F <= 0 || H <= 0 || W <= 0 || shade.n_lights < 0 || !(near > 0.f) || face_id == nullptr) return 1;
+  if (samples != 1 && samples != 4) return 1;
+  if (samples == 4 && ((size_t)face_id & 15) != 0) return 1;      // read as int4
   const int tiles_x = (W + RT_TILE - 1) / RT_TILE, strips_y = (H + TX_ROWS - 1) / TX_ROWS;
   const long grid = (long)B * tiles_x * strips_y;
   if (grid > 2147483647L) return 1;
-  hipLaunchKernelGGL(render_shade_textured_kernel<S>, dim3((unsigned)grid), dim3(TX_THREADS), 0, (hipStream_t)stream, screen, normals,
-                     faces, vt, ft, (const float4*)pyramid, shade, lights, n_lights, face_id, (unsigned*)rgba, uvl, V, F, Nt, Ht, Wt, L,
-                     H, W, tiles_x, strips_y, near, background);
+  const auto kernel = samples == 4 ? render_shade_kernel<4, Shade> : render_shade_kernel<1, Shade>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(TX_THREADS), 0, (hipStream_t)stream, shade, screen, faces, face_id,
+                     (unsigned*)rgba, uvl, V, F, H, W, tiles_x, strips_y, near, background);
   MSMD_RETURN_LAST();
+}
+
+int shade_textured(const float* screen, const float* normals, const int* faces, const float* vt, const int* ft, const float* pyramid,
+                   int Ht, int Wt, const float* shade, const float* lights, int n_lights, const int* face_id, void* rgba, float* uvl,
+                   int B, int V, int F, int Nt, int H, int W, float near, unsigned background, int samples, msmd_stream_t stream) {
+  if (Nt <= 0 || msmd_texture_texels(Ht, Wt) < 0) return 1;
+  TexturedShade t{};
+  t.nrm = normals; t.faces = faces; t.vt = vt; t.ft = ft; t.pyramid = (const float4*)pyramid; t.shade = shade; t.lights = lights;
+  t.n_lights = n_lights; t.Nt = Nt; t.Ht = Ht; t.Wt = Wt; t.L = 1;
+  for (int m = Ht > Wt ? Ht : Wt; m > 1; m >>= 1) ++t.L;
+  return launch_shade(t, screen, faces, face_id, rgba, uvl, B, V, F, H, W, near, background, samples, stream);
 }
 }  // namespace
 
@@ -723,8 +670,8 @@ extern "C" int msmd_render_shade_textured(const float* screen, const float* norm
                                           const float* pyramid, int Ht, int Wt, const float* shade, const float* lights,
                                           int n_lights, const int* face_id, void* rgba, float* uvl, int B, int V, int F, int Nt,
                                           int H, int W, float near, msmd_stream_t stream) {
-  return launch_shade_textured<1>(screen, normals, faces, vt, ft, pyramid, Ht, Wt, shade, lights, n_lights, face_id, rgba, uvl, B, V, F,
-                                  Nt, H, W, near, 0u, stream);
+  return shade_textured(screen, normals, faces, vt, ft, pyramid, Ht, Wt, shade, lights, n_lights, face_id, rgba, uvl, B, V, F, Nt, H, W,
+                        near, 0u, 1, stream);
 }
 
 extern "C" int msmd_render_shade_textured_ms(const float* screen, const float* normals, const int* faces, const float* vt,
@@ -732,42 +679,19 @@ extern "C" int msmd_render_shade_textured_ms(const float* screen, const float* n
                                              const float* lights, int n_lights, const int* sample_face_id, void* rgba, int B, int V,
                                              int F, int Nt, int H, int W, float near, unsigned background, int samples,
                                              msmd_stream_t stream) {
-  if (samples == 1)
-    return launch_shade_textured<1>(screen, normals, faces, vt, ft, pyramid, Ht, Wt, shade, lights, n_lights, sample_face_id, rgba,
-                                    nullptr, B, V, F, Nt, H, W, near, background, stream);
-  if (samples != 4) return 1;
-  return launch_shade_textured<4>(screen, normals, faces, vt, ft, pyramid, Ht, Wt, shade, lights, n_lights, sample_face_id, rgba,
-                                  nullptr, B, V, F, Nt, H, W, near, background, stream);
+  return shade_textured(screen, normals, faces, vt, ft, pyramid, Ht, Wt, shade, lights, n_lights, sample_face_id, rgba, nullptr, B, V,
+                        F, Nt, H, W, near, background, samples, stream);
 }
-
-namespace {
-template <int S>
-int launch_shade_vertex_color(const float* screen, const float* normals, const int* faces, const unsigned char* vcol, int color_per_frame,
-                              int lit, const float* shade, const float* lights, int n_lights, const int* face_id, void* rgba, int B,
-                              int V, int F, int H, int W, float near, unsigned background, msmd_stream_t stream) {
-  if (B <= 0 || V <= 0 || F <= 0 || H <= 0 || W <= 0 || n_lights < 0 || !(near > 0.f) || face_id == nullptr || vcol == nullptr ||
-      ((size_t)vcol & 3) != 0) return 1;                    // a vertex's four bytes are read as one word
-  if (S == 4 && ((size_t)face_id & 15) != 0) return 1;      // read as int4
-  const int tiles_x = (W + RT_TILE - 1) / RT_TILE, strips_y = (H + TX_ROWS - 1) / TX_ROWS;
-  const long grid = (long)B * tiles_x * strips_y;
-  if (grid > 2147483647L) return 1;
-  hipLaunchKernelGGL(render_shade_vertex_color_kernel<S>, dim3((unsigned)grid), dim3(TX_THREADS), 0, (hipStream_t)stream, screen,
-                     normals, faces, (const unsigned*)vcol, color_per_frame ? (long)V : 0L, lit != 0, shade, lights, n_lights, face_id,
-                     (unsigned*)rgba, V, F, H, W, tiles_x, strips_y, near, background);
-  MSMD_RETURN_LAST();
-}
-}  // namespace
 
 extern "C" int msmd_render_shade_vertex_color(const float* screen, const float* normals, const int* faces, const unsigned char* vcol,
                                               int color_per_frame, int lit, const float* shade, const float* lights, int n_lights,
                                               const int* sample_face_id, void* rgba, int B, int V, int F, int H, int W, float near,
                                               unsigned background, int samples, msmd_stream_t stream) {
-  if (samples == 1)
-    return launch_shade_vertex_color<1>(screen, normals, faces, vcol, color_per_frame, lit, shade, lights, n_lights, sample_face_id, rgba,
-                                        B, V, F, H, W, near, background, stream);
-  if (samples != 4) return 1;
-  return launch_shade_vertex_color<4>(screen, normals, faces, vcol, color_per_frame, lit, shade, lights, n_lights, sample_face_id, rgba,
-                                      B, V, F, H, W, near, background, stream);
+  if (vcol == nullptr || ((size_t)vcol & 3) != 0) return 1;      // a vertex's four bytes are read as one word
+  VertexColorShade t{};
+  t.nrm = normals; t.vcol = (const unsigned*)vcol; t.shade = shade; t.lights = lights;
+  t.col_stride = color_per_frame ? (long)V : 0L; t.n_lights = n_lights; t.lit = lit != 0;
+  return launch_shade(t, screen, faces, sample_face_id, rgba, nullptr, B, V, F, H, W, near, background, samples, stream);
 }
 
 extern "C" int msmd_render_vertices(const float* verts, const int* faces, const int* csr_offsets, const int* csr_faces,
@@ -782,18 +706,21 @@ extern "C" int msmd_render_vertices(const float* verts, const int* faces, const 
 }
 
 namespace {
-template <int S>
+// sample_depth is stored by the kernel at four samples only (as float4, and face_id as int4)
 int launch_raster(const float* screen, const float* normals, const int* faces, const float* shade, const float* lights, int n_lights,
                   void* rgba, float* depth, int* face_id, float* sample_depth, int B, int V, int F, int H, int W, float near, float far,
-                  unsigned background, msmd_stream_t stream) {
+                  unsigned background, int samples, msmd_stream_t stream) {
   if (B <= 0 || V <= 0 || F <= 0 || H <= 0 || W <= 0 || n_lights < 0 || !(near > 0.f) || !(far >= near)) return 1;
-  if (S == 4 && ((((size_t)face_id) | ((size_t)sample_depth)) & 15) != 0) return 1;      // stored as int4 / float4
-  const int tiles_x = (W + Rt<S>::tile - 1) / Rt<S>::tile, tiles_y = (H + Rt<S>::tile - 1) / Rt<S>::tile;
+  if (samples != 1 && samples != 4) return 1;
+  if (samples == 4 && ((((size_t)face_id) | ((size_t)sample_depth)) & 15) != 0) return 1;
+  const int tile = samples == 4 ? RT_TILE_MS : RT_TILE;
+  const int tiles_x = (W + tile - 1) / tile, tiles_y = (H + tile - 1) / tile;
   const long grid = (long)B * tiles_x * tiles_y;
   if (grid > 2147483647L) return 1;
-  hipLaunchKernelGGL(render_raster_kernel<S>, dim3((unsigned)grid), dim3(RT_THREADS), 0, (hipStream_t)stream, screen, normals, faces,
-                     shade, lights, n_lights, (unsigned*)rgba, depth, face_id, sample_depth, V, F, H, W, tiles_x, tiles_y, near, far,
-                     background);
+  const auto kernel = samples == 4 ? render_raster_kernel<4> : render_raster_kernel<1>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(RT_THREADS), 0, (hipStream_t)stream, screen, normals, faces, shade, lights,
+                     n_lights, (unsigned*)rgba, depth, face_id, samples == 4 ? sample_depth : nullptr, V, F, H, W, tiles_x, tiles_y, near,
+                     far, background);
   MSMD_RETURN_LAST();
 }
 }  // namespace
@@ -801,21 +728,17 @@ int launch_raster(const float* screen, const float* normals, const int* faces, c
 extern "C" int msmd_render_raster(const float* screen, const float* normals, const int* faces, const float* shade,
                                   const float* lights, int n_lights, void* rgba, float* depth, int* face_id, int B, int V,
                                   int F, int H, int W, float near, float far, unsigned background, msmd_stream_t stream) {
-  return launch_raster<1>(screen, normals, faces, shade, lights, n_lights, rgba, depth, face_id, nullptr, B, V, F, H, W, near, far,
-                          background, stream);
+  return launch_raster(screen, normals, faces, shade, lights, n_lights, rgba, depth, face_id, nullptr, B, V, F, H, W, near, far,
+                       background, 1, stream);
 }
 
 extern "C" int msmd_render_raster_ms(const float* screen, const float* normals, const int* faces, const float* shade,
                                      const float* lights, int n_lights, void* rgba, float* depth, int* sample_face_id,
                                      float* sample_depth, int B, int V, int F, int H, int W, float near, float far,
                                      unsigned background, int samples, msmd_stream_t stream) {
-  if (samples != 1 && samples != 4) return 1;
-  if (samples == 4)
-    return launch_raster<4>(screen, normals, faces, shade, lights, n_lights, rgba, depth, sample_face_id, sample_depth, B, V, F, H, W,
-                            near, far, background, stream);
-  const int rc = msmd_render_raster(screen, normals, faces, shade, lights, n_lights, rgba, depth, sample_face_id, B, V, F, H, W, near,
-                                    far, background, stream);
-  if (rc != 0 || sample_depth == nullptr) return rc;
+  const int rc = launch_raster(screen, normals, faces, shade, lights, n_lights, rgba, depth, sample_face_id, sample_depth, B, V, F, H, W,
+                               near, far, background, samples, stream);
+  if (rc != 0 || samples != 1 || sample_depth == nullptr) return rc;
   // one sample per pixel: the sample's depth is the pixel's
   return (int)hipMemcpyAsync(sample_depth, depth, (size_t)B * H * W * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream);
 }

@@ -1536,15 +1536,13 @@ def render_raster(screen, normals, faces_i32, shade, lights, height, width, near
     rgba = torch.empty(B, H, W, 4, device=screen.device, dtype=torch.uint8)
     depth = torch.empty(B, H, W, device=screen.device, dtype=torch.float32)
     face_id = torch.empty(per_sample, device=screen.device, dtype=torch.int32) if want_face_id else None
+    head = (_p(screen), _p(normals), _p(faces_i32), _p(shade), _p(lights), lights.shape[0], _p(rgba), _p(depth), _p(face_id))
+    tail = (B, V, faces_i32.shape[0], H, W, float(near), float(far), int(background) & 0xffffffff)
     if samples == 1 and not want_sample_depth:
-        _lib.check(lib.msmd_render_raster(_p(screen), _p(normals), _p(faces_i32), _p(shade), _p(lights), lights.shape[0], _p(rgba),
-                                          _p(depth), _p(face_id), B, V, faces_i32.shape[0], H, W, float(near), float(far),
-                                          int(background) & 0xffffffff, _stream()), "msmd_render_raster")
+        _lib.check(lib.msmd_render_raster(*head, *tail, _stream()), "msmd_render_raster")
         return rgba, depth, face_id
     sample_depth = torch.empty(per_sample, device=screen.device, dtype=torch.float32) if want_sample_depth else None
-    _lib.check(lib.msmd_render_raster_ms(_p(screen), _p(normals), _p(faces_i32), _p(shade), _p(lights), lights.shape[0], _p(rgba),
-                                         _p(depth), _p(face_id), _p(sample_depth), B, V, faces_i32.shape[0], H, W, float(near),
-                                         float(far), int(background) & 0xffffffff, int(samples), _stream()), "msmd_render_raster_ms")
+    _lib.check(lib.msmd_render_raster_ms(*head, _p(sample_depth), *tail, int(samples), _stream()), "msmd_render_raster_ms")
     return (rgba, depth, face_id, sample_depth) if want_sample_depth else (rgba, depth, face_id)
 
 
@@ -1565,6 +1563,23 @@ def texture_pyramid(img_u8):
     return pyramid
 
 
+def _deferred_pass_args(screen, normals, faces_i32, shade, lights, face_id, rgba, samples, background):
+    """What the deferred passes refuse and check alike -> the sizes their tensors bind (B, V, F, L, H, W)."""
+    if samples not in RENDER_SAMPLES:
+        raise ValueError(f"samples must be one of {RENDER_SAMPLES}, got {samples!r}")
+    if samples != 1 and background is None:
+        raise ValueError("samples=4 needs the background the raster pass was given: its uncovered samples take part in the resolve")
+    d = {}
+    _arg("screen", screen, torch.float32, "B V 3", d)
+    _arg("normals", normals, torch.float32, "B V 3", d)
+    _arg("faces", faces_i32, torch.int32, "F 3", d)
+    _arg("shade", shade, torch.float32, "6")
+    _arg("lights", lights, torch.float32, "L 4", d)
+    _arg("face_id", face_id, torch.int32, "B H W" if samples == 1 else f"B H W {samples}", d)
+    _arg("rgba", rgba, torch.uint8, "B H W 4", d)
+    return d
+
+
 def render_shade_textured(screen, normals, faces_i32, vt, ft, pyramid, tex_height, tex_width, shade, lights, face_id, rgba, near,
                           want_uvl=False, samples=1, background=None):
     """Overwrites rgba (B, H, W, 4) uint8 at the pixels face_id (B, H, W) int32 marks as covered with the mip-mapped,
@@ -1576,22 +1591,11 @@ def render_shade_textured(screen, normals, faces_i32, vt, ft, pyramid, tex_heigh
     covered sample is shaded at its own position and every pixel with a covered sample receives the resolve of its four, an
     uncovered sample counting as `background` (R | G << 8 | B << 16 | A << 24, the one render_raster was given: required).
     There is no uvl at four samples: want_uvl is a ValueError."""
-    if samples not in RENDER_SAMPLES:
-        raise ValueError(f"samples must be one of {RENDER_SAMPLES}, got {samples!r}")
+    d = _deferred_pass_args(screen, normals, faces_i32, shade, lights, face_id, rgba, samples, background)
     if samples != 1 and want_uvl:
         raise ValueError("(u, v, level of detail) is per pixel: it is not offered at four samples per pixel")
-    if samples != 1 and background is None:
-        raise ValueError("samples=4 needs the background the raster pass was given: its uncovered samples take part in the resolve")
-    d = {}
-    _arg("screen", screen, torch.float32, "B V 3", d)
-    _arg("normals", normals, torch.float32, "B V 3", d)
-    _arg("faces", faces_i32, torch.int32, "F 3", d)
     _arg("vt", vt, torch.float32, "Nt+ 2", d)
     _arg("ft", ft, torch.int32, "F 3", d)
-    _arg("shade", shade, torch.float32, "6")
-    _arg("lights", lights, torch.float32, "L 4", d)
-    _arg("face_id", face_id, torch.int32, "B H W" if samples == 1 else f"B H W {samples}", d)
-    _arg("rgba", rgba, torch.uint8, "B H W 4", d)
     B, V, Fc, H, W = (d[k] for k in "BVFHW")
     lib = _lib.load()
     Ht, Wt = int(tex_height), int(tex_width)
@@ -1620,20 +1624,9 @@ def render_shade_vertex_color(screen, normals, faces_i32, vcol, shade, lights, f
     multiplies the colour by render_raster's lighting as a texel is; lit=False stores the interpolated colour itself.  samples = 4:
     face_id is (B, H, W, 4), every covered sample is shaded at its own position and `background` (the one render_raster was
     given: required) stands for the uncovered samples of a pixel that has a covered one."""
-    if samples not in RENDER_SAMPLES:
-        raise ValueError(f"samples must be one of {RENDER_SAMPLES}, got {samples!r}")
-    if samples != 1 and background is None:
-        raise ValueError("samples=4 needs the background the raster pass was given: its uncovered samples take part in the resolve")
-    d = {}
-    _arg("screen", screen, torch.float32, "B V 3", d)
-    _arg("normals", normals, torch.float32, "B V 3", d)
-    _arg("faces", faces_i32, torch.int32, "F 3", d)
+    d = _deferred_pass_args(screen, normals, faces_i32, shade, lights, face_id, rgba, samples, background)
     per_frame = torch.is_tensor(vcol) and vcol.dim() == 3
     _arg("vcol", vcol, torch.uint8, "B V 4" if per_frame else "V 4", d)
-    _arg("shade", shade, torch.float32, "6")
-    _arg("lights", lights, torch.float32, "L 4", d)
-    _arg("face_id", face_id, torch.int32, "B H W" if samples == 1 else f"B H W {samples}", d)
-    _arg("rgba", rgba, torch.uint8, "B H W 4", d)
     B, V, Fc, H, W = (d[k] for k in "BVFHW")
     _lib.check(_lib.load().msmd_render_shade_vertex_color(_p(screen), _p(normals), _p(faces_i32), _p(vcol), int(per_frame), int(bool(lit)),
                                                           _p(shade), _p(lights), lights.shape[0], _p(face_id), _p(rgba), B, V, Fc, H, W,
